@@ -11,8 +11,10 @@ RCCL so that track ids stay globally consistent.
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   "roofline"     the steady-state K1 pre-process kernel against the HBM roofline (2,764,800 algorithmic B/frame: the
                  source rows it reads + the 360 content rows it writes; the first launch into a buffer also writes the
-                 constant letterbox border: 3,840,000 B/frame, reported beside it as "full_tensor_kernel"),
-  "cpu_baseline" the CPU oracle (oracle/, kind "port") + torch-CPU fp32 network on a bounded sample.
+                 constant letterbox border: 3,840,000 B/frame, reported beside it as "full_tensor_kernel" with --full),
+  "cpu_baseline" (--full) the CPU oracle (oracle/, kind "port") + torch-CPU fp32 network on a bounded sample.
+A plain run sets up, warms up, times --steps ticks and prints the line; --full adds every measurement taken after the timed
+region (see its help); --dump-outputs DIR writes the last timed tick's results as .npy files.
 Decode is NOT part of the step: librocdecode and an H.265 source are absent (reported as such).
 """
 from __future__ import annotations
@@ -64,12 +66,20 @@ def parse():
     ap.add_argument("--conf", type=float, default=0.25)
     ap.add_argument("--iou", type=float, default=0.45)
     ap.add_argument("--target-dets", type=int, default=120, help="calibrated candidates per frame (synthetic weights)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also take every further measurement of the record: the per-stage eager pass "
+                         "(stages_ms of the network / K2+K3 / K4, detector_tflops), long_run, power_clock, the cold K1 and 4K / clip "
+                         "rooflines, the device copy rate, the load sweeps, paced_30fps, decode, other_configs (child runs) and "
+                         "cpu_baseline.  Without it a run sets up, warms up, times --steps ticks and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed tick handed its caller (the track tables and the detections of every stream "
+                         "of rank 0) to DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the measurements taken after the timed region (cold K1 launch, device copy bandwidth, "
+                    help="with --full: skip the measurements taken after the timed region (cold K1 launch, device copy bandwidth, "
                          "post-process / tracker load sweep)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the two child runs (4 x YOLOv8m, 4 x YOLOv8n) that the default headline run appends to its record")
+                    help="with --full: skip the child runs (4 x YOLOv8m, 4 x YOLOv8n, temporal) that the headline run appends to its record")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU-baseline sample (0 = auto)")
     ap.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark = True")
     ap.add_argument("--no-graph", action="store_true",
@@ -164,6 +174,8 @@ def spawn_ranks(args) -> int:
 
 def main():
     args = parse()
+    if args.dump_outputs and args.workload == "temporal":
+        raise SystemExit("bench.py --dump-outputs: implemented for the detect workload (the headline), not --workload temporal")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args))
     from realtime_video_analytics_32streams_amd import dist as rdist
@@ -315,6 +327,7 @@ def main():
     torch.cuda.synchronize()
     rctx = ops.context(local)
     n_tracks = 0
+    last_tables = None
     dt = trk.device_tracker
 
     def enqueue(k):
@@ -326,8 +339,10 @@ def main():
         t_sub[k] = time.perf_counter() - t_enq[k]
 
     def finish(k):
+        nonlocal last_tables
         _, tables = runner.collect()
         lat[k] = time.perf_counter() - t_enq[k]
+        last_tables = tables
         return sum(t["n"] for t in tables)
 
     if id_sync is not None:
@@ -368,16 +383,21 @@ def main():
                                                      "slowest rank's tick), every 4th tick"},
                  "id_exchanges_per_rank": int(allr[0, 3])}
     dets_emitted = int(post.counts.sum().item())
+    if args.dump_outputs and rank == 0:     # before any later leg ticks the same tracker / post buffers again
+        dump_outputs(Path(args.dump_outputs), last_tables, post)
 
     k1_bracket_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))            # hipEventRecord before / after the launch
     k1_ms = float(np.mean([a.elapsed_time(b) for a, b in evk[::K1_SAMPLE_EVERY]]))   # the dispatch's own start / stop events
     if not (0.0 < k1_ms <= k1_bracket_ms * 1.05):                                    # events not written: fall back
         k1_ms = k1_bracket_ms
-    if use_graph:   # per-stage split of the captured part: eager passes AFTER the timed region (informational)
+    stage, stage_mode = None, None
+    if not use_graph:
+        stage = np.array([[e[i].elapsed_time(e[i + 1]) for i in range(1, 4)] for e in ev])
+        stage_mode = "timed region (no graph)"
+    elif args.full:   # per-stage split of the captured part: eager passes AFTER the timed region (informational)
         # one forward pass alone, with the detect branches on side streams and in line: how side streams map onto hardware
         # queues depends on which streams the process created before (a plan taken from the autotune cache never creates
         # the tuner's streams), so both layouts are timed and the faster one is reported with its name
-        stage, stage_mode = None, None
         for mode, serial in (("detect branches on side streams", "0"), ("detect branches in line", "1")):
             os.environ["RVA_SERIAL_HEADS"] = serial
             ev2 = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(20)]
@@ -390,10 +410,14 @@ def main():
             if stage is None or st.mean(0)[0] < stage.mean(0)[0]:
                 stage, stage_mode = st, mode
         os.environ.pop("RVA_SERIAL_HEADS", None)
-    else:
-        stage = np.array([[e[i].elapsed_time(e[i + 1]) for i in range(1, 4)] for e in ev])
-        stage_mode = "timed region (no graph)"
-    net_ms, post_ms, trk_ms = stage.mean(0)
+    stages_ms = {"k1_preprocess": round(float(k1_ms), 4)}
+    detector_alone = {}
+    if stage is not None:
+        net_ms, post_ms, trk_ms = stage.mean(0)
+        stages_ms.update(detector=round(float(net_ms), 4), k2k3_postprocess=round(float(post_ms), 4), k4_tracker=round(float(trk_ms), 4))
+        net_tflops = 2 * macs * S / (net_ms * 1e-3) / 1e12
+        detector_alone = {"detector_tflops": round(net_tflops, 2), "detector_frac_of_mfma_peak": round(net_tflops / MFMA_PEAK_TFLOPS, 4),
+                          "detector_alone_layout": stage_mode}
     frames = world * S * K
     fps = frames / elapsed
     k1_frame_bytes = k1_bytes(args.width, args.height)
@@ -405,7 +429,6 @@ def main():
     pmc = ROOT / "profiles" / "r04_k1_pmc.json"
     if pmc.exists() and S == 32 and (args.width, args.height) == (1920, 1080):
         k1_traffic = json.loads(pmc.read_text())["content_1080p"]["traffic_bytes_per_launch"]
-    net_tflops = 2 * macs * S / (net_ms * 1e-3) / 1e12
 
     if world > 1:
         workload = (f"{world * S}x{args.width}x{args.height} NV12 streams sharded {S} per GPU over {world} GPUs "
@@ -431,13 +454,11 @@ def main():
                                     "what": "wall time inside PipelinedTicks.submit() on the host thread (every launch of the tick enqueued)"},
         "chain_stream_probe": ops.chain_stream_report(dev),
         "ticks_in_flight": runner.depth, "network_streams": runner.net_streams, "warmup_ticks_run": warm_ticks, "hip_graph": bool(use_graph), "network_launch": net_launch, "hip_graph_scope": ("network + tail" if runner.replay_net else ("post-process / tracker tail (networks launched eagerly; a tick is one chain on its own stream, consecutive ticks rotate over %d streams)" % runner.net_streams if runner.net_streams >= 2 else "post-process / tracker tail (network launched eagerly: concurrent detect branches)")) if use_graph else None, "realtime_32x30fps": bool(fps / world >= 30.0 * S and np.percentile(lat, 99) < 1 / 30),
-        "stages_ms": {"k1_preprocess": round(float(k1_ms), 4), "detector": round(float(net_ms), 4),
-                      "k2k3_postprocess": round(float(post_ms), 4), "k4_tracker": round(float(trk_ms), 4)},
+        "stages_ms": stages_ms,
         "detections_per_frame": round(dets_emitted / S, 2), "tracks_per_stream": round(n_tracks / (K * S), 2),
-        "detector_tflops": round(net_tflops, 2), "detector_frac_of_mfma_peak": round(net_tflops / MFMA_PEAK_TFLOPS, 4),
-        "detector_alone_layout": stage_mode,
-        # one forward pass alone (the eager per-stage pass) above; below: the network FLOPs of a tick over the tick period of the
-        # timed region, where the forward passes of consecutive ticks overlap on two streams
+        **detector_alone,
+        # one forward pass alone (the eager per-stage pass, --full or --no-graph) above; below: the network FLOPs of a tick over the
+        # tick period of the timed region, where the forward passes of consecutive ticks overlap on two streams
         "detector_tflops_in_pipeline": round(2 * macs * S / (elapsed / K) / 1e12, 2),
         "detector_frac_of_mfma_peak_in_pipeline": round(2 * macs * S / (elapsed / K) / 1e12 / MFMA_PEAK_TFLOPS, 4),
         "roofline": {"kernel": "k1_ratio_content<3,half,2> (NV12 1080p -> content rows of fp16 3x640x640, one launch per tick; the "
@@ -460,7 +481,7 @@ def main():
     refined = getattr(det._plans.get((S, 640, 640)), "refined", None)
     if refined:     # what the second pass of the kernel selection (whole forward passes, three in flight) changed: layer, from, to, us before / after
         out["kernel_selection_refinements"] = [list(r) for r in refined]
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         try:
             if world == 1:
                 # what the metric names: a real percentile over >= 300 saturated ticks whatever --steps was --
@@ -486,13 +507,33 @@ def main():
             import traceback
             traceback.print_exc()
             out["extras_error"] = f"{type(exc).__name__}: {exc}"
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, net_cpu, shifts, sources, dcfg, tcfg)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(d: Path, tables, post):
+    """--dump-outputs: what the last timed tick handed its caller, one .npy per field.  ``tables``: the track tables of
+    ``PipelinedTicks.collect()`` (one per stream, in table order), concatenated over the streams with ``tracks_count``
+    giving each stream's rows; ``post``: the tick's K2/K3 result (kept detections in NMS order), concatenated the same way
+    with ``detections_count``.  Integers are written as float64 (exact), boxes and scores in the precision they have."""
+    d.mkdir(parents=True, exist_ok=True)
+    dets = post.to_host()
+    arrays = {"tracks_count": np.array([t["n"] for t in tables], np.float64)}
+    for f in ("id", "cls", "age", "hits", "last_det", "conf"):
+        arrays[f"tracks_{f}"] = np.concatenate([t[f] for t in tables]).astype(np.float64)
+    arrays["tracks_boxes"] = np.concatenate([t["boxes"] for t in tables]).astype(np.float64).reshape(-1, 4)
+    arrays["detections_count"] = np.array([r["n"] for r in dets], np.float64)
+    for f in ("cls", "anchor"):
+        arrays[f"detections_{f}"] = np.concatenate([r[f] for r in dets]).astype(np.float64)
+    arrays["detections_conf"] = np.concatenate([r["conf"] for r in dets]).astype(np.float32)
+    arrays["detections_boxes"] = np.concatenate([r["boxes"] for r in dets]).astype(np.float32).reshape(-1, 4)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def other_configs_leg(args):

@@ -13,7 +13,7 @@ import yaml
 
 from realtime_video_analytics_32streams_amd import config as C
 from realtime_video_analytics_32streams_amd.temporal import ClipSchedule
-from tests.conftest import load_golden
+from tests.conftest import GOLDEN, load_golden
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -273,13 +273,10 @@ def test_capture_loop_matches_reference_recording():
 
 
 def test_mp4_demuxer_on_the_reference_sample():
-    """MP4 -> Annex-B on the one real bitstream that exists offline (the reference's data/samples/demo.mp4; read in place,
-    never copied; absent on the GPU box -> skipped there).  Facts from SURVEY.md section 2 #23: H.264 High@L3.0, 640x360,
-    400 frames at 30000/1001 fps."""
+    """MP4 -> Annex-B on the one real bitstream that exists offline (the reference's data/samples/demo.mp4, stored as
+    tests/golden/demo.mp4).  Facts from SURVEY.md section 2 #23: H.264 High@L3.0, 640x360, 400 frames at 30000/1001 fps."""
     from realtime_video_analytics_32streams_amd import mp4
-    sample = Path("/root/reference/data/samples/demo.mp4")
-    if not sample.exists():
-        pytest.skip("reference sample not present on this machine")
+    sample = GOLDEN / "demo.mp4"
     with mp4.Mp4Demuxer(sample) as d:
         info = d.describe()
         assert (info["codec"], info["entry"], info["width"], info["height"], info["samples"]) == ("h264", "avc1", 640, 360, 400)
@@ -357,13 +354,11 @@ def test_rocdecode_stream_fails_like_an_unopenable_capture():
     if not rocdecode_status().startswith("available"):
         with pytest.raises(RuntimeError, match="Unable to open stream door: rocDecode unavailable"):
             asyncio.run(st.open())
-    sample = Path("/root/reference/data/samples/demo.mp4")
-    if sample.exists():
-        with mp4.Mp4Demuxer(sample) as d:
-            es = b"".join(au for au, _, _ in d.access_units())          # the file's elementary stream as one Annex-B blob
-            want = [au for au, _, _ in d.access_units()]
-        got = [au for au, _, _ in _annexb_access_units(es, N.RVA_CODEC_H264)]
-        assert len(got) == 400 and got == want                          # same access-unit boundaries as the container's samples
+    with mp4.Mp4Demuxer(GOLDEN / "demo.mp4") as d:
+        es = b"".join(au for au, _, _ in d.access_units())              # the file's elementary stream as one Annex-B blob
+        want = [au for au, _, _ in d.access_units()]
+    got = [au for au, _, _ in _annexb_access_units(es, N.RVA_CODEC_H264)]
+    assert len(got) == 400 and got == want                              # same access-unit boundaries as the container's samples
 
 
 def test_ultralytics_named_state_dict_loads(tmp_path):
@@ -403,19 +398,18 @@ def test_ultralytics_named_state_dict_loads(tmp_path):
         Y.load_detector_state_dict(Y.build_detector_net("n", seed=5), bad)
 
 
-REF_CONFIGS = Path("/root/reference/config")
-REF_TEMPORAL = Path("/root/reference/sample-temporal-pipeline.yaml")
+REF_CONFIGS = GOLDEN / "reference_config"                  # the reference's config/*.yaml, unchanged
+REF_TEMPORAL = GOLDEN / "sample-temporal-pipeline.yaml"    # the reference's sample-temporal-pipeline.yaml, unchanged
 
 
-@pytest.mark.skipif(not REF_CONFIGS.is_dir(), reason="the reference tree is not on this box (GPU box)")
 def test_reference_yaml_files_load_in_place():
-    """Every configuration file the reference ships (config/*.yaml, sample-temporal-pipeline.yaml) through ``load_config``, read
-    IN PLACE: each stream / detector / tracker field equals what the YAML says (known keys), defaults fill the rest, unknown
-    keys are dropped.  BASELINE configs[0] is config/pipeline-sim.yaml: its values are spelled out below
-    (/root/reference/config/pipeline-sim.yaml:6-30)."""
+    """Every configuration file the reference ships (config/*.yaml, sample-temporal-pipeline.yaml; stored unchanged under
+    tests/golden/) through ``load_config``: each stream / detector / tracker field equals what the YAML says (known keys),
+    defaults fill the rest, unknown keys are dropped.  BASELINE configs[0] is config/pipeline-sim.yaml: its values are spelled
+    out below (the reference's config/pipeline-sim.yaml:6-30)."""
     import dataclasses
-    files = sorted(REF_CONFIGS.glob("*.yaml")) + ([REF_TEMPORAL] if REF_TEMPORAL.is_file() else [])
-    assert len(files) >= 7
+    files = sorted(REF_CONFIGS.glob("*.yaml")) + [REF_TEMPORAL]
+    assert len(files) == 8
     for f in files:
         raw = yaml.safe_load(f.read_text())
         cfg = C.load_config(f)
@@ -442,14 +436,12 @@ def test_reference_yaml_files_load_in_place():
     assert (d.model_path, d.device, d.backend, d.confidence_threshold, d.iou_threshold, d.half, d.warmup) == \
         ("/app/models/yolo/yolov8n.pt", "cpu", "ultralytics", 0.35, 0.5, False, False)
     assert (sim.tracker.type, sim.tracker.max_age, sim.tracker.max_iou_distance, sim.tracker.min_hits) == ("byte_track", 30, 0.5, 1)
-    if REF_TEMPORAL.is_file():
-        t = C.load_config(REF_TEMPORAL)
-        cl = t.detectors["temporal_cnn_lstm"]
-        assert (cl.model_type, cl.sequence_length, cl.sequence_stride, cl.temporal_overlap, cl.half) == ("cnn_lstm", 16, 2, 0.5, False)
-        assert list(cl.input_size) == [224, 224] and cl.num_action_classes == 400
+    t = C.load_config(REF_TEMPORAL)
+    cl = t.detectors["temporal_cnn_lstm"]
+    assert (cl.model_type, cl.sequence_length, cl.sequence_stride, cl.temporal_overlap, cl.half) == ("cnn_lstm", 16, 2, 0.5, False)
+    assert list(cl.input_size) == [224, 224] and cl.num_action_classes == 400
 
 
-@pytest.mark.skipif(not REF_CONFIGS.is_dir(), reason="the reference tree is not on this box (GPU box)")
 def test_reference_config_routed_to_this_library_fails_with_the_documented_errors():
     """configs[0] as the reference ships it names the reference's own backend and a container path.  Routed to this library
     unchanged: ``backend: ultralytics`` -> the 'belongs to the reference implementation' RuntimeError of create_detector

@@ -11,7 +11,7 @@ grep -v amdgpu.ids $O/nosel2.txt
 RVA_TUNE_CACHE=0 timeout -k 10 300 python3 tools/show_tuning.py 32 s > $O/s32_conv_tuning.txt 2>&1; echo "s32 tuning rc=$?"; tail -3 $O/s32_conv_tuning.txt
 RVA_TUNE_CACHE=0 timeout -k 10 300 python3 tools/show_tuning.py 4 m > $O/m4_conv_tuning.txt 2>&1; echo "m4 tuning rc=$?"; tail -3 $O/m4_conv_tuning.txt
 for m in "s 32" "m 4"; do set -- $m
-timeout -k 10 300 python3 bench.py --model $1 --streams $2 --steps 400 --warmup 40 --no-cpu-baseline --no-extras > $O/bench_$1$2.log 2>&1; echo "bench $m rc=$?"; python3 -c "
+timeout -k 10 300 python3 bench.py --full --model $1 --streams $2 --steps 400 --warmup 40 --no-cpu-baseline --no-extras > $O/bench_$1$2.log 2>&1; echo "bench $m rc=$?"; python3 -c "
 import json,sys
 d=json.loads(open('$O/bench_$1$2.log').read().strip().splitlines()[-1]); print({k:d[k] for k in ('value','ms_per_step','p99_latency_ms','detector_frac_of_mfma_peak','detector_frac_of_mfma_peak_in_pipeline')})"
 done

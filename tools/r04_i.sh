@@ -9,7 +9,7 @@ d=json.loads(open('$1').read().strip().splitlines()[-1]); print('$1'.split('/')[
 for rep in 1 2; do
   for m in "s 32" "m 4"; do set -- $m
     for ov in 3 1 2; do
-    RVA_TUNE_CACHE=0 RVA_TUNE_LAYER_OVERLAP=$ov timeout -k 10 300 python3 bench.py --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/ov${ov}_$1$2_$rep.log 2>&1 || { echo FAIL; tail -5 $O/ov${ov}_$1$2_$rep.log; exit 1; }
+    RVA_TUNE_CACHE=0 RVA_TUNE_LAYER_OVERLAP=$ov timeout -k 10 300 python3 bench.py --full --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/ov${ov}_$1$2_$rep.log 2>&1 || { echo FAIL; tail -5 $O/ov${ov}_$1$2_$rep.log; exit 1; }
     show $O/ov${ov}_$1$2_$rep.log
     done
   done

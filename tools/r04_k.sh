@@ -3,7 +3,7 @@ ROOT=$PWD
 export TMPDIR=/tmp PYTHONPATH=$ROOT
 O=$ROOT/gpurun_out/r04k; rm -rf $O; mkdir -p $O
 t0=$(date +%s)
-timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2> $O/bench_driver.err; echo "driver-like bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -3 $O/bench_driver.err
+timeout -k 10 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.log 2> $O/bench_driver.err; echo "driver-like bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -3 $O/bench_driver.err
 python3 - <<PY
 import json
 d=json.loads(open('$O/bench_driver.log').read().strip().splitlines()[-1])

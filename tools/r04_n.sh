@@ -8,7 +8,7 @@ import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1]); r=d['roofline']; print('$1'.split('/')[-1], {k:d.get(k) for k in ('value','ms_per_step','p99_latency_ms')}, 'K1 us', r['avg_launch_us'], 'frac', r['frac'], 'cold', r.get('cold_launch_us'))"; }
 for rep in 1 2; do
   for cfg in "base" "RVA_K1_NT=1" "RVA_K1_NT=2" "RVA_K1_NT=3" "RVA_K1_PRIO=1"; do
-    env $( [ "$cfg" = base ] || echo $cfg ) timeout -k 10 300 python3 bench.py --steps 400 --warmup 40 --no-cpu-baseline --net-graph off > $O/k1_${cfg}_$rep.log 2>&1 || { echo FAIL $cfg; tail -5 $O/k1_${cfg}_$rep.log; }
+    env $( [ "$cfg" = base ] || echo $cfg ) timeout -k 10 300 python3 bench.py --full --steps 400 --warmup 40 --no-cpu-baseline --net-graph off > $O/k1_${cfg}_$rep.log 2>&1 || { echo FAIL $cfg; tail -5 $O/k1_${cfg}_$rep.log; }
     show $O/k1_${cfg}_$rep.log
   done
 done

@@ -10,9 +10,9 @@ import json,sys
 d=json.loads(open('$1').read().strip().splitlines()[-1]); print('$1'.split('/')[-1], {k:d.get(k) for k in ('value','ms_per_step','p99_latency_ms')}, d['network_launch']['mode'], d['stages_ms']['detector'])"; }
 for rep in 1 2; do
 for m in "m 4" "n 4"; do set -- $m
-  timeout -k 10 300 python3 bench.py --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/pad_$1$2_$rep.log 2>&1 || { echo FAIL; tail -3 $O/pad_$1$2_$rep.log; }
+  timeout -k 10 300 python3 bench.py --full --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/pad_$1$2_$rep.log 2>&1 || { echo FAIL; tail -3 $O/pad_$1$2_$rep.log; }
   show $O/pad_$1$2_$rep.log
-  RVA_NO_CIN_PAD=1 timeout -k 10 300 python3 bench.py --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/nopad_$1$2_$rep.log 2>&1 || { echo FAIL; tail -3 $O/nopad_$1$2_$rep.log; }
+  RVA_NO_CIN_PAD=1 timeout -k 10 300 python3 bench.py --full --model $1 --streams $2 --steps 500 --warmup 40 --no-cpu-baseline --no-extras > $O/nopad_$1$2_$rep.log 2>&1 || { echo FAIL; tail -3 $O/nopad_$1$2_$rep.log; }
   show $O/nopad_$1$2_$rep.log
 done
 done
