@@ -361,9 +361,41 @@ int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_
                        int anchors_total, const float *strides, rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * fp32 detector primitives (NHWC float32) -- the reference's default precision (`half: false`: an fp32
+ * ONNX Runtime graph, detector.py:248-251, 597-609), everything fp32 in and out.
+ *
+ * rva_conv2d_nhwc_f32_v: out = [SiLU](conv(in, weights) + bias) [+ residual]; ksize 1 or 3 (pad ksize/2), stride 1 or 2,
+ *   Cin % 16 == 0, row strides ldi (multiple of 4) / ldo / ldr in floats; in and weights 16-byte aligned.  weights: float32
+ *   [Cout][ksize*ksize][Cin] (no padding), bias float32 [Cout] or NULL.  Implicit GEMM on the exact fp32-input MFMA; the
+ *   k*k*Cin sum of an output element runs in ONE fixed order for every variant and every batch size (no split-K), so results
+ *   are bit-identical across variants 1..rva_conv_f32_num_variants() and 0 (= heuristic).  Only channels [0, Cin) of the
+ *   input slice are read and only channels [0, Cout) of the output slice are written.
+ * rva_stem_conv_f32: 3x3 stride 2 pad 1 + SiLU on the PLANAR fp32 [batch,3,H,W] tensor K1 writes for half=0; weights = the
+ *   checkpoint's float32 [Cout][3][3][3], Cout % 4 == 0; NHWC out with row stride ldo.
+ * rva_maxpool5_nhwc_f32 / rva_upsample2x_nhwc_f32: SPPF pooling (5x5, stride 1, -inf padding), FPN nearest 2x upsample, on
+ *   channel slices (C, ldi, ldo multiples of 4).
+ * rva_yolo_head_f32: one pyramid level, the module's formula in fp32: DFL softmax (max-subtracted) -> expectation ->
+ *   xywh = ((x1y1 + x2y2) / 2, x2y2 - x1y1) * stride, sigmoid scores, into out[batch, 4+nc, anchors_total] at anchor_offset.
+ * -------------------------------------------------------------------------------------------- */
+int rva_conv_f32_num_variants(void);
+int rva_conv2d_nhwc_f32_v(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias,
+                          void *out, int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin,
+                          int Cout, int ksize, int stride, int act, int variant, rva_stream_t stream);
+int rva_stem_conv_f32(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias,
+                      void *out, int ldo, int batch, int H, int W, int Cout, rva_stream_t stream);
+int rva_maxpool5_nhwc_f32(rva_ctx *ctx, const void *in, int ldi, void *out, int ldo, int batch, int H,
+                          int W, int C, rva_stream_t stream);
+int rva_upsample2x_nhwc_f32(rva_ctx *ctx, const void *in, int ldi, void *out, int ldo, int batch, int H,
+                            int W, int C, rva_stream_t stream);
+int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc,
+                      void *out, int batch, int h, int w, int nc, int anchors_total, int anchor_offset,
+                      float stride, rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The fused YOLOv8 detector as ONE object (round 4) -- replaces `self.session.run` of the reference's ONNX Runtime
  * backend (/root/reference/src/realtime_analytics/detector.py:597-609; the network it runs is the exported ultralytics graph,
- * detector.py:575-586) for `half: true`.
+ * detector.py:575-586) for `half: true` (fp16 operands, fp32 accumulation) or, with RVA_PLAN_F32 in desc.flags, for
+ * `half: false` in the reference's own fp32 precision.
  *
  * rva_yolov8_plan_create: `convs` = the network's n_convs convolutions with BatchNorm folded, in MODULE ORDER, each in the
  *   checkpoint's own layout (fp32 host arrays, weight [cout][cin][k][k], bias [cout] or NULL).  Module order: b0, b1, C2f(b2), b3,
@@ -372,7 +404,7 @@ int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_
  *   checks every shape against the descriptor (RVA_ERR_ARG names the first convolution that does not fit), packs the weights
  *   for the kernels above, allocates all activation buffers in HBM and lays down the static list of launches.
  * rva_yolov8_plan_run: input = fp16 planar [batch,3,height,width] (what rva_preprocess_* writes), output = fp16
- *   [batch, 4+nc, anchors] (what rva_postprocess_batch reads; anchors = H/8*W/8 + H/16*W/16 + H/32*W/32); every launch of the
+ *   [batch, 4+nc, anchors] (fp32 input and output for an RVA_PLAN_F32 plan; what rva_postprocess_batch reads; anchors = H/8*W/8 + H/16*W/16 + H/32*W/32); every launch of the
  *   forward pass goes to `stream`, no host synchronisation, no allocation: capturable.  _run_lanes additionally forks the
  *   stride-8 / stride-16 detect branches onto two side streams (events inside the plan) and joins them at the end: +6 % for one
  *   pass at a time; with several passes in flight use _run.  _run_range(first, last) replays steps [first, last) (a caller that
@@ -381,10 +413,15 @@ int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_
  *   A tuner times rva_yolov8_plan_launch_tunable(index, variant) on the plan's own buffers (RVA_ERR_ARG = variant does not
  *   apply to that layer) and fixes its choice with _set_variant; _tunable_desc gives "Cin->Cout kKsS HxW" (the key of a
  *   persisted selection).  Results do not depend on the variant beyond fp32 summation order.
+ * RVA_PLAN_F32: the same graph, plan object and entry points with fp32 activation buffers and the fp32 primitives above (one
+ *   stem launch, one convolution launch per Conv-BN-SiLU, three pool launches for SPPF, upsample launches into the concat
+ *   buffers, one head launch per level on the level's detect lane); the tunable steps carry rva_conv2d_nhwc_f32_v variants, and
+ *   the output does not depend on them at all (bit-identical).  RVA_PLAN_NO_STEM2 / NO_CIN_PAD / NO_PAIR32 have no effect on it.
  * -------------------------------------------------------------------------------------------- */
 #define RVA_PLAN_NO_STEM2 1   /* rva_yolov8_desc.flags: stem and first downsampling convolution as two launches (A/B switch) */
 #define RVA_PLAN_NO_CIN_PAD 2 /* ... convolutions with Cin % 32 != 0 keep their Cin (default: declared rounded up to 32, zero weights) */
 #define RVA_PLAN_NO_PAIR32 4  /* ... the 32-channel C2f bottlenecks (YOLOv8s at 160 x 160) as two convolution launches instead of rva_c2f_pair32_f16 */
+#define RVA_PLAN_F32 8        /* ... fp32 plan: fp32 input, buffers, weights and output (every convolution's Cin % 16 == 0) */
 typedef struct rva_yolov8_plan rva_yolov8_plan;
 typedef struct rva_yolov8_desc {
     int32_t batch, height, width;     /* input tensor; height and width multiples of 32 */

@@ -18,8 +18,8 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
-SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_plan.hip", "rva_gates.hip",
-           "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip",
+           "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]
@@ -58,6 +58,7 @@ class ConvWeights(C.Structure):
 RVA_PLAN_NO_STEM2 = 1
 RVA_PLAN_NO_CIN_PAD = 2
 RVA_PLAN_NO_PAIR32 = 4
+RVA_PLAN_F32 = 8
 
 
 def _stale() -> bool:
@@ -177,6 +178,13 @@ def lib() -> C.CDLL:
         "rva_upsample2x_nhwc_f16": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
         "rva_yolo_head_f16": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_float, _P]),
+        "rva_conv_f32_num_variants": (C.c_int, []),
+        "rva_conv2d_nhwc_f32_v": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int] + [C.c_int] * 9 + [_P]),
+        "rva_stem_conv_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_maxpool5_nhwc_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_upsample2x_nhwc_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_yolo_head_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_float, _P]),
         "rva_yolov8_plan_create": (C.c_int, [_P, C.POINTER(YoloV8Desc), C.POINTER(ConvWeights), C.POINTER(_P)]),
         "rva_yolov8_plan_destroy": (None, [_P]),
         "rva_yolov8_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p, i32p]),
@@ -213,6 +221,8 @@ EXPORTS = [
     "rva_decoder_next_frame", "rva_decoder_release", "rva_motion_nv12_batch", "rva_motion_nv12_masked_batch", "rva_motion_bgr_batch",
     "rva_preprocess_nv12_masked_batch", "rva_resize_nv12_to_bgr_batch", "rva_tracker_set_box_scale", "rva_conv_cout_pad", "rva_conv_num_variants", "rva_conv2d_nhwc_f16", "rva_conv2d_nhwc_f16_v", "rva_stem_conv_f16", "rva_stem2_f16", "rva_c2f_pair32_f16",
     "rva_conv1x1_head_f16", "rva_conv1x1_upcat_f16", "rva_sppf_pool3_nhwc_f16", "rva_maxpool5_nhwc_f16", "rva_upsample2x_nhwc_f16", "rva_yolo_head_f16", "rva_yolo_head3_f16",
+    "rva_conv_f32_num_variants", "rva_conv2d_nhwc_f32_v", "rva_stem_conv_f32", "rva_maxpool5_nhwc_f32", "rva_upsample2x_nhwc_f32",
+    "rva_yolo_head_f32",
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
     "rva_yolov8_plan_get_variant", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",

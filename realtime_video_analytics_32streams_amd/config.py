@@ -8,7 +8,10 @@ Compatibility rules kept from the reference:
   * fields that the reference declares but never reads (``batch_size``, ``tracker.type``, ...) are
     accepted and carried, so a reference YAML loads unchanged.
 Additions: backend ``"hip"`` (this library) is a valid detector backend, and the out-of-scope
-sections (kafka / prometheus / ffmpeg_simulator) are kept as opaque dicts.
+sections (kafka / prometheus / ffmpeg_simulator) are kept as opaque dicts.  With backend ``"hip"``, the
+detector key ``hip_engine`` picks the YOLO network's engine: ``"auto"`` (default; what a reference YAML gets)
+= the hand-written fp16 plan for ``half: true`` and PyTorch-ROCm for ``half: false``; ``"plan"`` = the
+hand-written plan at the configured precision, i.e. the fp32 plan for ``half: false``.
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import yaml
 
 HIP_BACKENDS = ("hip", "rocm", "mi355x")
 REFERENCE_BACKENDS = ("ultralytics", "tensorrt", "onnx", "onnxruntime", "openvino", "rknn", "rk3588")
+HIP_ENGINES = ("auto", "plan")
 TEMPORAL_MODELS = ("cnn_lstm", "3d_cnn", "conv_gru", "slow_fast")
 MODEL_TYPES = ("yolov5", "yolov8", "resnet") + TEMPORAL_MODELS
 
@@ -92,9 +96,11 @@ class DetectorConfig:
     temporal_pooling: str = "avg"
     action_classes: Optional[List[str]] = None
     num_action_classes: int = 400
+    hip_engine: str = "auto"                # backend "hip", YOLO: "auto" or "plan" (module docstring)
 
     def validate(self) -> None:
         _need(bool(self.model_path), "Detector model_path must not be empty")
+        _need(self.hip_engine in HIP_ENGINES, f"hip_engine must be one of {set(HIP_ENGINES)}")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,
               f"Detector backend must be one of {set(REFERENCE_BACKENDS + HIP_BACKENDS)}")
         _need(self.model_type in MODEL_TYPES, f"Model type must be one of {set(MODEL_TYPES)}")

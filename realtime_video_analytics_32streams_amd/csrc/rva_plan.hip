@@ -1,6 +1,7 @@
 // rva_yolov8_plan_*: the fused YOLOv8 detector as ONE object behind the C ABI.
 //
-// Replaces the reference's `session.run` (detector.py:597-609: ONNX Runtime on the exported ultralytics graph) for the fp16 path:
+// Replaces the reference's `session.run` (detector.py:597-609: ONNX Runtime on the exported ultralytics graph) in fp16 or, with
+// RVA_PLAN_F32, in the reference's own fp32 (the same graph on fp32 buffers and the kernels of rva_conv_f32.hip, see build()):
 // create() takes the network's convolutions in module order (BatchNorm folded, the checkpoint's own fp32 [Cout][Cin][k][k]
 // layout), packs them for the kernels of rva_conv.hip, allocates every NHWC fp16 activation buffer in HBM and lays down the static
 // list of launches (one per Conv-BN-SiLU; concat / chunk / upsample never materialise: producers write channel slices of the
@@ -23,11 +24,12 @@
 
 namespace {
 
-enum StepKind { K_CONV, K_UPCAT, K_HEAD, K_STEM2, K_STEM, K_SPPF3, K_POOL5, K_UP2, K_HEAD3, K_PAIR32 };
+enum StepKind { K_CONV, K_UPCAT, K_HEAD, K_STEM2, K_STEM, K_SPPF3, K_POOL5, K_UP2, K_HEAD3, K_PAIR32,
+                K_CONV_F32, K_STEM_F32, K_POOL5_F32, K_UP2_F32, K_HEAD_F32 };
 
-struct View {           // a channel slice of an NHWC buffer
-    char *base = nullptr; int ld = 0, off = 0, ch = 0;
-    void *ptr() const { return base + 2 * (size_t)off; }
+struct View {           // a channel slice of an NHWC buffer (es = bytes per element: 2 fp16, 4 fp32)
+    char *base = nullptr; int ld = 0, off = 0, ch = 0, es = 2;
+    void *ptr() const { return base + (size_t)es * off; }
     View sub(int o, int c) const { View v = *this; v.off += o; v.ch = c; return v; }
 };
 
@@ -61,6 +63,7 @@ struct rva_yolov8_plan {
     int quiet_step = 0;
     hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr}, join_ev[3] = {nullptr, nullptr, nullptr};
     bool fused_stem = false, fused_head = false;
+    bool f32 = false;                     // RVA_PLAN_F32: fp32 buffers and the kernels of rva_conv_f32.hip
 };
 
 namespace {
@@ -87,11 +90,47 @@ struct Builder {
         View v;
         // + 64 B: a convolution whose Cin is not a multiple of 32 runs with Cin rounded up (zero weights for the extra channels, see
         // conv()) and reads up to 31 channels past its slice -- the next slice of the row, the next row, or, behind the last row, this slack
-        v.base = (char *)dev_alloc((size_t)m * ch * 2 + 64, true);
+        v.es = p->f32 ? 4 : 2;
+        v.base = (char *)dev_alloc((size_t)m * ch * v.es + 64, true);
         v.ld = ch; v.off = 0; v.ch = ch;
         return v;
     }
     // Pack sibling convolutions (equal Cin / kernel / stride, outputs concatenated) as [CoutPad][k*k][CinPad] fp16 + [CoutPad] fp32
+    bool upload(const void *host, size_t bytes, const void **dev)
+    {
+        void *d = dev_alloc(bytes, false);
+        if (!d) return false;
+        if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("weight upload failed");
+        *dev = d;
+        return true;
+    }
+    // fp32 plan: sibling convolutions packed as [Cout][k*k][Cin] fp32 (no padding: rva_conv2d_nhwc_f32_v masks the tile edges) + [Cout] fp32
+    bool pack_f32(const rva_conv_weights *const *cv, int n, const void **w_dev, const float **b_dev, int *cin, int *cout, int *k, int *stride)
+    {
+        const rva_conv_weights &c0 = *cv[0];
+        int co = 0;
+        for (int i = 0; i < n; ++i) {
+            if (!cv[i]->weight || cv[i]->cin != c0.cin || cv[i]->k != c0.k || cv[i]->stride != c0.stride) return fail("sibling convolutions differ");
+            co += cv[i]->cout;
+        }
+        const int kk = c0.k * c0.k;
+        std::vector<float> hw((size_t)co * kk * c0.cin, 0.f), hb(co, 0.f);
+        int o = 0;
+        for (int i = 0; i < n; ++i) {
+            const rva_conv_weights &c = *cv[i];
+            for (int oc = 0; oc < c.cout; ++oc) {
+                for (int ic = 0; ic < c.cin; ++ic)
+                    for (int t = 0; t < kk; ++t)
+                        hw[((size_t)(o + oc) * kk + t) * c.cin + ic] = c.weight[((size_t)oc * c.cin + ic) * kk + t];
+                if (c.bias) hb[o + oc] = c.bias[oc];
+            }
+            o += c.cout;
+        }
+        const void *db = nullptr;
+        if (!upload(hw.data(), hw.size() * 4, w_dev) || !upload(hb.data(), hb.size() * 4, &db)) return false;
+        *b_dev = (const float *)db; *cin = c0.cin; *cout = co; *k = c0.k; *stride = c0.stride;
+        return true;
+    }
     bool pack(const rva_conv_weights *const *cv, int n, const void **w_dev, const float **b_dev, int *cin, int *cout, int *k, int *stride)
     {
         const rva_conv_weights &c0 = *cv[0];
@@ -148,12 +187,19 @@ struct Builder {
     // one Conv-BN-SiLU (or a fused group of siblings); returns false on error
     bool conv(const rva_conv_weights *const *cv, int n, View src, View dst, int h, int w, int act, const View *res = nullptr)
     {
-        Step s{}; s.kind = K_CONV;
-        if (!pack(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
+        Step s{}; s.kind = p->f32 ? K_CONV_F32 : K_CONV;
+        const bool packed = p->f32 ? pack_f32(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)
+                                   : pack(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride);
+        if (!packed) return false;
         if (s.Cin != src.ch || s.Cout != dst.ch) return fail("convolution does not fit its buffers");
         s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.act = act;
         if (res) { s.res = res->ptr(); s.ldr = res->ld; }
         const int cin_real = s.Cin;
+        if (p->f32) {                     // every channel count is read as it is: the kernel never reads past its slice
+            if (s.Cin % 16) return fail("fp32 plan: convolution input channels must be multiples of 16");
+            push(s, "%d->%d k%ds%d %dx%d", cin_real, s.Cout, s.k, s.stride, h, w);
+            return true;
+        }
         // Cin 48 / 16 (YOLOv8m / n): the LDS-DMA kernels want whole 32-channel chunks.  The packed weights already carry zero
         // columns up to the next multiple of 32, so the step simply declares the padded Cin: the extra channels it reads are whatever
         // follows the slice (finite activations of the neighbouring slice / pixel, or the buffer's zero slack) times zero.
@@ -200,7 +246,7 @@ struct Builder {
         for (int i = 0; i < n; ++i) {
             const rva_conv_weights *b1 = take(c, c, 3, 1, what), *b2 = take(c, c, 3, 1, what);
             View x = cat.sub((1 + i) * c, c);
-            if (c == 32 && shortcut && !(p->d.flags & RVA_PLAN_NO_PAIR32)) {
+            if (c == 32 && shortcut && !p->f32 && !(p->d.flags & RVA_PLAN_NO_PAIR32)) {
                 // both 3x3 convolutions and the shortcut in one launch, the intermediate in LDS (rva_c2f_pair32_f16)
                 Step s{}; s.kind = K_PAIR32;
                 int ci, co, kk, st;
@@ -226,35 +272,52 @@ struct Builder {
         // stem (planar input from K1): weights [64][32] fp16, column order k = 2 j + kx (kx in {0, 1}), k = 18 + j (kx = 2), j = c*3 + ky
         const rva_conv_weights *b0 = take(3, c1, 3, 2, "b0"), *b1 = take(c1, c2, 3, 2, "b1");
         if (!b0 || !b1) return false;
-        if (c1 > 64) return fail("stem wider than 64 channels");
-        std::vector<_Float16> sw(64 * 32, (_Float16)0.f);
-        std::vector<float> sb(64, 0.f);
-        for (int co = 0; co < c1; ++co) {
-            for (int j = 0; j < 9; ++j)                       // j = c*3 + ky;  weight[co][c][ky][kx]
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float v = b0->weight[((size_t)co * 3 + j / 3) * 9 + (j % 3) * 3 + kx];
-                    sw[co * 32 + (kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)v;
-                }
-            if (b0->bias) sb[co] = b0->bias[co];
-        }
-        void *dsw = dev_alloc(sw.size() * 2, false), *dsb = dev_alloc(sb.size() * 4, false);
-        if (!dsw || !dsb) return false;
-        if (hipMemcpy(dsw, sw.data(), sw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dsb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("stem upload failed");
-        View x1 = buf((long)B * h2 * w2, c2);
-        if (!x1.base) return false;
-        p->fused_stem = c1 == 32 && c2 == 64 && !(d.flags & RVA_PLAN_NO_STEM2);
-        if (p->fused_stem) {
-            Step s{}; s.kind = K_STEM2; s.w = dsw; s.b = (const float *)dsb; s.out = x1.ptr(); s.ldo = x1.ld; s.H = H; s.W = W;
-            int ci, co, k, st;
-            if (!pack(&b1, 1, &s.w2, &s.b2, &ci, &co, &k, &st)) return false;
-            push(s, nullptr);
-        } else {
+        View x1;
+        if (p->f32) {
+            // stem from the planar fp32 input (rva_stem_conv_f32): the checkpoint's [c1][3][3][3] weights as they are
+            Step s{}; s.kind = K_STEM_F32;
+            std::vector<float> sb(c1, 0.f);
+            if (b0->bias) memcpy(sb.data(), b0->bias, sizeof(float) * c1);
+            const void *db = nullptr;
+            if (!b0->weight || !upload(b0->weight, sizeof(float) * c1 * 27, &s.w) || !upload(sb.data(), sizeof(float) * c1, &db)) return false;
+            s.b = (const float *)db;
             View x0 = buf((long)B * h1 * w1, c1);
-            if (!x0.base) return false;
-            Step s{}; s.kind = K_STEM; s.w = dsw; s.b = (const float *)dsb; s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
+            x1 = buf((long)B * h2 * w2, c2);
+            if (!x0.base || !x1.base) return false;
+            s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
             push(s, nullptr);
             if (!conv1(b1, x0, x1, h1, w1, 1)) return false;
+        } else {
+            if (c1 > 64) return fail("stem wider than 64 channels");
+            std::vector<_Float16> sw(64 * 32, (_Float16)0.f);
+            std::vector<float> sb(64, 0.f);
+            for (int co = 0; co < c1; ++co) {
+                for (int j = 0; j < 9; ++j)                       // j = c*3 + ky;  weight[co][c][ky][kx]
+                    for (int kx = 0; kx < 3; ++kx) {
+                        const float v = b0->weight[((size_t)co * 3 + j / 3) * 9 + (j % 3) * 3 + kx];
+                        sw[co * 32 + (kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)v;
+                    }
+                if (b0->bias) sb[co] = b0->bias[co];
+            }
+            void *dsw = dev_alloc(sw.size() * 2, false), *dsb = dev_alloc(sb.size() * 4, false);
+            if (!dsw || !dsb) return false;
+            if (hipMemcpy(dsw, sw.data(), sw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(dsb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("stem upload failed");
+            x1 = buf((long)B * h2 * w2, c2);
+            if (!x1.base) return false;
+            p->fused_stem = c1 == 32 && c2 == 64 && !(d.flags & RVA_PLAN_NO_STEM2);
+            if (p->fused_stem) {
+                Step s{}; s.kind = K_STEM2; s.w = dsw; s.b = (const float *)dsb; s.out = x1.ptr(); s.ldo = x1.ld; s.H = H; s.W = W;
+                int ci, co, k, st;
+                if (!pack(&b1, 1, &s.w2, &s.b2, &ci, &co, &k, &st)) return false;
+                push(s, nullptr);
+            } else {
+                View x0 = buf((long)B * h1 * w1, c1);
+                if (!x0.base) return false;
+                Step s{}; s.kind = K_STEM; s.w = dsw; s.b = (const float *)dsb; s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
+                push(s, nullptr);
+                if (!conv1(b1, x0, x1, h1, w1, 1)) return false;
+            }
         }
         View x2 = buf((long)B * h2 * w2, c2);
         if (!x2.base || !c2f(c2, c2, d.depth_backbone[0], true, &x1, nullptr, nullptr, x2, h2, w2, "b2")) return false;
@@ -279,30 +342,30 @@ struct Builder {
             const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
             View cat = buf((long)B * h5 * w5, 4 * c_);
             if (!cat.base || !conv1(cv1, t5b, cat.sub(0, c_), h5, w5, 1)) return false;
-            if (h5 * w5 <= 2400) {
+            if (h5 * w5 <= 2400 && !p->f32) {
                 Step s{}; s.kind = K_SPPF3; s.in = cat.sub(0, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub(c_, c_).ptr(); s.out2 = cat.sub(2 * c_, c_).ptr();
                 s.out3 = cat.sub(3 * c_, c_).ptr(); s.ldo = cat.ld; s.H = h5; s.W = w5; s.Cin = c_;
                 push(s, nullptr);
             } else {
                 for (int i = 0; i < 3; ++i) {
-                    Step s{}; s.kind = K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
+                    Step s{}; s.kind = p->f32 ? K_POOL5_F32 : K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
                     s.H = h5; s.W = w5; s.Cin = c_;
                     push(s, nullptr);
                 }
             }
             if (!conv1(cv2, cat, p5, h5, w5, 1)) return false;
         }
-        const bool fuse_up = c5 % 64 == 0 && c4 % 64 == 0 && c3 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4;
+        const bool fuse_up = !p->f32 && c5 % 64 == 0 && c4 % 64 == 0 && c3 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4;
         View n3 = buf((long)B * h3 * w3, c3);
         if (!n3.base) return false;
         if (fuse_up) {    // FPN top-down path: upsample + concat folded into the consuming 1x1 convolutions
             if (!c2f(c5 + c4, c4, nh, false, nullptr, &p5, &p4, n4, h4, w4, "h12")) return false;
             if (!c2f(c4 + c3, c3, nh, false, nullptr, &n4, &p3, n3, h3, w3, "h15")) return false;
         } else {
-            Step u1{}; u1.kind = K_UP2; u1.in = p5.ptr(); u1.ldi = p5.ld; u1.out = cat12.sub(0, c5).ptr(); u1.ldo = cat12.ld; u1.H = h5; u1.W = w5; u1.Cin = c5;
+            Step u1{}; u1.kind = p->f32 ? K_UP2_F32 : K_UP2; u1.in = p5.ptr(); u1.ldi = p5.ld; u1.out = cat12.sub(0, c5).ptr(); u1.ldo = cat12.ld; u1.H = h5; u1.W = w5; u1.Cin = c5;
             push(u1, nullptr);
             if (!c2f(c5 + c4, c4, nh, false, &cat12, nullptr, nullptr, n4, h4, w4, "h12")) return false;
-            Step u2{}; u2.kind = K_UP2; u2.in = n4.ptr(); u2.ldi = n4.ld; u2.out = cat15.sub(0, c4).ptr(); u2.ldo = cat15.ld; u2.H = h4; u2.W = w4; u2.Cin = c4;
+            Step u2{}; u2.kind = p->f32 ? K_UP2_F32 : K_UP2; u2.in = n4.ptr(); u2.ldi = n4.ld; u2.out = cat15.sub(0, c4).ptr(); u2.ldo = cat15.ld; u2.H = h4; u2.W = w4; u2.Cin = c4;
             push(u2, nullptr);
             if (!c2f(c4 + c3, c3, nh, false, &cat15, nullptr, nullptr, n3, h3, w3, "h15")) return false;
         }
@@ -332,7 +395,7 @@ struct Builder {
             if (!cls[l][0] || !cls[l][1] || !cls[l][2]) return false;
         }
         if (next != d.n_convs) return fail("convolution list longer than the architecture");
-        p->fused_head = cb % 64 == 0 && cc % 64 == 0 && rm4 == 64 && d.nc % 8 == 0;
+        p->fused_head = !p->f32 && cb % 64 == 0 && cc % 64 == 0 && rm4 == 64 && d.nc % 8 == 0;
         const View feats[3] = {n3, m4, m5};
         const int hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
         const float strides[3] = {8.f, 16.f, 32.f};
@@ -341,7 +404,7 @@ struct Builder {
         for (int l = 0; l < 3; ++l) {
             // the three detect branches only depend on their own feature map and write disjoint anchor ranges: the stride-8 and
             // stride-16 branches may run on side streams beside the rest of the neck (rva_yolov8_plan_run_lanes)
-            lane = (p->fused_head && l < 2) ? l + 1 : 0;
+            lane = ((p->fused_head || p->f32) && l < 2) ? l + 1 : 0;
             if (lane) p->fork_step[lane] = l == 0 ? fork_n3 : fork_m4;
             const long m = (long)B * hs[l] * ws[l];
             View first = buf(m, cb + cc), b2 = buf(m, cb), k2 = buf(m, cc);
@@ -357,11 +420,16 @@ struct Builder {
                 if (!conv1(box[l][1], first.sub(0, cb), b2, hs[l], ws[l], 1) || !conv1(box[l][2], b2, bo, hs[l], ws[l], 0)) return false;
                 if (!conv1(cls[l][1], first.sub(cb, cc), k2, hs[l], ws[l], 1) || !conv1(cls[l][2], k2, ko, hs[l], ws[l], 0)) return false;
                 h3s.hb[l] = bo.ptr(); h3s.hldb[l] = bo.ld; h3s.hk[l] = ko.ptr(); h3s.hldc[l] = ko.ld; h3s.hh[l] = hs[l]; h3s.hw[l] = ws[l]; h3s.hs[l] = strides[l];
+                if (p->f32) {             // the level's decode on its own lane (rva_yolo_head_f32): disjoint anchor range of the output
+                    Step hs1{}; hs1.kind = K_HEAD_F32; hs1.in = bo.ptr(); hs1.ldi = bo.ld; hs1.in2 = ko.ptr(); hs1.ldi2 = ko.ld;
+                    hs1.H = hs[l]; hs1.W = ws[l]; hs1.a0 = a0; hs1.stride_px = strides[l];
+                    push(hs1, nullptr);
+                }
             }
             a0 += hs[l] * ws[l];
         }
         lane = 0;
-        if (!p->fused_head) push(h3s, nullptr);
+        if (!p->fused_head && !p->f32) push(h3s, nullptr);
         return err.empty();
     }
 };
@@ -380,6 +448,11 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
     case K_POOL5: return rva_maxpool5_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
     case K_UP2: return rva_upsample2x_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
     case K_HEAD3: return rva_yolo_head3_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, p->B, s.hh, s.hw, p->nc, p->A, s.hs, st);
+    case K_CONV_F32: return rva_conv2d_nhwc_f32_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
+    case K_STEM_F32: return rva_stem_conv_f32(c, input, s.w, s.b, s.out, s.ldo, p->B, s.H, s.W, s.Cout, st);
+    case K_POOL5_F32: return rva_maxpool5_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
+    case K_UP2_F32: return rva_upsample2x_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
+    case K_HEAD_F32: return rva_yolo_head_f32(c, s.in, s.ldi, s.in2, s.ldi2, output, p->B, s.H, s.W, p->nc, p->A, s.a0, s.stride_px, st);
     }
     return RVA_ERR_ARG;
 }
@@ -387,6 +460,7 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
 bool variant_fits(const Step &s, int variant)
 {
     if (s.kind == K_CONV) return variant >= 0;
+    if (s.kind == K_CONV_F32) return variant >= 0 && variant <= rva_conv_f32_num_variants();
     return variant == 0 || (variant >= 33 && variant <= 39);     // upcat / head: the LDS-DMA gather family
 }
 
@@ -406,6 +480,7 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
     RVA_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
     p->ctx = ctx; p->d = *desc; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
+    p->f32 = (desc->flags & RVA_PLAN_F32) != 0;
     Builder b{p.get(), convs};
     const bool ok = b.build();
     if (!ok) {

@@ -97,8 +97,9 @@ class HipYoloDetector(BaseDetector):
                  seed: int = 0, device: Optional[int] = None):
         """``half: true`` (every BASELINE configuration) runs the network as the librva plan: hand-written MFMA kernels, one
         launch per layer, fp16 operands with fp32 accumulation.  ``half: false`` is the reference's fp32 precision
-        (detector.py:248-251): there is no hand-written fp32 plan, the module then runs through PyTorch-ROCm (MIOpen) and
-        the constructor says so in the log -- a configuration never changes engines silently."""
+        (detector.py:248-251): by default (``hip_engine: auto``) the module then runs through PyTorch-ROCm (MIOpen) and the
+        constructor says so in the log -- a configuration never changes engines silently; ``hip_engine: plan`` runs it as the
+        hand-written fp32 plan instead (engine ``"fused-f32"``: exact fp32 MFMA, bit-reproducible, same pipeline integration)."""
         super().__init__(config)
         self._plans = {}
         self.ctx = ops.context(device)            # raises RuntimeError when no HIP device (no CPU fallback)
@@ -108,7 +109,7 @@ class HipYoloDetector(BaseDetector):
         else:
             self.input_hw = (640, 640)            # detector.py:582-583 default
         self.half = bool(config.half)
-        self.engine = "fused" if self.half else "torch-fp32"
+        self.engine = "fused" if self.half else ("fused-f32" if getattr(config, "hip_engine", "auto") == "plan" else "torch-fp32")
         self._infer_fn = infer_fn
         self.net = None
         if infer_fn is None:
@@ -117,7 +118,7 @@ class HipYoloDetector(BaseDetector):
                 net = build_detector_net(scale, seed=seed, weights=config.model_path)
                 LOGGER.info("hip detector: YOLOv8%s, %s weights", scale,
                             "local state-dict" if _is_file(config.model_path) else "seeded random (no weights offline)")
-            if not self.half:
+            if self.engine == "torch-fp32":
                 LOGGER.warning("hip detector: half=false -> fp32 network through PyTorch-ROCm (MIOpen); the hand-written fp16 "
                                "MFMA plan runs with `half: true`")
             net = net.fuse().to(self.device)
@@ -181,7 +182,8 @@ class HipYoloDetector(BaseDetector):
             from .engine import FusedYoloV8
             first = self._plans.get(shape) if self._slot else None
             plan = self._plans[key] = FusedYoloV8(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
-                                                  autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1))
+                                                  autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
+                                                  precision="fp32" if self.engine == "fused-f32" else "fp16")
             if first is not None:
                 plan.copy_tuning(first)
         return plan
@@ -192,6 +194,10 @@ class HipYoloDetector(BaseDetector):
         if self.half:
             if tensor.dtype != torch.float16:
                 raise TypeError("half detector: the fused plan takes the fp16 tensor K1 writes")
+            return self.plan_for(tensor)(tensor.contiguous())
+        if self.engine == "fused-f32":
+            if tensor.dtype != torch.float32:
+                raise TypeError("fp32 plan: takes the fp32 tensor K1 writes for half=false")
             return self.plan_for(tensor)(tensor.contiguous())
         return self.net(tensor.float().contiguous(memory_format=torch.channels_last))
 

@@ -12,7 +12,9 @@ The plan itself -- weight packing, the NHWC fp16 activation buffers, the static 
   * the result tensors (a pipelined caller alternates several).
 
 Output: the same ``[B, 4+nc, A]`` fp16 tensor the torch module returns, so everything downstream (K2/K3/K4) and every parity
-test is unchanged.  No host synchronisation and no allocation after construction: a whole tick can be captured into a hipGraph.
+test is unchanged.  ``precision="fp32"`` builds the same plan in the reference's own precision (``RVA_PLAN_F32``: fp32 input,
+activations, weights and ``[B, 4+nc, A]`` fp32 output; kernels of ``csrc/rva_conv_f32.hip``, bit-identical across kernel variants).
+No host synchronisation and no allocation after construction: a whole tick can be captured into a hipGraph.
 """
 from __future__ import annotations
 
@@ -82,8 +84,12 @@ class _VariantCell:
 
 class FusedYoloV8:
     def __init__(self, net: YoloV8, batch: int, hw: Tuple[int, int] = (640, 640), device: Optional[torch.device] = None,
-                 ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1):
+                 ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16"):
         import os
+        if precision not in ("fp16", "fp32"):
+            raise ValueError(f"precision must be 'fp16' or 'fp32', not {precision!r}")
+        self.precision = precision
+        self.f32 = precision == "fp32"
         self.tune_overlap = int(tune_overlap)
         self.ctx = ctx or ops.context()
         self.dev = device or torch.device("cuda", self.ctx.device)
@@ -112,7 +118,8 @@ class FusedYoloV8:
         d.nc, d.reg_max, d.n_convs = net.nc, net.detect.reg_max, len(convs)
         d.flags = (N.RVA_PLAN_NO_STEM2 if os.environ.get("RVA_NO_STEM2", "0") == "1" else 0) | \
                   (N.RVA_PLAN_NO_CIN_PAD if os.environ.get("RVA_NO_CIN_PAD", "0") == "1" else 0) | \
-                  (0 if self._use_pair32() else N.RVA_PLAN_NO_PAIR32)
+                  (0 if self._use_pair32() else N.RVA_PLAN_NO_PAIR32) | \
+                  (N.RVA_PLAN_F32 if self.f32 else 0)
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
             self.ctx.check(self.L.rva_yolov8_plan_create(self.ctx.handle, C.byref(d), arr, C.byref(h)), "rva_yolov8_plan_create")
@@ -122,9 +129,10 @@ class FusedYoloV8:
         self.ctx.check(self.L.rva_yolov8_plan_info(h, *[C.byref(v) for v in info]), "rva_yolov8_plan_info")
         self.A, rows, self._n_steps, n_tun, self.quiet_step = (int(v.value) for v in info)
         assert rows == 4 + self.nc
-        self.out = torch.empty((batch, rows, self.A), dtype=torch.float16, device=self.dev)
+        self.dtype = torch.float32 if self.f32 else torch.float16
+        self.out = torch.empty((batch, rows, self.A), dtype=self.dtype, device=self.dev)
         self._outs = {0: self.out}
-        self.fused_stem = not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
+        self.fused_stem = not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
         # (launch(stream, variant) -> rc, state["variant"], "Cin->Cout kKsS HxW") per convolution step, as the tuner and the tools use them
         self._tunable = []
         buf = C.create_string_buffer(96)
@@ -141,8 +149,9 @@ class FusedYoloV8:
             self.autotune()
 
     def fused_head_lanes(self) -> bool:
-        """Whether the plan has detect branches that may run on side streams (head decode fused into the branches)."""
-        return any(d.startswith("head1:") for _, _, d in self._tunable)
+        """Whether the plan has detect branches that may run on side streams (head decode fused into the branches, or an fp32
+        plan, whose per-level head launches ride on the branches' lanes)."""
+        return self.f32 or any(d.startswith("head1:") for _, _, d in self._tunable)
 
     def __del__(self):  # best effort
         try:
@@ -167,6 +176,8 @@ class FusedYoloV8:
         h.update(repr([os.environ.get(k, "") for k in ("RVA_SKIP_VARIANTS", "RVA_TUNE_IN_PLAN", "RVA_TUNE_OVERLAP", "RVA_TUNE_TOP",
                                                        "RVA_TUNE_WITHIN", "RVA_NO_STEM2", "RVA_HEAD_SPLIT", "RVA_NO_CIN_PAD")]).encode())
         h.update(repr(int(os.environ.get("RVA_TUNE_LAYER_OVERLAP", getattr(self, "tune_overlap", 1)))).encode())
+        if getattr(self, "f32", False):
+            h.update(b"precision fp32")                 # fp16 keys stay as they were: existing caches remain valid
         return h.hexdigest()[:24]
 
     def _load_tuning(self) -> bool:
@@ -282,7 +293,7 @@ class FusedYoloV8:
 
     def copy_tuning(self, other: "FusedYoloV8") -> None:
         """Take over the kernel selection of a plan built from the same network and batch shape."""
-        assert len(self._tunable) == len(other._tunable)
+        assert len(self._tunable) == len(other._tunable) and self.precision == other.precision
         for (_, mine, d1), (_, theirs, d2) in zip(self._tunable, other._tunable):
             assert d1 == d2
             mine["variant"] = theirs["variant"]
@@ -297,7 +308,7 @@ class FusedYoloV8:
         128-KB workgroup per CU) shares worse than a two-workgroups-per-CU one that is a few per cent slower alone.  For the
         layers with runners-up within 25 % the whole forward pass is timed with each candidate (coordinate descent, most
         expensive layers first) and a candidate is kept when the pass gets faster by more than the timing noise."""
-        x = torch.zeros((self.B, 3, self.H, self.W), dtype=torch.float16, device=self.dev)
+        x = torch.zeros((self.B, 3, self.H, self.W), dtype=self.dtype, device=self.dev)
         # The objective is what the pipeline does with the plan: forward passes of consecutive ticks rotate over three streams
         # and overlap (PipelinedTicks, depth 3), so the pass is timed as a group -- this plan on one stream, twins with the same
         # kernel selection on the others.  RVA_TUNE_OVERLAP=n: n passes in flight (0 / 1: a single pass alone).
@@ -305,7 +316,8 @@ class FusedYoloV8:
         lanes = self.concurrent_heads
         n_over = int(os.environ.get("RVA_TUNE_OVERLAP", "3"))
         if n_over >= 2:
-            twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False) for _ in range(n_over - 1)]
+            twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision)
+                     for _ in range(n_over - 1)]
             from .ops import chain_streams
             streams = chain_streams(self.dev, n_over)                  # the streams the pipeline's tick chains will run on
             self.concurrent_heads = False                              # as PipelinedTicks runs overlapping passes: branches in line
@@ -371,8 +383,9 @@ class FusedYoloV8:
 
     # -- run ------------------------------------------------------------------------------------------
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        """``x``: fp16 planar ``[B,3,H,W]`` contiguous (what K1 writes).  Returns ``[B, 4+nc, A]`` fp16.  One ABI call."""
-        assert x.is_cuda and x.dtype == torch.float16 and x.is_contiguous() and tuple(x.shape) == (self.B, 3, self.H, self.W)
+        """``x``: fp16 (fp32 for an fp32 plan) planar ``[B,3,H,W]`` contiguous (what K1 writes).  Returns ``[B, 4+nc, A]`` of the
+        plan's precision.  One ABI call."""
+        assert x.is_cuda and x.dtype == self.dtype and x.is_contiguous() and tuple(x.shape) == (self.B, 3, self.H, self.W)
         main = torch.cuda.current_stream()
         stream = C.c_void_p(main.cuda_stream)
         xin, out = C.c_void_p(x.data_ptr()), C.c_void_p(self.out.data_ptr())

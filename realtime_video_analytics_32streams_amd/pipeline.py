@@ -435,7 +435,9 @@ class PipelinedTicks:
         self.nslots = max(depth, 2)           # a tick's slot ("parity") = k mod nslots: buffers, events, snapshot slot
         self.det, self.dt = pipe.detector, pipe.tracker.device_tracker
         self.world_sharded = pipe.id_sync is not None
-        is_fused = lambda d: getattr(d, "engine", None) == "fused" and d.half and d._infer_fn is None      # noqa: E731
+        # the hand-written plans: fp16 ("fused", half: true) and fp32 ("fused-f32", half: false with hip_engine: plan)
+        is_fused = lambda d: ((getattr(d, "engine", None) == "fused" and d.half) or getattr(d, "engine", None) == "fused-f32") \
+            and d._infer_fn is None      # noqa: E731
         fused = all(is_fused(d) for d in pipe.detectors)
         # temporal heads run their (torch) network eagerly; they may still run as two chains: every result buffer of theirs
         # exists per tick parity and their frame ring has two slots more than a clip needs
@@ -640,7 +642,7 @@ class PipelinedTicks:
         pres, raws = [], []
         for gi, g in enumerate(plan.groups):
             det = p.detectors[g.det]
-            plan_det = hasattr(det, "plan_for") and getattr(det, "engine", None) == "fused" and det._infer_fn is None
+            plan_det = hasattr(det, "plan_for") and getattr(det, "engine", None) in ("fused", "fused-f32") and det._infer_fn is None
             with torch.cuda.stream(sk), torch.inference_mode():
                 if events and gi == 0: events[0].record()
                 if before_k1 and gi == 0: before_k1()
