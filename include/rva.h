@@ -451,6 +451,53 @@ int rva_yolov8_plan_set_variant(rva_yolov8_plan *plan, int index, int variant);
 int rva_yolov8_plan_get_variant(const rva_yolov8_plan *plan, int index);
 
 /* ----------------------------------------------------------------------------------------------
+ * The CNN-LSTM clip network as ONE fp32 object -- replaces the network call of the reference's CNN-LSTM head
+ * (the inference call of CNNLSTMDetector._predict_sequence, temporal_detector.py:382-388; the network is
+ * DummyCNNLSTM of scripts/convert_temporal_model_to_onnx.py:34-88) and its top-5 (temporal_detector.py:392-424), for `half:
+ * false`.  Per frame: Conv2d(3,64,7,s2,p3)+BN+ReLU -> MaxPool(3,s2,p1) -> Conv2d(64,128,3,p1)+BN+ReLU -> mean over H,W; per
+ * clip: 2-layer LSTM(128 -> hidden, gates i,f,g,o) -> Linear(hidden -> classes) on the last step.
+ *
+ * rva_cnnlstm_plan_create: `weights` = the module's tensors in the field order of rva_cnnlstm_weights as fp32 host arrays (all
+ *   required): conv1 weight [64][3][7][7] and bias [64], conv2 weight [128][64][3][3] and bias [128], each with its BatchNorm folded in; LSTM layer 1
+ *   weight_ih [4h][128], bias_ih + bias_hh [4h], weight_hh [4h][h]; layer 2 weight_ih [4h][h], weight_hh [4h][h], bias_ih +
+ *   bias_hh [4h]; head weight [classes][h] and bias [classes] (gate rows in PyTorch's order i, f, g, o).  The plan copies and
+ *   packs them, and allocates its whole workspace for desc.max_clips clips (frames 1..64, hidden 1..1024, classes 1..16384).
+ * rva_cnnlstm_plan_run: frames = a device ring of planar fp32 frames [3][height][width] (what rva_preprocess_frames_* writes
+ *   with RVA_NORM_IMAGENET_F32); frame_index = device int32 [n_clips * frames]: frame t of clip b is ring + frame_index[b*T+t] *
+ *   3*height*width (no gathered copy).  logits = device fp32 [n_clips][classes], the raw outputs (no softmax).  Every launch
+ *   goes to `stream`; no host synchronisation, no allocation: capturable.  Each sum runs in one fixed order (no split-K that
+ *   follows the grid, no atomics): a clip's logits are bit-identical for every batch size, position in the batch and launch
+ *   mode.
+ * rva_cnnlstm_plan_run_post: one result row per stream of the tick.  rows = device int32 [n_rows][3]: (clip of the row or -1,
+ *   frame width, frame height).  A row with a clip gets the top k = min(5, classes) of its logits in the reference's order
+ *   (ascending stable sort, last k reversed: exact ties rank the larger class index first, NaN ranks above every number as in torch.sort) in scores[row][0..k) / cls, boxes
+ *   (0, 0, w, h) and counts[row] = k; a row without one gets counts[row] = 0.  scores / boxes / cls have row stride max_det
+ *   (>= k) as in the post-process buffers of rva_postprocess_batch.
+ * rva_cnnlstm_plan_info: pooled map size (height / width after the max pool), conv2 tiles per frame, launches per _run.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_cnnlstm_plan rva_cnnlstm_plan;
+typedef struct rva_cnnlstm_desc {
+    int32_t height, width;            /* frame size of the clip (224 x 224 by default) */
+    int32_t frames;                   /* T = sequence_length */
+    int32_t hidden, classes;
+    int32_t max_clips;                /* capacity: the most clips one _run may take */
+} rva_cnnlstm_desc;
+typedef struct rva_cnnlstm_weights {
+    const float *conv1_w, *conv1_b, *conv2_w, *conv2_b;
+    const float *w_ih1, *b1, *w_hh1;
+    const float *w_ih2, *w_hh2, *b2;
+    const float *head_w, *head_b;
+} rva_cnnlstm_weights;
+int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rva_cnnlstm_weights *weights, rva_cnnlstm_plan **out);
+void rva_cnnlstm_plan_destroy(rva_cnnlstm_plan *plan);
+int rva_cnnlstm_plan_info(const rva_cnnlstm_plan *plan, int32_t *pooled_h, int32_t *pooled_w, int32_t *conv2_tiles,
+                          int32_t *n_launches);
+int rva_cnnlstm_plan_run(rva_cnnlstm_plan *plan, const void *frames, const int32_t *frame_index, int n_clips, void *logits,
+                         rva_stream_t stream);
+int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                              void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)
  * for a tick of NV12 surfaces: gray -> 5x5 Gaussian -> |diff| against prev_blur[i] -> counts[i] = number of
  * pixels with diff > 25 (device int32[n]; -1 where prev_blur[i] is NULL = first frame of that stream).

@@ -18,7 +18,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
-SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip",
+SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip", "rva_clip.hip",
            "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -53,6 +53,18 @@ class ConvWeights(C.Structure):
     """``rva_conv_weights`` (include/rva.h): one convolution in the checkpoint's own fp32 layout."""
     _fields_ = [("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("cout", C.c_int32), ("cin", C.c_int32),
                 ("k", C.c_int32), ("stride", C.c_int32)]
+
+
+class CnnLstmDesc(C.Structure):
+    """``rva_cnnlstm_desc`` (include/rva.h)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("frames", C.c_int32), ("hidden", C.c_int32), ("classes", C.c_int32),
+                ("max_clips", C.c_int32)]
+
+
+class CnnLstmWeights(C.Structure):
+    """``rva_cnnlstm_weights`` (include/rva.h): the module's tensors in module order, BatchNorm folded, LSTM biases summed."""
+    NAMES = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "w_ih1", "b1", "w_hh1", "w_ih2", "w_hh2", "b2", "head_w", "head_b")
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
 
 
 RVA_PLAN_NO_STEM2 = 1
@@ -195,6 +207,11 @@ def lib() -> C.CDLL:
         "rva_yolov8_plan_launch_tunable": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
         "rva_yolov8_plan_set_variant": (C.c_int, [_P, C.c_int, C.c_int]),
         "rva_yolov8_plan_get_variant": (C.c_int, [_P, C.c_int]),
+        "rva_cnnlstm_plan_create": (C.c_int, [_P, C.POINTER(CnnLstmDesc), C.POINTER(CnnLstmWeights), C.POINTER(_P)]),
+        "rva_cnnlstm_plan_destroy": (None, [_P]),
+        "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
+        "rva_cnnlstm_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+        "rva_cnnlstm_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -225,7 +242,8 @@ EXPORTS = [
     "rva_yolo_head_f32",
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
-    "rva_yolov8_plan_get_variant", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
+    "rva_cnnlstm_plan_run_post", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
 ]
 
 

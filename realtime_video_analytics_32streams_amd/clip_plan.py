@@ -1,0 +1,177 @@
+"""fp32 CNN-LSTM clip plan: a thin caller of ``rva_cnnlstm_plan_*`` (include/rva.h, kernels in ``csrc/rva_clip.hip``).
+
+The whole clip network of :class:`temporal.CnnLstmNet` -- conv stem with its max pool, conv2 with the spatial mean, the
+2-layer LSTM, the linear head -- and the top-5 of the CNN-LSTM head run as librva kernels that read the clip frames straight
+from the detector's HBM ring through a device table of frame indices.  What stays here:
+
+  * :func:`pack_cnn_lstm`: the module's tensors in the ABI's order, BatchNorm folded and the two LSTM biases summed in
+    float64, each rounded once to fp32;
+  * :func:`clip_engine`: which engine a temporal head runs (``hip_engine: plan`` selects this plan for ``cnn_lstm`` with
+    ``half: false``);
+  * :func:`clip_flops`: the FLOP / byte count of one clip (tools/clip_plan_report.py);
+  * :class:`FusedCnnLstm`: owns one plan (weights and the workspace for ``max_clips`` clips) and its logits buffer.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import logging
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as N
+from . import ops
+
+LOGGER = logging.getLogger(__name__)
+
+ENGINE = "clip-f32"          # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
+
+
+def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False) -> str:
+    """Engine of a temporal head: ``"infer_fn"`` (a caller's function overrides everything), ``"clip-f32"`` (``cnn_lstm``,
+    ``half: false``, ``hip_engine: plan``) or ``"torch"``.  ``half: true`` with ``plan`` on ``cnn_lstm`` raises (the plan is fp32
+    only); the other temporal heads have no plan and keep torch with a warning, so a configuration never changes engines
+    silently."""
+    if has_infer_fn:
+        return "infer_fn"
+    if hip_engine != "plan":
+        return "torch"
+    if model_type == "cnn_lstm":
+        if half:
+            raise ValueError("hip_engine: plan runs the CNN-LSTM head as an fp32 plan only; set half: false "
+                             "(or hip_engine: auto for the PyTorch fp16 network)")
+        return ENGINE
+    LOGGER.warning("hip_engine: plan has no hand-written plan for model_type %r: the network runs through PyTorch-ROCm",
+                   model_type)
+    return "torch"
+
+
+def conv_out(n: int, k: int, s: int, p: int) -> int:
+    return (n + 2 * p - k) // s + 1
+
+
+def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 400) -> Dict[str, float]:
+    """FLOP (multiply + add = 2) and the bytes a clip's network must at least move, from the shapes alone."""
+    hc, wc = conv_out(h, 7, 2, 3), conv_out(w, 7, 2, 3)
+    hp, wp = conv_out(hc, 3, 2, 1), conv_out(wc, 3, 2, 1)
+    conv1 = 2.0 * hc * wc * 64 * 3 * 49
+    conv2 = 2.0 * hp * wp * 128 * 64 * 9
+    g4 = 4 * hidden
+    lstm = 2.0 * frames * (g4 * 128 + g4 * hidden + g4 * 2 * hidden)
+    head = 2.0 * hidden * classes
+    weights = 4.0 * (64 * 147 + 64 + 128 * 576 + 128 + g4 * (128 + 3 * hidden + 2) + classes * (hidden + 1))
+    return {"conv1_per_frame": conv1, "conv2_per_frame": conv2, "frame": conv1 + conv2, "lstm": lstm, "head": head,
+            "clip": frames * (conv1 + conv2) + lstm + head, "frame_bytes": 4.0 * 3 * h * w, "weight_bytes": weights,
+            "lstm_weight_bytes_per_step": 4.0 * g4 * 3 * hidden}
+
+
+def _fold(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d) -> Tuple[np.ndarray, np.ndarray]:
+    w = conv.weight.detach().double().cpu()
+    b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64)
+    scale = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
+    wf = w * scale[:, None, None, None]
+    bf = (b - bn.running_mean.detach().double().cpu()) * scale + bn.bias.detach().double().cpu()
+    return wf.float().numpy(), bf.float().numpy()
+
+
+def pack_cnn_lstm(net) -> Dict[str, np.ndarray]:
+    """The ``rva_cnnlstm_weights`` arrays of a :class:`temporal.CnnLstmNet` (``N.CnnLstmWeights.NAMES`` order), contiguous fp32."""
+    st, rnn = net.stem, net.rnn
+    if not (isinstance(st[0], torch.nn.Conv2d) and st[0].out_channels == 64 and st[0].kernel_size == (7, 7) and
+            isinstance(st[4], torch.nn.Conv2d) and st[4].out_channels == 128 and rnn.num_layers == 2 and rnn.input_size == 128
+            and rnn.batch_first and not rnn.bidirectional and rnn.proj_size == 0):
+        raise ValueError("pack_cnn_lstm: not the CnnLstmNet architecture")
+    p = {n: t.detach().double().cpu() for n, t in rnn.named_parameters()}
+    c1w, c1b = _fold(st[0], st[1])
+    c2w, c2b = _fold(st[4], st[5])
+    f32 = lambda t: np.ascontiguousarray(t.float().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)  # noqa: E731
+    out = {"conv1_w": c1w, "conv1_b": c1b, "conv2_w": c2w, "conv2_b": c2b,
+           "w_ih1": p["weight_ih_l0"], "b1": p["bias_ih_l0"] + p["bias_hh_l0"], "w_hh1": p["weight_hh_l0"],
+           "w_ih2": p["weight_ih_l1"], "w_hh2": p["weight_hh_l1"], "b2": p["bias_ih_l1"] + p["bias_hh_l1"],
+           "head_w": net.head.weight.detach().double().cpu(), "head_b": net.head.bias.detach().double().cpu()}
+    return {n: f32(out[n]) for n in N.CnnLstmWeights.NAMES}
+
+
+class FusedCnnLstm:
+    """One ``rva_cnnlstm_plan``: the fp32 clip network of ``net`` for clips of ``frames`` frames at ``hw``, up to ``max_clips``
+    clips per call.  No host synchronisation and no allocation after construction (capturable)."""
+
+    def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
+                 device: Optional[torch.device] = None):
+        self.ctx = ctx or ops.context()
+        self.dev = device or torch.device("cuda", self.ctx.device)
+        self.H, self.W, self.T, self.max_clips = int(hw[0]), int(hw[1]), int(frames), int(max_clips)
+        self.hidden, self.classes = int(net.rnn.hidden_size), int(net.head.out_features)
+        self.L = N.lib()
+        packed = pack_cnn_lstm(net)
+        wt = N.CnnLstmWeights(*[packed[n].ctypes.data_as(C.POINTER(C.c_float)) for n in N.CnnLstmWeights.NAMES])
+        d = N.CnnLstmDesc(self.H, self.W, self.T, self.hidden, self.classes, self.max_clips)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            self.ctx.check(self.L.rva_cnnlstm_plan_create(self.ctx.handle, C.byref(d), C.byref(wt), C.byref(h)),
+                           "rva_cnnlstm_plan_create")
+        self.handle = h
+        del packed
+        info = [C.c_int32() for _ in range(4)]
+        self.ctx.check(self.L.rva_cnnlstm_plan_info(h, *[C.byref(v) for v in info]), "rva_cnnlstm_plan_info")
+        self.pooled_hw = (info[0].value, info[1].value)
+        self.conv2_tiles, self.n_launches = info[2].value, info[3].value
+        self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
+        self._iota: Optional[torch.Tensor] = None
+
+    def __del__(self):  # best effort
+        try:
+            if getattr(self, "handle", None):
+                self.L.rva_cnnlstm_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:  # noqa: BLE001
+            pass
+
+    def run(self, ring: torch.Tensor, frame_index: torch.Tensor, n_clips: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Logits ``[n_clips, classes]`` of the clips whose frame t of clip b is ``ring.view(-1, 3, H, W)[frame_index[b * T + t]]``,
+        launched on the current stream: a view of ``out`` (contiguous fp32 ``[>= n_clips, classes]`` on the device) or of the
+        plan's own buffer."""
+        if ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous() or ring.numel() % (3 * self.H * self.W):
+            raise ValueError(f"ring must be a contiguous fp32 device tensor of [*, 3, {self.H}, {self.W}] frames")
+        if frame_index.dtype != torch.int32 or not frame_index.is_cuda or frame_index.numel() < n_clips * self.T:
+            raise ValueError("frame_index must be a device int32 tensor of n_clips * T frame indices")
+        if not 1 <= n_clips <= self.max_clips:
+            raise ValueError(f"n_clips must be in 1..{self.max_clips}, got {n_clips}")
+        out = self.logits if out is None else out
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or \
+                out.shape[1] != self.classes or out.shape[0] < n_clips:
+            raise ValueError(f"out must be a contiguous fp32 device tensor of [>= {n_clips}, {self.classes}]")
+        self.ctx.check(self.L.rva_cnnlstm_plan_run(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()),
+                                                   int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()),
+                       "rva_cnnlstm_plan_run")
+        return out[:n_clips]
+
+    def __call__(self, clips: torch.Tensor) -> torch.Tensor:
+        """``CnnLstmNet.forward`` of contiguous clips ``[B, T, 3, H, W]`` fp32: a fresh ``[B, classes]`` tensor."""
+        b = int(clips.shape[0])
+        if tuple(clips.shape[1:]) != (self.T, 3, self.H, self.W):
+            raise ValueError(f"clips must be [B, {self.T}, 3, {self.H}, {self.W}], got {tuple(clips.shape)}")
+        if self._iota is None:
+            self._iota = torch.arange(self.max_clips * self.T, dtype=torch.int32, device=self.dev)
+        return self.run(clips.contiguous(), self._iota, b).clone()
+
+    def post(self, logits: torch.Tensor, rows: torch.Tensor, n_rows: int, post: ops.PostBuffers) -> ops.PostBuffers:
+        """Top-k result rows into ``post``: ``rows`` = device int32 ``[n_rows, 3]`` of (clip or -1, width, height)."""
+        self.ctx.check(self.L.rva_cnnlstm_plan_run_post(self.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                        int(n_rows), int(post.max_det), C.c_void_p(post.scores.data_ptr()),
+                                                        C.c_void_p(post.cls.data_ptr()), C.c_void_p(post.boxes.data_ptr()),
+                                                        C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
+                       "rva_cnnlstm_plan_run_post")
+        return post
+
+
+def fired_tables(fired: Sequence, cols: Sequence[int], ring_columns: int, rows: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Host tables of one tick: frame indices into ``ring.view(-1, 3, H, W)`` (clip-major) and the ``[rows, 3]`` result-row
+    table (clip or -1, width, height).  ``fired``: ``(row, ring slots of the clip, (h, w))`` as ``stage_pre`` lists them."""
+    idx = np.array([sl * ring_columns + cols[row] for row, slots, _ in fired for sl in slots], dtype=np.int32)
+    tab = np.zeros((rows, 3), dtype=np.int32)
+    tab[:, 0] = -1
+    for clip, (row, _, hw) in enumerate(fired):
+        tab[row] = (clip, hw[1], hw[0])
+    return idx, tab

@@ -9,9 +9,12 @@ Compatibility rules kept from the reference:
     accepted and carried, so a reference YAML loads unchanged.
 Additions: backend ``"hip"`` (this library) is a valid detector backend, and the out-of-scope
 sections (kafka / prometheus / ffmpeg_simulator) are kept as opaque dicts.  With backend ``"hip"``, the
-detector key ``hip_engine`` picks the YOLO network's engine: ``"auto"`` (default; what a reference YAML gets)
-= the hand-written fp16 plan for ``half: true`` and PyTorch-ROCm for ``half: false``; ``"plan"`` = the
-hand-written plan at the configured precision, i.e. the fp32 plan for ``half: false``.
+detector key ``hip_engine`` picks the network's engine: ``"auto"`` (default; what a reference YAML gets)
+= the hand-written fp16 plan for YOLO with ``half: true``, PyTorch-ROCm for YOLO with ``half: false`` and for
+every temporal head; ``"plan"`` = the hand-written plan at the configured precision, i.e. the fp32 YOLO plan for
+``half: false`` and, for ``model_type: cnn_lstm``, the fp32 clip plan (``half: false`` only: ``half: true`` is
+refused at construction).  The other temporal heads have no plan: with ``"plan"`` they keep PyTorch-ROCm and log
+a warning.
 """
 from __future__ import annotations
 
@@ -96,7 +99,7 @@ class DetectorConfig:
     temporal_pooling: str = "avg"
     action_classes: Optional[List[str]] = None
     num_action_classes: int = 400
-    hip_engine: str = "auto"                # backend "hip", YOLO: "auto" or "plan" (module docstring)
+    hip_engine: str = "auto"                # backend "hip", YOLO and cnn_lstm: "auto" or "plan" (module docstring)
 
     def validate(self) -> None:
         _need(bool(self.model_path), "Detector model_path must not be empty")

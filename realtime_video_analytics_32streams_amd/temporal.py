@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import _native as N
 from . import ops
+from .clip_plan import ENGINE as CLIP_PLAN, FusedCnnLstm, clip_engine, fired_tables
 from .config import DetectorConfig
 from .detector import Detection
 from .video_stream import FramePacket
@@ -88,6 +89,18 @@ class _ClipTick:
     cols: List[int]                             # ring column of every row
     infos: Dict[str, ClipInfo]
     slot: int                                   # pipeline slot (tick parity) whose buffers this tick uses
+    rows_table: Optional[torch.Tensor] = None   # clip plan: device [rows, 3] (clip or -1, w, h) uploaded by stage_net
+
+
+class _PlanSlot:
+    """One tick slot's clip plan and its two buffer sets (logits, pinned host tables, device tables, upload event)."""
+
+    def __init__(self, plan: FusedCnnLstm, rows_cap: int, device):
+        self.plan, self.rows_cap, self.turn = plan, rows_cap, 0
+        n = plan.max_clips * plan.T + 3 * rows_cap
+        self.sets = [(torch.empty((plan.max_clips, plan.classes), dtype=torch.float32, device=device),
+                      torch.empty(n, dtype=torch.int32, pin_memory=True), torch.empty(n, dtype=torch.int32, device=device),
+                      torch.cuda.Event()) for _ in range(2)]
 
 
 class CnnLstmNet(nn.Module):
@@ -153,6 +166,8 @@ class _HipTemporalDetector:
         self.sequence_step = self.sched.step
         self.half = bool(config.half)
         self._infer_fn = infer_fn
+        # "torch", "infer_fn" or "clip-f32" (hip_engine: plan, cnn_lstm, half: false): clip_plan.clip_engine
+        self.engine = clip_engine(config.model_type, self.half, getattr(config, "hip_engine", "auto"), infer_fn is not None)
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -172,6 +187,8 @@ class _HipTemporalDetector:
         self._bbuf: Dict[str, Deque] = {}      # per stream: (frame_id, ring slot, (h, w)) of the buffered frames
         self._bring: Optional[torch.Tensor] = None
         self._post: Dict[tuple, ops.PostBuffers] = {}
+        self._plans: Dict[int, _PlanSlot] = {}  # clip plan per tick slot, with two buffer sets used alternately
+        self._seq_plan: Optional[FusedCnnLstm] = None   # clip plan of the single-stream predict path
         self.two_chain_ok = True               # PipelinedTicks may run consecutive ticks as two chains on two streams
 
     # -- per-head hooks ---------------------------------------------------------------------------
@@ -281,12 +298,16 @@ class _HipTemporalDetector:
             if clip is not None:
                 fired.append((row, [c[1] for c in clip], clip[0][2]))
                 infos[n] = ClipInfo(clip[0][0], clip[-1][0], self.config.action_classes, min(5, self.config.num_action_classes))
+        if self.engine == CLIP_PLAN and self._slot not in self._plans:
+            self._plan_slot(self._slot, 0, len(packets))     # built on the slot's first tick, before any clip can fire
         return _ClipTick(len(packets), fired, cols, infos, self._slot)
 
     def stage_net(self, pre: _ClipTick) -> Optional[torch.Tensor]:
         """The clips that fired this tick as ONE network batch: ``[n_fired, classes]`` raw outputs (no softmax)."""
         if not pre.fired:
             return None
+        if self.engine == CLIP_PLAN:
+            return self._plan_net(pre)
         C_ = self._bring.shape[1]
         flat = self._bring.view(-1, 3, *self.input_hw)
         idx = torch.tensor([[sl * C_ + pre.cols[row] for sl in slots] for row, slots, _ in pre.fired], device=self.device)
@@ -305,6 +326,8 @@ class _HipTemporalDetector:
         post = self._post.get(key)
         if post is None:
             post = self._post[key] = ops.PostBuffers.allocate(pre.rows, 8, self.device)
+        if raw is not None and self.engine == CLIP_PLAN:
+            return self._plans[pre.slot].plan.post(raw, pre.rows_table, pre.rows, post)
         post.counts.zero_()
         if raw is not None:
             k = min(5, raw.shape[1])
@@ -322,12 +345,49 @@ class _HipTemporalDetector:
         self.last_clip_infos = pre.infos
         return self.stage_post(self.stage_net(pre), pre)
 
+    # -- clip plan (engine "clip-f32") --------------------------------------------------------------------------------------
+    def _plan_slot(self, slot: int, n_clips: int, rows: int) -> "_PlanSlot":
+        """The plan of a tick slot, sized for every ring column; rebuilt (after a device drain) only if a stream shows up
+        that was not announced and more clips or rows than that ever appear."""
+        ps = self._plans.get(slot)
+        if ps is None or ps.plan.max_clips < n_clips or ps.rows_cap < rows:
+            if ps is not None:
+                torch.cuda.synchronize(self.device)          # the old buffers may still be read by a tail in flight
+            cap = max(n_clips, rows, len(self._col), 1)
+            plan = FusedCnnLstm(self.net, self.input_hw, self.sched.L, cap, ctx=self.ctx, device=self.device)
+            ps = self._plans[slot] = _PlanSlot(plan, cap, self.device)
+        return ps
+
+    def _plan_net(self, pre: _ClipTick) -> torch.Tensor:
+        """The tick's clips through the slot's plan.  The logits and the device tables go to the slot's NEXT buffer set:
+        the tail of the previous tick that used this slot may still be reading the other set (with one network stream every
+        tick uses slot 0 and the tail of tick k-1 runs beside the network of tick k), while the tick two uses back has
+        finished its tail before this tick's network starts (PipelinedTicks orders it so)."""
+        ps = self._plan_slot(pre.slot, len(pre.fired), pre.rows)
+        idx, tab = fired_tables(pre.fired, pre.cols, self._bring.shape[1], pre.rows)
+        logits, host, dev, ev = ps.sets[ps.turn]
+        ps.turn ^= 1
+        n = idx.size + tab.size
+        ev.synchronize()                       # this set's previous upload has left the pinned staging buffer
+        host.numpy()[:idx.size] = idx
+        host.numpy()[idx.size:n] = tab.ravel()
+        dev[:n].copy_(host[:n], non_blocking=True)
+        ev.record()
+        pre.rows_table = dev[idx.size:n]
+        return ps.plan.run(self._bring, dev[:idx.size], len(pre.fired), out=logits)
+
     def _predict_sequence(self, name: str, ring: torch.Tensor, clip) -> List[Detection]:
-        idx = torch.tensor([c[1] for c in clip], device=self.device)
-        x = ring.index_select(0, idx)                                   # [T,3,H,W]
-        x = (x.permute(1, 0, 2, 3).contiguous() if self.CLIP_LAYOUT == "CTHW" else x).unsqueeze(0)
-        with torch.inference_mode():
-            raw = self._infer_fn(x) if self._infer_fn is not None else self.net(x)
+        if self.engine == CLIP_PLAN:
+            idx = torch.tensor([c[1] for c in clip], dtype=torch.int32, device=self.device)
+            if self._seq_plan is None:
+                self._seq_plan = FusedCnnLstm(self.net, self.input_hw, self.sched.L, 1, ctx=self.ctx, device=self.device)
+            raw = self._seq_plan.run(ring, idx, 1)
+        else:
+            idx = torch.tensor([c[1] for c in clip], device=self.device)
+            x = ring.index_select(0, idx)                                   # [T,3,H,W]
+            x = (x.permute(1, 0, 2, 3).contiguous() if self.CLIP_LAYOUT == "CTHW" else x).unsqueeze(0)
+            with torch.inference_mode():
+                raw = self._infer_fn(x) if self._infer_fn is not None else self.net(x)
         out = raw.float().flatten().cpu().numpy()
         top_k = min(5, len(out))
         order = np.argsort(out, kind="stable")[-top_k:][::-1]     # temporal_detector.py:396-398
@@ -347,7 +407,9 @@ class _HipTemporalDetector:
 
 
 class HipCNNLSTMDetector(_HipTemporalDetector):
-    """CNN-LSTM head (temporal_detector.py:150-426): float32 ImageNet normalisation, clips ``[1,T,3,H,W]``."""
+    """CNN-LSTM head (temporal_detector.py:150-426): float32 ImageNet normalisation, clips ``[1,T,3,H,W]``.  With ``half: false``
+    and ``hip_engine: plan`` the network and its top-5 run as the hand-written fp32 clip plan (engine ``"clip-f32"``,
+    clip_plan.FusedCnnLstm), reading the clip frames straight from the frame ring; ``half: true`` with ``plan`` is refused."""
 
     def _default_net(self) -> nn.Module:
         return CnnLstmNet(self.config.num_action_classes)
