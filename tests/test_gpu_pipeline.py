@@ -49,9 +49,10 @@ def _tab(tracks):
 
 
 @pytest.mark.parametrize("depth", [2, 4])
-def test_bench_configuration_end_to_end_against_the_oracle(depth):
+def test_bench_configuration_end_to_end_against_the_oracle(depth, monkeypatch):
     """BASELINE configs[2] as bench.py runs it (32 x 1080p, YOLOv8s fused plan, tick chains on probed streams -- four by default,
-    two as the sharded runs use --, hipGraph tails), 12 ticks."""
+    two as the sharded runs use --, hipGraph tails), 12 ticks.  Each tick's input tensor is the oracle pre-process of the
+    surfaces the sources delivered, and every tick after a slot's first ran the steady-state (content-only) K1."""
     S, T = 32, 12
     streams = [StreamConfig(name=f"cam{i:03d}", url="synthetic://1920x1080", warmup_seconds=0.0) for i in range(S)]
     srcs = [SyntheticNv12Stream(s, index=i, n_unique=3) for i, s in enumerate(streams)]
@@ -64,11 +65,38 @@ def test_bench_configuration_end_to_end_against_the_oracle(depth):
     assert runner.net_streams == depth
     otr = orc.Tracker(S, tcfg.max_age, tcfg.max_iou_distance, tcfg.min_hits)
     checked = 0
+    delivered = [[] for _ in range(S)]                             # ring index of the surface each source delivered, per tick
+    for s, src in enumerate(srcs):
+        def deliver(s=s, src=src, real=src.next_packet):
+            p = real()
+            delivered[s].append(next(j for j, f in enumerate(src._ring) if f is p.frame))
+            return p
+        monkeypatch.setattr(src, "next_packet", deliver)
+    k1_content = []                                                # content_only of every K1 call, in tick order
+    real_k1 = ops.preprocess_nv12
+
+    def k1_spy(*a, **kw):
+        k1_content.append(bool(kw.get("content_only", False)))
+        return real_k1(*a, **kw)
+    monkeypatch.setattr(ops, "preprocess_nv12", k1_spy)
+    want_k1 = {}                                                   # (stream, ring index) -> oracle bits
+
+    def oracle_k1(s, j):
+        if (s, j) not in want_k1:
+            f = srcs[s]._ring[j]
+            want_k1[(s, j)] = orc.preprocess_nv12(f.y.cpu().numpy(), f.uv.cpu().numpy(), 1920, 1080, 640, 640, True)[0].view(np.uint16)
+        return want_k1[(s, j)]
 
     def check(k):
         nonlocal checked
         _, tables = runner.collect()
         par = k % runner.nslots                                    # every slot runs on its own plan, head tensor 0 of that plan:
+        # the slot's input tensor: written by tick k's K1, not again before tick k + nslots (not submitted yet: nslots == depth)
+        assert runner.nslots == runner.depth and len(k1_content) == runner._next
+        x = det._in_bufs[S if par == 0 else (S, par)].cpu().numpy().view(np.uint16)
+        for s in range(S):
+            assert np.array_equal(x[s], oracle_k1(s, delivered[s][k])), ("K1 input tensor", k, s)
+        assert k1_content[k] == (k >= runner.nslots), ("steady-state K1 after the slot's first tick", k, k1_content)
         head = det._plans[(S, 640, 640) if par == 0 else (S, 640, 640, par)]._outs[0].float().cpu().numpy()   # intact until tick k + depth's network
         for s in range(S):                                         # canonical order: tick-major, stream-minor
             r = orc.postprocess(head[s], det.config.confidence_threshold, det.config.iou_threshold, None, (1920, 1080))
