@@ -157,6 +157,17 @@ int rva_postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtype, int batc
                           int32_t *out_counts, int32_t *out_ncand, rva_stream_t stream);
 
 /* Host-synchronous: bit 0 = max_det overflow, bit 1 = candidate capacity overflow since the last call. */
+/* The same post-process with the boxes taken from an fp32 side tensor (split mode of the fp16 plan, RVA_PLAN_BOX_F32): raw is
+ * [batch, channels, anchors] only (channels >= 5, channels < anchors; float16 or float32), boxes is device float
+ * [batch, 4, anchors] = cx, cy, w, h in input pixels.  Rows 0-3 of raw are never read; scores, the class-shift quirk, thresholds,
+ * class filter, letterbox undo, division and clipping are the code of rva_postprocess_batch, as are K3 and all outputs.  K2 reads
+ * channels x anchors x 2 B + 4 x anchors x 4 B per image (84 x 8400: +9.5 % over the fp16 head alone). */
+int rva_postprocess_boxes_batch(rva_ctx *ctx, const void *raw, int raw_dtype, const float *boxes, int batch, int channels,
+                                int anchors, double conf_thr, double iou_thr, const int32_t *classes, int n_classes,
+                                const rva_letterbox *metas, int n_metas, int max_det, float *out_boxes, float *out_scores,
+                                int32_t *out_cls, int32_t *out_anchor, int32_t *out_cand, int32_t *out_counts,
+                                int32_t *out_ncand, rva_stream_t stream);
+
 int rva_post_status(rva_ctx *ctx, rva_stream_t stream, int *flags);
 
 /* Host-synchronous diagnostic: the number of images since the last call whose NMS scanned the kept list through the centre-bin
@@ -322,6 +333,13 @@ int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, 
 int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch,
                          int H, int W, int Cin, int Cout, int mode, void *out, int nc, int anchors_total,
                          int anchor_offset, float stride_px, int variant, rva_stream_t stream);
+/* The box branch (mode 1, Cout = 64) of rva_conv1x1_head_f16 with the fp32 side tensor: out is written exactly as
+ * rva_conv1x1_head_f16 writes it (rows 0-3 bit-identical), and boxes32[batch, 4, anchors_total] (device float, anchor axis
+ * contiguous, same anchor_offset) receives the fp32 values that were rounded into those rows: (half)boxes32 == rows 0-3 bit for
+ * bit.  Nothing outside [anchor_offset, anchor_offset + H*W) is written in either tensor. */
+int rva_conv1x1_head_box32_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch,
+                               int H, int W, int Cin, void *out, float *boxes32, int nc, int anchors_total, int anchor_offset,
+                               float stride_px, int variant, rva_stream_t stream);
 int rva_stem_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias,
                       void *out, int ldo, int batch, int H, int W, int Cout, rva_stream_t stream);
 
@@ -359,6 +377,15 @@ int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void 
 int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
                        const int32_t *ldc, void *out, int batch, const int32_t *h, const int32_t *w, int nc,
                        int anchors_total, const float *strides, rva_stream_t stream);
+/* rva_yolo_head_f16 / rva_yolo_head3_f16 with the fp32 side tensor boxes32[batch, 4, anchors_total] of the box rows (same contract
+ * as rva_conv1x1_head_box32_f16: out bit-identical to the plain call, (half)boxes32 == rows 0-3, nothing outside the levels'
+ * anchor ranges written). */
+int rva_yolo_head_box32_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out,
+                            float *boxes32, int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride,
+                            rva_stream_t stream);
+int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                             const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
+                             int anchors_total, const float *strides, rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * fp32 detector primitives (NHWC float32) -- the reference's default precision (`half: false`: an fp32
@@ -417,11 +444,19 @@ int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void 
  *   stem launch, one convolution launch per Conv-BN-SiLU, three pool launches for SPPF, upsample launches into the concat
  *   buffers, one head launch per level on the level's detect lane); the tunable steps carry rva_conv2d_nhwc_f32_v variants, and
  *   the output does not depend on them at all (bit-identical).  RVA_PLAN_NO_STEM2 / NO_CIN_PAD / NO_PAIR32 have no effect on it.
+ * RVA_PLAN_BOX_F32 (fp16 plans only, opt-in): the fp16 head's box rows carry the fp16 ulp (0.25 px between 256 and 512, 0.5 px
+ *   above) although DFL + dist2bbox are computed in fp32.  With the flag the head kernels store those fp32 values as well:
+ *   `output` of every run entry point is then ONE buffer of rva_yolov8_plan_output_layout's total_bytes -- the fp16 head
+ *   [batch, 4+nc, anchors], written in full and bit-identical to the plan without the flag, followed at boxes_offset (a
+ *   multiple of 256) by float boxes32[batch, 4, anchors] = cx, cy, w, h in input pixels, with (half)boxes32 == rows 0-3.  Feed
+ *   both to rva_postprocess_boxes_batch.  Same launches, same kernel selection, still no allocation and no synchronisation.
+ *   Without the flag boxes_offset is -1 and total_bytes is the size of the head tensor.
  * -------------------------------------------------------------------------------------------- */
 #define RVA_PLAN_NO_STEM2 1   /* rva_yolov8_desc.flags: stem and first downsampling convolution as two launches (A/B switch) */
 #define RVA_PLAN_NO_CIN_PAD 2 /* ... convolutions with Cin % 32 != 0 keep their Cin (default: declared rounded up to 32, zero weights) */
 #define RVA_PLAN_NO_PAIR32 4  /* ... the 32-channel C2f bottlenecks (YOLOv8s at 160 x 160) as two convolution launches instead of rva_c2f_pair32_f16 */
 #define RVA_PLAN_F32 8        /* ... fp32 plan: fp32 input, buffers, weights and output (every convolution's Cin % 16 == 0) */
+#define RVA_PLAN_BOX_F32 16   /* ... fp16 plan whose head kernels also write the four box rows as fp32 (see RVA_PLAN_BOX_F32 above); RVA_ERR_ARG with RVA_PLAN_F32 */
 typedef struct rva_yolov8_plan rva_yolov8_plan;
 typedef struct rva_yolov8_desc {
     int32_t batch, height, width;     /* input tensor; height and width multiples of 32 */
@@ -441,6 +476,7 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
 void rva_yolov8_plan_destroy(rva_yolov8_plan *plan);
 int rva_yolov8_plan_info(const rva_yolov8_plan *plan, int32_t *anchors, int32_t *out_rows, int32_t *n_steps, int32_t *n_tunable,
                          int32_t *quiet_step);
+int rva_yolov8_plan_output_layout(const rva_yolov8_plan *plan, int64_t *total_bytes, int64_t *boxes_offset);
 int rva_yolov8_plan_run(rva_yolov8_plan *plan, const void *input, void *output, rva_stream_t stream);
 int rva_yolov8_plan_run_lanes(rva_yolov8_plan *plan, const void *input, void *output, rva_stream_t stream, rva_stream_t side1,
                               rva_stream_t side2);

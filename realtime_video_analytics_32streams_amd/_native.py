@@ -71,6 +71,7 @@ RVA_PLAN_NO_STEM2 = 1
 RVA_PLAN_NO_CIN_PAD = 2
 RVA_PLAN_NO_PAIR32 = 4
 RVA_PLAN_F32 = 8
+RVA_PLAN_BOX_F32 = 16
 
 
 def _stale() -> bool:
@@ -141,6 +142,9 @@ def lib() -> C.CDLL:
         "rva_postprocess_batch": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, i32p,
                                             C.c_int, C.POINTER(Letterbox), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
                                             _P]),
+        "rva_postprocess_boxes_batch": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, i32p,
+                                                  C.c_int, C.POINTER(Letterbox), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                                  _P]),
         "rva_post_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
         "rva_post_filter_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
         "rva_tracker_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(_P)]),
@@ -182,6 +186,12 @@ def lib() -> C.CDLL:
         "rva_c2f_pair32_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
         "rva_conv1x1_head_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int,
                                            C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+        "rva_conv1x1_head_box32_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int,
+                                                 C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+        "rva_yolo_head_box32_f16": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_float, _P]),
+        "rva_yolo_head3_box32_f16": (C.c_int, [_P, pp, i32p, pp, i32p, _P, _P, C.c_int, i32p, i32p, C.c_int, C.c_int,
+                                               C.POINTER(C.c_float), _P]),
         "rva_conv1x1_upcat_f16": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_int, _P]),
         "rva_yolo_head3_f16": (C.c_int, [_P, pp, i32p, pp, i32p, _P, C.c_int, i32p, i32p, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
@@ -200,6 +210,7 @@ def lib() -> C.CDLL:
         "rva_yolov8_plan_create": (C.c_int, [_P, C.POINTER(YoloV8Desc), C.POINTER(ConvWeights), C.POINTER(_P)]),
         "rva_yolov8_plan_destroy": (None, [_P]),
         "rva_yolov8_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p, i32p]),
+        "rva_yolov8_plan_output_layout": (C.c_int, [_P, i64p, i64p]),
         "rva_yolov8_plan_run": (C.c_int, [_P, _P, _P, _P]),
         "rva_yolov8_plan_run_lanes": (C.c_int, [_P, _P, _P, _P, _P, _P]),
         "rva_yolov8_plan_run_range": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P]),
@@ -240,6 +251,8 @@ EXPORTS = [
     "rva_conv1x1_head_f16", "rva_conv1x1_upcat_f16", "rva_sppf_pool3_nhwc_f16", "rva_maxpool5_nhwc_f16", "rva_upsample2x_nhwc_f16", "rva_yolo_head_f16", "rva_yolo_head3_f16",
     "rva_conv_f32_num_variants", "rva_conv2d_nhwc_f32_v", "rva_stem_conv_f32", "rva_maxpool5_nhwc_f32", "rva_upsample2x_nhwc_f32",
     "rva_yolo_head_f32",
+    "rva_postprocess_boxes_batch", "rva_conv1x1_head_box32_f16", "rva_yolo_head_box32_f16", "rva_yolo_head3_box32_f16",
+    "rva_yolov8_plan_output_layout",
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
     "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",

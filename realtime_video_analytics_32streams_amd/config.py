@@ -14,7 +14,11 @@ detector key ``hip_engine`` picks the network's engine: ``"auto"`` (default; wha
 every temporal head; ``"plan"`` = the hand-written plan at the configured precision, i.e. the fp32 YOLO plan for
 ``half: false`` and, for ``model_type: cnn_lstm``, the fp32 clip plan (``half: false`` only: ``half: true`` is
 refused at construction).  The other temporal heads have no plan: with ``"plan"`` they keep PyTorch-ROCm and log
-a warning.
+a warning.  ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
+rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
+0.25 px between 256 and 512; ``"fp32"`` = the head kernels also write them as an fp32 side tensor and the post-process
+reads its boxes from there (class rows stay fp16).  With ``half: false`` the boxes are fp32 already and the key is
+accepted without effect, as it is for a detector that is given an ``infer_fn`` (no plan).
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import yaml
 HIP_BACKENDS = ("hip", "rocm", "mi355x")
 REFERENCE_BACKENDS = ("ultralytics", "tensorrt", "onnx", "onnxruntime", "openvino", "rknn", "rk3588")
 HIP_ENGINES = ("auto", "plan")
+HIP_BOX_ROWS = ("fp16", "fp32")
 TEMPORAL_MODELS = ("cnn_lstm", "3d_cnn", "conv_gru", "slow_fast")
 MODEL_TYPES = ("yolov5", "yolov8", "resnet") + TEMPORAL_MODELS
 
@@ -100,10 +105,12 @@ class DetectorConfig:
     action_classes: Optional[List[str]] = None
     num_action_classes: int = 400
     hip_engine: str = "auto"                # backend "hip", YOLO and cnn_lstm: "auto" or "plan" (module docstring)
+    hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
 
     def validate(self) -> None:
         _need(bool(self.model_path), "Detector model_path must not be empty")
         _need(self.hip_engine in HIP_ENGINES, f"hip_engine must be one of {set(HIP_ENGINES)}")
+        _need(self.hip_box_rows in HIP_BOX_ROWS, f"hip_box_rows must be one of {set(HIP_BOX_ROWS)}")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,
               f"Detector backend must be one of {set(REFERENCE_BACKENDS + HIP_BACKENDS)}")
         _need(self.model_type in MODEL_TYPES, f"Model type must be one of {set(MODEL_TYPES)}")

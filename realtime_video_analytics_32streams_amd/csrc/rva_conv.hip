@@ -47,7 +47,12 @@ struct ConvArgs {
     const __half *w;          // [CoutPad][taps][Cin]
     const float *bias;        // [CoutPad]
     __half *out; int ldo;
-    const __half *res; int ldr;
+    // One pointer slot for two optional tensors no kernel takes together (the argument block of every kernel keeps its layout):
+    union {
+        const __half *res;    // residual added after the activation (NULL = none)
+        float *hbox;          // k_conv_gbig<..., HEAD>, hmode 1: fp32 side tensor [B, 4, hA] of the box rows (NULL = fp16 rows only)
+    };
+    int ldr;
     int CoutPad;
     // k_conv_gbig<..., HEAD>: the detect head's last 1x1 convolutions decode straight into out[B, 4+nc, A]
     __half *hout; int hmode, hnc, hA, ha0, hW, hHW; float hstride;   // hmode 1 = box branch (DFL + dist2bbox), 2 = class branch (sigmoid)
@@ -1077,7 +1082,8 @@ struct HeadArgs {
 
 struct Head3Args { HeadArgs lv[3]; int blocks[3]; };     // blocks[l] = 256-anchor blocks of level l
 
-__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b);
+template <bool BOX32 = false>
+__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, float *box32 = nullptr);
 
 __global__ void __launch_bounds__(256) k_head(HeadArgs a)
 {
@@ -1095,7 +1101,24 @@ __global__ void __launch_bounds__(256) k_head3(Head3Args a)
     if (i < h.h * h.w) head_anchor(h, i, blockIdx.y);
 }
 
-__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b)
+// the same launches with the fp32 side tensor box32[B, 4, A] of the box rows (rva_yolo_head_box32_f16 / rva_yolo_head3_box32_f16)
+__global__ void __launch_bounds__(256) k_head_box32(HeadArgs a, float *box32)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < a.h * a.w) head_anchor<true>(a, i, blockIdx.y, box32);
+}
+
+__global__ void __launch_bounds__(256) k_head3_box32(Head3Args a, float *box32)
+{
+    int blk = blockIdx.x, l = 0;
+    if (blk >= a.blocks[0]) { blk -= a.blocks[0]; l = 1; if (blk >= a.blocks[1]) { blk -= a.blocks[1]; l = 2; } }
+    const HeadArgs &h = a.lv[l];
+    const int i = blk * 256 + threadIdx.x;
+    if (i < h.h * h.w) head_anchor<true>(h, i, blockIdx.y, box32);
+}
+
+template <bool BOX32>
+__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, float *box32)
 {
     const int hw = a.h * a.w;
     const size_t pix = (size_t)b * hw + i;
@@ -1125,6 +1148,13 @@ __device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b)
     o[(size_t)a.A] = __float2half_rn((y1 + y2) * 0.5f * a.stride);
     o[(size_t)2 * a.A] = __float2half_rn((x2 - x1) * a.stride);
     o[(size_t)3 * a.A] = __float2half_rn((y2 - y1) * a.stride);
+    if constexpr (BOX32) {    // the four values the roundings above took (the same fp32 operations: one value each), anchor axis
+        float *o32 = box32 + (size_t)b * 4 * a.A + a.a0 + i;      // contiguous like the fp16 rows
+        o32[0] = (x1 + x2) * 0.5f * a.stride;
+        o32[(size_t)a.A] = (y1 + y2) * 0.5f * a.stride;
+        o32[(size_t)2 * a.A] = (x2 - x1) * a.stride;
+        o32[(size_t)3 * a.A] = (y2 - y1) * a.stride;
+    }
     const __half *cp = a.cls + pix * a.ldc;
     for (int c = 0; c < a.nc; c += 8) {
         const uint4 q = *reinterpret_cast<const uint4 *>(cp + c);
@@ -2438,6 +2468,13 @@ __global__ void __launch_bounds__(512)
                 o[(size_t)a.hA] = __float2half_rn((y1 + y2) * 0.5f * a.hstride);
                 o[(size_t)2 * a.hA] = __float2half_rn((x2 - x1) * a.hstride);
                 o[(size_t)3 * a.hA] = __float2half_rn((y2 - y1) * a.hstride);
+                if (a.hbox) {             // uniform.  The four values the roundings above took (the same fp32 operations: one value each),
+                    float *o32 = a.hbox + (size_t)b * 4 * a.hA + a.ha0 + i;      // anchor axis contiguous like the fp16 rows
+                    o32[0] = (x1 + x2) * 0.5f * a.hstride;
+                    o32[(size_t)a.hA] = (y1 + y2) * 0.5f * a.hstride;
+                    o32[(size_t)2 * a.hA] = (x2 - x1) * a.hstride;
+                    o32[(size_t)3 * a.hA] = (y2 - y1) * a.hstride;
+                }
             } else {
                 const int cend = min(BN, a.Cout - n0);
                 for (int c = 0; c < cend; c += 8) {
@@ -3854,9 +3891,9 @@ int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, 
     return RVA_OK;
 }
 
-int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
-                         int Cin, int Cout, int mode, void *out, int nc, int anchors_total, int anchor_offset, float stride_px,
-                         int variant, rva_stream_t stream_)
+static int conv1x1_head(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                        int Cin, int Cout, int mode, void *out, float *boxes32, int nc, int anchors_total, int anchor_offset, float stride_px,
+                        int variant, rva_stream_t stream_)
 {
     if (!ctx) return RVA_ERR_ARG;
     if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || Cin % 64 || Cout % 8 || ldi % 8 || nc % 8 ||
@@ -3869,6 +3906,7 @@ int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weig
     a.CoutPad = rva_ceil_div(Cout, 64) * 64;
     a.hout = (__half *)out; a.hmode = mode; a.hnc = nc; a.hA = anchors_total; a.ha0 = anchor_offset; a.hW = W; a.hHW = H * W;
     a.hstride = stride_px;
+    a.hbox = boxes32;
     hipStream_t s = (hipStream_t)stream_;
     hipError_t ev;
     switch (variant) {
@@ -3884,6 +3922,23 @@ int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weig
     }
     if (ev != hipSuccess) return rva_fail(ctx, RVA_ERR_HIP, "rva_conv1x1_head_f16: launch failed: %s", hipGetErrorString(ev));
     return RVA_OK;
+}
+
+int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                         int Cin, int Cout, int mode, void *out, int nc, int anchors_total, int anchor_offset, float stride_px,
+                         int variant, rva_stream_t stream_)
+{
+    return conv1x1_head(ctx, in, ldi, weights, bias, batch, H, W, Cin, Cout, mode, out, nullptr, nc, anchors_total, anchor_offset, stride_px, variant, stream_);
+}
+
+int rva_conv1x1_head_box32_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                               int Cin, void *out, float *boxes32, int nc, int anchors_total, int anchor_offset, float stride_px,
+                               int variant, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!boxes32 || (uintptr_t)boxes32 % 4 || anchor_offset < 0 || anchor_offset + H * W > anchors_total)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_box32_f16: boxes32 must be a float tensor [batch, 4, anchors_total] and the level must lie inside it");
+    return conv1x1_head(ctx, in, ldi, weights, bias, batch, H, W, Cin, 64, 1, out, boxes32, nc, anchors_total, anchor_offset, stride_px, variant, stream_);
 }
 
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }
@@ -3998,9 +4053,9 @@ int rva_upsample2x_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, void *out, in
     return RVA_OK;
 }
 
-int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
-                       const int32_t *ldc, void *out, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
-                       const float *strides, rva_stream_t stream_)
+static int yolo_head3(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                      const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
+                      const float *strides, rva_stream_t stream_)
 {
     if (!ctx || !box_logits || !cls_logits || !ldb || !ldc || !h || !w || !strides || !out || nc % 8)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: bad argument");
@@ -4016,9 +4071,26 @@ int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_
         a0 += h[l] * w[l];
     }
     if (a0 != anchors_total) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: anchors_total != sum of h*w");
-    k_head3<<<dim3(total, batch), 256, 0, (hipStream_t)stream_>>>(a);
+    if (boxes32) k_head3_box32<<<dim3(total, batch), 256, 0, (hipStream_t)stream_>>>(a, boxes32);
+    else k_head3<<<dim3(total, batch), 256, 0, (hipStream_t)stream_>>>(a);
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
+}
+
+int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                       const int32_t *ldc, void *out, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
+                       const float *strides, rva_stream_t stream_)
+{
+    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, nullptr, batch, h, w, nc, anchors_total, strides, stream_);
+}
+
+int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                             const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
+                             int anchors_total, const float *strides, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!boxes32 || (uintptr_t)boxes32 % 4) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_box32_f16: boxes32 must be a float tensor [batch, 4, anchors_total]");
+    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, boxes32, batch, h, w, nc, anchors_total, strides, stream_);
 }
 
 int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, int batch,
@@ -4030,6 +4102,21 @@ int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void 
                anchors_total, anchor_offset, stride};
     dim3 g(rva_ceil_div(h * w, 256), batch);
     k_head<<<g, 256, 0, (hipStream_t)stream_>>>(a);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
+int rva_yolo_head_box32_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, float *boxes32,
+                            int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!box_logits || !cls_logits || !out || !boxes32 || (uintptr_t)boxes32 % 4 || nc % 8 || ldb % 8 || ldc % 8 || batch <= 0 || h <= 0 || w <= 0 ||
+        anchor_offset < 0 || anchor_offset + h * w > anchors_total)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_box32_f16: bad argument (boxes32 [batch, 4, anchors_total] float, the level inside the anchor range)");
+    HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
+               anchors_total, anchor_offset, stride};
+    dim3 g(rva_ceil_div(h * w, 256), batch);
+    k_head_box32<<<g, 256, 0, (hipStream_t)stream_>>>(a, boxes32);
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
 }

@@ -64,6 +64,8 @@ struct rva_yolov8_plan {
     hipEvent_t fork_ev[3] = {nullptr, nullptr, nullptr}, join_ev[3] = {nullptr, nullptr, nullptr};
     bool fused_stem = false, fused_head = false;
     bool f32 = false;                     // RVA_PLAN_F32: fp32 buffers and the kernels of rva_conv_f32.hip
+    bool box32 = false;                   // RVA_PLAN_BOX_F32: the head kernels also write the box rows as fp32 [B, 4, A] behind the fp16 head
+    size_t box_off = 0;                   // ... at this byte offset of `output` (rva_yolov8_plan_output_layout)
 };
 
 namespace {
@@ -437,6 +439,13 @@ struct Builder {
 int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *input, void *output, rva_stream_t st)
 {
     rva_ctx *c = p->ctx;
+    if (p->box32 && output) {             // the two launch forms that write box rows, with the side tensor of this output
+        float *boxes = (float *)((char *)output + p->box_off);
+        if (s.kind == K_HEAD && s.mode == 1)
+            return rva_conv1x1_head_box32_f16(c, s.in, s.ldi, s.w, s.b, p->B, s.H, s.W, s.Cin, output, boxes, p->nc, p->A, s.a0, s.stride_px, variant, st);
+        if (s.kind == K_HEAD3)
+            return rva_yolo_head3_box32_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, boxes, p->B, s.hh, s.hw, p->nc, p->A, s.hs, st);
+    }
     switch (s.kind) {
     case K_CONV: return rva_conv2d_nhwc_f16_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
     case K_UPCAT: return rva_conv1x1_upcat_f16(c, s.in, s.ldi, s.c_in, s.in2, s.ldi2, s.c_in2, s.w, s.b, s.out, s.ldo, p->B, s.H, s.W, s.Cout, s.act, variant, st);
@@ -481,6 +490,9 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
     std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
     p->ctx = ctx; p->d = *desc; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
     p->f32 = (desc->flags & RVA_PLAN_F32) != 0;
+    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
+    if (p->f32 && p->box32)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: RVA_PLAN_BOX_F32 belongs to fp16 plans (the output of an RVA_PLAN_F32 plan is fp32 already)");
     Builder b{p.get(), convs};
     const bool ok = b.build();
     if (!ok) {
@@ -494,6 +506,7 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
             RVA_HIP(ctx, hipEventCreateWithFlags(&p->join_ev[l], hipEventDisableTiming));
         }
     RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
+    if (p->box32) p->box_off = ((size_t)p->B * (4 + p->nc) * p->A * 2 + 255) / 256 * 256;
     *out = p.release();
     return RVA_OK;
 }
@@ -517,6 +530,15 @@ int rva_yolov8_plan_info(const rva_yolov8_plan *p, int32_t *anchors, int32_t *ou
     if (n_steps) *n_steps = (int32_t)p->steps.size();
     if (n_tunable) *n_tunable = (int32_t)p->tunables.size();
     if (quiet_step) *quiet_step = p->quiet_step;
+    return RVA_OK;
+}
+
+int rva_yolov8_plan_output_layout(const rva_yolov8_plan *p, int64_t *total_bytes, int64_t *boxes_offset)
+{
+    if (!p) return RVA_ERR_ARG;
+    const size_t head = (size_t)p->B * (4 + p->nc) * p->A * (p->f32 ? 4 : 2);
+    if (total_bytes) *total_bytes = (int64_t)(p->box32 ? p->box_off + (size_t)p->B * 4 * p->A * 4 : head);
+    if (boxes_offset) *boxes_offset = p->box32 ? (int64_t)p->box_off : -1;
     return RVA_OK;
 }
 

@@ -57,8 +57,10 @@ struct K2Args {
 __device__ __forceinline__ float ldf(const float *p) { return *p; }
 __device__ __forceinline__ float ldf(const __half *p) { return __half2float(*p); }
 
-template <typename T>
-__global__ void __launch_bounds__(256) k2_decode(K2Args a)
+// SPLIT: cx, cy, w, h come from the fp32 side tensor boxes[batch, 4, A] (anchor axis contiguous) instead of rows 0-3 of the head
+// tensor, which are then never read; everything else is the same code
+template <typename T, bool SPLIT>
+__device__ __forceinline__ void k2_body(const K2Args &a, const float *boxes)
 {
     const int b = blockIdx.y;
     const int anchor = blockIdx.x * 256 + threadIdx.x;
@@ -83,7 +85,13 @@ __global__ void __launch_bounds__(256) k2_decode(K2Args a)
         if (a.use_cls) pass = pass && bi < 1024 && ((a.cls_mask[bi >> 5] >> (bi & 31)) & 1u);  // :313-314
         if (pass) {
             const PostMeta m = a.meta[b];
-            const float cx = ldf(p), cy = ldf(p + a.sc), w = ldf(p + 2 * a.sc), h = ldf(p + 3 * a.sc);
+            float cx, cy, w, h;
+            if constexpr (SPLIT) {
+                const float *q = boxes + (long)b * 4 * a.A + anchor;
+                cx = q[0]; cy = q[a.A]; w = q[2 * (long)a.A]; h = q[3 * (long)a.A];
+            } else {
+                cx = ldf(p); cy = ldf(p + a.sc); w = ldf(p + 2 * a.sc); h = ldf(p + 3 * a.sc);
+            }
             float x1 = cx - w / 2.0f, y1 = cy - h / 2.0f, x2 = cx + w / 2.0f, y2 = cy + h / 2.0f;  // :352-359
             x1 -= m.left; x2 -= m.left; y1 -= m.top; y2 -= m.top;                                // :345-346
             x1 = __fdiv_rn(x1, m.scale); y1 = __fdiv_rn(y1, m.scale);                           // :347
@@ -106,6 +114,12 @@ __global__ void __launch_bounds__(256) k2_decode(K2Args a)
         if (w < a.nwords) a.bits[(long)b * a.nwords + w] = (uint32_t)(mask >> (32 * lane));
     }
 }
+
+template <typename T>
+__global__ void __launch_bounds__(256) k2_decode(K2Args a) { k2_body<T, false>(a, nullptr); }
+
+template <typename T>
+__global__ void __launch_bounds__(256) k2_decode_split(K2Args a, const float *boxes) { k2_body<T, true>(a, boxes); }
 
 // detector.py:469-481, float32; a = the kept (higher-priority) box
 __device__ __forceinline__ float iou32(const float4 a, const float4 b)
@@ -823,11 +837,12 @@ __global__ void k_zero_counts(int32_t *p, int n)
 
 }  // namespace
 
-extern "C" int rva_postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtype, int batch, int d1, int d2,
-                                     double conf_thr, double iou_thr, const int32_t *classes, int n_classes,
-                                     const rva_letterbox *metas, int n_metas, int max_det, float *out_boxes,
-                                     float *out_scores, int32_t *out_cls, int32_t *out_anchor, int32_t *out_cand,
-                                     int32_t *out_counts, int32_t *out_ncand, rva_stream_t stream_)
+// boxes == nullptr: rva_postprocess_batch; otherwise rva_postprocess_boxes_batch (the caller has checked the orientation)
+static int postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtype, const float *boxes, int batch, int d1, int d2,
+                             double conf_thr, double iou_thr, const int32_t *classes, int n_classes,
+                             const rva_letterbox *metas, int n_metas, int max_det, float *out_boxes,
+                             float *out_scores, int32_t *out_cls, int32_t *out_anchor, int32_t *out_cand,
+                             int32_t *out_counts, int32_t *out_ncand, rva_stream_t stream_)
 {
     if (!ctx) return RVA_ERR_ARG;
     hipStream_t stream = (hipStream_t)stream_;
@@ -881,7 +896,12 @@ extern "C" int rva_postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtyp
         k2.bits = ctx->cand_bits; k2.nwords = nwords;
         k2.irr = ctx->post_flags + 1;
         dim3 g2(rva_ceil_div(A, 256), nb);
-        if (raw_dtype == RVA_F16) k2_decode<__half><<<g2, 256, 0, stream>>>(k2);
+        if (boxes) {
+            const float *bx = boxes + (size_t)b0 * 4 * A;
+            if (raw_dtype == RVA_F16) k2_decode_split<__half><<<g2, 256, 0, stream>>>(k2, bx);
+            else k2_decode_split<float><<<g2, 256, 0, stream>>>(k2, bx);
+        }
+        else if (raw_dtype == RVA_F16) k2_decode<__half><<<g2, 256, 0, stream>>>(k2);
         else k2_decode<float><<<g2, 256, 0, stream>>>(k2);
 
         K3Args k3{};
@@ -921,6 +941,29 @@ extern "C" int rva_postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtyp
     }
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
+}
+
+extern "C" int rva_postprocess_batch(rva_ctx *ctx, const void *raw, int raw_dtype, int batch, int d1, int d2,
+                                     double conf_thr, double iou_thr, const int32_t *classes, int n_classes,
+                                     const rva_letterbox *metas, int n_metas, int max_det, float *out_boxes,
+                                     float *out_scores, int32_t *out_cls, int32_t *out_anchor, int32_t *out_cand,
+                                     int32_t *out_counts, int32_t *out_ncand, rva_stream_t stream_)
+{
+    return postprocess_batch(ctx, raw, raw_dtype, nullptr, batch, d1, d2, conf_thr, iou_thr, classes, n_classes, metas, n_metas, max_det,
+                             out_boxes, out_scores, out_cls, out_anchor, out_cand, out_counts, out_ncand, stream_);
+}
+
+extern "C" int rva_postprocess_boxes_batch(rva_ctx *ctx, const void *raw, int raw_dtype, const float *boxes, int batch, int channels,
+                                           int anchors, double conf_thr, double iou_thr, const int32_t *classes, int n_classes,
+                                           const rva_letterbox *metas, int n_metas, int max_det, float *out_boxes,
+                                           float *out_scores, int32_t *out_cls, int32_t *out_anchor, int32_t *out_cand,
+                                           int32_t *out_counts, int32_t *out_ncand, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!boxes || (uintptr_t)boxes % 4 || channels < 5 || channels >= anchors)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_postprocess_boxes_batch: boxes [batch, 4, anchors] float and a [channels, anchors] head with 5 <= channels < anchors");
+    return postprocess_batch(ctx, raw, raw_dtype, boxes, batch, channels, anchors, conf_thr, iou_thr, classes, n_classes, metas, n_metas, max_det,
+                             out_boxes, out_scores, out_cls, out_anchor, out_cand, out_counts, out_ncand, stream_);
 }
 
 extern "C" int rva_post_filter_stats(rva_ctx *ctx, rva_stream_t stream_, int *binned_images)

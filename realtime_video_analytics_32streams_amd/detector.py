@@ -99,7 +99,10 @@ class HipYoloDetector(BaseDetector):
         launch per layer, fp16 operands with fp32 accumulation.  ``half: false`` is the reference's fp32 precision
         (detector.py:248-251): by default (``hip_engine: auto``) the module then runs through PyTorch-ROCm (MIOpen) and the
         constructor says so in the log -- a configuration never changes engines silently; ``hip_engine: plan`` runs it as the
-        hand-written fp32 plan instead (engine ``"fused-f32"``: exact fp32 MFMA, bit-reproducible, same pipeline integration)."""
+        hand-written fp32 plan instead (engine ``"fused-f32"``: exact fp32 MFMA, bit-reproducible, same pipeline integration).
+        ``hip_box_rows: fp32`` (engine ``"fused"`` only) makes the plan keep the four box rows in fp32 beside its fp16 head
+        (``engine.FusedYoloV8(box_rows="fp32")``); the side tensor travels from ``stage_net`` to ``stage_post`` as an
+        ``ops.SplitHead`` and K2 reads its boxes from it."""
         super().__init__(config)
         self._plans = {}
         self.ctx = ops.context(device)            # raises RuntimeError when no HIP device (no CPU fallback)
@@ -111,6 +114,8 @@ class HipYoloDetector(BaseDetector):
         self.half = bool(config.half)
         self.engine = "fused" if self.half else ("fused-f32" if getattr(config, "hip_engine", "auto") == "plan" else "torch-fp32")
         self._infer_fn = infer_fn
+        # where the fp16 plan keeps its box rows; fp32 elsewhere already (half: false), and no plan behind an infer_fn
+        self.box_rows = getattr(config, "hip_box_rows", "fp16") if (self.engine == "fused" and infer_fn is None) else "fp16"
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -183,25 +188,31 @@ class HipYoloDetector(BaseDetector):
             first = self._plans.get(shape) if self._slot else None
             plan = self._plans[key] = FusedYoloV8(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
                                                   autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
-                                                  precision="fp32" if self.engine == "fused-f32" else "fp16")
+                                                  precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows)
             if first is not None:
                 plan.copy_tuning(first)
         return plan
 
-    def _infer(self, tensor: torch.Tensor) -> torch.Tensor:
+    def _infer(self, tensor: torch.Tensor):
+        """The head tensor of the batch; with ``hip_box_rows: fp32`` an ``ops.SplitHead`` (head tensor, fp32 box rows)."""
         if self._infer_fn is not None:
             return self._infer_fn(tensor)
         if self.half:
             if tensor.dtype != torch.float16:
                 raise TypeError("half detector: the fused plan takes the fp16 tensor K1 writes")
-            return self.plan_for(tensor)(tensor.contiguous())
+            plan = self.plan_for(tensor)
+            plan(tensor.contiguous())
+            return plan.result()
         if self.engine == "fused-f32":
             if tensor.dtype != torch.float32:
                 raise TypeError("fp32 plan: takes the fp32 tensor K1 writes for half=false")
             return self.plan_for(tensor)(tensor.contiguous())
         return self.net(tensor.float().contiguous(memory_format=torch.channels_last))
 
-    def _postprocess_device(self, raw: torch.Tensor, metas: Sequence[N.Letterbox]) -> ops.PostBuffers:
+    def _postprocess_device(self, raw, metas: Sequence[N.Letterbox]) -> ops.PostBuffers:
+        boxes = None
+        if isinstance(raw, ops.SplitHead):
+            raw, boxes = raw
         raw = raw.contiguous()
         B = raw.shape[0]
         A = raw.shape[2] if raw.shape[1] < raw.shape[2] else raw.shape[1]
@@ -209,7 +220,7 @@ class HipYoloDetector(BaseDetector):
         if self._post is None:
             self._post = self._post_bufs[(B, A)] = ops.PostBuffers.allocate(B, A, raw.device)
         return ops.postprocess(raw, self.config.confidence_threshold, self.config.iou_threshold, self.config.classes,
-                               metas, max_det=A, out=self._post, ctx=self.ctx)
+                               metas, max_det=A, out=self._post, ctx=self.ctx, boxes=boxes)
 
     # -- the three stages of a tick, as the pipelined runner drives them (same protocol as the temporal heads) -------------
     def stage_pre(self, packets: Sequence[FramePacket]):

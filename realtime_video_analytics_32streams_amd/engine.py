@@ -14,6 +14,9 @@ The plan itself -- weight packing, the NHWC fp16 activation buffers, the static 
 Output: the same ``[B, 4+nc, A]`` fp16 tensor the torch module returns, so everything downstream (K2/K3/K4) and every parity
 test is unchanged.  ``precision="fp32"`` builds the same plan in the reference's own precision (``RVA_PLAN_F32``: fp32 input,
 activations, weights and ``[B, 4+nc, A]`` fp32 output; kernels of ``csrc/rva_conv_f32.hip``, bit-identical across kernel variants).
+``box_rows="fp32"`` (fp16 plans, opt-in; ``RVA_PLAN_BOX_F32``) makes the head kernels also store the four box rows as an fp32 side
+tensor ``boxes32[B, 4, A]`` of the same output slot -- one allocation with the head tensor, which is still written in full and is
+bit-identical to the default plan's; ``ops.postprocess(..., boxes=plan.boxes32)`` reads its boxes from it.
 No host synchronisation and no allocation after construction: a whole tick can be captured into a hipGraph.
 """
 from __future__ import annotations
@@ -84,10 +87,16 @@ class _VariantCell:
 
 class FusedYoloV8:
     def __init__(self, net: YoloV8, batch: int, hw: Tuple[int, int] = (640, 640), device: Optional[torch.device] = None,
-                 ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16"):
+                 ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16",
+                 box_rows: str = "fp16"):
         import os
         if precision not in ("fp16", "fp32"):
             raise ValueError(f"precision must be 'fp16' or 'fp32', not {precision!r}")
+        if box_rows not in ("fp16", "fp32"):
+            raise ValueError(f"box_rows must be 'fp16' or 'fp32', not {box_rows!r}")
+        if box_rows == "fp32" and precision == "fp32":
+            raise ValueError("box_rows='fp32' belongs to the fp16 plan: the output of precision='fp32' is fp32 already")
+        self.box_rows = box_rows
         self.precision = precision
         self.f32 = precision == "fp32"
         self.tune_overlap = int(tune_overlap)
@@ -119,7 +128,7 @@ class FusedYoloV8:
         d.flags = (N.RVA_PLAN_NO_STEM2 if os.environ.get("RVA_NO_STEM2", "0") == "1" else 0) | \
                   (N.RVA_PLAN_NO_CIN_PAD if os.environ.get("RVA_NO_CIN_PAD", "0") == "1" else 0) | \
                   (0 if self._use_pair32() else N.RVA_PLAN_NO_PAIR32) | \
-                  (N.RVA_PLAN_F32 if self.f32 else 0)
+                  (N.RVA_PLAN_F32 if self.f32 else 0) | (N.RVA_PLAN_BOX_F32 if box_rows == "fp32" else 0)
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
             self.ctx.check(self.L.rva_yolov8_plan_create(self.ctx.handle, C.byref(d), arr, C.byref(h)), "rva_yolov8_plan_create")
@@ -130,7 +139,16 @@ class FusedYoloV8:
         self.A, rows, self._n_steps, n_tun, self.quiet_step = (int(v.value) for v in info)
         assert rows == 4 + self.nc
         self.dtype = torch.float32 if self.f32 else torch.float16
-        self.out = torch.empty((batch, rows, self.A), dtype=self.dtype, device=self.dev)
+        self.boxes32: Optional[torch.Tensor] = None       # box_rows="fp32": the side tensor of the current output slot
+        self._boxes = {}
+        if box_rows == "fp32":
+            total, off = C.c_int64(), C.c_int64()
+            self.ctx.check(self.L.rva_yolov8_plan_output_layout(h, C.byref(total), C.byref(off)), "rva_yolov8_plan_output_layout")
+            self._out_layout = (int(total.value), int(off.value))
+            self.out, self.boxes32 = self._alloc_split()
+            self._boxes[0] = self.boxes32
+        else:
+            self.out = torch.empty((batch, rows, self.A), dtype=self.dtype, device=self.dev)
         self._outs = {0: self.out}
         self.fused_stem = not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
         # (launch(stream, variant) -> rc, state["variant"], "Cin->Cout kKsS HxW") per convolution step, as the tuner and the tools use them
@@ -147,6 +165,15 @@ class FusedYoloV8:
         self.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1"      # A/B switch for measurements
         if autotune:
             self.autotune()
+
+    def _alloc_split(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One allocation in the plan's output layout: the fp16 head, then ``boxes32`` at the offset the plan reports."""
+        total, off = self._out_layout
+        rows = 4 + self.nc
+        buf = torch.empty((total,), dtype=torch.uint8, device=self.dev)
+        head = buf[:self.B * rows * self.A * 2].view(torch.float16).view(self.B, rows, self.A)
+        boxes = buf[off:off + self.B * 4 * self.A * 4].view(torch.float32).view(self.B, 4, self.A)
+        return head, boxes
 
     def fused_head_lanes(self) -> bool:
         """Whether the plan has detect branches that may run on side streams (head decode fused into the branches, or an fp32
@@ -293,7 +320,7 @@ class FusedYoloV8:
 
     def copy_tuning(self, other: "FusedYoloV8") -> None:
         """Take over the kernel selection of a plan built from the same network and batch shape."""
-        assert len(self._tunable) == len(other._tunable) and self.precision == other.precision
+        assert len(self._tunable) == len(other._tunable) and self.precision == other.precision      # (either box_rows: same selection)
         for (_, mine, d1), (_, theirs, d2) in zip(self._tunable, other._tunable):
             assert d1 == d2
             mine["variant"] = theirs["variant"]
@@ -316,7 +343,8 @@ class FusedYoloV8:
         lanes = self.concurrent_heads
         n_over = int(os.environ.get("RVA_TUNE_OVERLAP", "3"))
         if n_over >= 2:
-            twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision)
+            twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision,
+                                 box_rows=self.box_rows)
                      for _ in range(n_over - 1)]
             from .ops import chain_streams
             streams = chain_streams(self.dev, n_over)                  # the streams the pipeline's tick chains will run on
@@ -411,9 +439,18 @@ class FusedYoloV8:
         allocated on first use).  A pipelined caller alternates two per tick (and uses a pair per frame group), so the
         post-process of tick k can still read its head tensor on another HIP stream while the network of tick k+1 runs."""
         if index not in self._outs:
-            self._outs[index] = torch.empty_like(self._outs[0])
+            if self.box_rows == "fp32":
+                self._outs[index], self._boxes[index] = self._alloc_split()
+            else:
+                self._outs[index] = torch.empty_like(self._outs[0])
         self.out = self._outs[index]
+        self.boxes32 = self._boxes.get(index)
         return self.out
+
+    def result(self):
+        """What a caller hands to the post-process for the current output slot: the head tensor, or with ``box_rows="fp32"`` an
+        ``ops.SplitHead`` of the head tensor and its side tensor."""
+        return self.out if self.boxes32 is None else ops.SplitHead(self.out, self.boxes32)
 
     def _use_pair32(self) -> bool:
         """The 32-channel C2f bottleneck (YOLOv8s at 160 x 160) as ONE launch with the intermediate in LDS (rva_c2f_pair32_f16) or as

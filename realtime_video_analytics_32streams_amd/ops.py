@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -357,10 +357,18 @@ class PostBuffers:
                      keep=cand[b, :c], n_cand=int(ncand[b])) for b, c in enumerate(counts)]
 
 
+class SplitHead(NamedTuple):
+    """What a ``box_rows="fp32"`` plan hands on: the fp16 head tensor ``[B, 4+nc, A]`` (written in full) and the fp32 side tensor
+    ``[B, 4, A]`` of its box rows, both of the same output slot."""
+    head: torch.Tensor
+    boxes: torch.Tensor
+
+
 def postprocess(raw: torch.Tensor, conf_thr: float, iou_thr: float, classes: Optional[Sequence[int]],
                 metas: Sequence[N.Letterbox], max_det: Optional[int] = None, out: Optional[PostBuffers] = None,
-                ctx: Optional[N.Context] = None) -> PostBuffers:
-    """K2+K3 over ``raw[B, d1, d2]`` (float16/float32, device)."""
+                ctx: Optional[N.Context] = None, boxes: Optional[torch.Tensor] = None) -> PostBuffers:
+    """K2+K3 over ``raw[B, d1, d2]`` (float16/float32, device).  ``boxes``: fp32 ``[B, 4, A]`` side tensor (cx, cy, w, h) that
+    K2 reads instead of rows 0-3 of ``raw``, which must then be ``[B, channels, A]`` (``rva_postprocess_boxes_batch``)."""
     ctx = ctx or context()
     _require_cuda(raw, "head tensor")
     if raw.dim() == 2:
@@ -374,6 +382,23 @@ def postprocess(raw: torch.Tensor, conf_thr: float, iou_thr: float, classes: Opt
     assert out.max_det == max_det and out.counts.shape[0] >= B
     marr = (N.Letterbox * len(metas))(*metas)
     cls_p, _keep = (N.i32_array(list(classes)) if classes else (None, None))
+    if boxes is not None:
+        _require_cuda(boxes, "box side tensor")
+        if boxes.dim() == 2:
+            boxes = boxes.unsqueeze(0)
+        if not (d1 < d2 and boxes.dtype == torch.float32 and boxes.is_contiguous() and tuple(boxes.shape) == (B, 4, d2)
+                and boxes.device == raw.device):
+            raise ValueError(f"boxes must be a contiguous float32 [{B}, 4, {d2}] tensor beside a [B, channels, anchors] head, "
+                             f"got {boxes.dtype} {tuple(boxes.shape)} beside {tuple(raw.shape)}")
+        rc = N.lib().rva_postprocess_boxes_batch(
+            ctx.handle, C.c_void_p(raw.data_ptr()), N.RVA_F16 if raw.dtype == torch.float16 else N.RVA_F32,
+            C.c_void_p(boxes.data_ptr()), B, d1, d2,
+            float(conf_thr), float(iou_thr), cls_p, len(classes) if classes else 0, marr, len(metas), max_det,
+            C.c_void_p(out.boxes.data_ptr()), C.c_void_p(out.scores.data_ptr()), C.c_void_p(out.cls.data_ptr()),
+            C.c_void_p(out.anchor.data_ptr()), C.c_void_p(out.cand.data_ptr()), C.c_void_p(out.counts.data_ptr()),
+            C.c_void_p(out.ncand.data_ptr()), _stream_ptr())
+        ctx.check(rc, "rva_postprocess_boxes_batch")
+        return out
     rc = N.lib().rva_postprocess_batch(
         ctx.handle, C.c_void_p(raw.data_ptr()), N.RVA_F16 if raw.dtype == torch.float16 else N.RVA_F32, B, d1, d2,
         float(conf_thr), float(iou_thr), cls_p, len(classes) if classes else 0, marr, len(metas), max_det,

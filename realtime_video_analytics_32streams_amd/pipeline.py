@@ -407,6 +407,9 @@ class PipelinedTicks:
     strictly one tick at a time.  Same results as ``TickPipeline.tick`` in every layout (same kernels, same order per
     stream).  Detectors without a batched device path need the host in the loop and are not supported here.
 
+    With ``hip_box_rows: fp32`` a slot's head tensor and the fp32 side tensor of its box rows are one buffer of the slot's plan
+    (``FusedYoloV8.result()``): eager and captured tails of every layout hand K2 the side tensor of the same slot.
+
     ``submit()`` enqueues one tick and returns its ticket; ``collect()`` returns ``(ticket, tables)`` of the oldest
     outstanding tick, ``tables[slot]`` being the arrays of ``DeviceTracker.snapshot_fetch``; ``collect_result()`` returns
     the :class:`TickResult` instead.  Both raise if the device reported an overflow (tracker capacity / NMS capacity).
@@ -560,7 +563,8 @@ class PipelinedTicks:
                         pre_par = (det.input_tensor(int(pres[gi][0].shape[0])),) + tuple(pres[gi][1:])
                 fp = self._plan_of(det, pre_par[0])
                 # head tensor (group, parity): a stable buffer of the plan (two network streams: of the parity's own plan)
-                raws[gi][par] = fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
+                fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
+                raws[gi][par] = fp.result()                        # (with hip_box_rows: fp32 the slot's side tensor rides along)
                 if self.net_graph:
                     gr = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gr):
