@@ -308,14 +308,17 @@ int rva_tracker_set_next_id(rva_tracker *trk, int64_t next_id, rva_stream_t stre
 int rva_conv_cout_pad(int Cout);
 /* number of explicit kernel variants rva_conv2d_nhwc_f16_v accepts (1..N); the plan's autotuner iterates over them */
 int rva_conv_num_variants(void);
+/* printable name of a variant number ("auto" for 0, e.g. "big<256,128>" for 21): what tools/show_tuning.py prints and the
+ * tables under profiles/ record.  NULL for a number no kernel is assigned to. */
+const char *rva_conv_variant_name(int variant);
 int rva_conv2d_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias,
                         void *out, int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin,
                         int Cout, int ksize, int stride, int act, rva_stream_t stream);
 /* Same with an explicit kernel variant, so that a plan can time the applicable variants per layer once and keep the
- * fastest (0 = heuristic; 1..rva_conv_num_variants() = one kernel family and tile each, listed beside the dispatch in
- * csrc/rva_conv.hip: register-staged gather / resident-chunk / row-reuse kernels, and the LDS-DMA large-tile kernels
- * -- row reuse for 3x3 stride 1, gather with 64- or 32-channel K-steps for 1x1 and strided 3x3).  RVA_ERR_ARG if a
- * variant does not apply to the shape. */
+ * fastest (0 = heuristic; 1..rva_conv_num_variants() = one kernel family and tile each, one row each of the table
+ * kConvVariants in csrc/rva_conv.hip: register-staged gather / resident-chunk / row-reuse kernels, and the LDS-DMA
+ * large-tile kernels -- row reuse for 3x3 stride 1, gather with 64- or 32-channel K-steps for 1x1 and strided 3x3).
+ * RVA_ERR_ARG if a variant does not apply to the shape. */
 int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias,
                           void *out, int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin,
                           int Cout, int ksize, int stride, int act, int variant, rva_stream_t stream);

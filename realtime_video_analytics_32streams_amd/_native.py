@@ -179,6 +179,7 @@ def lib() -> C.CDLL:
         "rva_tracker_set_box_scale": (C.c_int, [_P, f64p]),
         "rva_conv_cout_pad": (C.c_int, [C.c_int]),
         "rva_conv_num_variants": (C.c_int, []),
+        "rva_conv_variant_name": (C.c_char_p, [C.c_int]),
         "rva_conv2d_nhwc_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int] + [C.c_int] * 8 + [_P]),
         "rva_conv2d_nhwc_f16_v": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int] + [C.c_int] * 9 + [_P]),
         "rva_stem_conv_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -247,7 +248,7 @@ EXPORTS = [
     "rva_tracker_snapshot_fetch", "rva_tracker_state",
     "rva_tracker_set_next_id", "rva_preview_nv12", "rva_decode_available", "rva_decoder_create", "rva_decoder_destroy", "rva_decoder_feed",
     "rva_decoder_next_frame", "rva_decoder_release", "rva_motion_nv12_batch", "rva_motion_nv12_masked_batch", "rva_motion_bgr_batch",
-    "rva_preprocess_nv12_masked_batch", "rva_resize_nv12_to_bgr_batch", "rva_tracker_set_box_scale", "rva_conv_cout_pad", "rva_conv_num_variants", "rva_conv2d_nhwc_f16", "rva_conv2d_nhwc_f16_v", "rva_stem_conv_f16", "rva_stem2_f16", "rva_c2f_pair32_f16",
+    "rva_preprocess_nv12_masked_batch", "rva_resize_nv12_to_bgr_batch", "rva_tracker_set_box_scale", "rva_conv_cout_pad", "rva_conv_num_variants", "rva_conv_variant_name", "rva_conv2d_nhwc_f16", "rva_conv2d_nhwc_f16_v", "rva_stem_conv_f16", "rva_stem2_f16", "rva_c2f_pair32_f16",
     "rva_conv1x1_head_f16", "rva_conv1x1_upcat_f16", "rva_sppf_pool3_nhwc_f16", "rva_maxpool5_nhwc_f16", "rva_upsample2x_nhwc_f16", "rva_yolo_head_f16", "rva_yolo_head3_f16",
     "rva_conv_f32_num_variants", "rva_conv2d_nhwc_f32_v", "rva_stem_conv_f32", "rva_maxpool5_nhwc_f32", "rva_upsample2x_nhwc_f32",
     "rva_yolo_head_f32",

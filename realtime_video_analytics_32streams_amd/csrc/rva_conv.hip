@@ -3453,49 +3453,387 @@ __global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Dispatch: from a variant number to a launch.
+//
+// rva_conv2d_nhwc_f16_v validates its arguments once and hands every variant the same ConvCall.  A family's adapter (v_*)
+// states the family's precondition on ksize / stride / Cin / Cout, builds the family's argument struct and calls the
+// family's launch_*, whose shape checks stay the only place where the family's limits are stated.  An adapter returns
+// hipErrorInvalidValue for "does not apply to this shape" (RVA_ERR_ARG at the C ABI); any other error is a HIP failure.
+struct ConvCall {
+    ConvArgs a;               // validated, Ho / Wo / M / CinPad derived; n_tiles, m_tiles and CoutPad are the family's to set
+    int batch, ksize;
+    int cpad;                 // Cout rounded up to 64: what the caller padded the weights to (rva_conv_cout_pad)
+    int num_cus;
+    hipStream_t s;
+};
+
+// the fields every family's argument struct shares (the structs themselves are part of the compiled kernels and stay apart)
+template <class G>
+G family_args(const ConvCall &c)
+{
+    const ConvArgs &a = c.a;
+    G g{};
+    g.in = a.in; g.ldi = a.ldi; g.w = a.w; g.bias = a.bias; g.out = a.out; g.ldo = a.ldo; g.res = a.res; g.ldr = a.ldr;
+    g.H = a.H; g.W = a.W; g.Cout = a.Cout; g.act = a.act;
+    return g;
+}
+
+// BigArgs / RunArgs: the 3x3 LDS-DMA families
+template <class G>
+G dma3_args(const ConvCall &c)
+{
+    G g = family_args<G>(c);
+    g.Cin = c.a.Cin; g.CoutPad = c.cpad; g.M = c.a.M;
+    return g;
+}
+
+inline bool is_3x3(const ConvCall &c, int stride) { return c.ksize == 3 && c.a.stride == stride; }
+
+// register-staged gather kernel: any ksize / stride; BN = 128 needs the weights padded to 128 output channels
+template <int BN, int WPX, int BK = 32>
+hipError_t v_gather(const ConvCall &c)
+{
+    if (c.cpad % BN) return hipErrorInvalidValue;
+    ConvArgs a = c.a;
+    a.n_tiles = c.cpad / BN;
+    a.m_tiles = rva_ceil_div(a.M, 4 * WPX);
+    return c.ksize == 1 ? launch_conv<BN, WPX, 1, BK>(a, c.s) : launch_conv<BN, WPX, 3, BK>(a, c.s);
+}
+
+// resident-chunk kernel: stride 1; 3x3 with 32-channel chunks, 1x1 with 128-channel chunks where Cin allows them, else 32
+// (last launch_res parameter: the staging registers of that tile and chunk).  <128,32> is 3x3 only; BN = 128 not with 1x1 x 32.
+template <int BN, int WPX>
+hipError_t v_res(const ConvCall &c)
+{
+    if (c.cpad % BN || c.a.stride != 1) return hipErrorInvalidValue;
+    ResArgs ra = family_args<ResArgs>(c);
+    ra.Cin = c.a.Cin; ra.CinPad = c.a.CinPad; ra.M = c.a.M;
+    ra.n_tiles = c.cpad / BN;
+#ifdef RVA_ROW_STAMPS
+    { const char *e = getenv("RVA_CONV_DBG"); ra.dbg = e ? atoi(e) : 0; }
+#endif
+    if (c.ksize == 3) return launch_res<BN, WPX, 3, 32, WPX == 64 ? 9 : 11>(ra, c.batch, c.num_cus, c.s);
+    if constexpr (BN == 64 || WPX == 64)
+        if (c.a.CinPad % 128 == 0) return launch_res<BN, WPX, 1, 128, WPX == 64 ? 16 : 8>(ra, c.batch, c.num_cus, c.s);
+    if constexpr (BN == 64)
+        if (c.a.CinPad % 128) return launch_res<BN, WPX, 1, 32, WPX == 64 ? 4 : 2>(ra, c.batch, c.num_cus, c.s);
+    return hipErrorInvalidValue;
+}
+
+// row-reuse kernel (PF2: two K-steps of loads in flight): 3x3 stride 1
+template <int BN, int WPX, bool PF2 = false>
+hipError_t v_row(const ConvCall &c)
+{
+    if (c.cpad % BN || !is_3x3(c, 1)) return hipErrorInvalidValue;
+    RowArgs rr = family_args<RowArgs>(c);
+    rr.Cin = c.a.Cin; rr.CinPad = c.a.CinPad;
+    rr.n_tiles = c.cpad / BN;
+    return launch_row<BN, WPX, PF2>(rr, c.batch, c.s);
+}
+
+// large-tile LDS-DMA kernel: 3x3 stride 1 (Cin % 32 == 0)
+template <int BM, int BN, int WGM, int WGN, int NSLOT>
+hipError_t v_big(const ConvCall &c)
+{
+    if (!is_3x3(c, 1)) return hipErrorInvalidValue;
+    BigArgs g = dma3_args<BigArgs>(c);
+    return launch_big<BM, BN, WGM, WGN, NSLOT>(g, c.s);
+}
+
+// large-tile LDS-DMA gather kernel: 1x1 stride 1, 3x3 of either stride (Cin % BK == 0); SUB K-steps per barrier
+template <int BM, int BN, int WGM, int WGN, int NSLOT, int BK = 64, int SUB = 1>
+hipError_t v_gbig(const ConvCall &c)
+{
+    if (c.ksize == 1 && c.a.stride != 1) return hipErrorInvalidValue;
+    ConvArgs a = c.a;
+    a.CoutPad = c.cpad;
+    return launch_gbig<BM, BN, WGM, WGN, NSLOT, BK, SUB>(a, c.ksize, c.s);
+}
+
+// patch kernels (weights resident in LDS): 3x3 of the kernel's stride and exactly its Cin.  Cin = 32: Cout up to CO; Cin = 64:
+// Cout up to 64, walked in resident groups of CO
+template <int STRIDE, int CIN, int CO, int NWV, int NBUF, int RPW = 1>
+hipError_t v_patch(const ConvCall &c)
+{
+    if (!is_3x3(c, STRIDE) || c.a.Cin != CIN || c.a.Cout > (CIN == 64 ? 64 : CO)) return hipErrorInvalidValue;
+    S2Args g = family_args<S2Args>(c);
+    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad;
+    return launch_patch<STRIDE, CIN, CO, NWV, NBUF, RPW>(g, c.num_cus, c.s);
+}
+
+// patch kernel with two wave sets half a tile period apart: 3x3 stride 1, exactly its Cin, Cout <= CO
+template <int CIN, int CO, int SW, int RPW>
+hipError_t v_patch2(const ConvCall &c)
+{
+    if (!is_3x3(c, 1) || c.a.Cin != CIN || c.a.Cout > CO) return hipErrorInvalidValue;
+    S2Args g = family_args<S2Args>(c);
+    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad;
+    return launch_patch2<CIN, CO, SW, RPW>(g, c.num_cus, c.s);
+}
+
+// the RunArgs families, 3x3 of one stride (Cin % 32 == 0): launch_run ("long run"; PADO: on the padded raster, no padding
+// selects in the MFMA phase), launch_s2run (its stride-2 form, see k_conv3_s2run), launch_chunk ("whole chunk per barrier")
+template <hipError_t (*LAUNCH)(RunArgs &, hipStream_t), int STRIDE = 1>
+hipError_t v_run(const ConvCall &c)
+{
+    if (!is_3x3(c, STRIDE)) return hipErrorInvalidValue;
+    RunArgs g = dma3_args<RunArgs>(c);
+    return LAUNCH(g, c.s);
+}
+
+#ifdef RVA_EXPERIMENTS
+// run<BM,BN> without the padding selects.  The select-free kernels give wrong border pixels: opt-in per process, and any
+// failure reads as "not applicable"
+template <int BM, int BN, int WGM, int WGN>
+hipError_t v_run_nosel(const ConvCall &c)
+{
+    const char *nosel = getenv("RVA_NOSEL");
+    if (!is_3x3(c, 1) || !nosel || nosel[0] != '1') return hipErrorInvalidValue;
+    RunArgs g = dma3_args<RunArgs>(c);
+    return launch_run<BM, BN, WGM, WGN, true>(g, c.s) == hipSuccess ? hipSuccess : hipErrorInvalidValue;
+}
+#endif
+
+hipError_t launch_variant(int variant, const ConvCall &c);
+
+// Variant 0, for callers that do not autotune.  First the LDS-DMA kernels wherever their channel constraints hold, tile
+// picked from the autotune tables of the YOLOv8 layers (tools/show_tuning.py); if that launch fails for any reason, the
+// resident kernel with the largest tile that still yields two tiles per CU; if its geometry does not fit, the gather kernel.
+hipError_t v_auto(const ConvCall &c)
+{
+    const ConvArgs &a = c.a;
+    const int cpad = c.cpad;
+    const bool bn128 = cpad % 128 == 0;
+    int pick = 0;
+    if (is_3x3(c, 1) && a.Cin % 32 == 0)
+        pick = bn128 ? ((long)a.M * a.Cout >= 20000000L ? 25 : 21) : (a.M >= 100000 ? 31 : 23);
+    else if (a.Cin % 64 == 0 && (c.ksize == 3 || a.stride == 1))
+        pick = 37;
+    if (pick) {
+        if (launch_variant(pick, c) == hipSuccess) return hipSuccess;
+        (void)hipGetLastError();
+    }
+    if (a.stride == 1) {
+        const long want = 2 * c.num_cus;
+        hipError_t e = hipErrorInvalidValue;
+        if (c.ksize == 3) {
+            // tile = 256 px x 128 ch when that yields enough tiles for every CU, else smaller tiles
+            const long t256 = (long)c.batch * rva_ceil_div(a.H * a.W, 256), t128 = (long)c.batch * rva_ceil_div(a.H * a.W, 128);
+            if (bn128 && t256 * (cpad / 128) >= want) e = launch_variant(7, c);
+            if (e == hipErrorInvalidValue && t256 * (cpad / 64) >= want) e = launch_variant(5, c);
+            if (e == hipErrorInvalidValue && bn128 && t128 * (cpad / 128) >= want) e = launch_variant(8, c);
+            if (e == hipErrorInvalidValue) e = launch_variant(6, c);
+        } else if (a.CinPad % 128 == 0) {
+            const long t256 = rva_ceil_div(a.M, 256);
+            if (bn128 && t256 * (cpad / 128) >= want) e = launch_variant(7, c);
+            if (e == hipErrorInvalidValue && t256 * (cpad / 64) >= want) e = launch_variant(5, c);
+            if (e == hipErrorInvalidValue) e = launch_variant(6, c);
+        } else {
+            const long t256 = rva_ceil_div(a.M, 256);
+            e = launch_variant(t256 * (cpad / 64) >= want ? 5 : 6, c);
+        }
+        if (e != hipErrorInvalidValue) return e;
+        (void)hipGetLastError();   // geometry does not fit the resident kernel: fall through to the gather kernel
+    }
+    // small problems: 128-pixel tiles keep more CUs busy
+    const bool small = (long)rva_ceil_div(a.M, 256) * (cpad / (bn128 ? 128 : 64)) < 512;
+    return launch_variant(bn128 ? (small ? 4 : 3) : (small ? 2 : 1), c);
+}
+
+// The seven tiles of the LDS-DMA gather kernel with 64-channel K-steps, <BM, BN, WGM, WGN, NSLOT>.  Besides the plain
+// convolution (variants 33..39 below) the fused "upsample + concat" and detect-head 1x1 convolutions select from them.
+#define RVA_GATHER64_TILES(X)                                                                       \
+    X(33, "gb<256,128>", 256, 128, 4, 2, 3)      /* 144 KB, one block per CU */                      \
+    X(34, "gb<128,128>", 128, 128, 2, 4, 3)      /* 96 KB */                                         \
+    X(35, "gb<256,64>", 256, 64, 4, 2, 3)        /* 120 KB */                                        \
+    X(36, "gb<128,64>", 128, 64, 2, 4, 3)        /* 72 KB: two blocks per CU */                      \
+    X(37, "gb2<128,128>", 128, 128, 2, 4, 2)     /* 64 KB: two blocks per CU */                      \
+    X(38, "gb2<256,64>", 256, 64, 4, 2, 2)       /* 80 KB: two blocks per CU */                      \
+    X(39, "gb2<192,128>", 192, 128, 4, 2, 2)     /* 80 KB: two blocks per CU */
+
+// One row per variant number: what the plan's autotuner times per layer, what persisted selections, RVA_SKIP_VARIANTS,
+// DESIGN.md and profiles/ cite.  Numbers never move; a new variant is a new row at the end.
+struct ConvVariant {
+    int number;
+    const char *name;         // as printed by tools/show_tuning.py and recorded under profiles/
+    hipError_t (*launch)(const ConvCall &);
+};
+
+constexpr ConvVariant kConvVariants[] = {
+    {0, "auto", v_auto},
+    // register-staged gather kernel <BN,WPX>
+    {1, "gather<64,64>", v_gather<64, 64>},
+    {2, "gather<64,32>", v_gather<64, 32>},
+    {3, "gather<128,64>", v_gather<128, 64>},
+    {4, "gather<128,32>", v_gather<128, 32>},
+    // resident kernel <BN,WPX>
+    {5, "res<64,64>", v_res<64, 64>},
+    {6, "res<64,32>", v_res<64, 32>},
+    {7, "res<128,64>", v_res<128, 64>},
+    {8, "res<128,32>", v_res<128, 32>},
+    // row-reuse kernel <BN,WPX>
+    {9, "row<64,64>", v_row<64, 64>},
+    {10, "row<64,32>", v_row<64, 32>},
+    {11, "row<128,64>", v_row<128, 64>},
+    {12, "row<128,32>", v_row<128, 32>},
+    // gather kernel with 64-channel K-steps (Cin padded to 64)
+    {13, "g64<64,64>", v_gather<64, 64, 64>},
+    {14, "g64<64,32>", v_gather<64, 32, 64>},
+    {15, "g64<128,64>", v_gather<128, 64, 64>},
+    {16, "g64<128,32>", v_gather<128, 32, 64>},
+    // row-reuse kernel with two K-steps of loads in flight
+    {17, "row2<64,64>", v_row<64, 64, true>},
+    {18, "row2<64,32>", v_row<64, 32, true>},
+    {19, "row2<128,64>", v_row<128, 64, true>},
+    {20, "row2<128,32>", v_row<128, 32, true>},
+    // large-tile LDS-DMA kernel <BM,BN>, 3-slot ring
+    {21, "big<256,128>", v_big<256, 128, 4, 2, 3>},
+    {22, "big<128,128>", v_big<128, 128, 2, 4, 3>},
+    {23, "big<256,64>", v_big<256, 64, 4, 2, 3>},
+    {24, "big<128,64>", v_big<128, 64, 2, 4, 3>},
+    // the same with a 2-slot ring: two or three blocks per CU; the extra tile heights exist so that the tile count can fit
+    // whole rounds of the 256 CUs
+    {25, "big2<192,128>", v_big<192, 128, 4, 2, 2>},      // 74 KB: two blocks per CU
+    {26, "big2<128,128>", v_big<128, 128, 2, 4, 2>},      // 66 KB: two blocks per CU
+    {27, "big2<256,64>", v_big<256, 64, 4, 2, 2>},        // 58 KB: two blocks per CU
+    {28, "big2<128,64>", v_big<128, 64, 2, 4, 2>},        // 42 KB: three blocks per CU
+    {29, "big2<224,128>", v_big<224, 128, 2, 4, 2>},      // 78 KB: two blocks per CU
+    {30, "big2<160,128>", v_big<160, 128, 2, 4, 2>},      // 70 KB
+    {31, "big2<384,64>", v_big<384, 64, 8, 1, 2>},        // 74 KB
+    {32, "big2<320,64>", v_big<320, 64, 4, 2, 2>},        // 66 KB
+    // large-tile LDS-DMA gather kernel, 64-channel K-steps: 33..36 3-slot ring, 37..39 2-slot
+#define RVA_ROW(n, name, ...) {n, name, v_gbig<__VA_ARGS__>},
+    RVA_GATHER64_TILES(RVA_ROW)
+#undef RVA_ROW
+    // the same with 32-channel K-steps (64-byte rows, swz32): the layers with Cin = 32 / 96
+    {40, "gb32<256,64>", v_gbig<256, 64, 4, 2, 3, 32>},   // 60 KB: two blocks per CU
+    {41, "gb32<128,64>", v_gbig<128, 64, 2, 4, 3, 32>},   // 36 KB: four blocks per CU
+    {42, "gb32_2<256,64>", v_gbig<256, 64, 4, 2, 2, 32>}, // 40 KB: three blocks per CU
+    // patch kernels for Cin = 32: 43 = 3x3 stride 2, Cout <= 64 (the first downsampling convolution); 44 / 45 = 3x3 stride 1,
+    // Cout <= 32, tiles of 4 / 8 rows (the 32 -> 32 bottleneck convolutions)
+    {43, "s2patch", v_patch<2, 32, 64, 4, 1>},
+    {44, "s1patch4", v_patch<1, 32, 32, 4, 1>},
+    {45, "s1patch8", v_patch<1, 32, 32, 8, 1>},
+    // patch kernels for 3x3 stride 1, 64 -> 64: 72 KB of weights resident, one block per CU
+    {46, "p64x4db", v_patch<1, 64, 64, 4, 2>},            // 124 KB, two patch buffers
+    {47, "p64x8", v_patch<1, 64, 64, 8, 1>},              // 116 KB, eight waves, one buffer
+    {48, "p64x4", v_patch<1, 64, 64, 4, 1>},              // 98 KB
+    {49, "p64x8db", v_patch<1, 64, 64, 8, 2>},            // 158 KB: eight waves, two patch buffers
+    {50, "p64x4r2db", v_patch<1, 64, 64, 4, 2, 2>},       // 158 KB: four waves x two rows, two buffers
+    {51, "p64x8r2", v_patch<1, 64, 64, 8, 1, 2>},         // 149 KB: 16-row tile, eight waves x two rows
+    // "long run" kernels: a 32-channel chunk's activation run staged once for the three vertical taps
+    {52, "run<256,64>", v_run<launch_run<256, 64, 4, 2>>},
+    {53, "run<128,64>", v_run<launch_run<128, 64, 2, 4>>},
+    {54, "run<384,64>", v_run<launch_run<384, 64, 8, 1>>},
+    {55, "run<192,128>", v_run<launch_run<192, 128, 4, 2>>},
+    {56, "run<256,128>", v_run<launch_run<256, 128, 4, 2>>},
+    {57, "run<128,128>", v_run<launch_run<128, 128, 2, 4>>},
+    {58, "run<224,128>", v_run<launch_run<224, 128, 2, 4>>},          // tile heights that fit whole rounds of the 256 CUs better
+    {59, "run<160,128>", v_run<launch_run<160, 128, 2, 4>>},
+    {60, "run<320,64>", v_run<launch_run<320, 64, 4, 2>>},
+    // patch kernels for 64 -> 64 with the output channels in two groups of 32: 36 KB of weights per block, two blocks per CU
+    {61, "p64h32x8", v_patch<1, 64, 32, 8, 1, 1>},        // 79 KB: 8-row tile
+    {62, "p64h32x4", v_patch<1, 64, 32, 4, 1, 1>},        // 62 KB: 4-row tile
+    {63, "p64h32x4r2", v_patch<1, 64, 32, 4, 1, 2>},      // 79 KB: 8-row tile, four waves x two rows
+    // LDS-DMA gather kernel with 256-channel output tiles: 43-64 MACs per staged byte against 32 of the 128 x 128 tile.  The
+    // CU's vector-memory path moves 64 B/clk, its MFMAs 4096 MAC/clk: below 64 MAC/B the staging, not the matrix pipe, caps a
+    // 1x1 convolution (a plain GEMM, no tap reuse).  One block per CU.
+    // (measured and dropped: <128,256> tiles, three- and four-slot rings with 32-channel steps -- more bytes in flight per CU
+    //  did not help the memory-latency-bound 1x1 layers, profiles/r02_conv_tuning.txt)
+    {64, "gb2<256,256>", v_gbig<256, 256, 4, 2, 2>},          // 128 KB ring, wave tile 64 x 128
+    {65, "gb2<256,256>w128x64", v_gbig<256, 256, 2, 4, 2>},   // 128 KB ring, wave tile 128 x 64
+    // patch kernel with two wave sets half a tile period apart (3x3 stride 1, Cin = 64, Cout <= 64).  Sixteen waves: two sets
+    // of eight, one output row per wave -- two MFMA waves per SIMD in every phase.  (The 2 x 4 waves x two rows form, one
+    // 256-register MFMA wave per SIMD, measured 27.0 us against 25.6 us at 80 x 80 and was dropped.)
+    {66, "p64 two sets", v_patch2<64, 64, 8, 1>},
+    // "whole chunk per barrier" kernels for layers with few pixels: one barrier per 32-channel chunk (nine taps), one block per CU
+    {67, "chunk<128,64>", v_run<launch_chunk<128, 64, 4, 2>>},
+    {68, "chunk<64,64>", v_run<launch_chunk<64, 64, 2, 4>>},
+    {69, "chunk<256,64>", v_run<launch_chunk<256, 64, 4, 2>>},
+    {70, "chunk<64,96>", v_run<launch_chunk<64, 96, 4, 2>>},
+    {71, "chunk<128,96>", v_run<launch_chunk<128, 96, 4, 2>>},
+    {72, "chunk<192,64>", v_run<launch_chunk<192, 64, 4, 2>>},
+    {73, "chunk<256,96>", v_run<launch_chunk<256, 96, 4, 2>>},
+    // LDS-DMA gather kernel (as 37..39, two-slot ring) with SUB 64-channel K-steps per barrier, <BM,BN>xSUB: the small-M layers
+    {74, "gbs<128,128>x2", v_gbig<128, 128, 2, 4, 2, 64, 2>}, // 128 KB
+    {75, "gbs<128,64>x2", v_gbig<128, 64, 2, 4, 2, 64, 2>},   // 96 KB
+    {76, "gbs<128,64>x3", v_gbig<128, 64, 2, 4, 2, 64, 3>},   // 144 KB
+    {77, "gbs<64,64>x4", v_gbig<64, 64, 2, 4, 2, 64, 4>},     // 128 KB
+    {78, "gbs<64,128>x3", v_gbig<64, 128, 2, 4, 2, 64, 3>},   // 144 KB
+    {79, "gbs<64,64>x2", v_gbig<64, 64, 2, 4, 2, 64, 2>},     // 64 KB: two blocks per CU
+    // "long run" kernels on the padded raster (k_conv3_run<..., PADO>: no padding selects)
+    {80, "runp<256,64>", v_run<launch_run<256, 64, 4, 2, false, true>>},
+    {81, "runp<256,128>", v_run<launch_run<256, 128, 4, 2, false, true>>},
+    {82, "runp<224,128>", v_run<launch_run<224, 128, 2, 4, false, true>>},
+    {83, "runp<320,64>", v_run<launch_run<320, 64, 4, 2, false, true>>},
+    {84, "runp<192,128>", v_run<launch_run<192, 128, 4, 2, false, true>>},
+    {85, "runp<128,64>", v_run<launch_run<128, 64, 2, 4, false, true>>},
+    // stride-2 "long run" kernels on the padded output raster
+    {86, "s2run<256,128>", v_run<launch_s2run<256, 128, 4, 2>, 2>},      // 147 KB
+    {87, "s2run<256,64>", v_run<launch_s2run<256, 64, 4, 2>, 2>},        // 123 KB
+    {88, "s2run<128,128>", v_run<launch_s2run<128, 128, 2, 4>, 2>},      // 99 KB
+    {89, "s2run<128,64>", v_run<launch_s2run<128, 64, 2, 4>, 2>},        // 75 KB: two blocks per CU
+#ifdef RVA_EXPERIMENTS
+    // 96..: timing-only experiment kernels of a private build (tools/exp_build.py), never in librva.so; 90..95 are unassigned
+    {96, "run<256,128> nosel", v_run_nosel<256, 128, 4, 2>},
+    {97, "run<256,64> nosel", v_run_nosel<256, 64, 4, 2>},
+#endif
+};
+
+constexpr int kConvRows = (int)(sizeof kConvVariants / sizeof kConvVariants[0]);
+#ifdef RVA_EXPERIMENTS
+constexpr int RVA_CONV_VARIANTS = kConvRows - 3, kConvVariantsMax = 99;       // two experiment rows
+#else
+constexpr int RVA_CONV_VARIANTS = kConvRows - 1, kConvVariantsMax = RVA_CONV_VARIANTS;      // 89, by rva_conv_num_variants()
+#endif
+
+constexpr bool conv_rows_numbered()
+{
+    for (int i = 0; i <= RVA_CONV_VARIANTS; ++i)
+        if (kConvVariants[i].number != i) return false;
+    return true;
+}
+static_assert(conv_rows_numbered(), "row i of kConvVariants carries variant number i: no gaps, no reordering");
+
+const ConvVariant *find_variant(int variant)
+{
+    if (variant >= 0 && variant <= RVA_CONV_VARIANTS) return &kConvVariants[variant];
+    for (int i = RVA_CONV_VARIANTS + 1; i < kConvRows; ++i)
+        if (kConvVariants[i].number == variant) return &kConvVariants[i];
+    return nullptr;
+}
+
+hipError_t launch_variant(int variant, const ConvCall &c) { return find_variant(variant)->launch(c); }
+
+// rva_conv1x1_upcat_f16 / the fused detect-head convolutions: k_conv_gbig<..., UP / HEAD> on one of the RVA_GATHER64_TILES
+template <bool UP, bool HEAD>
+int launch_gather64_1x1(rva_ctx *ctx, const char *who, ConvArgs &a, int variant, hipStream_t s)
+{
+    hipError_t ev;
+    switch (variant ? variant : 37) {
+#define RVA_CASE(n, name, ...) case n: ev = launch_gbig1<__VA_ARGS__, 1, 64, UP, HEAD>(a, s); break;
+    RVA_GATHER64_TILES(RVA_CASE)
+#undef RVA_CASE
+    default: return rva_fail(ctx, RVA_ERR_ARG, "%s: variant %d not applicable (0 or 33..39)", who, variant);
+    }
+    if (ev != hipSuccess) return rva_fail(ctx, RVA_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(ev));
+    return RVA_OK;
+}
+
 }  // namespace
 
-#define RVA_CONV_VARIANTS 89
-#ifdef RVA_EXPERIMENTS
-#define RVA_CONV_VARIANTS_MAX 99      // 96..: timing-only experiment kernels of a private build (tools/exp_build.py), never in librva.so
-#else
-#define RVA_CONV_VARIANTS_MAX RVA_CONV_VARIANTS
-#endif
+bool rva_conv_variant_is_gather64(int variant)
+{
+#define RVA_IS(n, ...) variant == n ||
+    return RVA_GATHER64_TILES(RVA_IS) false;
+#undef RVA_IS
+}
 
 extern "C" {
 #ifdef RVA_ROW_STAMPS
 int rva_dbg_read_stamps(unsigned long long *host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 8 * 256); }
 #endif
-
-// variant: 0 = heuristic choice; otherwise an explicit kernel (used by the plan's per-layer autotune):
-//   1..4  gather kernel  <BN,WPX> = <64,64> <64,32> <128,64> <128,32>
-//   5..8  resident kernel <BN,WPX> = <64,64> <64,32> <128,64> <128,32>   (stride 1 only)
-//   9..12 row-reuse kernel, same tile order                               (3x3 stride 1 only)
-//   13..16 gather kernel with 64-channel K-steps, same tile order         (Cin padded to 64)
-//   17..20 row-reuse kernel with two K-steps of loads in flight           (3x3 stride 1 only)
-//   21..24 large-tile LDS-DMA kernel <BM,BN> = <256,128> <128,128> <256,64> <128,64>, 3-slot ring (3x3 stride 1, Cin % 32 == 0)
-//   25..32 the same with a 2-slot ring, <192,128> <128,128> <256,64> <128,64> <224,128> <160,128> <384,64> <320,64>:
-//          two or three blocks per CU; the extra tile heights exist so that the tile count can fit whole rounds of the 256 CUs
-//   33..38 large-tile LDS-DMA gather kernel with 64-channel K-steps (1x1; 3x3 stride 1 or 2; Cin % 64 == 0):
-//          <256,128> <128,128> <256,64> <128,64> 3-slot, <128,128> <256,64> <192,128> 2-slot
-//   40..42 the same with 32-channel K-steps (Cin % 32 == 0): <256,64> 3-slot, <128,64> 3-slot, <256,64> 2-slot
-//   43..45 patch kernels for Cin = 32 (weights resident, input patch staged once per tile): 3x3 stride 2 with Cout <= 64;
-//          3x3 stride 1 with Cout <= 32, 4- and 8-row tiles
-//   46..51 patch kernels for 3x3 stride 1, Cin = 64, Cout <= 64 (double-buffered 4-row tile, 8-row tile, 4-row tile,
-//          double-buffered 8-row tile, and two forms with two output rows per wave)
-//   52..60 "long run" kernels: a 32-channel chunk's activation run staged once for the three vertical taps (3x3 stride 1)
-//   61..63 patch kernels for Cin = 64 with the output channels in two resident groups of 32
-//   64..65 LDS-DMA gather kernel with 256 x 256 tiles (64 MACs per staged byte; one block per CU): wave tile 64 x 128 / 128 x 64
-//   66     patch kernel with two wave sets half a tile period apart (3x3 stride 1, Cin = 64, Cout <= 64): 2 x 8 waves, one output row per wave
-//   67..73 "whole chunk per barrier" kernels for layers with few pixels (3x3 stride 1, Cin % 32 == 0): <BM,BN> = <128,64> <64,64>
-//          <256,64> <64,96> <128,96> <192,64> <256,96>; one barrier per 32-channel chunk (nine taps), one block per CU
-//   74..79 LDS-DMA gather kernel (as 33..39, two-slot ring) with SUB 64-channel K-steps per barrier: <BM,BN>xSUB = <128,128>x2 <128,64>x2
-//          <128,64>x3 <64,64>x4 <64,128>x3 <64,64>x2
-//   80..85 "long run" kernels on the padded raster (k_conv3_run<..., PADO>: no padding selects): <256,64> <256,128> <224,128> <320,64>
-//          <192,128> <128,64>
-int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
-                          int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
-                          int stride, int act, int variant, rva_stream_t stream_);
 
 int rva_conv2d_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
                         int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
@@ -3505,17 +3843,19 @@ int rva_conv2d_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weigh
                                  act, 0, stream_);
 }
 
+// variant: 0 = heuristic choice; otherwise the kernel of that row of kConvVariants (used by the plan's per-layer autotune)
 int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
                           int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
                           int stride, int act, int variant, rva_stream_t stream_)
 {
     if (!ctx) return RVA_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream_;
+    const ConvVariant *row = find_variant(variant);
     if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) ||
-        (stride != 1 && stride != 2) || Cin % 8 || Cout % 8 || ldi % 8 || ldo % 8 || (residual && ldr % 8) || variant < 0 || variant > RVA_CONV_VARIANTS_MAX ||
+        (stride != 1 && stride != 2) || Cin % 8 || Cout % 8 || ldi % 8 || ldo % 8 || (residual && ldr % 8) || !row ||
         ((uintptr_t)in | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)residual) % 16)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_conv2d_nhwc_f16: unsupported shape/alignment (Cin%%8, Cout%%8, ld%%8, 16-byte pointers)");
-    ConvArgs a{};
+    ConvCall c{};
+    ConvArgs &a = c.a;
     a.in = (const __half *)in; a.ldi = ldi; a.w = (const __half *)weights; a.bias = bias;
     a.out = (__half *)out; a.ldo = ldo; a.res = (const __half *)residual; a.ldr = ldr;
     a.H = H; a.W = W; a.Cin = Cin; a.CinPad = rva_ceil_div(Cin, 32) * 32; a.Cout = Cout; a.stride = stride; a.act = act;
@@ -3523,341 +3863,15 @@ int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *wei
     a.Ho = (H + 2 * pad - ksize) / stride + 1;
     a.Wo = (W + 2 * pad - ksize) / stride + 1;
     a.M = batch * a.Ho * a.Wo;
-    // tile choice: weights are padded to a multiple of 64 output channels by the caller (rva_conv_cout_pad)
-    const int cpad = rva_ceil_div(Cout, 64) * 64;
-    const bool bn128 = cpad % 128 == 0;
-    if (!ctx->num_cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-        if (ctx->num_cus <= 0) ctx->num_cus = 256;
-    }
-    const int num_cus = ctx->num_cus;
-    if (variant == 0) {
-        // heuristic (callers that do not autotune): the LDS-DMA kernels wherever their channel constraints hold,
-        // tile picked from the autotune tables of the YOLOv8 layers (tools/show_tuning.py)
-        int pick = 0;
-        if (ksize == 3 && stride == 1 && Cin % 32 == 0)
-            pick = cpad % 128 == 0 ? ((long)a.M * Cout >= 20000000L ? 25 : 21) : (a.M >= 100000 ? 31 : 23);
-        else if (Cin % 64 == 0 && (ksize == 3 || stride == 1))
-            pick = 37;
-        if (pick) {
-            const int rc = rva_conv2d_nhwc_f16_v(ctx, in, ldi, weights, bias, out, ldo, residual, ldr, batch, H, W, Cin, Cout, ksize,
-                                                 stride, act, pick, stream_);
-            if (rc == RVA_OK) return rc;
-        }
-    }
-    if (variant >= 86 && variant <= 89) {
-        // stride-2 "long run" kernels on the padded output raster: see k_conv3_s2run
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 2) {
-            RunArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            switch (variant) {
-            case 86: ev = launch_s2run<256, 128, 4, 2>(g, s); break;     // 147 KB
-            case 87: ev = launch_s2run<256, 64, 4, 2>(g, s); break;      // 123 KB
-            case 88: ev = launch_s2run<128, 128, 2, 4>(g, s); break;     // 99 KB
-            default: ev = launch_s2run<128, 64, 2, 4>(g, s); break;      // 75 KB: two blocks per CU
-            }
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 80 && variant <= 85) {
-        // "long run" kernels on the padded raster (no padding selects in the MFMA phase): see k_conv3_run<..., PADO>
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 1) {
-            RunArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            switch (variant) {
-            case 80: ev = launch_run<256, 64, 4, 2, false, true>(g, s); break;
-            case 81: ev = launch_run<256, 128, 4, 2, false, true>(g, s); break;
-            case 82: ev = launch_run<224, 128, 2, 4, false, true>(g, s); break;
-            case 83: ev = launch_run<320, 64, 4, 2, false, true>(g, s); break;
-            case 84: ev = launch_run<192, 128, 4, 2, false, true>(g, s); break;
-            default: ev = launch_run<128, 64, 2, 4, false, true>(g, s); break;
-            }
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-#ifdef RVA_EXPERIMENTS
-    if (variant >= 96) {
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 1) {
-            RunArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            const char *nosel = getenv("RVA_NOSEL");      // the select-free kernels give wrong border pixels: opt-in per process
-            if (variant == 96) { if (nosel && nosel[0] == '1') ev = launch_run<256, 128, 4, 2, true>(g, s); }       // run<256,128> without the padding selects
-            else if (variant == 97) { if (nosel && nosel[0] == '1') ev = launch_run<256, 64, 4, 2, true>(g, s); }   // run<256,64> without the padding selects
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, RVA_ERR_ARG, "experiment variant %d not applicable here", variant);
-    }
-#endif
-    if (variant >= 74) {
-        // LDS-DMA gather kernel with several 64-channel K-steps per barrier (1x1, 3x3 of either stride; Cin % 64 == 0): the small-M layers
-        a.CoutPad = cpad;
-        if (ksize == 1 && stride != 1) return rva_fail(ctx, RVA_ERR_ARG, "conv variant %d not applicable here", variant);
-        hipError_t ev;
-        switch (variant) {
-        case 74: ev = launch_gbig<128, 128, 2, 4, 2, 64, 2>(a, ksize, s); break;   // 128 KB
-        case 75: ev = launch_gbig<128, 64, 2, 4, 2, 64, 2>(a, ksize, s); break;    // 96 KB
-        case 76: ev = launch_gbig<128, 64, 2, 4, 2, 64, 3>(a, ksize, s); break;    // 144 KB
-        case 77: ev = launch_gbig<64, 64, 2, 4, 2, 64, 4>(a, ksize, s); break;     // 128 KB
-        case 78: ev = launch_gbig<64, 128, 2, 4, 2, 64, 3>(a, ksize, s); break;    // 144 KB
-        default: ev = launch_gbig<64, 64, 2, 4, 2, 64, 2>(a, ksize, s); break;     // 64 KB: two blocks per CU
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 67) {
-        // "whole chunk per barrier" kernels (3x3 stride 1, Cin % 32 == 0): the small-M layers, see k_conv3_chunk
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 1) {
-            RunArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            switch (variant) {
-            case 67: ev = launch_chunk<128, 64, 4, 2>(g, s); break;
-            case 68: ev = launch_chunk<64, 64, 2, 4>(g, s); break;
-            case 69: ev = launch_chunk<256, 64, 4, 2>(g, s); break;
-            case 70: ev = launch_chunk<64, 96, 4, 2>(g, s); break;
-            case 71: ev = launch_chunk<128, 96, 4, 2>(g, s); break;
-            case 72: ev = launch_chunk<192, 64, 4, 2>(g, s); break;
-            default: ev = launch_chunk<256, 96, 4, 2>(g, s); break;
-            }
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 66) {
-        // patch kernel with two wave sets half a tile period apart (3x3 stride 1, Cin = 64, Cout <= 64)
-        hipError_t ev = hipErrorInvalidValue;
-        S2Args g{a.in, ldi, a.w, bias, a.out, ldo, a.res, ldr, batch, H, W, a.Ho, a.Wo, Cout, cpad, act, 0, 0, 0};
-        // sixteen waves: two sets of eight, one output row per wave -- two MFMA waves per SIMD in every phase.  (The 2 x 4 waves x
-        // two rows form, one 256-register MFMA wave per SIMD, measured 27.0 us against 25.6 us at 80 x 80 and was dropped.)
-        if (ksize == 3 && stride == 1 && Cin == 64 && Cout <= 64) ev = launch_patch2<64, 64, 8, 1>(g, num_cus, s);
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 64) {
-        // LDS-DMA gather kernel with 256-channel output tiles: 43-64 MACs per staged byte against 32 of the 128 x 128 tile.  The CU's
-        // vector-memory path moves 64 B/clk, its MFMAs 4096 MAC/clk: below 64 MAC/B the staging, not the matrix pipe, caps a
-        // 1x1 convolution (a plain GEMM, no tap reuse).  One block per CU.
-        a.CoutPad = cpad;
-        if (ksize == 1 && stride != 1) return rva_fail(ctx, RVA_ERR_ARG, "conv variant %d not applicable here", variant);
-        hipError_t ev;
-        // (measured and dropped: <128,256> tiles, three- and four-slot rings with 32-channel steps -- more bytes in flight per CU
-        //  did not help the memory-latency-bound 1x1 layers, profiles/r02_conv_tuning.txt)
-        if (variant == 64) ev = launch_gbig<256, 256, 4, 2, 2>(a, ksize, s);     // 128 KB ring, wave tile 64 x 128
-        else ev = launch_gbig<256, 256, 2, 4, 2>(a, ksize, s);                   // 128 KB ring, wave tile 128 x 64
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 52 && variant <= 60) {
-        // "long run" LDS-DMA kernels (3x3 stride 1, Cin % 32 == 0): a chunk's activation run staged once for all three dy
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 1) {
-            RunArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            switch (variant) {
-            case 52: ev = launch_run<256, 64, 4, 2>(g, s); break;
-            case 53: ev = launch_run<128, 64, 2, 4>(g, s); break;
-            case 54: ev = launch_run<384, 64, 8, 1>(g, s); break;
-            case 55: ev = launch_run<192, 128, 4, 2>(g, s); break;
-            case 56: ev = launch_run<256, 128, 4, 2>(g, s); break;
-            case 57: ev = launch_run<128, 128, 2, 4>(g, s); break;
-            case 58: ev = launch_run<224, 128, 2, 4>(g, s); break;    // tile heights that fit whole rounds of the 256 CUs better
-            case 59: ev = launch_run<160, 128, 2, 4>(g, s); break;
-            default: ev = launch_run<320, 64, 4, 2>(g, s); break;
-            }
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 43) {
-        // patch kernels (weights resident in LDS): Cin = 32: 43 = 3x3 stride 2, Cout <= 64 (the first downsampling
-        // convolution); 44 / 45 = 3x3 stride 1, Cout <= 32, tiles of 4 / 8 rows (the 32 -> 32 bottleneck convolutions)
-        hipError_t ev = hipErrorInvalidValue;
-        S2Args g{a.in, ldi, a.w, bias, a.out, ldo, a.res, ldr, batch, H, W, a.Ho, a.Wo, Cout, cpad, act, 0, 0, 0};
-        if (ksize == 3 && Cin == 32) {
-            if (variant == 43 && stride == 2 && Cout <= 64) ev = launch_patch<2, 32, 64, 4, 1>(g, num_cus, s);
-            else if (variant == 44 && stride == 1 && Cout <= 32) ev = launch_patch<1, 32, 32, 4, 1>(g, num_cus, s);
-            else if (variant == 45 && stride == 1 && Cout <= 32) ev = launch_patch<1, 32, 32, 8, 1>(g, num_cus, s);
-        } else if (ksize == 3 && Cin == 64 && stride == 1 && Cout <= 64) {
-            // 64 -> 64: 72 KB of weights resident, one block per CU
-            if (variant == 46) ev = launch_patch<1, 64, 64, 4, 2>(g, num_cus, s);         // 124 KB, two patch buffers
-            else if (variant == 47) ev = launch_patch<1, 64, 64, 8, 1>(g, num_cus, s);    // 116 KB, eight waves, one buffer
-            else if (variant == 48) ev = launch_patch<1, 64, 64, 4, 1>(g, num_cus, s);    // 98 KB
-            else if (variant == 49) ev = launch_patch<1, 64, 64, 8, 2>(g, num_cus, s);    // 158 KB: eight waves, two patch buffers
-            else if (variant == 50) ev = launch_patch<1, 64, 64, 4, 2, 2>(g, num_cus, s); // 158 KB: four waves x two rows, two buffers
-            else if (variant == 51) ev = launch_patch<1, 64, 64, 8, 1, 2>(g, num_cus, s); // 149 KB: 16-row tile, eight waves x two rows
-            // output channels in two groups of 32: 36 KB of weights per block, two blocks per CU
-            else if (variant == 61) ev = launch_patch<1, 64, 32, 8, 1, 1>(g, num_cus, s); // 79 KB: 8-row tile
-            else if (variant == 62) ev = launch_patch<1, 64, 32, 4, 1, 1>(g, num_cus, s); // 62 KB: 4-row tile
-            else if (variant == 63) ev = launch_patch<1, 64, 32, 4, 1, 2>(g, num_cus, s); // 79 KB: 8-row tile, four waves x two rows
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 33) {
-        // large-tile LDS-DMA gather kernel, 64-channel K-steps (1x1, and 3x3 of either stride; Cin % 64 == 0)
-        a.CoutPad = cpad;
-        if (ksize == 1 && stride != 1) return rva_fail(ctx, RVA_ERR_ARG, "conv variant %d not applicable here", variant);
-        hipError_t ev;
-        switch (variant) {
-        case 33: ev = launch_gbig<256, 128, 4, 2, 3>(a, ksize, s); break;    // 144 KB, one block per CU
-        case 34: ev = launch_gbig<128, 128, 2, 4, 3>(a, ksize, s); break;    // 96 KB
-        case 35: ev = launch_gbig<256, 64, 4, 2, 3>(a, ksize, s); break;     // 120 KB
-        case 36: ev = launch_gbig<128, 64, 2, 4, 3>(a, ksize, s); break;     // 72 KB: two blocks per CU
-        case 37: ev = launch_gbig<128, 128, 2, 4, 2>(a, ksize, s); break;    // 64 KB: two blocks per CU
-        case 38: ev = launch_gbig<256, 64, 4, 2, 2>(a, ksize, s); break;     // 80 KB: two blocks per CU
-        case 39: ev = launch_gbig<192, 128, 4, 2, 2>(a, ksize, s); break;    // 80 KB: two blocks per CU
-        // 32-channel K-steps (64-byte rows, swz32): the layers with Cin = 32 / 96
-        case 40: ev = launch_gbig<256, 64, 4, 2, 3, 32>(a, ksize, s); break; // 60 KB: two blocks per CU
-        case 41: ev = launch_gbig<128, 64, 2, 4, 3, 32>(a, ksize, s); break; // 36 KB: four blocks per CU
-        default: ev = launch_gbig<256, 64, 4, 2, 2, 32>(a, ksize, s); break; // 40 KB: three blocks per CU
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant >= 21) {
-        // large-tile LDS-DMA kernel (3x3 stride 1, Cin % 32 == 0)
-        hipError_t ev = hipErrorInvalidValue;
-        if (ksize == 3 && stride == 1) {
-            BigArgs g{};
-            g.in = a.in; g.ldi = ldi; g.w = a.w; g.bias = bias; g.out = a.out; g.ldo = ldo; g.res = a.res; g.ldr = ldr;
-            g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.CoutPad = rva_ceil_div(Cout, 64) * 64; g.act = act; g.M = a.M;
-            switch (variant) {
-            case 21: ev = launch_big<256, 128, 4, 2, 3>(g, s); break;
-            case 22: ev = launch_big<128, 128, 2, 4, 3>(g, s); break;
-            case 23: ev = launch_big<256, 64, 4, 2, 3>(g, s); break;
-            case 24: ev = launch_big<128, 64, 2, 4, 3>(g, s); break;
-            case 25: ev = launch_big<192, 128, 4, 2, 2>(g, s); break;     // 74 KB: two blocks per CU
-            case 26: ev = launch_big<128, 128, 2, 4, 2>(g, s); break;     // 66 KB: two blocks per CU
-            case 27: ev = launch_big<256, 64, 4, 2, 2>(g, s); break;      // 58 KB: two blocks per CU
-            case 28: ev = launch_big<128, 64, 2, 4, 2>(g, s); break;      // 42 KB: three blocks per CU
-            case 29: ev = launch_big<224, 128, 2, 4, 2>(g, s); break;     // 78 KB: two blocks per CU
-            case 30: ev = launch_big<160, 128, 2, 4, 2>(g, s); break;     // 70 KB
-            case 31: ev = launch_big<384, 64, 8, 1, 2>(g, s); break;      // 74 KB
-            default: ev = launch_big<320, 64, 4, 2, 2>(g, s); break;      // 66 KB
-            }
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (variant) {
-        const int v = (variant - 1) & 3;                      // 0:<64,64> 1:<64,32> 2:<128,64> 3:<128,32>
-        const int vbn = v >= 2 ? 128 : 64, vwpx = (v & 1) ? 32 : 64;
-        if (vbn == 128 && !bn128) return rva_fail(ctx, RVA_ERR_ARG, "variant needs Cout padded to 128");
-        hipError_t ev = hipErrorInvalidValue;
-        if (variant <= 4) {
-            a.n_tiles = cpad / vbn;
-            a.m_tiles = rva_ceil_div(a.M, 4 * vwpx);
-#define RVA_V(BN_, WPX_) (ksize == 1 ? launch_conv<BN_, WPX_, 1>(a, s) : launch_conv<BN_, WPX_, 3>(a, s))
-            ev = v == 0 ? RVA_V(64, 64) : v == 1 ? RVA_V(64, 32) : v == 2 ? RVA_V(128, 64) : RVA_V(128, 32);
-#undef RVA_V
-        } else if (variant >= 17) {
-            if (ksize == 3 && stride == 1) {
-                RowArgs rr{};
-                rr.in = a.in; rr.ldi = ldi; rr.w = a.w; rr.bias = bias; rr.out = a.out; rr.ldo = ldo; rr.res = a.res; rr.ldr = ldr;
-                rr.H = H; rr.W = W; rr.Cin = Cin; rr.CinPad = a.CinPad; rr.Cout = Cout; rr.act = act;
-                rr.n_tiles = cpad / vbn;
-                ev = v == 0 ? launch_row<64, 64, true>(rr, batch, s) : v == 1 ? launch_row<64, 32, true>(rr, batch, s)
-                   : v == 2 ? launch_row<128, 64, true>(rr, batch, s) : launch_row<128, 32, true>(rr, batch, s);
-            }
-        } else if (variant >= 13) {
-            a.n_tiles = cpad / vbn;
-            a.m_tiles = rva_ceil_div(a.M, 4 * vwpx);
-#define RVA_V64(BN_, WPX_) (ksize == 1 ? launch_conv<BN_, WPX_, 1, 64>(a, s) : launch_conv<BN_, WPX_, 3, 64>(a, s))
-            ev = v == 0 ? RVA_V64(64, 64) : v == 1 ? RVA_V64(64, 32) : v == 2 ? RVA_V64(128, 64) : RVA_V64(128, 32);
-#undef RVA_V64
-        } else if (variant >= 9) {
-            if (ksize == 3 && stride == 1) {
-                RowArgs rr{};
-                rr.in = a.in; rr.ldi = ldi; rr.w = a.w; rr.bias = bias; rr.out = a.out; rr.ldo = ldo; rr.res = a.res; rr.ldr = ldr;
-                rr.H = H; rr.W = W; rr.Cin = Cin; rr.CinPad = a.CinPad; rr.Cout = Cout; rr.act = act;
-                rr.n_tiles = cpad / vbn;
-                ev = v == 0 ? launch_row<64, 64>(rr, batch, s) : v == 1 ? launch_row<64, 32>(rr, batch, s)
-                   : v == 2 ? launch_row<128, 64>(rr, batch, s) : launch_row<128, 32>(rr, batch, s);
-            }
-        } else if (stride == 1) {
-            ResArgs ra{};
-            ra.in = a.in; ra.ldi = ldi; ra.w = a.w; ra.bias = bias; ra.out = a.out; ra.ldo = ldo; ra.res = a.res; ra.ldr = ldr;
-            ra.H = H; ra.W = W; ra.Cin = Cin; ra.CinPad = a.CinPad; ra.Cout = Cout; ra.act = act; ra.M = a.M;
-            ra.n_tiles = cpad / vbn;
-            if (ksize == 3)
-                ev = v == 0 ? launch_res<64, 64, 3, 32, 9>(ra, batch, num_cus, s) : v == 1 ? launch_res<64, 32, 3, 32, 11>(ra, batch, num_cus, s)
-                   : v == 2 ? launch_res<128, 64, 3, 32, 9>(ra, batch, num_cus, s) : launch_res<128, 32, 3, 32, 11>(ra, batch, num_cus, s);
-            else if (a.CinPad % 128 == 0)
-                ev = v == 0 ? launch_res<64, 64, 1, 128, 16>(ra, batch, num_cus, s) : v == 1 ? launch_res<64, 32, 1, 128, 8>(ra, batch, num_cus, s)
-                   : v == 2 ? launch_res<128, 64, 1, 128, 16>(ra, batch, num_cus, s) : hipErrorInvalidValue;
-            else
-                ev = v == 0 ? launch_res<64, 64, 1, 32, 4>(ra, batch, num_cus, s) : v == 1 ? launch_res<64, 32, 1, 32, 2>(ra, batch, num_cus, s)
-                   : hipErrorInvalidValue;
-        }
-        if (ev == hipSuccess) return RVA_OK;
-        (void)hipGetLastError();
-        return rva_fail(ctx, ev == hipErrorInvalidValue ? RVA_ERR_ARG : RVA_ERR_HIP, "conv variant %d not applicable here", variant);
-    }
-    if (stride == 1) {
-        ResArgs ra{};
-        ra.in = a.in; ra.ldi = ldi; ra.w = a.w; ra.bias = bias; ra.out = a.out; ra.ldo = ldo; ra.res = a.res; ra.ldr = ldr;
-        ra.H = H; ra.W = W; ra.Cin = Cin; ra.CinPad = a.CinPad; ra.Cout = Cout; ra.act = act; ra.M = a.M;
-#ifdef RVA_ROW_STAMPS
-        { const char *e = getenv("RVA_CONV_DBG"); ra.dbg = e ? atoi(e) : 0; }
-#endif
-        const bool bn128 = cpad % 128 == 0;
-        hipError_t e2 = hipErrorInvalidValue;
-        if (ksize == 3) {
-            // tile = 256 px x 128 ch when that yields enough tiles for every CU, else smaller tiles
-            const long t256 = (long)batch * rva_ceil_div(H * W, 256), t128 = (long)batch * rva_ceil_div(H * W, 128);
-            if (bn128 && t256 * (cpad / 128) >= 2 * num_cus) { ra.n_tiles = cpad / 128; e2 = launch_res<128, 64, 3, 32, 9>(ra, batch, num_cus, s); }
-            if (e2 == hipErrorInvalidValue && t256 * (cpad / 64) >= 2 * num_cus) { ra.n_tiles = cpad / 64; e2 = launch_res<64, 64, 3, 32, 9>(ra, batch, num_cus, s); }
-            if (e2 == hipErrorInvalidValue && bn128 && t128 * (cpad / 128) >= 2 * num_cus) { ra.n_tiles = cpad / 128; e2 = launch_res<128, 32, 3, 32, 11>(ra, batch, num_cus, s); }
-            if (e2 == hipErrorInvalidValue) { ra.n_tiles = cpad / 64; e2 = launch_res<64, 32, 3, 32, 11>(ra, batch, num_cus, s); }
-        } else if (a.CinPad % 128 == 0) {
-            const long t256 = rva_ceil_div(a.M, 256);
-            if (bn128 && t256 * (cpad / 128) >= 2 * num_cus) { ra.n_tiles = cpad / 128; e2 = launch_res<128, 64, 1, 128, 16>(ra, batch, num_cus, s); }
-            if (e2 == hipErrorInvalidValue && t256 * (cpad / 64) >= 2 * num_cus) { ra.n_tiles = cpad / 64; e2 = launch_res<64, 64, 1, 128, 16>(ra, batch, num_cus, s); }
-            if (e2 == hipErrorInvalidValue) { ra.n_tiles = cpad / 64; e2 = launch_res<64, 32, 1, 128, 8>(ra, batch, num_cus, s); }
-        } else {
-            const long t256 = rva_ceil_div(a.M, 256);
-            if (t256 * (cpad / 64) >= 2 * num_cus) { ra.n_tiles = cpad / 64; e2 = launch_res<64, 64, 1, 32, 4>(ra, batch, num_cus, s); }
-            else { ra.n_tiles = cpad / 64; e2 = launch_res<64, 32, 1, 32, 2>(ra, batch, num_cus, s); }
-        }
-        if (e2 == hipSuccess) return RVA_OK;
-        if (e2 != hipErrorInvalidValue) return rva_fail(ctx, RVA_ERR_HIP, "resident conv launch failed: %s", hipGetErrorString(e2));
-        (void)hipGetLastError();   // geometry does not fit the resident kernel: fall through to the gather kernel
-    }
-    a.n_tiles = cpad / (bn128 ? 128 : 64);
-    // small problems: 128-pixel tiles keep more CUs busy
-    const bool small = (long)rva_ceil_div(a.M, 256) * a.n_tiles < 512;
-    const int BM = small ? 128 : 256;
-    a.m_tiles = rva_ceil_div(a.M, BM);
-    hipError_t e;
-#define RVA_CONV(BN_, WPX_)                                                  \
-    (ksize == 1 ? launch_conv<BN_, WPX_, 1>(a, s) : launch_conv<BN_, WPX_, 3>(a, s))
-    if (bn128) e = small ? RVA_CONV(128, 32) : RVA_CONV(128, 64);
-    else e = small ? RVA_CONV(64, 32) : RVA_CONV(64, 64);
-#undef RVA_CONV
-    if (e != hipSuccess) return rva_fail(ctx, RVA_ERR_HIP, "conv launch failed: %s", hipGetErrorString(e));
-    return RVA_OK;
+    c.batch = batch; c.ksize = ksize;
+    c.cpad = rva_ceil_div(Cout, 64) * 64;
+    c.num_cus = rva_num_cus(ctx);
+    c.s = (hipStream_t)stream_;
+    const hipError_t ev = row->launch(c);
+    if (ev == hipSuccess) return RVA_OK;
+    (void)hipGetLastError();
+    if (ev == hipErrorInvalidValue) return rva_fail(ctx, RVA_ERR_ARG, "conv variant %d not applicable here", variant);
+    return rva_fail(ctx, RVA_ERR_HIP, "conv variant %d: launch failed: %s", variant, hipGetErrorString(ev));
 }
 
 int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, const void *skip, int ld_skip, int c_skip,
@@ -3874,21 +3888,7 @@ int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, 
     a.w = (const __half *)weights; a.bias = bias; a.out = (__half *)out; a.ldo = ldo; a.res = nullptr; a.ldr = 0;
     a.H = H; a.W = W; a.Cin = c_low + c_skip; a.CinPad = a.Cin; a.Cout = Cout; a.stride = 1; a.act = act;
     a.Ho = H; a.Wo = W; a.M = batch * H * W; a.CoutPad = rva_ceil_div(Cout, 64) * 64;
-    hipStream_t s = (hipStream_t)stream_;
-    hipError_t ev;
-    switch (variant) {
-    case 33: ev = launch_gbig1<256, 128, 4, 2, 3, 1, 64, true>(a, s); break;
-    case 34: ev = launch_gbig1<128, 128, 2, 4, 3, 1, 64, true>(a, s); break;
-    case 35: ev = launch_gbig1<256, 64, 4, 2, 3, 1, 64, true>(a, s); break;
-    case 36: ev = launch_gbig1<128, 64, 2, 4, 3, 1, 64, true>(a, s); break;
-    case 0:
-    case 37: ev = launch_gbig1<128, 128, 2, 4, 2, 1, 64, true>(a, s); break;
-    case 38: ev = launch_gbig1<256, 64, 4, 2, 2, 1, 64, true>(a, s); break;
-    case 39: ev = launch_gbig1<192, 128, 4, 2, 2, 1, 64, true>(a, s); break;
-    default: return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_upcat_f16: variant %d not applicable (0 or 33..39)", variant);
-    }
-    if (ev != hipSuccess) return rva_fail(ctx, RVA_ERR_HIP, "rva_conv1x1_upcat_f16: launch failed: %s", hipGetErrorString(ev));
-    return RVA_OK;
+    return launch_gather64_1x1<true, false>(ctx, "rva_conv1x1_upcat_f16", a, variant, (hipStream_t)stream_);
 }
 
 static int conv1x1_head(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
@@ -3907,21 +3907,7 @@ static int conv1x1_head(rva_ctx *ctx, const void *in, int ldi, const void *weigh
     a.hout = (__half *)out; a.hmode = mode; a.hnc = nc; a.hA = anchors_total; a.ha0 = anchor_offset; a.hW = W; a.hHW = H * W;
     a.hstride = stride_px;
     a.hbox = boxes32;
-    hipStream_t s = (hipStream_t)stream_;
-    hipError_t ev;
-    switch (variant) {
-    case 33: ev = launch_gbig1<256, 128, 4, 2, 3, 1, 64, false, true>(a, s); break;
-    case 34: ev = launch_gbig1<128, 128, 2, 4, 3, 1, 64, false, true>(a, s); break;
-    case 35: ev = launch_gbig1<256, 64, 4, 2, 3, 1, 64, false, true>(a, s); break;
-    case 36: ev = launch_gbig1<128, 64, 2, 4, 3, 1, 64, false, true>(a, s); break;
-    case 0:
-    case 37: ev = launch_gbig1<128, 128, 2, 4, 2, 1, 64, false, true>(a, s); break;
-    case 38: ev = launch_gbig1<256, 64, 4, 2, 2, 1, 64, false, true>(a, s); break;
-    case 39: ev = launch_gbig1<192, 128, 4, 2, 2, 1, 64, false, true>(a, s); break;
-    default: return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_f16: variant %d not applicable (0 or 33..39)", variant);
-    }
-    if (ev != hipSuccess) return rva_fail(ctx, RVA_ERR_HIP, "rva_conv1x1_head_f16: launch failed: %s", hipGetErrorString(ev));
-    return RVA_OK;
+    return launch_gather64_1x1<false, true>(ctx, "rva_conv1x1_head_f16", a, variant, (hipStream_t)stream_);
 }
 
 int rva_conv1x1_head_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
@@ -3943,7 +3929,13 @@ int rva_conv1x1_head_box32_f16(rva_ctx *ctx, const void *in, int ldi, const void
 
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }
 
-int rva_conv_num_variants(void) { return RVA_CONV_VARIANTS_MAX; }
+int rva_conv_num_variants(void) { return kConvVariantsMax; }
+
+const char *rva_conv_variant_name(int variant)
+{
+    const ConvVariant *row = find_variant(variant);
+    return row ? row->name : nullptr;
+}
 
 int rva_stem_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
                       int batch, int H, int W, int Cout, rva_stream_t stream_)
@@ -3970,16 +3962,11 @@ int rva_c2f_pair32_f16(rva_ctx *ctx, const void *in, int ldi, const void *w1, co
         return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: bad argument");
     if ((((size_t)in) | ((size_t)out) | ((size_t)w1) | ((size_t)w2)) & 15) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: 16-byte aligned tensors");
     if ((size_t)batch * H * W >= (1ull << 31)) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: tensor too large");
-    if (!ctx->num_cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-        if (ctx->num_cus <= 0) ctx->num_cus = 256;
-    }
     PairArgs a{(const __half *)in, ldi, (const __half *)w1, b1, (const __half *)w2, b2, (__half *)out, ldo, batch, H, W,
                rva_ceil_div(W, PR_TW), rva_ceil_div(H, PR_TH), 0};
     a.total = a.tiles_x * a.tiles_y * batch;
     RVA_HIP(ctx, rva_func_smem((const void *)k_c2f_pair32, PR_SMEM));
-    int grid = 2 * ctx->num_cus;
+    int grid = 2 * rva_num_cus(ctx);
     if (grid > a.total) grid = a.total;
     k_c2f_pair32<<<grid, 256, PR_SMEM, (hipStream_t)stream_>>>(a);
     RVA_HIP(ctx, hipGetLastError());
@@ -3999,12 +3986,7 @@ int rva_stem2_f16(rva_ctx *ctx, const void *in_planar, const void *w1, const flo
     a.total = a.tiles_x * a.tiles_y * batch;
     constexpr size_t smem = S2_SMEM;
     RVA_HIP(ctx, rva_func_smem((const void *)k_stem2, smem));
-    if (!ctx->num_cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-        if (ctx->num_cus <= 0) ctx->num_cus = 256;
-    }
-    int grid = ctx->num_cus;                               // persistent: one block per CU (159 KB of LDS each)
+    int grid = rva_num_cus(ctx);                           // persistent: one block per CU (159 KB of LDS each)
     if (grid > a.total) grid = a.total;
     k_stem2<<<grid, 1024, smem, (hipStream_t)stream_>>>(a);
     RVA_HIP(ctx, hipGetLastError());

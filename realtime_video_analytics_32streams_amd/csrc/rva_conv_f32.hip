@@ -309,12 +309,7 @@ int rva_conv2d_nhwc_f32_v(rva_ctx *ctx, const void *in, int ldi, const void *wei
     a.B = batch; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = ksize; a.stride = stride; a.pad = ksize / 2; a.act = act;
     a.Ho = (H + 2 * a.pad - ksize) / stride + 1; a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
     a.M = (long)batch * a.Ho * a.Wo;
-    if (!ctx->num_cus) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
-        if (ctx->num_cus <= 0) ctx->num_cus = 256;
-    }
-    const int v = variant ? variant : conv_f32_heuristic(a.M, Cout, ctx->num_cus);
+    const int v = variant ? variant : conv_f32_heuristic(a.M, Cout, rva_num_cus(ctx));
     const dim3 g = conv_f32_grid(v, a.M, Cout);
     if (Cin % 32 == 0) launch_conv_f32<32>(v, g, (hipStream_t)stream_, a);
     else launch_conv_f32<16>(v, g, (hipStream_t)stream_, a);

@@ -23,6 +23,16 @@ hipError_t rva_func_smem(const void *fn, size_t bytes)
     return hipSuccess;
 }
 
+int rva_num_cus(rva_ctx *ctx)
+{
+    if (!ctx->num_cus) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) ctx->num_cus = prop.multiProcessorCount;
+        if (ctx->num_cus <= 0) ctx->num_cus = 256;
+    }
+    return ctx->num_cus;
+}
+
 extern "C" {
 
 int rva_abi_version(void) { return RVA_ABI_VERSION; }

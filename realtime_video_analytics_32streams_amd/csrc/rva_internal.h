@@ -75,5 +75,11 @@ static inline int rva_ceil_div(int a, int b) { return (a + b - 1) / b; }
 // reached for the first time inside a stream capture: callers run one eager launch of every kernel before capturing.
 hipError_t rva_func_smem(const void *fn, size_t bytes);
 
+// multiProcessorCount of ctx->device, read once into ctx->num_cus (256 if the query fails)
+int rva_num_cus(rva_ctx *ctx);
+
+// true for the variants of rva_conv2d_nhwc_f16_v that the fused 1x1 forms (rva_conv1x1_upcat_f16, rva_conv1x1_head_*) also take
+bool rva_conv_variant_is_gather64(int variant);
+
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);

@@ -470,7 +470,7 @@ bool variant_fits(const Step &s, int variant)
 {
     if (s.kind == K_CONV) return variant >= 0;
     if (s.kind == K_CONV_F32) return variant >= 0 && variant <= rva_conv_f32_num_variants();
-    return variant == 0 || (variant >= 33 && variant <= 39);     // upcat / head: the LDS-DMA gather family
+    return variant == 0 || rva_conv_variant_is_gather64(variant);     // upcat / head: the LDS-DMA gather family
 }
 
 }  // namespace

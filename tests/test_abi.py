@@ -27,6 +27,10 @@ def test_library_builds_and_exports_header_symbols():
         assert hasattr(L, name), f"{name} declared in rva.h but not exported"
     assert sorted(N.EXPORTS) == declared, "python binding table out of sync with rva.h"
     assert L.rva_abi_version() == 1
+    L.rva_conv_variant_name.restype = ctypes.c_char_p
+    names = [L.rva_conv_variant_name(v) for v in range(1, L.rva_conv_num_variants() + 1)]
+    assert all(names) and len(set(names)) == len(names), "a convolution variant number without a name of its own"
+    assert L.rva_conv_variant_name(0) == b"auto" and L.rva_conv_variant_name(len(names) + 1) is None
 
 
 def test_letterbox_meta_matches_golden():
