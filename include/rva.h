@@ -537,6 +537,48 @@ int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *plan, const void *logits, const 
                               void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The 3D-CNN clip network as ONE fp32 object -- replaces the network call of the reference's 3D-CNN head and its top-5
+ * (CNN3DDetector._predict_sequence, temporal_detector.py:596-641; the network is Dummy3DCNN of
+ * scripts/convert_temporal_model_to_onnx.py:91-121), for `half: false`.  Per clip [3][T][H][W]: Conv3d(3,64,3,p1)+BN+ReLU ->
+ * MaxPool3d((1,2,2)) -> Conv3d(64,128,3,p1)+BN+ReLU -> MaxPool3d(2) -> Conv3d(128,256,3,p1)+BN+ReLU -> mean over T,H,W ->
+ * Linear(256 -> classes).  The pools floor as torch's do (trailing odd rows, columns and frames are dropped).
+ *
+ * rva_cnn3d_plan_create: `weights` = fp32 host arrays in the field order of rva_cnn3d_weights (all required), each conv with
+ *   its BatchNorm folded in: conv1 weight [64][3][3][3][3] = [co][ci][kt][ky][kx] (the checkpoint's layout) and bias [64];
+ *   conv2 weight [128][27][64] and conv3 weight [256][27][128] = [co][tap = (kt*3 + ky)*3 + kx][ci] (channels innermost: what
+ *   the kernels read) with biases [128] / [256]; head weight [classes][256] and bias [classes].  The plan copies them and
+ *   allocates its whole workspace for desc.max_clips clips (height, width >= 4, frames >= 2, classes 1..16384, max_clips *
+ *   frames <= 65535); a workspace larger than the free device memory is refused with RVA_ERR_CAPACITY.
+ * rva_cnn3d_plan_run: frames = a device ring of planar fp32 frames [3][height][width] (what rva_preprocess_frames_* writes
+ *   with RVA_NORM_VIDEO_F32); frame_index = device int32 [n_clips * frames]: frame t of clip b is ring + frame_index[b*T+t] *
+ *   3*height*width, and its temporal neighbours are entries b*T+t-1 and b*T+t+1 (zero padding at the clip's ends; no gathered
+ *   or permuted copy).  logits = device fp32 [n_clips][classes], the raw outputs.  Every launch goes to `stream`; no host
+ *   synchronisation, no allocation: capturable.  Each sum runs in one fixed order (no split-K that follows the grid, no
+ *   atomics): a clip's logits are bit-identical for every batch size, position in the batch and launch mode.
+ * rva_cnn3d_plan_run_post: the arguments and the rule of rva_cnnlstm_plan_run_post (the same kernel).
+ * rva_cnn3d_plan_info: pool1[3] = (T, H/2, W/2) after the first pool, pool2[3] = (T/2, H/4, W/4) after the second, tiles[3] =
+ *   blocks per frame of conv1 and blocks per clip of conv2 and conv3 (per channel half), launches per _run.  Any may be NULL.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_cnn3d_plan rva_cnn3d_plan;
+typedef struct rva_cnn3d_desc {
+    int32_t height, width;            /* frame size of the clip (112 x 112 by default) */
+    int32_t frames;                   /* T = sequence_length */
+    int32_t classes;
+    int32_t max_clips;                /* capacity: the most clips one _run may take */
+} rva_cnn3d_desc;
+typedef struct rva_cnn3d_weights {
+    const float *conv1_w, *conv1_b, *conv2_w, *conv2_b, *conv3_w, *conv3_b;
+    const float *head_w, *head_b;
+} rva_cnn3d_weights;
+int rva_cnn3d_plan_create(rva_ctx *ctx, const rva_cnn3d_desc *desc, const rva_cnn3d_weights *weights, rva_cnn3d_plan **out);
+void rva_cnn3d_plan_destroy(rva_cnn3d_plan *plan);
+int rva_cnn3d_plan_info(const rva_cnn3d_plan *plan, int32_t *pool1, int32_t *pool2, int32_t *tiles, int32_t *n_launches);
+int rva_cnn3d_plan_run(rva_cnn3d_plan *plan, const void *frames, const int32_t *frame_index, int n_clips, void *logits,
+                       rva_stream_t stream);
+int rva_cnn3d_plan_run_post(rva_cnn3d_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                            void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)
  * for a tick of NV12 surfaces: gray -> 5x5 Gaussian -> |diff| against prev_blur[i] -> counts[i] = number of
  * pixels with diff > 25 (device int32[n]; -1 where prev_blur[i] is NULL = first frame of that stream).

@@ -19,7 +19,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
 SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip", "rva_clip.hip",
-           "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+           "rva_clip3d.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]
@@ -64,6 +64,18 @@ class CnnLstmDesc(C.Structure):
 class CnnLstmWeights(C.Structure):
     """``rva_cnnlstm_weights`` (include/rva.h): the module's tensors in module order, BatchNorm folded, LSTM biases summed."""
     NAMES = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "w_ih1", "b1", "w_hh1", "w_ih2", "w_hh2", "b2", "head_w", "head_b")
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
+
+
+class Cnn3dDesc(C.Structure):
+    """``rva_cnn3d_desc`` (include/rva.h)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("frames", C.c_int32), ("classes", C.c_int32), ("max_clips", C.c_int32)]
+
+
+class Cnn3dWeights(C.Structure):
+    """``rva_cnn3d_weights`` (include/rva.h): the three convolutions with BatchNorm folded, in the layouts the kernels read
+    (``clip_plan.pack_cnn3d``), and the head."""
+    NAMES = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "head_w", "head_b")
     _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
 
 
@@ -224,6 +236,11 @@ def lib() -> C.CDLL:
         "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
         "rva_cnnlstm_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_cnnlstm_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_cnn3d_plan_create": (C.c_int, [_P, C.POINTER(Cnn3dDesc), C.POINTER(Cnn3dWeights), C.POINTER(_P)]),
+        "rva_cnn3d_plan_destroy": (None, [_P]),
+        "rva_cnn3d_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
+        "rva_cnn3d_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+        "rva_cnn3d_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -257,7 +274,8 @@ EXPORTS = [
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
     "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
-    "rva_cnnlstm_plan_run_post", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_cnnlstm_plan_run_post", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
+    "rva_cnn3d_plan_run_post", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
 ]
 
 

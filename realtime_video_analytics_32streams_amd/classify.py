@@ -62,6 +62,9 @@ class HipResNetDetector(BaseDetector):
         self.device = torch.device("cuda", self.ctx.device)
         self.input_hw = (int(config.input_size[0]), int(config.input_size[1])) if config.input_size else (224, 224)
         self._infer_fn = infer_fn
+        if infer_fn is None and getattr(config, "hip_engine", "auto") == "native":
+            raise ValueError("hip_engine: native has no hand-written plan for model_type 'resnet' (the network runs through "
+                             "PyTorch-ROCm with hip_engine: auto)")
         self.net = None
         if infer_fn is None:
             if net is None:

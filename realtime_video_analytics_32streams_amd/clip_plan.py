@@ -10,6 +10,9 @@ from the detector's HBM ring through a device table of frame indices.  What stay
     ``half: false``);
   * :func:`clip_flops`: the FLOP / byte count of one clip (tools/clip_plan_report.py);
   * :class:`FusedCnnLstm`: owns one plan (weights and the workspace for ``max_clips`` clips) and its logits buffer.
+
+The 3D-CNN head (:class:`temporal.Cnn3dNet`; ``3d_cnn`` and ``slow_fast``) has the same pieces for ``rva_cnn3d_plan_*``
+(``csrc/rva_clip3d.hip``, selected by ``hip_engine: native``): :func:`pack_cnn3d`, :func:`clip3d_flops`, :class:`Fused3dCnn`.
 """
 from __future__ import annotations
 
@@ -28,22 +31,38 @@ LOGGER = logging.getLogger(__name__)
 ENGINE = "clip-f32"          # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
 
 
+ENGINE_3D = "clip3d-f32"     # the 3D-CNN plan (3d_cnn / slow_fast, hip_engine: native)
+
+
 def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False) -> str:
     """Engine of a temporal head: ``"infer_fn"`` (a caller's function overrides everything), ``"clip-f32"`` (``cnn_lstm``,
-    ``half: false``, ``hip_engine: plan``) or ``"torch"``.  ``half: true`` with ``plan`` on ``cnn_lstm`` raises (the plan is fp32
-    only); the other temporal heads have no plan and keep torch with a warning, so a configuration never changes engines
-    silently."""
+    ``half: false``, ``hip_engine: plan`` or ``native``), ``"clip3d-f32"`` (``3d_cnn`` / ``slow_fast``, ``half: false``,
+    ``hip_engine: native``) or ``"torch"``.  ``plan`` is best effort: ``half: true`` on ``cnn_lstm`` raises (the plan is fp32
+    only), the other temporal heads keep torch with a warning, so a configuration never changes engines silently.  ``native``
+    is strict: the network runs as hand-written HIP at the configured precision or the call raises ``ValueError`` (``half:
+    true`` on either plan; ``conv_gru``, for which the reference defines no architecture)."""
     if has_infer_fn:
         return "infer_fn"
-    if hip_engine != "plan":
+    if hip_engine not in ("plan", "native"):
         return "torch"
     if model_type == "cnn_lstm":
         if half:
-            raise ValueError("hip_engine: plan runs the CNN-LSTM head as an fp32 plan only; set half: false "
+            raise ValueError(f"hip_engine: {hip_engine} runs the CNN-LSTM head as an fp32 plan only; set half: false "
                              "(or hip_engine: auto for the PyTorch fp16 network)")
         return ENGINE
-    LOGGER.warning("hip_engine: plan has no hand-written plan for model_type %r: the network runs through PyTorch-ROCm",
-                   model_type)
+    if hip_engine == "native":
+        if model_type in ("3d_cnn", "slow_fast"):
+            if half:
+                raise ValueError("hip_engine: native runs the 3D-CNN head as an fp32 plan only; set half: false "
+                                 "(or hip_engine: auto for the PyTorch fp16 network)")
+            return ENGINE_3D
+        if model_type == "conv_gru":
+            raise ValueError("hip_engine: native has no hand-written plan for model_type 'conv_gru': the reference defines no "
+                             "architecture for this head (use hip_engine: auto with net=... or infer_fn=...)")
+        raise ValueError(f"hip_engine: native has no hand-written plan for model_type {model_type!r}")
+    hint = " (hip_engine: native runs it as the fp32 clip3d-f32 plan)" if model_type in ("3d_cnn", "slow_fast") else ""
+    LOGGER.warning("hip_engine: plan has no hand-written plan for model_type %r: the network runs through PyTorch-ROCm%s",
+                   model_type, hint)
     return "torch"
 
 
@@ -66,11 +85,12 @@ def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 40
             "lstm_weight_bytes_per_step": 4.0 * g4 * 3 * hidden}
 
 
-def _fold(conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d) -> Tuple[np.ndarray, np.ndarray]:
+def _fold(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
+    """Conv2d / Conv3d with its BatchNorm (eval statistics) folded in, in float64, rounded once to fp32."""
     w = conv.weight.detach().double().cpu()
     b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64)
     scale = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
-    wf = w * scale[:, None, None, None]
+    wf = w * scale.reshape(-1, *([1] * (w.dim() - 1)))
     bf = (b - bn.running_mean.detach().double().cpu()) * scale + bn.bias.detach().double().cpu()
     return wf.float().numpy(), bf.float().numpy()
 
@@ -163,6 +183,128 @@ class FusedCnnLstm:
                                                         C.c_void_p(post.cls.data_ptr()), C.c_void_p(post.boxes.data_ptr()),
                                                         C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
                        "rva_cnnlstm_plan_run_post")
+        return post
+
+
+def clip3d_flops(h: int, w: int, frames: int, classes: int = 400) -> Dict[str, float]:
+    """FLOP (multiply + add = 2) and the bytes one 3D-CNN clip must at least move, from the shapes alone.  The pools floor, and
+    only the convolution outputs a pool keeps are counted (the plan computes no others)."""
+    h1, w1 = h // 2, w // 2
+    t2, h2, w2 = frames // 2, h1 // 2, w1 // 2
+    conv1 = 2.0 * frames * (2 * h1) * (2 * w1) * 64 * 81
+    conv2 = 2.0 * (2 * t2) * (2 * h2) * (2 * w2) * 128 * 1728
+    conv3 = 2.0 * t2 * h2 * w2 * 256 * 3456
+    head = 2.0 * 256 * classes
+    weights = 4.0 * (64 * 81 + 64 + 128 * 1728 + 128 + 256 * 3456 + 256 + classes * 257)
+    return {"conv1": conv1, "conv2": conv2, "conv3": conv3, "head": head, "clip": conv1 + conv2 + conv3 + head,
+            "pool1": (frames, h1, w1), "pool2": (t2, h2, w2), "clip_bytes": 4.0 * 3 * frames * h * w, "weight_bytes": weights,
+            "act1_bytes": 4.0 * frames * h1 * w1 * 64, "act2_bytes": 4.0 * t2 * h2 * w2 * 128}
+
+
+def pack_cnn3d(net) -> Dict[str, np.ndarray]:
+    """The ``rva_cnn3d_weights`` arrays of a :class:`temporal.Cnn3dNet` (``N.Cnn3dWeights.NAMES`` order), contiguous fp32, each
+    Conv3d with its BatchNorm folded in float64 and rounded once, in the layouts the kernels read:
+
+      * ``conv1_w`` ``[64, 3, 3, 3, 3]`` = ``[co, ci, kt, ky, kx]`` (the module's own layout: the VALU kernel keeps a channel's
+        81 taps in registers in this order);
+      * ``conv2_w`` ``[128, 27, 64]`` and ``conv3_w`` ``[256, 27, 128]`` = ``[co, tap, ci]`` with ``tap = (kt*3 + ky)*3 + kx``
+        (channels innermost, as the channels-last activations: a lane's MFMA operands are contiguous float4 reads);
+      * biases ``[64]`` / ``[128]`` / ``[256]``, ``head_w`` ``[classes, 256]``, ``head_b`` ``[classes]``."""
+    seq, fc = getattr(net, "conv3d", None), getattr(net, "fc", None)
+    ok = isinstance(seq, torch.nn.Sequential) and len(seq) == 12 and isinstance(fc, torch.nn.Linear)
+    if ok:
+        for i, (cin, cout) in zip((0, 4, 8), ((3, 64), (64, 128), (128, 256))):
+            c, bn = seq[i], seq[i + 1]
+            ok = ok and isinstance(c, torch.nn.Conv3d) and isinstance(bn, torch.nn.BatchNorm3d) and \
+                (c.in_channels, c.out_channels) == (cin, cout) and c.kernel_size == (3, 3, 3) and c.stride == (1, 1, 1) and \
+                c.padding == (1, 1, 1) and c.dilation == (1, 1, 1) and c.groups == 1
+        p1, p2 = seq[3], seq[7]
+        pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v,) * 3  # noqa: E731
+        ok = ok and isinstance(p1, torch.nn.MaxPool3d) and pair(p1.kernel_size) == (1, 2, 2) and pair(p1.stride) == (1, 2, 2) and \
+            isinstance(p2, torch.nn.MaxPool3d) and pair(p2.kernel_size) == (2, 2, 2) and pair(p2.stride) == (2, 2, 2) and \
+            pair(p1.padding) == (0, 0, 0) and pair(p2.padding) == (0, 0, 0) and not p1.ceil_mode and not p2.ceil_mode and \
+            isinstance(seq[11], torch.nn.AdaptiveAvgPool3d) and fc.in_features == 256
+    if not ok:
+        raise ValueError("pack_cnn3d: not the Cnn3dNet architecture")
+    c1w, c1b = _fold(seq[0], seq[1])
+    c2w, c2b = _fold(seq[4], seq[5])
+    c3w, c3b = _fold(seq[8], seq[9])
+    taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], 27).transpose(0, 2, 1)  # noqa: E731  [co,ci,27] -> [co,27,ci]
+    bias = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
+    out = {"conv1_w": c1w, "conv1_b": c1b, "conv2_w": taps_last(c2w), "conv2_b": c2b, "conv3_w": taps_last(c3w), "conv3_b": c3b,
+           "head_w": fc.weight.detach().float().cpu().numpy(), "head_b": bias}
+    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in N.Cnn3dWeights.NAMES}
+
+
+class Fused3dCnn:
+    """One ``rva_cnn3d_plan``: the fp32 clip network of ``net`` (a :class:`temporal.Cnn3dNet`) for clips of ``frames`` frames at
+    ``hw``, up to ``max_clips`` clips per call.  Same surface as :class:`FusedCnnLstm` (``max_clips``, ``T``, ``classes``,
+    ``logits``, ``run``, ``post``, ``__call__``).  No host synchronisation and no allocation after construction (capturable)."""
+
+    def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
+                 device: Optional[torch.device] = None):
+        packed = pack_cnn3d(net)
+        self.ctx = ctx or ops.context()
+        self.dev = device or torch.device("cuda", self.ctx.device)
+        self.H, self.W, self.T, self.max_clips = int(hw[0]), int(hw[1]), int(frames), int(max_clips)
+        self.classes = int(net.fc.out_features)
+        self.L = N.lib()
+        wt = N.Cnn3dWeights(*[packed[n].ctypes.data_as(C.POINTER(C.c_float)) for n in N.Cnn3dWeights.NAMES])
+        d = N.Cnn3dDesc(self.H, self.W, self.T, self.classes, self.max_clips)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            self.ctx.check(self.L.rva_cnn3d_plan_create(self.ctx.handle, C.byref(d), C.byref(wt), C.byref(h)), "rva_cnn3d_plan_create")
+        self.handle = h
+        del packed
+        p1, p2, tiles, nl = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_int32()
+        self.ctx.check(self.L.rva_cnn3d_plan_info(h, p1, p2, tiles, C.byref(nl)), "rva_cnn3d_plan_info")
+        self.pool1, self.pool2, self.tiles, self.n_launches = tuple(p1), tuple(p2), tuple(tiles), nl.value
+        self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
+        self._iota: Optional[torch.Tensor] = None
+
+    def __del__(self):  # best effort
+        try:
+            if getattr(self, "handle", None):
+                self.L.rva_cnn3d_plan_destroy(self.handle)
+                self.handle = None
+        except Exception:  # noqa: BLE001
+            pass
+
+    def run(self, ring: torch.Tensor, frame_index: torch.Tensor, n_clips: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Logits ``[n_clips, classes]`` of the clips whose frame t of clip b is ``ring.view(-1, 3, H, W)[frame_index[b * T + t]]``,
+        launched on the current stream: a view of ``out`` (contiguous fp32 ``[>= n_clips, classes]`` on the device) or of the
+        plan's own buffer."""
+        if ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous() or ring.numel() % (3 * self.H * self.W):
+            raise ValueError(f"ring must be a contiguous fp32 device tensor of [*, 3, {self.H}, {self.W}] frames")
+        if frame_index.dtype != torch.int32 or not frame_index.is_cuda or frame_index.numel() < n_clips * self.T:
+            raise ValueError("frame_index must be a device int32 tensor of n_clips * T frame indices")
+        if not 1 <= n_clips <= self.max_clips:
+            raise ValueError(f"n_clips must be in 1..{self.max_clips}, got {n_clips}")
+        out = self.logits if out is None else out
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or \
+                out.shape[1] != self.classes or out.shape[0] < n_clips:
+            raise ValueError(f"out must be a contiguous fp32 device tensor of [>= {n_clips}, {self.classes}]")
+        self.ctx.check(self.L.rva_cnn3d_plan_run(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()),
+                                                 int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()), "rva_cnn3d_plan_run")
+        return out[:n_clips]
+
+    def __call__(self, clips: torch.Tensor) -> torch.Tensor:
+        """``Cnn3dNet.forward`` of clips ``[B, 3, T, H, W]`` fp32: a fresh ``[B, classes]`` tensor.  The permute to frames
+        ``[B, T, 3, H, W]`` is for this (test) path only: the detector's ring holds planar frames already."""
+        b = int(clips.shape[0])
+        if tuple(clips.shape[1:]) != (3, self.T, self.H, self.W):
+            raise ValueError(f"clips must be [B, 3, {self.T}, {self.H}, {self.W}], got {tuple(clips.shape)}")
+        if self._iota is None:
+            self._iota = torch.arange(self.max_clips * self.T, dtype=torch.int32, device=self.dev)
+        return self.run(clips.permute(0, 2, 1, 3, 4).contiguous(), self._iota, b).clone()
+
+    def post(self, logits: torch.Tensor, rows: torch.Tensor, n_rows: int, post: ops.PostBuffers) -> ops.PostBuffers:
+        """Top-k result rows into ``post``: ``rows`` = device int32 ``[n_rows, 3]`` of (clip or -1, width, height)."""
+        self.ctx.check(self.L.rva_cnn3d_plan_run_post(self.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                      int(n_rows), int(post.max_det), C.c_void_p(post.scores.data_ptr()),
+                                                      C.c_void_p(post.cls.data_ptr()), C.c_void_p(post.boxes.data_ptr()),
+                                                      C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
+                       "rva_cnn3d_plan_run_post")
         return post
 
 

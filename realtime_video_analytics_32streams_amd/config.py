@@ -14,7 +14,17 @@ detector key ``hip_engine`` picks the network's engine: ``"auto"`` (default; wha
 every temporal head; ``"plan"`` = the hand-written plan at the configured precision, i.e. the fp32 YOLO plan for
 ``half: false`` and, for ``model_type: cnn_lstm``, the fp32 clip plan (``half: false`` only: ``half: true`` is
 refused at construction).  The other temporal heads have no plan: with ``"plan"`` they keep PyTorch-ROCm and log
-a warning.  ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
+a warning.  ``"native"`` is the strict form of ``"plan"``: every network of the detector runs as hand-written HIP at the
+configured precision, or construction fails with ``ValueError`` (an ``infer_fn`` still overrides everything):
+
+    head                    half: false                       half: true
+    yolov5 / yolov8         as plan: engine "fused-f32"       as plan: engine "fused"
+    cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only)
+    3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only)
+    conv_gru                ValueError (the reference defines no architecture, so there is no plan)
+    resnet                  ValueError (no hand-written plan)
+
+``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
 rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
 0.25 px between 256 and 512; ``"fp32"`` = the head kernels also write them as an fp32 side tensor and the post-process
 reads its boxes from there (class rows stay fp16).  With ``half: false`` the boxes are fp32 already and the key is
@@ -31,7 +41,7 @@ import yaml
 
 HIP_BACKENDS = ("hip", "rocm", "mi355x")
 REFERENCE_BACKENDS = ("ultralytics", "tensorrt", "onnx", "onnxruntime", "openvino", "rknn", "rk3588")
-HIP_ENGINES = ("auto", "plan")
+HIP_ENGINES = ("auto", "plan", "native")
 HIP_BOX_ROWS = ("fp16", "fp32")
 TEMPORAL_MODELS = ("cnn_lstm", "3d_cnn", "conv_gru", "slow_fast")
 MODEL_TYPES = ("yolov5", "yolov8", "resnet") + TEMPORAL_MODELS
@@ -104,7 +114,7 @@ class DetectorConfig:
     temporal_pooling: str = "avg"
     action_classes: Optional[List[str]] = None
     num_action_classes: int = 400
-    hip_engine: str = "auto"                # backend "hip", YOLO and cnn_lstm: "auto" or "plan" (module docstring)
+    hip_engine: str = "auto"                # backend "hip": "auto", "plan" or "native" (module docstring)
     hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
 
     def validate(self) -> None:

@@ -381,6 +381,41 @@ size_t lstm_lds(int hidden) { return (size_t)(LSTM_G * 2 * hidden + LSTM_R * LST
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------------------
+// K_head and K_post serve every clip plan (rva_clip3d.hip launches them through these; declared in rva_internal.h).
+int rva_clip_head_prepare(rva_ctx *ctx, int hidden)
+{
+    if (rva_func_smem((const void *)k_clip_head, (size_t)hidden * sizeof(float)) != hipSuccess)
+        return rva_fail(ctx, RVA_ERR_HIP, "clip plan: cannot raise the head kernel's LDS limit");
+    return RVA_OK;
+}
+
+int rva_clip_head_launch(rva_ctx *ctx, const float *x, const float *wh, const float *bh, float *logits, int hidden, int classes,
+                         int n_clips, hipStream_t st)
+{
+    k_clip_head<<<dim3(rva_ceil_div(classes, 256), n_clips), 256, (size_t)hidden * sizeof(float), st>>>(x, wh, bh, logits, hidden, classes);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
+int rva_clip_post_prepare(rva_ctx *ctx, int classes)
+{
+    if (rva_func_smem((const void *)k_clip_post, (size_t)classes * sizeof(float)) != hipSuccess)
+        return rva_fail(ctx, RVA_ERR_HIP, "clip plan: cannot raise the post kernel's LDS limit");
+    return RVA_OK;
+}
+
+int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, const int32_t *rows, int n_rows, int max_det,
+                         float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st)
+{
+    const int k = std::min(5, classes);
+    if (!logits || !rows || n_rows < 1 || max_det < k || !scores || !cls || !counts || !boxes || ((uintptr_t)boxes & 15))
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad argument (n_rows >= 1, max_det >= %d, 16-byte aligned boxes)", who, k);
+    k_clip_post<<<n_rows, 256, (size_t)classes * sizeof(float), st>>>(logits, classes, rows, k, max_det, scores, cls, boxes, counts);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
 struct rva_cnnlstm_plan {
     rva_ctx *ctx = nullptr;
     rva_cnnlstm_desc d{};
@@ -472,8 +507,7 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the stem kernel's LDS limit");
     if (rc == RVA_OK && rva_func_smem((const void *)k_clip_lstm, lstm_lds(h)) != hipSuccess)
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the LSTM kernel's LDS limit");
-    if (rc == RVA_OK && rva_func_smem((const void *)k_clip_post, (size_t)d.classes * sizeof(float)) != hipSuccess)
-        rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the post kernel's LDS limit");
+    if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
         rva_cnnlstm_plan_destroy(p);
         return rc;
@@ -524,24 +558,16 @@ int rva_cnnlstm_plan_run(rva_cnnlstm_plan *p, const void *frames, const int32_t 
                                                                                 p->gx, p->bl2, p->h1, p->h2, p->c1, p->c2);
         RVA_HIP(ctx, hipGetLastError());
     }
-    k_clip_head<<<dim3(rva_ceil_div(p->d.classes, 256), n_clips), 256, (size_t)h * sizeof(float), st>>>(
-        p->h2 + (size_t)(T - 1) * p->d.max_clips * h, p->wh, p->bh, (float *)logits, h, p->d.classes);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
+    return rva_clip_head_launch(ctx, p->h2 + (size_t)(T - 1) * p->d.max_clips * h, p->wh, p->bh, (float *)logits, h, p->d.classes,
+                                n_clips, st);
 }
 
 int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
                               void *cls, void *boxes, void *counts, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
-    rva_ctx *ctx = p->ctx;
-    const int k = std::min(5, p->d.classes);
-    if (!logits || !rows || n_rows < 1 || max_det < k || !scores || !cls || !counts || !boxes || ((uintptr_t)boxes & 15))
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_run_post: bad argument (n_rows >= 1, max_det >= %d, 16-byte aligned boxes)", k);
-    k_clip_post<<<n_rows, 256, (size_t)p->d.classes * sizeof(float), (hipStream_t)stream_>>>(
-        (const float *)logits, p->d.classes, rows, k, max_det, (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
+    return rva_clip_post_launch(p->ctx, "rva_cnnlstm_plan_run_post", (const float *)logits, p->d.classes, rows, n_rows, max_det,
+                                (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -83,3 +83,13 @@ bool rva_conv_variant_is_gather64(int variant);
 
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);
+
+// The head (Linear: one thread per class, k in order) and top-k (rank counting) kernels of the clip plans, defined in
+// rva_clip.hip and shared by rva_clip3d.hip.  *_prepare raises the kernel's dynamic-LDS limit (at plan creation, never inside a
+// capture); *_launch only launches on `st`.  `who` names the ABI entry in the argument error of the top-k launch.
+int rva_clip_head_prepare(rva_ctx *ctx, int hidden);
+int rva_clip_head_launch(rva_ctx *ctx, const float *x, const float *wh, const float *bh, float *logits, int hidden, int classes,
+                         int n_clips, hipStream_t st);
+int rva_clip_post_prepare(rva_ctx *ctx, int classes);
+int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, const int32_t *rows, int n_rows, int max_det,
+                         float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);

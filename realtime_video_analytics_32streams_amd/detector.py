@@ -99,7 +99,8 @@ class HipYoloDetector(BaseDetector):
         launch per layer, fp16 operands with fp32 accumulation.  ``half: false`` is the reference's fp32 precision
         (detector.py:248-251): by default (``hip_engine: auto``) the module then runs through PyTorch-ROCm (MIOpen) and the
         constructor says so in the log -- a configuration never changes engines silently; ``hip_engine: plan`` runs it as the
-        hand-written fp32 plan instead (engine ``"fused-f32"``: exact fp32 MFMA, bit-reproducible, same pipeline integration).
+        hand-written fp32 plan instead (engine ``"fused-f32"``: exact fp32 MFMA, bit-reproducible, same pipeline integration);
+        ``hip_engine: native`` (the strict form, config.py) selects the same engines as ``plan`` here.
         ``hip_box_rows: fp32`` (engine ``"fused"`` only) makes the plan keep the four box rows in fp32 beside its fp16 head
         (``engine.FusedYoloV8(box_rows="fp32")``); the side tensor travels from ``stage_net`` to ``stage_post`` as an
         ``ops.SplitHead`` and K2 reads its boxes from it."""
@@ -112,7 +113,7 @@ class HipYoloDetector(BaseDetector):
         else:
             self.input_hw = (640, 640)            # detector.py:582-583 default
         self.half = bool(config.half)
-        self.engine = "fused" if self.half else ("fused-f32" if getattr(config, "hip_engine", "auto") == "plan" else "torch-fp32")
+        self.engine = "fused" if self.half else ("fused-f32" if getattr(config, "hip_engine", "auto") in ("plan", "native") else "torch-fp32")
         self._infer_fn = infer_fn
         # where the fp16 plan keeps its box rows; fp32 elsewhere already (half: false), and no plan behind an infer_fn
         self.box_rows = getattr(config, "hip_box_rows", "fp16") if (self.engine == "fused" and infer_fn is None) else "fp16"

@@ -27,12 +27,14 @@ import torch.nn as nn
 
 from . import _native as N
 from . import ops
-from .clip_plan import ENGINE as CLIP_PLAN, FusedCnnLstm, clip_engine, fired_tables
+from .clip_plan import ENGINE as CLIP_PLAN, ENGINE_3D as CLIP_PLAN_3D, Fused3dCnn, FusedCnnLstm, clip_engine, fired_tables
 from .config import DetectorConfig
 from .detector import Detection
 from .video_stream import FramePacket
 
 LOGGER = logging.getLogger(__name__)
+
+CLIP_PLANS = (CLIP_PLAN, CLIP_PLAN_3D)      # engines that run the clip network as a hand-written plan (_make_plan)
 
 
 @dataclass(slots=True)
@@ -95,7 +97,7 @@ class _ClipTick:
 class _PlanSlot:
     """One tick slot's clip plan and its two buffer sets (logits, pinned host tables, device tables, upload event)."""
 
-    def __init__(self, plan: FusedCnnLstm, rows_cap: int, device):
+    def __init__(self, plan, rows_cap: int, device):
         self.plan, self.rows_cap, self.turn = plan, rows_cap, 0
         n = plan.max_clips * plan.T + 3 * rows_cap
         self.sets = [(torch.empty((plan.max_clips, plan.classes), dtype=torch.float32, device=device),
@@ -166,7 +168,8 @@ class _HipTemporalDetector:
         self.sequence_step = self.sched.step
         self.half = bool(config.half)
         self._infer_fn = infer_fn
-        # "torch", "infer_fn" or "clip-f32" (hip_engine: plan, cnn_lstm, half: false): clip_plan.clip_engine
+        # "torch", "infer_fn", "clip-f32" (cnn_lstm, half: false, hip_engine: plan / native) or "clip3d-f32" (3d_cnn / slow_fast,
+        # half: false, hip_engine: native): clip_plan.clip_engine
         self.engine = clip_engine(config.model_type, self.half, getattr(config, "hip_engine", "auto"), infer_fn is not None)
         self.net = None
         if infer_fn is None:
@@ -188,7 +191,7 @@ class _HipTemporalDetector:
         self._bring: Optional[torch.Tensor] = None
         self._post: Dict[tuple, ops.PostBuffers] = {}
         self._plans: Dict[int, _PlanSlot] = {}  # clip plan per tick slot, with two buffer sets used alternately
-        self._seq_plan: Optional[FusedCnnLstm] = None   # clip plan of the single-stream predict path
+        self._seq_plan = None                  # clip plan of the single-stream predict path
         self.two_chain_ok = True               # PipelinedTicks may run consecutive ticks as two chains on two streams
 
     # -- per-head hooks ---------------------------------------------------------------------------
@@ -197,6 +200,10 @@ class _HipTemporalDetector:
 
     def _frame_dtype(self) -> torch.dtype:
         return torch.float16 if self.half else torch.float32
+
+    def _make_plan(self, max_clips: int):
+        """The hand-written plan of this head's network for ``max_clips`` clips (engines of ``CLIP_PLANS`` only)."""
+        raise NotImplementedError(f"{type(self).__name__} has no hand-written clip plan")
 
     # -- reference-shaped pre-process of a whole clip (parity surface for _preprocess_sequence) -----
     def preprocess_sequence(self, frames: Sequence) -> torch.Tensor:
@@ -298,7 +305,7 @@ class _HipTemporalDetector:
             if clip is not None:
                 fired.append((row, [c[1] for c in clip], clip[0][2]))
                 infos[n] = ClipInfo(clip[0][0], clip[-1][0], self.config.action_classes, min(5, self.config.num_action_classes))
-        if self.engine == CLIP_PLAN and self._slot not in self._plans:
+        if self.engine in CLIP_PLANS and self._slot not in self._plans:
             self._plan_slot(self._slot, 0, len(packets))     # built on the slot's first tick, before any clip can fire
         return _ClipTick(len(packets), fired, cols, infos, self._slot)
 
@@ -306,7 +313,7 @@ class _HipTemporalDetector:
         """The clips that fired this tick as ONE network batch: ``[n_fired, classes]`` raw outputs (no softmax)."""
         if not pre.fired:
             return None
-        if self.engine == CLIP_PLAN:
+        if self.engine in CLIP_PLANS:
             return self._plan_net(pre)
         C_ = self._bring.shape[1]
         flat = self._bring.view(-1, 3, *self.input_hw)
@@ -326,7 +333,7 @@ class _HipTemporalDetector:
         post = self._post.get(key)
         if post is None:
             post = self._post[key] = ops.PostBuffers.allocate(pre.rows, 8, self.device)
-        if raw is not None and self.engine == CLIP_PLAN:
+        if raw is not None and self.engine in CLIP_PLANS:
             return self._plans[pre.slot].plan.post(raw, pre.rows_table, pre.rows, post)
         post.counts.zero_()
         if raw is not None:
@@ -345,7 +352,7 @@ class _HipTemporalDetector:
         self.last_clip_infos = pre.infos
         return self.stage_post(self.stage_net(pre), pre)
 
-    # -- clip plan (engine "clip-f32") --------------------------------------------------------------------------------------
+    # -- clip plans (engines "clip-f32" / "clip3d-f32") --------------------------------------------------------------------------------------
     def _plan_slot(self, slot: int, n_clips: int, rows: int) -> "_PlanSlot":
         """The plan of a tick slot, sized for every ring column; rebuilt (after a device drain) only if a stream shows up
         that was not announced and more clips or rows than that ever appear."""
@@ -354,7 +361,7 @@ class _HipTemporalDetector:
             if ps is not None:
                 torch.cuda.synchronize(self.device)          # the old buffers may still be read by a tail in flight
             cap = max(n_clips, rows, len(self._col), 1)
-            plan = FusedCnnLstm(self.net, self.input_hw, self.sched.L, cap, ctx=self.ctx, device=self.device)
+            plan = self._make_plan(cap)
             ps = self._plans[slot] = _PlanSlot(plan, cap, self.device)
         return ps
 
@@ -377,10 +384,10 @@ class _HipTemporalDetector:
         return ps.plan.run(self._bring, dev[:idx.size], len(pre.fired), out=logits)
 
     def _predict_sequence(self, name: str, ring: torch.Tensor, clip) -> List[Detection]:
-        if self.engine == CLIP_PLAN:
+        if self.engine in CLIP_PLANS:
             idx = torch.tensor([c[1] for c in clip], dtype=torch.int32, device=self.device)
             if self._seq_plan is None:
-                self._seq_plan = FusedCnnLstm(self.net, self.input_hw, self.sched.L, 1, ctx=self.ctx, device=self.device)
+                self._seq_plan = self._make_plan(1)
             raw = self._seq_plan.run(ring, idx, 1)
         else:
             idx = torch.tensor([c[1] for c in clip], device=self.device)
@@ -414,10 +421,17 @@ class HipCNNLSTMDetector(_HipTemporalDetector):
     def _default_net(self) -> nn.Module:
         return CnnLstmNet(self.config.num_action_classes)
 
+    def _make_plan(self, max_clips: int) -> FusedCnnLstm:
+        return FusedCnnLstm(self.net, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
+
 
 class HipCNN3DDetector(_HipTemporalDetector):
     """3D-CNN head (temporal_detector.py:429-641; also what the reference instantiates for ``slow_fast``,
-    detector.py:70-74): mean 0.45 / std 0.225, clips ``[1,3,T,H,W]``, default input 112x112 (:544)."""
+    detector.py:70-74): mean 0.45 / std 0.225, clips ``[1,3,T,H,W]``, default input 112x112 (:544).  With ``half: false`` and
+    ``hip_engine: native`` the network and its top-5 run as the hand-written fp32 plan (engine ``"clip3d-f32"``,
+    clip_plan.Fused3dCnn): it reads the planar frames straight from the frame ring through the frame-index table, so neither the
+    gather nor the ``[B,3,T,H,W]`` permute exists on that path.  ``half: true`` with ``native`` is refused; ``hip_engine: plan``
+    keeps PyTorch-ROCm with a warning."""
 
     NORM = N.NORM_VIDEO_F32
     CLIP_LAYOUT = "CTHW"
@@ -425,6 +439,9 @@ class HipCNN3DDetector(_HipTemporalDetector):
 
     def _default_net(self) -> nn.Module:
         return Cnn3dNet(self.config.num_action_classes)
+
+    def _make_plan(self, max_clips: int) -> Fused3dCnn:
+        return Fused3dCnn(self.net, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
 
 
 class HipConvGRUDetector(_HipTemporalDetector):
