@@ -221,8 +221,47 @@ def clip_schedule(L, stride, overlap, n_frames):
     return fired[:n].tolist(), ids[:n].tolist()
 
 
-def motion_step_nv12(y, uv, w, h, prev_blur=None):
-    """One MotionFilter.should_process step on an NV12 frame: returns (changed-pixel count or -1, new blur)."""
+def bgr_to_gray(bgr):
+    """cv2.cvtColor(BGR2GRAY) restated: uint8 [h, w, 3] -> uint8 [h, w]."""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    h, w = bgr.shape[:2]
+    out = np.empty((h, w), np.uint8)
+    lib().orc_bgr_to_gray(C.c_void_p(bgr.ctypes.data), w, h, C.c_void_p(out.ctypes.data))
+    return out
+
+
+def gaussian5_u8(gray):
+    """cv2.GaussianBlur(gray, (5, 5), 0) restated: uint8 [h, w] -> uint8 [h, w] (w, h >= 3)."""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    h, w = gray.shape
+    out = np.empty((h, w), np.uint8)
+    lib().orc_gaussian5_u8(C.c_void_p(gray.ctypes.data), w, h, C.c_void_p(out.ctypes.data))
+    return out
+
+
+def motion_step_bgr(bgr, prev_blur=None):
+    """One MotionFilter.should_process step on a BGR uint8 [h, w, 3] frame: returns (changed-pixel count or -1, new blur)."""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    h, w = bgr.shape[:2]
+    out = np.empty((h, w), np.uint8)
+    L = lib()
+    L.orc_motion_step_bgr.restype = C.c_long
+    if prev_blur is not None:
+        prev_blur = np.ascontiguousarray(prev_blur, np.uint8)
+        assert prev_blur.shape == (h, w)
+    pp = C.c_void_p(prev_blur.ctypes.data) if prev_blur is not None else None
+    n = L.orc_motion_step_bgr(C.c_void_p(bgr.ctypes.data), w, h, pp, C.c_void_p(out.ctypes.data))
+    return int(n), out
+
+
+def motion_step_nv12(y, uv, w, h, prev_blur=None, mask=None):
+    """One MotionFilter.should_process step on an NV12 frame: returns (changed-pixel count or -1, new blur).  ``mask``
+    (uint8 [h, w]): apply_roi in front of the gate -- pixels where the mask is 0 become black, any other value keeps
+    the pixel, as cv2.bitwise_and(frame, frame, mask=mask) does."""
+    if mask is not None:
+        bgr = nv12_to_bgr(y, uv, w, h)
+        bgr[np.asarray(mask) == 0] = 0
+        return motion_step_bgr(bgr, prev_blur)
     y = np.ascontiguousarray(y); uv = np.ascontiguousarray(uv)
     out = np.empty((h, w), np.uint8)
     L = lib()

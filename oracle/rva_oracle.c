@@ -548,7 +548,11 @@ ORC_API int orc_clip_schedule(int L, int stride, double overlap, int n_frames, i
     return clips;
 }
 
-/* ------------------------------------------------------------------ frame gates (UNPINNED: OpenCV absent) */
+/* ------------------------------------------------------------------ frame gates */
+/* PINNED (tests/test_oracle_golden.py): the arithmetic definition -- orc_gaussian5_u8 exactly to an independent statement of
+ * the separable [1,4,6,4,1] correlation with mirror (reflect-101) borders and (sum + 128) >> 8, orc_bgr_to_gray to the float
+ * definition 0.114 B + 0.587 G + 0.299 R within the rounding of its 14-bit coefficients.
+ * STILL UNPINNED: that these are OpenCV's own bits -- no cv2 recording of cvtColor / GaussianBlur exists (OpenCV absent). */
 /* utils/frame_filter.py:26-40 MotionFilter.should_process, one step:
  *   gray = cvtColor(BGR2GRAY): (B*1868 + G*9617 + R*4899 + 8192) >> 14   (OpenCV 8-bit, yuv_shift = 14)
  *   blur = GaussianBlur(gray, (5,5), 0): separable [1,4,6,4,1]/16, BORDER_REFLECT_101, OpenCV's 8-bit

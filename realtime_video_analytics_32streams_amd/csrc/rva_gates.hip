@@ -22,6 +22,13 @@ struct K5Args {
 constexpr int TW = 64, TH = 16, HW_ = TW + 4, HH_ = TH + 4;
 
 __device__ __forceinline__ int refl101(int i, int n) { if (i < 0) i = -i; if (i >= n) i = 2 * n - 2 - i; return i; }
+// Source index of halo cell i of an n-pixel axis.  A block loads the cells i = t0 - 2 .. t0 + T + 1 of its tile (t0 >= 0 a
+// multiple of T, t0 < n), so i lies in [-2, n + T].  The in-range outputs (< n) only need i in [-2, n + 1], where one
+// reflection is exact for every accepted n >= 3: -i <= 2 <= n - 1 and 2n - 2 - i >= n - 3 >= 0.  The cells beyond n + 1 feed no
+// output that is kept, but their single reflection 2n - 2 - i is negative once i > 2n - 2 (n <= T / 2 + 1 or n == T + 1 for
+// the tile sizes here), so the result is clamped to [0, n - 1]: every surface, mask and history address stays inside its row
+// and column range, and nothing changes for the cells that matter.
+__device__ __forceinline__ int halo_index(int i, int n) { i = refl101(i, n); return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
 __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 template <bool NV12>
@@ -36,7 +43,7 @@ __global__ void __launch_bounds__(256) k5_motion(K5Args a)
     const int pitch = a.pitch[s];
     for (int i = tid; i < HH_ * HW_; i += 256) {
         const int r = i / HW_, c = i - r * HW_;
-        const int py = refl101(y0 + r - 2, a.h), px = refl101(x0 + c - 2, a.w);
+        const int py = halo_index(y0 + r - 2, a.h), px = halo_index(x0 + c - 2, a.w);   // both in [0, n - 1]: surface and mask index
         int B, G, R;
         if (NV12) {
             const int Y = yp[(size_t)py * pitch + px];

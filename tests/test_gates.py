@@ -25,6 +25,41 @@ def test_adaptive_fps_schedule_matches_reference_worker():
         assert updates == case["tracker_updates"]
 
 
+_FIXED_THRESHOLDS = [0.0, 1.0, 1.5, -0.1, 0.02, 0.3, 0.9, 1e-9, 0.999999, 0.5, 1.0 / 3.0, 0.01, 0.001]
+
+
+def test_motion_min_count_is_the_reference_float_compare():
+    """gates.motion_min_count (what the device gate in K4 compares the K5 count with) against the reference's decision
+    ``changed / float(total) >= threshold`` by brute force: for every n in 1..199 and every threshold that can sit on a
+    decision boundary -- each quotient c/n itself and its two float neighbours -- plus the fixed set, the result is the
+    smallest c in [0, n] whose quotient passes, or n + 1 when none does (threshold above 1)."""
+    from realtime_video_analytics_32streams_amd.gates import motion_min_count
+    cases = 0
+    for n in range(1, 200):
+        q = np.arange(n + 1, dtype=np.float64) / float(n)            # IEEE double division, as float(c) / float(n)
+        thr = np.concatenate([q, np.nextafter(q, np.inf), np.nextafter(q, -np.inf), _FIXED_THRESHOLDS])
+        ok = q[None, :] >= thr[:, None]
+        want = np.where(ok.any(1), ok.argmax(1), n + 1)
+        got = [motion_min_count(float(t), n) for t in thr]
+        assert got == want.tolist(), (n, [(float(t), g, int(x)) for t, g, x in zip(thr, got, want) if g != x][:5])
+        cases += len(thr)
+    assert cases == 3 * (199 * 200 // 2 + 199) + 199 * len(_FIXED_THRESHOLDS)
+
+
+@pytest.mark.parametrize("n", [640 * 360, 1920 * 1080])
+def test_motion_min_count_at_frame_sizes(n):
+    """At real frame sizes brute force is too long; the two inequalities that define the result are checked instead:
+    c passes (or is n + 1: nothing passes) and c - 1 does not (or c is 0)."""
+    from realtime_video_analytics_32streams_amd.gates import motion_min_count
+    cs = np.array([0, 1, 2, n // 100, n // 50, n // 3, n // 2, n - 1, n, 12345, 4608, 6221], dtype=np.float64)
+    q = cs / float(n)
+    for t in np.concatenate([q, np.nextafter(q, np.inf), np.nextafter(q, -np.inf), _FIXED_THRESHOLDS]).tolist():
+        c = motion_min_count(t, n)
+        assert 0 <= c <= n + 1
+        assert c == n + 1 or float(c) / float(n) >= t, (t, c)
+        assert c == 0 or not (float(c - 1) / float(n) >= t), (t, c)
+
+
 @pytest.mark.gpu
 def test_motion_gate_matches_oracle_over_ticks():
     import torch

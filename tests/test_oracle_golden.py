@@ -271,3 +271,61 @@ def test_nv12_colour_matrix_agrees_with_the_bt601_definition():
     ref = np.stack([1.164383 * Y + 2.017232 * cb, 1.164383 * Y - 0.391762 * cb - 0.812968 * cr, 1.164383 * Y + 1.596027 * cr], -1)
     ref = np.clip(ref, 0.0, 255.0)
     assert np.abs(bgr - ref).max() <= 1.0 and np.abs(bgr - ref).mean() < 0.4
+
+
+@pytest.mark.parametrize("w,h", [(3, 3), (4, 4), (5, 3), (33, 9), (65, 17), (64, 16), (130, 34), (250, 123)])
+def test_motion_blur_oracle_is_the_mirrored_14641_correlation(w, h):
+    """The motion gate's blur (orc_gaussian5_u8, what K5 is held to byte for byte) against an independent statement of its
+    definition: scipy's 1-D correlation with [1, 4, 6, 4, 1] and mode="mirror" (reflect about the edge pixel's centre, i.e.
+    BORDER_REFLECT_101) in int64 along x, then along y, then (s + 128) >> 8.  Exact.  Sizes: the smallest accepted (3: the
+    reflection of x + 2 reaches back to x - 2), one and two pixels more, the sizes at which K5's tile halo reflects past the
+    far edge, a whole tile, several tiles with a remainder, odd x odd.  That the result is OpenCV's GaussianBlur bit stays
+    unpinned (no cv2 here); the published 8-bit path is exact for these dyadic weights."""
+    from scipy.ndimage import correlate1d
+    gray = np.random.default_rng(1000 * w + h).integers(0, 256, (h, w), dtype=np.uint8)
+    k = np.array([1, 4, 6, 4, 1], np.int64)
+    s = correlate1d(correlate1d(gray.astype(np.int64), k, axis=1, mode="mirror"), k, axis=0, mode="mirror")
+    assert np.array_equal(orc.gaussian5_u8(gray), ((s + 128) >> 8).astype(np.uint8))
+
+
+def test_motion_gray_oracle_agrees_with_the_luma_definition():
+    """orc_bgr_to_gray (14-bit integer coefficients, round half up) against the float64 definition
+    Y = 0.114 B + 0.587 G + 0.299 R.  Bound, from the coefficients themselves: the integer form is the nearest integer of
+    sum(q_i x_i) / 16384 (at most 0.5 away), and that differs from the definition by at most 255 * sum|q_i / 16384 - c_i|.
+    The coefficients sum to 16384, so a grey pixel B = G = R = v maps to exactly v -- which the threshold-boundary tests of
+    K5 rely on."""
+    q = np.array([1868, 9617, 4899], np.int64)
+    c = np.array([0.114, 0.587, 0.299], np.float64)
+    assert int(q.sum()) == 16384
+    bound = 0.5 + 255.0 * float(np.abs(q / 16384.0 - c).sum())
+    assert bound <= 0.5 + 255.0 * 3 / 32768                               # each coefficient is the definition's within half a 14-bit step
+    rng = np.random.default_rng(5)
+    bgr = rng.integers(0, 256, (123, 250, 3), dtype=np.uint8)
+    bgr[0, :8] = [[0, 0, 0], [255, 255, 255], [255, 0, 0], [0, 255, 0], [0, 0, 255], [255, 255, 0], [0, 255, 255], [255, 0, 255]]
+    got = orc.bgr_to_gray(bgr).astype(np.float64)
+    err = np.abs(got - bgr.astype(np.float64) @ c).max()
+    assert err <= bound, (err, bound)
+    for v in (0, 100, 125, 126, 255):
+        assert np.array_equal(orc.bgr_to_gray(np.full((5, 7, 3), v, np.uint8)), np.full((5, 7), v, np.uint8))
+
+
+def test_motion_step_bindings_compose_the_pinned_stages():
+    """motion_step_bgr is gray -> blur -> count(|blur - prev| > 25); motion_step_nv12 is the same on nv12_to_bgr, with an
+    optional mask that blackens exactly the pixels where it is 0 (any non-zero value keeps the pixel)."""
+    rng = np.random.default_rng(9)
+    w, h = 34, 10
+    f0, f1 = (rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(2))
+    c0, b0 = orc.motion_step_bgr(f0)
+    assert c0 == -1 and np.array_equal(b0, orc.gaussian5_u8(orc.bgr_to_gray(f0)))
+    c1, b1 = orc.motion_step_bgr(f1, b0)
+    assert np.array_equal(b1, orc.gaussian5_u8(orc.bgr_to_gray(f1)))
+    assert c1 == int((np.abs(b1.astype(np.int64) - b0.astype(np.int64)) > 25).sum()) and 0 < c1 < w * h
+    y = rng.integers(0, 256, (h, w + 6), dtype=np.uint8)
+    uv = rng.integers(0, 256, (h // 2, w + 6), dtype=np.uint8)
+    mask = rng.choice(np.array([0, 1, 128, 255], np.uint8), (h, w))
+    bgr = orc.nv12_to_bgr(y, uv, w, h)
+    assert orc.motion_step_nv12(y, uv, w, h, b0)[0] == orc.motion_step_bgr(bgr, b0)[0]
+    cm, bm = orc.motion_step_nv12(y, uv, w, h, b0, mask=mask)
+    want_c, want_b = orc.motion_step_bgr(bgr * (mask != 0)[..., None].astype(np.uint8), b0)
+    assert cm == want_c and np.array_equal(bm, want_b)
+    assert not np.array_equal(bm, orc.motion_step_nv12(y, uv, w, h, b0)[1])
