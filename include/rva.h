@@ -622,6 +622,21 @@ int rva_preview_nv12(rva_ctx *ctx, const void *y, const void *uv, int pitch, int
                      void *out_bgr, int dst_w, int dst_h, const int32_t *rects, const uint8_t *colors, int n_rects,
                      const int32_t *glyphs, int n_glyphs, int glyph_scale, rva_stream_t stream);
 
+/* K6 for n surfaces in ONE launch (the previews of a tick, kafka_sink.py:134-146): the same per-pixel arithmetic as
+ * rva_preview_nv12 for every item.  `table_host` (pinned host memory, so that the copy is asynchronous; untouched until it has
+ * run) holds, back to back: rva_preview_item[n]; int32 rects[n_rects][4]; int32 glyphs[n_glyphs][3]; uint8 colors[n_rects][4] --
+ * an item draws rects / colors [rect_first, rect_first + n_rects) and glyphs [glyph_first, glyph_first + n_glyphs) of the packed
+ * arrays.  The call checks every item, copies the table to `table_dev` (device, table_bytes >= the table's size) with one
+ * asynchronous copy and launches once.  ratio per item as above (0: out_bgr already holds the base image, y / uv unused). */
+typedef struct rva_preview_item {
+    const void *y, *uv;
+    void *out_bgr;
+    int32_t pitch, src_w, src_h, ratio, dst_w, dst_h;
+    int32_t rect_first, n_rects, glyph_first, n_glyphs;
+} rva_preview_item;
+int rva_preview_nv12_batch(rva_ctx *ctx, const void *table_host, void *table_dev, int64_t table_bytes, int n, int n_rects,
+                           int n_glyphs, int glyph_scale, rva_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * D1 decode -- stands where VideoStream.open()/frames() sit on cv2.VideoCapture(url, CAP_FFMPEG) (video_stream.py:76,
  * 173): an H.264 / H.265 Annex-B elementary stream goes to the VCN decoder through rocDecode and comes back as NV12
@@ -664,12 +679,36 @@ int rva_decoder_release(rva_decoder *dec, int pic_index);
  * edge rules, islow DCT, quantisation tables of `quality`), Annex-K Huffman tables, one restart interval per MCU row: a decoder
  * reconstructs exactly the picture it reconstructs from libjpeg's own file of the same quality (the reference asks for the
  * progressive, Huffman-optimised form of the same coefficients).  rva_jpeg_max_bytes: a capacity that fits photographic content
- * (128 B per 8x8 block); rva_jpeg_status (host-synchronous): bit 0 = the stream did not fit since the last call.
+ * (128 B per 8x8 block); rva_jpeg_status (host-synchronous): bit 0 = a stream did not fit since the last call (*out_size is -1
+ * for such a picture).
+ * CONCURRENCY: the scratch of rva_jpeg_encode_bgr belongs to the context -- ONE stream and one thread at a time per context
+ * (calls on the same stream queue up safely; a larger picture than any before regrows the scratch behind a device
+ * synchronisation).  Concurrent encodes take one rva_jpeg_batch each.
  * -------------------------------------------------------------------------------------------- */
 int rva_jpeg_max_bytes(int width, int height);
 int rva_jpeg_encode_bgr(rva_ctx *ctx, const void *bgr, int pitch, int width, int height, int quality, void *out,
                         int out_capacity, int32_t *out_size, rva_stream_t stream);
 int rva_jpeg_status(rva_ctx *ctx, rva_stream_t stream, int *flags);
+
+/* Batched K7: KafkaSink.send_tracks renders and encodes one preview per due stream (sinks/kafka_sink.py:134-146, 200-294); the
+ * rate limit of 0.1 s (kafka_sink.py:49) makes every stream of a 30 fps pipeline due on the same tick.  An rva_jpeg_batch owns
+ * every buffer an encode touches (coefficients, interval staging, sizes, flags, the descriptor table and its pinned staging),
+ * allocated once by _create for up to max_images pictures of up to max_width x max_height each: _encode allocates nothing,
+ * never synchronises the device and never regrows -- a batch outside those bounds is RVA_ERR_ARG and launches nothing.
+ * _encode: n BGR images in HBM (HOST arrays of n device pointers / pitches / widths / heights / qualities, mixed freely) ->
+ * their JFIF streams back to back in `out` (device, out_capacity bytes), in order; out_sizes[n] (device or mapped host int32):
+ * the length of each stream, or -1 for a picture that failed (an interval overflowed its 128 B per block, or `out` had no room
+ * left for it) -- it takes no bytes and the pictures after it pack on.  A fixed number of launches whatever n (one table copy,
+ * transform, entropy coding, size scan, gather), all asynchronous on `stream`; every byte is what rva_jpeg_encode_bgr writes for
+ * that picture alone.
+ * CONCURRENCY: one object serves one stream at a time (consecutive calls on that stream queue up safely; the pinned staging is
+ * guarded by an event).  Distinct objects share nothing and are independent on distinct streams and threads. */
+typedef struct rva_jpeg_batch rva_jpeg_batch;
+int rva_jpeg_batch_create(rva_ctx *ctx, int max_images, int max_width, int max_height, rva_jpeg_batch **out);
+void rva_jpeg_batch_destroy(rva_jpeg_batch *enc);
+int rva_jpeg_batch_encode(rva_jpeg_batch *enc, int n, const void *const *bgr, const int32_t *pitch, const int32_t *width,
+                          const int32_t *height, const int32_t *quality, void *out, int64_t out_capacity, int32_t *out_sizes,
+                          rva_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,12 @@ class Cnn3dWeights(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
 
 
+class PreviewItem(C.Structure):
+    """``rva_preview_item`` (include/rva.h): one surface of ``rva_preview_nv12_batch``."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("out_bgr", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("pitch", "src_w", "src_h", "ratio", "dst_w", "dst_h", "rect_first", "n_rects", "glyph_first", "n_glyphs")]
+
+
 RVA_PLAN_NO_STEM2 = 1
 RVA_PLAN_NO_CIN_PAD = 2
 RVA_PLAN_NO_PAIR32 = 4
@@ -244,6 +250,10 @@ def lib() -> C.CDLL:
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
+        "rva_jpeg_batch_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+        "rva_jpeg_batch_destroy": (None, [_P]),
+        "rva_jpeg_batch_encode": (C.c_int, [_P, C.c_int, pp, i32p, i32p, i32p, i32p, _P, C.c_int64, _P, _P]),
+        "rva_preview_nv12_batch": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == header/library mismatch: fail loudly
@@ -276,6 +286,7 @@ EXPORTS = [
     "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
     "rva_cnnlstm_plan_run_post", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
     "rva_cnn3d_plan_run_post", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
 ]
 
 

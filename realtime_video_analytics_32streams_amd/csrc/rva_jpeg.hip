@@ -15,9 +15,15 @@
 //                 bit counts places the blocks, lanes OR their bits into the pass's stream (LDS atomics), the complete bytes
 //                 are byte-stuffed (0xFF -> 0xFF 0x00; positions by ballot + popcount) into the interval's staging area, the
 //                 odd bits carry into the next pass; the interval ends padded with ones + RSTn (EOI after the last).
-//   k7_gather     header + intervals -> one contiguous stream, its length to `out_size`.
-// Every stage is byte / integer work: bit-exact against the oracle (tests/test_gpu_api.py).  Not a hot-path kernel: previews are
-// rate-limited to 10 per second per stream (kafka_sink.py:49) -- 1080p encodes in well under a millisecond, latency-bound.
+//   k7_scan       per image the offset of every interval in its stream and the stream's length; then the images back to back.
+//   k7_gather     header + intervals -> one contiguous stream per image, its length to `out_size[image]`.
+// The kernels take a DESCRIPTOR TABLE (per image: pointer, geometry, quantisation divisors, header bytes -- built on the host, one
+// async copy from pinned staging) and the image index in blockIdx.y, so n pictures of mixed sizes and qualities are one launch
+// set: the ~4 300 restart intervals of 32 x 1080p fill the chip where one picture's 68 waves cannot (rva_jpeg_batch_*).
+// rva_jpeg_encode_bgr is a batch of one through the same kernels.  An image whose interval overflows its staging area, or that
+// the remaining capacity of `out` does not hold, reports -1, takes no bytes and leaves its neighbours intact.
+// Every stage is byte / integer work: bit-exact against the oracle (tests/test_gpu_api.py, tests/test_gpu_preview_batch.py).
+// Previews are rate-limited to 10 per second per stream (kafka_sink.py:49): at 30 fps all streams come due on the same tick.
 #include <cstring>
 
 #include "rva_internal.h"
@@ -60,18 +66,28 @@ struct HuffTables {          // code << 8 | size per symbol: [0] DC luma, [1] DC
     uint32_t t[4][256];
 };
 
-struct K7Args {
+struct K7Img {                             // one image of a batch: what the host builds per picture (the descriptor table)
     const uint8_t *bgr; int pitch, w, h;
     int mw, mh;                         // MCUs per row / rows
+    int header_len;
     uint16_t qdiv[2][64];               // quantisation divisors (table << 3), natural order: [0] luma, [1] chroma
-    int16_t *coef;                      // [mh * mw * 6][64] zigzag order
-    const HuffTables *huff;
-    uint8_t *stage; int stage_stride;   // per restart interval: stage_stride bytes
-    int32_t *isize;                     // [mh] bytes of each interval (marker included)
-    int32_t *flags;                     // bit 0: an interval did not fit its staging area / the stream did not fit `out`
-    uint8_t *out; int out_cap; int32_t *out_size;
-    uint8_t header[640]; int header_len;
+    uint8_t header[640];
 };
+
+struct K7Args {                            // one launch set: image i owns slot i of every scratch array (sized for the object's largest picture)
+    const K7Img *img; int n;
+    int16_t *coef; size_t coef_img;     // [n][coef_img] int16: [mh * mw * 6][64] zigzag order per image
+    const HuffTables *huff;
+    uint8_t *stage; size_t stage_img;   // [n][stage_img] bytes; per restart interval of an image: mw * 6 * 128 + 16 bytes
+    int32_t *isize, *ioff; int rows_img;// [n][rows_img] bytes of each interval (marker included) / its offset in the image's stream
+    int32_t *flags;                     // [n] bit 0: an interval of the image did not fit its staging area (cleared by k7_scan)
+    int32_t *total;                     // [n] bytes of the image's stream, -1: failed
+    long long *img_off;                 // [n] offset of the image's stream in `out`, -1: failed or no room left
+    uint8_t *out; long long out_cap; int32_t *out_size;      // out_size[n]: bytes of each stream, -1: failed (takes no bytes)
+    int32_t *sticky;                    // optional: bit 0 set when any image of the launch failed (rva_jpeg_status)
+};
+
+__device__ __forceinline__ int k7_stride(const K7Img &d) { return d.mw * 6 * 128 + 16; }
 
 __device__ __forceinline__ void ycc(const uint8_t *p, int &y, int &cb, int &cr)
 {
@@ -116,7 +132,9 @@ __device__ __forceinline__ int quant(int x, int q)                 // jcdctmgr.c
 }
 
 // sample of component `comp` (0 Y, 1 Cb, 2 Cr) at its own resolution, with libjpeg's edge rules
-__device__ __forceinline__ int sample(const K7Args &a, int comp, int yy, int xx)
+struct K7Geom { const uint8_t *bgr; int pitch, w, h; };            // the part of a descriptor a sample needs, in registers
+
+__device__ __forceinline__ int sample(const K7Geom &a, int comp, int yy, int xx)
 {
     int y, cb, cr;
     if (comp == 0) {
@@ -136,17 +154,20 @@ __device__ __forceinline__ int sample(const K7Args &a, int comp, int yy, int xx)
     return s >> 2;
 }
 
-__global__ void __launch_bounds__(64) k7_transform(K7Args a)
+__global__ void __launch_bounds__(64) k7_transform(K7Args b)
 {
+    const int img = blockIdx.y;
+    const K7Img &a = b.img[img];
     const int blk = blockIdx.x * 64 + threadIdx.x;
-    if (blk >= a.mw * a.mh * 6) return;
+    if (blk >= a.mw * a.mh * 6) return;                            // the grid covers the largest image of the batch
+    const K7Geom g{a.bgr, a.pitch, a.w, a.h};
     const int mcu = blk / 6, k = blk - mcu * 6, my = mcu / a.mw, mx = mcu - my * a.mw;
     const int comp = k < 4 ? 0 : k - 3;
     int by = comp == 0 ? 2 * my + (k >> 1) : my, bx = comp == 0 ? 2 * mx + (k & 1) : mx;
-    int16_t *o = a.coef + (size_t)blk * 64;
+    int16_t *o = b.coef + (size_t)img * b.coef_img + (size_t)blk * 64;
     const uint16_t *qd = a.qdiv[comp ? 1 : 0];
     if (comp == 0) {
-        const int nby = (a.h + 7) >> 3, nbx = (a.w + 7) >> 3;
+        const int nby = (g.h + 7) >> 3, nbx = (g.w + 7) >> 3;
         const bool dr = bx >= nbx, db = by >= nby;                 // dummy block at the right edge / in a dummy row at the bottom
         if (dr || db) {
             // jccoefct.c: AC = 0, DC = the DC of the block before it in the MCU buffer -- the block to the left (right edge), the
@@ -155,7 +176,7 @@ __global__ void __launch_bounds__(64) k7_transform(K7Args a)
             if (db) { by = 2 * my; bx = 2 * mx + 1; }
             if (bx >= nbx) bx = 2 * mx;
             int sum = 0;
-            for (int i = 0; i < 64; ++i) sum += sample(a, 0, by * 8 + (i >> 3), bx * 8 + (i & 7)) - 128;
+            for (int i = 0; i < 64; ++i) sum += sample(g, 0, by * 8 + (i >> 3), bx * 8 + (i & 7)) - 128;
             o[0] = (int16_t)quant(sum, qd[0]);
             for (int i = 1; i < 64; ++i) o[i] = 0;
             return;
@@ -163,7 +184,7 @@ __global__ void __launch_bounds__(64) k7_transform(K7Args a)
     }
     int d[64];
 #pragma unroll
-    for (int i = 0; i < 64; ++i) d[i] = sample(a, comp, by * 8 + (i >> 3), bx * 8 + (i & 7)) - 128;
+    for (int i = 0; i < 64; ++i) d[i] = sample(g, comp, by * 8 + (i >> 3), bx * 8 + (i & 7)) - 128;
 #pragma unroll
     for (int r = 0; r < 8; ++r) fdct8<true>(d + 8 * r, 1);
 #pragma unroll
@@ -189,14 +210,19 @@ __device__ __forceinline__ void put(BitW &b, uint32_t code, int size)
 __device__ __forceinline__ void put_sym(BitW &b, uint32_t e) { put(b, e >> 8, (int)(e & 0xff)); }
 __device__ __forceinline__ int nbits(int v) { const int t = v < 0 ? -v : v; return t ? 32 - __clz(t) : 0; }
 
-__global__ void __launch_bounds__(64) k7_entropy(K7Args a)
+__global__ void __launch_bounds__(64) k7_entropy(K7Args b)
 {
     __shared__ uint32_t priv[64 * K7_PRIV];
     __shared__ uint32_t grp[K7_GROUP];
+    const int img = blockIdx.y;
+    const K7Img &a = b.img[img];
     const int my = blockIdx.x, lane = threadIdx.x;
+    if (my >= a.mh) return;                                        // the grid covers the tallest image of the batch
     const int nblk = a.mw * 6;
-    uint8_t *dst = a.stage + (size_t)my * a.stage_stride;
-    const int cap = a.stage_stride - 8;
+    const int stage_stride = k7_stride(a);
+    uint8_t *dst = b.stage + (size_t)img * b.stage_img + (size_t)my * stage_stride;
+    const int16_t *coef = b.coef + (size_t)img * b.coef_img;
+    const int cap = stage_stride - 8;
     int out_pos = 0, carry_bits = 0;
     bool over = false;
     for (int i = lane; i < K7_GROUP; i += 64) grp[i] = 0;
@@ -208,11 +234,11 @@ __global__ void __launch_bounds__(64) k7_entropy(K7Args a)
         uint32_t *mine = priv + lane * K7_PRIV;
         if (live) {
             const int mx = bi / 6, k = bi - mx * 6;
-            const int16_t *zz = a.coef + ((size_t)my * nblk + bi) * 64;
+            const int16_t *zz = coef + ((size_t)my * nblk + bi) * 64;
             int pred = 0;                                          // DC prediction restarts with the interval
             if (k >= 1 && k <= 3) pred = zz[-64];
             else if (mx > 0) pred = k == 0 ? zz[-3 * 64] : zz[-6 * 64];
-            const uint32_t *dc = a.huff->t[k < 4 ? 0 : 1], *ac = a.huff->t[k < 4 ? 2 : 3];
+            const uint32_t *dc = b.huff->t[k < 4 ? 0 : 1], *ac = b.huff->t[k < 4 ? 2 : 3];
             BitW bw{0ull, 0, 0, mine};
             const int diff = (int)zz[0] - pred;
             int nb = nbits(diff);
@@ -286,27 +312,55 @@ __global__ void __launch_bounds__(64) k7_entropy(K7Args a)
             dst[out_pos + 1] = my + 1 < a.mh ? (uint8_t)(0xd0 + (my & 7)) : 0xd9;      // RSTn between intervals, EOI after the last
         }
         out_pos += 2;
-        a.isize[my] = out_pos;
-        if (over || out_pos > a.stage_stride) atomicOr(a.flags, 1);
+        b.isize[(size_t)img * b.rows_img + my] = out_pos;
+        if (over || out_pos > stage_stride) atomicOr(b.flags + img, 1);
     }
 }
 
-__global__ void __launch_bounds__(256) k7_gather(K7Args a)
+// sizes and packed offsets: per image the offset of every interval inside its stream and the stream's length, then (one thread,
+// n is small) the images back to back in `out`.  An image with an overflowed interval, or one the remaining capacity does not
+// hold, reports -1 and takes no bytes; the ones after it pack on.  Clears the per-image flags for the next launch set.
+__global__ void __launch_bounds__(256) k7_scan(K7Args b)
 {
-    const int my = blockIdx.x, tid = threadIdx.x;
-    long off = a.header_len;
-    for (int j = 0; j < my; ++j) off += a.isize[j];
-    const int n = a.isize[my];
-    const bool fits = off + n <= a.out_cap && n <= a.stage_stride;
-    if (my == 0)
-        for (int i = tid; i < a.header_len && i < a.out_cap; i += 256) a.out[i] = a.header[i];
-    if (fits) {
-        const uint8_t *src = a.stage + (size_t)my * a.stage_stride;
-        for (int i = tid; i < n; i += 256) a.out[off + i] = src[i];
-    } else if (tid == 0) {
-        atomicOr(a.flags, 1);
+    for (int i = threadIdx.x; i < b.n; i += 256) {
+        const K7Img &a = b.img[i];
+        int off = a.header_len;
+        for (int my = 0; my < a.mh; ++my) {
+            b.ioff[(size_t)i * b.rows_img + my] = off;
+            off += b.isize[(size_t)i * b.rows_img + my];
+        }
+        b.total[i] = b.flags[i] ? -1 : off;
+        b.flags[i] = 0;
     }
-    if (my == a.mh - 1 && tid == 0) *a.out_size = (int32_t)(off + n);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long pos = 0;
+        bool failed = false;
+        for (int i = 0; i < b.n; ++i) {
+            const int t = b.total[i];
+            if (t > 0 && pos + t <= b.out_cap) {
+                b.img_off[i] = pos; b.out_size[i] = t; pos += t;
+            } else {
+                b.img_off[i] = -1; b.out_size[i] = -1; failed = true;
+            }
+        }
+        if (failed && b.sticky) atomicOr(b.sticky, 1);
+    }
+}
+
+__global__ void __launch_bounds__(256) k7_gather(K7Args b)
+{
+    const int img = blockIdx.y, my = blockIdx.x, tid = threadIdx.x;
+    const K7Img &a = b.img[img];
+    if (my >= a.mh) return;
+    const long long base = b.img_off[img];
+    if (base < 0) return;
+    uint8_t *o = b.out + base;
+    if (my == 0)
+        for (int i = tid; i < a.header_len; i += 256) o[i] = a.header[i];
+    const int n = b.isize[(size_t)img * b.rows_img + my], off = b.ioff[(size_t)img * b.rows_img + my];
+    const uint8_t *src = b.stage + (size_t)img * b.stage_img + (size_t)my * k7_stride(a);
+    for (int i = tid; i < n; i += 256) o[off + i] = src[i];
 }
 
 void make_codes(const uint8_t *bits, const uint8_t *vals, uint32_t *tbl)     // jchuff.c jpeg_make_c_derived_tbl
@@ -326,70 +380,11 @@ int put_seg(uint8_t *h, int p, uint8_t marker, const uint8_t *payload, int n)
     return p + n;
 }
 
-}  // namespace
-
-struct rva_jpeg_state {      // per-context scratch of the encoder (grown on demand, freed with the context)
-    HuffTables *huff = nullptr;
-    int16_t *coef = nullptr; size_t coef_bytes = 0;
-    uint8_t *stage = nullptr; size_t stage_bytes = 0;
-    int32_t *isize = nullptr; int isize_n = 0;
-    int32_t *flags = nullptr;
-};
-
-void rva_jpeg_free(rva_ctx *ctx)
+// per-image descriptor: geometry, quantisation divisors of `quality`, the JFIF header bytes
+void make_desc(K7Img &a, const void *bgr, int pitch, int width, int height, int quality)
 {
-    rva_jpeg_state *s = ctx->jpeg;
-    if (!s) return;
-    (void)hipFree(s->huff); (void)hipFree(s->coef); (void)hipFree(s->stage); (void)hipFree(s->isize); (void)hipFree(s->flags);
-    delete s;
-    ctx->jpeg = nullptr;
-}
-
-extern "C" {
-
-int rva_jpeg_max_bytes(int width, int height)
-{
-    if (width <= 0 || height <= 0) return 0;
-    const long mw = (width + 15) / 16, mh = (height + 15) / 16;
-    return (int)(640 + mh * (mw * 6 * 128 + 16));                 // header + 128 B per block: ample for photographic content at quality <= 95
-}
-
-int rva_jpeg_encode_bgr(rva_ctx *ctx, const void *bgr, int pitch, int width, int height, int quality, void *out, int out_capacity,
-                        int32_t *out_size, rva_stream_t stream)
-{
-    if (!ctx || !bgr || !out || !out_size || width <= 0 || height <= 0 || width > 65500 || height > 65500 || pitch < 3 * width ||
-        quality < 1 || quality > 100 || out_capacity < 1024)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_jpeg_encode_bgr: bad argument (quality 1..100, pitch >= 3 width, capacity >= 1024)");
-    RVA_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (!ctx->jpeg) {
-        ctx->jpeg = new rva_jpeg_state();
-        HuffTables h{};
-        make_codes(kDcLumaBits, kDcVals, h.t[0]);
-        make_codes(kDcChromaBits, kDcVals, h.t[1]);
-        make_codes(kAcLumaBits, kAcLumaVals, h.t[2]);
-        make_codes(kAcChromaBits, kAcChromaVals, h.t[3]);
-        RVA_HIP(ctx, hipMalloc(&ctx->jpeg->huff, sizeof(HuffTables)));
-        RVA_HIP(ctx, hipMemcpy(ctx->jpeg->huff, &h, sizeof(HuffTables), hipMemcpyHostToDevice));
-        RVA_HIP(ctx, hipMalloc(&ctx->jpeg->flags, 4));
-        RVA_HIP(ctx, hipMemset(ctx->jpeg->flags, 0, 4));
-    }
-    rva_jpeg_state *st = ctx->jpeg;
-    K7Args a{};
     a.bgr = (const uint8_t *)bgr; a.pitch = pitch; a.w = width; a.h = height;
     a.mw = (width + 15) / 16; a.mh = (height + 15) / 16;
-    const size_t nblk = (size_t)a.mw * a.mh * 6;
-    a.stage_stride = a.mw * 6 * 128 + 16;
-    if (nblk * 128 > st->coef_bytes || (size_t)a.mh * a.stage_stride > st->stage_bytes || a.mh > st->isize_n) {
-        RVA_HIP(ctx, hipDeviceSynchronize());                      // a larger picture than before: regrow the scratch (not on the steady path)
-        (void)hipFree(st->coef); (void)hipFree(st->stage); (void)hipFree(st->isize);
-        st->coef = nullptr; st->stage = nullptr; st->isize = nullptr; st->coef_bytes = st->stage_bytes = 0; st->isize_n = 0;
-        RVA_HIP(ctx, hipMalloc(&st->coef, nblk * 128)); st->coef_bytes = nblk * 128;
-        RVA_HIP(ctx, hipMalloc(&st->stage, (size_t)a.mh * a.stage_stride)); st->stage_bytes = (size_t)a.mh * a.stage_stride;
-        RVA_HIP(ctx, hipMalloc(&st->isize, (size_t)a.mh * 4)); st->isize_n = a.mh;
-    }
-    a.coef = st->coef; a.huff = st->huff; a.stage = st->stage; a.isize = st->isize; a.flags = st->flags;
-    a.out = (uint8_t *)out; a.out_cap = out_capacity; a.out_size = out_size;
     // quantisation tables: jcparam.c jpeg_quality_scaling + jpeg_add_quant_table (force_baseline)
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     uint8_t ql[64], qc[64];
@@ -400,19 +395,16 @@ int rva_jpeg_encode_bgr(rva_ctx *ctx, const void *bgr, int pitch, int width, int
         a.qdiv[0][i] = (uint16_t)(ql[i] << 3);
         a.qdiv[1][i] = (uint16_t)(qc[i] << 3);
     }
-    // header: SOI, JFIF APP0, two DQT, SOF0 (4:2:0), four DHT, DRI (one MCU row), SOS
-    static const uint8_t zz[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
-                                   28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
-                                   47, 55, 62, 63};
+    // header: SOI, JFIF APP0, two DQT, SOF0 (4:2:0), four DHT, DRI (one MCU row), SOS -- 629 bytes
     uint8_t *h = a.header;
     int p = 0;
     h[p++] = 0xff; h[p++] = 0xd8;
     const uint8_t app0[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     p = put_seg(h, p, 0xe0, app0, 14);
     uint8_t dqt[65];
-    dqt[0] = 0; for (int i = 0; i < 64; ++i) dqt[1 + i] = ql[zz[i]];
+    dqt[0] = 0; for (int i = 0; i < 64; ++i) dqt[1 + i] = ql[kZigzag[i]];
     p = put_seg(h, p, 0xdb, dqt, 65);
-    dqt[0] = 1; for (int i = 0; i < 64; ++i) dqt[1 + i] = qc[zz[i]];
+    dqt[0] = 1; for (int i = 0; i < 64; ++i) dqt[1 + i] = qc[kZigzag[i]];
     p = put_seg(h, p, 0xdb, dqt, 65);
     const uint8_t sof[15] = {8, (uint8_t)(height >> 8), (uint8_t)(height & 0xff), (uint8_t)(width >> 8), (uint8_t)(width & 0xff), 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};
     p = put_seg(h, p, 0xc0, sof, 15);
@@ -430,12 +422,168 @@ int rva_jpeg_encode_bgr(rva_ctx *ctx, const void *bgr, int pitch, int width, int
     const uint8_t sos[10] = {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
     p = put_seg(h, p, 0xda, sos, 10);
     a.header_len = p;
-    if (p > (int)sizeof a.header) return rva_fail(ctx, RVA_ERR_ARG, "rva_jpeg_encode_bgr: header overflow");
-    k7_transform<<<(unsigned)((nblk + 63) / 64), 64, 0, s>>>(a);
-    k7_entropy<<<a.mh, 64, 0, s>>>(a);
-    k7_gather<<<a.mh, 256, 0, s>>>(a);
+}
+static_assert(sizeof(((K7Img *)nullptr)->header) >= 629, "the JFIF header of make_desc is 629 bytes");
+
+}  // namespace
+
+// The encoder object: every buffer a launch set touches, allocated once for `max_images` pictures of up to max_w x max_h.
+struct rva_jpeg_batch {
+    rva_ctx *ctx = nullptr;
+    int max_images = 0, max_w = 0, max_h = 0;
+    K7Args a{};                          // the device pointers and per-image slot sizes (img / n / out* are set per call)
+    HuffTables *huff = nullptr;
+    K7Img *tab_dev = nullptr, *tab_host = nullptr;      // descriptor table and its pinned staging
+    hipEvent_t uploaded = nullptr;       // the staging is free to rewrite once the previous call's copy has run
+};
+
+namespace {
+
+int batch_run(rva_jpeg_batch *e, const char *who, int n, const void *const *bgr, const int32_t *pitch, const int32_t *width,
+              const int32_t *height, const int32_t *quality, void *out, long long out_capacity, int32_t *out_sizes, int32_t *sticky,
+              hipStream_t s)
+{
+    rva_ctx *ctx = e->ctx;
+    if (n < 1 || n > e->max_images) return rva_fail(ctx, RVA_ERR_ARG, "%s: %d images, the encoder was created for 1..%d", who, n, e->max_images);
+    int top_w = 0, top_h = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!bgr[i] || width[i] <= 0 || height[i] <= 0 || width[i] > 65500 || height[i] > 65500 || pitch[i] < 3 * width[i] || quality[i] < 1 ||
+            quality[i] > 100)
+            return rva_fail(ctx, RVA_ERR_ARG, "%s: bad argument for image %d (quality 1..100, pitch >= 3 width)", who, i);
+        if (width[i] > e->max_w || height[i] > e->max_h)
+            return rva_fail(ctx, RVA_ERR_ARG, "%s: image %d is %dx%d, the encoder was created for up to %dx%d", who, i, width[i], height[i],
+                            e->max_w, e->max_h);
+        top_w = width[i] > top_w ? width[i] : top_w;
+        top_h = height[i] > top_h ? height[i] : top_h;
+    }
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    RVA_HIP(ctx, hipEventSynchronize(e->uploaded));               // (returns at once unless a previous table is still on its way)
+    for (int i = 0; i < n; ++i) make_desc(e->tab_host[i], bgr[i], pitch[i], width[i], height[i], quality[i]);
+    RVA_HIP(ctx, hipMemcpyAsync(e->tab_dev, e->tab_host, (size_t)n * sizeof(K7Img), hipMemcpyHostToDevice, s));
+    RVA_HIP(ctx, hipEventRecord(e->uploaded, s));
+    K7Args a = e->a;
+    a.img = e->tab_dev; a.n = n;
+    a.out = (uint8_t *)out; a.out_cap = out_capacity; a.out_size = out_sizes; a.sticky = sticky;
+    const unsigned rows = (unsigned)((top_h + 15) / 16), blocks = (unsigned)((top_w + 15) / 16) * rows * 6;
+    k7_transform<<<dim3((blocks + 63) / 64, (unsigned)n), 64, 0, s>>>(a);
+    k7_entropy<<<dim3(rows, (unsigned)n), 64, 0, s>>>(a);
+    k7_scan<<<1, 256, 0, s>>>(a);
+    k7_gather<<<dim3(rows, (unsigned)n), 256, 0, s>>>(a);
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
+}
+
+}  // namespace
+
+struct rva_jpeg_state {      // per-context encoder of rva_jpeg_encode_bgr: a batch object for one picture (regrown for a larger one, freed with the context)
+    rva_jpeg_batch *one = nullptr;
+    int32_t *flags = nullptr;
+};
+
+void rva_jpeg_free(rva_ctx *ctx)
+{
+    rva_jpeg_state *s = ctx->jpeg;
+    if (!s) return;
+    rva_jpeg_batch_destroy(s->one);
+    (void)hipFree(s->flags);
+    delete s;
+    ctx->jpeg = nullptr;
+}
+
+extern "C" {
+
+int rva_jpeg_max_bytes(int width, int height)
+{
+    if (width <= 0 || height <= 0) return 0;
+    const long mw = (width + 15) / 16, mh = (height + 15) / 16;
+    return (int)(640 + mh * (mw * 6 * 128 + 16));                 // header + 128 B per block: ample for photographic content at quality <= 95
+}
+
+int rva_jpeg_batch_create(rva_ctx *ctx, int max_images, int max_width, int max_height, rva_jpeg_batch **out)
+{
+    if (!ctx || !out || max_images < 1 || max_images > 4096 || max_width <= 0 || max_height <= 0 || max_width > 65500 || max_height > 65500)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_jpeg_batch_create: bad argument (1..4096 images of up to 65500x65500)");
+    *out = nullptr;
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    rva_jpeg_batch *e = new rva_jpeg_batch();
+    e->ctx = ctx; e->max_images = max_images; e->max_w = max_width; e->max_h = max_height;
+    const size_t mw = (size_t)(max_width + 15) / 16, mh = (size_t)(max_height + 15) / 16, n = (size_t)max_images;
+    K7Args &a = e->a;
+    a.coef_img = mw * mh * 6 * 64; a.stage_img = mh * (mw * 6 * 128 + 16); a.rows_img = (int)mh;
+    HuffTables h{};
+    make_codes(kDcLumaBits, kDcVals, h.t[0]);
+    make_codes(kDcChromaBits, kDcVals, h.t[1]);
+    make_codes(kAcLumaBits, kAcLumaVals, h.t[2]);
+    make_codes(kAcChromaBits, kAcChromaVals, h.t[3]);
+    hipError_t err = hipMalloc(&e->huff, sizeof(HuffTables));
+    if (err == hipSuccess) err = hipMemcpy(e->huff, &h, sizeof(HuffTables), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMalloc(&a.coef, n * a.coef_img * sizeof(int16_t));
+    if (err == hipSuccess) err = hipMalloc(&a.stage, n * a.stage_img);
+    if (err == hipSuccess) err = hipMalloc(&a.isize, n * mh * 4);
+    if (err == hipSuccess) err = hipMalloc(&a.ioff, n * mh * 4);
+    if (err == hipSuccess) err = hipMalloc(&a.flags, n * 4);
+    if (err == hipSuccess) err = hipMemset(a.flags, 0, n * 4);
+    if (err == hipSuccess) err = hipMalloc(&a.total, n * 4);
+    if (err == hipSuccess) err = hipMalloc(&a.img_off, n * 8);
+    if (err == hipSuccess) err = hipMalloc(&e->tab_dev, n * sizeof(K7Img));
+    if (err == hipSuccess) err = hipHostMalloc(&e->tab_host, n * sizeof(K7Img), hipHostMallocDefault);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&e->uploaded, hipEventDisableTiming);
+    if (err != hipSuccess) {
+        rva_jpeg_batch_destroy(e);
+        return rva_fail(ctx, RVA_ERR_HIP, "rva_jpeg_batch_create: %s (%d images of up to %dx%d)", hipGetErrorString(err), max_images, max_width,
+                        max_height);
+    }
+    a.huff = e->huff;
+    *out = e;
+    return RVA_OK;
+}
+
+void rva_jpeg_batch_destroy(rva_jpeg_batch *e)
+{
+    if (!e) return;
+    (void)hipSetDevice(e->ctx->device);
+    (void)hipFree(e->huff); (void)hipFree(e->a.coef); (void)hipFree(e->a.stage); (void)hipFree(e->a.isize); (void)hipFree(e->a.ioff);
+    (void)hipFree(e->a.flags); (void)hipFree(e->a.total); (void)hipFree(e->a.img_off); (void)hipFree(e->tab_dev);
+    if (e->tab_host) (void)hipHostFree(e->tab_host);
+    if (e->uploaded) (void)hipEventDestroy(e->uploaded);
+    delete e;
+}
+
+int rva_jpeg_batch_encode(rva_jpeg_batch *enc, int n, const void *const *bgr, const int32_t *pitch, const int32_t *width,
+                          const int32_t *height, const int32_t *quality, void *out, int64_t out_capacity, int32_t *out_sizes,
+                          rva_stream_t stream)
+{
+    if (!enc) return RVA_ERR_ARG;
+    if (!bgr || !pitch || !width || !height || !quality || !out || !out_sizes || out_capacity < 1)
+        return rva_fail(enc->ctx, RVA_ERR_ARG, "rva_jpeg_batch_encode: bad argument");
+    return batch_run(enc, "rva_jpeg_batch_encode", n, bgr, pitch, width, height, quality, out, out_capacity, out_sizes, nullptr,
+                     (hipStream_t)stream);
+}
+
+int rva_jpeg_encode_bgr(rva_ctx *ctx, const void *bgr, int pitch, int width, int height, int quality, void *out, int out_capacity,
+                        int32_t *out_size, rva_stream_t stream)
+{
+    if (!ctx || !bgr || !out || !out_size || width <= 0 || height <= 0 || width > 65500 || height > 65500 || pitch < 3 * width ||
+        quality < 1 || quality > 100 || out_capacity < 1024)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_jpeg_encode_bgr: bad argument (quality 1..100, pitch >= 3 width, capacity >= 1024)");
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->jpeg) {
+        ctx->jpeg = new rva_jpeg_state();
+        RVA_HIP(ctx, hipMalloc(&ctx->jpeg->flags, 4));
+        RVA_HIP(ctx, hipMemset(ctx->jpeg->flags, 0, 4));
+    }
+    rva_jpeg_state *st = ctx->jpeg;
+    if (!st->one || width > st->one->max_w || height > st->one->max_h) {
+        RVA_HIP(ctx, hipDeviceSynchronize());                      // a larger picture than before: regrow the scratch (not on the steady path)
+        const int mw = st->one && st->one->max_w > width ? st->one->max_w : width, mh = st->one && st->one->max_h > height ? st->one->max_h : height;
+        rva_jpeg_batch_destroy(st->one);
+        st->one = nullptr;
+        const int rc = rva_jpeg_batch_create(ctx, 1, mw, mh, &st->one);
+        if (rc != RVA_OK) return rc;
+    }
+    const void *const images[1] = {bgr};
+    const int32_t p[1] = {pitch}, w[1] = {width}, h[1] = {height}, q[1] = {quality};
+    return batch_run(st->one, "rva_jpeg_encode_bgr", 1, images, p, w, h, q, out, out_capacity, out_size, st->flags, (hipStream_t)stream);
 }
 
 int rva_jpeg_status(rva_ctx *ctx, rva_stream_t stream, int *flags)

@@ -40,10 +40,9 @@ __device__ __forceinline__ int font_row(int ch)
     switch (ch) { case 'I': return 10; case 'D': return 11; case 'c': return 13; case 'l': return 14; case 's': return 15; default: return 12; }
 }
 
-__global__ void __launch_bounds__(256) k6_preview(K6Args a)
+// one output pixel: the body shared by the single-surface and the batched kernel
+__device__ __forceinline__ void k6_pixel(const K6Args &a, int x, int yy)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), yy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= a.dst_w || yy >= a.dst_h) return;
     uint8_t *o = a.out + ((size_t)yy * a.dst_w + x) * 3;
     int b, g, r;
     if (a.ratio == 0) {
@@ -77,6 +76,31 @@ __global__ void __launch_bounds__(256) k6_preview(K6Args a)
     o[0] = (uint8_t)b; o[1] = (uint8_t)g; o[2] = (uint8_t)r;
 }
 
+__global__ void __launch_bounds__(256) k6_preview(K6Args a)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), yy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.dst_w || yy >= a.dst_h) return;
+    k6_pixel(a, x, yy);
+}
+
+struct K6Batch {
+    const rva_preview_item *items;
+    const int32_t *rects, *glyphs;       // the packed arrays of the table
+    const uint8_t *colors;
+    int glyph_scale;
+};
+
+__global__ void __launch_bounds__(256) k6_preview_batch(K6Batch b)      // blockIdx.z: the item; the grid covers the largest output
+{
+    const rva_preview_item &it = b.items[blockIdx.z];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), yy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= it.dst_w || yy >= it.dst_h) return;
+    const K6Args a{(const uint8_t *)it.y, (const uint8_t *)it.uv, it.pitch, it.src_w, it.src_h, it.ratio, (uint8_t *)it.out_bgr, it.dst_w, it.dst_h,
+                   b.rects + 4 * (size_t)it.rect_first, b.colors + 4 * (size_t)it.rect_first, it.n_rects,
+                   b.glyphs + 3 * (size_t)it.glyph_first, it.n_glyphs, b.glyph_scale};
+    k6_pixel(a, x, yy);
+}
+
 }  // namespace
 
 extern "C" int rva_preview_nv12(rva_ctx *ctx, const void *y, const void *uv, int pitch, int src_w, int src_h, int ratio, void *out_bgr,
@@ -92,6 +116,38 @@ extern "C" int rva_preview_nv12(rva_ctx *ctx, const void *y, const void *uv, int
              rects, colors, n_rects, glyphs, n_glyphs, glyph_scale};
     dim3 grid(rva_ceil_div(dst_w, 64), rva_ceil_div(dst_h, 4));
     k6_preview<<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
+extern "C" int rva_preview_nv12_batch(rva_ctx *ctx, const void *table_host, void *table_dev, int64_t table_bytes, int n, int n_rects,
+                                      int n_glyphs, int glyph_scale, rva_stream_t stream)
+{
+    if (!ctx || !table_host || !table_dev || n < 1 || n > 65535 || n_rects < 0 || n_glyphs < 0 || glyph_scale < 1)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_preview_nv12_batch: bad argument");
+    const size_t o_rects = (size_t)n * sizeof(rva_preview_item), o_glyphs = o_rects + (size_t)n_rects * 16,
+                 o_colors = o_glyphs + (size_t)n_glyphs * 12, bytes = o_colors + (size_t)n_rects * 4;
+    if (table_bytes < 0 || (size_t)table_bytes < bytes)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_preview_nv12_batch: the table takes %zu bytes, table_bytes is %lld", bytes, (long long)table_bytes);
+    const rva_preview_item *items = (const rva_preview_item *)table_host;
+    int top_w = 0, top_h = 0;
+    for (int i = 0; i < n; ++i) {
+        const rva_preview_item &t = items[i];
+        if (!t.out_bgr || t.dst_w <= 0 || t.dst_h <= 0 || t.ratio < 0 || t.n_rects < 0 || t.n_glyphs < 0 || t.rect_first < 0 || t.glyph_first < 0 ||
+            (long)t.rect_first + t.n_rects > n_rects || (long)t.glyph_first + t.n_glyphs > n_glyphs)
+            return rva_fail(ctx, RVA_ERR_ARG, "rva_preview_nv12_batch: bad item %d (output, size or a primitive range outside the table)", i);
+        if (t.ratio > 0 && (!t.y || !t.uv || t.pitch < t.src_w || ((t.src_w | t.src_h) & 1) || (long)t.dst_w * t.ratio > t.src_w ||
+                            (long)t.dst_h * t.ratio > t.src_h || t.ratio > 8))
+            return rva_fail(ctx, RVA_ERR_ARG, "rva_preview_nv12_batch: the surface of item %d does not cover dst x ratio (even NV12 size, ratio <= 8)", i);
+        top_w = t.dst_w > top_w ? t.dst_w : top_w;
+        top_h = t.dst_h > top_h ? t.dst_h : top_h;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    RVA_HIP(ctx, hipMemcpyAsync(table_dev, table_host, bytes, hipMemcpyHostToDevice, s));
+    const uint8_t *d = (const uint8_t *)table_dev;
+    K6Batch b{(const rva_preview_item *)d, (const int32_t *)(d + o_rects), (const int32_t *)(d + o_glyphs), d + o_colors, glyph_scale};
+    dim3 grid(rva_ceil_div(top_w, 64), rva_ceil_div(top_h, 4), n);
+    k6_preview_batch<<<grid, 256, 0, s>>>(b);
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
 }

@@ -3,6 +3,7 @@ every computation happens in librva.so (HIP).  No operation here has a torch/CPU
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -616,27 +617,182 @@ class DeviceTracker:
         self.ctx.check(N.lib().rva_tracker_set_next_id(self.handle, int(v), _stream_ptr()), "rva_tracker_set_next_id")
 
 
+_JPEG_LOCK = threading.Lock()      # rva_jpeg_encode_bgr's scratch belongs to the context: one encode at a time (include/rva.h)
+
+
+def _check_bgr_image(img: torch.Tensor, who: str) -> None:
+    _require_cuda(img, "image")
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or img.stride(2) != 1 or img.stride(1) != 3:
+        raise ValueError(f"{who} takes a uint8 [h, w, 3] device tensor with packed pixels")
+
+
 def jpeg_encode_bgr(img: torch.Tensor, quality: int, ctx: Optional[N.Context] = None) -> bytes:
     """K7: a uint8 BGR image ``[h, w, 3]`` in HBM (what ``preview.render_nv12`` returns) -> baseline JFIF bytes, encoded on the
     device (``rva_jpeg_encode_bgr``: libjpeg's arithmetic, 4:2:0, Annex-K tables, one restart interval per MCU row).  Only the
-    finished stream crosses PCIe.  Replaces ``cv2.imencode('.jpg', ...)`` of sinks/kafka_sink.py:260-284."""
+    finished stream crosses PCIe.  Replaces ``cv2.imencode('.jpg', ...)`` of sinks/kafka_sink.py:260-284.  Calls are serialised:
+    the encoder's scratch is one set per context (threads that encode concurrently take a :class:`JpegBatchEncoder` each)."""
     ctx = ctx or context()
-    _require_cuda(img, "image")
-    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or img.stride(2) != 1 or img.stride(1) != 3:
-        raise ValueError("jpeg_encode_bgr takes a uint8 [h, w, 3] device tensor with packed pixels")
+    _check_bgr_image(img, "jpeg_encode_bgr")
     h, w = int(img.shape[0]), int(img.shape[1])
     L = N.lib()
     cap = int(L.rva_jpeg_max_bytes(w, h))
-    bufs = ctx.__dict__.setdefault("_jpeg_bufs", {})
-    if cap not in bufs:
-        bufs[cap] = (torch.empty(cap, dtype=torch.uint8, device=img.device), torch.zeros(1, dtype=torch.int32, device=img.device))
-    out, size = bufs[cap]
-    s = _stream_ptr()
-    ctx.check(L.rva_jpeg_encode_bgr(ctx.handle, C.c_void_p(img.data_ptr()), int(img.stride(0)), w, h, int(quality), C.c_void_p(out.data_ptr()),
-                                    cap, C.c_void_p(size.data_ptr()), s), "rva_jpeg_encode_bgr")
-    n = int(size.item())                                            # the one host sync
-    flags = C.c_int(0)
-    ctx.check(L.rva_jpeg_status(ctx.handle, s, C.byref(flags)), "rva_jpeg_status")
-    if flags.value & 1 or not 0 < n <= cap:
-        raise RuntimeError(f"device JPEG encoder: the stream did not fit {cap} bytes ({w}x{h}, quality {quality})")
-    return out[:n].cpu().numpy().tobytes()
+    with _JPEG_LOCK:
+        bufs = ctx.__dict__.setdefault("_jpeg_bufs", {})
+        if cap not in bufs:
+            bufs[cap] = (torch.empty(cap, dtype=torch.uint8, device=img.device), torch.zeros(1, dtype=torch.int32, device=img.device))
+        out, size = bufs[cap]
+        s = _stream_ptr()
+        ctx.check(L.rva_jpeg_encode_bgr(ctx.handle, C.c_void_p(img.data_ptr()), int(img.stride(0)), w, h, int(quality), C.c_void_p(out.data_ptr()),
+                                        cap, C.c_void_p(size.data_ptr()), s), "rva_jpeg_encode_bgr")
+        n = int(size.item())                                            # the one host sync
+        flags = C.c_int(0)
+        ctx.check(L.rva_jpeg_status(ctx.handle, s, C.byref(flags)), "rva_jpeg_status")
+        if flags.value & 1 or not 0 < n <= cap:
+            raise RuntimeError(f"device JPEG encoder: the stream did not fit {cap} bytes ({w}x{h}, quality {quality})")
+        return out[:n].cpu().numpy().tobytes()
+
+
+class JpegBatchEncoder:
+    """Batched K7 (``rva_jpeg_batch_*``): ``n <= max_images`` BGR images in HBM, each up to ``max_wh``, sizes and qualities mixed,
+    encoded by ONE launch set -- every stream is what :func:`jpeg_encode_bgr` gives for that image alone.  The object owns the
+    encoder's scratch, the packed output buffer and the pinned host buffers, all allocated here: ``encode`` allocates nothing on
+    the device and synchronises with the host twice whatever ``n`` (the sizes, then one copy of the packed bytes).
+    One object serves one stream at a time; distinct objects are independent on distinct streams and threads.
+    ``enqueue`` + ``fetch`` are the two halves of ``encode`` (work of several objects can be queued before any host wait)."""
+
+    def __init__(self, max_images: int, max_wh: Tuple[int, int] = (1920, 1080), ctx: Optional[N.Context] = None):
+        self.ctx = ctx or context()
+        self.max_images, self.max_wh = int(max_images), (int(max_wh[0]), int(max_wh[1]))
+        L = N.lib()
+        h = C.c_void_p()
+        self.ctx.check(L.rva_jpeg_batch_create(self.ctx.handle, self.max_images, self.max_wh[0], self.max_wh[1], C.byref(h)), "rva_jpeg_batch_create")
+        self.handle = h
+        dev = torch.device("cuda", self.ctx.device)
+        self.capacity = self.max_images * int(L.rva_jpeg_max_bytes(*self.max_wh))
+        self._out = torch.empty(self.capacity, dtype=torch.uint8, device=dev)
+        self._sizes = torch.zeros(self.max_images, dtype=torch.int32, device=dev)
+        self._h_out = torch.empty(self.capacity, dtype=torch.uint8).pin_memory()
+        self._h_sizes = torch.zeros(self.max_images, dtype=torch.int32).pin_memory()
+        self._done = torch.cuda.Event()
+        self._pending = None
+        self.host_syncs = 0              # host synchronisations so far (two per batch)
+
+    def encode_into(self, images: Sequence[torch.Tensor], qualities: Sequence[int], out: torch.Tensor, capacity: int, sizes: torch.Tensor) -> None:
+        """The C call itself: streams packed into ``out[:capacity]``, lengths (or -1) into ``sizes[:n]``; asynchronous."""
+        n = len(images)
+        if len(qualities) != n:
+            raise ValueError("one quality per image")
+        for im in images:
+            _check_bgr_image(im, "JpegBatchEncoder")
+        ptrs, keep_p = N.ptr_array([im.data_ptr() for im in images])
+        pitch, keep_a = N.i32_array([im.stride(0) for im in images])
+        ws, keep_b = N.i32_array([im.shape[1] for im in images])
+        hs, keep_c = N.i32_array([im.shape[0] for im in images])
+        qs, keep_d = N.i32_array(qualities)
+        self.ctx.check(N.lib().rva_jpeg_batch_encode(self.handle, n, ptrs, pitch, ws, hs, qs, C.c_void_p(out.data_ptr()), int(capacity),
+                                                     C.c_void_p(sizes.data_ptr()), _stream_ptr()), "rva_jpeg_batch_encode")
+
+    def enqueue(self, images: Sequence[torch.Tensor], qualities: Sequence[int]) -> None:
+        if self._pending is not None:
+            raise RuntimeError("JpegBatchEncoder: the previous batch has not been fetched")
+        images = list(images)
+        self.encode_into(images, qualities, self._out, self.capacity, self._sizes)
+        n = len(images)
+        self._h_sizes[:n].copy_(self._sizes[:n], non_blocking=True)
+        self._done.record()
+        self._pending = (images, torch.cuda.current_stream())      # the images stay alive until their streams are on the host
+
+    def fetch(self) -> List[bytes]:
+        if self._pending is None:
+            raise RuntimeError("JpegBatchEncoder: nothing was enqueued")
+        images, stream = self._pending
+        self._pending = None
+        n = len(images)
+        self._done.synchronize(); self.host_syncs += 1               # sync 1: the sizes
+        sizes = self._h_sizes[:n].tolist()
+        total = sum(v for v in sizes if v > 0)
+        if total:
+            with torch.cuda.stream(stream):
+                self._h_out[:total].copy_(self._out[:total], non_blocking=True)
+                self._done.record()
+            self._done.synchronize(); self.host_syncs += 1           # sync 2: the packed bytes, one copy
+        failed = [i for i, v in enumerate(sizes) if v <= 0]
+        if failed:
+            raise RuntimeError(f"device JPEG encoder: the streams of images {failed} of {n} did not fit (128 B per 8x8 block, "
+                               f"{self.capacity} bytes for the batch)")
+        buf = self._h_out.numpy()
+        res, pos = [], 0
+        for v in sizes:
+            res.append(buf[pos:pos + v].tobytes())
+            pos += v
+        return res
+
+    def encode(self, images: Sequence[torch.Tensor], qualities: Sequence[int]) -> List[bytes]:
+        self.enqueue(images, qualities)
+        return self.fetch()
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.ctx.device)
+            N.lib().rva_jpeg_batch_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class PreviewStaging:
+    """Pinned host table + its device copy for :func:`preview_nv12_batch` (grown on demand, outside the steady path)."""
+
+    def __init__(self, device, nbytes: int = 1 << 16):
+        self.device = device
+        self.host = self.dev = None
+        self.free = torch.cuda.Event()       # recorded behind each upload: the host table may be rewritten once it has run
+        self.ensure(nbytes)
+
+    def ensure(self, nbytes: int) -> None:
+        if self.host is None or self.host.numel() < nbytes:
+            if self.host is not None:
+                self.free.synchronize()
+            size = max(int(nbytes), 2 * (self.host.numel() if self.host is not None else 0))
+            self.host = torch.empty(size, dtype=torch.uint8).pin_memory()
+            self.dev = torch.empty(size, dtype=torch.uint8, device=self.device)
+
+
+def preview_nv12_batch(surfaces: Sequence[Optional[Nv12Surface]], outs: Sequence[torch.Tensor], ratios: Sequence[int], prims: Sequence[tuple],
+                       glyph_scale: int = 2, ctx: Optional[N.Context] = None, staging: Optional[PreviewStaging] = None) -> List[torch.Tensor]:
+    """K6 for ``n`` surfaces in one launch (``rva_preview_nv12_batch``): ``outs[i]`` (uint8 ``[h, w, 3]`` in HBM) becomes the preview of
+    ``surfaces[i]`` box-averaged down by ``ratios[i]`` (0: ``outs[i]`` already holds the base image, the surface may be None) with
+    ``prims[i] = (rects, colors, glyphs)`` of ``preview.raster_primitives`` drawn over it -- pixel for pixel what
+    ``rva_preview_nv12`` writes per surface.  The descriptors and every primitive go up as ONE table in one async copy from pinned
+    memory (``staging``: reused across calls; without one a table is allocated for the call)."""
+    from .preview import pack_primitives
+    ctx = ctx or context()
+    n = len(outs)
+    if not (len(surfaces) == len(ratios) == len(prims) == n) or n < 1:
+        raise ValueError("preview_nv12_batch: one surface, ratio and primitive set per output (at least one)")
+    rects, colors, glyphs, offs = pack_primitives(prims)
+    items = (N.PreviewItem * n)()
+    for i, (sf, out, ratio) in enumerate(zip(surfaces, outs, ratios)):
+        _check_bgr_image(out, "preview_nv12_batch")
+        if not out.is_contiguous():
+            raise ValueError("preview_nv12_batch: outputs are contiguous [h, w, 3] images")
+        it = items[i]
+        if ratio:
+            it.y, it.uv, it.pitch, it.src_w, it.src_h = sf.y.data_ptr(), sf.uv.data_ptr(), sf.pitch, sf.width, sf.height
+        it.out_bgr, it.ratio, it.dst_w, it.dst_h = out.data_ptr(), int(ratio), int(out.shape[1]), int(out.shape[0])
+        it.rect_first, it.n_rects, it.glyph_first, it.n_glyphs = offs[i]
+    blob = b"".join((bytes(items), rects.tobytes(), glyphs.tobytes(), colors.tobytes()))
+    st = staging or PreviewStaging(outs[0].device, len(blob))
+    st.ensure(len(blob))
+    st.free.synchronize()                                            # (at once unless the previous table is still on its way)
+    st.host.numpy()[:len(blob)] = np.frombuffer(blob, np.uint8)
+    ctx.check(N.lib().rva_preview_nv12_batch(ctx.handle, C.c_void_p(st.host.data_ptr()), C.c_void_p(st.dev.data_ptr()), len(blob), n,
+                                             len(rects), len(glyphs), int(glyph_scale), _stream_ptr()), "rva_preview_nv12_batch")
+    st.free.record()
+    if staging is None:
+        st.free.synchronize()                                        # the table dies with this call
+    return list(outs)

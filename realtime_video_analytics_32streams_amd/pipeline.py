@@ -31,12 +31,12 @@ from __future__ import annotations
 
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import ops
+from . import ops, wire
 from .config import PipelineConfig, StreamConfig
 from .detector import create_detector, filter_detections
 from .gates import AdaptiveFps, MotionGate, rasterize_polygons
@@ -50,6 +50,7 @@ class TickResult:
     tracks: Dict[str, List[Track]]          # per stream, every surviving track (tracker.py:95)
     detections_emitted: Dict[str, int]      # len(filtered) of pipeline.py:187 (after F1)
     latency_s: float
+    frame_jpeg: Dict[str, str] = field(default_factory=dict)   # per stream whose preview was due: the wire message's ``frame_jpeg`` data URL
 
 
 class StreamCounters:
@@ -120,6 +121,7 @@ class TickPipeline:
         self.n_global = n_global_streams or len(self.streams)
         self._tick = 0
         self.snapshots = None          # a preview.SnapshotWriter: StreamWorker._maybe_save_snapshot (pipeline.py:196, 264-290)
+        self.previews = None           # a preview.PreviewBatcher: the ``frame_jpeg`` of KafkaSink.send_tracks (kafka_sink.py:134-146), one batch per tick
         # pre-detector gates, configured by the reference's StreamConfig keys
         self.adaptive = [AdaptiveFps(s) for s in self.streams]
         self._motion: Optional[MotionGate] = None
@@ -353,10 +355,18 @@ class TickPipeline:
             for i, n in zip(live, names):                             # frame's surface must still be alive when its tick is collected
                 if n in emitted:
                     self.snapshots.maybe_save(packets[i], tracks[n])
+        frame_jpeg: Dict[str, str] = {}
+        if self.previews is not None:                                 # same frames, same lifetime rule as the snapshot: the previews of every
+            due = [(i, n) for i, n in zip(live, names) if n in emitted]      # stream the rate limit lets through are ONE render + encode batch
+            payloads = [wire.tracks_payload(n, packets[i].frame_id, tracks[n]) for i, n in due]
+            surfaces = [packets[i].frame if isinstance(packets[i].frame, ops.Nv12Surface) else None for i, _ in due]
+            for p in self.previews.attach(payloads, surfaces):
+                if "frame_jpeg" in p:
+                    frame_jpeg[p["stream"]] = p["frame_jpeg"]
         for n in names:
             self.counters.update(n, 1, emitted.get(n, 0), len(tracks[n]))
         self._tick += 1
-        return TickResult(self._tick - 1, tracks, emitted, time.perf_counter() - t0)
+        return TickResult(self._tick - 1, tracks, emitted, time.perf_counter() - t0, frame_jpeg)
 
     def tick(self, process: Optional[Sequence[bool]] = None, device_gates: bool = False) -> TickResult:
         """One synchronous tick.  Gates: decided on the host by default (gated-out frames never reach the detector);

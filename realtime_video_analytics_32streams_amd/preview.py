@@ -227,6 +227,129 @@ def attach_preview(payload: dict, surface, policy: PreviewPolicy, ctx=None) -> d
     return payload
 
 
+# ---------------------------------------------------------------------------------------------- a whole tick's previews
+# The rate limit is per stream and 0.1 s wide: at 30 fps every stream comes due on the same tick, every third tick.  One
+# render_frame per stream pays three uploads, four launches and three host waits each; render_frames does the same work for all
+# of them with one table upload, one K6 launch, one K7 launch set and two host waits.
+
+def pack_primitives(prims: Sequence[tuple]):
+    """The primitives of a batch as ONE table: ``prims[i] = (rects, colors, glyphs)`` of :func:`raster_primitives` -> the three
+    arrays concatenated in order + per image ``(rect_first, n_rects, glyph_first, n_glyphs)`` (what ``rva_preview_item`` carries)."""
+    offs, r0, g0 = [], 0, 0
+    for r, c, g in prims:
+        if len(r) != len(c):
+            raise ValueError("one colour per rectangle")
+        offs.append((r0, len(r), g0, len(g)))
+        r0 += len(r); g0 += len(g)
+    cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(p[k], dt).reshape(-1, w) for p in prims] or  # noqa: E731
+                                                              [np.zeros((0, w), dt)]), dt)
+    return cat(0, np.int32, 4), cat(1, np.uint8, 4), cat(2, np.int32, 3), offs
+
+
+def _target(surface, ops: Sequence[list]) -> Tuple[int, int, int]:
+    """(tw, th, ratio) of a plan on a surface: ratio 1 same size, k an integer box mean, 0 a resize stage first (render_nv12)."""
+    w, h = surface.width, surface.height
+    tw, th = w, h
+    for op in ops:
+        if op[0] == "resize":
+            tw, th = op[1]
+    if (tw, th) == (w, h):
+        return tw, th, 1
+    if w % tw == 0 and h % th == 0 and w // tw == h // th:
+        return tw, th, w // tw
+    return tw, th, 0
+
+
+def render_frames(surfaces: Sequence, track_lists: Sequence[Sequence[dict]], qualities: Sequence[Optional[int]],
+                  policy: Optional[PreviewPolicy] = None, ctx=None, batcher: Optional["PreviewBatcher"] = None) -> List[str]:
+    """``[render_frame(s, t, q, policy, ctx) for s, t, q in zip(...)]`` -- the same data URLs -- with the device work of all
+    images batched: one table upload and one K6 launch draw every preview, one K7 launch set encodes every JPEG one, the sizes
+    and then the packed streams come back in two copies.  WebP images (``webp_available`` and quality >= 80) are drawn in the
+    batch and encoded per image on the host, as in ``render_frame``.  ``batcher`` owns the encoder and the staging across calls
+    (``PreviewBatcher``); without one a batcher cached on the context is used (re-created when a batch outgrows it)."""
+    import torch
+    from . import ops as O
+    n = len(surfaces)
+    if not (len(track_lists) == len(qualities) == n):
+        raise ValueError("render_frames: one track list and one quality per surface")
+    if n == 0:
+        return []
+    policy = policy or (batcher.policy if batcher is not None else PreviewPolicy())
+    ctx = ctx or (batcher.ctx if batcher is not None else O.context())
+    plans, outs, ratios, prims, enc = [], [], [], [], []
+    for sf, tracks, q in zip(surfaces, track_lists, qualities):
+        q = policy.base_quality if q is None else q
+        ops = plan_render((sf.width, sf.height), tracks, q, policy.webp_available)
+        tw, th, ratio = _target(sf, ops)
+        if ratio == 0:                                         # non-integer downscale: the INTER_LINEAR resize stage, then draw only
+            out = O.resize_nv12_to_bgr([sf], (tw, th), ctx=ctx)[0].contiguous()
+        else:
+            out = torch.empty((th, tw, 3), dtype=torch.uint8, device=sf.y.device)
+        plans.append(ops); outs.append(out); ratios.append(ratio)
+        prims.append(raster_primitives(ops, (tw, th)))
+        enc.append(next((op[1], op[2]) for op in ops if op[0] == "encode"))
+    jpeg = [i for i, (ext, _) in enumerate(enc) if ext == ".jpg"]
+    if batcher is None:
+        batcher = _context_batcher(ctx, policy, len(jpeg), (max(o.shape[1] for o in outs), max(o.shape[0] for o in outs)))
+    O.preview_nv12_batch(surfaces, outs, ratios, prims, ctx=ctx, staging=batcher.staging)
+    data: List[Optional[Tuple[bytes, str]]] = [None] * n
+    if jpeg:
+        qs = [int(dict(zip(enc[i][1][0::2], enc[i][1][1::2])).get(IMWRITE_JPEG_QUALITY, 75)) for i in jpeg]
+        for i, b in zip(jpeg, batcher.encoder.encode([outs[i] for i in jpeg], qs)):
+            data[i] = (b, "image/jpeg")
+    for i, (ext, params) in enumerate(enc):
+        if ext != ".jpg":
+            data[i] = encode_image(outs[i].cpu().numpy(), ext, params)
+    return [f"data:{mime};base64,{base64.b64encode(b).decode('ascii')}" for b, mime in data]
+
+
+def attach_previews(payloads: Sequence[dict], surfaces: Sequence, policy: PreviewPolicy, ctx=None,
+                    batcher: Optional["PreviewBatcher"] = None) -> List[dict]:
+    """A loop of :func:`attach_preview` over ``zip(payloads, surfaces)`` with the rendering batched: the policy is asked per
+    payload, in order (its rate-limit state ends up exactly as the loop leaves it), then the due previews are one
+    :func:`render_frames` call."""
+    due = [i for i, (p, sf) in enumerate(zip(payloads, surfaces)) if sf is not None and policy.should_send_frame(p["stream"])]
+    if due:
+        urls = render_frames([surfaces[i] for i in due], [payloads[i]["tracks"] for i in due],
+                             [policy.adaptive_quality(len(payloads[i]["tracks"])) for i in due], policy, ctx, batcher)
+        for i, u in zip(due, urls):
+            payloads[i]["frame_jpeg"] = u
+    return list(payloads)
+
+
+class PreviewBatcher:
+    """What a pipeline needs to send previews (``TickPipeline.previews``): the policy (rate limit, adaptive quality), a
+    :class:`ops.JpegBatchEncoder` for ``max_streams`` previews of up to ``max_wh`` (the plan never exceeds 1920x1080) and the
+    pinned staging of the K6 table -- allocated here, reused every tick."""
+
+    def __init__(self, policy: Optional[PreviewPolicy] = None, max_streams: int = 32, max_wh: Tuple[int, int] = (1920, 1080), ctx=None):
+        from . import ops as O
+        self.policy = policy or PreviewPolicy()
+        self.ctx = ctx or O.context()
+        self.max_streams, self.max_wh = int(max_streams), (int(max_wh[0]), int(max_wh[1]))
+        self.encoder = O.JpegBatchEncoder(self.max_streams, self.max_wh, self.ctx)
+        self.staging = O.PreviewStaging(self.encoder._out.device, 64 * self.max_streams + 4096 * self.max_streams)
+
+    def render(self, surfaces: Sequence, track_lists: Sequence[Sequence[dict]], qualities: Sequence[Optional[int]]) -> List[str]:
+        return render_frames(surfaces, track_lists, qualities, self.policy, self.ctx, self)
+
+    def attach(self, payloads: Sequence[dict], surfaces: Sequence) -> List[dict]:
+        return attach_previews(payloads, surfaces, self.policy, self.ctx, self)
+
+
+def _context_batcher(ctx, policy: PreviewPolicy, n: int, wh: Tuple[int, int]) -> PreviewBatcher:
+    """The batcher ``render_frames`` falls back on: one per context, replaced by a larger one when a batch outgrows it."""
+    b = ctx.__dict__.get("_preview_batcher")
+    n = max(n, 1)
+    if b is None or n > b.max_streams or wh[0] > b.max_wh[0] or wh[1] > b.max_wh[1]:
+        old = b
+        b = PreviewBatcher(policy, max(n, old.max_streams if old else 1), (max(wh[0], old.max_wh[0] if old else 1), max(wh[1], old.max_wh[1] if old else 1)), ctx)
+        if old is not None:
+            old.encoder.close()
+        ctx.__dict__["_preview_batcher"] = b
+    return b
+
+
 # ---------------------------------------------------------------------------------------------- five-minute snapshots
 SNAPSHOT_INTERVAL = 300.0                     # pipeline.py:269
 SNAPSHOT_ROOT = "/data/outputs"               # pipeline.py:282
