@@ -513,6 +513,19 @@ int rva_yolov8_plan_get_variant(const rva_yolov8_plan *plan, int index);
  *   (0, 0, w, h) and counts[row] = k; a row without one gets counts[row] = 0.  scores / boxes / cls have row stride max_det
  *   (>= k) as in the post-process buffers of rva_postprocess_batch.
  * rva_cnnlstm_plan_info: pooled map size (height / width after the max pool), conv2 tiles per frame, launches per _run.
+ * rva_cnnlstm_plan_stage: a read-only tap on the workspace for tests and tools: ONE device-to-device copy on `stream` of the
+ *   first n_clips clips' worth of one intermediate tensor into dst (device fp32, dst_floats elements of room), the element
+ *   count in *n_floats (may be NULL).  Valid after a _run of at least n_clips clips on the same stream, until the next _run.
+ *   dst == NULL only reports the count.  RVA_ERR_ARG (and no copy) for a null plan, an unknown stage, n_clips outside
+ *   1..max_clips or dst_floats below the count.  _run neither changes nor gains a launch.  With n = n_clips, T = frames,
+ *   h = hidden, Hp x Wp the pooled map and P = Hp * Wp:
+ *     RVA_CNNLSTM_STAGE_POOLED   [n*T][Hp][Wp][64]          stem output: conv1 + BN + ReLU + max pool, channels last
+ *     RVA_CNNLSTM_STAGE_PARTIAL  [n*T][conv2_tiles][128]    per-tile channel sums of ReLU(conv2 + BN); tile k holds pixels
+ *                                                           256k .. min(256k + 255, P - 1) of the raster [Hp][Wp]
+ *     RVA_CNNLSTM_STAGE_FEAT     [n*T][128]                 the spatial mean: tile sums in tile order, divided by P
+ *     RVA_CNNLSTM_STAGE_GX       [n][T][4h]                 layer 1's input projection feat . W_ih1^T + (b_ih1 + b_hh1)
+ *     RVA_CNNLSTM_STAGE_H1 / H2  [T][n][h]                  hidden state of LSTM layer 1 / 2 at every step (the workspace
+ *                                                           keeps max_clips rows per step; the tap copies n of them)
  * -------------------------------------------------------------------------------------------- */
 typedef struct rva_cnnlstm_plan rva_cnnlstm_plan;
 typedef struct rva_cnnlstm_desc {
@@ -535,6 +548,12 @@ int rva_cnnlstm_plan_run(rva_cnnlstm_plan *plan, const void *frames, const int32
                          rva_stream_t stream);
 int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
                               void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+enum rva_cnnlstm_stage {
+    RVA_CNNLSTM_STAGE_POOLED = 0, RVA_CNNLSTM_STAGE_PARTIAL = 1, RVA_CNNLSTM_STAGE_FEAT = 2, RVA_CNNLSTM_STAGE_GX = 3,
+    RVA_CNNLSTM_STAGE_H1 = 4, RVA_CNNLSTM_STAGE_H2 = 5
+};
+int rva_cnnlstm_plan_stage(rva_cnnlstm_plan *plan, int stage, int n_clips, void *dst, int64_t dst_floats, int64_t *n_floats,
+                           rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * The 3D-CNN clip network as ONE fp32 object -- replaces the network call of the reference's 3D-CNN head and its top-5
@@ -558,6 +577,13 @@ int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *plan, const void *logits, const 
  * rva_cnn3d_plan_run_post: the arguments and the rule of rva_cnnlstm_plan_run_post (the same kernel).
  * rva_cnn3d_plan_info: pool1[3] = (T, H/2, W/2) after the first pool, pool2[3] = (T/2, H/4, W/4) after the second, tiles[3] =
  *   blocks per frame of conv1 and blocks per clip of conv2 and conv3 (per channel half), launches per _run.  Any may be NULL.
+ * rva_cnn3d_plan_stage: the read-only workspace tap of rva_cnnlstm_plan_stage (same arguments, rules and errors).  With n =
+ *   n_clips, (T, H1, W1) = pool1 and (T2, H2, W2) = pool2 of _info:
+ *     RVA_CNN3D_STAGE_ACT1     [n][T][H1][W1][64]       conv1 + BN + ReLU + (1,2,2) max pool, channels last
+ *     RVA_CNN3D_STAGE_ACT2     [n][T2*H2*W2][128]       conv2 + BN + ReLU + (2,2,2) max pool, positions linear over [T2][H2][W2]
+ *     RVA_CNN3D_STAGE_PARTIAL  [n][conv3_tiles][256]    per-tile channel sums of ReLU(conv3 + BN); tile k holds positions
+ *                                                       256k .. min(256k + 255, T2*H2*W2 - 1), linear over [T2][H2][W2]
+ *     RVA_CNN3D_STAGE_FEAT     [n][256]                 the mean over T2, H2, W2: tile sums in tile order, divided by T2*H2*W2
  * -------------------------------------------------------------------------------------------- */
 typedef struct rva_cnn3d_plan rva_cnn3d_plan;
 typedef struct rva_cnn3d_desc {
@@ -577,6 +603,9 @@ int rva_cnn3d_plan_run(rva_cnn3d_plan *plan, const void *frames, const int32_t *
                        rva_stream_t stream);
 int rva_cnn3d_plan_run_post(rva_cnn3d_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
                             void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+enum rva_cnn3d_stage { RVA_CNN3D_STAGE_ACT1 = 0, RVA_CNN3D_STAGE_ACT2 = 1, RVA_CNN3D_STAGE_PARTIAL = 2, RVA_CNN3D_STAGE_FEAT = 3 };
+int rva_cnn3d_plan_stage(rva_cnn3d_plan *plan, int stage, int n_clips, void *dst, int64_t dst_floats, int64_t *n_floats,
+                         rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)

@@ -242,11 +242,13 @@ def lib() -> C.CDLL:
         "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
         "rva_cnnlstm_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_cnnlstm_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_cnnlstm_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
         "rva_cnn3d_plan_create": (C.c_int, [_P, C.POINTER(Cnn3dDesc), C.POINTER(Cnn3dWeights), C.POINTER(_P)]),
         "rva_cnn3d_plan_destroy": (None, [_P]),
         "rva_cnn3d_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
         "rva_cnn3d_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_cnn3d_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_cnn3d_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -284,8 +286,8 @@ EXPORTS = [
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
     "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
-    "rva_cnnlstm_plan_run_post", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
-    "rva_cnn3d_plan_run_post", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_cnnlstm_plan_run_post", "rva_cnnlstm_plan_stage", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
+    "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
 ]
 

@@ -113,6 +113,20 @@ def pack_cnn_lstm(net) -> Dict[str, np.ndarray]:
     return {n: f32(out[n]) for n in N.CnnLstmWeights.NAMES}
 
 
+def _tap(plan, fn, what: str, stages: Dict[str, tuple], name: str, n_clips: int) -> torch.Tensor:
+    """``stage()`` of both plans: the count from a ``dst == NULL`` call, then the one device-to-device copy."""
+    if name not in stages:
+        raise ValueError(f"{what}: unknown stage {name!r} (one of {', '.join(stages)})")
+    code, shape = stages[name]
+    n = C.c_int64()
+    plan.ctx.check(fn(plan.handle, code, int(n_clips), None, 0, C.byref(n), None), what)
+    if n.value != int(np.prod(shape)):
+        raise RuntimeError(f"{what}: stage {name} has {n.value} floats, the layout {shape} says {int(np.prod(shape))}")
+    out = torch.empty(shape, dtype=torch.float32, device=plan.dev)
+    plan.ctx.check(fn(plan.handle, code, int(n_clips), C.c_void_p(out.data_ptr()), out.numel(), None, ops._stream_ptr()), what)
+    return out
+
+
 class FusedCnnLstm:
     """One ``rva_cnnlstm_plan``: the fp32 clip network of ``net`` for clips of ``frames`` frames at ``hw``, up to ``max_clips``
     clips per call.  No host synchronisation and no allocation after construction (capturable)."""
@@ -166,6 +180,16 @@ class FusedCnnLstm:
                                                    int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()),
                        "rva_cnnlstm_plan_run")
         return out[:n_clips]
+
+    def stage(self, name: str, n_clips: int) -> torch.Tensor:
+        """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n_clips`` clips, on the current stream), in
+        the layout ``rva_cnnlstm_plan_stage`` documents (include/rva.h): ``"pooled"`` ``[n*T, Hp, Wp, 64]``, ``"partial"``
+        ``[n*T, conv2_tiles, 128]``, ``"feat"`` ``[n*T, 128]``, ``"gx"`` ``[n, T, 4*hidden]``, ``"h1"`` / ``"h2"``
+        ``[T, n, hidden]``.  A read-only tap for tests and tools."""
+        n, T, h = int(n_clips), self.T, self.hidden
+        stages = {"pooled": (0, (n * T, *self.pooled_hw, 64)), "partial": (1, (n * T, self.conv2_tiles, 128)),
+                  "feat": (2, (n * T, 128)), "gx": (3, (n, T, 4 * h)), "h1": (4, (T, n, h)), "h2": (5, (T, n, h))}
+        return _tap(self, self.L.rva_cnnlstm_plan_stage, "rva_cnnlstm_plan_stage", stages, name, n)
 
     def __call__(self, clips: torch.Tensor) -> torch.Tensor:
         """``CnnLstmNet.forward`` of contiguous clips ``[B, T, 3, H, W]`` fp32: a fresh ``[B, classes]`` tensor."""
@@ -287,6 +311,16 @@ class Fused3dCnn:
         self.ctx.check(self.L.rva_cnn3d_plan_run(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()),
                                                  int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()), "rva_cnn3d_plan_run")
         return out[:n_clips]
+
+    def stage(self, name: str, n_clips: int) -> torch.Tensor:
+        """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n_clips`` clips, on the current stream), in
+        the layout ``rva_cnn3d_plan_stage`` documents (include/rva.h): ``"act1"`` ``[n, T, H1, W1, 64]``, ``"act2"``
+        ``[n, T2*H2*W2, 128]``, ``"partial"`` ``[n, conv3_tiles, 256]``, ``"feat"`` ``[n, 256]``.  A read-only tap for tests and
+        tools."""
+        n = int(n_clips)
+        stages = {"act1": (0, (n, *self.pool1, 64)), "act2": (1, (n, int(np.prod(self.pool2)), 128)),
+                  "partial": (2, (n, self.tiles[2], 256)), "feat": (3, (n, 256))}
+        return _tap(self, self.L.rva_cnn3d_plan_stage, "rva_cnn3d_plan_stage", stages, name, n)
 
     def __call__(self, clips: torch.Tensor) -> torch.Tensor:
         """``Cnn3dNet.forward`` of clips ``[B, 3, T, H, W]`` fp32: a fresh ``[B, classes]`` tensor.  The permute to frames

@@ -570,4 +570,42 @@ int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *p, const void *logits, const int
                                 (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 
+// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  h1 / h2 keep max_clips rows per
+// step, so fewer clips than the capacity are T rows of n_clips * hidden out of a pitch of max_clips * hidden: one 2D copy.
+int rva_cnnlstm_plan_stage(rva_cnnlstm_plan *p, int stage, int n_clips, void *dst, int64_t dst_floats, int64_t *n_floats,
+                           rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (n_clips < 1 || n_clips > p->d.max_clips)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
+    const int64_t T = p->d.frames, h = p->d.hidden, nf = (int64_t)n_clips * T;
+    const float *src = nullptr;
+    int64_t count = 0;
+    switch (stage) {
+    case RVA_CNNLSTM_STAGE_POOLED: src = p->pooled; count = nf * p->Hp * p->Wp * C1; break;
+    case RVA_CNNLSTM_STAGE_PARTIAL: src = p->partial; count = nf * p->conv2_tiles * C2; break;
+    case RVA_CNNLSTM_STAGE_FEAT: src = p->feat; count = nf * C2; break;
+    case RVA_CNNLSTM_STAGE_GX: src = p->gx; count = nf * 4 * h; break;
+    case RVA_CNNLSTM_STAGE_H1: src = p->h1; count = nf * h; break;
+    case RVA_CNNLSTM_STAGE_H2: src = p->h2; count = nf * h; break;
+    default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: unknown stage %d", stage);
+    }
+    if (n_floats) *n_floats = count;
+    if (!dst) return RVA_OK;
+    if (dst_floats < count)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: dst holds %lld floats, stage %d of %d clips has %lld",
+                        (long long)dst_floats, stage, n_clips, (long long)count);
+    const hipStream_t st = (hipStream_t)stream_;
+    const bool rows = (stage == RVA_CNNLSTM_STAGE_H1 || stage == RVA_CNNLSTM_STAGE_H2) && n_clips < p->d.max_clips;
+    if (rows) {
+        const size_t width = (size_t)n_clips * h * sizeof(float);
+        RVA_HIP(ctx, hipMemcpy2DAsync(dst, width, src, (size_t)p->d.max_clips * h * sizeof(float), width, (size_t)T,
+                                      hipMemcpyDeviceToDevice, st));
+    } else {
+        RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return RVA_OK;
+}
+
 }  // extern "C"

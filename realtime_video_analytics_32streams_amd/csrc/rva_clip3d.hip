@@ -401,4 +401,31 @@ int rva_cnn3d_plan_run_post(rva_cnn3d_plan *p, const void *logits, const int32_t
                                 (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 
+// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is clip-major.
+int rva_cnn3d_plan_stage(rva_cnn3d_plan *p, int stage, int n_clips, void *dst, int64_t dst_floats, int64_t *n_floats,
+                         rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (n_clips < 1 || n_clips > p->d.max_clips)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
+    const int64_t ng = (int64_t)p->T2 * p->H2 * p->W2;
+    const float *src = nullptr;
+    int64_t count = 0;
+    switch (stage) {
+    case RVA_CNN3D_STAGE_ACT1: src = p->act1; count = (int64_t)n_clips * p->d.frames * p->H1 * p->W1 * C1; break;
+    case RVA_CNN3D_STAGE_ACT2: src = p->act2; count = (int64_t)n_clips * ng * C2; break;
+    case RVA_CNN3D_STAGE_PARTIAL: src = p->partial; count = (int64_t)n_clips * p->conv3_tiles * C3; break;
+    case RVA_CNN3D_STAGE_FEAT: src = p->feat; count = (int64_t)n_clips * C3; break;
+    default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: unknown stage %d", stage);
+    }
+    if (n_floats) *n_floats = count;
+    if (!dst) return RVA_OK;
+    if (dst_floats < count)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: dst holds %lld floats, stage %d of %d clips has %lld",
+                        (long long)dst_floats, stage, n_clips, (long long)count);
+    RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+    return RVA_OK;
+}
+
 }  // extern "C"

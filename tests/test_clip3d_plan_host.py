@@ -128,7 +128,7 @@ def test_flop_counter():
 
 def test_new_names_exported():
     for name in ("rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
-                 "rva_cnn3d_plan_run_post"):
+                 "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage"):
         assert name in N.EXPORTS
         assert hasattr(N.lib(), name)
     assert "rva_clip3d.hip" in N.SOURCES

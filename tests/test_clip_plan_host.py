@@ -68,6 +68,6 @@ def test_fired_tables():
 
 def test_new_names_exported():
     for name in ("rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
-                 "rva_cnnlstm_plan_run_post"):
+                 "rva_cnnlstm_plan_run_post", "rva_cnnlstm_plan_stage"):
         assert name in N.EXPORTS
         assert hasattr(N.lib(), name)

@@ -1,0 +1,353 @@
+"""CPU-only proof that the stage bounds of tests/clip_stage_refs.py can see the bugs the clip kernels can make, and that a
+correct fp32 implementation meets them.
+
+For every stage the smallest mutation of its bug class is applied to the float64 reference, which must then leave the bound by
+a factor of at least 4 at one element or more; and torch's own fp32 operators on the CPU, fed the same inputs, must stay inside
+the bound (the reference alone meets the condition the GPU tests put on the kernels).  The inputs are the seeded cases of the
+GPU stage tests; the "taps" are the float64 references rounded once to fp32."""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import clip_stage_refs as R
+
+FACTOR = 4.0                               # a mutation must exceed FACTOR x bound
+L_SMALL, L_RAGGED, L_ODD, L_PASSES, L_BIG = R.LSTM_SHAPES
+C_ONE, C_ODD, C_RAGGED = R.C3D_SHAPES
+
+
+@functools.lru_cache(maxsize=None)
+def _lstm(shape):
+    net, p, clips = R.lstm_case(shape)
+    refs = R.lstm_refs(None, clips, p, shape)
+    taps = {k: v[0].float() for k, v in refs.items() if k != "_lstm"}
+    return p, clips, refs, taps
+
+
+@functools.lru_cache(maxsize=None)
+def _c3d(shape):
+    net, p, frames = R.c3d_case(shape)
+    refs = R.c3d_refs(None, frames, p, shape)
+    return p, frames, refs, {k: v[0].float() for k, v in refs.items()}
+
+
+def _seen(mutated, ref, tol):
+    """The mutation's largest distance from the reference in units of the bound."""
+    r, _ = R.ratio(mutated, ref, tol)
+    return r
+
+
+def _f32(t):
+    return R.f64(t).float()
+
+
+def _tiles32(v):
+    return torch.stack([v[:, :, k:k + R.TILE].sum(2) for k in range(0, v.shape[2], R.TILE)], 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference alone: torch fp32 on the CPU is inside every bound
+@pytest.mark.parametrize("shape", R.LSTM_SHAPES, ids=R.shape_id)
+def test_cnnlstm_torch_fp32_is_inside_every_bound(shape):
+    p, clips, refs, taps = _lstm(shape)
+    H, W, T, hidden, classes, n, _ = shape
+    q = {k: v.float() for k, v in p.items()}
+    got = {}
+    y = F.conv2d(clips.flatten(0, 1).float(), q["conv1_w"], q["conv1_b"], stride=2, padding=3)
+    got["pooled"] = F.max_pool2d(y.relu(), 3, 2, 1).permute(0, 2, 3, 1)
+    y = F.conv2d(taps["pooled"].permute(0, 3, 1, 2), q["conv2_w"], q["conv2_b"], padding=1).relu()
+    got["partial"] = _tiles32(y.flatten(2))
+    got["feat"] = taps["partial"].sum(1) / torch.tensor(float(y.shape[2] * y.shape[3]), dtype=torch.float32)
+    got["gx"] = (taps["feat"] @ q["w_ih1"].T + q["b1"]).view(n, T, -1)
+    got["h1"], got["h2"] = R.lstm(taps["gx"], p, dtype=torch.float32)
+    got["logits"] = taps["h2"][T - 1] @ q["head_w"].T + q["head_b"]
+    e_ref, bound = refs["_lstm"]
+    print(f"{R.shape_id(shape)}: e_ref {e_ref:.3e}, LSTM bound {bound:.3e}")
+    bad = []
+    for k, v in got.items():
+        assert v.dtype == torch.float32
+        R.report(shape, k, v, *refs[k], out=bad)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("shape", R.C3D_SHAPES, ids=R.shape_id)
+def test_cnn3d_torch_fp32_is_inside_every_bound(shape):
+    p, frames, refs, taps = _c3d(shape)
+    T, H, W, classes, n, _ = shape
+    thw = (T // 2, H // 4, W // 4)
+    q = {k: v.float() for k, v in p.items()}
+    got = {}
+    y = F.conv3d(frames.float().permute(0, 2, 1, 3, 4), q["conv1_w"], q["conv1_b"], padding=1)
+    got["act1"] = F.max_pool3d(y.relu(), (1, 2, 2)).permute(0, 2, 3, 4, 1)
+    y = F.conv3d(taps["act1"].permute(0, 4, 1, 2, 3), q["conv2_w"], q["conv2_b"], padding=1)
+    got["act2"] = F.max_pool3d(y.relu(), 2).permute(0, 2, 3, 4, 1).flatten(1, 3)
+    y = F.conv3d(taps["act2"].view(n, *thw, 128).permute(0, 4, 1, 2, 3), q["conv3_w"], q["conv3_b"], padding=1).relu()
+    got["partial"] = _tiles32(y.flatten(2))
+    got["feat"] = taps["partial"].sum(1) / torch.tensor(float(thw[0] * thw[1] * thw[2]), dtype=torch.float32)
+    got["logits"] = taps["feat"] @ q["head_w"].T + q["head_b"]
+    bad = []
+    for k, v in got.items():
+        assert v.dtype == torch.float32
+        R.report(shape, k, v, *refs[k], out=bad)
+    assert not bad, bad
+
+
+def test_own_float64_lstm_is_torch_nn_lstm():
+    p, clips, refs, taps = _lstm(L_RAGGED)
+    n, T = L_RAGGED[5], L_RAGGED[2]
+    gx = R.gx_from_feat(taps["feat"], p, n, T)[0]
+    for a, b in zip(R.lstm(gx, p), R.torch_lstm(taps["feat"], p, n, T, torch.float64)):
+        assert (a - b).abs().max() < 1e-13
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stem (k_clip_stem)
+def _stem(shape):
+    p, clips, refs, _ = _lstm(shape)
+    y, t = R.stem_conv(R.f64(clips).flatten(0, 1), p)
+    return p, R.f64(clips).flatten(0, 1), y, t, refs["pooled"]
+
+
+@pytest.mark.parametrize("shape", [L_RAGGED, L_ODD, L_BIG], ids=R.shape_id)
+def test_stem_tap_dropped_in_the_last_conv_column_that_reads_it(shape):
+    """Tap (c, ky, kx) = (2, 6, 6) dropped in one conv column.  In the very last column, (W - 1) // 2, that tap reads input
+    column 2 cx + 3 >= W -- zero padding for every W -- so dropping it there changes nothing; the mutation takes the last column
+    in which the tap is inside the frame, cx = (W - 4) // 2."""
+    p, x, y, t, (ref, tol) = _stem(shape)
+    W, Wc = shape[1], y.shape[3]
+    cx = (W - 4) // 2
+    assert 2 * cx + 3 < W <= 2 * (cx + 1) + 3 and 2 * (Wc - 1) + 3 >= W
+    w = p["conv1_w"].clone()
+    w[:, 2, 6, 6] = 0
+    ym = F.conv2d(x, w, p["conv1_b"], stride=2, padding=3)
+    assert torch.equal(ym[..., cx + 1:], y[..., cx + 1:])
+    y2 = y.clone()
+    y2[..., cx] = ym[..., cx]
+    seen = _seen(R.stem_pool(y2, t)[0], ref, tol)
+    print(f"{R.shape_id(shape)}: seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+@pytest.mark.parametrize("shape", [L_RAGGED, L_PASSES], ids=R.shape_id)
+def test_stem_pool_window_loses_a_column(shape):
+    _, _, y, t, (ref, tol) = _stem(shape)
+    assert y.shape[3] % 2 == 0                              # even Wc: dx = 2 of the last pooled column is a real conv column
+    v = y.relu()
+    v[..., -1] = -float("inf")
+    mut = F.max_pool2d(v, 3, 2, 1).permute(0, 2, 3, 1)
+    assert torch.equal(mut[:, :, :-1], ref[:, :, :-1])
+    assert _seen(mut, ref, tol) > FACTOR
+
+
+@pytest.mark.parametrize("shape", [L_RAGGED, L_ODD, L_BIG], ids=R.shape_id)
+def test_stem_ragged_tile_shifted_by_one_pixel(shape):
+    _, _, _, _, (ref, tol) = _stem(shape)
+    Wp = ref.shape[2]
+    x0 = 8 * ((Wp - 1) // 8)
+    assert Wp % 8 and x0 > 0                                # the last tile column is ragged
+    mut = ref.clone()
+    mut[:, :, x0:] = ref[:, :, x0 - 1:Wp - 1]
+    assert _seen(mut, ref, tol) > FACTOR
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# conv2 (k_clip_conv2) and 3D conv3 (k_c3d_conv3): per-tile sums that never write the map; 3D conv2: the pooled map
+def _conv2(shape):
+    p, _, refs, taps = _lstm(shape)
+    x = taps["pooled"].double().permute(0, 3, 1, 2)
+    y, t = R.conv2_map(taps["pooled"], p)
+    return x, p["conv2_w"], p["conv2_b"], y, t, refs["partial"], F.conv2d, 576
+
+
+def _conv3(shape):
+    p, _, refs, taps = _c3d(shape)
+    T, H, W, _, n, _ = shape
+    thw = (T // 2, H // 4, W // 4)
+    x = taps["act2"].double().view(n, *thw, 128).permute(0, 4, 1, 2, 3)
+    y, t = R.c3d_conv3(taps["act2"], p, thw)
+    return x, p["conv3_w"], p["conv3_b"], y, t, refs["partial"], F.conv3d, 3456
+
+
+def _c3d_conv2(shape):
+    p, _, refs, taps = _c3d(shape)
+    x = taps["act1"].double().permute(0, 4, 1, 2, 3)
+    y, t = R.c3d_conv2(taps["act1"], p)
+    return x, p["conv2_w"], p["conv2_b"], y, t, refs["act2"], F.conv3d, 1728
+
+
+def _finish(case, y, t):
+    """The stage's output from a (mutated) pre-ReLU map."""
+    if case is _c3d_conv2:
+        return R.c3d_pool(y, t, (2, 2, 2))[0].flatten(1, 3)
+    return R.partial_from_map(y, t)[0]
+
+
+TILE_SUMS = [(_conv2, s) for s in (L_SMALL, L_RAGGED, L_ODD, L_PASSES, L_BIG)] + [(_conv3, s) for s in R.C3D_SHAPES]
+CONVS = [(_conv2, s) for s in (L_RAGGED, L_ODD, L_PASSES, L_BIG)] + [(_conv3, s) for s in (C_ODD, C_RAGGED)] + \
+    [(_c3d_conv2, s) for s in (C_ODD, C_RAGGED)]
+_ids = lambda v: v.__name__.strip("_") if callable(v) else R.shape_id(v)  # noqa: E731
+
+
+@pytest.mark.parametrize("case,shape", TILE_SUMS, ids=_ids)
+def test_last_pixel_left_out_of_its_tile_sum(case, shape):
+    x, w, b, y, t, (ref, tol), conv, n = case(shape)
+    y2 = y.clone().flatten(2)
+    y2[:, :, -1] = 0
+    seen = _seen(_finish(case, y2.view_as(y), t), ref, tol)
+    print(f"{case.__name__} {R.shape_id(shape)}: seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+def _drop_tap8(w):
+    w2 = w.clone().flatten(2)
+    w2[:, 60:64, 8] = 0                                    # tap 8 = (ky, kx) = (2, 2), in 3D (kt, ky, kx) = (0, 2, 2)
+    return w2.view_as(w)
+
+
+@pytest.mark.parametrize("shape", [C_ODD, C_RAGGED], ids=R.shape_id)
+def test_four_input_channels_of_tap_8_dropped_at_one_pixel_of_a_pooled_map(shape):
+    """3D conv2 writes its (pooled) map, so the drop is seen where it happens: the centre of the second frame."""
+    x, w, b, y, t, (ref, tol), conv, n = _c3d_conv2(shape)
+    at = (slice(None), slice(None), 1, y.shape[3] // 2, y.shape[4] // 2)
+    y2 = y.clone()
+    y2[at] = conv(x, _drop_tap8(w), b, padding=1)[at]
+    assert not torch.equal(y2, y)
+    seen = _seen(_finish(_c3d_conv2, y2, t), ref, tol)
+    print(f"c3d_conv2 {R.shape_id(shape)}: seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+# what multiplies the weights of the four dropped taps, see the docstring below
+TAP8_SCALE = {_conv2: 8.0, _conv3: 256.0}
+
+
+@pytest.mark.parametrize("case,shape", [(_conv2, s) for s in (L_RAGGED, L_ODD, L_PASSES, L_BIG)] + [(_conv3, s) for s in (C_ODD, C_RAGGED)],
+                         ids=_ids)
+def test_four_input_channels_of_tap_8_dropped_at_one_pixel_of_a_tile_sum(case, shape):
+    """Behind a tile sum the drop of 4 of n products at ONE of the tile's P pixels competes with the rounding of all P: with
+    every product alike it is (4 / n) against the bound P (n + 2) u, i.e. 50 / P bounds for conv2 (n = 576) and 1.4 / P for 3D
+    conv3 (n = 3456).  So the pixel is the one (of one frame) at which the drop shows most.  With the seeded weights that gives
+    3.9, 9.2, 2.2 and 11.2 x bound at the four conv2 shapes (P of the tile = 140, 72, 256, 49) and 0.1 / 0.4 x bound for conv3:
+    the GPU check of the partials sees so small a drop only in a short tile, and sees the drops of the tests around this one
+    everywhere.  Following the rule to change the inputs where a mutation stays inside 4 x bound, the weights of the four
+    dropped taps are 8 times (conv2) and 256 times (conv3) larger here -- inputs on which torch's fp32 convolution still meets
+    the bound, checked below -- and only this test uses them."""
+    x, w, b, y, t, (ref, tol), conv, n = case(shape)
+    w = w.clone().flatten(2)
+    w[:, 60:64, 8] *= TAP8_SCALE[case]
+    w = w.view(-1, x.shape[1], *(3,) * (x.dim() - 2))
+    y, t = R.conv_bound(conv, x, w, b, n, padding=1)
+    ref, tol = R.partial_from_map(y, t)
+    got = _tiles32(conv(x.float(), w.float(), b.float(), padding=1).relu().flatten(2))
+    assert _seen(got, ref, tol) <= 1.0
+    ym = conv(x, _drop_tap8(w), b, padding=1)
+    d = (ym.relu() - y.relu()).flatten(2).abs()            # [F, C, P]: what the drop at pixel p alone takes from its tile sum
+    P = d.shape[2]
+    r = (d / tol.permute(0, 2, 1)[:, :, torch.arange(P) // R.TILE]).amax(1)
+    f, px = divmod(int(r.argmax()), P)
+    y2 = y.clone()
+    y2.flatten(2)[f, :, px] = ym.flatten(2)[f, :, px]
+    assert int((y2 != y).flatten(2).any(1).sum()) == 1      # one pixel of one frame
+    seen = _seen(_finish(case, y2, t), ref, tol)
+    print(f"{case.__name__} {R.shape_id(shape)}: pixel {px} of {P}, seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+@pytest.mark.parametrize("case,shape", CONVS, ids=_ids)
+def test_zero_padding_replaced_by_edge_clamping_on_the_right(case, shape):
+    x, w, b, y, t, (ref, tol), conv, n = case(shape)
+    xp = F.pad(x, (1, 1) * (x.dim() - 2))
+    xp[..., -1] = xp[..., -2]
+    y2 = y.clone()
+    y2[..., -1] = conv(xp, w, b)[..., -1]
+    seen = _seen(_finish(case, y2, t), ref, tol)
+    print(f"{case.__name__} {R.shape_id(shape)}: seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+@pytest.mark.parametrize("shape", R.C3D_SHAPES, ids=R.shape_id)
+def test_c3d_pool_group_takes_seven_of_eight(shape):
+    x, w, b, y, t, (ref, tol), conv, n = _c3d_conv2(shape)
+    T2, H2, W2 = shape[0] // 2, shape[1] // 4, shape[2] // 4
+    worst = []
+    for e in range(8):                                     # whichever of the eight positions the last group loses
+        y2 = y.clone()
+        y2[:, :, 2 * (T2 - 1) + (e >> 2), 2 * (H2 - 1) + ((e >> 1) & 1), 2 * (W2 - 1) + (e & 1)] = -float("inf")
+        mut = _finish(_c3d_conv2, y2, t)
+        assert torch.equal(mut[:, :-1], ref[:, :-1])
+        worst.append(_seen(mut, ref, tol))
+    print(f"{R.shape_id(shape)}: seen {min(worst):.1f} .. {max(worst):.1f} x bound")
+    assert min(worst) > FACTOR
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stages whose input is small: mean, projection, LSTM, head
+@pytest.mark.parametrize("shape", [L_BIG, C_RAGGED], ids=R.shape_id)
+def test_mean_drops_the_last_tile(shape):
+    _, _, refs, taps = _lstm(shape) if len(shape) == 7 else _c3d(shape)
+    ref, tol = refs["feat"]
+    part = taps["partial"].double()
+    assert part.shape[1] >= 2
+    P = R.pooled_hw(shape[0], shape[1]) if len(shape) == 7 else (shape[0] // 2, shape[1] // 4 * (shape[2] // 4))
+    assert _seen(part[:, :-1].sum(1) / (P[0] * P[1]), ref, tol) > FACTOR
+
+
+@pytest.mark.parametrize("shape", R.LSTM_SHAPES, ids=R.shape_id)
+def test_projection_and_head_drop_the_last_k(shape):
+    p, _, refs, taps = _lstm(shape)
+    H, W, T, hidden, classes, n, _ = shape
+    q = dict(p)
+    q["w_ih1"] = p["w_ih1"].clone()
+    q["w_ih1"][:, -1] = 0
+    assert _seen(R.gx_from_feat(taps["feat"], q, n, T)[0], *refs["gx"]) > FACTOR
+    q["head_w"] = p["head_w"].clone()
+    q["head_w"][:, -1] = 0
+    seen = _seen(R.head(taps["h2"].double()[T - 1], q)[0], *refs["logits"])
+    print(f"{R.shape_id(shape)}: head seen {seen:.1f} x bound")
+    assert seen > FACTOR
+
+
+@pytest.mark.parametrize("shape", R.C3D_SHAPES, ids=R.shape_id)
+def test_c3d_head_drops_the_last_k(shape):
+    p, _, refs, taps = _c3d(shape)
+    w = p["head_w"].clone()
+    w[:, -1] = 0
+    assert _seen(R.linear(taps["feat"], w, p["head_b"], 256)[0], *refs["logits"]) > FACTOR
+
+
+def _lstm_seen(shape, mut=None, q=None):
+    p, _, refs, taps = _lstm(shape)
+    h1, h2 = R.lstm(taps["gx"], q or p, mut=mut)
+    e_ref, bound = refs["_lstm"]
+    d = max(float((h1 - refs["h1"][0]).abs().max()), float((h2 - refs["h2"][0]).abs().max()))
+    print(f"{R.shape_id(shape)} {mut or 'weights'}: e_ref {e_ref:.3e}, bound {bound:.3e}, mutation moves h by {d:.3e} = {d / bound:.0f} x bound")
+    return d / bound
+
+
+@pytest.mark.parametrize("shape", [L_RAGGED, L_ODD, L_PASSES, L_BIG], ids=R.shape_id)       # T >= 2: W_hh1 is live
+def test_lstm_last_k_column_of_w_hh1_zeroed(shape):
+    p = _lstm(shape)[0]
+    q = dict(p)
+    q["w_hh1"] = p["w_hh1"].clone()
+    q["w_hh1"][:, -1] = 0
+    assert _lstm_seen(shape, q=q) > 8.0                     # the bound may never exceed 1/8 of this mutation's effect
+
+
+@pytest.mark.parametrize("shape", [L_PASSES, L_BIG], ids=R.shape_id)                        # more than 8 clips, T >= 2
+def test_lstm_cell_state_read_as_zero_from_clip_8(shape):
+    assert shape[5] > 8 and shape[2] >= 2
+    p, _, refs, taps = _lstm(shape)
+    h1, _ = R.lstm(taps["gx"], p, mut="c0_from_8")
+    assert torch.equal(h1[:, :8], refs["h1"][0][:, :8])    # the first pass is untouched: only a reference for clips >= 8 sees it
+    assert _lstm_seen(shape, mut="c0_from_8") > 8.0
+
+
+@pytest.mark.parametrize("shape", [L_RAGGED, L_ODD, L_PASSES, L_BIG], ids=R.shape_id)
+def test_lstm_layer_2_reads_the_wrong_step_of_h1(shape):
+    assert _lstm_seen(shape, mut="l2_next") > 8.0
+
+
+def test_lstm_bound_rule():
+    assert R.lstm_bound(1e-9) == 1e-6 and R.lstm_bound(1e-7) == 64e-7
