@@ -119,6 +119,17 @@ def plan_rounded_reference(net, x, device=None):
         return torch.cat(outs, 2)
 
 
+def assert_conv_close(got, want, res=None, what=""):
+    """fp16-ulp bound, per element.  Both sides use the same fp16 operands; the reference is fp32 (or wider) throughout, the
+    kernel accumulates in fp32 (K <= 4608 terms: order effects ~1e-6 relative), rounds the activated value to fp16 once and,
+    with a residual, rounds the sum once more: |err| <= ulp(|silu|)/2 + ulp(|out|)/2 with ulp(v) = 2^-10 |v| and
+    |silu| <= |want| + |res|.  A kernel that drops a K-step, a tap or a tail channel is off by ~1e-1 here."""
+    mag = want.abs() + (res.float().abs() if res is not None else 0.0)
+    tol = 2.0 ** -10 * mag + 1e-4
+    bad = (got - want).abs() > tol
+    assert not bool(bad.any()), (what, float((got - want).abs().max()), int(bad.sum()))
+
+
 def assert_matches_rounded_reference(got16, want32, score_tol=2e-3, box_eps=0.03):
     """``got16``: the plan's fp16 head tensor; ``want32``: :func:`plan_rounded_reference`.  Boxes: half an fp16 ulp of the
     value (the store's rounding: 0.125 px below 512, 0.25 px below 1024) + ``box_eps``; scores: ``score_tol`` absolute."""

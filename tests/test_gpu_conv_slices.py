@@ -1,0 +1,321 @@
+"""Every row of the fp16 convolution variant table (``kConvVariants``, csrc/rva_conv.hip) where the fused plan really calls
+it: on channel slices of concat buffers with the plan's row strides, offsets and rounded-up Cin (part 1, against float64), and
+forced on the steps of real plans (part 2, against the rounding-matched reference).  The autotuner picks rows by time alone;
+these tests are what makes "all variants compute the same layer" true for the layouts it picks them on."""
+import ctypes as C
+from typing import NamedTuple, Optional, Tuple
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from realtime_video_analytics_32streams_amd import _native as N
+from realtime_video_analytics_32streams_amd import ops
+from realtime_video_analytics_32streams_amd.engine import FusedYoloV8
+from realtime_video_analytics_32streams_amd.yolov8 import build_detector_net
+from tests.helpers import assert_conv_close, assert_matches_rounded_reference, plan_rounded_reference
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 7.0
+
+
+# ---------------------------------------------------------------------------------------------------
+# Part 1: rva_conv2d_nhwc_f16_v on the plan's slice layouts
+# ---------------------------------------------------------------------------------------------------
+class Layout(NamedTuple):
+    name: str
+    cin: int                                   # real input channels (the reference reads these)
+    cin_decl: int                              # what the step declares: Cin rounded up to 32 (Builder::conv), zero weight columns
+    cout: int
+    k: int
+    stride: int
+    act: int
+    inp: Tuple[int, int]                       # (row stride, channel offset) of the input slice
+    out: Tuple[int, int]                       # ... of the output slice
+    res: Optional[Tuple[int, int]] = None      # ... of the residual slice, which lives in the OUTPUT allocation (Builder::c2f)
+
+
+def _cv1(c, decl, n, i):
+    """Bottleneck cv1: reads cat.sub((1+i)*c, c) of a (2+n)*c row, writes the contiguous tmp."""
+    return Layout(f"cv1 c{c} n{n} i{i}", c, decl, c, 3, 1, 1, ((2 + n) * c, (1 + i) * c), (c, 0))
+
+
+def _cv2(c, decl, n, i, shortcut=True):
+    """Bottleneck cv2: reads the contiguous tmp, writes cat.sub((2+i)*c, c); the shortcut is the neighbouring slice."""
+    ld = (2 + n) * c
+    return Layout(f"cv2 c{c} n{n} i{i}" + ("" if shortcut else " no shortcut"), c, decl, c, 3, 1, 1, (c, 0), (ld, (2 + i) * c),
+                  (ld, (1 + i) * c) if shortcut else None)
+
+
+STRIDE1_LAYOUTS = [
+    # rva_plan.hip:250,261 (Builder::c2f, `conv1(b1, x, tmp, ...)` with x = cat.sub((1+i)*c, c)).
+    _cv1(16, 32, 1, 0),        # YOLOv8n b2: Cin 16 declared 32; the 16 channels read past the slice are the row's last slice
+    _cv1(16, 32, 2, 0),        # ... are a real neighbour in the middle of the row
+    _cv1(48, 64, 1, 0),        # YOLOv8m b2 widths: Cin 48 declared 64, past = last slice
+    _cv1(48, 64, 2, 0),        # ... past = the neighbour slice
+    _cv1(48, 64, 2, 1),        # ... past = the last slice, behind two slices
+    _cv1(64, 64, 2, 1),        # YOLOv8n b6 / s b4: nothing read past the slice
+    _cv1(128, 128, 1, 0),      # YOLOv8n b8 / s b6
+    # rva_plan.hip:262 (Builder::c2f, `conv1(b2, tmp, cat.sub((2+i)*c, c), ..., shortcut ? &x : nullptr)`): contiguous tmp in --
+    # with c = 16 / 48 the declared Cin reaches into the next pixel and, behind the last pixel, into the 64-byte slack --
+    # output slice and residual slice side by side in one allocation, ldr = ldo = (2+n)*c
+    _cv2(16, 32, 1, 0),
+    _cv2(48, 64, 2, 1),
+    _cv2(64, 64, 2, 0),
+    _cv2(128, 128, 1, 0),
+    _cv2(32, 32, 1, 0, shortcut=False),        # neck C2f (h15 of YOLOv8n): no shortcut
+    # rva_plan.hip:264,333 (C2f closing 1x1 `conv1(cv2, cat, dst, ...)` with dst = p3 = cat15.sub(c4, c3)): whole cat row in, back
+    # half of a neck concat buffer out, ldo = c4 + c3 and offset c4 (YOLOv8n b4: c = 32, n = 2)
+    Layout("c2f close -> p3", 128, 128, 64, 1, 1, 1, (128, 0), (128 + 64, 128)),
+    # rva_plan.hip:264,325 (the same of YOLOv8n b2: cat of 3 x 16 channels declared 64, read into the next pixel / the slack)
+    Layout("c2f close c16", 48, 64, 32, 1, 1, 1, (48, 0), (32, 0)),
+    # rva_plan.hip:417 (`conv1(box[l][1], first.sub(0, cb), b2, ...)`): row stride cb + cc = 144 halves = 288 bytes (YOLOv8n)
+    Layout("detect box.1 n", 64, 64, 64, 3, 1, 1, (64 + 80, 0), (64, 0)),
+    # rva_plan.hip:418,423 (`conv1(cls[l][1], first.sub(cb, cc), k2, ...)`).  YOLOv8n: cc = 80 declared 96, so the step reads 16
+    # channels of the NEXT pixel's box half; YOLOv8s: cc = 128, row stride 192
+    Layout("detect cls.1 n", 80, 96, 80, 3, 1, 1, (64 + 80, 64), (80, 0)),
+    Layout("detect cls.1 s", 128, 128, 128, 3, 1, 1, (64 + 128, 64), (128, 0)),
+    # rva_plan.hip:423 (`conv1(cls[l][2], k2, ko, ..., 0)`, the unfused head of YOLOv8n): no activation, Cin 80 declared 96 on a
+    # contiguous 80-channel buffer
+    Layout("detect cls.2 n", 80, 96, 80, 1, 1, 0, (80, 0), (80, 0)),
+    # rva_plan.hip:415 (sibling launch `conv(sib, 2, feats[l], first, ...)`): Cout = cb + cc = 144 across the 64- and 96-channel tiles
+    Layout("detect first n", 64, 64, 64 + 80, 3, 1, 1, (64, 0), (64 + 80, 0)),
+]
+
+STRIDE2_LAYOUTS = [
+    # rva_plan.hip:335 (`conv1(take(c3, c4, 3, 2, "b5"), p3, t4, ...)`, p3 = cat15.sub(c4, c3)): reads a back-half slice
+    Layout("b5 n", 64, 64, 128, 3, 2, 1, (128 + 64, 128), (128, 0)),
+    Layout("b5 m", 192, 192, 384, 3, 2, 1, (384 + 192, 384), (384, 0)),
+    # rva_plan.hip:375 (`conv1(take(c3, c3, 3, 2, "h16"), n3, cat18.sub(0, c3), ...)`): writes a front-half slice
+    Layout("h16 n", 64, 64, 64, 3, 2, 1, (64, 0), (64 + 128, 0)),
+    # rva_plan.hip:332 (`b3` of YOLOv8n, 32 -> 64: the Cin = 32 stride-2 patch kernel) into a front-half slice as h16 writes it
+    Layout("s2 32->64 front half", 32, 32, 64, 3, 2, 1, (32, 0), (64 + 128, 0)),
+]
+
+# B, H, W: tiles that straddle rows and images, and an M tail (9 x 7: 189 pixels); stride 2 with even sizes (the s2run rows)
+STRIDE1_SHAPES = [(3, 12, 20), (3, 6, 10), (3, 9, 7)]
+STRIDE2_SHAPES = [(2, 12, 20)]
+CASES = [(lay, s) for lay in STRIDE1_LAYOUTS for s in STRIDE1_SHAPES] + [(lay, s) for lay in STRIDE2_LAYOUTS for s in STRIDE2_SHAPES]
+
+
+def _plan_buffer(m, ld, fill):
+    """An activation buffer as ``Builder::buf()`` allocates it: exactly ``m * ld`` halves and 64 bytes of zero slack."""
+    t = torch.zeros((m * ld * 2 + 64,), dtype=torch.uint8, device="cuda").view(torch.float16)
+    t[:m * ld] = fill.reshape(-1).to(device="cuda", dtype=torch.float16)
+    return t
+
+
+def _bits(t):
+    return t.view(torch.int16)
+
+
+@pytest.mark.parametrize("layout,shape", CASES, ids=[f"{lay.name} {b}x{h}x{w}".replace(" ", "_") for lay, (b, h, w) in CASES])
+def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
+    """Each row of the variant table on one slice layout of the plan: within the fp16-ulp bound of the float64 convolution of the
+    real channels, nothing written outside the output slice, nothing taken from outside the declared input slice, and the same
+    rows accepted as for the contiguous tensor of that shape."""
+    lay, (B, H, W) = layout, shape
+    k, s = lay.k, lay.stride
+    Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
+    Mi, Mo = B * H * W, B * Ho * Wo
+    (ldi, offi), (ldo, offo) = lay.inp, lay.out
+    assert offi % 8 == 0 and offo % 8 == 0 and offi + lay.cin <= ldi and offo + lay.cout <= ldo
+    g = torch.Generator().manual_seed(11)
+    x_rows = (torch.randn((Mi, ldi), generator=g) * 0.5).half()
+    w = (torch.randn((lay.cout, lay.cin, k, k), generator=g) / (lay.cin * k * k) ** 0.5).half()
+    b = torch.randn((lay.cout,), generator=g) * 0.1
+    out_rows = torch.full((Mo, ldo), SENTINEL, dtype=torch.float16)
+    res = None
+    if lay.res is not None:
+        ldr, offr = lay.res
+        assert ldr == ldo and offr % 8 == 0 and (offr + lay.cout <= offo or offr >= offo + lay.cout)
+        res = (torch.randn((Mo, lay.cout), generator=g) * 0.5).half()
+        out_rows[:, offr:offr + lay.cout] = res
+
+    # float64 reference on the fp16-rounded operands: the real Cin channels and the real Cout rows only
+    xs = x_rows[:, offi:offi + lay.cin].reshape(B, H, W, lay.cin).double().permute(0, 3, 1, 2)
+    y = F.conv2d(xs, w.double(), b.double(), stride=s, padding=k // 2)
+    if lay.act:
+        y = y * torch.sigmoid(y)
+    want = y.permute(0, 2, 3, 1).reshape(Mo, lay.cout)
+    if res is not None:
+        want = want + res.double()
+    want = want.cuda()
+    res_dev = res.cuda() if res is not None else None
+
+    L, ctx = N.lib(), ops.context()
+    cpad, cinp = L.rva_conv_cout_pad(lay.cout), (lay.cin_decl + 31) // 32 * 32
+    wp = torch.zeros((cpad, k * k, cinp), dtype=torch.float16)
+    wp[:lay.cout, :, :lay.cin] = w.permute(0, 2, 3, 1).reshape(lay.cout, k * k, lay.cin)      # columns cin.. stay zero, as Builder::pack
+    bp = torch.zeros(cpad)
+    bp[:lay.cout] = b
+    wp, bp = wp.cuda(), bp.cuda()
+
+    x_buf = _plan_buffer(Mi, ldi, x_rows)
+    # the same slice with everything else of every row replaced: what the zero weight columns (and nothing else) may touch
+    other = x_rows.clone()
+    outside = torch.ones(ldi, dtype=torch.bool)
+    outside[offi:offi + lay.cin] = False
+    sign = torch.where(torch.arange(Mi * ldi).reshape(Mi, ldi) % 2 == 0, 6.0e4, -6.0e4).half()
+    other[:, outside] = sign[:, outside]
+    x_other = _plan_buffer(Mi, ldi, other) if bool(outside.any()) else None
+    out_init = _plan_buffer(Mo, ldo, out_rows)
+    written = torch.zeros((Mo, ldo), dtype=torch.bool)
+    written[:, offo:offo + lay.cout] = True
+    untouched = torch.cat((~written.reshape(-1), torch.ones(32, dtype=torch.bool))).cuda()      # the rest of the rows + the slack
+    # the contiguous call of the same shape (declared Cin, ld = C, offset 0): decides nothing but which rows apply
+    xc = _plan_buffer(Mi, lay.cin_decl, torch.randn((Mi, lay.cin_decl), generator=g) * 0.5)
+    oc = _plan_buffer(Mo, lay.cout, torch.zeros((Mo, lay.cout)))
+    rc_res = _plan_buffer(Mo, lay.cout, res) if res is not None else None
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def launch(variant, xin, ld_in, off_in, out, ld_out, off_out, resid, ld_res):
+        return L.rva_conv2d_nhwc_f16_v(ctx.handle, C.c_void_p(xin.data_ptr() + 2 * off_in), ld_in, C.c_void_p(wp.data_ptr()),
+                                       C.c_void_p(bp.data_ptr()), C.c_void_p(out.data_ptr() + 2 * off_out), ld_out,
+                                       C.c_void_p(resid) if resid else None, ld_res, B, H, W, lay.cin_decl, lay.cout, k, s, lay.act,
+                                       variant, stream)
+
+    on_slice, on_contiguous = [], []
+    for v in range(0, L.rva_conv_num_variants() + 1):
+        name = (v, (L.rva_conv_variant_name(v) or b"?").decode())
+        out = out_init.clone()
+        resid = out.data_ptr() + 2 * lay.res[1] if lay.res is not None else 0
+        rc = launch(v, x_buf, ldi, offi, out, ldo, offo, resid, ldo if resid else 0)
+        if rc != N.RVA_ERR_ARG:
+            assert rc == N.RVA_OK, (name, rc)
+            torch.cuda.synchronize()                 # a HIP error ends the test here: nothing more is launched after it
+            on_slice.append(v)
+            got = out[:Mo * ldo].reshape(Mo, ldo)[:, offo:offo + lay.cout].double()
+            assert_conv_close(got, want, res_dev, name)
+            assert torch.equal(_bits(out)[untouched], _bits(out_init)[untouched]), (name, "wrote outside its output slice")
+            if x_other is not None:
+                out2 = out_init.clone()
+                resid2 = out2.data_ptr() + 2 * lay.res[1] if lay.res is not None else 0
+                rc = launch(v, x_other, ldi, offi, out2, ldo, offo, resid2, ldo if resid2 else 0)
+                assert rc == N.RVA_OK, (name, rc)
+                torch.cuda.synchronize()
+                assert torch.equal(_bits(out2), _bits(out)), (name, "result depends on channels outside the declared slice")
+        rc = launch(v, xc, lay.cin_decl, 0, oc, lay.cout, 0, rc_res.data_ptr() if rc_res is not None else 0, lay.cout if rc_res is not None else 0)
+        if rc != N.RVA_ERR_ARG:
+            assert rc == N.RVA_OK, (name, "contiguous", rc)
+            torch.cuda.synchronize()
+            on_contiguous.append(v)
+    assert 0 in on_slice and len(on_slice) >= 3, on_slice
+    assert on_slice == on_contiguous, ("applicability depends on strides", sorted(set(on_slice) ^ set(on_contiguous)))
+
+
+# ---------------------------------------------------------------------------------------------------
+# Part 2: every row forced on the steps of real plans
+# ---------------------------------------------------------------------------------------------------
+# scale, batch, (H, W), environment at construction.  (96, 160): levels 12 x 20, 6 x 10, 3 x 5 -- even where a step upsamples -- and
+# batch 3 so that tiles straddle images; 640 x 640 at batch 1 puts the W <= 160 and 2^24 gates where production has them.
+# RVA_PAIR32=0 turns the fused 32 -> 32 bottleneck pairs into convolution steps, RVA_NO_STEM2=1 the first downsampling convolution.
+CONFIGS = {
+    "n": ("n", 3, (96, 160), {}),
+    "s": ("s", 3, (96, 160), {}),
+    "m": ("m", 3, (96, 160), {}),
+    "s-640": ("s", 1, (640, 640), {}),
+    "s-no-pair32": ("s", 3, (96, 160), {"RVA_PAIR32": "0"}),
+    "s-no-stem2": ("s", 3, (96, 160), {"RVA_NO_STEM2": "1"}),
+}
+_PLAN_ENV = ("RVA_PAIR32", "RVA_NO_STEM2", "RVA_NO_CIN_PAD", "RVA_TUNE_LAYER_OVERLAP", "RVA_SERIAL_HEADS")
+
+# Rows that no convolution step of any configuration above accepts, with the launcher's gate that keeps them out.
+NEVER_APPLIES = {}
+
+_forced = {}           # configuration -> [(desc, variant)] or the exception that ended it (never run twice)
+
+
+def _force_every_variant(key, monkeypatch):
+    if key in _forced:
+        if isinstance(_forced[key], BaseException):
+            pytest.fail(f"configuration {key} failed earlier in this session: {_forced[key]!r}")
+        return _forced[key]
+    scale, batch, hw, env = CONFIGS[key]
+    try:
+        with monkeypatch.context() as mp:
+            for name in _PLAN_ENV:
+                mp.delenv(name, raising=False)
+            for name, value in env.items():
+                mp.setenv(name, value)
+            net = build_detector_net(scale, seed=3)
+            plan = FusedYoloV8(net, batch, hw=hw, autotune=False)      # the tuning cache is not consulted
+        x = torch.rand((batch, 3, *hw), device="cuda", generator=torch.Generator(device="cuda").manual_seed(17)).half()
+        want = plan_rounded_reference(net, x)
+        _forced[key] = _run_forced(plan, x, want)
+    except BaseException as exc:
+        _forced[key] = exc
+        raise
+    return _forced[key]
+
+
+def _run_forced(plan, x, want):
+    L = N.lib()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def run_and_check(what):
+        got = plan(x)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(got).all()), (what, "non-finite output")
+        try:
+            return assert_matches_rounded_reference(got, want)
+        except AssertionError as exc:
+            raise AssertionError((what, *exc.args)) from None
+
+    assert all(state["variant"] == 0 for _, state, _ in plan._tunable)
+    print("variant 0: box / score error", run_and_check("variant 0"))
+    ran = []
+    try:
+        for v in range(1, L.rva_conv_num_variants() + 1):
+            picks = []
+            for launch, _, desc in plan._tunable:
+                rc = launch(stream, v)                   # the autotuner's probe: RVA_ERR_ARG = "does not apply", from host code
+                assert rc in (N.RVA_OK, N.RVA_ERR_ARG), (desc, v, rc)
+                picks.append(v if rc == N.RVA_OK else 0)
+            torch.cuda.synchronize()
+            if not any(picks):
+                continue
+            for (_, state, _), pv in zip(plan._tunable, picks):
+                state["variant"] = pv
+            try:
+                run_and_check(("variant", v))
+            except AssertionError as exc:
+                # name the steps: one at a time (a HIP error is no AssertionError and ends everything above)
+                guilty = []
+                for i, (_, state, desc) in enumerate(plan._tunable):
+                    if not picks[i]:
+                        continue
+                    for j, (_, other, _) in enumerate(plan._tunable):
+                        other["variant"] = v if j == i else 0
+                    try:
+                        run_and_check(desc)
+                    except AssertionError as one:
+                        guilty.append((desc, one.args))
+                raise AssertionError((exc.args, "steps that miss alone", guilty)) from None
+            ran += [(desc, v) for (_, _, desc), pv in zip(plan._tunable, picks) if pv]
+    finally:
+        for _, state, _ in plan._tunable:
+            state["variant"] = 0
+    return ran
+
+
+@pytest.mark.parametrize("key", list(CONFIGS))
+def test_every_variant_forced_on_the_plan_steps(key, monkeypatch):
+    """Variant v on every step that accepts it (0 on the rest), for every v: the whole plan stays within the project's bound of
+    the rounding-matched reference (``assert_matches_rounded_reference`` at its defaults), as with variant 0."""
+    ran = _force_every_variant(key, monkeypatch)
+    print(f"{key}: {len(ran)} (step, variant) pairs forced, {len({v for _, v in ran})} distinct rows")
+    assert ran
+
+
+def test_forced_variants_cover_the_table(monkeypatch):
+    """Over all configurations every row ran on a real plan step, but for the rows listed in NEVER_APPLIES; each LDS-DMA gather
+    tile (33..39) ran on an upsample + concat step and on a fused head step of each mode."""
+    ran = [pair for key in CONFIGS for pair in _force_every_variant(key, monkeypatch)]
+    rows = set(range(1, N.lib().rva_conv_num_variants() + 1))
+    seen = {v for _, v in ran}
+    assert rows - seen == set(NEVER_APPLIES), sorted(rows - seen)
+    for v in range(33, 40):
+        for prefix in ("up", "head1:", "head2:"):
+            assert any(pv == v and desc.startswith(prefix) for desc, pv in ran), (v, prefix)

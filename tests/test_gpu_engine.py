@@ -12,20 +12,10 @@ from realtime_video_analytics_32streams_amd import _native as N
 from realtime_video_analytics_32streams_amd import ops
 from realtime_video_analytics_32streams_amd.engine import FusedYoloV8
 from realtime_video_analytics_32streams_amd.yolov8 import build_detector_net
+from tests.helpers import assert_conv_close as _assert_conv_close      # the fp16-ulp bound, shared with test_gpu_conv_slices.py
 from tests.helpers import assert_matches_rounded_reference, fp16_error_report, plan_rounded_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def _assert_conv_close(got, want, res=None, what=""):
-    """fp16-ulp bound, per element.  Both sides use the same fp16 operands; the reference is fp32 throughout, the kernel
-    accumulates in fp32 (K <= 4608 terms: order effects ~1e-6 relative), rounds the activated value to fp16 once and,
-    with a residual, rounds the sum once more: |err| <= ulp(|silu|)/2 + ulp(|out|)/2 with ulp(v) = 2^-10 |v| and
-    |silu| <= |want| + |res|.  A kernel that drops a K-step, a tap or a tail channel is off by ~1e-1 here."""
-    mag = want.abs() + (res.float().abs() if res is not None else 0.0)
-    tol = 2.0 ** -10 * mag + 1e-4
-    bad = (got - want).abs() > tol
-    assert not bool(bad.any()), (what, float((got - want).abs().max()), int(bad.sum()))
 
 
 def _conv_ref(x_nhwc, w, b, k, stride, act, res=None):
@@ -94,7 +84,8 @@ def test_conv_primitive_matches_fp32_reference(shape):
                                    # channel tile, a tensor smaller than one tile, the widest layer of the plan
                                    (3, 40, 40, 128, 192, 3, 2), (5, 24, 36, 96, 96, 3, 2), (1, 6, 4, 64, 64, 3, 2), (2, 160, 160, 64, 128, 3, 2)])
 def test_every_conv_variant_agrees(shape):
-    """All kernel variants the autotuner may pick (gather / resident / row-reuse, every tile) give the same layer."""
+    """All kernel variants the autotuner may pick (gather / resident / row-reuse, every tile) give the same layer.
+    Contiguous tensors only: the plan's strided concat slices and padded Cin are in tests/test_gpu_conv_slices.py."""
     B, H, W, Cin, Cout, k, stride = shape
     g = torch.Generator().manual_seed(7)
     x = (torch.randn((B, H, W, Cin), generator=g) * 0.5).half().cuda()
