@@ -96,7 +96,7 @@ def _stale() -> bool:
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "rva_internal.h", ROOT / "include" / "rva.h"]
+    deps = [CSRC / s for s in SOURCES] + [CSRC / "rva_internal.h", CSRC / "rva_mfma_f32.h", ROOT / "include" / "rva.h"]
     return any(d.exists() and d.stat().st_mtime > t for d in deps)
 
 

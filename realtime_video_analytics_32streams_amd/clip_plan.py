@@ -113,51 +113,34 @@ def pack_cnn_lstm(net) -> Dict[str, np.ndarray]:
     return {n: f32(out[n]) for n in N.CnnLstmWeights.NAMES}
 
 
-def _tap(plan, fn, what: str, stages: Dict[str, tuple], name: str, n_clips: int) -> torch.Tensor:
-    """``stage()`` of both plans: the count from a ``dst == NULL`` call, then the one device-to-device copy."""
-    if name not in stages:
-        raise ValueError(f"{what}: unknown stage {name!r} (one of {', '.join(stages)})")
-    code, shape = stages[name]
-    n = C.c_int64()
-    plan.ctx.check(fn(plan.handle, code, int(n_clips), None, 0, C.byref(n), None), what)
-    if n.value != int(np.prod(shape)):
-        raise RuntimeError(f"{what}: stage {name} has {n.value} floats, the layout {shape} says {int(np.prod(shape))}")
-    out = torch.empty(shape, dtype=torch.float32, device=plan.dev)
-    plan.ctx.check(fn(plan.handle, code, int(n_clips), C.c_void_p(out.data_ptr()), out.numel(), None, ops._stream_ptr()), what)
-    return out
+class _ClipPlan:
+    """What every clip plan shares, over the ABI entries ``<ABI>_create / _destroy / _run / _run_post / _stage``: the subclass
+    sets ``ABI`` and its constructor calls :meth:`_open`, then :meth:`_create` with its descriptor and packed weights."""
 
+    ABI = ""
 
-class FusedCnnLstm:
-    """One ``rva_cnnlstm_plan``: the fp32 clip network of ``net`` for clips of ``frames`` frames at ``hw``, up to ``max_clips``
-    clips per call.  No host synchronisation and no allocation after construction (capturable)."""
+    def _fn(self, name: str):
+        return getattr(self.L, f"{self.ABI}_{name}")
 
-    def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
-                 device: Optional[torch.device] = None):
+    def _open(self, hw, frames: int, max_clips: int, classes: int, ctx: Optional[N.Context], device: Optional[torch.device]) -> None:
         self.ctx = ctx or ops.context()
         self.dev = device or torch.device("cuda", self.ctx.device)
-        self.H, self.W, self.T, self.max_clips = int(hw[0]), int(hw[1]), int(frames), int(max_clips)
-        self.hidden, self.classes = int(net.rnn.hidden_size), int(net.head.out_features)
+        self.H, self.W, self.T, self.max_clips, self.classes = int(hw[0]), int(hw[1]), int(frames), int(max_clips), int(classes)
         self.L = N.lib()
-        packed = pack_cnn_lstm(net)
-        wt = N.CnnLstmWeights(*[packed[n].ctypes.data_as(C.POINTER(C.c_float)) for n in N.CnnLstmWeights.NAMES])
-        d = N.CnnLstmDesc(self.H, self.W, self.T, self.hidden, self.classes, self.max_clips)
+        self._iota: Optional[torch.Tensor] = None
+
+    def _create(self, desc, weights_type, packed: Dict[str, np.ndarray]) -> None:
+        wt = weights_type(*[packed[n].ctypes.data_as(C.POINTER(C.c_float)) for n in weights_type.NAMES])
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
-            self.ctx.check(self.L.rva_cnnlstm_plan_create(self.ctx.handle, C.byref(d), C.byref(wt), C.byref(h)),
-                           "rva_cnnlstm_plan_create")
+            self.ctx.check(self._fn("create")(self.ctx.handle, C.byref(desc), C.byref(wt), C.byref(h)), f"{self.ABI}_create")
         self.handle = h
-        del packed
-        info = [C.c_int32() for _ in range(4)]
-        self.ctx.check(self.L.rva_cnnlstm_plan_info(h, *[C.byref(v) for v in info]), "rva_cnnlstm_plan_info")
-        self.pooled_hw = (info[0].value, info[1].value)
-        self.conv2_tiles, self.n_launches = info[2].value, info[3].value
         self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
-        self._iota: Optional[torch.Tensor] = None
 
     def __del__(self):  # best effort
         try:
             if getattr(self, "handle", None):
-                self.L.rva_cnnlstm_plan_destroy(self.handle)
+                self._fn("destroy")(self.handle)
                 self.handle = None
         except Exception:  # noqa: BLE001
             pass
@@ -176,10 +159,55 @@ class FusedCnnLstm:
         if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or \
                 out.shape[1] != self.classes or out.shape[0] < n_clips:
             raise ValueError(f"out must be a contiguous fp32 device tensor of [>= {n_clips}, {self.classes}]")
-        self.ctx.check(self.L.rva_cnnlstm_plan_run(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()),
-                                                   int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()),
-                       "rva_cnnlstm_plan_run")
+        self.ctx.check(self._fn("run")(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()), int(n_clips),
+                                       C.c_void_p(out.data_ptr()), ops._stream_ptr()), f"{self.ABI}_run")
         return out[:n_clips]
+
+    def _run_frames(self, frames: torch.Tensor, n_clips: int) -> torch.Tensor:
+        """``__call__``: contiguous frames ``[n_clips, T, 3, H, W]`` through the identity index table, a fresh tensor."""
+        if self._iota is None:
+            self._iota = torch.arange(self.max_clips * self.T, dtype=torch.int32, device=self.dev)
+        return self.run(frames, self._iota, n_clips).clone()
+
+    def _tap(self, stages: Dict[str, tuple], name: str, n_clips: int) -> torch.Tensor:
+        """``stage()``: the count from a ``dst == NULL`` call, then the one device-to-device copy."""
+        fn, what = self._fn("stage"), f"{self.ABI}_stage"
+        if name not in stages:
+            raise ValueError(f"{what}: unknown stage {name!r} (one of {', '.join(stages)})")
+        code, shape = stages[name]
+        n = C.c_int64()
+        self.ctx.check(fn(self.handle, code, int(n_clips), None, 0, C.byref(n), None), what)
+        if n.value != int(np.prod(shape)):
+            raise RuntimeError(f"{what}: stage {name} has {n.value} floats, the layout {shape} says {int(np.prod(shape))}")
+        out = torch.empty(shape, dtype=torch.float32, device=self.dev)
+        self.ctx.check(fn(self.handle, code, int(n_clips), C.c_void_p(out.data_ptr()), out.numel(), None, ops._stream_ptr()), what)
+        return out
+
+    def post(self, logits: torch.Tensor, rows: torch.Tensor, n_rows: int, post: ops.PostBuffers) -> ops.PostBuffers:
+        """Top-k result rows into ``post``: ``rows`` = device int32 ``[n_rows, 3]`` of (clip or -1, width, height)."""
+        self.ctx.check(self._fn("run_post")(self.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(rows.data_ptr()), int(n_rows),
+                                            int(post.max_det), C.c_void_p(post.scores.data_ptr()), C.c_void_p(post.cls.data_ptr()),
+                                            C.c_void_p(post.boxes.data_ptr()), C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
+                       f"{self.ABI}_run_post")
+        return post
+
+
+class FusedCnnLstm(_ClipPlan):
+    """One ``rva_cnnlstm_plan``: the fp32 clip network of ``net`` for clips of ``frames`` frames at ``hw``, up to ``max_clips``
+    clips per call.  No host synchronisation and no allocation after construction (capturable)."""
+
+    ABI = "rva_cnnlstm_plan"
+
+    def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
+                 device: Optional[torch.device] = None):
+        self._open(hw, frames, max_clips, net.head.out_features, ctx, device)
+        self.hidden = int(net.rnn.hidden_size)
+        self._create(N.CnnLstmDesc(self.H, self.W, self.T, self.hidden, self.classes, self.max_clips), N.CnnLstmWeights,
+                     pack_cnn_lstm(net))
+        info = [C.c_int32() for _ in range(4)]
+        self.ctx.check(self.L.rva_cnnlstm_plan_info(self.handle, *[C.byref(v) for v in info]), "rva_cnnlstm_plan_info")
+        self.pooled_hw = (info[0].value, info[1].value)
+        self.conv2_tiles, self.n_launches = info[2].value, info[3].value
 
     def stage(self, name: str, n_clips: int) -> torch.Tensor:
         """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n_clips`` clips, on the current stream), in
@@ -189,25 +217,14 @@ class FusedCnnLstm:
         n, T, h = int(n_clips), self.T, self.hidden
         stages = {"pooled": (0, (n * T, *self.pooled_hw, 64)), "partial": (1, (n * T, self.conv2_tiles, 128)),
                   "feat": (2, (n * T, 128)), "gx": (3, (n, T, 4 * h)), "h1": (4, (T, n, h)), "h2": (5, (T, n, h))}
-        return _tap(self, self.L.rva_cnnlstm_plan_stage, "rva_cnnlstm_plan_stage", stages, name, n)
+        return self._tap(stages, name, n)
 
     def __call__(self, clips: torch.Tensor) -> torch.Tensor:
         """``CnnLstmNet.forward`` of contiguous clips ``[B, T, 3, H, W]`` fp32: a fresh ``[B, classes]`` tensor."""
         b = int(clips.shape[0])
         if tuple(clips.shape[1:]) != (self.T, 3, self.H, self.W):
             raise ValueError(f"clips must be [B, {self.T}, 3, {self.H}, {self.W}], got {tuple(clips.shape)}")
-        if self._iota is None:
-            self._iota = torch.arange(self.max_clips * self.T, dtype=torch.int32, device=self.dev)
-        return self.run(clips.contiguous(), self._iota, b).clone()
-
-    def post(self, logits: torch.Tensor, rows: torch.Tensor, n_rows: int, post: ops.PostBuffers) -> ops.PostBuffers:
-        """Top-k result rows into ``post``: ``rows`` = device int32 ``[n_rows, 3]`` of (clip or -1, width, height)."""
-        self.ctx.check(self.L.rva_cnnlstm_plan_run_post(self.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                        int(n_rows), int(post.max_det), C.c_void_p(post.scores.data_ptr()),
-                                                        C.c_void_p(post.cls.data_ptr()), C.c_void_p(post.boxes.data_ptr()),
-                                                        C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
-                       "rva_cnnlstm_plan_run_post")
-        return post
+        return self._run_frames(clips.contiguous(), b)
 
 
 def clip3d_flops(h: int, w: int, frames: int, classes: int = 400) -> Dict[str, float]:
@@ -260,57 +277,21 @@ def pack_cnn3d(net) -> Dict[str, np.ndarray]:
     return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in N.Cnn3dWeights.NAMES}
 
 
-class Fused3dCnn:
+class Fused3dCnn(_ClipPlan):
     """One ``rva_cnn3d_plan``: the fp32 clip network of ``net`` (a :class:`temporal.Cnn3dNet`) for clips of ``frames`` frames at
     ``hw``, up to ``max_clips`` clips per call.  Same surface as :class:`FusedCnnLstm` (``max_clips``, ``T``, ``classes``,
     ``logits``, ``run``, ``post``, ``__call__``).  No host synchronisation and no allocation after construction (capturable)."""
 
+    ABI = "rva_cnn3d_plan"
+
     def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
                  device: Optional[torch.device] = None):
-        packed = pack_cnn3d(net)
-        self.ctx = ctx or ops.context()
-        self.dev = device or torch.device("cuda", self.ctx.device)
-        self.H, self.W, self.T, self.max_clips = int(hw[0]), int(hw[1]), int(frames), int(max_clips)
-        self.classes = int(net.fc.out_features)
-        self.L = N.lib()
-        wt = N.Cnn3dWeights(*[packed[n].ctypes.data_as(C.POINTER(C.c_float)) for n in N.Cnn3dWeights.NAMES])
-        d = N.Cnn3dDesc(self.H, self.W, self.T, self.classes, self.max_clips)
-        h = C.c_void_p()
-        with torch.cuda.device(self.dev):
-            self.ctx.check(self.L.rva_cnn3d_plan_create(self.ctx.handle, C.byref(d), C.byref(wt), C.byref(h)), "rva_cnn3d_plan_create")
-        self.handle = h
-        del packed
+        packed = pack_cnn3d(net)                                    # a wrong architecture is refused before the device is touched
+        self._open(hw, frames, max_clips, net.fc.out_features, ctx, device)
+        self._create(N.Cnn3dDesc(self.H, self.W, self.T, self.classes, self.max_clips), N.Cnn3dWeights, packed)
         p1, p2, tiles, nl = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_int32()
-        self.ctx.check(self.L.rva_cnn3d_plan_info(h, p1, p2, tiles, C.byref(nl)), "rva_cnn3d_plan_info")
+        self.ctx.check(self.L.rva_cnn3d_plan_info(self.handle, p1, p2, tiles, C.byref(nl)), "rva_cnn3d_plan_info")
         self.pool1, self.pool2, self.tiles, self.n_launches = tuple(p1), tuple(p2), tuple(tiles), nl.value
-        self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
-        self._iota: Optional[torch.Tensor] = None
-
-    def __del__(self):  # best effort
-        try:
-            if getattr(self, "handle", None):
-                self.L.rva_cnn3d_plan_destroy(self.handle)
-                self.handle = None
-        except Exception:  # noqa: BLE001
-            pass
-
-    def run(self, ring: torch.Tensor, frame_index: torch.Tensor, n_clips: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Logits ``[n_clips, classes]`` of the clips whose frame t of clip b is ``ring.view(-1, 3, H, W)[frame_index[b * T + t]]``,
-        launched on the current stream: a view of ``out`` (contiguous fp32 ``[>= n_clips, classes]`` on the device) or of the
-        plan's own buffer."""
-        if ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous() or ring.numel() % (3 * self.H * self.W):
-            raise ValueError(f"ring must be a contiguous fp32 device tensor of [*, 3, {self.H}, {self.W}] frames")
-        if frame_index.dtype != torch.int32 or not frame_index.is_cuda or frame_index.numel() < n_clips * self.T:
-            raise ValueError("frame_index must be a device int32 tensor of n_clips * T frame indices")
-        if not 1 <= n_clips <= self.max_clips:
-            raise ValueError(f"n_clips must be in 1..{self.max_clips}, got {n_clips}")
-        out = self.logits if out is None else out
-        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or out.dim() != 2 or \
-                out.shape[1] != self.classes or out.shape[0] < n_clips:
-            raise ValueError(f"out must be a contiguous fp32 device tensor of [>= {n_clips}, {self.classes}]")
-        self.ctx.check(self.L.rva_cnn3d_plan_run(self.handle, C.c_void_p(ring.data_ptr()), C.c_void_p(frame_index.data_ptr()),
-                                                 int(n_clips), C.c_void_p(out.data_ptr()), ops._stream_ptr()), "rva_cnn3d_plan_run")
-        return out[:n_clips]
 
     def stage(self, name: str, n_clips: int) -> torch.Tensor:
         """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n_clips`` clips, on the current stream), in
@@ -320,7 +301,7 @@ class Fused3dCnn:
         n = int(n_clips)
         stages = {"act1": (0, (n, *self.pool1, 64)), "act2": (1, (n, int(np.prod(self.pool2)), 128)),
                   "partial": (2, (n, self.tiles[2], 256)), "feat": (3, (n, 256))}
-        return _tap(self, self.L.rva_cnn3d_plan_stage, "rva_cnn3d_plan_stage", stages, name, n)
+        return self._tap(stages, name, n)
 
     def __call__(self, clips: torch.Tensor) -> torch.Tensor:
         """``Cnn3dNet.forward`` of clips ``[B, 3, T, H, W]`` fp32: a fresh ``[B, classes]`` tensor.  The permute to frames
@@ -328,18 +309,7 @@ class Fused3dCnn:
         b = int(clips.shape[0])
         if tuple(clips.shape[1:]) != (3, self.T, self.H, self.W):
             raise ValueError(f"clips must be [B, 3, {self.T}, {self.H}, {self.W}], got {tuple(clips.shape)}")
-        if self._iota is None:
-            self._iota = torch.arange(self.max_clips * self.T, dtype=torch.int32, device=self.dev)
-        return self.run(clips.permute(0, 2, 1, 3, 4).contiguous(), self._iota, b).clone()
-
-    def post(self, logits: torch.Tensor, rows: torch.Tensor, n_rows: int, post: ops.PostBuffers) -> ops.PostBuffers:
-        """Top-k result rows into ``post``: ``rows`` = device int32 ``[n_rows, 3]`` of (clip or -1, width, height)."""
-        self.ctx.check(self.L.rva_cnn3d_plan_run_post(self.handle, C.c_void_p(logits.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                      int(n_rows), int(post.max_det), C.c_void_p(post.scores.data_ptr()),
-                                                      C.c_void_p(post.cls.data_ptr()), C.c_void_p(post.boxes.data_ptr()),
-                                                      C.c_void_p(post.counts.data_ptr()), ops._stream_ptr()),
-                       "rva_cnn3d_plan_run_post")
-        return post
+        return self._run_frames(clips.permute(0, 2, 1, 3, 4).contiguous(), b)
 
 
 def fired_tables(fired: Sequence, cols: Sequence[int], ring_columns: int, rows: int) -> Tuple[np.ndarray, np.ndarray]:

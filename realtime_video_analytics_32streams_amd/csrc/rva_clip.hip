@@ -11,8 +11,8 @@
 //   K_stem   conv1 + bias + ReLU + 3x3/s2 max pool, 8x8 pooled tile per block (17x17 conv tile incl. the pool halo in LDS);
 //            reads the planar frames straight from the caller's ring through a device table of frame indices.  VALU fmaf,
 //            taps in the checkpoint's (ci, ky, kx) order.  NHWC out.
-//   K_conv2  3x3 conv on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32), bias + ReLU, then the tile's per-channel sum
-//            (pixels in tile order): the 128-channel map itself is never written.
+//   K_conv2  3x3 conv on the exact fp32-input MFMA core of rva_mfma_f32.h (which defines the reduction order), bias + ReLU, then
+//            the tile's per-channel sum (pixels in tile order): the 128-channel map itself is never written.
 //   K_mean   partial sums of a frame reduced in tile order and divided by H*W: the spatial mean, once per frame.
 //   K_xproj  layer 1's input projection X.W_ih1^T + (b_ih1 + b_hh1) for all T steps.
 //   K_lstm   T+1 "diagonal" launches: launch s runs layer 1 at step s and layer 2 at step s-1 (both read h1[s-1]).  A block owns
@@ -21,12 +21,11 @@
 //   K_post   (rva_cnnlstm_plan_run_post) top-k per result row by rank counting, boxes (0, 0, w, h), counts; rows without a clip
 //            get count 0.
 #include "rva_internal.h"
+#include "rva_mfma_f32.h"
 
 #include <algorithm>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int C1 = 64, C2 = 128, K1 = 7;                  // stem widths of the architecture
 constexpr int PT = 8;                                      // pooled tile (PT x PT) of K_stem
@@ -107,108 +106,41 @@ __global__ void __launch_bounds__(STEM_THREADS) k_clip_stem(const float *ring, c
 
 // ---------------------------------------------------------------------------------------------------
 // K_conv2.  NHWC implicit GEMM, one frame per grid row: block = 256 pixels of the frame (four waves of 64) x all 128 channels.
-// Reduction order of an output element: taps in order, in a tap the 64 channels in two chunks of 32 of which MFMA step (q, e)
-// takes channel c + 4q + e (lane half 0) and c + 16 + 4q + e (lane half 1) -- the order of rva_conv_f32.hip's kernel.  Epilogue:
-// v = max(acc + bias, 0); per channel the sum over the wave's pixels (mt, then i, in order), lane halves 0 + 1, then waves 0..3.
+// Reduction order and epilogue (bias + ReLU, then the tile's per-channel sum) are rva_mfma_f32.h's: 9 taps x two chunks of 32
+// channels -- what rva_conv2d_nhwc_f32_v runs on the same input -- then f32_tile_sum.
 __global__ void __launch_bounds__(256) k_clip_conv2(const float *pooled, const float *w2, const float *b2, float *partial, int Hp,
                                                     int Wp, int tiles)
 {
-    constexpr int MT = 2, NT = 4, CK = 32, NQ = CK / 8;
-    __shared__ float red[4][2][C2];
+    constexpr int MT = 2, NT = 4;
     const int f = blockIdx.y, tile = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
+    const int r = threadIdx.x & 31, wave = threadIdx.x >> 6;
     const int P = Hp * Wp;
     const int m0 = tile * 256 + wave * 64;
-    const float *in = pooled + (size_t)f * P * C1;
-    int py[MT], px[MT];
+    int pt[MT], py[MT], px[MT];
     bool pv[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int p = m0 + mt * 32 + r;
         pv[mt] = p < P;
+        pt[mt] = 0;
         py[mt] = pv[mt] ? p / Wp : 0;
         px[mt] = pv[mt] ? p % Wp : 0;
     }
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-    for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap % 3;
-        const float *arow[MT];
-        bool av[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int iy = py[mt] + ky - 1, ix = px[mt] + kx - 1;
-            av[mt] = pv[mt] && (unsigned)iy < (unsigned)Hp && (unsigned)ix < (unsigned)Wp;
-            arow[mt] = in + ((size_t)(av[mt] ? iy : 0) * Wp + (av[mt] ? ix : 0)) * C1 + (CK / 2) * h;
-        }
-#pragma unroll
-        for (int c = 0; c < C1; c += CK) {
-            float4 fa[MT][NQ], fb[NT][NQ];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fa[mt][q] = av[mt] ? *reinterpret_cast<const float4 *>(arow[mt] + c + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fb[nt][q] = *reinterpret_cast<const float4 *>(w2 + ((size_t)(nt * 32 + r) * 9 + tap) * C1 + c + (CK / 2) * h + 4 * q);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const float a_ = e == 0 ? fa[mt][q].x : e == 1 ? fa[mt][q].y : e == 2 ? fa[mt][q].z : fa[mt][q].w;
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const float b_ = e == 0 ? fb[nt][q].x : e == 1 ? fb[nt][q].y : e == 2 ? fb[nt][q].z : fb[nt][q].w;
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b_, acc[mt][nt], 0, 0, 0);
-                        }
-                    }
-        }
-    }
-    // C/D map of the 32x32 shapes: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = nt * 32 + r;
-        const float bias = b2[co];
-        float s = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int p = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (p < P) s = s + fmaxf(acc[mt][nt][i] + bias, 0.f);
-            }
-        red[wave][h][co] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < C2) {
-        const int co = threadIdx.x;
-        float s = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) s = s + (red[wv][0][co] + red[wv][1][co]);
-        partial[((size_t)f * tiles + tile) * C2 + co] = s;
-    }
+    f32x16 acc[MT][NT] = {};
+    f32_conv_taps<C1, 1>(acc, pooled + (size_t)f * P * C1, w2, pt, py, px, pv, 1, Hp, Wp);
+    f32_tile_sum(acc, b2, m0, P, partial + ((size_t)f * tiles + tile) * C2);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K_mean.  Block = frame, thread = channel: feat[f][c] = (sum of the frame's tile partials in tile order) / (Hp * Wp).
-__global__ void __launch_bounds__(C2) k_clip_mean(const float *partial, int tiles, float hw, float *feat)
+// K_mean.  Block = row (a frame here, a clip in rva_clip3d.hip), thread = channel, blockDim.x channels: feat[row][c] = (sum of
+// the row's tile partials in tile order) / n.
+__global__ void __launch_bounds__(256) k_clip_mean(const float *partial, int tiles, float n, float *feat)
 {
-    const int f = blockIdx.x, c = threadIdx.x;
-    const float *pp = partial + (size_t)f * tiles * C2 + c;
+    const int row = blockIdx.x, c = threadIdx.x, C = blockDim.x;
+    const float *pp = partial + (size_t)row * tiles * C + c;
     float s = 0.f;
-    for (int k = 0; k < tiles; ++k) s = s + pp[(size_t)k * C2];
-    feat[(size_t)f * C2 + c] = s / hw;
+    for (int k = 0; k < tiles; ++k) s = s + pp[(size_t)k * C];
+    feat[(size_t)row * C + c] = s / n;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -382,7 +314,15 @@ size_t lstm_lds(int hidden) { return (size_t)(LSTM_G * 2 * hidden + LSTM_R * LST
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-// K_head and K_post serve every clip plan (rva_clip3d.hip launches them through these; declared in rva_internal.h).
+// K_mean, K_head and K_post serve every clip plan (rva_clip3d.hip launches them through these; declared in rva_internal.h).
+int rva_clip_mean_launch(rva_ctx *ctx, const float *partial, int tiles, float n, float *feat, int rows, int channels, hipStream_t st)
+{
+    if (channels < 1 || channels > 256) return rva_fail(ctx, RVA_ERR_ARG, "rva_clip_mean_launch: %d channels, one block holds 1..256", channels);
+    k_clip_mean<<<rows, channels, 0, st>>>(partial, tiles, n, feat);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
 int rva_clip_head_prepare(rva_ctx *ctx, int hidden)
 {
     if (rva_func_smem((const void *)k_clip_head, (size_t)hidden * sizeof(float)) != hipSuccess)
@@ -416,6 +356,24 @@ int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int
     return RVA_OK;
 }
 
+int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n_clips, const float *src, int64_t count, int64_t rows,
+                        int64_t row_floats, int64_t pitch_floats, void *dst, int64_t dst_floats, int64_t *n_floats, hipStream_t st)
+{
+    if (n_floats) *n_floats = count;
+    if (!dst) return RVA_OK;
+    if (dst_floats < count)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: dst holds %lld floats, stage %d of %d clips has %lld", who, (long long)dst_floats, stage,
+                        n_clips, (long long)count);
+    if (rows) {
+        const size_t width = (size_t)row_floats * sizeof(float);
+        RVA_HIP(ctx, hipMemcpy2DAsync(dst, width, src, (size_t)pitch_floats * sizeof(float), width, (size_t)rows,
+                                      hipMemcpyDeviceToDevice, st));
+    } else {
+        RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    return RVA_OK;
+}
+
 struct rva_cnnlstm_plan {
     rva_ctx *ctx = nullptr;
     rva_cnnlstm_desc d{};
@@ -423,29 +381,8 @@ struct rva_cnnlstm_plan {
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;                 // stem
     float *wih1 = nullptr, *bl1 = nullptr, *whh1 = nullptr, *wl2 = nullptr, *bl2 = nullptr, *wh = nullptr, *bh = nullptr;
     float *pooled = nullptr, *partial = nullptr, *feat = nullptr, *gx = nullptr, *h1 = nullptr, *h2 = nullptr, *c1 = nullptr, *c2 = nullptr;
-    std::vector<void *> allocs;
+    rva_dev_arena mem;
 };
-
-namespace {
-
-int plan_alloc(rva_cnnlstm_plan *p, float **dst, size_t n)
-{
-    void *m = nullptr;
-    RVA_HIP(p->ctx, hipMalloc(&m, std::max<size_t>(n, 1) * sizeof(float)));
-    p->allocs.push_back(m);
-    *dst = (float *)m;
-    return RVA_OK;
-}
-
-int plan_upload(rva_cnnlstm_plan *p, float **dst, const std::vector<float> &src)
-{
-    int rc = plan_alloc(p, dst, src.size());
-    if (rc != RVA_OK) return rc;
-    RVA_HIP(p->ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
-    return RVA_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -471,7 +408,6 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
     p->conv2_tiles = rva_ceil_div(p->Hp * p->Wp, 256);
     const int h = d.hidden, G4 = 4 * h, T = d.frames;
     const size_t nf = (size_t)d.max_clips * T;
-    auto vec = [](const float *a, size_t n) { return std::vector<float>(a, a + n); };
     // conv2: [co][ci][ky][kx] -> [co][tap][ci]; layer 2: [W_ih2 | W_hh2] -> [4h][2h]
     std::vector<float> w2((size_t)C2 * 9 * C1), wl2((size_t)G4 * 2 * h);
     for (int co = 0; co < C2; ++co)
@@ -484,29 +420,30 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
         }
     int rc = RVA_OK;
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    step(plan_upload(p, &p->w1, vec(wt->conv1_w, (size_t)C1 * 3 * K1 * K1)));
-    step(plan_upload(p, &p->b1, vec(wt->conv1_b, C1)));
-    step(plan_upload(p, &p->w2, w2));
-    step(plan_upload(p, &p->b2, vec(wt->conv2_b, C2)));
-    step(plan_upload(p, &p->wih1, vec(wt->w_ih1, (size_t)G4 * C2)));
-    step(plan_upload(p, &p->bl1, vec(wt->b1, G4)));
-    step(plan_upload(p, &p->whh1, vec(wt->w_hh1, (size_t)G4 * h)));
-    step(plan_upload(p, &p->wl2, wl2));
-    step(plan_upload(p, &p->bl2, vec(wt->b2, G4)));
-    step(plan_upload(p, &p->wh, vec(wt->head_w, (size_t)d.classes * h)));
-    step(plan_upload(p, &p->bh, vec(wt->head_b, d.classes)));
-    step(plan_alloc(p, &p->pooled, nf * p->Hp * p->Wp * C1));
-    step(plan_alloc(p, &p->partial, nf * p->conv2_tiles * C2));
-    step(plan_alloc(p, &p->feat, nf * C2));
-    step(plan_alloc(p, &p->gx, nf * G4));
-    step(plan_alloc(p, &p->h1, (size_t)T * d.max_clips * h));
-    step(plan_alloc(p, &p->h2, (size_t)T * d.max_clips * h));
-    step(plan_alloc(p, &p->c1, (size_t)d.max_clips * h));
-    step(plan_alloc(p, &p->c2, (size_t)d.max_clips * h));
+    step(p->mem.upload(ctx, &p->w1, wt->conv1_w, (size_t)C1 * 3 * K1 * K1));
+    step(p->mem.upload(ctx, &p->b1, wt->conv1_b, C1));
+    step(p->mem.upload(ctx, &p->w2, w2.data(), w2.size()));
+    step(p->mem.upload(ctx, &p->b2, wt->conv2_b, C2));
+    step(p->mem.upload(ctx, &p->wih1, wt->w_ih1, (size_t)G4 * C2));
+    step(p->mem.upload(ctx, &p->bl1, wt->b1, G4));
+    step(p->mem.upload(ctx, &p->whh1, wt->w_hh1, (size_t)G4 * h));
+    step(p->mem.upload(ctx, &p->wl2, wl2.data(), wl2.size()));
+    step(p->mem.upload(ctx, &p->bl2, wt->b2, G4));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * h));
+    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
+    step(p->mem.alloc(ctx, &p->pooled, nf * p->Hp * p->Wp * C1));
+    step(p->mem.alloc(ctx, &p->partial, nf * p->conv2_tiles * C2));
+    step(p->mem.alloc(ctx, &p->feat, nf * C2));
+    step(p->mem.alloc(ctx, &p->gx, nf * G4));
+    step(p->mem.alloc(ctx, &p->h1, (size_t)T * d.max_clips * h));
+    step(p->mem.alloc(ctx, &p->h2, (size_t)T * d.max_clips * h));
+    step(p->mem.alloc(ctx, &p->c1, (size_t)d.max_clips * h));
+    step(p->mem.alloc(ctx, &p->c2, (size_t)d.max_clips * h));
     if (rc == RVA_OK && rva_func_smem((const void *)k_clip_stem, STEM_LDS) != hipSuccess)
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the stem kernel's LDS limit");
     if (rc == RVA_OK && rva_func_smem((const void *)k_clip_lstm, lstm_lds(h)) != hipSuccess)
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the LSTM kernel's LDS limit");
+    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, h);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
         rva_cnnlstm_plan_destroy(p);
@@ -519,7 +456,7 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
 void rva_cnnlstm_plan_destroy(rva_cnnlstm_plan *p)
 {
     if (!p) return;
-    for (void *m : p->allocs) (void)hipFree(m);
+    p->mem.release();
     delete p;
 }
 
@@ -548,8 +485,8 @@ int rva_cnnlstm_plan_run(rva_cnnlstm_plan *p, const void *frames, const int32_t 
     RVA_HIP(ctx, hipGetLastError());
     k_clip_conv2<<<dim3(p->conv2_tiles, nf), 256, 0, st>>>(p->pooled, p->w2, p->b2, p->partial, p->Hp, p->Wp, p->conv2_tiles);
     RVA_HIP(ctx, hipGetLastError());
-    k_clip_mean<<<nf, C2, 0, st>>>(p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat);
-    RVA_HIP(ctx, hipGetLastError());
+    int rc = rva_clip_mean_launch(ctx, p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat, nf, C2, st);
+    if (rc != RVA_OK) return rc;
     k_clip_xproj<<<dim3(rva_ceil_div(G4, 256), n_clips), 256, (size_t)T * C2 * sizeof(float), st>>>(
         p->feat, p->wih1, p->bl1, p->gx, T, G4);
     RVA_HIP(ctx, hipGetLastError());
@@ -591,21 +528,9 @@ int rva_cnnlstm_plan_stage(rva_cnnlstm_plan *p, int stage, int n_clips, void *ds
     case RVA_CNNLSTM_STAGE_H2: src = p->h2; count = nf * h; break;
     default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: unknown stage %d", stage);
     }
-    if (n_floats) *n_floats = count;
-    if (!dst) return RVA_OK;
-    if (dst_floats < count)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: dst holds %lld floats, stage %d of %d clips has %lld",
-                        (long long)dst_floats, stage, n_clips, (long long)count);
-    const hipStream_t st = (hipStream_t)stream_;
     const bool rows = (stage == RVA_CNNLSTM_STAGE_H1 || stage == RVA_CNNLSTM_STAGE_H2) && n_clips < p->d.max_clips;
-    if (rows) {
-        const size_t width = (size_t)n_clips * h * sizeof(float);
-        RVA_HIP(ctx, hipMemcpy2DAsync(dst, width, src, (size_t)p->d.max_clips * h * sizeof(float), width, (size_t)T,
-                                      hipMemcpyDeviceToDevice, st));
-    } else {
-        RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    return RVA_OK;
+    return rva_clip_stage_copy(ctx, "rva_cnnlstm_plan_stage", stage, n_clips, src, count, rows ? T : 0, n_clips * h, p->d.max_clips * h, dst,
+                               dst_floats, n_floats, (hipStream_t)stream_);
 }
 
 }  // extern "C"

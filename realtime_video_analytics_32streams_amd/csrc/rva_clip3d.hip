@@ -15,21 +15,18 @@
 //            from the caller's ring through the device table of frame indices (frame t of clip b and its temporal neighbours
 //            are entries b*T + t - 1 .. b*T + t + 1; zero outside the clip).  VALU fmaf, taps in the checkpoint's (ci, kt, ky,
 //            kx) order.  Writes [T][H/2][W/2][64].
-//   K_conv2  27 taps x 64 channels on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32); a block owns 32 whole 2x2x2 pool
+//   K_conv2  27 taps x 64 channels on the exact fp32-input MFMA core of rva_mfma_f32.h (which defines the reduction order); a block owns 32 whole 2x2x2 pool
 //            groups, so the max pool + bias + ReLU run in the epilogue and the unpooled 128-channel volume is never written.
 //            Writes [T/2][H/4][W/4][128].
-//   K_conv3  27 taps x 128 channels, same MFMA; bias + ReLU, then the tile's per-channel sum (positions in tile order): the
+//   K_conv3  27 taps x 128 channels, same core; bias + ReLU, then the tile's per-channel sum (positions in tile order): the
 //            256-channel volume is never written.
-//   K_mean   a clip's tile partials reduced in tile order and divided by T'*H'*W'.
+//   K_mean   a clip's tile partials reduced in tile order and divided by T'*H'*W': the mean kernel of rva_clip.hip.
 //   K_head   Linear: the head kernel of rva_clip.hip (one thread per class, k in order).
 //   K_post   (rva_cnn3d_plan_run_post) the top-k kernel of rva_clip.hip.
 #include "rva_internal.h"
-
-#include <algorithm>
+#include "rva_mfma_f32.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int C1 = 64, C2 = 128, C3 = 256;                 // widths of the architecture
 constexpr int TAPS = 27;
@@ -101,68 +98,10 @@ __global__ void __launch_bounds__(CONV1_THREADS) k_c3d_conv1(const float *ring, 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The MFMA loop of K_conv2 / K_conv3: a wave's 64 positions (MT tiles of 32; lane & 31 = position of the tile) x 128 output
-// channels (NT tiles of 32; lane & 31 = channel of the tile) over a channels-last volume [Ti][Hi][Wi][CIN], zero padded.
-// Reduction order of an output element: taps (kt, ky, kx) in order, in a tap the CIN channels in chunks of 32 of which MFMA step
-// (q, e) takes channel c + 4q + e (lane half 0) and then c + 16 + 4q + e (lane half 1) -- the order of rva_clip.hip's conv2.
-// `w` = [128][27][CIN] weights of the block's output channels.
-template <int CIN>
-__device__ __forceinline__ void c3d_mfma_taps(f32x16 (&acc)[MT][NT], const float *in, const float *w, const int (&pt)[MT],
-                                              const int (&py)[MT], const int (&px)[MT], const bool (&pv)[MT], int Ti, int Hi, int Wi,
-                                              int r, int h)
-{
-    constexpr int CK = 32, NQ = CK / 8;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-    for (int tap = 0; tap < TAPS; ++tap) {
-        const int kt = tap / 9, ky = (tap / 3) % 3, kx = tap % 3;
-        const float *arow[MT];
-        bool av[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int it = pt[mt] + kt - 1, iy = py[mt] + ky - 1, ix = px[mt] + kx - 1;
-            av[mt] = pv[mt] && (unsigned)it < (unsigned)Ti && (unsigned)iy < (unsigned)Hi && (unsigned)ix < (unsigned)Wi;
-            arow[mt] = in + (((size_t)(av[mt] ? it : 0) * Hi + (av[mt] ? iy : 0)) * Wi + (av[mt] ? ix : 0)) * CIN + (CK / 2) * h;
-        }
-#pragma unroll
-        for (int c = 0; c < CIN; c += CK) {
-            float4 fa[MT][NQ], fb[NT][NQ];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fa[mt][q] = av[mt] ? *reinterpret_cast<const float4 *>(arow[mt] + c + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fb[nt][q] = *reinterpret_cast<const float4 *>(w + ((size_t)(nt * 32 + r) * TAPS + tap) * CIN + c + (CK / 2) * h + 4 * q);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const float a_ = e == 0 ? fa[mt][q].x : e == 1 ? fa[mt][q].y : e == 2 ? fa[mt][q].z : fa[mt][q].w;
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const float b_ = e == 0 ? fb[nt][q].x : e == 1 ? fb[nt][q].y : e == 2 ? fb[nt][q].z : fb[nt][q].w;
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_, b_, acc[mt][nt], 0, 0, 0);
-                        }
-                    }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // K_conv2.  Block = 32 pool groups (linear over [T2][H2][W2]) of one clip x all 128 channels; wave = 8 groups = 64 conv positions.
-// Row m of a wave's 64: group m >> 3, position (dt, dy, dx) = bits 2, 1, 0 of m & 7 inside it.  C/D map of the 32x32 shapes:
-// column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) -- so registers 4j .. 4j+3 of a lane are half a pool group and
-// the other lane half holds the rest.  Epilogue: max of the eight raw sums, + bias, ReLU.
+// Row m of a wave's 64: group m >> 3, position (dt, dy, dx) = bits 2, 1, 0 of m & 7 inside it.  C/D map (f32_cd_row): column =
+// lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) -- so registers 4j .. 4j+3 of a lane are half a pool group and the other
+// lane half holds the rest.  Epilogue: max of the eight raw sums, + bias, ReLU.
 __global__ void __launch_bounds__(256) k_c3d_conv2(const float *act1, const float *w2, const float *b2, float *act2, int T, int H1,
                                                    int W1, int T2, int H2, int W2)
 {
@@ -183,8 +122,8 @@ __global__ void __launch_bounds__(256) k_c3d_conv2(const float *act1, const floa
         py[mt] = 2 * ((gg / W2) % H2) + ((e >> 1) & 1);
         px[mt] = 2 * (gg % W2) + (e & 1);
     }
-    f32x16 acc[MT][NT];
-    c3d_mfma_taps<C1>(acc, in, w2, pt, py, px, pv, T, H1, W1, r, h);
+    f32x16 acc[MT][NT] = {};
+    f32_conv_taps<C1, 3>(acc, in, w2, pt, py, px, pv, T, H1, W1);
     float *out = act2 + (size_t)clip * NG * C2;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -204,18 +143,14 @@ __global__ void __launch_bounds__(256) k_c3d_conv2(const float *act1, const floa
 
 // ---------------------------------------------------------------------------------------------------
 // K_conv3.  Block = 256 positions (linear over [T2][H2][W2]; four waves of 64) of one clip x 128 of the 256 channels
-// (blockIdx.y = channel half).  Epilogue as rva_clip.hip's conv2: v = max(acc + bias, 0); per channel the sum over the wave's
-// positions (mt, then i, in order), lane halves 0 + 1, then waves 0..3.
+// (blockIdx.y = channel half).  Epilogue: f32_tile_sum (bias + ReLU, then the tile's per-channel sum).
 __global__ void __launch_bounds__(256) k_c3d_conv3(const float *act2, const float *w3, const float *b3, float *partial, int T2, int H2,
                                                    int W2, int tiles)
 {
-    __shared__ float red[4][2][C2];
     const int clip = blockIdx.z, cb = blockIdx.y, tile = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
+    const int r = threadIdx.x & 31, wave = threadIdx.x >> 6;
     const int P = T2 * H2 * W2;
     const int m0 = tile * 256 + wave * 64;
-    const float *in = act2 + (size_t)clip * P * C2;
     int pt[MT], py[MT], px[MT];
     bool pv[MT];
 #pragma unroll
@@ -227,41 +162,9 @@ __global__ void __launch_bounds__(256) k_c3d_conv3(const float *act2, const floa
         py[mt] = (pp / W2) % H2;
         px[mt] = pp % W2;
     }
-    f32x16 acc[MT][NT];
-    c3d_mfma_taps<C2>(acc, in, w3 + (size_t)cb * C2 * TAPS * C2, pt, py, px, pv, T2, H2, W2, r, h);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int co = nt * 32 + r;
-        const float bias = b3[cb * C2 + co];
-        float s = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int p = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (p < P) s = s + fmaxf(acc[mt][nt][i] + bias, 0.f);
-            }
-        red[wave][h][co] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < C2) {
-        const int co = threadIdx.x;
-        float s = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) s = s + (red[wv][0][co] + red[wv][1][co]);
-        partial[((size_t)clip * tiles + tile) * C3 + cb * C2 + co] = s;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// K_mean.  Block = clip, thread = channel: feat[clip][c] = (sum of the clip's tile partials in tile order) / (T2 * H2 * W2).
-__global__ void __launch_bounds__(C3) k_c3d_mean(const float *partial, int tiles, float n, float *feat)
-{
-    const int clip = blockIdx.x, c = threadIdx.x;
-    const float *pp = partial + (size_t)clip * tiles * C3 + c;
-    float s = 0.f;
-    for (int k = 0; k < tiles; ++k) s = s + pp[(size_t)k * C3];
-    feat[(size_t)clip * C3 + c] = s / n;
+    f32x16 acc[MT][NT] = {};
+    f32_conv_taps<C2, 3>(acc, act2 + (size_t)clip * P * C2, w3 + (size_t)cb * C2 * TAPS * C2, pt, py, px, pv, T2, H2, W2);
+    f32_tile_sum(acc, b3 + cb * C2, m0, P, partial + ((size_t)clip * tiles + tile) * C3 + cb * C2);
 }
 
 }  // namespace
@@ -272,29 +175,8 @@ struct rva_cnn3d_plan {
     int H1 = 0, W1 = 0, T2 = 0, H2 = 0, W2 = 0, conv1_tiles_x = 0, conv1_tiles = 0, conv2_tiles = 0, conv3_tiles = 0;
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr, *wh = nullptr, *bh = nullptr;
     float *act1 = nullptr, *act2 = nullptr, *partial = nullptr, *feat = nullptr;
-    std::vector<void *> allocs;
+    rva_dev_arena mem;
 };
-
-namespace {
-
-int plan_alloc(rva_cnn3d_plan *p, float **dst, size_t n)
-{
-    void *m = nullptr;
-    RVA_HIP(p->ctx, hipMalloc(&m, std::max<size_t>(n, 1) * sizeof(float)));
-    p->allocs.push_back(m);
-    *dst = (float *)m;
-    return RVA_OK;
-}
-
-int plan_upload(rva_cnn3d_plan *p, float **dst, const float *src, size_t n)
-{
-    int rc = plan_alloc(p, dst, n);
-    if (rc != RVA_OK) return rc;
-    RVA_HIP(p->ctx, hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
-    return RVA_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -333,18 +215,18 @@ int rva_cnn3d_plan_create(rva_ctx *ctx, const rva_cnn3d_desc *desc, const rva_cn
     }
     int rc = RVA_OK;
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    step(plan_upload(p, &p->w1, wt->conv1_w, (size_t)C1 * 3 * TAPS));
-    step(plan_upload(p, &p->b1, wt->conv1_b, C1));
-    step(plan_upload(p, &p->w2, wt->conv2_w, (size_t)C2 * TAPS * C1));
-    step(plan_upload(p, &p->b2, wt->conv2_b, C2));
-    step(plan_upload(p, &p->w3, wt->conv3_w, (size_t)C3 * TAPS * C2));
-    step(plan_upload(p, &p->b3, wt->conv3_b, C3));
-    step(plan_upload(p, &p->wh, wt->head_w, (size_t)d.classes * C3));
-    step(plan_upload(p, &p->bh, wt->head_b, d.classes));
-    step(plan_alloc(p, &p->act1, n_act1));
-    step(plan_alloc(p, &p->act2, n_act2));
-    step(plan_alloc(p, &p->partial, n_part));
-    step(plan_alloc(p, &p->feat, n_feat));
+    step(p->mem.upload(ctx, &p->w1, wt->conv1_w, (size_t)C1 * 3 * TAPS));
+    step(p->mem.upload(ctx, &p->b1, wt->conv1_b, C1));
+    step(p->mem.upload(ctx, &p->w2, wt->conv2_w, (size_t)C2 * TAPS * C1));
+    step(p->mem.upload(ctx, &p->b2, wt->conv2_b, C2));
+    step(p->mem.upload(ctx, &p->w3, wt->conv3_w, (size_t)C3 * TAPS * C2));
+    step(p->mem.upload(ctx, &p->b3, wt->conv3_b, C3));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * C3));
+    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
+    step(p->mem.alloc(ctx, &p->act1, n_act1));
+    step(p->mem.alloc(ctx, &p->act2, n_act2));
+    step(p->mem.alloc(ctx, &p->partial, n_part));
+    step(p->mem.alloc(ctx, &p->feat, n_feat));
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, C3);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
@@ -358,7 +240,7 @@ int rva_cnn3d_plan_create(rva_ctx *ctx, const rva_cnn3d_desc *desc, const rva_cn
 void rva_cnn3d_plan_destroy(rva_cnn3d_plan *p)
 {
     if (!p) return;
-    for (void *m : p->allocs) (void)hipFree(m);
+    p->mem.release();
     delete p;
 }
 
@@ -388,8 +270,8 @@ int rva_cnn3d_plan_run(rva_cnn3d_plan *p, const void *frames, const int32_t *fra
     RVA_HIP(ctx, hipGetLastError());
     k_c3d_conv3<<<dim3(p->conv3_tiles, 2, n_clips), 256, 0, st>>>(p->act2, p->w3, p->b3, p->partial, p->T2, p->H2, p->W2, p->conv3_tiles);
     RVA_HIP(ctx, hipGetLastError());
-    k_c3d_mean<<<n_clips, C3, 0, st>>>(p->partial, p->conv3_tiles, (float)((size_t)p->T2 * p->H2 * p->W2), p->feat);
-    RVA_HIP(ctx, hipGetLastError());
+    int rc = rva_clip_mean_launch(ctx, p->partial, p->conv3_tiles, (float)((size_t)p->T2 * p->H2 * p->W2), p->feat, n_clips, C3, st);
+    if (rc != RVA_OK) return rc;
     return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C3, p->d.classes, n_clips, st);
 }
 
@@ -419,13 +301,8 @@ int rva_cnn3d_plan_stage(rva_cnn3d_plan *p, int stage, int n_clips, void *dst, i
     case RVA_CNN3D_STAGE_FEAT: src = p->feat; count = (int64_t)n_clips * C3; break;
     default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: unknown stage %d", stage);
     }
-    if (n_floats) *n_floats = count;
-    if (!dst) return RVA_OK;
-    if (dst_floats < count)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: dst holds %lld floats, stage %d of %d clips has %lld",
-                        (long long)dst_floats, stage, n_clips, (long long)count);
-    RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream_));
-    return RVA_OK;
+    return rva_clip_stage_copy(ctx, "rva_cnn3d_plan_stage", stage, n_clips, src, count, 0, 0, 0, dst, dst_floats, n_floats,
+                               (hipStream_t)stream_);
 }
 
 }  // extern "C"

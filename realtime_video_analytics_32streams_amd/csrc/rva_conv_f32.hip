@@ -3,16 +3,14 @@
 //
 // Convolution: NHWC implicit GEMM on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered fmaf chain, no
 // reduced-precision shortcut).  Rows of the GEMM = output pixels, columns = output channels, K = k*k*Cin.  Every variant (tile
-// shape) and every batch size runs the SAME reduction for an output element: no split-K, taps in order, and inside a tap the
-// channels in chunks of CK (32 when Cin % 32 == 0, else 16) of which step (j, e) takes channel c + 4j + e (lane half 0) and then
-// c + CK/2 + 4j + e (lane half 1).  The sum starts from zero; bias, SiLU (x / (1 + expf(-x))) and the residual follow in that order.
+// shape) and every batch size runs the SAME reduction for an output element: the order rva_mfma_f32.h defines, with chunks of
+// CK = 32 channels when Cin % 32 == 0, else 16.  Bias, SiLU (x / (1 + expf(-x))) and the residual follow in that order.
 // Results are therefore bit-identical across variants, batch sizes and launch orders.  A lane reads only the channels
 // [0, Cin) of its input slice (Cin % 16 == 0): nothing next door is ever multiplied, not even by a zero weight.
 #include "rva_internal.h"
+#include "rva_mfma_f32.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvF32Args {
     const float *in; int ldi;
@@ -29,7 +27,6 @@ template <int MT, int NT, int WM, int WN, int CK>
 __global__ void __launch_bounds__(256) k_conv_f32(ConvF32Args a)
 {
     static_assert(WM * WN == 4, "four waves");
-    constexpr int NQ = CK / 8;                      // float4 loads per lane per operand per chunk
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave % WM, wn = wave / WM;
     const int r = lane & 31, h = lane >> 5;
@@ -56,14 +53,7 @@ __global__ void __launch_bounds__(256) k_conv_f32(ConvF32Args a)
         wv[nt] = co < a.Cout;
         wrow[nt] = a.w + (size_t)(wv[nt] ? co : 0) * kk * a.Cin + (CK / 2) * h;
     }
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
-
+    f32x16 acc[MT][NT] = {};
     for (int tap = 0; tap < kk; ++tap) {
         const int ky = tap / a.k, kx = tap - ky * a.k;
         const float *arow[MT];
@@ -75,36 +65,8 @@ __global__ void __launch_bounds__(256) k_conv_f32(ConvF32Args a)
             arow[mt] = a.in + ((size_t)((long)pn[mt] * a.H + (av[mt] ? iy : 0)) * a.W + (av[mt] ? ix : 0)) * a.ldi + (CK / 2) * h;
         }
         const size_t wtap = (size_t)tap * a.Cin;
-        for (int c = 0; c < a.Cin; c += CK) {
-            float4 fa[MT][NQ], fb[NT][NQ];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fa[mt][q] = av[mt] ? *reinterpret_cast<const float4 *>(arow[mt] + c + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q)
-                    fb[nt][q] = wv[nt] ? *reinterpret_cast<const float4 *>(wrow[nt] + wtap + c + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const float av_ = e == 0 ? fa[mt][q].x : e == 1 ? fa[mt][q].y : e == 2 ? fa[mt][q].z : fa[mt][q].w;
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) {
-                            const float bv_ = e == 0 ? fb[nt][q].x : e == 1 ? fb[nt][q].y : e == 2 ? fb[nt][q].z : fb[nt][q].w;
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av_, bv_, acc[mt][nt], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
+        for (int c = 0; c < a.Cin; c += CK) f32_chunk<MT, NT, CK>(acc, arow, av, c, wrow, wv, wtap + c);
     }
-    // C/D map of the 32x32 shapes: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int co = n0 + nt * 32 + r;
@@ -114,7 +76,7 @@ __global__ void __launch_bounds__(256) k_conv_f32(ConvF32Args a)
         for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const long p = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const long p = m0 + mt * 32 + f32_cd_row(i, h);
                 if (p >= a.M) continue;
                 float v = acc[mt][nt][i] + bias;
                 if (a.act) v = v / (1.f + expf(-v));

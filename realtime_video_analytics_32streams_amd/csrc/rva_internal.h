@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -84,12 +85,47 @@ bool rva_conv_variant_is_gather64(int variant);
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);
 
-// The head (Linear: one thread per class, k in order) and top-k (rank counting) kernels of the clip plans, defined in
-// rva_clip.hip and shared by rva_clip3d.hip.  *_prepare raises the kernel's dynamic-LDS limit (at plan creation, never inside a
-// capture); *_launch only launches on `st`.  `who` names the ABI entry in the argument error of the top-k launch.
+// Device memory of a clip plan: every buffer is a float array owned until release().
+struct rva_dev_arena {
+    std::vector<void *> allocs;
+
+    int alloc(rva_ctx *ctx, float **dst, size_t n)
+    {
+        void *m = nullptr;
+        RVA_HIP(ctx, hipMalloc(&m, std::max<size_t>(n, 1) * sizeof(float)));
+        allocs.push_back(m);
+        *dst = (float *)m;
+        return RVA_OK;
+    }
+
+    int upload(rva_ctx *ctx, float **dst, const float *src, size_t n)
+    {
+        const int rc = alloc(ctx, dst, n);
+        if (rc != RVA_OK) return rc;
+        RVA_HIP(ctx, hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
+        return RVA_OK;
+    }
+
+    void release()
+    {
+        for (void *m : allocs) (void)hipFree(m);
+        allocs.clear();
+    }
+};
+
+// The mean (tile partials in tile order / n; `rows` blocks of `channels` threads), head (Linear: one thread per class, k in
+// order) and top-k (rank counting) kernels of the clip plans, defined in rva_clip.hip and shared by rva_clip3d.hip.  *_prepare
+// raises the kernel's dynamic-LDS limit (at plan creation, never inside a capture); *_launch only launches on `st`.  `who` names
+// the ABI entry in the argument error of the top-k launch.
+int rva_clip_mean_launch(rva_ctx *ctx, const float *partial, int tiles, float n, float *feat, int rows, int channels, hipStream_t st);
 int rva_clip_head_prepare(rva_ctx *ctx, int hidden);
 int rva_clip_head_launch(rva_ctx *ctx, const float *x, const float *wh, const float *bh, float *logits, int hidden, int classes,
                          int n_clips, hipStream_t st);
 int rva_clip_post_prepare(rva_ctx *ctx, int classes);
 int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, const int32_t *rows, int n_rows, int max_det,
                          float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);
+
+// The tail of every *_plan_stage tap: reports `count` through n_floats, and if dst is given checks its size and copies `count`
+// floats device to device on `st` -- as `rows` rows of row_floats out of a pitch of pitch_floats if rows > 0, else flat.
+int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n_clips, const float *src, int64_t count, int64_t rows,
+                        int64_t row_floats, int64_t pitch_floats, void *dst, int64_t dst_floats, int64_t *n_floats, hipStream_t st);

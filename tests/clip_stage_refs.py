@@ -90,6 +90,33 @@ def tile_partial(v, tol):
     return torch.stack(parts, 1), torch.stack(tols, 1)
 
 
+def tile_partial_in_kernel_order(y, dtype=np.float32):
+    """The tile sums of f32_tile_sum (csrc/rva_mfma_f32.h) from the map before the ReLU, ``y [F, P, C]`` -> ``[F, tiles, C]``, every
+    operation in ``dtype``: v = max(y, 0); per tile of 256 positions, per wave (64 positions from m0 = 256 tile + 64 wave) and
+    lane half h a sum from zero over positions m0 + 32 mt + (i & 3) + 8 (i >> 2) + 4 h for mt = 0, 1 then i = 0 .. 15, positions
+    >= P skipped; then halves 0 + 1; then waves 0 .. 3 added in order to zero."""
+    v = np.maximum(np.asarray(y, dtype=dtype), dtype(0))
+    F_, P, C_ = v.shape
+    out = np.zeros((F_, -(-P // TILE), C_), dtype=dtype)
+    for tile in range(out.shape[1]):
+        total = np.zeros((F_, C_), dtype=dtype)
+        for wave in range(4):
+            m0 = tile * TILE + wave * 64
+            halves = []
+            for h in range(2):
+                s = np.zeros((F_, C_), dtype=dtype)
+                for mt in range(2):
+                    for i in range(16):
+                        p = m0 + mt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h
+                        if p < P:
+                            s = s + v[:, p]
+                halves.append(s)
+            total = total + (halves[0] + halves[1])
+        out[:, tile] = total
+    assert out.dtype == dtype
+    return out
+
+
 def feat_from_partial(partial, P):
     """``[F, tiles, C]`` tile sums -> (mean ``[F, C]``, bound)."""
     partial = f64(partial)

@@ -7,6 +7,7 @@ the bound (the reference alone meets the condition the GPU tests put on the kern
 GPU stage tests; the "taps" are the float64 references rounded once to fp32."""
 import functools
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -198,6 +199,20 @@ def test_last_pixel_left_out_of_its_tile_sum(case, shape):
     seen = _seen(_finish(case, y2.view_as(y), t), ref, tol)
     print(f"{case.__name__} {R.shape_id(shape)}: seen {seen:.1f} x bound")
     assert seen > FACTOR
+
+
+@pytest.mark.parametrize("P", [4, 140, 256, 257, 561])
+def test_kernel_order_tile_sum_visits_every_position_once(P):
+    """The order emulation the GPU test compares bits with, in float64 on values whose sums are exact: channel c is 1 at
+    position c and -1 (0 after the ReLU) everywhere else, channel P + c counts the positions up to c, so a position visited
+    twice or never moves a sum by a whole number.  Per tile and over all P it must equal the plain per-channel sum."""
+    pos = np.arange(P)
+    y = np.concatenate([np.where(pos[:, None] == pos[None, :], 1.0, -1.0), np.where(pos[:, None] <= pos[None, :], 3.0, -2.0)], 1)[None]
+    got = R.tile_partial_in_kernel_order(y, np.float64)
+    v = np.maximum(y, 0.0)
+    want = np.stack([v[:, k:k + R.TILE].sum(1) for k in range(0, P, R.TILE)], 1)
+    assert got.shape == want.shape == (1, -(-P // R.TILE), 2 * P)
+    assert np.array_equal(got, want) and np.array_equal(got.sum(1), v.sum(1))
 
 
 def _drop_tap8(w):

@@ -4,12 +4,14 @@ both LSTM layers at every step and clip, and the logits.  Each stage's reference
 it with the bounds of tests/clip_stage_refs.py, so a failure names the kernel; tests/test_clip_stages_host.py proves on the
 CPU that these bounds see the kernels' bug classes.  Shapes: the smallest legal plan; ragged stem tiles and one partial conv2
 tile; odd conv map (live -inf pool padding); exactly one full conv2 tile and three LSTM passes; a 1-wide ragged stem edge, three
-conv2 tiles with a tail, hidden = 130 and a capacity above the clip count.
+conv2 tiles with a tail, hidden = 130 and a capacity above the clip count.  And conv2 bit for bit as what it is built from: the
+fp32 convolution primitive on the pooled tap, summed on the host in the order of csrc/rva_mfma_f32.h's tile sum.
 
-Observed / bound: every test prints it per stage (``pytest -s``).  These tests have not run on a GPU yet; on the
-CPU torch's fp32 operators sit at 0.00 .. 0.58 of the bounds (the mean is the tightest)."""
+Observed / bound: every test prints it per stage (``pytest -s``).  On the CPU torch's fp32 operators sit at 0.00 .. 0.58 of
+the bounds (the mean is the tightest)."""
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 
@@ -66,6 +68,33 @@ def test_stages_through_a_permuted_index_table_are_bit_equal():
     got = _run(plan, ring, perm.to(torch.int32).to(DEV), n)
     for k in want:
         assert torch.equal(got[k], want[k]), k
+
+
+def test_conv2_is_the_f32_conv_primitive_summed_in_the_documented_order():
+    """k_clip_conv2 and rva_conv2d_nhwc_f32_v share one MFMA core (csrc/rva_mfma_f32.h): on the pooled tap the primitive (Cin 64,
+    Cout 128, k 3, stride 1, no activation, the plan's bias; variant 0 and every forced variant) gives conv2's map before the
+    ReLU, and that map summed in fp32 on the host in the tile sum's documented order is the ``partial`` tap, bit for bit.
+    17 x 33 = 561 pixels: three tiles, the last one ragged."""
+    shape = R.LSTM_SHAPES[4]
+    H, W, T, hidden, classes, n, cap = shape
+    net, p, clips = R.lstm_case(shape)
+    plan = FusedCnnLstm(net, (H, W), T, cap)
+    taps = _run(plan, clips.to(DEV).view(-1, 3, H, W).contiguous(), torch.arange(n * T, dtype=torch.int32, device=DEV), n)
+    pooled, partial = taps["pooled"], taps["partial"].cpu().numpy()
+    F_, Hp, Wp = pooled.shape[:3]
+    assert (F_, Hp, Wp, partial.shape) == (n * T, 17, 33, (n * T, 3, 128))
+    w = p["conv2_w"].permute(0, 2, 3, 1).contiguous().float().to(DEV)          # [co][ci][ky][kx] -> [co][tap][ci]
+    b = p["conv2_b"].float().to(DEV)
+    variants = range(int(plan.L.rva_conv_f32_num_variants()) + 1)
+    assert len(variants) >= 2
+    for v in variants:
+        out = torch.full((F_, Hp, Wp, 128), float("nan"), device=DEV)
+        plan.ctx.check(plan.L.rva_conv2d_nhwc_f32_v(plan.ctx.handle, C.c_void_p(pooled.data_ptr()), 64, C.c_void_p(w.data_ptr()),
+                                                    C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()), 128, None, 0, F_, Hp, Wp,
+                                                    64, 128, 3, 1, 0, v, ops._stream_ptr()),
+                       "rva_conv2d_nhwc_f32_v")
+        got = R.tile_partial_in_kernel_order(out.cpu().numpy().reshape(F_, Hp * Wp, 128))
+        assert got.dtype == np.float32 and np.array_equal(got, partial), ("variant", v)
 
 
 def test_tap_contract():

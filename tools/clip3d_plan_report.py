@@ -41,7 +41,7 @@ from realtime_video_analytics_32streams_amd.video_stream import SyntheticNv12Str
 
 PEAK_F32_TF = 157.3
 T, HW = 16, (112, 112)
-STAGES = {"k_c3d_conv1": "conv1+pool", "k_c3d_conv2": "conv2+pool", "k_c3d_conv3": "conv3+sums", "k_c3d_mean": "mean",
+STAGES = {"k_c3d_conv1": "conv1+pool", "k_c3d_conv2": "conv2+pool", "k_c3d_conv3": "conv3+sums", "k_clip_mean": "mean",
           "k_clip_head": "head", "k_clip_post": "top5"}
 
 
