@@ -608,6 +608,64 @@ int rva_cnn3d_plan_stage(rva_cnn3d_plan *plan, int stage, int n_clips, void *dst
                          rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The ResNet-18 classifier as ONE fp32 object -- replaces the network call of the reference's ResNet head and its top-K
+ * (detector.py:870-1001) for a batch of frames.  Per frame [3][H][W]: Conv 7x7 s2 p3 + BN + ReLU -> MaxPool 3x3 s2 p1 -> eight
+ * BasicBlocks (widths 64, 64, 128, 128, 256, 256, 512, 512; blocks 2, 4 and 6 have stride 2 and a 1x1 stride-2 shortcut
+ * convolution) -> mean over H,W -> Linear(512 -> classes).
+ *
+ * rva_resnet_plan_create: `weights` = fp32 host arrays (all required), every convolution with its BatchNorm folded in (by the
+ *   caller, in float64, rounded once): stem weight [64][3][7][7] (the checkpoint's layout) and bias [64]; conv[19] = the block
+ *   convolutions as [Cout][k*k][Cin] (tap = ky*k + kx, channels innermost: what the kernel reads) with bias [Cout], block by
+ *   block in the order conv1 (3x3), conv2 (3x3), then the block's shortcut (1x1) where it has one -- so conv[6], conv[11] and
+ *   conv[16] are the shortcuts of blocks 2, 4 and 6; head weight [classes][512] and bias [classes].  The plan copies them and
+ *   allocates its whole workspace for desc.max_frames frames (height, width >= 1, classes 1..16384, top_k >= 1, max_frames
+ *   1..65535); a workspace larger than the free device memory is refused with RVA_ERR_CAPACITY.
+ * rva_resnet_plan_run: frames = device planar fp32 frames [3][height][width] (what rva_preprocess_frames_* writes with
+ *   RVA_NORM_IMAGENET_F32); frame_index = device int32 [n]: frame b is frames + frame_index[b] * 3*height*width (no gathered
+ *   copy).  logits = device fp32 [n][classes], the raw outputs (no softmax).  Every launch goes to `stream`; no host
+ *   synchronisation, no allocation: capturable.  Each sum runs in one fixed order (no split-K, no atomics): a frame's logits
+ *   are bit-identical for every batch size, position in the batch and launch mode.
+ * rva_resnet_plan_run_post: the arguments and the rule of rva_cnnlstm_plan_run_post (the same kernel) with k = min(desc.top_k,
+ *   classes); the row table's first column is the batch row of the result row or -1.
+ * rva_resnet_plan_info: maps[5][2] = (height, width) of the pooled map and of the four stages' maps, the workspace size in
+ *   bytes (activations of max_frames frames), launches per _run.  Any may be NULL.
+ * rva_resnet_plan_stage: the read-only workspace tap of rva_cnnlstm_plan_stage (same arguments, rules and errors; n_clips =
+ *   frames).  Every tensor is [n][h][w][C] (channels last) with (h, w) the map of the block's stage and C its width:
+ *     RVA_RESNET_STAGE_POOLED         [n][Hp][Wp][64]   stem output: conv1 + BN + ReLU + max pool
+ *     RVA_RESNET_STAGE_MID0 + b       b = 0..7: ReLU(conv1 + BN) of block b
+ *     RVA_RESNET_STAGE_DOWN2 / 4 / 6  shortcut convolution + BN of blocks 2, 4, 6
+ *     RVA_RESNET_STAGE_OUT0 + b       b = 0..7: ReLU((conv2 + BN) + shortcut) of block b
+ *     RVA_RESNET_STAGE_FEAT           [n][512]          the spatial mean: pixels in raster order from zero, divided by h*w
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_resnet_plan rva_resnet_plan;
+typedef struct rva_resnet_desc {
+    int32_t height, width;            /* frame size (224 x 224 by default) */
+    int32_t classes, top_k;
+    int32_t max_frames;               /* capacity: the most frames one _run may take */
+} rva_resnet_desc;
+typedef struct rva_resnet_conv {
+    const float *w, *b;
+} rva_resnet_conv;
+typedef struct rva_resnet_weights {
+    const float *stem_w, *stem_b;
+    rva_resnet_conv conv[19];
+    const float *head_w, *head_b;
+} rva_resnet_weights;
+int rva_resnet_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *weights, rva_resnet_plan **out);
+void rva_resnet_plan_destroy(rva_resnet_plan *plan);
+int rva_resnet_plan_info(const rva_resnet_plan *plan, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches);
+int rva_resnet_plan_run(rva_resnet_plan *plan, const void *frames, const int32_t *frame_index, int n, void *logits,
+                        rva_stream_t stream);
+int rva_resnet_plan_run_post(rva_resnet_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                             void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+enum rva_resnet_stage {
+    RVA_RESNET_STAGE_POOLED = 0, RVA_RESNET_STAGE_MID0 = 1, RVA_RESNET_STAGE_DOWN2 = 9, RVA_RESNET_STAGE_DOWN4 = 10,
+    RVA_RESNET_STAGE_DOWN6 = 11, RVA_RESNET_STAGE_OUT0 = 12, RVA_RESNET_STAGE_FEAT = 20
+};
+int rva_resnet_plan_stage(rva_resnet_plan *plan, int stage, int n, void *dst, int64_t dst_floats, int64_t *n_floats,
+                          rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)
  * for a tick of NV12 surfaces: gray -> 5x5 Gaussian -> |diff| against prev_blur[i] -> counts[i] = number of
  * pixels with diff > 25 (device int32[n]; -1 where prev_blur[i] is NULL = first frame of that stream).

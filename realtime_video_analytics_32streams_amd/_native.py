@@ -19,7 +19,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
 SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip", "rva_clip.hip",
-           "rva_clip3d.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+           "rva_clip3d.hip", "rva_resnet.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]
@@ -76,6 +76,18 @@ class Cnn3dWeights(C.Structure):
     """``rva_cnn3d_weights`` (include/rva.h): the three convolutions with BatchNorm folded, in the layouts the kernels read
     (``clip_plan.pack_cnn3d``), and the head."""
     NAMES = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "head_w", "head_b")
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
+
+
+class ResNetDesc(C.Structure):
+    """``rva_resnet_desc`` (include/rva.h)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("classes", C.c_int32), ("top_k", C.c_int32), ("max_frames", C.c_int32)]
+
+
+class ResNetWeights(C.Structure):
+    """``rva_resnet_weights`` (include/rva.h): the stem, the 19 block convolutions (``c<i>_w`` / ``c<i>_b`` = ``conv[i].w`` /
+    ``.b``, in the layouts ``resnet_plan.pack_resnet18`` writes) and the head."""
+    NAMES = ("stem_w", "stem_b") + tuple(f"c{i}_{x}" for i in range(19) for x in "wb") + ("head_w", "head_b")
     _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
 
 
@@ -249,6 +261,12 @@ def lib() -> C.CDLL:
         "rva_cnn3d_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_cnn3d_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
         "rva_cnn3d_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
+        "rva_resnet_plan_create": (C.c_int, [_P, C.POINTER(ResNetDesc), C.POINTER(ResNetWeights), C.POINTER(_P)]),
+        "rva_resnet_plan_destroy": (None, [_P]),
+        "rva_resnet_plan_info": (C.c_int, [_P, i32p, i64p, i32p]),
+        "rva_resnet_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+        "rva_resnet_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_resnet_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -287,7 +305,8 @@ EXPORTS = [
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
     "rva_yolov8_plan_get_variant", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
     "rva_cnnlstm_plan_run_post", "rva_cnnlstm_plan_stage", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
-    "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage", "rva_resnet_plan_create", "rva_resnet_plan_destroy", "rva_resnet_plan_info",
+    "rva_resnet_plan_run", "rva_resnet_plan_run_post", "rva_resnet_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
 ]
 

@@ -8,7 +8,8 @@ network here is a from-scratch torch ResNet-18 with seeded weights (no model fil
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -18,6 +19,7 @@ from . import _native as N
 from . import ops
 from .config import DetectorConfig
 from .detector import BaseDetector, Detection
+from .resnet_plan import ENGINE as RESNET_PLAN, FusedResNet18
 from .video_stream import FramePacket
 
 
@@ -52,8 +54,33 @@ class ResNet18(nn.Module):
         return self.fc(self.layers(self.stem(x)).mean((2, 3)))
 
 
+@dataclass
+class _ResTick:
+    """What ``stage_pre`` hands to ``stage_net`` / ``stage_post`` for one tick of one frame group."""
+    rows: int                                   # streams of the group (batch rows of the PostBuffers)
+    wh: Tuple[int, int]                         # (width, height) of the group's frames: the full-frame box
+    slot: int                                   # pipeline slot (tick parity) whose buffers this tick uses
+    x: torch.Tensor                             # [rows, 3, H, W] fp32: a view of the slot's input buffer
+
+
+class _ResSlot:
+    """One tick slot's input buffer (K1 writes it, the network reads it) and, on the plan engine, its plan with two logits
+    sets used in turn: the tail of the previous tick that used this slot may still read the other set (temporal._PlanSlot)."""
+
+    def __init__(self, cap: int, hw, device, plan: Optional[FusedResNet18]):
+        self.cap, self.plan, self.turn = cap, plan, 0
+        self.input = torch.empty((cap, 3, *hw), dtype=torch.float32, device=device)
+        self.iota = torch.arange(cap, dtype=torch.int32, device=device)
+        self.logits = [torch.empty((cap, plan.classes), dtype=torch.float32, device=device) for _ in range(2)] if plan else []
+
+
 class HipResNetDetector(BaseDetector):
-    """``predict(packet)`` / ``predict_batch(packets)`` with the reference's top-K rule (detector.py:945-977)."""
+    """``predict(packet)`` / ``predict_batch(packets)`` with the reference's top-K rule (detector.py:945-977), and the batched
+    device path of the tick pipeline (``stage_pre`` / ``stage_net`` / ``stage_post``: K1 into the tick slot's input buffer, the
+    network, the top-K as device result rows -- no host synchronisation).  ``engine``: ``"infer_fn"`` (a caller's function
+    overrides everything), ``"resnet-f32"`` (``hip_engine: plan``: the network and the device path's top-K run as the
+    hand-written fp32 plan, resnet_plan.FusedResNet18) or ``"torch"`` (PyTorch-ROCm).  ``half`` has no effect on this head: it
+    runs float32 like the reference's pre-process.  ``hip_engine: native`` is refused."""
 
     def __init__(self, config: DetectorConfig, net: Optional[nn.Module] = None, infer_fn=None, seed: int = 2,
                  device: Optional[int] = None):
@@ -62,9 +89,11 @@ class HipResNetDetector(BaseDetector):
         self.device = torch.device("cuda", self.ctx.device)
         self.input_hw = (int(config.input_size[0]), int(config.input_size[1])) if config.input_size else (224, 224)
         self._infer_fn = infer_fn
-        if infer_fn is None and getattr(config, "hip_engine", "auto") == "native":
+        hip_engine = getattr(config, "hip_engine", "auto")
+        if infer_fn is None and hip_engine == "native":
             raise ValueError("hip_engine: native has no hand-written plan for model_type 'resnet' (the network runs through "
                              "PyTorch-ROCm with hip_engine: auto)")
+        self.engine = "infer_fn" if infer_fn is not None else (RESNET_PLAN if hip_engine == "plan" else "torch")
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -73,8 +102,16 @@ class HipResNetDetector(BaseDetector):
                 net = ResNet18(config.resnet_num_classes)
                 torch.random.set_rng_state(st)
             self.net = net.eval().float().to(self.device).to(memory_format=torch.channels_last)
+        # batched device path
+        self._slot = 0                         # set by PipelinedTicks: tick parity -> which buffers a tick uses
+        self.two_chain_ok = True               # every buffer of a tick exists per slot: consecutive ticks may run as two chains
+        self._streams = 0                      # streams the pipeline announced (reserve_streams): the slots' capacity
+        self._slots: Dict[int, _ResSlot] = {}
+        self._post: Dict[tuple, ops.PostBuffers] = {}
+        self._tables: Dict[tuple, torch.Tensor] = {}      # (rows, w, h) -> device row table / box rows, uploaded once
+        self._host_plan: Optional[FusedResNet18] = None   # plan of predict / predict_batch
 
-    def _preprocess(self, frames: Sequence) -> torch.Tensor:
+    def _preprocess(self, frames: Sequence, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         dev = []
         for f in frames:
             if isinstance(f, ops.Nv12Surface):
@@ -82,19 +119,32 @@ class HipResNetDetector(BaseDetector):
             else:
                 t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
                 dev.append(t.to(self.device).contiguous())
-        return ops.preprocess_frames(dev, self.input_hw, N.NORM_IMAGENET_F32, N.LAYOUT_NCHW, torch.float32, ctx=self.ctx)
+        if out is None:
+            out = torch.empty((len(dev), 3, *self.input_hw), dtype=torch.float32, device=self.device)
+        for b0 in range(0, len(dev), N.RVA_MAX_BATCH):
+            ops.preprocess_frames(dev[b0:b0 + N.RVA_MAX_BATCH], self.input_hw, N.NORM_IMAGENET_F32, N.LAYOUT_NCHW, torch.float32,
+                                  out=out[b0:b0 + N.RVA_MAX_BATCH], ctx=self.ctx)
+        return out
+
+    def _make_plan(self, max_frames: int) -> FusedResNet18:
+        return FusedResNet18(self.net, self.input_hw, max_frames, self.config.resnet_top_k, ctx=self.ctx, device=self.device)
+
+    def _network(self, x: torch.Tensor) -> torch.Tensor:
+        """``[B, 3, H, W]`` -> raw ``[B, classes]`` on this detector's engine (the host path: a fresh tensor)."""
+        if self.engine == RESNET_PLAN:
+            if self._host_plan is None or self._host_plan.max_clips < x.shape[0]:
+                self._host_plan = self._make_plan(int(x.shape[0]))
+            return self._host_plan(x)
+        return self._infer_fn(x) if self._infer_fn is not None else self.net(x)
 
     def predict_batch(self, packets: Sequence[FramePacket]) -> List[List[Detection]]:
         groups = {}
         for i, p in enumerate(packets):
-            f = p.frame
-            key = (f.width, f.height, "nv12") if isinstance(f, ops.Nv12Surface) else (int(f.shape[1]), int(f.shape[0]), "bgr")
-            groups.setdefault(key, []).append(i)
+            groups.setdefault(self.geometry_key(p.frame), []).append(i)
         out: List[Optional[List[Detection]]] = [None] * len(packets)
         for (w, h, _), idxs in groups.items():
             with torch.inference_mode():
-                x = self._preprocess([packets[i].frame for i in idxs])
-                raw = self._infer_fn(x) if self._infer_fn is not None else self.net(x)
+                raw = self._network(self._preprocess([packets[i].frame for i in idxs]))
             scores = raw.float().cpu().numpy()
             for row, i in enumerate(idxs):
                 p, o = packets[i], scores[row].flatten()
@@ -106,3 +156,69 @@ class HipResNetDetector(BaseDetector):
 
     def predict(self, packet: FramePacket) -> List[Detection]:
         return self.predict_batch([packet])[0]
+
+    # -- batched device path: a whole tick of this head without a host round trip ----------------------------------------
+    @staticmethod
+    def geometry_key(frame) -> tuple:
+        if isinstance(frame, ops.Nv12Surface):
+            return (int(frame.width), int(frame.height), "nv12")
+        return (int(frame.shape[1]), int(frame.shape[0]), "bgr")
+
+    def reserve_streams(self, names: Sequence[str]) -> None:
+        """The most frames a tick can bring (TickPipeline calls this once): the slots are sized for it and never regrown."""
+        self._streams = max(self._streams, len(names))
+
+    def _tick_slot(self, slot: int, rows: int) -> _ResSlot:
+        """The buffers (and plan) of a tick slot; rebuilt, after a device drain, only for more frames than were announced."""
+        rs = self._slots.get(slot)
+        if rs is None or rs.cap < rows:
+            if rs is not None:
+                torch.cuda.synchronize(self.device)          # the old buffers may still be read by a tick in flight
+            cap = max(rows, self._streams, 1)
+            rs = self._slots[slot] = _ResSlot(cap, self.input_hw, self.device, self._make_plan(cap) if self.engine == RESNET_PLAN else None)
+        return rs
+
+    def stage_pre(self, packets: Sequence[FramePacket]) -> _ResTick:
+        """K1 of the tick: the group's frames (one geometry) pre-processed into the slot's input buffer."""
+        rs = self._tick_slot(self._slot, len(packets))
+        x = self._preprocess([p.frame for p in packets], out=rs.input[:len(packets)])
+        w, h, _ = self.geometry_key(packets[0].frame)
+        return _ResTick(len(packets), (w, h), self._slot, x)
+
+    def stage_net(self, pre: _ResTick) -> torch.Tensor:
+        """The group's frames as ONE network batch: ``[rows, classes]`` raw outputs (no softmax)."""
+        if self.engine == RESNET_PLAN:
+            rs = self._slots[pre.slot]
+            logits = rs.logits[rs.turn]
+            rs.turn ^= 1
+            return rs.plan.run(rs.input, rs.iota, pre.rows, out=logits)
+        with torch.inference_mode():
+            return (self._infer_fn(pre.x) if self._infer_fn is not None else self.net(pre.x)).float()
+
+    def stage_post(self, raw: torch.Tensor, pre: _ResTick) -> ops.PostBuffers:
+        """Top-K of the raw output per frame in the reference's order (ascending stable sort, last K reversed: detector.py:956),
+        full-frame boxes; the ``>= confidence_threshold`` test is the tracker kernel's filter (same float64 comparison)."""
+        k = min(int(self.config.resnet_top_k), int(raw.shape[1]))
+        key = (pre.rows, pre.slot)
+        post = self._post.get(key)
+        if post is None:
+            post = self._post[key] = ops.PostBuffers.allocate(pre.rows, max(8, k), self.device)
+        plan = self.engine == RESNET_PLAN
+        tkey = (pre.rows, *pre.wh, plan)
+        tab = self._tables.get(tkey)
+        if tab is None:                        # every row has a frame: the table is constant per (rows, w, h)
+            w, h = pre.wh
+            tab = self._tables[tkey] = torch.tensor([[r, w, h] for r in range(pre.rows)], dtype=torch.int32, device=self.device) \
+                if plan else torch.tensor([0.0, 0.0, float(w), float(h)], device=self.device)
+        if plan:
+            return self._slots[pre.slot].plan.post(raw, tab, pre.rows, post)
+        order = torch.sort(raw, dim=1, stable=True).indices[:, -k:].flip(1)                # [rows, k]
+        post.scores[:, :k] = torch.gather(raw, 1, order)
+        post.cls[:, :k] = order.to(torch.int32)
+        post.boxes[:, :k] = tab
+        post.counts.fill_(k)
+        return post
+
+    def predict_batch_device(self, packets: Sequence[FramePacket]) -> ops.PostBuffers:
+        pre = self.stage_pre(packets)
+        return self.stage_post(self.stage_net(pre), pre)

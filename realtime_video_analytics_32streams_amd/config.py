@@ -13,8 +13,9 @@ detector key ``hip_engine`` picks the network's engine: ``"auto"`` (default; wha
 = the hand-written fp16 plan for YOLO with ``half: true``, PyTorch-ROCm for YOLO with ``half: false`` and for
 every temporal head; ``"plan"`` = the hand-written plan at the configured precision, i.e. the fp32 YOLO plan for
 ``half: false`` and, for ``model_type: cnn_lstm``, the fp32 clip plan (``half: false`` only: ``half: true`` is
-refused at construction).  The other temporal heads have no plan: with ``"plan"`` they keep PyTorch-ROCm and log
-a warning.  ``"native"`` is the strict form of ``"plan"``: every network of the detector runs as hand-written HIP at the
+refused at construction) and, for ``model_type: resnet``, the fp32 ResNet-18 plan (engine ``"resnet-f32"``,
+resnet_plan.py; this head always runs float32, ``half`` has no effect on it).  The other temporal heads have no plan: with
+``"plan"`` they keep PyTorch-ROCm and log a warning.  ``"native"`` is the strict form of ``"plan"``: every network of the detector runs as hand-written HIP at the
 configured precision, or construction fails with ``ValueError`` (an ``infer_fn`` still overrides everything):
 
     head                    half: false                       half: true

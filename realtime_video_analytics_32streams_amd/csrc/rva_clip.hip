@@ -314,7 +314,26 @@ size_t lstm_lds(int hidden) { return (size_t)(LSTM_G * 2 * hidden + LSTM_R * LST
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-// K_mean, K_head and K_post serve every clip plan (rva_clip3d.hip launches them through these; declared in rva_internal.h).
+// K_stem, K_mean, K_head and K_post serve the other plans too (rva_clip3d.hip and rva_resnet.hip launch them through these;
+// declared in rva_internal.h).
+int rva_clip_stem_prepare(rva_ctx *ctx)
+{
+    if (rva_func_smem((const void *)k_clip_stem, STEM_LDS) != hipSuccess)
+        return rva_fail(ctx, RVA_ERR_HIP, "clip plan: cannot raise the stem kernel's LDS limit");
+    return RVA_OK;
+}
+
+int rva_clip_stem_launch(rva_ctx *ctx, const float *frames, const int32_t *frame_index, const float *w1, const float *b1, float *pooled,
+                         int H, int W, int n_frames, hipStream_t st)
+{
+    const int Hc = (H + 2 * 3 - K1) / 2 + 1, Wc = (W + 2 * 3 - K1) / 2 + 1, Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;
+    const int tiles_x = rva_ceil_div(Wp, PT);
+    k_clip_stem<<<dim3(tiles_x * rva_ceil_div(Hp, PT), n_frames), STEM_THREADS, STEM_LDS, st>>>(frames, frame_index, w1, b1, pooled, H, W,
+                                                                                                Hc, Wc, Hp, Wp, tiles_x);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
 int rva_clip_mean_launch(rva_ctx *ctx, const float *partial, int tiles, float n, float *feat, int rows, int channels, hipStream_t st)
 {
     if (channels < 1 || channels > 256) return rva_fail(ctx, RVA_ERR_ARG, "rva_clip_mean_launch: %d channels, one block holds 1..256", channels);
@@ -345,11 +364,10 @@ int rva_clip_post_prepare(rva_ctx *ctx, int classes)
     return RVA_OK;
 }
 
-int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, const int32_t *rows, int n_rows, int max_det,
-                         float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st)
+int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, int k, const int32_t *rows, int n_rows,
+                         int max_det, float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st)
 {
-    const int k = std::min(5, classes);
-    if (!logits || !rows || n_rows < 1 || max_det < k || !scores || !cls || !counts || !boxes || ((uintptr_t)boxes & 15))
+    if (k < 1 || k > classes || !logits || !rows || n_rows < 1 || max_det < k || !scores || !cls || !counts || !boxes || ((uintptr_t)boxes & 15))
         return rva_fail(ctx, RVA_ERR_ARG, "%s: bad argument (n_rows >= 1, max_det >= %d, 16-byte aligned boxes)", who, k);
     k_clip_post<<<n_rows, 256, (size_t)classes * sizeof(float), st>>>(logits, classes, rows, k, max_det, scores, cls, boxes, counts);
     RVA_HIP(ctx, hipGetLastError());
@@ -439,8 +457,7 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
     step(p->mem.alloc(ctx, &p->h2, (size_t)T * d.max_clips * h));
     step(p->mem.alloc(ctx, &p->c1, (size_t)d.max_clips * h));
     step(p->mem.alloc(ctx, &p->c2, (size_t)d.max_clips * h));
-    if (rc == RVA_OK && rva_func_smem((const void *)k_clip_stem, STEM_LDS) != hipSuccess)
-        rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the stem kernel's LDS limit");
+    if (rc == RVA_OK) rc = rva_clip_stem_prepare(ctx);
     if (rc == RVA_OK && rva_func_smem((const void *)k_clip_lstm, lstm_lds(h)) != hipSuccess)
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_plan_create: cannot raise the LSTM kernel's LDS limit");
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, h);
@@ -479,13 +496,11 @@ int rva_cnnlstm_plan_run(rva_cnnlstm_plan *p, const void *frames, const int32_t 
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_run: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
     const hipStream_t st = (hipStream_t)stream_;
     const int T = p->d.frames, h = p->d.hidden, G4 = 4 * h, nf = n_clips * T;
-    k_clip_stem<<<dim3(p->stem_tiles, nf), STEM_THREADS, STEM_LDS, st>>>((const float *)frames, frame_index, p->w1, p->b1, p->pooled,
-                                                                          p->d.height, p->d.width, p->Hc, p->Wc, p->Hp, p->Wp,
-                                                                          p->stem_tiles_x);
-    RVA_HIP(ctx, hipGetLastError());
+    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->w1, p->b1, p->pooled, p->d.height, p->d.width, nf, st);
+    if (rc != RVA_OK) return rc;
     k_clip_conv2<<<dim3(p->conv2_tiles, nf), 256, 0, st>>>(p->pooled, p->w2, p->b2, p->partial, p->Hp, p->Wp, p->conv2_tiles);
     RVA_HIP(ctx, hipGetLastError());
-    int rc = rva_clip_mean_launch(ctx, p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat, nf, C2, st);
+    rc = rva_clip_mean_launch(ctx, p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat, nf, C2, st);
     if (rc != RVA_OK) return rc;
     k_clip_xproj<<<dim3(rva_ceil_div(G4, 256), n_clips), 256, (size_t)T * C2 * sizeof(float), st>>>(
         p->feat, p->wih1, p->bl1, p->gx, T, G4);
@@ -503,7 +518,7 @@ int rva_cnnlstm_plan_run_post(rva_cnnlstm_plan *p, const void *logits, const int
                               void *cls, void *boxes, void *counts, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
-    return rva_clip_post_launch(p->ctx, "rva_cnnlstm_plan_run_post", (const float *)logits, p->d.classes, rows, n_rows, max_det,
+    return rva_clip_post_launch(p->ctx, "rva_cnnlstm_plan_run_post", (const float *)logits, p->d.classes, std::min(5, p->d.classes), rows, n_rows, max_det,
                                 (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 

@@ -279,7 +279,7 @@ int rva_cnn3d_plan_run_post(rva_cnn3d_plan *p, const void *logits, const int32_t
                             void *cls, void *boxes, void *counts, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
-    return rva_clip_post_launch(p->ctx, "rva_cnn3d_plan_run_post", (const float *)logits, p->d.classes, rows, n_rows, max_det,
+    return rva_clip_post_launch(p->ctx, "rva_cnn3d_plan_run_post", (const float *)logits, p->d.classes, std::min(5, p->d.classes), rows, n_rows, max_det,
                                 (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 

@@ -113,17 +113,22 @@ struct rva_dev_arena {
     }
 };
 
-// The mean (tile partials in tile order / n; `rows` blocks of `channels` threads), head (Linear: one thread per class, k in
-// order) and top-k (rank counting) kernels of the clip plans, defined in rva_clip.hip and shared by rva_clip3d.hip.  *_prepare
-// raises the kernel's dynamic-LDS limit (at plan creation, never inside a capture); *_launch only launches on `st`.  `who` names
-// the ABI entry in the argument error of the top-k launch.
+// The stem (Conv 7x7 s2 p3 + bias + ReLU + MaxPool 3x3 s2 p1 from planar fp32 frames read through a frame-index table, NHWC
+// out: `pooled` = [n_frames][Hp][Wp][64]), mean (tile partials in tile order / n; `rows` blocks of `channels` threads), head
+// (Linear: one thread per class, k in order) and top-k (rank counting, the first k ranks, 1 <= k <= classes) kernels of the clip
+// plans, defined in rva_clip.hip and shared by rva_clip3d.hip and rva_resnet.hip.  *_prepare raises the kernel's dynamic-LDS limit
+// (at plan creation, never inside a capture); *_launch only launches on `st`.  `who` names the ABI entry in the argument error
+// of the top-k launch.
+int rva_clip_stem_prepare(rva_ctx *ctx);
+int rva_clip_stem_launch(rva_ctx *ctx, const float *frames, const int32_t *frame_index, const float *w1, const float *b1, float *pooled,
+                         int H, int W, int n_frames, hipStream_t st);
 int rva_clip_mean_launch(rva_ctx *ctx, const float *partial, int tiles, float n, float *feat, int rows, int channels, hipStream_t st);
 int rva_clip_head_prepare(rva_ctx *ctx, int hidden);
 int rva_clip_head_launch(rva_ctx *ctx, const float *x, const float *wh, const float *bh, float *logits, int hidden, int classes,
                          int n_clips, hipStream_t st);
 int rva_clip_post_prepare(rva_ctx *ctx, int classes);
-int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, const int32_t *rows, int n_rows, int max_det,
-                         float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);
+int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, int k, const int32_t *rows, int n_rows,
+                         int max_det, float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);
 
 // The tail of every *_plan_stage tap: reports `count` through n_floats, and if dst is given checks its size and copies `count`
 // floats device to device on `st` -- as `rows` rows of row_floats out of a pitch of pitch_floats if rows > 0, else flat.

@@ -1,0 +1,352 @@
+// fp32 ResNet-18 classifier (classify.ResNet18: the reference's ResNet head, detector.py:870-1001) as one plan object:
+//
+//   per frame [3,H,W]: Conv 7x7 s2 p3 + BN + ReLU -> MaxPool 3x3 s2 p1 -> 8 BasicBlocks (64, 64, 128, 128, 256, 256, 512, 512; the
+//                      first block of the 128 / 256 / 512 stages has stride 2 and a 1x1 stride-2 shortcut convolution)
+//                      -> mean over H,W -> Linear(512 -> classes) -> top-k
+//
+// Everything is fp32 (BatchNorm is folded by the caller in float64 and rounded once); activations are NHWC.  The contracts are
+// those of rva_clip.hip: every sum runs in ONE fixed order that depends neither on the number of frames, nor on a frame's position
+// in the batch, nor on the tile shape, nor on the launch mode -- no split-K and no float atomics -- so logits are bit-identical
+// across batch sizes, batch rows, an index-table permutation of the frames, eager launches and hipGraph replay.  The launches of
+// one pass (rva_resnet_plan_run), all on the caller's stream:
+//
+//   K_stem   k_clip_stem of rva_clip.hip through rva_clip_stem_launch: conv1 + bias + ReLU + max pool from the planar frames
+//            (read through the device table of frame indices), NHWC out.
+//   K_conv   x 19: k_res_conv, the NHWC implicit GEMM of a block convolution on the exact fp32-input MFMA core of
+//            rva_mfma_f32.h (which defines the reduction order: what rva_conv2d_nhwc_f32_v runs on the same input).  Rows = output
+//            pixels of the whole batch, columns = output channels.  Per block: mid = ReLU(conv1(x) + b), [down = conv_d(x) + b],
+//            out = ReLU((conv2(mid) + b) + (down or x)).
+//   K_mean   k_res_mean: per image and channel the pixels in raster order from zero, then one division by h*w.
+//   K_head   Linear: the head kernel of rva_clip.hip (one thread per class, k in order), hidden = 512.
+//   K_post   (rva_resnet_plan_run_post) the top-k kernel of rva_clip.hip with the descriptor's k.
+//
+// Every stage keeps its own workspace buffer (rva_resnet_plan_stage reads them).
+#include "rva_internal.h"
+#include "rva_mfma_f32.h"
+
+namespace {
+
+constexpr int C_STEM = 64, C_FEAT = 512, N_BLOCKS = 8, N_CONVS = 19;
+constexpr int MAX_CLASSES = 16384;
+constexpr int EPI_RELU = 0, EPI_BIAS = 1, EPI_RES_RELU = 2;
+
+struct ResConvArgs {
+    const float *in;                 // [n][H][W][Cin]
+    const float *w;                  // [Cout][KS*KS][Cin]
+    const float *bias;               // [Cout]
+    const float *res;                // [n][Ho][Wo][Cout] (EPI_RES_RELU)
+    float *out;                      // [n][Ho][Wo][Cout]
+    int H, W, Ho, Wo, Cin, Cout, stride, epi;
+    long M;                          // n * Ho * Wo
+};
+
+// ---------------------------------------------------------------------------------------------------
+// K_conv.  MT x NT tiles of 32 x 32 per wave, WM x WN waves per block: block = 32 MT WM pixels x 32 NT WN channels (Cout is a
+// multiple of it: no column tail).  KS = 3 (pad 1) or 1 (pad 0).  Row p of the GEMM = pixel (p / (Ho Wo), (p / Wo) % Ho, p % Wo) of
+// the batch, so a tile may span two images; rows >= M read nothing and write nothing.  Reduction: taps in order, channels in
+// chunks of 32, f32_chunk's step order, from zero.  Epilogues: max(acc + bias, 0) | acc + bias | max((acc + bias) + res, 0).
+template <int MT, int NT, int WM, int WN, int KS>
+__global__ void __launch_bounds__(64 * WM * WN) k_res_conv(ResConvArgs a)
+{
+    constexpr int CK = 32, PAD = KS / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave % WM, wn = wave / WM;
+    const int r = lane & 31, h = lane >> 5;
+    const long m0 = ((long)blockIdx.x * WM + wm) * (32 * MT);
+    const int n0 = (blockIdx.y * WN + wn) * (32 * NT);
+
+    int pn[MT], py[MT], px[MT];
+    bool pv[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        long p = m0 + mt * 32 + r;
+        pv[mt] = p < a.M;
+        if (!pv[mt]) p = 0;
+        px[mt] = (int)(p % a.Wo);
+        py[mt] = (int)((p / a.Wo) % a.Ho);
+        pn[mt] = (int)(p / ((long)a.Wo * a.Ho));
+    }
+    const float *wrow[NT];
+    bool wv[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        wv[nt] = true;
+        wrow[nt] = a.w + (size_t)(n0 + nt * 32 + r) * (KS * KS) * a.Cin + (CK / 2) * h;
+    }
+    f32x16 acc[MT][NT] = {};
+    for (int tap = 0; tap < KS * KS; ++tap) {
+        const int ky = tap / KS, kx = tap - ky * KS;
+        const float *arow[MT];
+        bool av[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int iy = py[mt] * a.stride + ky - PAD, ix = px[mt] * a.stride + kx - PAD;
+            av[mt] = pv[mt] && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+            arow[mt] = a.in + ((size_t)((long)pn[mt] * a.H + (av[mt] ? iy : 0)) * a.W + (av[mt] ? ix : 0)) * a.Cin + (CK / 2) * h;
+        }
+        const size_t wtap = (size_t)tap * a.Cin;
+        for (int c = 0; c < a.Cin; c += CK) f32_chunk<MT, NT, CK>(acc, arow, av, c, wrow, wv, wtap + c);
+    }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int co = n0 + nt * 32 + r;
+        const float bias = a.bias[co];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const long p = m0 + mt * 32 + f32_cd_row(i, h);
+                if (p >= a.M) continue;
+                const size_t o = (size_t)p * a.Cout + co;
+                float v = acc[mt][nt][i] + bias;
+                if (a.epi == EPI_RES_RELU) v = v + a.res[o];
+                if (a.epi != EPI_BIAS) v = fmaxf(v, 0.f);
+                a.out[o] = v;
+            }
+        }
+    }
+}
+
+// The tile table: (MT, NT, WM, WN) -> block of (32 MT WM) pixels x (32 NT WN) channels, largest first.  The wide layers (many
+// rows) take the 2 x 2 tiles per wave (four accumulators, a quarter of the operand traffic per MFMA); the deep layers (few rows,
+// long K) take one tile per wave in small blocks so the grid still covers the device.
+struct ResTile { int mt, nt, wm, wn; };
+constexpr ResTile kResTiles[] = {
+    {2, 2, 4, 1},    // 0: 256 x 64
+    {1, 2, 4, 1},    // 1: 128 x 64
+    {1, 1, 2, 2},    // 2: 64 x 64
+    {1, 1, 1, 2},    // 3: 32 x 64
+};
+constexpr int kNumResTiles = (int)(sizeof kResTiles / sizeof kResTiles[0]);
+
+dim3 res_grid(int v, long M, int Cout)
+{
+    const ResTile &t = kResTiles[v];
+    return dim3((unsigned)((M + 32L * t.mt * t.wm - 1) / (32L * t.mt * t.wm)), (unsigned)(Cout / (32 * t.nt * t.wn)));
+}
+
+// the largest tile that still gives every CU a block, else the smallest
+int res_tile_for(long M, int Cout, int num_cus)
+{
+    const long want = num_cus > 0 ? num_cus : 256;
+    for (int v = 0; v < kNumResTiles; ++v) {
+        const dim3 g = res_grid(v, M, Cout);
+        if ((long)g.x * g.y >= want) return v;
+    }
+    return kNumResTiles - 1;
+}
+
+template <int KS>
+void launch_res_conv(int v, dim3 g, hipStream_t st, const ResConvArgs &a)
+{
+    switch (v) {
+    case 0: k_res_conv<2, 2, 4, 1, KS><<<g, 256, 0, st>>>(a); break;
+    case 1: k_res_conv<1, 2, 4, 1, KS><<<g, 256, 0, st>>>(a); break;
+    case 2: k_res_conv<1, 1, 2, 2, KS><<<g, 256, 0, st>>>(a); break;
+    default: k_res_conv<1, 1, 1, 2, KS><<<g, 128, 0, st>>>(a); break;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// K_mean.  Block = image, thread = channel (512): feat[img][c] = (sum of the image's P pixels in raster order, from zero) / P.
+__global__ void __launch_bounds__(C_FEAT) k_res_mean(const float *x, int P, float *feat)
+{
+    const int img = blockIdx.x, c = threadIdx.x;
+    const float *xp = x + (size_t)img * P * C_FEAT + c;
+    float s = 0.f;
+    for (int p = 0; p < P; ++p) s = s + xp[(size_t)p * C_FEAT];
+    feat[(size_t)img * C_FEAT + c] = s / (float)P;
+}
+
+struct ResLayer {                    // one block convolution of the plan
+    int cin, cout, k, stride, H, W, Ho, Wo, epi;
+    float *w = nullptr, *b = nullptr;
+    const float *in = nullptr, *res = nullptr;
+    float *out = nullptr;
+};
+
+}  // namespace
+
+struct rva_resnet_plan {
+    rva_ctx *ctx = nullptr;
+    rva_resnet_desc d{};
+    int k = 0;                                             // min(top_k, classes)
+    int maps[5][2] = {};                                   // (h, w) of the pooled map and of the four stages
+    float *ws = nullptr, *bs = nullptr, *wh = nullptr, *bh = nullptr;
+    float *pooled = nullptr, *mid[N_BLOCKS] = {}, *down[N_BLOCKS] = {}, *outb[N_BLOCKS] = {}, *feat = nullptr;
+    ResLayer conv[N_CONVS];                                // in launch order: per block conv1, [shortcut], conv2
+    int n_convs = 0;
+    size_t workspace_bytes = 0;
+    rva_dev_arena mem;
+};
+
+extern "C" {
+
+int rva_resnet_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *wt, rva_resnet_plan **out)
+{
+    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: null argument");
+    *out = nullptr;
+    const rva_resnet_desc d = *desc;
+    if (d.height < 1 || d.width < 1 || d.classes < 1 || d.classes > MAX_CLASSES || d.top_k < 1 || d.max_frames < 1 ||
+        d.max_frames > 65535 || (int64_t)d.height * d.width > (1 << 26))
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, "
+                        "max_frames 1..65535)", MAX_CLASSES);
+    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
+    for (int i = 0; i < N_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
+    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: every weight array is required");
+    auto *p = new rva_resnet_plan();
+    p->ctx = ctx;
+    p->d = d;
+    p->k = std::min(d.top_k, d.classes);
+    auto half = [](int n, int k, int pad) { return (n + 2 * pad - k) / 2 + 1; };
+    p->maps[0][0] = half(half(d.height, 7, 3), 3, 1);
+    p->maps[0][1] = half(half(d.width, 7, 3), 3, 1);
+    p->maps[1][0] = p->maps[0][0]; p->maps[1][1] = p->maps[0][1];
+    for (int s = 2; s <= 4; ++s) { p->maps[s][0] = half(p->maps[s - 1][0], 3, 1); p->maps[s][1] = half(p->maps[s - 1][1], 3, 1); }
+    const size_t mf = (size_t)d.max_frames;
+    // sizes first: the workspace must fit before anything is allocated
+    size_t n_act = mf * p->maps[0][0] * p->maps[0][1] * C_STEM + mf * C_FEAT, n_w = (size_t)C_STEM * 147 + C_STEM + (size_t)d.classes * (C_FEAT + 1);
+    for (int b = 0; b < N_BLOCKS; ++b) {
+        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c;
+        const size_t px = mf * p->maps[s][0] * p->maps[s][1] * c;
+        n_act += px * (cin != c ? 3 : 2);
+        n_w += (size_t)c * 9 * cin + (size_t)c * 9 * c + 2 * c + (cin != c ? (size_t)c * cin + c : 0);
+    }
+    p->workspace_bytes = n_act * sizeof(float);
+    const size_t need = (n_act + n_w) * sizeof(float);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
+        delete p;
+        return rva_fail(ctx, RVA_ERR_CAPACITY, "rva_resnet_plan_create: the workspace for %d frames of %d x %d needs %zu MB, the "
+                        "device has %zu MB free", d.max_frames, d.height, d.width, need >> 20, free_b >> 20);
+    }
+    int rc = RVA_OK;
+    auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
+    step(p->mem.upload(ctx, &p->ws, wt->stem_w, (size_t)C_STEM * 147));
+    step(p->mem.upload(ctx, &p->bs, wt->stem_b, C_STEM));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * C_FEAT));
+    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
+    step(p->mem.alloc(ctx, &p->pooled, mf * p->maps[0][0] * p->maps[0][1] * C_STEM));
+    step(p->mem.alloc(ctx, &p->feat, mf * C_FEAT));
+    const float *x = p->pooled;
+    int wi = 0, hin = p->maps[0][0], win = p->maps[0][1];
+    for (int b = 0; b < N_BLOCKS; ++b) {
+        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c, stride = cin != c ? 2 : 1;
+        const int ho = p->maps[s][0], wo = p->maps[s][1];
+        const size_t px = mf * ho * wo * c;
+        step(p->mem.alloc(ctx, &p->mid[b], px));
+        step(p->mem.alloc(ctx, &p->outb[b], px));
+        if (cin != c) step(p->mem.alloc(ctx, &p->down[b], px));
+        // the ABI's weight order of a block: conv1, conv2, then the shortcut
+        float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *wd = nullptr, *bd = nullptr;
+        step(p->mem.upload(ctx, &w1, wt->conv[wi].w, (size_t)c * 9 * cin));
+        step(p->mem.upload(ctx, &b1, wt->conv[wi].b, c));
+        step(p->mem.upload(ctx, &w2, wt->conv[wi + 1].w, (size_t)c * 9 * c));
+        step(p->mem.upload(ctx, &b2, wt->conv[wi + 1].b, c));
+        wi += 2;
+        if (cin != c) {
+            step(p->mem.upload(ctx, &wd, wt->conv[wi].w, (size_t)c * cin));
+            step(p->mem.upload(ctx, &bd, wt->conv[wi].b, c));
+            ++wi;
+        }
+        ResLayer l1{cin, c, 3, stride, hin, win, ho, wo, EPI_RELU};
+        l1.w = w1; l1.b = b1; l1.in = x; l1.out = p->mid[b];
+        p->conv[p->n_convs++] = l1;
+        if (cin != c) {
+            ResLayer ld{cin, c, 1, 2, hin, win, ho, wo, EPI_BIAS};
+            ld.w = wd; ld.b = bd; ld.in = x; ld.out = p->down[b];
+            p->conv[p->n_convs++] = ld;
+        }
+        ResLayer l2{c, c, 3, 1, ho, wo, ho, wo, EPI_RES_RELU};
+        l2.w = w2; l2.b = b2; l2.in = p->mid[b]; l2.res = cin != c ? p->down[b] : x; l2.out = p->outb[b];
+        p->conv[p->n_convs++] = l2;
+        x = p->outb[b];
+        hin = ho; win = wo;
+    }
+    if (rc == RVA_OK) rc = rva_clip_stem_prepare(ctx);
+    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, C_FEAT);
+    if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
+    if (rc != RVA_OK) {
+        rva_resnet_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return RVA_OK;
+}
+
+void rva_resnet_plan_destroy(rva_resnet_plan *p)
+{
+    if (!p) return;
+    p->mem.release();
+    delete p;
+}
+
+int rva_resnet_plan_info(const rva_resnet_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
+{
+    if (!p) return RVA_ERR_ARG;
+    if (maps)
+        for (int s = 0; s < 5; ++s) { maps[2 * s] = p->maps[s][0]; maps[2 * s + 1] = p->maps[s][1]; }
+    if (workspace_bytes) *workspace_bytes = (int64_t)p->workspace_bytes;
+    if (n_launches) *n_launches = 1 + N_CONVS + 2;
+    return RVA_OK;
+}
+
+int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+    const hipStream_t st = (hipStream_t)stream_;
+    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->ws, p->bs, p->pooled, p->d.height, p->d.width, n, st);
+    if (rc != RVA_OK) return rc;
+    const int cus = rva_num_cus(ctx);
+    for (int i = 0; i < p->n_convs; ++i) {
+        const ResLayer &l = p->conv[i];
+        ResConvArgs a{};
+        a.in = l.in; a.w = l.w; a.bias = l.b; a.res = l.res; a.out = l.out;
+        a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
+        a.M = (long)n * l.Ho * l.Wo;
+        const int v = res_tile_for(a.M, l.cout, cus);
+        const dim3 g = res_grid(v, a.M, l.cout);
+        if (l.k == 3) launch_res_conv<3>(v, g, st, a);
+        else launch_res_conv<1>(v, g, st, a);
+        RVA_HIP(ctx, hipGetLastError());
+    }
+    k_res_mean<<<n, C_FEAT, 0, st>>>(p->outb[N_BLOCKS - 1], p->maps[4][0] * p->maps[4][1], p->feat);
+    RVA_HIP(ctx, hipGetLastError());
+    return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C_FEAT, p->d.classes, n, st);
+}
+
+int rva_resnet_plan_run_post(rva_resnet_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
+                             void *cls, void *boxes, void *counts, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    return rva_clip_post_launch(p->ctx, "rva_resnet_plan_run_post", (const float *)logits, p->d.classes, p->k, rows, n_rows, max_det,
+                                (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
+}
+
+// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is frame-major NHWC.
+int rva_resnet_plan_stage(rva_resnet_plan *p, int stage, int n, void *dst, int64_t dst_floats, int64_t *n_floats, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (n < 1 || n > p->d.max_frames)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+    const float *src = nullptr;
+    int64_t count = 0;
+    auto block = [&](float *const *bufs, int b) {
+        const int s = 1 + b / 2;
+        src = bufs[b];
+        count = (int64_t)n * p->maps[s][0] * p->maps[s][1] * (C_STEM << (s - 1));
+    };
+    if (stage == RVA_RESNET_STAGE_POOLED) { src = p->pooled; count = (int64_t)n * p->maps[0][0] * p->maps[0][1] * C_STEM; }
+    else if (stage >= RVA_RESNET_STAGE_MID0 && stage < RVA_RESNET_STAGE_MID0 + N_BLOCKS) block(p->mid, stage - RVA_RESNET_STAGE_MID0);
+    else if (stage >= RVA_RESNET_STAGE_DOWN2 && stage <= RVA_RESNET_STAGE_DOWN6) block(p->down, 2 * (stage - RVA_RESNET_STAGE_DOWN2) + 2);
+    else if (stage >= RVA_RESNET_STAGE_OUT0 && stage < RVA_RESNET_STAGE_OUT0 + N_BLOCKS) block(p->outb, stage - RVA_RESNET_STAGE_OUT0);
+    else if (stage == RVA_RESNET_STAGE_FEAT) { src = p->feat; count = (int64_t)n * C_FEAT; }
+    else return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: unknown stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_resnet_plan_stage", stage, n, src, count, 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
+}
+
+}  // extern "C"

@@ -1,0 +1,171 @@
+"""fp32 ResNet-18 plan: a thin caller of ``rva_resnet_plan_*`` (include/rva.h, kernels in ``csrc/rva_resnet.hip``).
+
+The whole network of :class:`classify.ResNet18` -- the 7x7 stem with its max pool, the eight BasicBlocks with their three
+shortcut convolutions, the spatial mean, the linear head -- and the top-k of the ResNet head run as librva kernels that read
+planar fp32 frames (what K1 writes) through a device table of frame indices.  What stays here:
+
+  * :func:`pack_resnet18`: the module's tensors in the ABI's order and layouts, every BatchNorm folded in float64 and rounded
+    once to fp32;
+  * :func:`resnet_flops`: the FLOP count per layer (tools/resnet_plan_report.py);
+  * :class:`FusedResNet18`: owns one plan (weights and the workspace for ``max_frames`` frames) and its logits buffer.
+
+``hip_engine: plan`` with ``model_type: resnet`` selects it (:class:`classify.HipResNetDetector`, engine ``"resnet-f32"``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .clip_plan import _ClipPlan, _fold, conv_out
+
+ENGINE = "resnet-f32"        # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
+
+WIDTHS = (64, 128, 256, 512)
+# launch-order names of the 19 block convolutions' outputs = the taps of rva_resnet_plan_stage
+STAGE_CODES = {"pooled": 0, **{f"mid{b}": 1 + b for b in range(8)}, "down2": 9, "down4": 10, "down6": 11,
+               **{f"out{b}": 12 + b for b in range(8)}, "feat": 20}
+
+
+def block_shapes() -> List[Tuple[int, int, int]]:
+    """(cin, cout, stride) of the eight BasicBlocks."""
+    out, cin = [], 64
+    for i, c in enumerate(WIDTHS):
+        out += [(cin, c, 1 if i == 0 else 2), (c, c, 1)]
+        cin = c
+    return out
+
+
+def resnet_maps(h: int, w: int) -> List[Tuple[int, int]]:
+    """(height, width) of the pooled map and of the four stages' maps."""
+    m = [(conv_out(conv_out(h, 7, 2, 3), 3, 2, 1), conv_out(conv_out(w, 7, 2, 3), 3, 2, 1))]
+    m.append(m[0])
+    for _ in range(3):
+        m.append((conv_out(m[-1][0], 3, 2, 1), conv_out(m[-1][1], 3, 2, 1)))
+    return m
+
+
+def resnet_flops(h: int, w: int, classes: int = 1000) -> Dict[str, object]:
+    """FLOP (multiply + add = 2) of one frame from the shapes alone: ``stem``, ``convs`` (the 19 block convolutions as ``(name,
+    flop, rows per frame, K, Cout)`` in launch order), ``head``, ``frame`` (everything) and the activation floats a frame
+    leaves in the plan's workspace."""
+    hc, wc = conv_out(h, 7, 2, 3), conv_out(w, 7, 2, 3)
+    maps = resnet_maps(h, w)
+    stem = 2.0 * hc * wc * 64 * 147
+    convs, act = [], maps[0][0] * maps[0][1] * 64 + 512
+    for b, (cin, c, stride) in enumerate(block_shapes()):
+        ho, wo = maps[1 + b // 2]
+        px = ho * wo
+        convs.append((f"mid{b}", 2.0 * px * c * 9 * cin, px, 9 * cin, c))
+        if cin != c:
+            convs.append((f"down{b}", 2.0 * px * c * cin, px, cin, c))
+        convs.append((f"out{b}", 2.0 * px * c * 9 * c, px, 9 * c, c))
+        act += px * c * (3 if cin != c else 2)
+    head = 2.0 * 512 * classes
+    return {"stem": stem, "convs": convs, "head": head, "frame": stem + sum(c[1] for c in convs) + head,
+            "workspace_floats": act, "frame_bytes": 4.0 * 3 * h * w}
+
+
+def _is_resnet18(net) -> bool:
+    nn = torch.nn
+    stem, layers, fc = getattr(net, "stem", None), getattr(net, "layers", None), getattr(net, "fc", None)
+    if not (isinstance(stem, nn.Sequential) and len(stem) == 4 and isinstance(layers, nn.Sequential) and len(layers) == 8 and
+            isinstance(fc, nn.Linear) and fc.in_features == 512):
+        return False
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)  # noqa: E731
+
+    def conv_is(c, cin, cout, k, s, p):
+        return isinstance(c, nn.Conv2d) and (c.in_channels, c.out_channels) == (cin, cout) and c.kernel_size == (k, k) and \
+            c.stride == (s, s) and c.padding == (p, p) and c.dilation == (1, 1) and c.groups == 1
+
+    bn_is = lambda m, c: isinstance(m, nn.BatchNorm2d) and m.num_features == c and m.track_running_stats  # noqa: E731
+    pool = stem[3]
+    if not (conv_is(stem[0], 3, 64, 7, 2, 3) and bn_is(stem[1], 64) and isinstance(stem[2], nn.ReLU) and
+            isinstance(pool, nn.MaxPool2d) and pair(pool.kernel_size) == (3, 3) and pair(pool.stride) == (2, 2) and
+            pair(pool.padding) == (1, 1) and pair(pool.dilation) == (1, 1) and not pool.ceil_mode):
+        return False
+    for blk, (cin, c, s) in zip(layers, block_shapes()):
+        if not all(hasattr(blk, a) for a in ("c1", "b1", "c2", "b2", "down")):
+            return False
+        if not (conv_is(blk.c1, cin, c, 3, s, 1) and bn_is(blk.b1, c) and conv_is(blk.c2, c, c, 3, 1, 1) and bn_is(blk.b2, c)):
+            return False
+        if cin != c:
+            d = blk.down
+            if not (isinstance(d, nn.Sequential) and len(d) == 2 and conv_is(d[0], cin, c, 1, 2, 0) and bn_is(d[1], c)):
+                return False
+        elif blk.down is not None:
+            return False
+    return True
+
+
+def pack_resnet18(net) -> Dict[str, np.ndarray]:
+    """The ``rva_resnet_weights`` arrays of a :class:`classify.ResNet18` (``N.ResNetWeights.NAMES`` order), contiguous fp32, each
+    convolution with its BatchNorm folded in float64 and rounded once, in the layouts the kernels read:
+
+      * ``stem_w`` ``[64, 3, 7, 7]`` (the module's own layout: the VALU stem keeps a channel's 147 taps in registers);
+      * ``c<i>_w`` ``[Cout, k*k, Cin]`` with ``tap = ky*k + kx`` (channels innermost, as the NHWC activations), ``c<i>_b``
+        ``[Cout]``; per block conv1, conv2, then its shortcut where it has one (``c6``, ``c11``, ``c16``);
+      * ``head_w`` ``[classes, 512]``, ``head_b`` ``[classes]``."""
+    if not _is_resnet18(net):
+        raise ValueError("pack_resnet18: not the ResNet18 architecture")
+    taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)  # noqa: E731  [co,ci,kk] -> [co,kk,ci]
+    out = {}
+    out["stem_w"], out["stem_b"] = _fold(net.stem[0], net.stem[1])
+    i = 0
+    for blk in net.layers:
+        pairs = [(blk.c1, blk.b1), (blk.c2, blk.b2)] + ([(blk.down[0], blk.down[1])] if blk.down is not None else [])
+        for conv, bn in pairs:
+            w, b = _fold(conv, bn)
+            out[f"c{i}_w"], out[f"c{i}_b"] = taps_last(w), b
+            i += 1
+    fc = net.fc
+    out["head_w"] = fc.weight.detach().float().cpu().numpy()
+    out["head_b"] = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
+    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in N.ResNetWeights.NAMES}
+
+
+class FusedResNet18(_ClipPlan):
+    """One ``rva_resnet_plan``: the fp32 network of ``net`` (a :class:`classify.ResNet18`) for frames of ``hw``, up to
+    ``max_frames`` frames per call, with the top ``top_k`` in :meth:`post`.  The surface of the clip plans with ``T = 1``
+    (``max_clips`` = frames, ``classes``, ``logits``, ``run``, ``post``, ``stage``, ``__call__``).  No host synchronisation and
+    no allocation after construction (capturable)."""
+
+    ABI = "rva_resnet_plan"
+
+    def __init__(self, net, hw: Tuple[int, int], max_frames: int, top_k: int = 5, ctx: Optional[N.Context] = None,
+                 device: Optional[torch.device] = None):
+        packed = pack_resnet18(net)                                 # a wrong architecture is refused before the device is touched
+        self._open(hw, 1, max_frames, net.fc.out_features, ctx, device)
+        self.top_k = int(top_k)
+        self.k = min(self.top_k, self.classes)
+        self._create(N.ResNetDesc(self.H, self.W, self.classes, self.top_k, self.max_clips), N.ResNetWeights, packed)
+        maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
+        self.ctx.check(self.L.rva_resnet_plan_info(self.handle, maps, C.byref(ws), C.byref(nl)), "rva_resnet_plan_info")
+        self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
+        self.workspace_bytes, self.n_launches = ws.value, nl.value
+
+    def stage_shape(self, name: str, n: int) -> tuple:
+        if name == "feat":
+            return (n, 512)
+        if name == "pooled":
+            return (n, *self.maps[0], 64)
+        b = int(name[-1])
+        return (n, *self.maps[1 + b // 2], WIDTHS[b // 2])
+
+    def stage(self, name: str, n: int) -> torch.Tensor:
+        """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n`` frames, on the current stream), NHWC, as
+        ``rva_resnet_plan_stage`` documents (include/rva.h): ``"pooled"``, ``"mid0"`` .. ``"mid7"``, ``"down2"`` / ``"down4"``
+        / ``"down6"``, ``"out0"`` .. ``"out7"``, ``"feat"`` ``[n, 512]``.  A read-only tap for tests and tools."""
+        n = int(n)
+        stages = {k: (code, self.stage_shape(k, n)) for k, code in STAGE_CODES.items()}
+        return self._tap(stages, name, n)
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """``ResNet18.forward`` of frames ``[B, 3, H, W]`` fp32: a fresh ``[B, classes]`` tensor."""
+        b = int(frames.shape[0])
+        if tuple(frames.shape[1:]) != (3, self.H, self.W):
+            raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
+        return self._run_frames(frames.contiguous(), b)
