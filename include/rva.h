@@ -322,6 +322,18 @@ int rva_conv2d_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weigh
 int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias,
                           void *out, int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin,
                           int Cout, int ksize, int stride, int act, int variant, rva_stream_t stream);
+/* Same restricted to the output rows [y0, y1) of every image (y1 < 0 = up to the last row): only those rows are computed and
+ * written, bit-identical to the whole launch; input rows are read wherever the window's receptive field lies and zero padding
+ * is decided in the whole image.  The LDS-DMA gather variants (33..42, 64, 65, 74..79; variant 0 where it picks one: 1x1 and
+ * 3x3 stride 2 with Cin % 64 == 0) and the patch variants (43..51, 61..63, 66) take a window; RVA_ERR_ARG for any other
+ * variant unless the window is the whole image. */
+int rva_conv2d_nhwc_f16_rows(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias,
+                             void *out, int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin,
+                             int Cout, int ksize, int stride, int act, int variant, int y0, int y1, rva_stream_t stream);
+/* Rows of a convolution's output that depend on the input rows [lo, hi) of an image H_in rows high (host only; k = 1 or 3,
+ * pad k / 2, stride 1 or 2): the half-open window [*out_lo, *out_hi), clamped to the output.  Every output row outside it sees
+ * only input rows outside [lo, hi) and zero padding.  RVA_ERR_ARG for a window outside [0, H_in] or lo >= hi. */
+int rva_conv_rows_through(int k, int stride, int H_in, int lo, int hi, int32_t *out_lo, int32_t *out_hi);
 /* 1x1 convolution whose input is torch.cat([nearest-2x-upsample(low), skip], channel) -- the FPN pattern -- without
  * materialising either the upsampled tensor or the concatenation: low is [batch, H/2, W/2, c_low], skip is
  * [batch, H, W, c_skip] (row strides ld_low / ld_skip), weights [rva_conv_cout_pad(Cout)][1][c_low + c_skip].
@@ -363,6 +375,9 @@ int rva_c2f_pair32_f16(rva_ctx *ctx, const void *in, int ldi, const void *w1, co
  * order inside the stem's 27-tap dot product. */
 int rva_stem2_f16(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
                   void *out, int ldo, int batch, int H, int W, rva_stream_t stream);
+/* Same for the rows [y0, y1) of the quarter-resolution output only (y1 < 0 = up to the last row), bit-identical to them */
+int rva_stem2_f16_rows(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
+                       void *out, int ldo, int batch, int H, int W, int y0, int y1, rva_stream_t stream);
 
 /* SPPF's three chained 5x5/1 max pools in one launch: out1 = pool5(in), out2 = pool5(out1) = pool9(in),
  * out3 = pool5(out2) = pool13(in) (stride 1, -inf padding), all three with row stride ldo.  H*W*64 bytes must fit LDS
@@ -454,6 +469,17 @@ int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void 
  *   multiple of 256) by float boxes32[batch, 4, anchors] = cx, cy, w, h in input pixels, with (half)boxes32 == rows 0-3.  Feed
  *   both to rva_postprocess_boxes_batch.  Same launches, same kernel selection, still no allocation and no synchronisation.
  *   Without the flag boxes_offset is -1 and total_bytes is the size of the head tensor.
+ * Static rows (fp16 plans): rva_yolov8_plan_set_static_rows(plan, top, bottom) is the caller's promise that the rows outside
+ *   [top, bottom) of every image of `input` hold the same bytes on every later run until the next call (a letterbox border).
+ *   Every step then carries the window of its output rows that depend on [top, bottom) (rva_conv_rows_through chained through
+ *   the graph, _step_rows reads it); the other rows come out the same on every run.  The call, like create and _set_variant,
+ *   leaves the plan unprimed: the next complete run (_run / _run_lanes, not under stream capture) launches every step over all
+ *   rows and primes it, and from then on the steps whose kernel takes a row window (rva_conv2d_nhwc_f16_rows,
+ *   rva_stem2_f16_rows) launch their window only.  Steps of other kernels keep running all rows.  _run_range never primes and
+ *   launches windows only on a primed plan; a run under stream capture launches by the flag as it stands and leaves it alone.
+ *   (0, height) switches windowing off (the default).  RVA_ERR_ARG for a window outside [0, height] or top >= bottom.  fp32
+ *   plans accept the call and stay un-windowed.  RVA_PLAN_NO_STATIC_ROWS=1 in the environment makes the call a no-op (A/B).
+ *   _tunable_desc carries a window that is not the whole image (" r[y0,y1)"): such layers are tuned, and persisted, apart.
  * -------------------------------------------------------------------------------------------- */
 #define RVA_PLAN_NO_STEM2 1   /* rva_yolov8_desc.flags: stem and first downsampling convolution as two launches (A/B switch) */
 #define RVA_PLAN_NO_CIN_PAD 2 /* ... convolutions with Cin % 32 != 0 keep their Cin (default: declared rounded up to 32, zero weights) */
@@ -488,6 +514,8 @@ int rva_yolov8_plan_tunable_desc(const rva_yolov8_plan *plan, int index, char *b
 int rva_yolov8_plan_launch_tunable(rva_yolov8_plan *plan, int index, int variant, void *output, rva_stream_t stream);
 int rva_yolov8_plan_set_variant(rva_yolov8_plan *plan, int index, int variant);
 int rva_yolov8_plan_get_variant(const rva_yolov8_plan *plan, int index);
+int rva_yolov8_plan_set_static_rows(rva_yolov8_plan *plan, int top, int bottom);
+int rva_yolov8_plan_step_rows(const rva_yolov8_plan *plan, int step, int32_t *y0, int32_t *y1);
 
 /* ----------------------------------------------------------------------------------------------
  * The CNN-LSTM clip network as ONE fp32 object -- replaces the network call of the reference's CNN-LSTM head

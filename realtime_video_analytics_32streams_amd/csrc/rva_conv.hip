@@ -59,6 +59,9 @@ struct ConvArgs {
     const __half *in2; int ldi2, c_split;   // k_conv_gbig<..., UP>: `in` = low-res tensor (nearest 2x upsampled on the fly,
                                             // channels [0, c_split)), `in2` = full-res tensor (channels [c_split, Cin))
     int H, W, Cin, CinPad, Ho, Wo, Cout, stride, M, act, n_tiles, m_tiles;   // CinPad = Cin rounded up to 32 (weight rows are zero-padded)
+    // k_conv_gbig, output row window [wy0, wy0 + wrows) of every image (rva_conv2d_nhwc_f16_rows): M counts the window's pixels
+    // only, raster position m decodes to row wy0 + (m % (wrows * Wo)) / Wo.  The whole image: wy0 = 0, wrows = Ho.
+    int wy0, wrows;
 };
 
 // Timing-only ablation switches (skip the MFMA phase / the prefetch loads / the epilogue) exist in the private diagnostic
@@ -2253,7 +2256,7 @@ __global__ void __launch_bounds__(512)
     const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);
     if (m_tile >= a.m_tiles) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
-    const int HoWo = a.Ho * a.Wo;
+    const int HoWo = a.wrows * a.Wo;                               // raster positions per image: the row window's pixels
     const int cpt = a.Cin / BK;
     const int nsteps = TAPS * cpt;
     const int wrow = TAPS * a.Cin;
@@ -2277,7 +2280,7 @@ __global__ void __launch_bounds__(512)
         avm[k] = 0;
         if (UP) actr2[k] = (unsigned)(c8 * 2);
         if (wv + 8 * k < APIECES && m < a.M) {
-            const int b = div_s(m, HoWo, inv_howo), rem = m - b * HoWo, oy = div_s(rem, a.Wo, inv_wo), ox = rem - oy * a.Wo;
+            const int b = div_s(m, HoWo, inv_howo), rem = m - b * HoWo, oyw = div_s(rem, a.Wo, inv_wo), ox = rem - oyw * a.Wo, oy = oyw + a.wy0;
             const int iy0 = oy * a.stride - PAD, ix0 = ox * a.stride - PAD;
             const unsigned pix = (unsigned)((b * a.H + iy0 + PAD) * a.W + ix0 + PAD);
             actr[k] = pix * (unsigned)((UP ? a.ldi2 : a.ldi) * 2) + (unsigned)(c8 * 2);
@@ -2361,7 +2364,7 @@ __global__ void __launch_bounds__(512)
         if (KS == 3) {
             const int m = P0 + wm * TM + 16 * j + (lane & 15);
             if (m < a.M) {
-                const int b = div_s(m, HoWo, inv_howo), rem = m - b * HoWo, oy = div_s(rem, a.Wo, inv_wo), ox = rem - oy * a.Wo;
+                const int b = div_s(m, HoWo, inv_howo), rem = m - b * HoWo, oyw = div_s(rem, a.Wo, inv_wo), ox = rem - oyw * a.Wo, oy = oyw + a.wy0;
                 const int iy0 = oy * a.stride - 1, ix0 = ox * a.stride - 1;
                 const int vy = ((unsigned)iy0 < (unsigned)a.H ? 1 : 0) | ((unsigned)(iy0 + 1) < (unsigned)a.H ? 2 : 0) | ((unsigned)(iy0 + 2) < (unsigned)a.H ? 4 : 0);
                 const int vx = ((unsigned)ix0 < (unsigned)a.W ? 1 : 0) | ((unsigned)(ix0 + 1) < (unsigned)a.W ? 2 : 0) | ((unsigned)(ix0 + 2) < (unsigned)a.W ? 4 : 0);
@@ -2492,12 +2495,15 @@ __global__ void __launch_bounds__(512)
         return;
     }
     constexpr int CPR = BN / 8;
+    const int wskip = (a.Ho - a.wrows) * a.Wo;                     // output pixels of an image outside the row window (uniform; 0 = whole image)
 #pragma unroll 4
     for (int q = tid; q < BM * CPR; q += 512) {
         const int row = q / CPR, pc = q - row * CPR;
         const int co = n0 + pc * 8;
-        const int m = P0 + row;
-        if (m < a.M && co < a.Cout) {
+        const int mw = P0 + row;
+        if (mw < a.M && co < a.Cout) {
+            // pixel index in the whole output raster: the window's rows of image b start at (b * Ho + wy0) * Wo
+            const int m = wskip ? mw + div_s(mw, HoWo, inv_howo) * wskip + a.wy0 * a.Wo : mw;
             uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
             if (a.res) {
                 const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
@@ -2524,7 +2530,7 @@ hipError_t launch_gbig1(ConvArgs &a, hipStream_t s)
     if (hipError_t e = rva_func_smem((const void *)k_conv_gbig<BM, BN, WGM, WGN, NSLOT, KS, BK, UP, HEAD, SUB>, smem); e != hipSuccess) return e;
     a.n_tiles = rva_ceil_div(a.Cout, BN);
     // LDS-DMA addresses are a 64-bit scalar base + a 32-bit per-lane byte offset
-    if ((size_t)a.H * a.W * (size_t)(a.M / (a.Ho * a.Wo) + 1) * (UP ? a.ldi2 : a.ldi) * 2 >= (1ull << 32) ||
+    if ((size_t)a.H * a.W * (size_t)(a.M / (a.wrows * a.Wo) + 1) * (UP ? a.ldi2 : a.ldi) * 2 >= (1ull << 32) ||
         (size_t)a.CoutPad * KS * KS * a.Cin * 2 >= (1ull << 32))
         return hipErrorInvalidValue;
     if (a.M >= (1 << 24)) return hipErrorInvalidValue;             // div_s: raster positions below 2^24
@@ -2555,6 +2561,7 @@ struct S2Args {
     __half *out; int ldo;
     const __half *res; int ldr;
     int B, H, W, Ho, Wo, Cout, CoutPad, act, tiles_x, tiles_y, total, n_tiles;
+    int y0, y1;               // output row window: tile row ty covers rows y0 + ty * TH .., rows >= y1 are not written
 };
 
 template <int STRIDE, int CIN, int CO, int NWV, int NBUF, int RPW = 1>
@@ -2622,7 +2629,7 @@ __global__ void __launch_bounds__(NWV * 64) k_conv3_patch(S2Args a)
     }
     auto issue_patch = [&](int t, int pb) {
         const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-        const int iy_base = STRIDE * ty * TH - 1, ix_base = STRIDE * tx * TW - 1;
+        const int iy_base = STRIDE * (a.y0 + ty * TH) - 1, ix_base = STRIDE * tx * TW - 1;
         __half *dst = patch0 + (size_t)pb * PPIECES * 512;
         const int img = b * a.H;
 #pragma unroll
@@ -2663,10 +2670,10 @@ __global__ void __launch_bounds__(NWV * 64) k_conv3_patch(S2Args a)
         int vm[FMW];
 #pragma unroll
         for (int j = 0; j < FMW; ++j) {
-            const int oy = ty * TH + wv * RPW + (j >> 1);
+            const int oy = a.y0 + ty * TH + wv * RPW + (j >> 1);
             const int ox = tx * TW + 16 * (j & 1) + (lane & 15);
             int m = 0;
-            if (oy < a.Ho && ox < a.Wo) {
+            if (oy < a.y1 && ox < a.Wo) {
 #pragma unroll
                 for (int tp = 0; tp < 9; ++tp)
                     if ((unsigned)(STRIDE * oy - 1 + tp / 3) < (unsigned)a.H && (unsigned)(STRIDE * ox - 1 + tp % 3) < (unsigned)a.W) m |= 1 << tp;
@@ -2726,8 +2733,8 @@ __global__ void __launch_bounds__(NWV * 64) k_conv3_patch(S2Args a)
         const int cpr = min(CO, a.Cout - n0) >> 3;
         for (int q = tid; q < TH * TW * cpr; q += NT) {
             const int px = q / cpr, pc = q - px * cpr;
-            const int yy = ty * TH + px / TW, xx = tx * TW + px % TW;
-            if (yy < a.Ho && xx < a.Wo) {
+            const int yy = a.y0 + ty * TH + px / TW, xx = tx * TW + px % TW;
+            if (yy < a.y1 && xx < a.Wo) {
                 uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)px * SROW + pc * 8);
                 const size_t m = (size_t)(b * a.Ho + yy) * a.Wo + xx;
                 if (a.res) {
@@ -2758,7 +2765,7 @@ hipError_t launch_patch(S2Args &g, int num_cus, hipStream_t s)
     static_assert(smem <= 160 * 1024, "LDS budget");   // 163,840 B per CU
     constexpr int per_cu = smem <= 32 * 1024 ? 4 : smem <= 53 * 1024 ? 3 : smem <= 80 * 1024 ? 2 : 1;
     if (hipError_t e = rva_func_smem((const void *)k_conv3_patch<STRIDE, CIN, CO, NWV, NBUF, RPW>, smem); e != hipSuccess) return e;
-    g.tiles_x = rva_ceil_div(g.Wo, 32); g.tiles_y = rva_ceil_div(g.Ho, TH);
+    g.tiles_x = rva_ceil_div(g.Wo, 32); g.tiles_y = rva_ceil_div(g.y1 - g.y0, TH);
     g.total = g.tiles_x * g.tiles_y * g.B;
     g.n_tiles = rva_ceil_div(g.Cout, CO);
     int per_n = per_cu * num_cus / g.n_tiles;                  // persistent blocks per channel group
@@ -3013,7 +3020,7 @@ __global__ void __launch_bounds__(2 * SW * 64) __attribute__((amdgpu_waves_per_e
     const unsigned lds_patch = lds_addr(patch);
     auto issue_patch = [&](int t) {
         const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-        const int iy_base = ty * TH - 1, ix_base = tx * TW - 1;
+        const int iy_base = a.y0 + ty * TH - 1, ix_base = tx * TW - 1;
         const char *base = (const char *)a.in + ((long long)(b * a.H + iy_base) * a.W + ix_base) * (long long)ldi2;
         const unsigned centre = (unsigned)(a.W + 1) * ldi2;
 #pragma unroll
@@ -3063,9 +3070,9 @@ __global__ void __launch_bounds__(2 * SW * 64) __attribute__((amdgpu_waves_per_e
             int vm[FMW];
 #pragma unroll
             for (int j = 0; j < FMW; ++j) {
-                const int oy = ty * TH + ws * RPW + (j >> 1), ox = tx * TW + 16 * (j & 1) + n;
+                const int oy = a.y0 + ty * TH + ws * RPW + (j >> 1), ox = tx * TW + 16 * (j & 1) + n;
                 int m = 0;
-                if (oy < a.Ho && ox < a.Wo) {
+                if (oy < a.y1 && ox < a.Wo) {
                     const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= a.W - 2 ? 4 : 0);
                     m = (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= a.H - 2 ? hv << 6 : 0);
                 }
@@ -3139,8 +3146,8 @@ __global__ void __launch_bounds__(2 * SW * 64) __attribute__((amdgpu_waves_per_e
             const int ox = tx * TW + 16 * qh + n;
 #pragma unroll
             for (int r = 0; r < RPW; ++r) {
-                const int oy = ty * TH + ws * RPW + r;
-                const bool pv = oy < a.Ho && ox < a.Wo;
+                const int oy = a.y0 + ty * TH + ws * RPW + r;
+                const bool pv = oy < a.y1 && ox < a.Wo;
                 const size_t m = (size_t)(b * a.Ho + oy) * a.Wo + ox;
 #pragma unroll
                 for (int i = 0; i < FN; ++i) {
@@ -3192,7 +3199,7 @@ hipError_t launch_patch2(S2Args &g, int num_cus, hipStream_t s)
     static_assert(smem <= 160 * 1024, "LDS budget");
     if (g.Cout > CO || g.Cout % 8) return hipErrorInvalidValue;
     if (hipError_t e = rva_func_smem((const void *)k_conv3_patch2<CIN, CO, SW, RPW>, smem); e != hipSuccess) return e;
-    g.tiles_x = rva_ceil_div(g.Wo, 32); g.tiles_y = rva_ceil_div(g.Ho, TH);
+    g.tiles_x = rva_ceil_div(g.Wo, 32); g.tiles_y = rva_ceil_div(g.y1 - g.y0, TH);
     g.total = g.tiles_x * g.tiles_y * g.B;
     g.n_tiles = 1;
     int grid = num_cus;
@@ -3222,6 +3229,7 @@ hipError_t launch_patch2(S2Args &g, int num_cus, hipStream_t s)
 struct Stem2Args {
     const __half *in; const __half *w1; const float *b1; const __half *w2; const float *b2; __half *out; int ldo;
     int B, H, W, H1, W1, Ho, Wo, tiles_x, tiles_y, total;
+    int y0, y1;               // output row window (see S2Args)
 };
 
 constexpr int S2_TH = 4, S2_TW = 32;
@@ -3298,7 +3306,7 @@ __global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
         u4 pv[NPV];
         auto prefetch = [&](int t) {
             const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-            const int iy0 = 4 * ty * TH - 3, x00 = 4 * tx * TW - 8;
+            const int iy0 = 4 * (a.y0 + ty * TH) - 3, x00 = 4 * tx * TW - 8;
 #pragma unroll
             for (int k = 0; k < NPV; ++k) {
                 const int c16 = tid + 512 * k;
@@ -3344,7 +3352,7 @@ __global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
                 if (k + 1 < nk) prefetch(t + gridDim.x);
                 const __half *inp = inp0 + (size_t)(k & 1) * 3 * IR * IC;
                 __half *patch = patch0 + (size_t)(k & 1) * (PROWS + 1) * 32;
-                const int sy0 = 2 * ty * TH - 1, sx0 = 2 * tx * TW - 1;
+                const int sy0 = 2 * (a.y0 + ty * TH) - 1, sx0 = 2 * tx * TW - 1;
                 // fragments in pairs: the chain  LDS read -> 2 dependent MFMAs -> exp / rcp -> LDS write  of one fragment is
                 // ~700 cycles of latency (tools/stem2_stamps.py); independent chains overlap
                 const int pyb = -sy0, pxb = -sx0;                     // first in-image patch row / column
@@ -3434,13 +3442,13 @@ __global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
                     *reinterpret_cast<uint2 *>(stage + (size_t)n * SROW + co) = pk;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the stage rows are this wave's own: no barrier, just ordering
-                const int yy = ty * TH + orow;
+                const int yy = a.y0 + ty * TH + orow;
 #pragma unroll
                 for (int it = 0; it < 2; ++it) {
                     const int c16 = lane + 64 * it;
                     const int opx = c16 >> 3, pc = c16 & 7;
                     const int xx = tx * TW + 16 * ohalf + opx;
-                    if (yy < a.Ho && xx < a.Wo)
+                    if (yy < a.y1 && xx < a.Wo)
                         *reinterpret_cast<uint4 *>(a.out + ((size_t)(b * a.Ho + yy) * a.Wo + xx) * a.ldo + pc * 8) =
                             *reinterpret_cast<const uint4 *>(stage + (size_t)opx * SROW + pc * 8);
                 }
@@ -3466,6 +3474,8 @@ struct ConvCall {
     int cpad;                 // Cout rounded up to 64: what the caller padded the weights to (rva_conv_cout_pad)
     int num_cus;
     hipStream_t s;
+    int y0, y1;               // output row window (rva_conv2d_nhwc_f16_rows); [0, Ho) = the whole image
+    bool windowed() const { return y0 != 0 || y1 != a.Ho; }
 };
 
 // the fields every family's argument struct shares (the structs themselves are part of the compiled kernels and stay apart)
@@ -3494,6 +3504,7 @@ inline bool is_3x3(const ConvCall &c, int stride) { return c.ksize == 3 && c.a.s
 template <int BN, int WPX, int BK = 32>
 hipError_t v_gather(const ConvCall &c)
 {
+    if (c.windowed()) return hipErrorInvalidValue;      // this family runs whole images only
     if (c.cpad % BN) return hipErrorInvalidValue;
     ConvArgs a = c.a;
     a.n_tiles = c.cpad / BN;
@@ -3506,6 +3517,7 @@ hipError_t v_gather(const ConvCall &c)
 template <int BN, int WPX>
 hipError_t v_res(const ConvCall &c)
 {
+    if (c.windowed()) return hipErrorInvalidValue;      // this family runs whole images only
     if (c.cpad % BN || c.a.stride != 1) return hipErrorInvalidValue;
     ResArgs ra = family_args<ResArgs>(c);
     ra.Cin = c.a.Cin; ra.CinPad = c.a.CinPad; ra.M = c.a.M;
@@ -3525,6 +3537,7 @@ hipError_t v_res(const ConvCall &c)
 template <int BN, int WPX, bool PF2 = false>
 hipError_t v_row(const ConvCall &c)
 {
+    if (c.windowed()) return hipErrorInvalidValue;      // this family runs whole images only
     if (c.cpad % BN || !is_3x3(c, 1)) return hipErrorInvalidValue;
     RowArgs rr = family_args<RowArgs>(c);
     rr.Cin = c.a.Cin; rr.CinPad = c.a.CinPad;
@@ -3536,6 +3549,7 @@ hipError_t v_row(const ConvCall &c)
 template <int BM, int BN, int WGM, int WGN, int NSLOT>
 hipError_t v_big(const ConvCall &c)
 {
+    if (c.windowed()) return hipErrorInvalidValue;      // this family runs whole images only
     if (!is_3x3(c, 1)) return hipErrorInvalidValue;
     BigArgs g = dma3_args<BigArgs>(c);
     return launch_big<BM, BN, WGM, WGN, NSLOT>(g, c.s);
@@ -3548,6 +3562,7 @@ hipError_t v_gbig(const ConvCall &c)
     if (c.ksize == 1 && c.a.stride != 1) return hipErrorInvalidValue;
     ConvArgs a = c.a;
     a.CoutPad = c.cpad;
+    a.wy0 = c.y0; a.wrows = c.y1 - c.y0; a.M = c.batch * a.wrows * a.Wo;      // the raster of the row window
     return launch_gbig<BM, BN, WGM, WGN, NSLOT, BK, SUB>(a, c.ksize, c.s);
 }
 
@@ -3558,7 +3573,7 @@ hipError_t v_patch(const ConvCall &c)
 {
     if (!is_3x3(c, STRIDE) || c.a.Cin != CIN || c.a.Cout > (CIN == 64 ? 64 : CO)) return hipErrorInvalidValue;
     S2Args g = family_args<S2Args>(c);
-    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad;
+    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad; g.y0 = c.y0; g.y1 = c.y1;
     return launch_patch<STRIDE, CIN, CO, NWV, NBUF, RPW>(g, c.num_cus, c.s);
 }
 
@@ -3568,7 +3583,7 @@ hipError_t v_patch2(const ConvCall &c)
 {
     if (!is_3x3(c, 1) || c.a.Cin != CIN || c.a.Cout > CO) return hipErrorInvalidValue;
     S2Args g = family_args<S2Args>(c);
-    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad;
+    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad; g.y0 = c.y0; g.y1 = c.y1;
     return launch_patch2<CIN, CO, SW, RPW>(g, c.num_cus, c.s);
 }
 
@@ -3577,6 +3592,7 @@ hipError_t v_patch2(const ConvCall &c)
 template <hipError_t (*LAUNCH)(RunArgs &, hipStream_t), int STRIDE = 1>
 hipError_t v_run(const ConvCall &c)
 {
+    if (c.windowed()) return hipErrorInvalidValue;      // this family runs whole images only
     if (!is_3x3(c, STRIDE)) return hipErrorInvalidValue;
     RunArgs g = dma3_args<RunArgs>(c);
     return LAUNCH(g, c.s);
@@ -3597,6 +3613,9 @@ hipError_t v_run_nosel(const ConvCall &c)
 
 hipError_t launch_variant(int variant, const ConvCall &c);
 
+// variant 0's first choice is the LDS-DMA gather tile gb2<128,128> (37): 1x1 stride 1 and 3x3 stride 2 with whole 64-channel steps
+inline bool auto_picks_gather(int Cin, int ksize, int stride) { return Cin % 64 == 0 && ((ksize == 3 && stride == 2) || (ksize == 1 && stride == 1)); }
+
 // Variant 0, for callers that do not autotune.  First the LDS-DMA kernels wherever their channel constraints hold, tile
 // picked from the autotune tables of the YOLOv8 layers (tools/show_tuning.py); if that launch fails for any reason, the
 // resident kernel with the largest tile that still yields two tiles per CU; if its geometry does not fit, the gather kernel.
@@ -3608,8 +3627,9 @@ hipError_t v_auto(const ConvCall &c)
     int pick = 0;
     if (is_3x3(c, 1) && a.Cin % 32 == 0)
         pick = bn128 ? ((long)a.M * a.Cout >= 20000000L ? 25 : 21) : (a.M >= 100000 ? 31 : 23);
-    else if (a.Cin % 64 == 0 && (c.ksize == 3 || a.stride == 1))
+    else if (auto_picks_gather(a.Cin, c.ksize, a.stride))
         pick = 37;
+    if (c.windowed()) return pick == 37 ? launch_variant(37, c) : hipErrorInvalidValue;      // a row window: the gather tile or nothing
     if (pick) {
         if (launch_variant(pick, c) == hipSuccess) return hipSuccess;
         (void)hipGetLastError();
@@ -3658,6 +3678,7 @@ struct ConvVariant {
     int number;
     const char *name;         // as printed by tools/show_tuning.py and recorded under profiles/
     hipError_t (*launch)(const ConvCall &);
+    bool rows = false;        // the family's launch takes an output row window (rva_conv2d_nhwc_f16_rows)
 };
 
 constexpr ConvVariant kConvVariants[] = {
@@ -3703,25 +3724,25 @@ constexpr ConvVariant kConvVariants[] = {
     {31, "big2<384,64>", v_big<384, 64, 8, 1, 2>},        // 74 KB
     {32, "big2<320,64>", v_big<320, 64, 4, 2, 2>},        // 66 KB
     // large-tile LDS-DMA gather kernel, 64-channel K-steps: 33..36 3-slot ring, 37..39 2-slot
-#define RVA_ROW(n, name, ...) {n, name, v_gbig<__VA_ARGS__>},
+#define RVA_ROW(n, name, ...) {n, name, v_gbig<__VA_ARGS__>, true},
     RVA_GATHER64_TILES(RVA_ROW)
 #undef RVA_ROW
     // the same with 32-channel K-steps (64-byte rows, swz32): the layers with Cin = 32 / 96
-    {40, "gb32<256,64>", v_gbig<256, 64, 4, 2, 3, 32>},   // 60 KB: two blocks per CU
-    {41, "gb32<128,64>", v_gbig<128, 64, 2, 4, 3, 32>},   // 36 KB: four blocks per CU
-    {42, "gb32_2<256,64>", v_gbig<256, 64, 4, 2, 2, 32>}, // 40 KB: three blocks per CU
+    {40, "gb32<256,64>", v_gbig<256, 64, 4, 2, 3, 32>, true},   // 60 KB: two blocks per CU
+    {41, "gb32<128,64>", v_gbig<128, 64, 2, 4, 3, 32>, true},   // 36 KB: four blocks per CU
+    {42, "gb32_2<256,64>", v_gbig<256, 64, 4, 2, 2, 32>, true}, // 40 KB: three blocks per CU
     // patch kernels for Cin = 32: 43 = 3x3 stride 2, Cout <= 64 (the first downsampling convolution); 44 / 45 = 3x3 stride 1,
     // Cout <= 32, tiles of 4 / 8 rows (the 32 -> 32 bottleneck convolutions)
-    {43, "s2patch", v_patch<2, 32, 64, 4, 1>},
-    {44, "s1patch4", v_patch<1, 32, 32, 4, 1>},
-    {45, "s1patch8", v_patch<1, 32, 32, 8, 1>},
+    {43, "s2patch", v_patch<2, 32, 64, 4, 1>, true},
+    {44, "s1patch4", v_patch<1, 32, 32, 4, 1>, true},
+    {45, "s1patch8", v_patch<1, 32, 32, 8, 1>, true},
     // patch kernels for 3x3 stride 1, 64 -> 64: 72 KB of weights resident, one block per CU
-    {46, "p64x4db", v_patch<1, 64, 64, 4, 2>},            // 124 KB, two patch buffers
-    {47, "p64x8", v_patch<1, 64, 64, 8, 1>},              // 116 KB, eight waves, one buffer
-    {48, "p64x4", v_patch<1, 64, 64, 4, 1>},              // 98 KB
-    {49, "p64x8db", v_patch<1, 64, 64, 8, 2>},            // 158 KB: eight waves, two patch buffers
-    {50, "p64x4r2db", v_patch<1, 64, 64, 4, 2, 2>},       // 158 KB: four waves x two rows, two buffers
-    {51, "p64x8r2", v_patch<1, 64, 64, 8, 1, 2>},         // 149 KB: 16-row tile, eight waves x two rows
+    {46, "p64x4db", v_patch<1, 64, 64, 4, 2>, true},            // 124 KB, two patch buffers
+    {47, "p64x8", v_patch<1, 64, 64, 8, 1>, true},              // 116 KB, eight waves, one buffer
+    {48, "p64x4", v_patch<1, 64, 64, 4, 1>, true},              // 98 KB
+    {49, "p64x8db", v_patch<1, 64, 64, 8, 2>, true},            // 158 KB: eight waves, two patch buffers
+    {50, "p64x4r2db", v_patch<1, 64, 64, 4, 2, 2>, true},       // 158 KB: four waves x two rows, two buffers
+    {51, "p64x8r2", v_patch<1, 64, 64, 8, 1, 2>, true},         // 149 KB: 16-row tile, eight waves x two rows
     // "long run" kernels: a 32-channel chunk's activation run staged once for the three vertical taps
     {52, "run<256,64>", v_run<launch_run<256, 64, 4, 2>>},
     {53, "run<128,64>", v_run<launch_run<128, 64, 2, 4>>},
@@ -3733,20 +3754,20 @@ constexpr ConvVariant kConvVariants[] = {
     {59, "run<160,128>", v_run<launch_run<160, 128, 2, 4>>},
     {60, "run<320,64>", v_run<launch_run<320, 64, 4, 2>>},
     // patch kernels for 64 -> 64 with the output channels in two groups of 32: 36 KB of weights per block, two blocks per CU
-    {61, "p64h32x8", v_patch<1, 64, 32, 8, 1, 1>},        // 79 KB: 8-row tile
-    {62, "p64h32x4", v_patch<1, 64, 32, 4, 1, 1>},        // 62 KB: 4-row tile
-    {63, "p64h32x4r2", v_patch<1, 64, 32, 4, 1, 2>},      // 79 KB: 8-row tile, four waves x two rows
+    {61, "p64h32x8", v_patch<1, 64, 32, 8, 1, 1>, true},        // 79 KB: 8-row tile
+    {62, "p64h32x4", v_patch<1, 64, 32, 4, 1, 1>, true},        // 62 KB: 4-row tile
+    {63, "p64h32x4r2", v_patch<1, 64, 32, 4, 1, 2>, true},      // 79 KB: 8-row tile, four waves x two rows
     // LDS-DMA gather kernel with 256-channel output tiles: 43-64 MACs per staged byte against 32 of the 128 x 128 tile.  The
     // CU's vector-memory path moves 64 B/clk, its MFMAs 4096 MAC/clk: below 64 MAC/B the staging, not the matrix pipe, caps a
     // 1x1 convolution (a plain GEMM, no tap reuse).  One block per CU.
     // (measured and dropped: <128,256> tiles, three- and four-slot rings with 32-channel steps -- more bytes in flight per CU
     //  did not help the memory-latency-bound 1x1 layers, profiles/r02_conv_tuning.txt)
-    {64, "gb2<256,256>", v_gbig<256, 256, 4, 2, 2>},          // 128 KB ring, wave tile 64 x 128
-    {65, "gb2<256,256>w128x64", v_gbig<256, 256, 2, 4, 2>},   // 128 KB ring, wave tile 128 x 64
+    {64, "gb2<256,256>", v_gbig<256, 256, 4, 2, 2>, true},          // 128 KB ring, wave tile 64 x 128
+    {65, "gb2<256,256>w128x64", v_gbig<256, 256, 2, 4, 2>, true},   // 128 KB ring, wave tile 128 x 64
     // patch kernel with two wave sets half a tile period apart (3x3 stride 1, Cin = 64, Cout <= 64).  Sixteen waves: two sets
     // of eight, one output row per wave -- two MFMA waves per SIMD in every phase.  (The 2 x 4 waves x two rows form, one
     // 256-register MFMA wave per SIMD, measured 27.0 us against 25.6 us at 80 x 80 and was dropped.)
-    {66, "p64 two sets", v_patch2<64, 64, 8, 1>},
+    {66, "p64 two sets", v_patch2<64, 64, 8, 1>, true},
     // "whole chunk per barrier" kernels for layers with few pixels: one barrier per 32-channel chunk (nine taps), one block per CU
     {67, "chunk<128,64>", v_run<launch_chunk<128, 64, 4, 2>>},
     {68, "chunk<64,64>", v_run<launch_chunk<64, 64, 2, 4>>},
@@ -3756,12 +3777,12 @@ constexpr ConvVariant kConvVariants[] = {
     {72, "chunk<192,64>", v_run<launch_chunk<192, 64, 4, 2>>},
     {73, "chunk<256,96>", v_run<launch_chunk<256, 96, 4, 2>>},
     // LDS-DMA gather kernel (as 37..39, two-slot ring) with SUB 64-channel K-steps per barrier, <BM,BN>xSUB: the small-M layers
-    {74, "gbs<128,128>x2", v_gbig<128, 128, 2, 4, 2, 64, 2>}, // 128 KB
-    {75, "gbs<128,64>x2", v_gbig<128, 64, 2, 4, 2, 64, 2>},   // 96 KB
-    {76, "gbs<128,64>x3", v_gbig<128, 64, 2, 4, 2, 64, 3>},   // 144 KB
-    {77, "gbs<64,64>x4", v_gbig<64, 64, 2, 4, 2, 64, 4>},     // 128 KB
-    {78, "gbs<64,128>x3", v_gbig<64, 128, 2, 4, 2, 64, 3>},   // 144 KB
-    {79, "gbs<64,64>x2", v_gbig<64, 64, 2, 4, 2, 64, 2>},     // 64 KB: two blocks per CU
+    {74, "gbs<128,128>x2", v_gbig<128, 128, 2, 4, 2, 64, 2>, true}, // 128 KB
+    {75, "gbs<128,64>x2", v_gbig<128, 64, 2, 4, 2, 64, 2>, true},   // 96 KB
+    {76, "gbs<128,64>x3", v_gbig<128, 64, 2, 4, 2, 64, 3>, true},   // 144 KB
+    {77, "gbs<64,64>x4", v_gbig<64, 64, 2, 4, 2, 64, 4>, true},     // 128 KB
+    {78, "gbs<64,128>x3", v_gbig<64, 128, 2, 4, 2, 64, 3>, true},   // 144 KB
+    {79, "gbs<64,64>x2", v_gbig<64, 64, 2, 4, 2, 64, 2>, true},     // 64 KB: two blocks per CU
     // "long run" kernels on the padded raster (k_conv3_run<..., PADO>: no padding selects)
     {80, "runp<256,64>", v_run<launch_run<256, 64, 4, 2, false, true>>},
     {81, "runp<256,128>", v_run<launch_run<256, 128, 4, 2, false, true>>},
@@ -3823,6 +3844,15 @@ int launch_gather64_1x1(rva_ctx *ctx, const char *who, ConvArgs &a, int variant,
 
 }  // namespace
 
+// Whether a variant's launch takes an output row window (the `rows` column of kConvVariants: the LDS-DMA gather kernel in all its
+// tiles and the patch kernels); variant 0 does where its choice is the gather tile (v_auto).
+bool rva_conv_variant_rows(int variant, int Cin, int ksize, int stride)
+{
+    if (variant == 0) return auto_picks_gather(Cin, ksize, stride);
+    const ConvVariant *row = find_variant(variant);
+    return row && row->rows;
+}
+
 bool rva_conv_variant_is_gather64(int variant)
 {
 #define RVA_IS(n, ...) variant == n ||
@@ -3848,6 +3878,17 @@ int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *wei
                           int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
                           int stride, int act, int variant, rva_stream_t stream_)
 {
+    return rva_conv2d_nhwc_f16_rows(ctx, in, ldi, weights, bias, out, ldo, residual, ldr, batch, H, W, Cin, Cout, ksize, stride, act,
+                                    variant, 0, -1, stream_);
+}
+
+// The same restricted to the output rows [y0, y1) of every image: only those rows are computed and written; their inputs are
+// read wherever they lie, and padding is decided in the whole image.  y1 < 0 = the last row.  RVA_ERR_ARG for a variant
+// whose kernel runs whole images only (rva_conv_variant_rows says which can) unless the window is the whole image.
+int rva_conv2d_nhwc_f16_rows(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
+                             int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
+                             int stride, int act, int variant, int y0, int y1, rva_stream_t stream_)
+{
     if (!ctx) return RVA_ERR_ARG;
     const ConvVariant *row = find_variant(variant);
     if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) ||
@@ -3863,6 +3904,10 @@ int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *wei
     a.Ho = (H + 2 * pad - ksize) / stride + 1;
     a.Wo = (W + 2 * pad - ksize) / stride + 1;
     a.M = batch * a.Ho * a.Wo;
+    a.wy0 = 0; a.wrows = a.Ho;
+    if (y1 < 0) y1 = a.Ho;
+    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_conv2d_nhwc_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
+    c.y0 = y0; c.y1 = y1;
     c.batch = batch; c.ksize = ksize;
     c.cpad = rva_ceil_div(Cout, 64) * 64;
     c.num_cus = rva_num_cus(ctx);
@@ -3887,7 +3932,7 @@ int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, 
     a.in = (const __half *)low; a.ldi = ld_low; a.in2 = (const __half *)skip; a.ldi2 = ld_skip; a.c_split = c_low;
     a.w = (const __half *)weights; a.bias = bias; a.out = (__half *)out; a.ldo = ldo; a.res = nullptr; a.ldr = 0;
     a.H = H; a.W = W; a.Cin = c_low + c_skip; a.CinPad = a.Cin; a.Cout = Cout; a.stride = 1; a.act = act;
-    a.Ho = H; a.Wo = W; a.M = batch * H * W; a.CoutPad = rva_ceil_div(Cout, 64) * 64;
+    a.Ho = H; a.Wo = W; a.M = batch * H * W; a.CoutPad = rva_ceil_div(Cout, 64) * 64; a.wy0 = 0; a.wrows = H;
     return launch_gather64_1x1<true, false>(ctx, "rva_conv1x1_upcat_f16", a, variant, (hipStream_t)stream_);
 }
 
@@ -3903,7 +3948,7 @@ static int conv1x1_head(rva_ctx *ctx, const void *in, int ldi, const void *weigh
     ConvArgs a{};
     a.in = (const __half *)in; a.ldi = ldi; a.w = (const __half *)weights; a.bias = bias; a.out = nullptr; a.ldo = 0;
     a.H = H; a.W = W; a.Cin = Cin; a.CinPad = Cin; a.Cout = Cout; a.stride = 1; a.act = 0; a.Ho = H; a.Wo = W; a.M = batch * H * W;
-    a.CoutPad = rva_ceil_div(Cout, 64) * 64;
+    a.CoutPad = rva_ceil_div(Cout, 64) * 64; a.wy0 = 0; a.wrows = H;
     a.hout = (__half *)out; a.hmode = mode; a.hnc = nc; a.hA = anchors_total; a.ha0 = anchor_offset; a.hW = W; a.hHW = H * W;
     a.hstride = stride_px;
     a.hbox = boxes32;
@@ -3976,13 +4021,23 @@ int rva_c2f_pair32_f16(rva_ctx *ctx, const void *in, int ldi, const void *w1, co
 int rva_stem2_f16(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
                   void *out, int ldo, int batch, int H, int W, rva_stream_t stream_)
 {
+    return rva_stem2_f16_rows(ctx, in_planar, w1, b1, w2, b2, out, ldo, batch, H, W, 0, -1, stream_);
+}
+
+// rows [y0, y1) of the quarter-resolution output only (y1 < 0 = the last row): the 4 x 32 tiles are laid over the window
+int rva_stem2_f16_rows(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
+                       void *out, int ldo, int batch, int H, int W, int y0, int y1, rva_stream_t stream_)
+{
     if (!ctx || !in_planar || !w1 || !b1 || !w2 || !b2 || !out || ldo % 8 || ldo < 64 || batch <= 0 || H < 4 || W < 4)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16: bad argument");
     if (W % 8 || ((uintptr_t)in_planar & 15)) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16: W %% 8 == 0 and a 16-byte aligned input are required");
     Stem2Args a{(const __half *)in_planar, (const __half *)w1, b1, (const __half *)w2, b2, (__half *)out, ldo, batch, H, W};
     a.H1 = (H - 1) / 2 + 1; a.W1 = (W - 1) / 2 + 1;
     a.Ho = (a.H1 - 1) / 2 + 1; a.Wo = (a.W1 - 1) / 2 + 1;
-    a.tiles_x = rva_ceil_div(a.Wo, S2_TW); a.tiles_y = rva_ceil_div(a.Ho, S2_TH);
+    if (y1 < 0) y1 = a.Ho;
+    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
+    a.y0 = y0; a.y1 = y1;
+    a.tiles_x = rva_ceil_div(a.Wo, S2_TW); a.tiles_y = rva_ceil_div(y1 - y0, S2_TH);
     a.total = a.tiles_x * a.tiles_y * batch;
     constexpr size_t smem = S2_SMEM;
     RVA_HIP(ctx, rva_func_smem((const void *)k_stem2, smem));

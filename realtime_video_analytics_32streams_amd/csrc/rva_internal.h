@@ -81,6 +81,8 @@ int rva_num_cus(rva_ctx *ctx);
 
 // true for the variants of rva_conv2d_nhwc_f16_v that the fused 1x1 forms (rva_conv1x1_upcat_f16, rva_conv1x1_head_*) also take
 bool rva_conv_variant_is_gather64(int variant);
+// fp16 variants whose kernel takes an output row window (rva_conv2d_nhwc_f16_rows); variant 0 by the shape it would pick for
+bool rva_conv_variant_rows(int variant, int Cin, int ksize, int stride);
 
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);

@@ -10,6 +10,12 @@
 // rva_yolov8_plan_launch_tunable and fixes its choice with rva_yolov8_plan_set_variant; without a tuner every step uses the
 // library's heuristic (variant 0).  No host synchronisation, no allocation after create(): a run can be captured into a hipGraph.
 //
+// Static rows (rva_yolov8_plan_set_static_rows): a letterboxed frame leaves the same border rows in `input` on every run, and the
+// output rows of the early layers whose receptive field lies in the border (and the zero padding) come out the same every time.
+// Every step carries the window [y0, y1) of its output rows that can change, propagated from the input window through the step
+// list (propagate_rows); after one complete run over all rows has filled every buffer ("primed"), the steps whose kernel takes a
+// row window launch that window only.  The rows outside it keep the bytes of the priming run.
+//
 // Graph (ultralytics YOLOv8 n / s / m / l / x: widths c1..c5, C2f depths, nc classes, reg_max 16):
 //   b0 stem 3x3 s2 | b1 3x3 s2 | b2 C2f | b3 3x3 s2 | b4 C2f | b5 3x3 s2 | b6 C2f | b7 3x3 s2 | b8 C2f | b9 SPPF |
 //   h12 C2f(cat[up(p5), p4]) | h15 C2f(cat[up(n4), p3]) | h16 3x3 s2 | h18 C2f(cat[h16, n4]) | h19 3x3 s2 | h21 C2f(cat[h19, p5]) |
@@ -43,12 +49,14 @@ struct Step {
     const void *res = nullptr; int ldr = 0;
     int H = 0, W = 0, Cin = 0, Cout = 0, k = 0, stride = 0, act = 0, variant = 0;
     int mode = 0, a0 = 0; float stride_px = 0.f;
+    int c_real = 0;                       // K_CONV: input channels before padding (what the step really depends on)
+    int Ho = 0, y0 = 0, y1 = 0;           // output rows, and the window of them that depends on the non-static input rows
     // head3
     const void *hb[3] = {nullptr, nullptr, nullptr}, *hk[3] = {nullptr, nullptr, nullptr};
     int32_t hldb[3] = {0, 0, 0}, hldc[3] = {0, 0, 0}, hh[3] = {0, 0, 0}, hw[3] = {0, 0, 0}; float hs[3] = {0, 0, 0};
 };
 
-struct Tunable { int step; std::string desc; };
+struct Tunable { int step; std::string base, desc; };      // desc = base (+ the step's row window where it is not the whole image)
 
 }  // namespace
 
@@ -66,6 +74,9 @@ struct rva_yolov8_plan {
     bool f32 = false;                     // RVA_PLAN_F32: fp32 buffers and the kernels of rva_conv_f32.hip
     bool box32 = false;                   // RVA_PLAN_BOX_F32: the head kernels also write the box rows as fp32 [B, 4, A] behind the fp16 head
     size_t box_off = 0;                   // ... at this byte offset of `output` (rva_yolov8_plan_output_layout)
+    int rows_top = 0, rows_bottom = 0;    // input rows outside [top, bottom) are static (set_static_rows); (0, H) = none
+    bool windowed = false;                // some step's window is smaller than its image
+    bool primed = false;                  // every buffer holds a whole run's rows for the current windows and variants
 };
 
 namespace {
@@ -182,7 +193,7 @@ struct Builder {
             char d[96];
             va_list ap; va_start(ap, desc_fmt); vsnprintf(d, sizeof d, desc_fmt, ap); va_end(ap);
             s.tunable = (int)p->tunables.size();
-            p->tunables.push_back(Tunable{(int)p->steps.size(), d});
+            p->tunables.push_back(Tunable{(int)p->steps.size(), d, d});
         }
         p->steps.push_back(s);
     }
@@ -197,6 +208,7 @@ struct Builder {
         s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.act = act;
         if (res) { s.res = res->ptr(); s.ldr = res->ld; }
         const int cin_real = s.Cin;
+        s.c_real = cin_real;
         if (p->f32) {                     // every channel count is read as it is: the kernel never reads past its slice
             if (s.Cin % 16) return fail("fp32 plan: convolution input channels must be multiples of 16");
             push(s, "%d->%d k%ds%d %dx%d", cin_real, s.Cout, s.k, s.stride, h, w);
@@ -241,8 +253,8 @@ struct Builder {
         const long m = (long)p->B * h * w;
         const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, what), *cv2 = take((2 + n) * c, c2, 1, 1, what);
         if (!cv1 || !cv2) return false;
-        View cat = buf(m, (2 + n) * c), tmp = buf(m, c);
-        if (!cat.base || !tmp.base) return false;
+        View cat = buf(m, (2 + n) * c);
+        if (!cat.base) return false;
         if (low) { if (!upcat(cv1, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
         else if (!conv1(cv1, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
         for (int i = 0; i < n; ++i) {
@@ -258,6 +270,10 @@ struct Builder {
                 push(s, nullptr);
                 continue;
             }
+            // the intermediate, one buffer per bottleneck: with row windows a step rewrites part of its output only, and the rest must
+            // still be what THIS bottleneck's first convolution left there (the second one reads it as halo)
+            View tmp = buf(m, c);
+            if (!tmp.base) return false;
             if (!conv1(b1, x, tmp, h, w, 1)) return false;
             if (!conv1(b2, tmp, cat.sub((2 + i) * c, c), h, w, 1, shortcut ? &x : nullptr)) return false;
         }
@@ -436,9 +452,22 @@ struct Builder {
     }
 };
 
-int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *input, void *output, rva_stream_t st)
+// whether this step, run with this variant, can restrict its launch to a row window
+bool step_takes_rows(const Step &s, int variant)
+{
+    if (s.kind == K_STEM2) return true;
+    return s.kind == K_CONV && rva_conv_variant_rows(variant, s.Cin, s.k, s.stride);
+}
+
+// win: launch the step's row window where its kernel takes one (a primed plan; the tuner), else all rows
+int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *input, void *output, rva_stream_t st, bool win)
 {
     rva_ctx *c = p->ctx;
+    if (win && (s.y0 > 0 || s.y1 < s.Ho) && step_takes_rows(s, variant)) {
+        if (s.kind == K_STEM2) return rva_stem2_f16_rows(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, p->B, s.H, s.W, s.y0, s.y1, st);
+        return rva_conv2d_nhwc_f16_rows(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act,
+                                        variant, s.y0, s.y1, st);
+    }
     if (p->box32 && output) {             // the two launch forms that write box rows, with the side tensor of this output
         float *boxes = (float *)((char *)output + p->box_off);
         if (s.kind == K_HEAD && s.mode == 1)
@@ -471,6 +500,114 @@ bool variant_fits(const Step &s, int variant)
     if (s.kind == K_CONV) return variant >= 0;
     if (s.kind == K_CONV_F32) return variant >= 0 && variant <= rva_conv_f32_num_variants();
     return variant == 0 || rva_conv_variant_is_gather64(variant);     // upcat / head: the LDS-DMA gather family
+}
+
+int out_rows(int H, int k, int stride) { return (H + 2 * (k / 2) - k) / stride + 1; }
+
+// Windows of every step from the input window [top, bottom).  A written channel slice is known by the address of its first
+// pixel; a reader takes the union over the slices its channels overlap, and the whole image for channels nobody registered
+// (the outputs of the pooling / upsampling / head steps: those steps always run all rows).
+void propagate_rows(rva_yolov8_plan *p)
+{
+    struct Slice { const char *lo, *hi; int H, y0, y1; };
+    std::vector<Slice> written;
+    const int es = p->f32 ? 4 : 2;
+    const bool off = p->f32 || (p->rows_top <= 0 && p->rows_bottom >= p->H);
+    // window of rows [*lo, *hi) of an H-row image read through `ptr`, `ch` channels wide: false = everything
+    auto read = [&](const void *ptr, int ch, int H, int *lo, int *hi) {
+        const char *a = (const char *)ptr, *b = a + (size_t)ch * es;
+        long covered = 0;
+        int y0 = H, y1 = 0;
+        for (const Slice &w : written) {
+            const char *l = w.lo > a ? w.lo : a, *h = w.hi < b ? w.hi : b;
+            if (l >= h) continue;
+            if (w.H != H) return false;
+            covered += h - l;
+            if (w.y0 < y0) y0 = w.y0;
+            if (w.y1 > y1) y1 = w.y1;
+        }
+        if (covered != b - a || y0 >= y1) return false;
+        *lo = y0; *hi = y1;
+        return true;
+    };
+    auto through = [](int k, int stride, int H, int *lo, int *hi) {      // in place; returns the output height
+        int32_t a = 0, b = 0;
+        (void)rva_conv_rows_through(k, stride, H, *lo, *hi, &a, &b);
+        *lo = a; *hi = b;
+        return out_rows(H, k, stride);
+    };
+    p->windowed = false;
+    for (Step &s : p->steps) {
+        int lo = 0, hi = 0, Ho = s.H;
+        bool known = false;
+        switch (s.kind) {
+        case K_STEM2: case K_STEM:
+            lo = p->rows_top; hi = p->rows_bottom; known = true;
+            Ho = through(3, 2, s.H, &lo, &hi);
+            if (s.kind == K_STEM2) Ho = through(3, 2, Ho, &lo, &hi);
+            break;
+        case K_CONV:
+            known = read(s.in, s.c_real, s.H, &lo, &hi);
+            Ho = out_rows(s.H, s.k, s.stride);
+            if (known) {
+                (void)through(s.k, s.stride, s.H, &lo, &hi);
+                int rl = 0, rh = 0;
+                if (s.res) {                                   // the shortcut is added row for row
+                    known = read(s.res, s.Cout, Ho, &rl, &rh);
+                    if (rl < lo) lo = rl;
+                    if (rh > hi) hi = rh;
+                }
+            }
+            break;
+        case K_PAIR32:
+            known = read(s.in, 32, s.H, &lo, &hi);
+            if (known) { (void)through(3, 1, s.H, &lo, &hi); (void)through(3, 1, s.H, &lo, &hi); }
+            break;
+        case K_UPCAT: {
+            int l2 = 0, h2 = 0;
+            known = read(s.in, s.c_in, s.H / 2, &lo, &hi) && read(s.in2, s.c_in2, s.H, &l2, &h2);
+            lo = 2 * lo < l2 ? 2 * lo : l2;                    // low-resolution row r is rows 2r and 2r + 1 here
+            hi = 2 * hi > h2 ? 2 * hi : h2;
+            break;
+        }
+        default: break;
+        }
+        s.Ho = Ho;
+        if (off || !known || lo >= hi) { lo = 0; hi = Ho; }
+        s.y0 = lo; s.y1 = hi;
+        if (lo > 0 || hi < Ho) p->windowed = true;
+        if (s.kind == K_STEM2 || s.kind == K_STEM || s.kind == K_CONV || s.kind == K_PAIR32 || s.kind == K_UPCAT) {
+            const int ch = s.kind == K_STEM2 ? 64 : s.kind == K_PAIR32 ? 32 : s.Cout;
+            written.push_back(Slice{(const char *)s.out, (const char *)s.out + (size_t)ch * es, Ho, lo, hi});
+        }
+    }
+    for (Tunable &t : p->tunables) {
+        const Step &s = p->steps[t.step];
+        t.desc = t.base;
+        if (s.y0 > 0 || s.y1 < s.Ho) {
+            char w[32];
+            snprintf(w, sizeof w, " r[%d,%d)", s.y0, s.y1);
+            t.desc += w;
+        }
+    }
+    p->primed = false;
+}
+
+bool stream_is_capturing(rva_stream_t stream)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+int run_steps(rva_yolov8_plan *p, const void *input, void *output, int first, int last, rva_stream_t stream, bool win)
+{
+    for (int i = first; i < last; ++i) {
+        const Step &s = p->steps[i];
+        const int rc = launch_step(p, s, s.variant, input, output, stream, win);
+        if (rc != RVA_OK) return rc;
+    }
+    return RVA_OK;
 }
 
 }  // namespace
@@ -507,6 +644,8 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
         }
     RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
     if (p->box32) p->box_off = ((size_t)p->B * (4 + p->nc) * p->A * 2 + 255) / 256 * 256;
+    p->rows_top = 0; p->rows_bottom = p->H;
+    propagate_rows(p.get());
     *out = p.release();
     return RVA_OK;
 }
@@ -554,6 +693,7 @@ int rva_yolov8_plan_set_variant(rva_yolov8_plan *p, int index, int variant)
     if (!p || index < 0 || index >= (int)p->tunables.size()) return RVA_ERR_ARG;
     Step &s = p->steps[p->tunables[index].step];
     if (!variant_fits(s, variant) || variant > rva_conv_num_variants()) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_set_variant: variant %d does not exist for this layer", variant);
+    p->primed = false;                                     // another kernel may cover other rows: one whole run first
     s.variant = variant;
     return RVA_OK;
 }
@@ -570,24 +710,60 @@ int rva_yolov8_plan_launch_tunable(rva_yolov8_plan *p, int index, int variant, v
     const Step &s = p->steps[p->tunables[index].step];
     if (!variant_fits(s, variant)) return RVA_ERR_ARG;
     if (s.kind == K_HEAD && !output) return RVA_ERR_ARG;
-    return launch_step(p, s, variant, nullptr, output, stream);
+    return launch_step(p, s, variant, nullptr, output, stream, true);      // the row window where the variant takes one: what a primed run launches
 }
 
 int rva_yolov8_plan_run_range(rva_yolov8_plan *p, const void *input, void *output, int first, int last, rva_stream_t stream)
 {
     if (!p || !input || !output || first < 0 || last > (int)p->steps.size() || first > last) return RVA_ERR_ARG;
     if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
-    for (int i = first; i < last; ++i) {
-        const Step &s = p->steps[i];
-        const int rc = launch_step(p, s, s.variant, input, output, stream);
-        if (rc != RVA_OK) return rc;
-    }
-    return RVA_OK;
+    return run_steps(p, input, output, first, last, stream, p->primed);       // a range never primes
 }
 
 int rva_yolov8_plan_run(rva_yolov8_plan *p, const void *input, void *output, rva_stream_t stream)
 {
-    return p ? rva_yolov8_plan_run_range(p, input, output, 0, (int)p->steps.size(), stream) : RVA_ERR_ARG;
+    if (!p || !input || !output) return RVA_ERR_ARG;
+    if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
+    const int rc = run_steps(p, input, output, 0, (int)p->steps.size(), stream, p->primed);
+    // a whole run over all rows has been queued: later runs on this plan may launch windows.  A run that is only recorded
+    // (stream capture) executes who knows when, or never: it leaves the flag alone.
+    if (rc == RVA_OK && !p->primed && !stream_is_capturing(stream)) p->primed = true;
+    return rc;
+}
+
+int rva_yolov8_plan_set_static_rows(rva_yolov8_plan *p, int top, int bottom)
+{
+    if (!p) return RVA_ERR_ARG;
+    if (top < 0 || bottom > p->H || top >= bottom)
+        return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_set_static_rows: [%d, %d) is not a window of %d rows", top, bottom, p->H);
+    const char *e = getenv("RVA_PLAN_NO_STATIC_ROWS");
+    if (e && e[0] == '1') return RVA_OK;                   // A/B switch: the plan stays un-windowed
+    p->rows_top = top; p->rows_bottom = bottom;
+    propagate_rows(p);                                     // (an fp32 plan keeps whole images)
+    return RVA_OK;
+}
+
+int rva_yolov8_plan_step_rows(const rva_yolov8_plan *p, int step, int32_t *y0, int32_t *y1)
+{
+    if (!p || step < 0 || step >= (int)p->steps.size()) return RVA_ERR_ARG;
+    if (y0) *y0 = p->steps[step].y0;
+    if (y1) *y1 = p->steps[step].y1;
+    return RVA_OK;
+}
+
+// Output rows of a k x k, pad k / 2 convolution that see an input row of [lo, hi): row o reads o * stride - k / 2 .. + k - 1
+int rva_conv_rows_through(int k, int stride, int H_in, int lo, int hi, int32_t *out_lo, int32_t *out_hi)
+{
+    if ((k != 1 && k != 3) || (stride != 1 && stride != 2) || H_in <= 0 || lo < 0 || hi > H_in || lo >= hi || !out_lo || !out_hi) return RVA_ERR_ARG;
+    const int pad = k / 2, Ho = out_rows(H_in, k, stride);
+    // o * stride - pad + k - 1 >= lo  and  o * stride - pad <= hi - 1
+    int a = lo + pad - (k - 1), b = hi - 1 + pad;
+    a = a <= 0 ? 0 : (a + stride - 1) / stride;
+    b = b / stride + 1;
+    if (b > Ho) b = Ho;
+    if (a > b) a = b;
+    *out_lo = a; *out_hi = b;
+    return RVA_OK;
 }
 
 int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *output, rva_stream_t stream, rva_stream_t side1, rva_stream_t side2)
@@ -597,6 +773,7 @@ int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *outpu
     if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
     hipStream_t lanes[3] = {(hipStream_t)stream, (hipStream_t)side1, (hipStream_t)side2};
     bool started[3] = {true, false, false};
+    const bool win = p->primed;
     for (int i = 0; i < (int)p->steps.size(); ++i) {
         for (int l = 1; l <= 2; ++l)
             if (p->fork_step[l] == i) RVA_HIP(p->ctx, hipEventRecord(p->fork_ev[l], lanes[0]));      // everything the main lane has been given so far
@@ -605,7 +782,7 @@ int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *outpu
             RVA_HIP(p->ctx, hipStreamWaitEvent(lanes[s.lane], p->fork_ev[s.lane], 0));
             started[s.lane] = true;
         }
-        const int rc = launch_step(p, s, s.variant, input, output, (rva_stream_t)lanes[s.lane]);
+        const int rc = launch_step(p, s, s.variant, input, output, (rva_stream_t)lanes[s.lane], win);
         if (rc != RVA_OK) return rc;
     }
     for (int l = 1; l <= 2; ++l)
@@ -613,6 +790,7 @@ int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *outpu
             RVA_HIP(p->ctx, hipEventRecord(p->join_ev[l], lanes[l]));
             RVA_HIP(p->ctx, hipStreamWaitEvent(lanes[0], p->join_ev[l], 0));
         }
+    if (!p->primed && !stream_is_capturing(stream)) p->primed = true;       // as rva_yolov8_plan_run
     return RVA_OK;
 }
 

@@ -135,6 +135,10 @@ class HipYoloDetector(BaseDetector):
         self._post_bufs: dict = {}
         self._in_bufs: dict = {}
         self._in_border: dict = {}                        # batch size -> frame geometry whose letterbox border the buffer holds
+        # The same border lets the plan skip the rows of its early layers that only see it (FusedYoloV8.set_static_rows): per
+        # input buffer the content rows (top, bottom) of the geometry it holds, and whether the slot's plan has been told
+        self._rows: dict = {}                             # buffer key -> (top, bottom); the whole image where nothing is static
+        self._rows_told: dict = {}                        # buffer key -> the plan already runs with these rows
         self._post: Optional[ops.PostBuffers] = None      # result buffers of the latest call
         self._in: Optional[torch.Tensor] = None           # input tensor of the latest call
         # PipelinedTicks runs the networks of consecutive ticks on two streams: input tensor, letterbox-border state and
@@ -166,17 +170,29 @@ class HipYoloDetector(BaseDetector):
             steady = key is not None and self._in_border.get(n) == key
             res = ops.preprocess_nv12(frames, self.input_hw, self.half, out=self._in, ctx=self.ctx, content_only=steady)
             self._in_border[n] = key
+            if not steady:                                # new buffer, new geometry or ROI masks: the border was (re)written
+                lb = res[1]
+                self._note_rows(n, (int(lb.pad_top), int(lb.pad_top) + int(lb.new_h)) if key is not None else (0, self.input_hw[0]))
             return res
         dev = []
         for f in frames:  # host BGR ndarray (the reference's FramePacket.frame) or device tensor
             t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
             dev.append(t.to(self.device, non_blocking=True).contiguous())
         self._in_border[n] = None
+        self._note_rows(n, (0, self.input_hw[0]))         # K1 for host frames writes the whole tensor
         return ops.preprocess_bgr(dev, self.input_hw, self.half, out=self._in, ctx=self.ctx)
+
+    def _note_rows(self, n, rows) -> None:
+        """K1 has just written a whole input buffer whose rows outside ``rows`` will stay as they are on the steady ticks that
+        follow: the slot's plan hears of it before its next run (``_infer``), which then covers all rows once."""
+        rows = (max(rows[0], 0), min(rows[1], self.input_hw[0]))
+        self._rows[n] = rows
+        self._rows_told[n] = False
 
     def invalidate_engine(self) -> None:
         """Drop cached fused plans (call after editing ``self.net``'s weights)."""
         self._plans.clear()
+        self._rows_told.clear()
 
     def plan_for(self, tensor: torch.Tensor):
         """The fused plan of this batch shape and the current slot (built and autotuned on first use; a second slot's plan
@@ -187,12 +203,39 @@ class HipYoloDetector(BaseDetector):
         if plan is None:
             from .engine import FusedYoloV8
             first = self._plans.get(shape) if self._slot else None
+            # the static rows at construction: the tuner times the windowed launches, and a later slot's plan has the first
+            # slot's windows, whose kernel selection it takes over
+            n = shape[0] if self._slot == 0 else (shape[0], self._slot)
+            rows = first.static_rows if first is not None else self._rows.get(n)
             plan = self._plans[key] = FusedYoloV8(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
                                                   autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
-                                                  precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows)
+                                                  precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows,
+                                                  static_rows=rows if self.engine == "fused" else None)
             if first is not None:
                 plan.copy_tuning(first)
         return plan
+
+    def rows_pending(self, batch: int) -> bool:
+        """K1 has rewritten the border of the current slot's input buffer and the slot's plan has not run since."""
+        n = batch if self._slot == 0 else (batch, self._slot)
+        return not self._rows_told.get(n, True)
+
+    def _tell_rows(self, plan, tensor: torch.Tensor) -> None:
+        """Hand the plan the static rows K1 left in the slot's input buffer, once per (re)written border.  The promise is about
+        that buffer alone: any other tensor runs over all rows."""
+        batch = int(tensor.shape[0])
+        n = batch if self._slot == 0 else (batch, self._slot)
+        own = self._in_bufs.get(n)
+        if own is None or own.data_ptr() != tensor.data_ptr() or n not in self._rows:
+            if plan.static_rows != (0, plan.H):
+                plan.set_static_rows(0, plan.H)
+                if n in self._rows:
+                    self._rows_told[n] = False
+            return
+        if self._rows_told.get(n, True):
+            return
+        plan.set_static_rows(*self._rows[n])              # also where the rows are unchanged: the border bytes may be new
+        self._rows_told[n] = True
 
     def _infer(self, tensor: torch.Tensor):
         """The head tensor of the batch; with ``hip_box_rows: fp32`` an ``ops.SplitHead`` (head tensor, fp32 box rows)."""
@@ -202,6 +245,8 @@ class HipYoloDetector(BaseDetector):
             if tensor.dtype != torch.float16:
                 raise TypeError("half detector: the fused plan takes the fp16 tensor K1 writes")
             plan = self.plan_for(tensor)
+            if not torch.cuda.is_current_stream_capturing():
+                self._tell_rows(plan, tensor)
             plan(tensor.contiguous())
             return plan.result()
         if self.engine == "fused-f32":

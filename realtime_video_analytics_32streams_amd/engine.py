@@ -17,6 +17,9 @@ activations, weights and ``[B, 4+nc, A]`` fp32 output; kernels of ``csrc/rva_con
 ``box_rows="fp32"`` (fp16 plans, opt-in; ``RVA_PLAN_BOX_F32``) makes the head kernels also store the four box rows as an fp32 side
 tensor ``boxes32[B, 4, A]`` of the same output slot -- one allocation with the head tensor, which is still written in full and is
 bit-identical to the default plan's; ``ops.postprocess(..., boxes=plan.boxes32)`` reads its boxes from it.
+``static_rows=(top, bottom)`` (fp16 plans) is the caller's promise that the input rows outside that window -- a letterbox border --
+hold the same bytes on every run: after one priming run over all rows the early layers launch only the output rows that depend on
+the window (``rva_yolov8_plan_set_static_rows``, include/rva.h); results are bit-identical.
 No host synchronisation and no allocation after construction: a whole tick can be captured into a hipGraph.
 """
 from __future__ import annotations
@@ -83,12 +86,13 @@ class _VariantCell:
     def __setitem__(self, key, value):
         assert key == "variant"
         self.eng.ctx.check(self.eng.L.rva_yolov8_plan_set_variant(self.eng.handle, self.idx, int(value)), "rva_yolov8_plan_set_variant")
+        self.eng.primed = False            # as in the C plan: the next complete run covers all rows again
 
 
 class FusedYoloV8:
     def __init__(self, net: YoloV8, batch: int, hw: Tuple[int, int] = (640, 640), device: Optional[torch.device] = None,
                  ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16",
-                 box_rows: str = "fp16"):
+                 box_rows: str = "fp16", static_rows: Optional[Tuple[int, int]] = None):
         import os
         if precision not in ("fp16", "fp32"):
             raise ValueError(f"precision must be 'fp16' or 'fp32', not {precision!r}")
@@ -134,6 +138,13 @@ class FusedYoloV8:
             self.ctx.check(self.L.rva_yolov8_plan_create(self.ctx.handle, C.byref(d), arr, C.byref(h)), "rva_yolov8_plan_create")
         self.handle = h
         del keep
+        # row windows: set before the tuner runs, so that it times the windowed launches -- what will run
+        self.static_rows = (0, self.H)
+        self.rows_epoch = 0                # bumped by every set_static_rows: a hipGraph recorded with windows is good for one epoch
+        self.primed = False                # mirror of the C plan's flag: a complete eager run has covered all rows
+        if static_rows is not None and tuple(static_rows) != (0, self.H) and os.environ.get("RVA_PLAN_NO_STATIC_ROWS") != "1":
+            self.ctx.check(self.L.rva_yolov8_plan_set_static_rows(h, int(static_rows[0]), int(static_rows[1])), "rva_yolov8_plan_set_static_rows")
+            self.static_rows = (int(static_rows[0]), int(static_rows[1]))
         info = [C.c_int32() for _ in range(5)]
         self.ctx.check(self.L.rva_yolov8_plan_info(h, *[C.byref(v) for v in info]), "rva_yolov8_plan_info")
         self.A, rows, self._n_steps, n_tun, self.quiet_step = (int(v.value) for v in info)
@@ -152,19 +163,40 @@ class FusedYoloV8:
         self._outs = {0: self.out}
         self.fused_stem = not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
         # (launch(stream, variant) -> rc, state["variant"], "Cin->Cout kKsS HxW") per convolution step, as the tuner and the tools use them
-        self._tunable = []
-        buf = C.create_string_buffer(96)
-        for i in range(n_tun):
-            self.ctx.check(self.L.rva_yolov8_plan_tunable_desc(h, i, buf, 96), "rva_yolov8_plan_tunable_desc")
-
-            def launch(stream, variant, i=i):
-                return self.L.rva_yolov8_plan_launch_tunable(self.handle, i, variant, C.c_void_p(self.out.data_ptr()), stream)
-            self._tunable.append((launch, _VariantCell(self, i), buf.value.decode()))
+        self._n_tunable = n_tun
+        self._read_tunables()
         self._side = None                   # two side streams for the detect branches, created on first use
         self._forks = bool(self.fused_head_lanes())
         self.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1"      # A/B switch for measurements
         if autotune:
             self.autotune()
+
+    def _read_tunables(self) -> None:
+        self._tunable = []
+        buf = C.create_string_buffer(96)
+        for i in range(self._n_tunable):
+            self.ctx.check(self.L.rva_yolov8_plan_tunable_desc(self.handle, i, buf, 96), "rva_yolov8_plan_tunable_desc")
+
+            def launch(stream, variant, i=i):
+                return self.L.rva_yolov8_plan_launch_tunable(self.handle, i, variant, C.c_void_p(self.out.data_ptr()), stream)
+            self._tunable.append((launch, _VariantCell(self, i), buf.value.decode()))
+
+    def set_static_rows(self, top: int, bottom: int) -> None:
+        """Input rows outside ``[top, bottom)`` hold the same bytes on every run from now on (``(0, H)``: no such rows).  The plan
+        is unprimed afterwards: its next complete run covers all rows.  The kernel selection stays as it is (a selection made
+        for other windows is still correct: a kernel that cannot restrict rows runs them all)."""
+        self.ctx.check(self.L.rva_yolov8_plan_set_static_rows(self.handle, int(top), int(bottom)), "rva_yolov8_plan_set_static_rows")
+        if os.environ.get("RVA_PLAN_NO_STATIC_ROWS") == "1":
+            return                         # A/B switch: the library made the call a no-op
+        self.static_rows = (int(top), int(bottom))
+        self.rows_epoch += 1
+        self.primed = False
+        self._read_tunables()              # the descriptions carry the windows
+
+    def step_rows(self, step: int) -> Tuple[int, int]:
+        y0, y1 = C.c_int32(), C.c_int32()
+        self.ctx.check(self.L.rva_yolov8_plan_step_rows(self.handle, int(step), C.byref(y0), C.byref(y1)), "rva_yolov8_plan_step_rows")
+        return int(y0.value), int(y1.value)
 
     def _alloc_split(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """One allocation in the plan's output layout: the fp16 head, then ``boxes32`` at the offset the plan reports."""
@@ -344,7 +376,7 @@ class FusedYoloV8:
         n_over = int(os.environ.get("RVA_TUNE_OVERLAP", "3"))
         if n_over >= 2:
             twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision,
-                                 box_rows=self.box_rows)
+                                 box_rows=self.box_rows, static_rows=self.static_rows)
                      for _ in range(n_over - 1)]
             from .ops import chain_streams
             streams = chain_streams(self.dev, n_over)                  # the streams the pipeline's tick chains will run on
@@ -423,6 +455,7 @@ class FusedYoloV8:
                 self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
             self.ctx.check(self.L.rva_yolov8_plan_run_lanes(self.handle, xin, out, stream, C.c_void_p(self._side[0].cuda_stream),
                                                             C.c_void_p(self._side[1].cuda_stream)), "rva_yolov8_plan_run_lanes")
+            self.primed = self.primed or not torch.cuda.is_current_stream_capturing()
             return self.out
         ev = getattr(self, "phase_event", None)
         if ev is not None:
@@ -432,6 +465,7 @@ class FusedYoloV8:
                            "rva_yolov8_plan_run_range")
         else:
             self.ctx.check(self.L.rva_yolov8_plan_run(self.handle, xin, out, stream), "rva_yolov8_plan_run")
+            self.primed = self.primed or not torch.cuda.is_current_stream_capturing()
         return self.out
 
     def use_output(self, index: int) -> torch.Tensor:

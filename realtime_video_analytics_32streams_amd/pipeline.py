@@ -517,6 +517,7 @@ class PipelinedTicks:
         self._seen_sigs = set()               # tick shapes that have run eagerly once
         self._cap_sig = None                  # the captured shape
         self._net_graphs: List[List] = []     # [group][parity]
+        self._net_epochs: List[List] = []     # [group][parity]: the plan's rows_epoch a graph recorded with row windows is good for
         self._post_graphs = [None] * ns
         self._captured = False
 
@@ -560,10 +561,11 @@ class PipelinedTicks:
         p = self.pipe
         torch.cuda.synchronize()
         self._net_graphs = []
+        self._net_epochs = []
         raws = [[None] * self.nslots for _ in plan.groups]
         for gi, g in enumerate(plan.groups):
             det = p.detectors[g.det]
-            pair = []
+            pair, epochs = [], []
             for par in range(self.nslots):
                 self._set_slot(par)
                 # the slot's own input tensor (tick chains: one per slot; it exists once the slot has run, else it is made here)
@@ -575,6 +577,10 @@ class PipelinedTicks:
                 # head tensor (group, parity): a stable buffer of the plan (two network streams: of the parity's own plan)
                 fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
                 raws[gi][par] = fp.result()                        # (with hip_box_rows: fp32 the slot's side tensor rides along)
+                # A primed plan with static rows records its windowed launches: good while the border in the slot's input buffer
+                # stays.  A slot that has not run yet records every step over all rows: slower, good for any input.
+                windows = getattr(fp, "primed", False) and getattr(fp, "static_rows", None) != (0, getattr(fp, "H", 0))
+                epochs.append(fp.rows_epoch if windows else None)
                 if self.net_graph:
                     gr = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gr):
@@ -582,6 +588,7 @@ class PipelinedTicks:
                             det.stage_net(pre_par)                 # network only, writes that head tensor
                     pair.append(gr)
             self._net_graphs.append(pair)
+            self._net_epochs.append(epochs)
         torch.cuda.synchronize()
         for par in range(self.nslots):
             mo = None if motion is None else (p._motion_gate().counts[par], motion[1])   # the parity's K5 count row
@@ -595,6 +602,15 @@ class PipelinedTicks:
         self._set_slot(0)
         self._cap_sig = plan.signature
         self._captured = True
+
+    def _net_graph_ok(self, det, gi, par, pre) -> bool:
+        """Whether the recorded network of (group, slot) may stand in for this tick's: one recorded with row windows only while
+        K1 has not rewritten the border it was primed on (such a tick runs eagerly, which primes the plan again)."""
+        epoch = self._net_epochs[gi][par]
+        if epoch is None:
+            return True
+        fp = det.plan_for(pre[0])
+        return fp.rows_epoch == epoch and not det.rows_pending(int(pre[0].shape[0]))
 
     def _issue_post(self, k, after, stream=None):
         par, prev = k % self.nslots, (k - 1) % self.nslots
@@ -672,7 +688,7 @@ class PipelinedTicks:
                 if self.two_streams and gi == 0 and k >= self.nslots:
                     sa.wait_event(self._done[par])                 # the slot's previous tick has finished reading its head tensors
                 pres.append(pre)
-                if replay and self.net_graph and self.replay_net:
+                if replay and self.net_graph and self.replay_net and self._net_graph_ok(det, gi, par, pre):
                     self._net_graphs[gi][par].replay()
                 else:
                     with torch.inference_mode():
