@@ -480,6 +480,26 @@ int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void 
  *   (0, height) switches windowing off (the default).  RVA_ERR_ARG for a window outside [0, height] or top >= bottom.  fp32
  *   plans accept the call and stay un-windowed.  RVA_PLAN_NO_STATIC_ROWS=1 in the environment makes the call a no-op (A/B).
  *   _tunable_desc carries a window that is not the whole image (" r[y0,y1)"): such layers are tuned, and persisted, apart.
+ * Capacity (_run_n / _run_lanes_n / _run_range_n): desc.batch is the plan's capacity B, and a call runs the n leading images,
+ *   1 <= n <= B (RVA_ERR_ARG otherwise, before anything is launched): input = [n,3,height,width]; images [0, n) of `output` are
+ *   written, which keeps the layout [B, 4+nc, anchors] -- with RVA_PLAN_BOX_F32 boxes32 stays at the boxes_offset that
+ *   _output_layout reports for B.  Image b lies where it lies in a full run, and nothing of the images >= n is written, in
+ *   `output` or in any activation buffer.  Every step launches the kernel a full run launches -- variant 0 chooses from B, not from
+ *   n -- so images [0, n) are bit-identical to the same images of a full run on the same plan, fp16 and fp32, whatever the images
+ *   >= n hold.  _run / _run_lanes / _run_range are the _n forms with n = B.  (One plan of the largest batch serves every
+ *   smaller one: no second set of buffers, weights or kernel selections, and a stream's result does not depend on how many
+ *   other streams delivered a frame.)
+ *   Static rows with a capacity: "primed" is a count P of leading images whose buffers hold a whole run's rows for the current
+ *   windows and variants (_primed_images reads it).  Create, _set_static_rows and _set_variant set P = 0.  A complete run
+ *   (_run_n / _run_lanes_n) outside stream capture launches row windows if n <= P; otherwise it launches all rows of all n
+ *   images and sets P = n.  _run_range_n never changes P and launches windows only if n <= P; a run under stream capture
+ *   launches by P as it stands and leaves it alone.  The promise of _set_static_rows covers every image the caller passes.
+ *   Precondition (fp16 plans): a convolution whose Cin is not a multiple of 32 runs with Cin rounded up and zero weights for
+ *   the extra channels, so it reads up to 31 channels past its slice: the next slice of the row, the next pixel or, behind the
+ *   last pixel of image n - 1, stale bytes of image n.  Those bytes are multiplied by zero and must be FINITE.  Create
+ *   zero-fills every buffer and every kernel writes finite values for finite inputs and weights, so the precondition holds as
+ *   long as no run was fed non-finite input or weights; after such a run the images it covered must be run again with finite
+ *   input (all rows: _set_static_rows first) before a smaller n is trusted.
  * -------------------------------------------------------------------------------------------- */
 #define RVA_PLAN_NO_STEM2 1   /* rva_yolov8_desc.flags: stem and first downsampling convolution as two launches (A/B switch) */
 #define RVA_PLAN_NO_CIN_PAD 2 /* ... convolutions with Cin % 32 != 0 keep their Cin (default: declared rounded up to 32, zero weights) */
@@ -515,6 +535,11 @@ int rva_yolov8_plan_launch_tunable(rva_yolov8_plan *plan, int index, int variant
 int rva_yolov8_plan_set_variant(rva_yolov8_plan *plan, int index, int variant);
 int rva_yolov8_plan_get_variant(const rva_yolov8_plan *plan, int index);
 int rva_yolov8_plan_set_static_rows(rva_yolov8_plan *plan, int top, int bottom);
+int rva_yolov8_plan_run_n(rva_yolov8_plan *plan, const void *input, void *output, int n, rva_stream_t stream);
+int rva_yolov8_plan_run_lanes_n(rva_yolov8_plan *plan, const void *input, void *output, int n, rva_stream_t stream, rva_stream_t side1,
+                                rva_stream_t side2);
+int rva_yolov8_plan_run_range_n(rva_yolov8_plan *plan, const void *input, void *output, int n, int first, int last, rva_stream_t stream);
+int rva_yolov8_plan_primed_images(const rva_yolov8_plan *plan);
 int rva_yolov8_plan_step_rows(const rva_yolov8_plan *plan, int step, int32_t *y0, int32_t *y1);
 
 /* ----------------------------------------------------------------------------------------------

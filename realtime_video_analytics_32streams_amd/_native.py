@@ -254,6 +254,10 @@ def lib() -> C.CDLL:
         "rva_yolov8_plan_get_variant": (C.c_int, [_P, C.c_int]),
         "rva_yolov8_plan_set_static_rows": (C.c_int, [_P, C.c_int, C.c_int]),
         "rva_yolov8_plan_step_rows": (C.c_int, [_P, C.c_int, i32p, i32p]),
+        "rva_yolov8_plan_run_n": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+        "rva_yolov8_plan_run_lanes_n": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
+        "rva_yolov8_plan_run_range_n": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_yolov8_plan_primed_images": (C.c_int, [_P]),
         "rva_cnnlstm_plan_create": (C.c_int, [_P, C.POINTER(CnnLstmDesc), C.POINTER(CnnLstmWeights), C.POINTER(_P)]),
         "rva_cnnlstm_plan_destroy": (None, [_P]),
         "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
@@ -308,7 +312,8 @@ EXPORTS = [
     "rva_yolov8_plan_output_layout",
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",
-    "rva_yolov8_plan_get_variant", "rva_yolov8_plan_set_static_rows", "rva_yolov8_plan_step_rows", "rva_conv2d_nhwc_f16_rows",
+    "rva_yolov8_plan_get_variant", "rva_yolov8_plan_set_static_rows", "rva_yolov8_plan_step_rows", "rva_yolov8_plan_run_n",
+    "rva_yolov8_plan_run_lanes_n", "rva_yolov8_plan_run_range_n", "rva_yolov8_plan_primed_images", "rva_conv2d_nhwc_f16_rows",
     "rva_stem2_f16_rows", "rva_conv_rows_through", "rva_cnnlstm_plan_create", "rva_cnnlstm_plan_destroy", "rva_cnnlstm_plan_info", "rva_cnnlstm_plan_run",
     "rva_cnnlstm_plan_run_post", "rva_cnnlstm_plan_stage", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
     "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage", "rva_resnet_plan_create", "rva_resnet_plan_destroy", "rva_resnet_plan_info",

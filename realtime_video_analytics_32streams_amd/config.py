@@ -30,6 +30,14 @@ rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of
 0.25 px between 256 and 512; ``"fp32"`` = the head kernels also write them as an fp32 side tensor and the post-process
 reads its boxes from there (class rows stay fp16).  With ``half: false`` the boxes are fp32 already and the key is
 accepted without effect, as it is for a detector that is given an ``infer_fn`` (no plan).
+
+``hip_plan_capacity`` (an integer >= 0) says how the YOLO plans (engines ``"fused"`` and ``"fused-f32"``) serve the batch of
+a tick, which is the number of streams that delivered a frame: ``0`` (default; what a reference YAML gets) = one plan and one
+input buffer per batch size, built when that size first occurs; ``N > 0`` = ONE plan and one input buffer of ``N`` images per
+input size (and pipeline slot), of which a tick runs its leading ``n <= N`` (``rva_yolov8_plan_run_n``): no plan is built in
+the middle of a run when a stream drops a frame, and a stream's head tensor does not depend on how many others delivered one.
+A group of more than ``N`` frames gets an exact-size plan as with ``0``, and a warning in the log.  No effect behind an
+``infer_fn`` or on the PyTorch-ROCm engine (``half: false`` with ``hip_engine: auto``).
 """
 from __future__ import annotations
 
@@ -117,11 +125,14 @@ class DetectorConfig:
     num_action_classes: int = 400
     hip_engine: str = "auto"                # backend "hip": "auto", "plan" or "native" (module docstring)
     hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
+    hip_plan_capacity: int = 0              # backend "hip", YOLO plans: 0 = a plan per batch size, N = one plan of N images (module docstring)
 
     def validate(self) -> None:
         _need(bool(self.model_path), "Detector model_path must not be empty")
         _need(self.hip_engine in HIP_ENGINES, f"hip_engine must be one of {set(HIP_ENGINES)}")
         _need(self.hip_box_rows in HIP_BOX_ROWS, f"hip_box_rows must be one of {set(HIP_BOX_ROWS)}")
+        _need(isinstance(self.hip_plan_capacity, int) and not isinstance(self.hip_plan_capacity, bool) and self.hip_plan_capacity >= 0,
+              "hip_plan_capacity must be an integer >= 0")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,
               f"Detector backend must be one of {set(REFERENCE_BACKENDS + HIP_BACKENDS)}")
         _need(self.model_type in MODEL_TYPES, f"Model type must be one of {set(MODEL_TYPES)}")

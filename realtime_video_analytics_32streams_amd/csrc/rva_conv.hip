@@ -3471,6 +3471,7 @@ __global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
 struct ConvCall {
     ConvArgs a;               // validated, Ho / Wo / M / CinPad derived; n_tiles, m_tiles and CoutPad are the family's to set
     int batch, ksize;
+    int sel_batch;            // the batch variant 0 chooses its kernel for, >= batch: a plan's capacity (rva_conv2d_nhwc_f16_sel), else batch
     int cpad;                 // Cout rounded up to 64: what the caller padded the weights to (rva_conv_cout_pad)
     int num_cus;
     hipStream_t s;
@@ -3616,19 +3617,36 @@ hipError_t launch_variant(int variant, const ConvCall &c);
 // variant 0's first choice is the LDS-DMA gather tile gb2<128,128> (37): 1x1 stride 1 and 3x3 stride 2 with whole 64-channel steps
 inline bool auto_picks_gather(int Cin, int ksize, int stride) { return Cin % 64 == 0 && ((ksize == 3 && stride == 2) || (ksize == 1 && stride == 1)); }
 
+// The limits of variant 0's first choices that grow with the batch (launch_big: 21 / 23 / 25 / 31, launch_gbig1: 37), taken
+// at the selection batch: where a launch of sel_batch images would fall back, a launch of fewer of them falls back as well.
+inline bool first_choice_fits(const ConvCall &c, int pick)
+{
+    const ConvArgs &a = c.a;
+    if (pick == 37) {
+        const long m = (long)c.sel_batch * (c.y1 - c.y0) * a.Wo;
+        return m < (1 << 24) && (size_t)a.H * a.W * (size_t)(c.sel_batch + 1) * a.ldi * 2 < (1ull << 32);
+    }
+    const long m = (long)c.sel_batch * a.Ho * a.Wo;
+    return m < (1 << 24) && (size_t)m * a.ldi * 2 < (1ull << 32);
+}
+
 // Variant 0, for callers that do not autotune.  First the LDS-DMA kernels wherever their channel constraints hold, tile
 // picked from the autotune tables of the YOLOv8 layers (tools/show_tuning.py); if that launch fails for any reason, the
 // resident kernel with the largest tile that still yields two tiles per CU; if its geometry does not fit, the gather kernel.
+// Every size test reads the SELECTION batch (ConvCall::sel_batch), never the batch of the launch: a plan that runs n of its B
+// images launches the kernel its full run launches, and image b comes out bit for bit the same whatever n is.
 hipError_t v_auto(const ConvCall &c)
 {
     const ConvArgs &a = c.a;
     const int cpad = c.cpad;
     const bool bn128 = cpad % 128 == 0;
+    const long selM = (long)c.sel_batch * a.Ho * a.Wo;
     int pick = 0;
     if (is_3x3(c, 1) && a.Cin % 32 == 0)
-        pick = bn128 ? ((long)a.M * a.Cout >= 20000000L ? 25 : 21) : (a.M >= 100000 ? 31 : 23);
+        pick = bn128 ? (selM * a.Cout >= 20000000L ? 25 : 21) : (selM >= 100000 ? 31 : 23);
     else if (auto_picks_gather(a.Cin, c.ksize, a.stride))
         pick = 37;
+    if (pick && !first_choice_fits(c, pick)) pick = 0;
     if (c.windowed()) return pick == 37 ? launch_variant(37, c) : hipErrorInvalidValue;      // a row window: the gather tile or nothing
     if (pick) {
         if (launch_variant(pick, c) == hipSuccess) return hipSuccess;
@@ -3639,25 +3657,25 @@ hipError_t v_auto(const ConvCall &c)
         hipError_t e = hipErrorInvalidValue;
         if (c.ksize == 3) {
             // tile = 256 px x 128 ch when that yields enough tiles for every CU, else smaller tiles
-            const long t256 = (long)c.batch * rva_ceil_div(a.H * a.W, 256), t128 = (long)c.batch * rva_ceil_div(a.H * a.W, 128);
+            const long t256 = (long)c.sel_batch * rva_ceil_div(a.H * a.W, 256), t128 = (long)c.sel_batch * rva_ceil_div(a.H * a.W, 128);
             if (bn128 && t256 * (cpad / 128) >= want) e = launch_variant(7, c);
             if (e == hipErrorInvalidValue && t256 * (cpad / 64) >= want) e = launch_variant(5, c);
             if (e == hipErrorInvalidValue && bn128 && t128 * (cpad / 128) >= want) e = launch_variant(8, c);
             if (e == hipErrorInvalidValue) e = launch_variant(6, c);
         } else if (a.CinPad % 128 == 0) {
-            const long t256 = rva_ceil_div(a.M, 256);
+            const long t256 = (selM + 255) / 256;
             if (bn128 && t256 * (cpad / 128) >= want) e = launch_variant(7, c);
             if (e == hipErrorInvalidValue && t256 * (cpad / 64) >= want) e = launch_variant(5, c);
             if (e == hipErrorInvalidValue) e = launch_variant(6, c);
         } else {
-            const long t256 = rva_ceil_div(a.M, 256);
+            const long t256 = (selM + 255) / 256;
             e = launch_variant(t256 * (cpad / 64) >= want ? 5 : 6, c);
         }
         if (e != hipErrorInvalidValue) return e;
         (void)hipGetLastError();   // geometry does not fit the resident kernel: fall through to the gather kernel
     }
     // small problems: 128-pixel tiles keep more CUs busy
-    const bool small = (long)rva_ceil_div(a.M, 256) * (cpad / (bn128 ? 128 : 64)) < 512;
+    const bool small = (selM + 255) / 256 * (cpad / (bn128 ? 128 : 64)) < 512;
     return launch_variant(bn128 ? (small ? 4 : 3) : (small ? 2 : 1), c);
 }
 
@@ -3878,8 +3896,8 @@ int rva_conv2d_nhwc_f16_v(rva_ctx *ctx, const void *in, int ldi, const void *wei
                           int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
                           int stride, int act, int variant, rva_stream_t stream_)
 {
-    return rva_conv2d_nhwc_f16_rows(ctx, in, ldi, weights, bias, out, ldo, residual, ldr, batch, H, W, Cin, Cout, ksize, stride, act,
-                                    variant, 0, -1, stream_);
+    return rva_conv2d_nhwc_f16_sel(ctx, in, ldi, weights, bias, out, ldo, residual, ldr, batch, batch, H, W, Cin, Cout, ksize, stride, act,
+                                   variant, 0, -1, stream_);
 }
 
 // The same restricted to the output rows [y0, y1) of every image: only those rows are computed and written; their inputs are
@@ -3889,9 +3907,21 @@ int rva_conv2d_nhwc_f16_rows(rva_ctx *ctx, const void *in, int ldi, const void *
                              int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
                              int stride, int act, int variant, int y0, int y1, rva_stream_t stream_)
 {
+    return rva_conv2d_nhwc_f16_sel(ctx, in, ldi, weights, bias, out, ldo, residual, ldr, batch, batch, H, W, Cin, Cout, ksize, stride, act,
+                                   variant, y0, y1, stream_);
+}
+
+}  // extern "C"
+
+// The same for `batch` leading images of a buffer of sel_batch: variant 0 chooses the kernel it chooses for sel_batch images
+// (the YOLOv8 plan's capacity, rva_yolov8_plan_run_n); a numbered variant is the same kernel for every batch anyway.
+int rva_conv2d_nhwc_f16_sel(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
+                            int ldo, const void *residual, int ldr, int batch, int sel_batch, int H, int W, int Cin, int Cout, int ksize,
+                            int stride, int act, int variant, int y0, int y1, rva_stream_t stream_)
+{
     if (!ctx) return RVA_ERR_ARG;
     const ConvVariant *row = find_variant(variant);
-    if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) ||
+    if (!in || !weights || !bias || !out || batch <= 0 || sel_batch < batch || H <= 0 || W <= 0 || (ksize != 1 && ksize != 3) ||
         (stride != 1 && stride != 2) || Cin % 8 || Cout % 8 || ldi % 8 || ldo % 8 || (residual && ldr % 8) || !row ||
         ((uintptr_t)in | (uintptr_t)out | (uintptr_t)weights | (uintptr_t)residual) % 16)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_conv2d_nhwc_f16: unsupported shape/alignment (Cin%%8, Cout%%8, ld%%8, 16-byte pointers)");
@@ -3908,7 +3938,7 @@ int rva_conv2d_nhwc_f16_rows(rva_ctx *ctx, const void *in, int ldi, const void *
     if (y1 < 0) y1 = a.Ho;
     if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_conv2d_nhwc_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
     c.y0 = y0; c.y1 = y1;
-    c.batch = batch; c.ksize = ksize;
+    c.batch = batch; c.sel_batch = sel_batch; c.ksize = ksize;
     c.cpad = rva_ceil_div(Cout, 64) * 64;
     c.num_cus = rva_num_cus(ctx);
     c.s = (hipStream_t)stream_;
@@ -3918,6 +3948,8 @@ int rva_conv2d_nhwc_f16_rows(rva_ctx *ctx, const void *in, int ldi, const void *
     if (ev == hipErrorInvalidValue) return rva_fail(ctx, RVA_ERR_ARG, "conv variant %d not applicable here", variant);
     return rva_fail(ctx, RVA_ERR_HIP, "conv variant %d: launch failed: %s", variant, hipGetErrorString(ev));
 }
+
+extern "C" {
 
 int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, const void *skip, int ld_skip, int c_skip,
                           const void *weights, const float *bias, void *out, int ldo, int batch, int H, int W, int Cout,

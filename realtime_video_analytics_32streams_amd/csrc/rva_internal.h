@@ -84,6 +84,12 @@ bool rva_conv_variant_is_gather64(int variant);
 // fp16 variants whose kernel takes an output row window (rva_conv2d_nhwc_f16_rows); variant 0 by the shape it would pick for
 bool rva_conv_variant_rows(int variant, int Cin, int ksize, int stride);
 
+// rva_conv2d_nhwc_f16_rows on the `batch` leading images of buffers that hold sel_batch (>= batch): variant 0 chooses its kernel
+// from sel_batch, so that the kernel -- and with it every bit of an image -- does not depend on how many images a call runs
+int rva_conv2d_nhwc_f16_sel(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out, int ldo,
+                            const void *residual, int ldr, int batch, int sel_batch, int H, int W, int Cin, int Cout, int ksize, int stride,
+                            int act, int variant, int y0, int y1, rva_stream_t stream);
+
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);
 

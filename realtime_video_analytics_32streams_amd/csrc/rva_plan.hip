@@ -16,6 +16,13 @@
 // list (propagate_rows); after one complete run over all rows has filled every buffer ("primed"), the steps whose kernel takes a
 // row window launch that window only.  The rows outside it keep the bytes of the priming run.
 //
+// Capacity (rva_yolov8_plan_run_n): desc.batch is the number of images the buffers hold, and a run takes the n <= batch leading
+// ones.  Image b lies where it lies in a full run (NHWC: an image's offset does not depend on the batch), every step launches
+// the kernel a full run launches (a fixed variant is one kernel; variant 0 chooses from the capacity, rva_conv2d_nhwc_f16_sel;
+// the fp32 kernels give the same bits for every tile and batch), so images [0, n) come out bit for bit as in a full run and
+// nothing of the images behind them is written.  "Primed" is therefore a count: the leading images whose buffers hold a whole
+// run's rows.
+//
 // Graph (ultralytics YOLOv8 n / s / m / l / x: widths c1..c5, C2f depths, nc classes, reg_max 16):
 //   b0 stem 3x3 s2 | b1 3x3 s2 | b2 C2f | b3 3x3 s2 | b4 C2f | b5 3x3 s2 | b6 C2f | b7 3x3 s2 | b8 C2f | b9 SPPF |
 //   h12 C2f(cat[up(p5), p4]) | h15 C2f(cat[up(n4), p3]) | h16 3x3 s2 | h18 C2f(cat[h16, n4]) | h19 3x3 s2 | h21 C2f(cat[h19, p5]) |
@@ -76,7 +83,7 @@ struct rva_yolov8_plan {
     size_t box_off = 0;                   // ... at this byte offset of `output` (rva_yolov8_plan_output_layout)
     int rows_top = 0, rows_bottom = 0;    // input rows outside [top, bottom) are static (set_static_rows); (0, H) = none
     bool windowed = false;                // some step's window is smaller than its image
-    bool primed = false;                  // every buffer holds a whole run's rows for the current windows and variants
+    int primed = 0;                       // leading images whose buffers hold a whole run's rows for the current windows and variants
 };
 
 namespace {
@@ -459,38 +466,40 @@ bool step_takes_rows(const Step &s, int variant)
     return s.kind == K_CONV && rva_conv_variant_rows(variant, s.Cin, s.k, s.stride);
 }
 
+// n: the leading images of every buffer the launch covers (the boxes32 side tensor stays where the capacity puts it).
 // win: launch the step's row window where its kernel takes one (a primed plan; the tuner), else all rows
-int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *input, void *output, rva_stream_t st, bool win)
+int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *input, void *output, int n, rva_stream_t st, bool win)
 {
     rva_ctx *c = p->ctx;
     if (win && (s.y0 > 0 || s.y1 < s.Ho) && step_takes_rows(s, variant)) {
-        if (s.kind == K_STEM2) return rva_stem2_f16_rows(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, p->B, s.H, s.W, s.y0, s.y1, st);
-        return rva_conv2d_nhwc_f16_rows(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act,
-                                        variant, s.y0, s.y1, st);
+        if (s.kind == K_STEM2) return rva_stem2_f16_rows(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, s.y0, s.y1, st);
+        return rva_conv2d_nhwc_f16_sel(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act,
+                                       variant, s.y0, s.y1, st);
     }
     if (p->box32 && output) {             // the two launch forms that write box rows, with the side tensor of this output
         float *boxes = (float *)((char *)output + p->box_off);
         if (s.kind == K_HEAD && s.mode == 1)
-            return rva_conv1x1_head_box32_f16(c, s.in, s.ldi, s.w, s.b, p->B, s.H, s.W, s.Cin, output, boxes, p->nc, p->A, s.a0, s.stride_px, variant, st);
+            return rva_conv1x1_head_box32_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, output, boxes, p->nc, p->A, s.a0, s.stride_px, variant, st);
         if (s.kind == K_HEAD3)
-            return rva_yolo_head3_box32_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, boxes, p->B, s.hh, s.hw, p->nc, p->A, s.hs, st);
+            return rva_yolo_head3_box32_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, boxes, n, s.hh, s.hw, p->nc, p->A, s.hs, st);
     }
     switch (s.kind) {
-    case K_CONV: return rva_conv2d_nhwc_f16_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
-    case K_UPCAT: return rva_conv1x1_upcat_f16(c, s.in, s.ldi, s.c_in, s.in2, s.ldi2, s.c_in2, s.w, s.b, s.out, s.ldo, p->B, s.H, s.W, s.Cout, s.act, variant, st);
-    case K_HEAD: return rva_conv1x1_head_f16(c, s.in, s.ldi, s.w, s.b, p->B, s.H, s.W, s.Cin, s.Cout, s.mode, output, p->nc, p->A, s.a0, s.stride_px, variant, st);
-    case K_PAIR32: return rva_c2f_pair32_f16(c, s.in, s.ldi, s.w, s.b, s.w2, s.b2, s.out, s.ldo, p->B, s.H, s.W, st);
-    case K_STEM2: return rva_stem2_f16(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, p->B, s.H, s.W, st);
-    case K_STEM: return rva_stem_conv_f16(c, input, s.w, s.b, s.out, s.ldo, p->B, s.H, s.W, s.Cout, st);
-    case K_SPPF3: return rva_sppf_pool3_nhwc_f16(c, s.in, s.ldi, s.out, s.out2, s.out3, s.ldo, p->B, s.H, s.W, s.Cin, st);
-    case K_POOL5: return rva_maxpool5_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
-    case K_UP2: return rva_upsample2x_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
-    case K_HEAD3: return rva_yolo_head3_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, p->B, s.hh, s.hw, p->nc, p->A, s.hs, st);
-    case K_CONV_F32: return rva_conv2d_nhwc_f32_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
-    case K_STEM_F32: return rva_stem_conv_f32(c, input, s.w, s.b, s.out, s.ldo, p->B, s.H, s.W, s.Cout, st);
-    case K_POOL5_F32: return rva_maxpool5_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
-    case K_UP2_F32: return rva_upsample2x_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, p->B, s.H, s.W, s.Cin, st);
-    case K_HEAD_F32: return rva_yolo_head_f32(c, s.in, s.ldi, s.in2, s.ldi2, output, p->B, s.H, s.W, p->nc, p->A, s.a0, s.stride_px, st);
+    case K_CONV: return rva_conv2d_nhwc_f16_sel(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant,
+                                                0, -1, st);     // variant 0 chooses as for the capacity
+    case K_UPCAT: return rva_conv1x1_upcat_f16(c, s.in, s.ldi, s.c_in, s.in2, s.ldi2, s.c_in2, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, s.act, variant, st);
+    case K_HEAD: return rva_conv1x1_head_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, s.Cout, s.mode, output, p->nc, p->A, s.a0, s.stride_px, variant, st);
+    case K_PAIR32: return rva_c2f_pair32_f16(c, s.in, s.ldi, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, st);
+    case K_STEM2: return rva_stem2_f16(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, st);
+    case K_STEM: return rva_stem_conv_f16(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
+    case K_SPPF3: return rva_sppf_pool3_nhwc_f16(c, s.in, s.ldi, s.out, s.out2, s.out3, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_POOL5: return rva_maxpool5_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_UP2: return rva_upsample2x_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_HEAD3: return rva_yolo_head3_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, n, s.hh, s.hw, p->nc, p->A, s.hs, st);
+    case K_CONV_F32: return rva_conv2d_nhwc_f32_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
+    case K_STEM_F32: return rva_stem_conv_f32(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
+    case K_POOL5_F32: return rva_maxpool5_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_UP2_F32: return rva_upsample2x_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_HEAD_F32: return rva_yolo_head_f32(c, s.in, s.ldi, s.in2, s.ldi2, output, n, s.H, s.W, p->nc, p->A, s.a0, s.stride_px, st);
     }
     return RVA_ERR_ARG;
 }
@@ -590,7 +599,7 @@ void propagate_rows(rva_yolov8_plan *p)
             t.desc += w;
         }
     }
-    p->primed = false;
+    p->primed = 0;
 }
 
 bool stream_is_capturing(rva_stream_t stream)
@@ -600,14 +609,30 @@ bool stream_is_capturing(rva_stream_t stream)
     return cs != hipStreamCaptureStatusNone;
 }
 
-int run_steps(rva_yolov8_plan *p, const void *input, void *output, int first, int last, rva_stream_t stream, bool win)
+int run_steps(rva_yolov8_plan *p, const void *input, void *output, int n, int first, int last, rva_stream_t stream, bool win)
 {
     for (int i = first; i < last; ++i) {
         const Step &s = p->steps[i];
-        const int rc = launch_step(p, s, s.variant, input, output, stream, win);
+        const int rc = launch_step(p, s, s.variant, input, output, n, stream, win);
         if (rc != RVA_OK) return rc;
     }
     return RVA_OK;
+}
+
+// what every run entry point refuses before it launches anything
+int check_run(rva_yolov8_plan *p, const void *input, void *output, int n)
+{
+    if (!p || !input || !output) return RVA_ERR_ARG;
+    if (n <= 0 || n > p->B) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: n = %d is not 1 .. %d, the plan's capacity", n, p->B);
+    if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
+    return RVA_OK;
+}
+
+// A whole run over all rows of n images has been queued: later runs of up to n images may launch windows.  A run that is only
+// recorded (stream capture) executes who knows when, or never: it leaves the count alone.
+void note_complete_run(rva_yolov8_plan *p, int n, bool win, rva_stream_t stream)
+{
+    if (!win && !stream_is_capturing(stream)) p->primed = n;
 }
 
 }  // namespace
@@ -693,7 +718,7 @@ int rva_yolov8_plan_set_variant(rva_yolov8_plan *p, int index, int variant)
     if (!p || index < 0 || index >= (int)p->tunables.size()) return RVA_ERR_ARG;
     Step &s = p->steps[p->tunables[index].step];
     if (!variant_fits(s, variant) || variant > rva_conv_num_variants()) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_set_variant: variant %d does not exist for this layer", variant);
-    p->primed = false;                                     // another kernel may cover other rows: one whole run first
+    p->primed = 0;                                         // another kernel may cover other rows: one whole run first
     s.variant = variant;
     return RVA_OK;
 }
@@ -710,26 +735,36 @@ int rva_yolov8_plan_launch_tunable(rva_yolov8_plan *p, int index, int variant, v
     const Step &s = p->steps[p->tunables[index].step];
     if (!variant_fits(s, variant)) return RVA_ERR_ARG;
     if (s.kind == K_HEAD && !output) return RVA_ERR_ARG;
-    return launch_step(p, s, variant, nullptr, output, stream, true);      // the row window where the variant takes one: what a primed run launches
+    return launch_step(p, s, variant, nullptr, output, p->B, stream, true);      // all images; the row window where the variant takes one: what a primed run launches
+}
+
+int rva_yolov8_plan_run_range_n(rva_yolov8_plan *p, const void *input, void *output, int n, int first, int last, rva_stream_t stream)
+{
+    if (const int rc = check_run(p, input, output, n); rc != RVA_OK) return rc;
+    if (first < 0 || last > (int)p->steps.size() || first > last) return RVA_ERR_ARG;
+    return run_steps(p, input, output, n, first, last, stream, n <= p->primed);       // a range never primes
 }
 
 int rva_yolov8_plan_run_range(rva_yolov8_plan *p, const void *input, void *output, int first, int last, rva_stream_t stream)
 {
-    if (!p || !input || !output || first < 0 || last > (int)p->steps.size() || first > last) return RVA_ERR_ARG;
-    if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
-    return run_steps(p, input, output, first, last, stream, p->primed);       // a range never primes
+    return p ? rva_yolov8_plan_run_range_n(p, input, output, p->B, first, last, stream) : RVA_ERR_ARG;
+}
+
+int rva_yolov8_plan_run_n(rva_yolov8_plan *p, const void *input, void *output, int n, rva_stream_t stream)
+{
+    if (const int rc = check_run(p, input, output, n); rc != RVA_OK) return rc;
+    const bool win = n <= p->primed;
+    const int rc = run_steps(p, input, output, n, 0, (int)p->steps.size(), stream, win);
+    if (rc == RVA_OK) note_complete_run(p, n, win, stream);
+    return rc;
 }
 
 int rva_yolov8_plan_run(rva_yolov8_plan *p, const void *input, void *output, rva_stream_t stream)
 {
-    if (!p || !input || !output) return RVA_ERR_ARG;
-    if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
-    const int rc = run_steps(p, input, output, 0, (int)p->steps.size(), stream, p->primed);
-    // a whole run over all rows has been queued: later runs on this plan may launch windows.  A run that is only recorded
-    // (stream capture) executes who knows when, or never: it leaves the flag alone.
-    if (rc == RVA_OK && !p->primed && !stream_is_capturing(stream)) p->primed = true;
-    return rc;
+    return p ? rva_yolov8_plan_run_n(p, input, output, p->B, stream) : RVA_ERR_ARG;
 }
+
+int rva_yolov8_plan_primed_images(const rva_yolov8_plan *p) { return p ? p->primed : 0; }
 
 int rva_yolov8_plan_set_static_rows(rva_yolov8_plan *p, int top, int bottom)
 {
@@ -768,12 +803,16 @@ int rva_conv_rows_through(int k, int stride, int H_in, int lo, int hi, int32_t *
 
 int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *output, rva_stream_t stream, rva_stream_t side1, rva_stream_t side2)
 {
-    if (!p || !input || !output) return RVA_ERR_ARG;
-    if (!side1 || !side2 || p->fork_step[1] < 0) return rva_yolov8_plan_run(p, input, output, stream);
-    if (((uintptr_t)input | (uintptr_t)output) % 16) return rva_fail(p->ctx, RVA_ERR_ARG, "rva_yolov8_plan_run: input and output must be 16-byte aligned");
+    return p ? rva_yolov8_plan_run_lanes_n(p, input, output, p->B, stream, side1, side2) : RVA_ERR_ARG;
+}
+
+int rva_yolov8_plan_run_lanes_n(rva_yolov8_plan *p, const void *input, void *output, int n, rva_stream_t stream, rva_stream_t side1, rva_stream_t side2)
+{
+    if (const int rc = check_run(p, input, output, n); rc != RVA_OK) return rc;
+    if (!side1 || !side2 || p->fork_step[1] < 0) return rva_yolov8_plan_run_n(p, input, output, n, stream);
     hipStream_t lanes[3] = {(hipStream_t)stream, (hipStream_t)side1, (hipStream_t)side2};
     bool started[3] = {true, false, false};
-    const bool win = p->primed;
+    const bool win = n <= p->primed;
     for (int i = 0; i < (int)p->steps.size(); ++i) {
         for (int l = 1; l <= 2; ++l)
             if (p->fork_step[l] == i) RVA_HIP(p->ctx, hipEventRecord(p->fork_ev[l], lanes[0]));      // everything the main lane has been given so far
@@ -782,7 +821,7 @@ int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *outpu
             RVA_HIP(p->ctx, hipStreamWaitEvent(lanes[s.lane], p->fork_ev[s.lane], 0));
             started[s.lane] = true;
         }
-        const int rc = launch_step(p, s, s.variant, input, output, (rva_stream_t)lanes[s.lane], win);
+        const int rc = launch_step(p, s, s.variant, input, output, n, (rva_stream_t)lanes[s.lane], win);
         if (rc != RVA_OK) return rc;
     }
     for (int l = 1; l <= 2; ++l)
@@ -790,7 +829,7 @@ int rva_yolov8_plan_run_lanes(rva_yolov8_plan *p, const void *input, void *outpu
             RVA_HIP(p->ctx, hipEventRecord(p->join_ev[l], lanes[l]));
             RVA_HIP(p->ctx, hipStreamWaitEvent(lanes[0], p->join_ev[l], 0));
         }
-    if (!p->primed && !stream_is_capturing(stream)) p->primed = true;       // as rva_yolov8_plan_run
+    note_complete_run(p, n, win, stream);                  // as rva_yolov8_plan_run_n
     return RVA_OK;
 }
 

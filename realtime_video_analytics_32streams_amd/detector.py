@@ -103,7 +103,10 @@ class HipYoloDetector(BaseDetector):
         ``hip_engine: native`` (the strict form, config.py) selects the same engines as ``plan`` here.
         ``hip_box_rows: fp32`` (engine ``"fused"`` only) makes the plan keep the four box rows in fp32 beside its fp16 head
         (``engine.FusedYoloV8(box_rows="fp32")``); the side tensor travels from ``stage_net`` to ``stage_post`` as an
-        ``ops.SplitHead`` and K2 reads its boxes from it."""
+        ``ops.SplitHead`` and K2 reads its boxes from it.
+        ``hip_plan_capacity: N`` (engines ``"fused"`` and ``"fused-f32"``; default 0 = one plan and input buffer per batch size)
+        keeps ONE plan and ONE input buffer of ``N`` images per input size and slot: a call with ``n <= N`` frames writes and
+        runs the leading ``n`` images, with the kernels of a full run (config.py)."""
         super().__init__(config)
         self._plans = {}
         self.ctx = ops.context(device)            # raises RuntimeError when no HIP device (no CPU fallback)
@@ -117,6 +120,10 @@ class HipYoloDetector(BaseDetector):
         self._infer_fn = infer_fn
         # where the fp16 plan keeps its box rows; fp32 elsewhere already (half: false), and no plan behind an infer_fn
         self.box_rows = getattr(config, "hip_box_rows", "fp16") if (self.engine == "fused" and infer_fn is None) else "fp16"
+        # one plan of this many images serves every smaller batch (0: a plan per batch size); plans only
+        cap = int(getattr(config, "hip_plan_capacity", 0) or 0)
+        self.plan_capacity = cap if (infer_fn is None and self.engine in ("fused", "fused-f32")) else 0
+        self._over_capacity_warned = False
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -134,7 +141,7 @@ class HipYoloDetector(BaseDetector):
         # pointers to them, and an interleaved predict() with another batch size must not free what a graph replays on
         self._post_bufs: dict = {}
         self._in_bufs: dict = {}
-        self._in_border: dict = {}                        # batch size -> frame geometry whose letterbox border the buffer holds
+        self._in_border: dict = {}                        # buffer key -> (frame geometry, leading images) whose letterbox border the buffer holds
         # The same border lets the plan skip the rows of its early layers that only see it (FusedYoloV8.set_static_rows): per
         # input buffer the content rows (top, bottom) of the geometry it holds, and whether the slot's plan has been told
         self._rows: dict = {}                             # buffer key -> (top, bottom); the whole image where nothing is static
@@ -150,27 +157,50 @@ class HipYoloDetector(BaseDetector):
                                         dtype=torch.float16 if self.half else torch.float32))
 
     # -- stages ---------------------------------------------------------------------------------
+    def _images(self, batch: int) -> int:
+        """Images of the input buffer and of the plan that serve a group of ``batch`` frames: the batch itself, or with
+        ``hip_plan_capacity: N`` the capacity, for every group it holds (a larger one gets its exact size, and a warning)."""
+        cap = self.plan_capacity
+        if cap <= 0 or batch == cap:
+            return batch
+        if batch > cap:
+            if not self._over_capacity_warned:
+                self._over_capacity_warned = True
+                LOGGER.warning("hip detector: a group of %d frames exceeds hip_plan_capacity=%d: it gets a plan of its own size, "
+                               "built now", batch, cap)
+            return batch
+        return cap
+
+    def _buf_key(self, batch: int):
+        """Key of the input buffer (and of its border / static-rows state): images of the buffer (, slot)."""
+        m = self._images(batch)
+        return m if self._slot == 0 else (m, self._slot)
+
     def input_tensor(self, batch: int) -> torch.Tensor:
-        """The input tensor K1 writes for this batch size and the current slot (cached for the life of the detector)."""
-        n = batch if self._slot == 0 else (batch, self._slot)                  # buffer key: batch size (, slot)
+        """The input tensor K1 writes for this batch size and the current slot (cached for the life of the detector); with
+        ``hip_plan_capacity`` the leading ``batch`` images of the slot's one buffer."""
+        n, m = self._buf_key(batch), self._images(batch)
         t = self._in_bufs.get(n)
         if t is None:
             dt = torch.float16 if self.half else torch.float32
-            t = self._in_bufs[n] = torch.empty((batch, 3, *self.input_hw), dtype=dt, device=self.device)
-        return t
+            t = self._in_bufs[n] = torch.empty((m, 3, *self.input_hw), dtype=dt, device=self.device)
+        return t if m == batch else t[:batch]
 
     def _preprocess(self, frames: Sequence) -> tuple[torch.Tensor, N.Letterbox]:
-        n = len(frames) if self._slot == 0 else (len(frames), self._slot)      # buffer key: batch size (, slot)
+        n = self._buf_key(len(frames))
         self._in = self.input_tensor(len(frames))
         f0 = frames[0]
         if isinstance(f0, ops.Nv12Surface):
             # the border (pad value) of the input tensor is constant per geometry: the first launch into a buffer writes it,
             # the following ticks of the same geometry write the content rows only
             key = (f0.width, f0.height) if not any(f.mask is not None for f in frames) else None
-            steady = key is not None and self._in_border.get(n) == key
+            have, bordered = self._in_border.get(n, (None, 0))
+            # steady: the border of this geometry is in place in every image the tick writes (a capacity buffer serves ticks of
+            # several sizes: a tick larger than any before it is not steady)
+            steady = key is not None and have == key and len(frames) <= bordered
             res = ops.preprocess_nv12(frames, self.input_hw, self.half, out=self._in, ctx=self.ctx, content_only=steady)
-            self._in_border[n] = key
-            if not steady:                                # new buffer, new geometry or ROI masks: the border was (re)written
+            if not steady:                                # new buffer, new geometry, more images or ROI masks: the border was (re)written
+                self._in_border[n] = (key, len(frames))
                 lb = res[1]
                 self._note_rows(n, (int(lb.pad_top), int(lb.pad_top) + int(lb.new_h)) if key is not None else (0, self.input_hw[0]))
             return res
@@ -178,7 +208,7 @@ class HipYoloDetector(BaseDetector):
         for f in frames:  # host BGR ndarray (the reference's FramePacket.frame) or device tensor
             t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
             dev.append(t.to(self.device, non_blocking=True).contiguous())
-        self._in_border[n] = None
+        self._in_border[n] = (None, 0)
         self._note_rows(n, (0, self.input_hw[0]))         # K1 for host frames writes the whole tensor
         return ops.preprocess_bgr(dev, self.input_hw, self.half, out=self._in, ctx=self.ctx)
 
@@ -196,8 +226,10 @@ class HipYoloDetector(BaseDetector):
 
     def plan_for(self, tensor: torch.Tensor):
         """The fused plan of this batch shape and the current slot (built and autotuned on first use; a second slot's plan
-        takes over the first one's kernel selection instead of tuning again)."""
-        shape = (int(tensor.shape[0]), int(tensor.shape[2]), int(tensor.shape[3]))
+        takes over the first one's kernel selection instead of tuning again).  With ``hip_plan_capacity`` the one plan of that
+        many images, told how many of them ``tensor`` holds (``FusedYoloV8.n``: what its ``result()`` hands out)."""
+        batch = int(tensor.shape[0])
+        shape = (self._images(batch), int(tensor.shape[2]), int(tensor.shape[3]))
         key = shape if self._slot == 0 else shape + (self._slot,)
         plan = self._plans.get(key)
         if plan is None:
@@ -213,18 +245,17 @@ class HipYoloDetector(BaseDetector):
                                                   static_rows=rows if self.engine == "fused" else None)
             if first is not None:
                 plan.copy_tuning(first)
+        plan.n = batch
         return plan
 
     def rows_pending(self, batch: int) -> bool:
         """K1 has rewritten the border of the current slot's input buffer and the slot's plan has not run since."""
-        n = batch if self._slot == 0 else (batch, self._slot)
-        return not self._rows_told.get(n, True)
+        return not self._rows_told.get(self._buf_key(batch), True)
 
     def _tell_rows(self, plan, tensor: torch.Tensor) -> None:
         """Hand the plan the static rows K1 left in the slot's input buffer, once per (re)written border.  The promise is about
         that buffer alone: any other tensor runs over all rows."""
-        batch = int(tensor.shape[0])
-        n = batch if self._slot == 0 else (batch, self._slot)
+        n = self._buf_key(int(tensor.shape[0]))
         own = self._in_bufs.get(n)
         if own is None or own.data_ptr() != tensor.data_ptr() or n not in self._rows:
             if plan.static_rows != (0, plan.H):

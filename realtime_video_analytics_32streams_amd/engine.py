@@ -20,6 +20,9 @@ bit-identical to the default plan's; ``ops.postprocess(..., boxes=plan.boxes32)`
 ``static_rows=(top, bottom)`` (fp16 plans) is the caller's promise that the input rows outside that window -- a letterbox border --
 hold the same bytes on every run: after one priming run over all rows the early layers launch only the output rows that depend on
 the window (``rva_yolov8_plan_set_static_rows``, include/rva.h); results are bit-identical.
+``batch`` is the plan's capacity: a call takes ``[n,3,H,W]`` with ``1 <= n <= batch`` and runs the leading ``n`` images of every
+buffer (``rva_yolov8_plan_run_n``) with the kernels of a full run, so ``out[:n]`` is bit-identical to the same images of a full run
+and ``out[n:]`` is not touched.
 No host synchronisation and no allocation after construction: a whole tick can be captured into a hipGraph.
 """
 from __future__ import annotations
@@ -86,7 +89,6 @@ class _VariantCell:
     def __setitem__(self, key, value):
         assert key == "variant"
         self.eng.ctx.check(self.eng.L.rva_yolov8_plan_set_variant(self.eng.handle, self.idx, int(value)), "rva_yolov8_plan_set_variant")
-        self.eng.primed = False            # as in the C plan: the next complete run covers all rows again
 
 
 class FusedYoloV8:
@@ -107,6 +109,7 @@ class FusedYoloV8:
         self.ctx = ctx or ops.context()
         self.dev = device or torch.device("cuda", self.ctx.device)
         self.B, self.H, self.W = batch, hw[0], hw[1]
+        self.n = batch                     # images of the last run (or of the tensor a caller announced): what result() hands out
         assert hw[0] % 32 == 0 and hw[1] % 32 == 0
         net = net.fuse()
         self._net = net                     # kept for the twin plans of the in-plan kernel selection
@@ -141,7 +144,6 @@ class FusedYoloV8:
         # row windows: set before the tuner runs, so that it times the windowed launches -- what will run
         self.static_rows = (0, self.H)
         self.rows_epoch = 0                # bumped by every set_static_rows: a hipGraph recorded with windows is good for one epoch
-        self.primed = False                # mirror of the C plan's flag: a complete eager run has covered all rows
         if static_rows is not None and tuple(static_rows) != (0, self.H) and os.environ.get("RVA_PLAN_NO_STATIC_ROWS") != "1":
             self.ctx.check(self.L.rva_yolov8_plan_set_static_rows(h, int(static_rows[0]), int(static_rows[1])), "rva_yolov8_plan_set_static_rows")
             self.static_rows = (int(static_rows[0]), int(static_rows[1]))
@@ -190,8 +192,17 @@ class FusedYoloV8:
             return                         # A/B switch: the library made the call a no-op
         self.static_rows = (int(top), int(bottom))
         self.rows_epoch += 1
-        self.primed = False
         self._read_tunables()              # the descriptions carry the windows
+
+    @property
+    def primed_images(self) -> int:
+        """Leading images whose buffers hold a whole run's rows (``rva_yolov8_plan_primed_images``; never mirrored here)."""
+        return int(self.L.rva_yolov8_plan_primed_images(self.handle))
+
+    @property
+    def primed(self) -> bool:
+        """Whether a run of the last run's ``n`` images launches row windows: a complete eager run has covered all their rows."""
+        return self.primed_images >= self.n
 
     def step_rows(self, step: int) -> Tuple[int, int]:
         y0, y1 = C.c_int32(), C.c_int32()
@@ -443,9 +454,12 @@ class FusedYoloV8:
 
     # -- run ------------------------------------------------------------------------------------------
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        """``x``: fp16 (fp32 for an fp32 plan) planar ``[B,3,H,W]`` contiguous (what K1 writes).  Returns ``[B, 4+nc, A]`` of the
-        plan's precision.  One ABI call."""
-        assert x.is_cuda and x.dtype == self.dtype and x.is_contiguous() and tuple(x.shape) == (self.B, 3, self.H, self.W)
+        """``x``: fp16 (fp32 for an fp32 plan) planar ``[n,3,H,W]`` contiguous (what K1 writes), ``1 <= n <= B``.  Returns
+        ``out[:n]``: ``[n, 4+nc, A]`` of the plan's precision, image for image the bits of a full run.  One ABI call."""
+        assert x.is_cuda and x.dtype == self.dtype and x.is_contiguous() and x.dim() == 4 and tuple(x.shape[1:]) == (3, self.H, self.W)
+        n = int(x.shape[0])
+        assert 1 <= n <= self.B, f"{n} images on a plan of capacity {self.B}"
+        self.n = n
         main = torch.cuda.current_stream()
         stream = C.c_void_p(main.cuda_stream)
         xin, out = C.c_void_p(x.data_ptr()), C.c_void_p(self.out.data_ptr())
@@ -453,20 +467,22 @@ class FusedYoloV8:
             # fork / join over events inside the plan: works eagerly and inside a stream capture
             if self._side is None:
                 self._side = (torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev))
-            self.ctx.check(self.L.rva_yolov8_plan_run_lanes(self.handle, xin, out, stream, C.c_void_p(self._side[0].cuda_stream),
-                                                            C.c_void_p(self._side[1].cuda_stream)), "rva_yolov8_plan_run_lanes")
-            self.primed = self.primed or not torch.cuda.is_current_stream_capturing()
-            return self.out
+            self.ctx.check(self.L.rva_yolov8_plan_run_lanes_n(self.handle, xin, out, n, stream, C.c_void_p(self._side[0].cuda_stream),
+                                                              C.c_void_p(self._side[1].cuda_stream)), "rva_yolov8_plan_run_lanes_n")
+            return self._head()
         ev = getattr(self, "phase_event", None)
         if ev is not None:
-            self.ctx.check(self.L.rva_yolov8_plan_run_range(self.handle, xin, out, 0, self.quiet_step, stream), "rva_yolov8_plan_run_range")
+            self.ctx.check(self.L.rva_yolov8_plan_run_range_n(self.handle, xin, out, n, 0, self.quiet_step, stream), "rva_yolov8_plan_run_range_n")
             ev.record(main)                                # the pass enters its 20x20 phase
-            self.ctx.check(self.L.rva_yolov8_plan_run_range(self.handle, xin, out, self.quiet_step, self._n_steps, stream),
-                           "rva_yolov8_plan_run_range")
+            self.ctx.check(self.L.rva_yolov8_plan_run_range_n(self.handle, xin, out, n, self.quiet_step, self._n_steps, stream),
+                           "rva_yolov8_plan_run_range_n")
         else:
-            self.ctx.check(self.L.rva_yolov8_plan_run(self.handle, xin, out, stream), "rva_yolov8_plan_run")
-            self.primed = self.primed or not torch.cuda.is_current_stream_capturing()
-        return self.out
+            self.ctx.check(self.L.rva_yolov8_plan_run_n(self.handle, xin, out, n, stream), "rva_yolov8_plan_run_n")
+        return self._head()
+
+    def _head(self) -> torch.Tensor:
+        """The head tensor of the last run's images in the current output slot (the slot itself for a full run)."""
+        return self.out if self.n == self.B else self.out[:self.n]
 
     def use_output(self, index: int) -> torch.Tensor:
         """Select which result tensor the head kernels write (``index`` 0 is the one allocated at construction, others are
@@ -482,9 +498,11 @@ class FusedYoloV8:
         return self.out
 
     def result(self):
-        """What a caller hands to the post-process for the current output slot: the head tensor, or with ``box_rows="fp32"`` an
-        ``ops.SplitHead`` of the head tensor and its side tensor."""
-        return self.out if self.boxes32 is None else ops.SplitHead(self.out, self.boxes32)
+        """What a caller hands to the post-process for the current output slot: the head tensor of the last run's ``n`` images, or
+        with ``box_rows="fp32"`` an ``ops.SplitHead`` of it and of the same images of its side tensor."""
+        if self.boxes32 is None:
+            return self._head()
+        return ops.SplitHead(self._head(), self.boxes32 if self.n == self.B else self.boxes32[:self.n])
 
     def _use_pair32(self) -> bool:
         """The 32-channel C2f bottleneck (YOLOv8s at 160 x 160) as ONE launch with the intermediate in LDS (rva_c2f_pair32_f16) or as

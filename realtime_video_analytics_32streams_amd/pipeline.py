@@ -419,6 +419,9 @@ class PipelinedTicks:
 
     With ``hip_box_rows: fp32`` a slot's head tensor and the fp32 side tensor of its box rows are one buffer of the slot's plan
     (``FusedYoloV8.result()``): eager and captured tails of every layout hand K2 the side tensor of the same slot.
+    With ``hip_plan_capacity: N`` every slot keeps one plan and one input buffer of ``N`` images, and a tick whose live-stream
+    count is ``n <= N`` runs their leading ``n`` images (``det.input_tensor(n)``, ``det.plan_for(tensor)``): no plan is built
+    when a stream delivers no frame.  A tick of a new shape still runs eagerly once and re-captures its tail.
 
     ``submit()`` enqueues one tick and returns its ticket; ``collect()`` returns ``(ticket, tables)`` of the oldest
     outstanding tick, ``tables[slot]`` being the arrays of ``DeviceTracker.snapshot_fetch``; ``collect_result()`` returns
