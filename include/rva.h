@@ -661,6 +661,42 @@ int rva_cnn3d_plan_stage(rva_cnn3d_plan *plan, int stage, int n_clips, void *dst
                          rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The same 3D-CNN clip network for `half: true` (engine "clip3d-f16"): fp16 frames, fp16 convolution weights and fp16 stored
+ * activations on the fp16-input MFMA, every sum in fp32.  The reference honours `half` on this head by making the clip tensor
+ * float16 (temporal_detector.py:590-591).  Network, launches, pools and the reproducibility contract are those of
+ * rva_cnn3d_plan_*; the entries have the same signatures and reuse rva_cnn3d_desc, rva_cnn3d_weights and enum rva_cnn3d_stage.
+ *
+ * rva_cnn3d_f16_plan_create: `weights` = fp32 host arrays in the layouts of rva_cnn3d_plan_create (BatchNorm folded by the
+ *   caller).  The three convolution weights are rounded ONCE to fp16, round to nearest even; RVA_ERR_ARG, naming the array, if
+ *   a value does not stay finite in fp16.  Biases, head weight and head bias stay fp32.  The descriptor limits are those of
+ *   rva_cnn3d_plan_create, and a workspace (fp16 activations) larger than the free device memory is refused with
+ *   RVA_ERR_CAPACITY.
+ * rva_cnn3d_f16_plan_run: frames = a device ring of planar fp16 frames [3][height][width] (what rva_preprocess_frames_* writes
+ *   for RVA_F16 with RVA_NORM_VIDEO_F32; no alignment of a frame row is assumed), read through frame_index as in
+ *   rva_cnn3d_plan_run, zero padding at the clip's ends.  logits = device fp32 [n_clips][classes].  Arithmetic: every
+ *   convolution sum accumulates in fp32 (products of two fp16 values are exact in fp32) in one fixed order; the max pools take the
+ *   max of the raw fp32 sums, then + bias, ReLU, and ONE rounding to fp16 for the two stored activations; conv3's tile partials,
+ *   the mean, the head and the logits are fp32.  Every launch goes to `stream`; no host synchronisation, no allocation:
+ *   capturable.  A clip's logits are bit-identical for every batch size, position in the batch, index-table permutation of the
+ *   ring and launch mode.
+ * rva_cnn3d_f16_plan_run_post / _info: as rva_cnn3d_plan_run_post / _info.
+ * rva_cnn3d_f16_plan_stage: the tap of rva_cnn3d_plan_stage, one device-to-device copy and no kernel, with the same layouts,
+ *   rules and errors; dst_elems / *n_elems count ELEMENTS of the stage's type:
+ *     RVA_CNN3D_STAGE_ACT1 / ACT2      fp16 elements
+ *     RVA_CNN3D_STAGE_PARTIAL / FEAT   fp32 elements
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_cnn3d_f16_plan rva_cnn3d_f16_plan;
+int rva_cnn3d_f16_plan_create(rva_ctx *ctx, const rva_cnn3d_desc *desc, const rva_cnn3d_weights *weights, rva_cnn3d_f16_plan **out);
+void rva_cnn3d_f16_plan_destroy(rva_cnn3d_f16_plan *plan);
+int rva_cnn3d_f16_plan_info(const rva_cnn3d_f16_plan *plan, int32_t *pool1, int32_t *pool2, int32_t *tiles, int32_t *n_launches);
+int rva_cnn3d_f16_plan_run(rva_cnn3d_f16_plan *plan, const void *frames, const int32_t *frame_index, int n_clips, void *logits,
+                           rva_stream_t stream);
+int rva_cnn3d_f16_plan_run_post(rva_cnn3d_f16_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                                void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+int rva_cnn3d_f16_plan_stage(rva_cnn3d_f16_plan *plan, int stage, int n_clips, void *dst, int64_t dst_elems, int64_t *n_elems,
+                             rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The ResNet-18 classifier as ONE fp32 object -- replaces the network call of the reference's ResNet head and its top-K
  * (detector.py:870-1001) for a batch of frames.  Per frame [3][H][W]: Conv 7x7 s2 p3 + BN + ReLU -> MaxPool 3x3 s2 p1 -> eight
  * BasicBlocks (widths 64, 64, 128, 128, 256, 256, 512, 512; blocks 2, 4 and 6 have stride 2 and a 1x1 stride-2 shortcut

@@ -13,6 +13,8 @@ from the detector's HBM ring through a device table of frame indices.  What stay
 
 The 3D-CNN head (:class:`temporal.Cnn3dNet`; ``3d_cnn`` and ``slow_fast``) has the same pieces for ``rva_cnn3d_plan_*``
 (``csrc/rva_clip3d.hip``, selected by ``hip_engine: native``): :func:`pack_cnn3d`, :func:`clip3d_flops`, :class:`Fused3dCnn`.
+With ``half: true`` and the detector key ``hip_clip_fp16: true`` the same head runs as the fp16 MFMA plan ``rva_cnn3d_f16_plan_*``
+(``csrc/rva_clip3d_f16.hip``, engine ``"clip3d-f16"``): ``pack_cnn3d(net, half=True)`` and :class:`Fused3dCnnF16`.
 """
 from __future__ import annotations
 
@@ -32,15 +34,18 @@ ENGINE = "clip-f32"          # NOT "fused" / "fused-f32": PipelinedTicks reads t
 
 
 ENGINE_3D = "clip3d-f32"     # the 3D-CNN plan (3d_cnn / slow_fast, hip_engine: native)
+ENGINE_3D_F16 = "clip3d-f16"  # its fp16 MFMA form (half: true, hip_engine: native, hip_clip_fp16: true)
 
 
-def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False) -> str:
+def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False, clip_fp16: bool = False) -> str:
     """Engine of a temporal head: ``"infer_fn"`` (a caller's function overrides everything), ``"clip-f32"`` (``cnn_lstm``,
     ``half: false``, ``hip_engine: plan`` or ``native``), ``"clip3d-f32"`` (``3d_cnn`` / ``slow_fast``, ``half: false``,
     ``hip_engine: native``) or ``"torch"``.  ``plan`` is best effort: ``half: true`` on ``cnn_lstm`` raises (the plan is fp32
     only), the other temporal heads keep torch with a warning, so a configuration never changes engines silently.  ``native``
     is strict: the network runs as hand-written HIP at the configured precision or the call raises ``ValueError`` (``half:
-    true`` on either plan; ``conv_gru``, for which the reference defines no architecture)."""
+    true`` on either plan; ``conv_gru``, for which the reference defines no architecture).  ``clip_fp16`` (the detector key
+    ``hip_clip_fp16``) opts ``3d_cnn`` / ``slow_fast`` with ``half: true`` and ``native`` into ``"clip3d-f16"``; it changes nothing
+    else."""
     if has_infer_fn:
         return "infer_fn"
     if hip_engine not in ("plan", "native"):
@@ -52,9 +57,12 @@ def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool
         return ENGINE
     if hip_engine == "native":
         if model_type in ("3d_cnn", "slow_fast"):
+            if half and clip_fp16:
+                return ENGINE_3D_F16
             if half:
-                raise ValueError("hip_engine: native runs the 3D-CNN head as an fp32 plan only; set half: false "
-                                 "(or hip_engine: auto for the PyTorch fp16 network)")
+                raise ValueError("hip_engine: native runs the 3D-CNN head as an fp32 plan only; set half: false, or "
+                                 "hip_clip_fp16: true for the fp16 plan clip3d-f16 (or hip_engine: auto for the PyTorch fp16 "
+                                 "network)")
             return ENGINE_3D
         if model_type == "conv_gru":
             raise ValueError("hip_engine: native has no hand-written plan for model_type 'conv_gru': the reference defines no "
@@ -85,14 +93,31 @@ def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 40
             "lstm_weight_bytes_per_step": 4.0 * g4 * 3 * hidden}
 
 
-def _fold(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
-    """Conv2d / Conv3d with its BatchNorm (eval statistics) folded in, in float64, rounded once to fp32."""
+def _fold64(conv, bn) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Conv2d / Conv3d with its BatchNorm (eval statistics) folded in, in float64."""
     w = conv.weight.detach().double().cpu()
     b = conv.bias.detach().double().cpu() if conv.bias is not None else torch.zeros(w.shape[0], dtype=torch.float64)
     scale = bn.weight.detach().double().cpu() / torch.sqrt(bn.running_var.detach().double().cpu() + bn.eps)
     wf = w * scale.reshape(-1, *([1] * (w.dim() - 1)))
     bf = (b - bn.running_mean.detach().double().cpu()) * scale + bn.bias.detach().double().cpu()
+    return wf, bf
+
+
+def _fold(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
+    """:func:`_fold64` rounded once to fp32."""
+    wf, bf = _fold64(conv, bn)
     return wf.float().numpy(), bf.float().numpy()
+
+
+def _fold_f16(conv, bn, what: str) -> Tuple[np.ndarray, np.ndarray]:
+    """:func:`_fold64` with the weight rounded ONCE to fp16 (float64 -> fp16, to nearest even) and widened to fp32; the bias
+    rounded once to fp32.  A weight beyond fp16 raises ``ValueError``."""
+    wf, bf = _fold64(conv, bn)
+    with np.errstate(over="ignore"):
+        w16 = wf.numpy().astype(np.float16)
+    if not np.isfinite(w16).all():
+        raise ValueError(f"pack_cnn3d: a value of {what} does not stay finite in fp16")
+    return w16.astype(np.float32), bf.float().numpy()
 
 
 def pack_cnn_lstm(net) -> Dict[str, np.ndarray]:
@@ -118,6 +143,8 @@ class _ClipPlan:
     sets ``ABI`` and its constructor calls :meth:`_open`, then :meth:`_create` with its descriptor and packed weights."""
 
     ABI = ""
+    RING_DTYPE = torch.float32                # element type of the frame ring ``run`` reads
+    TAP_DTYPES: Dict[str, torch.dtype] = {}   # stages whose tap delivers another type than fp32
 
     def _fn(self, name: str):
         return getattr(self.L, f"{self.ABI}_{name}")
@@ -149,8 +176,9 @@ class _ClipPlan:
         """Logits ``[n_clips, classes]`` of the clips whose frame t of clip b is ``ring.view(-1, 3, H, W)[frame_index[b * T + t]]``,
         launched on the current stream: a view of ``out`` (contiguous fp32 ``[>= n_clips, classes]`` on the device) or of the
         plan's own buffer."""
-        if ring.dtype != torch.float32 or not ring.is_cuda or not ring.is_contiguous() or ring.numel() % (3 * self.H * self.W):
-            raise ValueError(f"ring must be a contiguous fp32 device tensor of [*, 3, {self.H}, {self.W}] frames")
+        if ring.dtype != self.RING_DTYPE or not ring.is_cuda or not ring.is_contiguous() or ring.numel() % (3 * self.H * self.W):
+            kind = "fp16" if self.RING_DTYPE == torch.float16 else "fp32"
+            raise ValueError(f"ring must be a contiguous {kind} device tensor of [*, 3, {self.H}, {self.W}] frames")
         if frame_index.dtype != torch.int32 or not frame_index.is_cuda or frame_index.numel() < n_clips * self.T:
             raise ValueError("frame_index must be a device int32 tensor of n_clips * T frame indices")
         if not 1 <= n_clips <= self.max_clips:
@@ -179,7 +207,7 @@ class _ClipPlan:
         self.ctx.check(fn(self.handle, code, int(n_clips), None, 0, C.byref(n), None), what)
         if n.value != int(np.prod(shape)):
             raise RuntimeError(f"{what}: stage {name} has {n.value} floats, the layout {shape} says {int(np.prod(shape))}")
-        out = torch.empty(shape, dtype=torch.float32, device=self.dev)
+        out = torch.empty(shape, dtype=self.TAP_DTYPES.get(name, torch.float32), device=self.dev)
         self.ctx.check(fn(self.handle, code, int(n_clips), C.c_void_p(out.data_ptr()), out.numel(), None, ops._stream_ptr()), what)
         return out
 
@@ -242,7 +270,7 @@ def clip3d_flops(h: int, w: int, frames: int, classes: int = 400) -> Dict[str, f
             "act1_bytes": 4.0 * frames * h1 * w1 * 64, "act2_bytes": 4.0 * t2 * h2 * w2 * 128}
 
 
-def pack_cnn3d(net) -> Dict[str, np.ndarray]:
+def pack_cnn3d(net, half: bool = False) -> Dict[str, np.ndarray]:
     """The ``rva_cnn3d_weights`` arrays of a :class:`temporal.Cnn3dNet` (``N.Cnn3dWeights.NAMES`` order), contiguous fp32, each
     Conv3d with its BatchNorm folded in float64 and rounded once, in the layouts the kernels read:
 
@@ -250,7 +278,11 @@ def pack_cnn3d(net) -> Dict[str, np.ndarray]:
         81 taps in registers in this order);
       * ``conv2_w`` ``[128, 27, 64]`` and ``conv3_w`` ``[256, 27, 128]`` = ``[co, tap, ci]`` with ``tap = (kt*3 + ky)*3 + kx``
         (channels innermost, as the channels-last activations: a lane's MFMA operands are contiguous float4 reads);
-      * biases ``[64]`` / ``[128]`` / ``[256]``, ``head_w`` ``[classes, 256]``, ``head_b`` ``[classes]``."""
+      * biases ``[64]`` / ``[128]`` / ``[256]``, ``head_w`` ``[classes, 256]``, ``head_b`` ``[classes]``.
+
+    ``half=True`` (the fp16 plan): each convolution weight is folded in float64, rounded once to fp16 and widened to fp32 --
+    the values ``rva_cnn3d_f16_plan_create`` then converts exactly; a value beyond fp16 raises ``ValueError``.  Biases and the head
+    stay fp32."""
     seq, fc = getattr(net, "conv3d", None), getattr(net, "fc", None)
     ok = isinstance(seq, torch.nn.Sequential) and len(seq) == 12 and isinstance(fc, torch.nn.Linear)
     if ok:
@@ -267,9 +299,10 @@ def pack_cnn3d(net) -> Dict[str, np.ndarray]:
             isinstance(seq[11], torch.nn.AdaptiveAvgPool3d) and fc.in_features == 256
     if not ok:
         raise ValueError("pack_cnn3d: not the Cnn3dNet architecture")
-    c1w, c1b = _fold(seq[0], seq[1])
-    c2w, c2b = _fold(seq[4], seq[5])
-    c3w, c3b = _fold(seq[8], seq[9])
+    fold = (lambda i, what: _fold_f16(seq[i], seq[i + 1], what)) if half else (lambda i, what: _fold(seq[i], seq[i + 1]))  # noqa: E731
+    c1w, c1b = fold(0, "conv1_w")
+    c2w, c2b = fold(4, "conv2_w")
+    c3w, c3b = fold(8, "conv3_w")
     taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], 27).transpose(0, 2, 1)  # noqa: E731  [co,ci,27] -> [co,27,ci]
     bias = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
     out = {"conv1_w": c1w, "conv1_b": c1b, "conv2_w": taps_last(c2w), "conv2_b": c2b, "conv3_w": taps_last(c3w), "conv3_b": c3b,
@@ -283,14 +316,15 @@ class Fused3dCnn(_ClipPlan):
     ``logits``, ``run``, ``post``, ``__call__``).  No host synchronisation and no allocation after construction (capturable)."""
 
     ABI = "rva_cnn3d_plan"
+    HALF = False                              # pack_cnn3d(half=...): the precision of the convolution weights
 
     def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
                  device: Optional[torch.device] = None):
-        packed = pack_cnn3d(net)                                    # a wrong architecture is refused before the device is touched
+        packed = pack_cnn3d(net, half=self.HALF)                    # a wrong architecture is refused before the device is touched
         self._open(hw, frames, max_clips, net.fc.out_features, ctx, device)
         self._create(N.Cnn3dDesc(self.H, self.W, self.T, self.classes, self.max_clips), N.Cnn3dWeights, packed)
         p1, p2, tiles, nl = (C.c_int32 * 3)(), (C.c_int32 * 3)(), (C.c_int32 * 3)(), C.c_int32()
-        self.ctx.check(self.L.rva_cnn3d_plan_info(self.handle, p1, p2, tiles, C.byref(nl)), "rva_cnn3d_plan_info")
+        self.ctx.check(self._fn("info")(self.handle, p1, p2, tiles, C.byref(nl)), f"{self.ABI}_info")
         self.pool1, self.pool2, self.tiles, self.n_launches = tuple(p1), tuple(p2), tuple(tiles), nl.value
 
     def stage(self, name: str, n_clips: int) -> torch.Tensor:
@@ -310,6 +344,22 @@ class Fused3dCnn(_ClipPlan):
         if tuple(clips.shape[1:]) != (3, self.T, self.H, self.W):
             raise ValueError(f"clips must be [B, 3, {self.T}, {self.H}, {self.W}], got {tuple(clips.shape)}")
         return self._run_frames(clips.permute(0, 2, 1, 3, 4).contiguous(), b)
+
+
+class Fused3dCnnF16(Fused3dCnn):
+    """One ``rva_cnn3d_f16_plan``: the network of :class:`Fused3dCnn` for ``half: true`` -- fp16 frames, fp16 convolution weights
+    (``net``'s fp32 parameters folded in float64 and rounded once) and fp16 stored activations on the fp16 MFMA, every sum in
+    fp32, fp32 logits.  Same surface: ``run`` takes an fp16 ring, ``stage`` returns ``act1`` / ``act2`` as fp16 tensors."""
+
+    ABI = "rva_cnn3d_f16_plan"
+    HALF = True
+    RING_DTYPE = torch.float16
+    TAP_DTYPES = {"act1": torch.float16, "act2": torch.float16}
+
+    def __call__(self, clips: torch.Tensor) -> torch.Tensor:
+        """``Cnn3dNet.forward`` of clips ``[B, 3, T, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
+        ``[B, classes]`` tensor."""
+        return super().__call__(clips.to(torch.float16))
 
 
 def fired_tables(fired: Sequence, cols: Sequence[int], ring_columns: int, rows: int) -> Tuple[np.ndarray, np.ndarray]:

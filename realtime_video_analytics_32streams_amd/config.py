@@ -21,9 +21,17 @@ configured precision, or construction fails with ``ValueError`` (an ``infer_fn``
     head                    half: false                       half: true
     yolov5 / yolov8         as plan: engine "fused-f32"       as plan: engine "fused"
     cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only)
-    3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only)
+    3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only) unless hip_clip_fp16: true
     conv_gru                ValueError (the reference defines no architecture, so there is no plan)
     resnet                  ValueError (no hand-written plan)
+
+``hip_clip_fp16`` (a bool, default ``false``: what a reference YAML gets) opts the 3D-CNN head into its fp16 plan: with
+``hip_engine: native``, ``model_type: 3d_cnn`` / ``slow_fast`` and ``half: true`` the network runs as engine ``"clip3d-f16"``
+(clip_plan.Fused3dCnnF16: fp16 frames, weights and stored activations on the fp16 MFMA, fp32 sums and logits) where it is
+otherwise refused.  The key changes nothing else: not ``half: false``, not ``cnn_lstm``, not ``plan`` or ``auto``:
+
+    head                    hip_clip_fp16: false              hip_clip_fp16: true
+    3d_cnn / slow_fast      half: true -> ValueError          half: true -> engine "clip3d-f16"  (hip_engine: native)
 
 ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
 rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
@@ -125,12 +133,14 @@ class DetectorConfig:
     num_action_classes: int = 400
     hip_engine: str = "auto"                # backend "hip": "auto", "plan" or "native" (module docstring)
     hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
+    hip_clip_fp16: bool = False             # backend "hip", 3d_cnn / slow_fast with half: true and native: the fp16 plan (module docstring)
     hip_plan_capacity: int = 0              # backend "hip", YOLO plans: 0 = a plan per batch size, N = one plan of N images (module docstring)
 
     def validate(self) -> None:
         _need(bool(self.model_path), "Detector model_path must not be empty")
         _need(self.hip_engine in HIP_ENGINES, f"hip_engine must be one of {set(HIP_ENGINES)}")
         _need(self.hip_box_rows in HIP_BOX_ROWS, f"hip_box_rows must be one of {set(HIP_BOX_ROWS)}")
+        _need(isinstance(self.hip_clip_fp16, bool), "hip_clip_fp16 must be true or false")
         _need(isinstance(self.hip_plan_capacity, int) and not isinstance(self.hip_plan_capacity, bool) and self.hip_plan_capacity >= 0,
               "hip_plan_capacity must be an integer >= 0")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,

@@ -16,6 +16,7 @@ time is a gather of 16 slots + the network.
 """
 from __future__ import annotations
 
+import copy
 import logging
 from collections import deque
 from dataclasses import dataclass
@@ -27,14 +28,15 @@ import torch.nn as nn
 
 from . import _native as N
 from . import ops
-from .clip_plan import ENGINE as CLIP_PLAN, ENGINE_3D as CLIP_PLAN_3D, Fused3dCnn, FusedCnnLstm, clip_engine, fired_tables
+from .clip_plan import (ENGINE as CLIP_PLAN, ENGINE_3D as CLIP_PLAN_3D, ENGINE_3D_F16 as CLIP_PLAN_3D_F16, Fused3dCnn, Fused3dCnnF16,
+                        FusedCnnLstm, clip_engine, fired_tables)
 from .config import DetectorConfig
 from .detector import Detection
 from .video_stream import FramePacket
 
 LOGGER = logging.getLogger(__name__)
 
-CLIP_PLANS = (CLIP_PLAN, CLIP_PLAN_3D)      # engines that run the clip network as a hand-written plan (_make_plan)
+CLIP_PLANS = (CLIP_PLAN, CLIP_PLAN_3D, CLIP_PLAN_3D_F16)      # engines that run the clip network as a hand-written plan (_make_plan)
 
 
 @dataclass(slots=True)
@@ -169,8 +171,10 @@ class _HipTemporalDetector:
         self.half = bool(config.half)
         self._infer_fn = infer_fn
         # "torch", "infer_fn", "clip-f32" (cnn_lstm, half: false, hip_engine: plan / native) or "clip3d-f32" (3d_cnn / slow_fast,
-        # half: false, hip_engine: native): clip_plan.clip_engine
-        self.engine = clip_engine(config.model_type, self.half, getattr(config, "hip_engine", "auto"), infer_fn is not None)
+        # half: false, hip_engine: native) or "clip3d-f16" (the same with half: true and hip_clip_fp16: true): clip_plan.clip_engine
+        self.engine = clip_engine(config.model_type, self.half, getattr(config, "hip_engine", "auto"), infer_fn is not None,
+                                  bool(getattr(config, "hip_clip_fp16", False)))
+        self._net_f32 = None                   # "clip3d-f16": an fp32 copy of the network, so the plan rounds its weights once
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -179,6 +183,8 @@ class _HipTemporalDetector:
                 net = self._default_net()
                 torch.random.set_rng_state(st)
             self.net = net.eval().to(self.device)
+            if self.engine == CLIP_PLAN_3D_F16:
+                self._net_f32 = copy.deepcopy(self.net)     # before the in-place conversion to fp16 below
             self.net = self.net.to(self._frame_dtype())
         self._buf: Dict[str, Deque] = {}
         self._ring: Dict[str, torch.Tensor] = {}
@@ -430,8 +436,10 @@ class HipCNN3DDetector(_HipTemporalDetector):
     detector.py:70-74): mean 0.45 / std 0.225, clips ``[1,3,T,H,W]``, default input 112x112 (:544).  With ``half: false`` and
     ``hip_engine: native`` the network and its top-5 run as the hand-written fp32 plan (engine ``"clip3d-f32"``,
     clip_plan.Fused3dCnn): it reads the planar frames straight from the frame ring through the frame-index table, so neither the
-    gather nor the ``[B,3,T,H,W]`` permute exists on that path.  ``half: true`` with ``native`` is refused; ``hip_engine: plan``
-    keeps PyTorch-ROCm with a warning."""
+    gather nor the ``[B,3,T,H,W]`` permute exists on that path.  ``half: true`` with ``native`` is refused unless ``hip_clip_fp16:
+    true`` opts into the fp16 MFMA plan (engine ``"clip3d-f16"``, clip_plan.Fused3dCnnF16: the ring holds fp16 frames and the
+    plan is packed from an fp32 copy of the network, so the weights are rounded once); ``hip_engine: plan`` keeps PyTorch-ROCm
+    with a warning."""
 
     NORM = N.NORM_VIDEO_F32
     CLIP_LAYOUT = "CTHW"
@@ -441,6 +449,8 @@ class HipCNN3DDetector(_HipTemporalDetector):
         return Cnn3dNet(self.config.num_action_classes)
 
     def _make_plan(self, max_clips: int) -> Fused3dCnn:
+        if self.engine == CLIP_PLAN_3D_F16:
+            return Fused3dCnnF16(self._net_f32, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
         return Fused3dCnn(self.net, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
 
 
