@@ -609,6 +609,43 @@ int rva_cnnlstm_plan_stage(rva_cnnlstm_plan *plan, int stage, int n_clips, void 
                            rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The same CNN-LSTM clip network for `half: true` (engine "clip-f16"): fp16 frames, fp16 convolution and LSTM weights and an
+ * fp16 stored stem output, conv1 and conv2 on the fp16-input MFMA, every sum in fp32.  Network, launches and the
+ * reproducibility contract are those of rva_cnnlstm_plan_*; the entries have the same signatures and reuse rva_cnnlstm_desc,
+ * rva_cnnlstm_weights and enum rva_cnnlstm_stage.
+ *
+ * rva_cnnlstm_f16_plan_create: `weights` = fp32 host arrays in the layouts of rva_cnnlstm_plan_create (BatchNorm folded by the
+ *   caller).  conv1_w, conv2_w, w_ih1, w_hh1, w_ih2 and w_hh2 are rounded ONCE to fp16, round to nearest even; RVA_ERR_ARG,
+ *   naming the array, if a value does not stay finite in fp16.  b1, b2, the conv biases, head weight and head bias stay fp32.
+ *   The descriptor limits are those of rva_cnnlstm_plan_create and max_clips * frames <= 65535; a workspace larger than the
+ *   free device memory is refused with RVA_ERR_CAPACITY.
+ * rva_cnnlstm_f16_plan_run: frames = a device ring of planar fp16 frames [3][height][width] (what rva_preprocess_frames_* writes
+ *   for RVA_F16 with RVA_NORM_IMAGENET_F32; no alignment of a frame row is assumed), read through frame_index as in
+ *   rva_cnnlstm_plan_run.  logits = device fp32 [n_clips][classes].  Arithmetic: every sum accumulates in fp32 (products of two
+ *   fp16 values are exact in fp32) in one fixed order; the stem output gets ONE rounding to fp16, of ReLU(max of the raw sums +
+ *   bias); conv2's tile partials, the mean, the LSTM's gates, hidden and cell states, the head and the logits are fp32.  Every
+ *   launch goes to `stream`; no host synchronisation, no allocation: capturable.  A clip's logits are bit-identical for every
+ *   batch size, position in the batch, index-table permutation of the ring and launch mode.
+ * rva_cnnlstm_f16_plan_run_post / _info: as rva_cnnlstm_plan_run_post / _info.
+ * rva_cnnlstm_f16_plan_stage: the tap of rva_cnnlstm_plan_stage, one device-to-device copy and no kernel, with the same
+ *   layouts, rules and errors; dst_elems / *n_elems count ELEMENTS of the stage's type:
+ *     RVA_CNNLSTM_STAGE_POOLED                          fp16 elements
+ *     RVA_CNNLSTM_STAGE_PARTIAL / FEAT / GX / H1 / H2   fp32 elements
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_cnnlstm_f16_plan rva_cnnlstm_f16_plan;
+int rva_cnnlstm_f16_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rva_cnnlstm_weights *weights,
+                                rva_cnnlstm_f16_plan **out);
+void rva_cnnlstm_f16_plan_destroy(rva_cnnlstm_f16_plan *plan);
+int rva_cnnlstm_f16_plan_info(const rva_cnnlstm_f16_plan *plan, int32_t *pooled_h, int32_t *pooled_w, int32_t *conv2_tiles,
+                              int32_t *n_launches);
+int rva_cnnlstm_f16_plan_run(rva_cnnlstm_f16_plan *plan, const void *frames, const int32_t *frame_index, int n_clips, void *logits,
+                             rva_stream_t stream);
+int rva_cnnlstm_f16_plan_run_post(rva_cnnlstm_f16_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                                  void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+int rva_cnnlstm_f16_plan_stage(rva_cnnlstm_f16_plan *plan, int stage, int n_clips, void *dst, int64_t dst_elems, int64_t *n_elems,
+                               rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The 3D-CNN clip network as ONE fp32 object -- replaces the network call of the reference's 3D-CNN head and its top-5
  * (CNN3DDetector._predict_sequence, temporal_detector.py:596-641; the network is Dummy3DCNN of
  * scripts/convert_temporal_model_to_onnx.py:91-121), for `half: false`.  Per clip [3][T][H][W]: Conv3d(3,64,3,p1)+BN+ReLU ->

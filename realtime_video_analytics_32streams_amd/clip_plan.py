@@ -15,6 +15,9 @@ The 3D-CNN head (:class:`temporal.Cnn3dNet`; ``3d_cnn`` and ``slow_fast``) has t
 (``csrc/rva_clip3d.hip``, selected by ``hip_engine: native``): :func:`pack_cnn3d`, :func:`clip3d_flops`, :class:`Fused3dCnn`.
 With ``half: true`` and the detector key ``hip_clip_fp16: true`` the same head runs as the fp16 MFMA plan ``rva_cnn3d_f16_plan_*``
 (``csrc/rva_clip3d_f16.hip``, engine ``"clip3d-f16"``): ``pack_cnn3d(net, half=True)`` and :class:`Fused3dCnnF16`.
+The CNN-LSTM head has its fp16 form too: with ``half: true`` and the detector key ``hip_lstm_fp16: true`` it runs as
+``rva_cnnlstm_f16_plan_*`` (``csrc/rva_clip_f16.hip``, engine ``"clip-f16"``): ``pack_cnn_lstm(net, half=True)`` and
+:class:`FusedCnnLstmF16`.
 """
 from __future__ import annotations
 
@@ -31,13 +34,14 @@ from . import ops
 LOGGER = logging.getLogger(__name__)
 
 ENGINE = "clip-f32"          # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
-
+ENGINE_F16 = "clip-f16"      # its fp16 MFMA form (half: true, hip_engine: plan / native, hip_lstm_fp16: true)
 
 ENGINE_3D = "clip3d-f32"     # the 3D-CNN plan (3d_cnn / slow_fast, hip_engine: native)
 ENGINE_3D_F16 = "clip3d-f16"  # its fp16 MFMA form (half: true, hip_engine: native, hip_clip_fp16: true)
 
 
-def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False, clip_fp16: bool = False) -> str:
+def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool = False, clip_fp16: bool = False,
+                lstm_fp16: bool = False) -> str:
     """Engine of a temporal head: ``"infer_fn"`` (a caller's function overrides everything), ``"clip-f32"`` (``cnn_lstm``,
     ``half: false``, ``hip_engine: plan`` or ``native``), ``"clip3d-f32"`` (``3d_cnn`` / ``slow_fast``, ``half: false``,
     ``hip_engine: native``) or ``"torch"``.  ``plan`` is best effort: ``half: true`` on ``cnn_lstm`` raises (the plan is fp32
@@ -45,15 +49,18 @@ def clip_engine(model_type: str, half: bool, hip_engine: str, has_infer_fn: bool
     is strict: the network runs as hand-written HIP at the configured precision or the call raises ``ValueError`` (``half:
     true`` on either plan; ``conv_gru``, for which the reference defines no architecture).  ``clip_fp16`` (the detector key
     ``hip_clip_fp16``) opts ``3d_cnn`` / ``slow_fast`` with ``half: true`` and ``native`` into ``"clip3d-f16"``; it changes nothing
-    else."""
+    else.  ``lstm_fp16`` (the detector key ``hip_lstm_fp16``) opts ``cnn_lstm`` with ``half: true`` and ``plan`` or ``native`` into
+    ``"clip-f16"``; it changes nothing else either."""
     if has_infer_fn:
         return "infer_fn"
     if hip_engine not in ("plan", "native"):
         return "torch"
     if model_type == "cnn_lstm":
+        if half and lstm_fp16:
+            return ENGINE_F16
         if half:
             raise ValueError(f"hip_engine: {hip_engine} runs the CNN-LSTM head as an fp32 plan only; set half: false "
-                             "(or hip_engine: auto for the PyTorch fp16 network)")
+                             "(or hip_engine: auto for the PyTorch fp16 network), or hip_lstm_fp16: true for the fp16 plan clip-f16")
         return ENGINE
     if hip_engine == "native":
         if model_type in ("3d_cnn", "slow_fast"):
@@ -78,8 +85,9 @@ def conv_out(n: int, k: int, s: int, p: int) -> int:
     return (n + 2 * p - k) // s + 1
 
 
-def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 400) -> Dict[str, float]:
-    """FLOP (multiply + add = 2) and the bytes a clip's network must at least move, from the shapes alone."""
+def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 400, half: bool = False) -> Dict[str, float]:
+    """FLOP (multiply + add = 2) and the bytes a clip's network must at least move, from the shapes alone.  ``half``: the byte
+    counts of the fp16 plan (fp16 frames, convolution and LSTM weights and ``pooled``; biases and the head fp32)."""
     hc, wc = conv_out(h, 7, 2, 3), conv_out(w, 7, 2, 3)
     hp, wp = conv_out(hc, 3, 2, 1), conv_out(wc, 3, 2, 1)
     conv1 = 2.0 * hc * wc * 64 * 3 * 49
@@ -87,10 +95,11 @@ def clip_flops(h: int, w: int, frames: int, hidden: int = 512, classes: int = 40
     g4 = 4 * hidden
     lstm = 2.0 * frames * (g4 * 128 + g4 * hidden + g4 * 2 * hidden)
     head = 2.0 * hidden * classes
-    weights = 4.0 * (64 * 147 + 64 + 128 * 576 + 128 + g4 * (128 + 3 * hidden + 2) + classes * (hidden + 1))
+    e = 2.0 if half else 4.0
+    weights = e * (64 * 147 + 128 * 576 + g4 * (128 + 3 * hidden)) + 4.0 * (64 + 128 + g4 * 2 + classes * (hidden + 1))
     return {"conv1_per_frame": conv1, "conv2_per_frame": conv2, "frame": conv1 + conv2, "lstm": lstm, "head": head,
-            "clip": frames * (conv1 + conv2) + lstm + head, "frame_bytes": 4.0 * 3 * h * w, "weight_bytes": weights,
-            "lstm_weight_bytes_per_step": 4.0 * g4 * 3 * hidden}
+            "clip": frames * (conv1 + conv2) + lstm + head, "frame_bytes": e * 3 * h * w, "weight_bytes": weights,
+            "lstm_weight_bytes_per_step": e * g4 * 3 * hidden, "pooled_bytes_per_frame": e * hp * wp * 64}
 
 
 def _fold64(conv, bn) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -109,32 +118,49 @@ def _fold(conv, bn) -> Tuple[np.ndarray, np.ndarray]:
     return wf.float().numpy(), bf.float().numpy()
 
 
-def _fold_f16(conv, bn, what: str) -> Tuple[np.ndarray, np.ndarray]:
+def _round_f16(w, what: str, who: str) -> np.ndarray:
+    """``w`` (float64 or fp32) rounded ONCE to fp16, to nearest even, and widened to fp32; a value beyond fp16 raises."""
+    with np.errstate(over="ignore"):
+        w16 = np.asarray(w).astype(np.float16)
+    if not np.isfinite(w16).all():
+        raise ValueError(f"{who}: a value of {what} does not stay finite in fp16")
+    return w16.astype(np.float32)
+
+
+def _fold_f16(conv, bn, what: str, who: str = "pack_cnn3d") -> Tuple[np.ndarray, np.ndarray]:
     """:func:`_fold64` with the weight rounded ONCE to fp16 (float64 -> fp16, to nearest even) and widened to fp32; the bias
     rounded once to fp32.  A weight beyond fp16 raises ``ValueError``."""
     wf, bf = _fold64(conv, bn)
-    with np.errstate(over="ignore"):
-        w16 = wf.numpy().astype(np.float16)
-    if not np.isfinite(w16).all():
-        raise ValueError(f"pack_cnn3d: a value of {what} does not stay finite in fp16")
-    return w16.astype(np.float32), bf.float().numpy()
+    return _round_f16(wf.numpy(), what, who), bf.float().numpy()
 
 
-def pack_cnn_lstm(net) -> Dict[str, np.ndarray]:
-    """The ``rva_cnnlstm_weights`` arrays of a :class:`temporal.CnnLstmNet` (``N.CnnLstmWeights.NAMES`` order), contiguous fp32."""
+def pack_cnn_lstm(net, half: bool = False) -> Dict[str, np.ndarray]:
+    """The ``rva_cnnlstm_weights`` arrays of a :class:`temporal.CnnLstmNet` (``N.CnnLstmWeights.NAMES`` order), contiguous fp32.
+
+    ``half=True`` (the fp16 plan): the same names, order and layouts, fp16-representable -- ``conv1_w`` / ``conv2_w`` are folded
+    with their BatchNorm in float64 and rounded once to fp16, ``w_ih1`` / ``w_hh1`` / ``w_ih2`` / ``w_hh2`` are rounded once to fp16
+    from the module's parameters, each widened to fp32 (the values ``rva_cnnlstm_f16_plan_create`` then converts exactly); a value
+    beyond fp16 raises ``ValueError`` naming the array.  The summed LSTM biases, the conv biases and the head stay fp32."""
     st, rnn = net.stem, net.rnn
     if not (isinstance(st[0], torch.nn.Conv2d) and st[0].out_channels == 64 and st[0].kernel_size == (7, 7) and
             isinstance(st[4], torch.nn.Conv2d) and st[4].out_channels == 128 and rnn.num_layers == 2 and rnn.input_size == 128
             and rnn.batch_first and not rnn.bidirectional and rnn.proj_size == 0):
         raise ValueError("pack_cnn_lstm: not the CnnLstmNet architecture")
     p = {n: t.detach().double().cpu() for n, t in rnn.named_parameters()}
-    c1w, c1b = _fold(st[0], st[1])
-    c2w, c2b = _fold(st[4], st[5])
+    if half:
+        c1w, c1b = _fold_f16(st[0], st[1], "conv1_w", "pack_cnn_lstm")
+        c2w, c2b = _fold_f16(st[4], st[5], "conv2_w", "pack_cnn_lstm")
+    else:
+        c1w, c1b = _fold(st[0], st[1])
+        c2w, c2b = _fold(st[4], st[5])
     f32 = lambda t: np.ascontiguousarray(t.float().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32)  # noqa: E731
     out = {"conv1_w": c1w, "conv1_b": c1b, "conv2_w": c2w, "conv2_b": c2b,
            "w_ih1": p["weight_ih_l0"], "b1": p["bias_ih_l0"] + p["bias_hh_l0"], "w_hh1": p["weight_hh_l0"],
            "w_ih2": p["weight_ih_l1"], "w_hh2": p["weight_hh_l1"], "b2": p["bias_ih_l1"] + p["bias_hh_l1"],
            "head_w": net.head.weight.detach().double().cpu(), "head_b": net.head.bias.detach().double().cpu()}
+    if half:
+        for k in ("w_ih1", "w_hh1", "w_ih2", "w_hh2"):
+            out[k] = _round_f16(out[k].numpy(), k, "pack_cnn_lstm")
     return {n: f32(out[n]) for n in N.CnnLstmWeights.NAMES}
 
 
@@ -225,15 +251,16 @@ class FusedCnnLstm(_ClipPlan):
     clips per call.  No host synchronisation and no allocation after construction (capturable)."""
 
     ABI = "rva_cnnlstm_plan"
+    HALF = False                              # pack_cnn_lstm(half=...): the precision of the convolution and LSTM weights
 
     def __init__(self, net, hw: Tuple[int, int], frames: int, max_clips: int, ctx: Optional[N.Context] = None,
                  device: Optional[torch.device] = None):
+        packed = pack_cnn_lstm(net, half=self.HALF)                 # a weight beyond fp16 is refused before the device is touched
         self._open(hw, frames, max_clips, net.head.out_features, ctx, device)
         self.hidden = int(net.rnn.hidden_size)
-        self._create(N.CnnLstmDesc(self.H, self.W, self.T, self.hidden, self.classes, self.max_clips), N.CnnLstmWeights,
-                     pack_cnn_lstm(net))
+        self._create(N.CnnLstmDesc(self.H, self.W, self.T, self.hidden, self.classes, self.max_clips), N.CnnLstmWeights, packed)
         info = [C.c_int32() for _ in range(4)]
-        self.ctx.check(self.L.rva_cnnlstm_plan_info(self.handle, *[C.byref(v) for v in info]), "rva_cnnlstm_plan_info")
+        self.ctx.check(self._fn("info")(self.handle, *[C.byref(v) for v in info]), f"{self.ABI}_info")
         self.pooled_hw = (info[0].value, info[1].value)
         self.conv2_tiles, self.n_launches = info[2].value, info[3].value
 
@@ -253,6 +280,23 @@ class FusedCnnLstm(_ClipPlan):
         if tuple(clips.shape[1:]) != (self.T, 3, self.H, self.W):
             raise ValueError(f"clips must be [B, {self.T}, 3, {self.H}, {self.W}], got {tuple(clips.shape)}")
         return self._run_frames(clips.contiguous(), b)
+
+
+class FusedCnnLstmF16(FusedCnnLstm):
+    """One ``rva_cnnlstm_f16_plan``: the network of :class:`FusedCnnLstm` for ``half: true`` -- fp16 frames, fp16 convolution and
+    LSTM weights (``net``'s fp32 parameters, the convolutions folded in float64, each rounded once) and an fp16 stored ``pooled``,
+    conv1 and conv2 on the fp16 MFMA, every sum in fp32, fp32 states and logits.  Same surface: ``run`` takes an fp16 ring,
+    ``stage`` returns ``pooled`` as an fp16 tensor."""
+
+    ABI = "rva_cnnlstm_f16_plan"
+    HALF = True
+    RING_DTYPE = torch.float16
+    TAP_DTYPES = {"pooled": torch.float16}
+
+    def __call__(self, clips: torch.Tensor) -> torch.Tensor:
+        """``CnnLstmNet.forward`` of clips ``[B, T, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
+        ``[B, classes]`` tensor."""
+        return super().__call__(clips.to(torch.float16))
 
 
 def clip3d_flops(h: int, w: int, frames: int, classes: int = 400) -> Dict[str, float]:

@@ -20,7 +20,7 @@ configured precision, or construction fails with ``ValueError`` (an ``infer_fn``
 
     head                    half: false                       half: true
     yolov5 / yolov8         as plan: engine "fused-f32"       as plan: engine "fused"
-    cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only)
+    cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only) unless hip_lstm_fp16: true
     3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only) unless hip_clip_fp16: true
     conv_gru                ValueError (the reference defines no architecture, so there is no plan)
     resnet                  ValueError (no hand-written plan)
@@ -32,6 +32,15 @@ otherwise refused.  The key changes nothing else: not ``half: false``, not ``cnn
 
     head                    hip_clip_fp16: false              hip_clip_fp16: true
     3d_cnn / slow_fast      half: true -> ValueError          half: true -> engine "clip3d-f16"  (hip_engine: native)
+
+``hip_lstm_fp16`` (a bool, default ``false``: what a reference YAML gets) does the same for the CNN-LSTM head: with ``hip_engine:
+plan`` or ``native``, ``model_type: cnn_lstm`` and ``half: true`` the network runs as engine ``"clip-f16"``
+(clip_plan.FusedCnnLstmF16: fp16 frames, convolution and LSTM weights and stem output, conv1 and conv2 on the fp16 MFMA, fp32
+sums, states and logits) where it is otherwise refused.  The key changes nothing else: not ``half: false``, not the other heads,
+not ``auto``:
+
+    head                    hip_lstm_fp16: false              hip_lstm_fp16: true
+    cnn_lstm                half: true -> ValueError          half: true -> engine "clip-f16"  (hip_engine: plan / native)
 
 ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
 rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
@@ -134,6 +143,7 @@ class DetectorConfig:
     hip_engine: str = "auto"                # backend "hip": "auto", "plan" or "native" (module docstring)
     hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
     hip_clip_fp16: bool = False             # backend "hip", 3d_cnn / slow_fast with half: true and native: the fp16 plan (module docstring)
+    hip_lstm_fp16: bool = False             # backend "hip", cnn_lstm with half: true and plan / native: the fp16 plan (module docstring)
     hip_plan_capacity: int = 0              # backend "hip", YOLO plans: 0 = a plan per batch size, N = one plan of N images (module docstring)
 
     def validate(self) -> None:
@@ -141,6 +151,7 @@ class DetectorConfig:
         _need(self.hip_engine in HIP_ENGINES, f"hip_engine must be one of {set(HIP_ENGINES)}")
         _need(self.hip_box_rows in HIP_BOX_ROWS, f"hip_box_rows must be one of {set(HIP_BOX_ROWS)}")
         _need(isinstance(self.hip_clip_fp16, bool), "hip_clip_fp16 must be true or false")
+        _need(isinstance(self.hip_lstm_fp16, bool), "hip_lstm_fp16 must be true or false")
         _need(isinstance(self.hip_plan_capacity, int) and not isinstance(self.hip_plan_capacity, bool) and self.hip_plan_capacity >= 0,
               "hip_plan_capacity must be an integer >= 0")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,

@@ -28,15 +28,15 @@ import torch.nn as nn
 
 from . import _native as N
 from . import ops
-from .clip_plan import (ENGINE as CLIP_PLAN, ENGINE_3D as CLIP_PLAN_3D, ENGINE_3D_F16 as CLIP_PLAN_3D_F16, Fused3dCnn, Fused3dCnnF16,
-                        FusedCnnLstm, clip_engine, fired_tables)
+from .clip_plan import (ENGINE as CLIP_PLAN, ENGINE_3D as CLIP_PLAN_3D, ENGINE_3D_F16 as CLIP_PLAN_3D_F16, ENGINE_F16 as CLIP_PLAN_F16,
+                        Fused3dCnn, Fused3dCnnF16, FusedCnnLstm, FusedCnnLstmF16, clip_engine, fired_tables)
 from .config import DetectorConfig
 from .detector import Detection
 from .video_stream import FramePacket
 
 LOGGER = logging.getLogger(__name__)
 
-CLIP_PLANS = (CLIP_PLAN, CLIP_PLAN_3D, CLIP_PLAN_3D_F16)      # engines that run the clip network as a hand-written plan (_make_plan)
+CLIP_PLANS = (CLIP_PLAN, CLIP_PLAN_F16, CLIP_PLAN_3D, CLIP_PLAN_3D_F16)      # engines that run the clip network as a hand-written plan (_make_plan)
 
 
 @dataclass(slots=True)
@@ -171,10 +171,11 @@ class _HipTemporalDetector:
         self.half = bool(config.half)
         self._infer_fn = infer_fn
         # "torch", "infer_fn", "clip-f32" (cnn_lstm, half: false, hip_engine: plan / native) or "clip3d-f32" (3d_cnn / slow_fast,
-        # half: false, hip_engine: native) or "clip3d-f16" (the same with half: true and hip_clip_fp16: true): clip_plan.clip_engine
+        # half: false, hip_engine: native) or "clip3d-f16" (the same with half: true and hip_clip_fp16: true) or "clip-f16" (cnn_lstm,
+        # half: true, hip_engine: plan / native, hip_lstm_fp16: true): clip_plan.clip_engine
         self.engine = clip_engine(config.model_type, self.half, getattr(config, "hip_engine", "auto"), infer_fn is not None,
-                                  bool(getattr(config, "hip_clip_fp16", False)))
-        self._net_f32 = None                   # "clip3d-f16": an fp32 copy of the network, so the plan rounds its weights once
+                                  bool(getattr(config, "hip_clip_fp16", False)), lstm_fp16=bool(getattr(config, "hip_lstm_fp16", False)))
+        self._net_f32 = None                   # the fp16 plans: an fp32 copy of the network, so the plan rounds its weights once
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -183,7 +184,7 @@ class _HipTemporalDetector:
                 net = self._default_net()
                 torch.random.set_rng_state(st)
             self.net = net.eval().to(self.device)
-            if self.engine == CLIP_PLAN_3D_F16:
+            if self.engine in (CLIP_PLAN_3D_F16, CLIP_PLAN_F16):
                 self._net_f32 = copy.deepcopy(self.net)     # before the in-place conversion to fp16 below
             self.net = self.net.to(self._frame_dtype())
         self._buf: Dict[str, Deque] = {}
@@ -422,12 +423,16 @@ class _HipTemporalDetector:
 class HipCNNLSTMDetector(_HipTemporalDetector):
     """CNN-LSTM head (temporal_detector.py:150-426): float32 ImageNet normalisation, clips ``[1,T,3,H,W]``.  With ``half: false``
     and ``hip_engine: plan`` the network and its top-5 run as the hand-written fp32 clip plan (engine ``"clip-f32"``,
-    clip_plan.FusedCnnLstm), reading the clip frames straight from the frame ring; ``half: true`` with ``plan`` is refused."""
+    clip_plan.FusedCnnLstm), reading the clip frames straight from the frame ring; ``half: true`` with ``plan`` is refused unless
+    ``hip_lstm_fp16: true`` opts into the fp16 MFMA plan (engine ``"clip-f16"``, clip_plan.FusedCnnLstmF16: the ring holds fp16
+    frames and the plan is packed from an fp32 copy of the network, so the weights are rounded once)."""
 
     def _default_net(self) -> nn.Module:
         return CnnLstmNet(self.config.num_action_classes)
 
     def _make_plan(self, max_clips: int) -> FusedCnnLstm:
+        if self.engine == CLIP_PLAN_F16:
+            return FusedCnnLstmF16(self._net_f32, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
         return FusedCnnLstm(self.net, self.input_hw, self.sched.L, max_clips, ctx=self.ctx, device=self.device)
 
 
