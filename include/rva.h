@@ -791,6 +791,41 @@ enum rva_resnet_stage {
 int rva_resnet_plan_stage(rva_resnet_plan *plan, int stage, int n, void *dst, int64_t dst_floats, int64_t *n_floats,
                           rva_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The fp16 ResNet-18 plan (csrc/rva_resnet_f16.hip): the network of rva_resnet_plan for `half: true` -- fp16 frames, fp16
+ * convolution weights and fp16 stored activations on v_mfma_f32_32x32x16_f16, every sum in fp32.  It shares rva_resnet_desc,
+ * rva_resnet_weights and enum rva_resnet_stage.
+ *
+ * rva_resnet_f16_plan_create: `weights` = fp32 host arrays in the layouts of rva_resnet_plan_create (BatchNorm folded by the
+ *   caller).  stem_w and the 19 conv[i].w are rounded ONCE to fp16, round to nearest even; RVA_ERR_ARG, naming the array
+ *   ("stem_w", "conv[i].w"), if a value does not stay finite in fp16.  All biases, head weight and head bias stay fp32.  The
+ *   descriptor limits are those of rva_resnet_plan_create; a workspace larger than the free device memory is refused with
+ *   RVA_ERR_CAPACITY before anything is allocated.
+ * rva_resnet_f16_plan_run: frames = a device array of planar fp16 frames [3][height][width] (what rva_preprocess_frames_* writes
+ *   for RVA_F16 with RVA_NORM_IMAGENET_F32; no alignment of a frame row is assumed), read through frame_index as in
+ *   rva_resnet_plan_run.  logits = device fp32 [n][classes].  Arithmetic: every sum accumulates in fp32 (products of two fp16
+ *   values are exact in fp32) in one fixed order per layer; the stored activations are fp16 with one rounding of the fp32 epilogue
+ *   value, except the last block's output, the spatial mean and the logits, which are fp32.  Every launch goes to `stream`; no
+ *   host synchronisation, no allocation: capturable.  A frame's logits are bit-identical for every batch size, position in the
+ *   batch, index-table permutation and launch mode.
+ * rva_resnet_f16_plan_run_post / _info: as rva_resnet_plan_run_post / _info (the workspace is about half the fp32 plan's).
+ * rva_resnet_f16_plan_stage: the tap of rva_resnet_plan_stage, one device-to-device copy and no kernel, with the same layouts,
+ *   rules and errors; dst_elems / *n_elems count ELEMENTS of the stage's type:
+ *     RVA_RESNET_STAGE_POOLED, MID0 + b, DOWN2 / 4 / 6, OUT0 + b for b = 0..6   fp16 elements
+ *     RVA_RESNET_STAGE_OUT0 + 7, RVA_RESNET_STAGE_FEAT                          fp32 elements
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_resnet_f16_plan rva_resnet_f16_plan;
+int rva_resnet_f16_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *weights,
+                               rva_resnet_f16_plan **out);
+void rva_resnet_f16_plan_destroy(rva_resnet_f16_plan *plan);
+int rva_resnet_f16_plan_info(const rva_resnet_f16_plan *plan, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches);
+int rva_resnet_f16_plan_run(rva_resnet_f16_plan *plan, const void *frames, const int32_t *frame_index, int n, void *logits,
+                            rva_stream_t stream);
+int rva_resnet_f16_plan_run_post(rva_resnet_f16_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                                 void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *plan, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems,
+                              rva_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)
  * for a tick of NV12 surfaces: gray -> 5x5 Gaussian -> |diff| against prev_blur[i] -> counts[i] = number of

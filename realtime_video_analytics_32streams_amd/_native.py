@@ -19,7 +19,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
 SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip", "rva_clip.hip",
-           "rva_clip3d.hip", "rva_clip3d_f16.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+           "rva_clip3d.hip", "rva_clip3d_f16.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]
@@ -288,6 +288,12 @@ def lib() -> C.CDLL:
         "rva_resnet_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_resnet_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
         "rva_resnet_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
+        "rva_resnet_f16_plan_create": (C.c_int, [_P, C.POINTER(ResNetDesc), C.POINTER(ResNetWeights), C.POINTER(_P)]),
+        "rva_resnet_f16_plan_destroy": (None, [_P]),
+        "rva_resnet_f16_plan_info": (C.c_int, [_P, i32p, i64p, i32p]),
+        "rva_resnet_f16_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+        "rva_resnet_f16_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_resnet_f16_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -331,7 +337,8 @@ EXPORTS = [
     "rva_cnnlstm_f16_plan_run", "rva_cnnlstm_f16_plan_run_post", "rva_cnnlstm_f16_plan_stage", "rva_cnn3d_plan_create", "rva_cnn3d_plan_destroy", "rva_cnn3d_plan_info", "rva_cnn3d_plan_run",
     "rva_cnn3d_plan_run_post", "rva_cnn3d_plan_stage", "rva_cnn3d_f16_plan_create", "rva_cnn3d_f16_plan_destroy", "rva_cnn3d_f16_plan_info",
     "rva_cnn3d_f16_plan_run", "rva_cnn3d_f16_plan_run_post", "rva_cnn3d_f16_plan_stage", "rva_resnet_plan_create", "rva_resnet_plan_destroy", "rva_resnet_plan_info",
-    "rva_resnet_plan_run", "rva_resnet_plan_run_post", "rva_resnet_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
+    "rva_resnet_plan_run", "rva_resnet_plan_run_post", "rva_resnet_plan_stage", "rva_resnet_f16_plan_create", "rva_resnet_f16_plan_destroy",
+    "rva_resnet_f16_plan_info", "rva_resnet_f16_plan_run", "rva_resnet_f16_plan_run_post", "rva_resnet_f16_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
 ]
 

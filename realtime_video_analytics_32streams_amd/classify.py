@@ -19,7 +19,7 @@ from . import _native as N
 from . import ops
 from .config import DetectorConfig
 from .detector import BaseDetector, Detection
-from .resnet_plan import ENGINE as RESNET_PLAN, FusedResNet18
+from .resnet_plan import ENGINE as RESNET_PLAN, ENGINE_F16 as RESNET_PLAN_F16, FusedResNet18, FusedResNet18F16
 from .video_stream import FramePacket
 
 
@@ -60,16 +60,16 @@ class _ResTick:
     rows: int                                   # streams of the group (batch rows of the PostBuffers)
     wh: Tuple[int, int]                         # (width, height) of the group's frames: the full-frame box
     slot: int                                   # pipeline slot (tick parity) whose buffers this tick uses
-    x: torch.Tensor                             # [rows, 3, H, W] fp32: a view of the slot's input buffer
+    x: torch.Tensor                             # [rows, 3, H, W] fp32 (fp16 on "resnet-f16"): a view of the slot's input buffer
 
 
 class _ResSlot:
     """One tick slot's input buffer (K1 writes it, the network reads it) and, on the plan engine, its plan with two logits
     sets used in turn: the tail of the previous tick that used this slot may still read the other set (temporal._PlanSlot)."""
 
-    def __init__(self, cap: int, hw, device, plan: Optional[FusedResNet18]):
+    def __init__(self, cap: int, hw, device, plan: Optional[FusedResNet18], dtype: torch.dtype = torch.float32):
         self.cap, self.plan, self.turn = cap, plan, 0
-        self.input = torch.empty((cap, 3, *hw), dtype=torch.float32, device=device)
+        self.input = torch.empty((cap, 3, *hw), dtype=dtype, device=device)
         self.iota = torch.arange(cap, dtype=torch.int32, device=device)
         self.logits = [torch.empty((cap, plan.classes), dtype=torch.float32, device=device) for _ in range(2)] if plan else []
 
@@ -79,8 +79,11 @@ class HipResNetDetector(BaseDetector):
     device path of the tick pipeline (``stage_pre`` / ``stage_net`` / ``stage_post``: K1 into the tick slot's input buffer, the
     network, the top-K as device result rows -- no host synchronisation).  ``engine``: ``"infer_fn"`` (a caller's function
     overrides everything), ``"resnet-f32"`` (``hip_engine: plan``: the network and the device path's top-K run as the
-    hand-written fp32 plan, resnet_plan.FusedResNet18) or ``"torch"`` (PyTorch-ROCm).  ``half`` has no effect on this head: it
-    runs float32 like the reference's pre-process.  ``hip_engine: native`` is refused."""
+    hand-written fp32 plan, resnet_plan.FusedResNet18), ``"resnet-f16"`` (below) or ``"torch"`` (PyTorch-ROCm).  Without the
+    detector key ``hip_resnet_fp16`` ``half`` has no effect on this head -- it runs float32 like the reference's pre-process --
+    and ``hip_engine: native`` is refused.  ``hip_resnet_fp16: true`` with ``half: true`` and ``hip_engine: plan`` or ``native``
+    opts into the fp16 MFMA plan (engine ``"resnet-f16"``, resnet_plan.FusedResNet18F16: K1 writes fp16 frames, fp16 weights and
+    stored activations, fp32 sums and logits); the key changes nothing else."""
 
     def __init__(self, config: DetectorConfig, net: Optional[nn.Module] = None, infer_fn=None, seed: int = 2,
                  device: Optional[int] = None):
@@ -90,10 +93,15 @@ class HipResNetDetector(BaseDetector):
         self.input_hw = (int(config.input_size[0]), int(config.input_size[1])) if config.input_size else (224, 224)
         self._infer_fn = infer_fn
         hip_engine = getattr(config, "hip_engine", "auto")
-        if infer_fn is None and hip_engine == "native":
+        fp16 = hip_engine in ("plan", "native") and bool(config.half) and bool(getattr(config, "hip_resnet_fp16", False))
+        if infer_fn is None and hip_engine == "native" and not fp16:
             raise ValueError("hip_engine: native has no hand-written plan for model_type 'resnet' (the network runs through "
-                             "PyTorch-ROCm with hip_engine: auto)")
-        self.engine = "infer_fn" if infer_fn is not None else (RESNET_PLAN if hip_engine == "plan" else "torch")
+                             "PyTorch-ROCm with hip_engine: auto; half: true with hip_resnet_fp16: true runs the fp16 plan "
+                             "resnet-f16)")
+        self.engine = "infer_fn" if infer_fn is not None else \
+            RESNET_PLAN_F16 if fp16 else (RESNET_PLAN if hip_engine == "plan" else "torch")
+        self._planned = self.engine in (RESNET_PLAN, RESNET_PLAN_F16)         # the network and the top-K run as a plan
+        self._in_dtype = torch.float16 if self.engine == RESNET_PLAN_F16 else torch.float32     # what K1 writes
         self.net = None
         if infer_fn is None:
             if net is None:
@@ -120,18 +128,19 @@ class HipResNetDetector(BaseDetector):
                 t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
                 dev.append(t.to(self.device).contiguous())
         if out is None:
-            out = torch.empty((len(dev), 3, *self.input_hw), dtype=torch.float32, device=self.device)
+            out = torch.empty((len(dev), 3, *self.input_hw), dtype=self._in_dtype, device=self.device)
         for b0 in range(0, len(dev), N.RVA_MAX_BATCH):
-            ops.preprocess_frames(dev[b0:b0 + N.RVA_MAX_BATCH], self.input_hw, N.NORM_IMAGENET_F32, N.LAYOUT_NCHW, torch.float32,
+            ops.preprocess_frames(dev[b0:b0 + N.RVA_MAX_BATCH], self.input_hw, N.NORM_IMAGENET_F32, N.LAYOUT_NCHW, self._in_dtype,
                                   out=out[b0:b0 + N.RVA_MAX_BATCH], ctx=self.ctx)
         return out
 
     def _make_plan(self, max_frames: int) -> FusedResNet18:
-        return FusedResNet18(self.net, self.input_hw, max_frames, self.config.resnet_top_k, ctx=self.ctx, device=self.device)
+        cls = FusedResNet18F16 if self.engine == RESNET_PLAN_F16 else FusedResNet18
+        return cls(self.net, self.input_hw, max_frames, self.config.resnet_top_k, ctx=self.ctx, device=self.device)
 
     def _network(self, x: torch.Tensor) -> torch.Tensor:
         """``[B, 3, H, W]`` -> raw ``[B, classes]`` on this detector's engine (the host path: a fresh tensor)."""
-        if self.engine == RESNET_PLAN:
+        if self._planned:
             if self._host_plan is None or self._host_plan.max_clips < x.shape[0]:
                 self._host_plan = self._make_plan(int(x.shape[0]))
             return self._host_plan(x)
@@ -175,7 +184,8 @@ class HipResNetDetector(BaseDetector):
             if rs is not None:
                 torch.cuda.synchronize(self.device)          # the old buffers may still be read by a tick in flight
             cap = max(rows, self._streams, 1)
-            rs = self._slots[slot] = _ResSlot(cap, self.input_hw, self.device, self._make_plan(cap) if self.engine == RESNET_PLAN else None)
+            rs = self._slots[slot] = _ResSlot(cap, self.input_hw, self.device, self._make_plan(cap) if self._planned else None,
+                                              self._in_dtype)
         return rs
 
     def stage_pre(self, packets: Sequence[FramePacket]) -> _ResTick:
@@ -187,7 +197,7 @@ class HipResNetDetector(BaseDetector):
 
     def stage_net(self, pre: _ResTick) -> torch.Tensor:
         """The group's frames as ONE network batch: ``[rows, classes]`` raw outputs (no softmax)."""
-        if self.engine == RESNET_PLAN:
+        if self._planned:
             rs = self._slots[pre.slot]
             logits = rs.logits[rs.turn]
             rs.turn ^= 1
@@ -203,7 +213,7 @@ class HipResNetDetector(BaseDetector):
         post = self._post.get(key)
         if post is None:
             post = self._post[key] = ops.PostBuffers.allocate(pre.rows, max(8, k), self.device)
-        plan = self.engine == RESNET_PLAN
+        plan = self._planned
         tkey = (pre.rows, *pre.wh, plan)
         tab = self._tables.get(tkey)
         if tab is None:                        # every row has a frame: the table is constant per (rows, w, h)

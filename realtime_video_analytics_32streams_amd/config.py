@@ -23,7 +23,7 @@ configured precision, or construction fails with ``ValueError`` (an ``infer_fn``
     cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only) unless hip_lstm_fp16: true
     3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only) unless hip_clip_fp16: true
     conv_gru                ValueError (the reference defines no architecture, so there is no plan)
-    resnet                  ValueError (no hand-written plan)
+    resnet                  ValueError (no hand-written plan) ValueError (no hand-written plan) unless hip_resnet_fp16: true
 
 ``hip_clip_fp16`` (a bool, default ``false``: what a reference YAML gets) opts the 3D-CNN head into its fp16 plan: with
 ``hip_engine: native``, ``model_type: 3d_cnn`` / ``slow_fast`` and ``half: true`` the network runs as engine ``"clip3d-f16"``
@@ -41,6 +41,16 @@ not ``auto``:
 
     head                    hip_lstm_fp16: false              hip_lstm_fp16: true
     cnn_lstm                half: true -> ValueError          half: true -> engine "clip-f16"  (hip_engine: plan / native)
+
+``hip_resnet_fp16`` (a bool, default ``false``: what a reference YAML gets) is the opt-in of the ResNet head: with ``hip_engine:
+plan`` or ``native``, ``model_type: resnet`` and ``half: true`` the network runs as engine ``"resnet-f16"``
+(resnet_plan.FusedResNet18F16: fp16 frames, convolution weights and stored activations on the fp16 MFMA, fp32 sums, mean and
+logits).  The key changes nothing else: without it ``plan`` stays ``"resnet-f32"`` whatever ``half`` says and ``native`` stays
+refused, as it does with ``half: false``; ``auto`` is PyTorch-ROCm:
+
+    head                    hip_resnet_fp16: false                        hip_resnet_fp16: true
+    resnet, plan            engine "resnet-f32" (half has no effect)      half: true -> engine "resnet-f16"
+    resnet, native          ValueError (no hand-written plan)             half: true -> engine "resnet-f16"
 
 ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
 rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
@@ -144,6 +154,7 @@ class DetectorConfig:
     hip_box_rows: str = "fp16"              # backend "hip", YOLO with half: true: "fp16" or "fp32" (module docstring)
     hip_clip_fp16: bool = False             # backend "hip", 3d_cnn / slow_fast with half: true and native: the fp16 plan (module docstring)
     hip_lstm_fp16: bool = False             # backend "hip", cnn_lstm with half: true and plan / native: the fp16 plan (module docstring)
+    hip_resnet_fp16: bool = False           # backend "hip", resnet with half: true and plan / native: the fp16 plan (module docstring)
     hip_plan_capacity: int = 0              # backend "hip", YOLO plans: 0 = a plan per batch size, N = one plan of N images (module docstring)
 
     def validate(self) -> None:
@@ -152,6 +163,7 @@ class DetectorConfig:
         _need(self.hip_box_rows in HIP_BOX_ROWS, f"hip_box_rows must be one of {set(HIP_BOX_ROWS)}")
         _need(isinstance(self.hip_clip_fp16, bool), "hip_clip_fp16 must be true or false")
         _need(isinstance(self.hip_lstm_fp16, bool), "hip_lstm_fp16 must be true or false")
+        _need(isinstance(self.hip_resnet_fp16, bool), "hip_resnet_fp16 must be true or false")
         _need(isinstance(self.hip_plan_capacity, int) and not isinstance(self.hip_plan_capacity, bool) and self.hip_plan_capacity >= 0,
               "hip_plan_capacity must be an integer >= 0")
         _need(self.backend in REFERENCE_BACKENDS + HIP_BACKENDS,

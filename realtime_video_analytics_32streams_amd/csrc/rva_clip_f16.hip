@@ -345,17 +345,6 @@ size_t lstm_lds(int hidden)
     return (size_t)(LSTM_G * LSTM_S * lstm_slice(2 * hidden) + LSTM_R * LSTM_S * LSTM_G + LSTM_R * LSTM_G) * sizeof(float);
 }
 
-// `n` fp32 values rounded once to fp16 (round to nearest even); false if one does not stay finite
-bool round_f16(const float *src, size_t n, std::vector<_Float16> &dst)
-{
-    dst.resize(n);
-    for (size_t i = 0; i < n; ++i) {
-        dst[i] = (_Float16)src[i];
-        if (!std::isfinite((float)dst[i])) return false;
-    }
-    return true;
-}
-
 // rows x (ka + kb) weights [a | b] -> the slice-major layout of K_lstm, zero-padded
 std::vector<_Float16> lstm_pack(const std::vector<_Float16> &a, int ka, const std::vector<_Float16> *b, int kb, int rows)
 {
@@ -369,10 +358,48 @@ std::vector<_Float16> lstm_pack(const std::vector<_Float16> &a, int ka, const st
 
 }  // namespace
 
+// The internal entry points of K_stem (rva_internal.h), shared with rva_resnet_f16.hip.
+bool rva_round_f16(const float *src, size_t n, std::vector<_Float16> &dst)
+{
+    dst.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        dst[i] = (_Float16)src[i];
+        if (!std::isfinite((float)dst[i])) return false;
+    }
+    return true;
+}
+
+// [co][ci][ky][kx] -> [co][(ci 7 + ky) 8 + kx] in rows of KPS, zero at kx = 7, in row 21 and in the row's tail
+std::vector<_Float16> rva_clip16_stem_pack(const std::vector<_Float16> &c1)
+{
+    std::vector<_Float16> w1((size_t)C1 * KPS, (_Float16)0.f);
+    for (int co = 0; co < C1; ++co)
+        for (int row = 0; row < 3 * K1; ++row)
+            for (int kx = 0; kx < K1; ++kx) w1[(size_t)co * KPS + row * 8 + kx] = c1[((size_t)co * 3 * K1 + row) * K1 + kx];
+    return w1;
+}
+
+// K_stem keeps its LDS static (51 KB): there is no limit to raise, the call only keeps the shape of rva_clip_stem_prepare
+int rva_clip16_stem_prepare(rva_ctx *ctx)
+{
+    return ctx ? RVA_OK : RVA_ERR_ARG;
+}
+
+int rva_clip16_stem_launch(rva_ctx *ctx, const _Float16 *frames, const int32_t *frame_index, const _Float16 *w1, const float *b1,
+                           _Float16 *pooled, int H, int W, int n_frames, hipStream_t st)
+{
+    const int Hc = (H + 2 * 3 - K1) / 2 + 1, Wc = (W + 2 * 3 - K1) / 2 + 1;
+    const int Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;
+    const int tiles_x = rva_ceil_div(Wp, PT), tiles = tiles_x * rva_ceil_div(Hp, PT);
+    k_clip16_stem<<<dim3(tiles, n_frames), STEM_THREADS, 0, st>>>(frames, frame_index, w1, b1, pooled, H, W, Hc, Wc, Hp, Wp, tiles_x);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
 struct rva_cnnlstm_f16_plan {
     rva_ctx *ctx = nullptr;
     rva_cnnlstm_desc d{};
-    int Hc = 0, Wc = 0, Hp = 0, Wp = 0, stem_tiles_x = 0, stem_tiles = 0, conv2_tiles = 0;
+    int Hc = 0, Wc = 0, Hp = 0, Wp = 0, conv2_tiles = 0;
     _Float16 *w1 = nullptr, *w2 = nullptr, *wih1 = nullptr, *whh1 = nullptr, *wl2 = nullptr, *pooled = nullptr;
     float *b1 = nullptr, *b2 = nullptr, *bl1 = nullptr, *bl2 = nullptr, *wh = nullptr, *bh = nullptr;
     float *partial = nullptr, *feat = nullptr, *gx = nullptr, *h1 = nullptr, *h2 = nullptr, *c1 = nullptr, *c2 = nullptr;
@@ -406,16 +433,14 @@ int rva_cnnlstm_f16_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, cons
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_create: every weight array is required");
     const int h = d.hidden, G4 = 4 * h, T = d.frames;
     std::vector<_Float16> c1, c2, ih1, hh1, ih2, hh2;
-    const char *bad = !round_f16(wt->conv1_w, (size_t)C1 * 3 * K1 * K1, c1) ? "conv1_w" :
-                      !round_f16(wt->conv2_w, (size_t)C2 * C1 * 9, c2) ? "conv2_w" :
-                      !round_f16(wt->w_ih1, (size_t)G4 * C2, ih1) ? "w_ih1" : !round_f16(wt->w_hh1, (size_t)G4 * h, hh1) ? "w_hh1" :
-                      !round_f16(wt->w_ih2, (size_t)G4 * h, ih2) ? "w_ih2" : !round_f16(wt->w_hh2, (size_t)G4 * h, hh2) ? "w_hh2" : nullptr;
+    const char *bad = !rva_round_f16(wt->conv1_w, (size_t)C1 * 3 * K1 * K1, c1) ? "conv1_w" :
+                      !rva_round_f16(wt->conv2_w, (size_t)C2 * C1 * 9, c2) ? "conv2_w" :
+                      !rva_round_f16(wt->w_ih1, (size_t)G4 * C2, ih1) ? "w_ih1" : !rva_round_f16(wt->w_hh1, (size_t)G4 * h, hh1) ? "w_hh1" :
+                      !rva_round_f16(wt->w_ih2, (size_t)G4 * h, ih2) ? "w_ih2" : !rva_round_f16(wt->w_hh2, (size_t)G4 * h, hh2) ? "w_hh2" : nullptr;
     if (bad) return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_create: a value of %s does not stay finite in fp16", bad);
-    // conv1: [co][ci][ky][kx] -> [co][(ci 7 + ky) 8 + kx] in rows of KPS, zero at kx = 7, in row 21 and in the row's tail; conv2: [co][ci][ky][kx] -> [co][tap][ci]
-    std::vector<_Float16> w1((size_t)C1 * KPS, (_Float16)0.f), w2((size_t)C2 * 9 * C1);
-    for (int co = 0; co < C1; ++co)
-        for (int row = 0; row < 3 * K1; ++row)
-            for (int kx = 0; kx < K1; ++kx) w1[(size_t)co * KPS + row * 8 + kx] = c1[((size_t)co * 3 * K1 + row) * K1 + kx];
+    // conv1: the stem's packed layout; conv2: [co][ci][ky][kx] -> [co][tap][ci]
+    const std::vector<_Float16> w1 = rva_clip16_stem_pack(c1);
+    std::vector<_Float16> w2((size_t)C2 * 9 * C1);
     for (int co = 0; co < C2; ++co)
         for (int ci = 0; ci < C1; ++ci)
             for (int t = 0; t < 9; ++t) w2[((size_t)co * 9 + t) * C1 + ci] = c2[((size_t)co * C1 + ci) * 9 + t];
@@ -426,8 +451,6 @@ int rva_cnnlstm_f16_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, cons
     if (const char *e = getenv("RVA_CLIP16_WLDS")) p->wlds = atoi(e) != 0;
     p->Hc = (d.height + 2 * 3 - K1) / 2 + 1; p->Wc = (d.width + 2 * 3 - K1) / 2 + 1;
     p->Hp = (p->Hc + 2 - 3) / 2 + 1; p->Wp = (p->Wc + 2 - 3) / 2 + 1;
-    p->stem_tiles_x = rva_ceil_div(p->Wp, PT);
-    p->stem_tiles = p->stem_tiles_x * rva_ceil_div(p->Hp, PT);
     p->conv2_tiles = rva_ceil_div(p->Hp * p->Wp, 256);
     const size_t nf = (size_t)d.max_clips * T, mc = (size_t)d.max_clips;
     const size_t n_pooled = nf * p->Hp * p->Wp * C1, n_part = nf * p->conv2_tiles * C2;
@@ -463,6 +486,7 @@ int rva_cnnlstm_f16_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, cons
     step(p->mem.alloc(ctx, &p->c2, mc * h));
     if (rc == RVA_OK && rva_func_smem((const void *)k_clip16_lstm, lstm_lds(h)) != hipSuccess)
         rc = rva_fail(ctx, RVA_ERR_HIP, "rva_cnnlstm_f16_plan_create: cannot raise the LSTM kernel's LDS limit");
+    if (rc == RVA_OK) rc = rva_clip16_stem_prepare(ctx);
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, h);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
@@ -499,13 +523,12 @@ int rva_cnnlstm_f16_plan_run(rva_cnnlstm_f16_plan *p, const void *frames, const 
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_run: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
     const hipStream_t st = (hipStream_t)stream_;
     const int T = p->d.frames, h = p->d.hidden, G4 = 4 * h, nf = n_clips * T;
-    k_clip16_stem<<<dim3(p->stem_tiles, nf), STEM_THREADS, 0, st>>>((const _Float16 *)frames, frame_index, p->w1, p->b1, p->pooled,
-                                                                    p->d.height, p->d.width, p->Hc, p->Wc, p->Hp, p->Wp, p->stem_tiles_x);
-    RVA_HIP(ctx, hipGetLastError());
+    int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->w1, p->b1, p->pooled, p->d.height, p->d.width, nf, st);
+    if (rc != RVA_OK) return rc;
     if (p->wlds) k_clip16_conv2<true><<<dim3(p->conv2_tiles, nf), 256, 0, st>>>(p->pooled, p->w2, p->b2, p->partial, p->Hp, p->Wp, p->conv2_tiles);
     else k_clip16_conv2<false><<<dim3(p->conv2_tiles, nf), 256, 0, st>>>(p->pooled, p->w2, p->b2, p->partial, p->Hp, p->Wp, p->conv2_tiles);
     RVA_HIP(ctx, hipGetLastError());
-    int rc = rva_clip_mean_launch(ctx, p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat, nf, C2, st);
+    rc = rva_clip_mean_launch(ctx, p->partial, p->conv2_tiles, (float)(p->Hp * p->Wp), p->feat, nf, C2, st);
     if (rc != RVA_OK) return rc;
     k_clip16_xproj<<<dim3(rva_ceil_div(G4, 256), n_clips), 256, (size_t)T * C2 * sizeof(float), st>>>(p->feat, p->wih1, p->bl1, p->gx, T, G4);
     RVA_HIP(ctx, hipGetLastError());

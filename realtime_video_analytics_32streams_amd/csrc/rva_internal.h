@@ -138,6 +138,19 @@ int rva_clip_post_prepare(rva_ctx *ctx, int classes);
 int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int classes, int k, const int32_t *rows, int n_rows,
                          int max_det, float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);
 
+// The fp16 stem of rva_clip_f16.hip (K_stem: the same network stage on v_mfma_f32_32x32x16_f16 from planar fp16 frames, `pooled`
+// fp16 NHWC with one rounding), shared with rva_resnet_f16.hip.  rva_round_f16: `n` fp32 values rounded once to fp16 (to nearest
+// even), false if one does not stay finite.  rva_clip16_stem_pack: the rounded conv1 weights [64][3][7][7] in the kernel's layout
+// (what `w1` of the launch points to, on the device).
+bool rva_round_f16(const float *src, size_t n, std::vector<_Float16> &dst);
+std::vector<_Float16> rva_clip16_stem_pack(const std::vector<_Float16> &c1);
+int rva_clip16_stem_prepare(rva_ctx *ctx);
+int rva_clip16_stem_launch(rva_ctx *ctx, const _Float16 *frames, const int32_t *frame_index, const _Float16 *w1, const float *b1,
+                           _Float16 *pooled, int H, int W, int n_frames, hipStream_t st);
+
+// K_mean of the ResNet plans (rva_resnet.hip): feat[img][c] = (the image's P pixels of x [n][P][512] in raster order, from zero) / P
+int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st);
+
 // The tail of every *_plan_stage tap: reports `count` through n_floats, and if dst is given checks its size and copies `count`
 // floats device to device on `st` -- as `rows` rows of row_floats out of a pitch of pitch_floats if rows > 0, else flat.
 int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n_clips, const float *src, int64_t count, int64_t rows,

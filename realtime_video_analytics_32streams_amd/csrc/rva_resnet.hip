@@ -167,6 +167,13 @@ struct ResLayer {                    // one block convolution of the plan
 
 }  // namespace
 
+int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st)
+{
+    k_res_mean<<<n, C_FEAT, 0, st>>>(x, P, feat);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
 struct rva_resnet_plan {
     rva_ctx *ctx = nullptr;
     rva_resnet_desc d{};
@@ -313,8 +320,8 @@ int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *f
         else launch_res_conv<1>(v, g, st, a);
         RVA_HIP(ctx, hipGetLastError());
     }
-    k_res_mean<<<n, C_FEAT, 0, st>>>(p->outb[N_BLOCKS - 1], p->maps[4][0] * p->maps[4][1], p->feat);
-    RVA_HIP(ctx, hipGetLastError());
+    rc = rva_res_mean_launch(ctx, p->outb[N_BLOCKS - 1], p->maps[4][0] * p->maps[4][1], p->feat, n, st);
+    if (rc != RVA_OK) return rc;
     return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C_FEAT, p->d.classes, n, st);
 }
 

@@ -10,6 +10,10 @@ planar fp32 frames (what K1 writes) through a device table of frame indices.  Wh
   * :class:`FusedResNet18`: owns one plan (weights and the workspace for ``max_frames`` frames) and its logits buffer.
 
 ``hip_engine: plan`` with ``model_type: resnet`` selects it (:class:`classify.HipResNetDetector`, engine ``"resnet-f32"``).
+
+With ``half: true`` and the detector key ``hip_resnet_fp16: true`` (``hip_engine: plan`` or ``native``) the same head runs as the
+fp16 MFMA plan ``rva_resnet_f16_plan_*`` (``csrc/rva_resnet_f16.hip``, engine ``"resnet-f16"``): ``pack_resnet18(net, half=True)``
+and :class:`FusedResNet18F16`.
 """
 from __future__ import annotations
 
@@ -20,9 +24,10 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .clip_plan import _ClipPlan, _fold, conv_out
+from .clip_plan import _ClipPlan, _fold, _fold_f16, conv_out
 
 ENGINE = "resnet-f32"        # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
+ENGINE_F16 = "resnet-f16"    # its fp16 MFMA form (half: true, hip_engine: plan / native, hip_resnet_fp16: true)
 
 WIDTHS = (64, 128, 256, 512)
 # launch-order names of the 19 block convolutions' outputs = the taps of rva_resnet_plan_stage
@@ -101,24 +106,29 @@ def _is_resnet18(net) -> bool:
     return True
 
 
-def pack_resnet18(net) -> Dict[str, np.ndarray]:
+def pack_resnet18(net, half: bool = False) -> Dict[str, np.ndarray]:
     """The ``rva_resnet_weights`` arrays of a :class:`classify.ResNet18` (``N.ResNetWeights.NAMES`` order), contiguous fp32, each
     convolution with its BatchNorm folded in float64 and rounded once, in the layouts the kernels read:
 
       * ``stem_w`` ``[64, 3, 7, 7]`` (the module's own layout: the VALU stem keeps a channel's 147 taps in registers);
       * ``c<i>_w`` ``[Cout, k*k, Cin]`` with ``tap = ky*k + kx`` (channels innermost, as the NHWC activations), ``c<i>_b``
         ``[Cout]``; per block conv1, conv2, then its shortcut where it has one (``c6``, ``c11``, ``c16``);
-      * ``head_w`` ``[classes, 512]``, ``head_b`` ``[classes]``."""
+      * ``head_w`` ``[classes, 512]``, ``head_b`` ``[classes]``.
+
+    ``half=True`` (the fp16 plan): the same names, order and layouts, fp16-representable -- ``stem_w`` and every ``c<i>_w`` are
+    folded with their BatchNorm in float64, rounded once to fp16 and widened to fp32 (the values ``rva_resnet_f16_plan_create``
+    then converts exactly); a value beyond fp16 raises ``ValueError`` naming the array.  The biases and the head stay fp32."""
     if not _is_resnet18(net):
         raise ValueError("pack_resnet18: not the ResNet18 architecture")
+    fold = (lambda conv, bn, what: _fold_f16(conv, bn, what, "pack_resnet18")) if half else (lambda conv, bn, what: _fold(conv, bn))  # noqa: E731
     taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)  # noqa: E731  [co,ci,kk] -> [co,kk,ci]
     out = {}
-    out["stem_w"], out["stem_b"] = _fold(net.stem[0], net.stem[1])
+    out["stem_w"], out["stem_b"] = fold(net.stem[0], net.stem[1], "stem_w")
     i = 0
     for blk in net.layers:
         pairs = [(blk.c1, blk.b1), (blk.c2, blk.b2)] + ([(blk.down[0], blk.down[1])] if blk.down is not None else [])
         for conv, bn in pairs:
-            w, b = _fold(conv, bn)
+            w, b = fold(conv, bn, f"c{i}_w")
             out[f"c{i}_w"], out[f"c{i}_b"] = taps_last(w), b
             i += 1
     fc = net.fc
@@ -134,16 +144,17 @@ class FusedResNet18(_ClipPlan):
     no allocation after construction (capturable)."""
 
     ABI = "rva_resnet_plan"
+    HALF = False                              # pack_resnet18(half=...): the precision of the convolution weights
 
     def __init__(self, net, hw: Tuple[int, int], max_frames: int, top_k: int = 5, ctx: Optional[N.Context] = None,
                  device: Optional[torch.device] = None):
-        packed = pack_resnet18(net)                                 # a wrong architecture is refused before the device is touched
+        packed = pack_resnet18(net, half=self.HALF)                 # a wrong architecture is refused before the device is touched
         self._open(hw, 1, max_frames, net.fc.out_features, ctx, device)
         self.top_k = int(top_k)
         self.k = min(self.top_k, self.classes)
         self._create(N.ResNetDesc(self.H, self.W, self.classes, self.top_k, self.max_clips), N.ResNetWeights, packed)
         maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
-        self.ctx.check(self.L.rva_resnet_plan_info(self.handle, maps, C.byref(ws), C.byref(nl)), "rva_resnet_plan_info")
+        self.ctx.check(self._fn("info")(self.handle, maps, C.byref(ws), C.byref(nl)), f"{self.ABI}_info")
         self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
         self.workspace_bytes, self.n_launches = ws.value, nl.value
 
@@ -169,3 +180,20 @@ class FusedResNet18(_ClipPlan):
         if tuple(frames.shape[1:]) != (3, self.H, self.W):
             raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
         return self._run_frames(frames.contiguous(), b)
+
+
+class FusedResNet18F16(FusedResNet18):
+    """One ``rva_resnet_f16_plan``: the network of :class:`FusedResNet18` for ``half: true`` -- fp16 frames, fp16 convolution
+    weights (``net``'s fp32 parameters folded in float64 and rounded once) and fp16 stored activations on the fp16 MFMA, every
+    sum in fp32, fp32 ``out7``, ``feat`` and logits.  Same surface: ``run`` takes fp16 frames, ``stage`` returns every stage but
+    ``out7`` and ``feat`` as an fp16 tensor."""
+
+    ABI = "rva_resnet_f16_plan"
+    HALF = True
+    RING_DTYPE = torch.float16
+    TAP_DTYPES = {n: torch.float16 for n in STAGE_CODES if n not in ("out7", "feat")}
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """``ResNet18.forward`` of frames ``[B, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
+        ``[B, classes]`` tensor."""
+        return super().__call__(frames.to(torch.float16))
