@@ -304,6 +304,8 @@ int rva_tracker_set_next_id(rva_tracker *trk, int64_t next_id, rva_stream_t stre
  * rva_maxpool5_nhwc_f16 / rva_upsample2x_nhwc_f16: SPPF pooling, FPN nearest upsample, on channel slices.
  * rva_yolo_head_f16: DFL expectation + dist2bbox + sigmoid of one pyramid level into
  *   out[batch, 4+nc, anchors_total] at anchor_offset -- the `[B,84,8400]` tensor rva_postprocess_batch reads.
+ *   nc, ldb, ldc % 8 == 0; batch, h, w > 0; 0 <= anchor_offset and anchor_offset + h*w <= anchors_total, else RVA_ERR_ARG
+ *   before any launch.  Logits must be finite (the running maximum of the DFL softmax starts at -1e30, not -inf).
  * -------------------------------------------------------------------------------------------- */
 int rva_conv_cout_pad(int Cout);
 /* number of explicit kernel variants rva_conv2d_nhwc_f16_v accepts (1..N); the plan's autotuner iterates over them */

@@ -4165,8 +4165,10 @@ int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const 
 int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, int batch,
                       int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
 {
-    if (!ctx || !box_logits || !cls_logits || !out || nc % 8 || ldb % 8 || ldc % 8)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_f16: bad argument");
+    if (!ctx) return RVA_ERR_ARG;
+    if (!box_logits || !cls_logits || !out || nc % 8 || ldb % 8 || ldc % 8 || batch <= 0 || h <= 0 || w <= 0 || anchor_offset < 0 ||
+        anchor_offset + h * w > anchors_total)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_f16: bad argument (nc, ldb, ldc %% 8; the level inside the anchor range)");
     HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
                anchors_total, anchor_offset, stride};
     dim3 g(rva_ceil_div(h * w, 256), batch);

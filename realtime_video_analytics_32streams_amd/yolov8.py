@@ -138,7 +138,9 @@ class DetectHead(nn.Module):
             return box, cls
         anchors, strides = self._anchors(feats)
         a = box.shape[2]
-        dist = box.view(b, 4, self.reg_max, a).float().softmax(2)
+        dist = box.view(b, 4, self.reg_max, a)
+        # softmax in fp32 for a half module; a float64 module (the references of the tests and tools) stays float64 throughout
+        dist = (dist if dist.dtype == torch.float64 else dist.float()).softmax(2)
         dist = (dist * self.proj.view(1, 1, -1, 1)).sum(2).to(box.dtype)      # DFL expectation, [b, 4, A]
         lt, rb = dist[:, :2], dist[:, 2:]
         x1y1, x2y2 = anchors.unsqueeze(0) - lt, anchors.unsqueeze(0) + rb

@@ -258,6 +258,34 @@ def test_pool_upsample_head_primitives():
     assert torch.equal(up, out.repeat_interleave(2, 1).repeat_interleave(2, 2))
 
 
+@pytest.mark.parametrize("shape", [(3, 13, 17, 24), (6, 13, 17, 1024)], ids=["8-channel-kernel", "four-groups-kernel"])
+def test_fp16_pools_pad_with_minus_infinity(shape):
+    """All-negative input, drawn from [-3, -1]: a pool that padded with 0 instead of -inf would return 0 at EVERY border pixel (on the
+    zero-mean input of test_pool_upsample_head_primitives only where a whole clipped window is negative).  rva_maxpool5_nhwc_f16 and
+    both kernels behind rva_sppf_pool3_nhwc_f16: C = 24 takes the 8-channel kernel, C % 32 == 0 with batch * C / 32 >= 192 the
+    four-groups one."""
+    L, ctx = N.lib(), ops.context()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    bb, hh, ww, cc = shape
+    ld = 32 + 4 * cc                                                           # [skip 32 | x | y1 | y2 | y3]
+    xs = (-(torch.rand((bb, hh, ww, ld), generator=torch.Generator().manual_seed(17)) * 2 + 1)).half().cuda()
+    assert float(xs.max()) <= -1.0 and float(xs.min()) >= -3.0
+    src = xs[..., 32:32 + cc].clone()
+    one = torch.zeros((bb, hh, ww, cc), dtype=torch.float16, device="cuda")
+    ctx.check(L.rva_maxpool5_nhwc_f16(ctx.handle, C.c_void_p(xs.data_ptr() + 2 * 32), ld, C.c_void_p(one.data_ptr()), cc, bb, hh, ww, cc, s))
+    ctx.check(L.rva_sppf_pool3_nhwc_f16(ctx.handle, C.c_void_p(xs.data_ptr() + 2 * 32), ld, C.c_void_p(xs.data_ptr() + 2 * (32 + cc)),
+                                        C.c_void_p(xs.data_ptr() + 2 * (32 + 2 * cc)), C.c_void_p(xs.data_ptr() + 2 * (32 + 3 * cc)), ld, bb, hh, ww, cc, s))
+    torch.cuda.synchronize()
+    p = src.permute(0, 3, 1, 2).float()
+    for i in range(3):
+        p = F.max_pool2d(p, 5, 1, 2)
+        assert float(p.max()) <= -1.0
+        if i == 0:
+            assert torch.equal(one.float(), p.permute(0, 2, 3, 1)), shape
+        assert torch.equal(xs[..., 32 + cc * (i + 1):32 + cc * (i + 2)].float(), p.permute(0, 2, 3, 1)), (shape, i)
+    assert torch.equal(xs[..., 32:32 + cc], src)                                # the source slice is read, not written
+
+
 def _calibrated_error_report(tag, net, x):
     """The fp16-vs-fp32 numbers north_star speaks in, on weights whose scores MATTER: the seeded network's
     class biases are shifted (as bench.py does) until ~120 anchors per frame clear conf 0.25 -- an uncalibrated random head
