@@ -108,7 +108,7 @@ def _stale() -> bool:
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "rva_internal.h", CSRC / "rva_mfma_f32.h", CSRC / "rva_mfma_f16.h", ROOT / "include" / "rva.h"]
+    deps = [CSRC / s for s in SOURCES] + [CSRC / "rva_internal.h", CSRC / "rva_plan_topo.h", CSRC / "rva_mfma_f32.h", CSRC / "rva_mfma_f16.h", ROOT / "include" / "rva.h"]
     return any(d.exists() and d.stat().st_mtime > t for d in deps)
 
 

@@ -37,7 +37,7 @@ constexpr int STEM_THREADS = 512;
 constexpr size_t STEM_LDS = (size_t)(CT * CTW * C1 + 3 * IT * ITW) * sizeof(float);
 constexpr int LSTM_U = 4, LSTM_S = 16, LSTM_G = 8;         // units per block, k-slices, clips per pass
 constexpr int LSTM_R = 4 * LSTM_U;                         // gate rows per block
-constexpr int MAX_HIDDEN = 1024, MAX_T = 64, MAX_CLASSES = 16384;
+constexpr int MAX_HIDDEN = 1024, MAX_T = 64, MAX_CLASSES = RVA_PLAN_MAX_CLASSES;
 
 // ---------------------------------------------------------------------------------------------------
 // K_stem.  Thread = output channel (tid & 63) x a wave-uniform conv position pair, so the input reads are LDS broadcasts and
@@ -326,7 +326,8 @@ int rva_clip_stem_prepare(rva_ctx *ctx)
 int rva_clip_stem_launch(rva_ctx *ctx, const float *frames, const int32_t *frame_index, const float *w1, const float *b1, float *pooled,
                          int H, int W, int n_frames, hipStream_t st)
 {
-    const int Hc = (H + 2 * 3 - K1) / 2 + 1, Wc = (W + 2 * 3 - K1) / 2 + 1, Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;
+    int Hc, Wc, Hp, Wp;
+    rva_stem_maps(H, W, &Hc, &Wc, &Hp, &Wp);
     const int tiles_x = rva_ceil_div(Wp, PT);
     k_clip_stem<<<dim3(tiles_x * rva_ceil_div(Hp, PT), n_frames), STEM_THREADS, STEM_LDS, st>>>(frames, frame_index, w1, b1, pooled, H, W,
                                                                                                 Hc, Wc, Hp, Wp, tiles_x);
@@ -374,21 +375,30 @@ int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int
     return RVA_OK;
 }
 
-int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n_clips, const float *src, int64_t count, int64_t rows,
-                        int64_t row_floats, int64_t pitch_floats, void *dst, int64_t dst_floats, int64_t *n_floats, hipStream_t st)
+int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n, const char *items, const void *src, size_t esize,
+                        const char *unit, int64_t count, int64_t rows, int64_t row_elems, int64_t pitch_elems, void *dst,
+                        int64_t dst_elems, int64_t *n_elems, hipStream_t st)
 {
-    if (n_floats) *n_floats = count;
+    if (n_elems) *n_elems = count;
     if (!dst) return RVA_OK;
-    if (dst_floats < count)
-        return rva_fail(ctx, RVA_ERR_ARG, "%s: dst holds %lld floats, stage %d of %d clips has %lld", who, (long long)dst_floats, stage,
-                        n_clips, (long long)count);
+    if (dst_elems < count)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: dst holds %lld %s, stage %d of %d %s has %lld", who, (long long)dst_elems, unit, stage,
+                        n, items, (long long)count);
     if (rows) {
-        const size_t width = (size_t)row_floats * sizeof(float);
-        RVA_HIP(ctx, hipMemcpy2DAsync(dst, width, src, (size_t)pitch_floats * sizeof(float), width, (size_t)rows,
-                                      hipMemcpyDeviceToDevice, st));
+        const size_t width = (size_t)row_elems * esize;
+        RVA_HIP(ctx, hipMemcpy2DAsync(dst, width, src, (size_t)pitch_elems * esize, width, (size_t)rows, hipMemcpyDeviceToDevice, st));
     } else {
-        RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, st));
+        RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * esize, hipMemcpyDeviceToDevice, st));
     }
+    return RVA_OK;
+}
+
+int rva_plan_fits(rva_ctx *ctx, const char *who, size_t need, const char *shape)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b)
+        return rva_fail(ctx, RVA_ERR_CAPACITY, "%s: the workspace for %s needs %zu MB, the device has %zu MB free", who, shape,
+                        need >> 20, free_b >> 20);
     return RVA_OK;
 }
 
@@ -416,21 +426,20 @@ int rva_cnnlstm_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, const rv
     if (!wt->conv1_w || !wt->conv1_b || !wt->conv2_w || !wt->conv2_b || !wt->w_ih1 || !wt->b1 || !wt->w_hh1 || !wt->w_ih2 ||
         !wt->w_hh2 || !wt->b2 || !wt->head_w || !wt->head_b)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_create: every weight array is required");
+    // no rva_plan_fits and no max_clips * frames <= 65535 here, unlike rva_cnnlstm_f16_plan_create: this entry has never refused
+    // either, and a new refusal is a change of behaviour that wants its own change
     auto *p = new rva_cnnlstm_plan();
     p->ctx = ctx;
     p->d = d;
-    p->Hc = (d.height + 2 * 3 - K1) / 2 + 1; p->Wc = (d.width + 2 * 3 - K1) / 2 + 1;
-    p->Hp = (p->Hc + 2 - 3) / 2 + 1; p->Wp = (p->Wc + 2 - 3) / 2 + 1;
+    rva_stem_maps(d.height, d.width, &p->Hc, &p->Wc, &p->Hp, &p->Wp);
     p->stem_tiles_x = rva_ceil_div(p->Wp, PT);
     p->stem_tiles = p->stem_tiles_x * rva_ceil_div(p->Hp, PT);
     p->conv2_tiles = rva_ceil_div(p->Hp * p->Wp, 256);
     const int h = d.hidden, G4 = 4 * h, T = d.frames;
     const size_t nf = (size_t)d.max_clips * T;
     // conv2: [co][ci][ky][kx] -> [co][tap][ci]; layer 2: [W_ih2 | W_hh2] -> [4h][2h]
-    std::vector<float> w2((size_t)C2 * 9 * C1), wl2((size_t)G4 * 2 * h);
-    for (int co = 0; co < C2; ++co)
-        for (int ci = 0; ci < C1; ++ci)
-            for (int t = 0; t < 9; ++t) w2[((size_t)co * 9 + t) * C1 + ci] = wt->conv2_w[((size_t)co * C1 + ci) * 9 + t];
+    const std::vector<float> w2 = rva_pack_taps_major(wt->conv2_w, C2, C1);
+    std::vector<float> wl2((size_t)G4 * 2 * h);
     for (int r = 0; r < G4; ++r)
         for (int k = 0; k < h; ++k) {
             wl2[(size_t)r * 2 * h + k] = wt->w_ih2[(size_t)r * h + k];
@@ -544,8 +553,8 @@ int rva_cnnlstm_plan_stage(rva_cnnlstm_plan *p, int stage, int n_clips, void *ds
     default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_plan_stage: unknown stage %d", stage);
     }
     const bool rows = (stage == RVA_CNNLSTM_STAGE_H1 || stage == RVA_CNNLSTM_STAGE_H2) && n_clips < p->d.max_clips;
-    return rva_clip_stage_copy(ctx, "rva_cnnlstm_plan_stage", stage, n_clips, src, count, rows ? T : 0, n_clips * h, p->d.max_clips * h, dst,
-                               dst_floats, n_floats, (hipStream_t)stream_);
+    return rva_clip_stage_copy(ctx, "rva_cnnlstm_plan_stage", stage, n_clips, "clips", src, sizeof(float), "floats", count, rows ? T : 0,
+                               n_clips * h, p->d.max_clips * h, dst, dst_floats, n_floats, (hipStream_t)stream_);
 }
 
 }  // extern "C"

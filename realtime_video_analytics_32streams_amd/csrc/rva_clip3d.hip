@@ -23,20 +23,19 @@
 //   K_mean   a clip's tile partials reduced in tile order and divided by T'*H'*W': the mean kernel of rva_clip.hip.
 //   K_head   Linear: the head kernel of rva_clip.hip (one thread per class, k in order).
 //   K_post   (rva_cnn3d_plan_run_post) the top-k kernel of rva_clip.hip.
-#include "rva_internal.h"
 #include "rva_mfma_f32.h"
+#include "rva_plan_topo.h"
 
 namespace {
 
-constexpr int C1 = 64, C2 = 128, C3 = 256;                 // widths of the architecture
-constexpr int TAPS = 27;
-constexpr int PT = 8;                                      // pooled tile (PT x PT) of K_conv1
+constexpr int C1 = C3D_C1, C2 = C3D_C2, C3 = C3D_C3;       // widths of the architecture
+constexpr int TAPS = C3D_TAPS;
+constexpr int PT = C3D_PT;                                 // pooled tile (PT x PT) of K_conv1
 constexpr int IT = 2 * PT + 2;                             // input rows / columns of that tile (18)
 constexpr int ITW = IT + 2;                                // padded LDS row (20)
 constexpr int CONV1_THREADS = 256;
 constexpr int MT = 2, NT = 4;                              // 32x32 MFMA tiles of a wave: 64 positions x 128 channels
-constexpr int GROUPS = 32;                                 // pool groups (of 8 conv positions) of a K_conv2 block
-constexpr int MAX_CLASSES = 16384;
+constexpr int GROUPS = C3D_GROUPS;                         // pool groups (of 8 conv positions) of a K_conv2 block
 
 // ---------------------------------------------------------------------------------------------------
 // K_conv1.  Thread = output channel (tid & 63) x a wave-uniform pooled position, so the input reads are LDS broadcasts and each
@@ -172,9 +171,9 @@ __global__ void __launch_bounds__(256) k_c3d_conv3(const float *act2, const floa
 struct rva_cnn3d_plan {
     rva_ctx *ctx = nullptr;
     rva_cnn3d_desc d{};
-    int H1 = 0, W1 = 0, T2 = 0, H2 = 0, W2 = 0, conv1_tiles_x = 0, conv1_tiles = 0, conv2_tiles = 0, conv3_tiles = 0;
+    rva_c3d_geom g{};
     float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr, *wh = nullptr, *bh = nullptr;
-    float *act1 = nullptr, *act2 = nullptr, *partial = nullptr, *feat = nullptr;
+    float *stage[4] = {};                                  // act1, act2, partial, feat: indexed by RVA_CNN3D_STAGE_*
     rva_dev_arena mem;
 };
 
@@ -182,51 +181,32 @@ extern "C" {
 
 int rva_cnn3d_plan_create(rva_ctx *ctx, const rva_cnn3d_desc *desc, const rva_cnn3d_weights *wt, rva_cnn3d_plan **out)
 {
-    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_create: null argument");
-    *out = nullptr;
+    int rc = rva_c3d_check_args(ctx, "rva_cnn3d_plan_create", desc, wt, (void **)out);
+    if (rc != RVA_OK) return rc;
     const rva_cnn3d_desc d = *desc;
-    // the pools floor: (1,2,2) then (2,2,2) leave nothing of fewer than 2 frames or 4 rows / columns (torch fails there too)
-    if (d.height < 4 || d.width < 4 || d.frames < 2 || d.classes < 1 || d.classes > MAX_CLASSES || d.max_clips < 1 ||
-        (int64_t)d.max_clips * d.frames > 65535 || (int64_t)d.height * d.width > (1 << 26))
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_create: bad descriptor (height, width >= 4, frames >= 2, classes 1..%d, "
-                        "max_clips >= 1, max_clips * frames <= 65535)", MAX_CLASSES);
-    if (!wt->conv1_w || !wt->conv1_b || !wt->conv2_w || !wt->conv2_b || !wt->conv3_w || !wt->conv3_b || !wt->head_w || !wt->head_b)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_create: every weight array is required");
+    const rva_c3d_geom g = rva_c3d_geometry(d);
+    const size_t mc = (size_t)d.max_clips;
+    const size_t n_w = C3D_W1 + C1 + C3D_W2 + C2 + C3D_W3 + C3 + (size_t)d.classes * (C3 + 1);
+    size_t need = n_w * sizeof(float);
+    for (int64_t e : g.elems) need += mc * e * sizeof(float);
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d clips of %d x %d x %d", d.max_clips, d.frames, d.height, d.width);
+    rc = rva_plan_fits(ctx, "rva_cnn3d_plan_create", need, shape);
+    if (rc != RVA_OK) return rc;
     auto *p = new rva_cnn3d_plan();
     p->ctx = ctx;
     p->d = d;
-    const int T = d.frames;
-    p->H1 = d.height / 2; p->W1 = d.width / 2;
-    p->T2 = T / 2; p->H2 = p->H1 / 2; p->W2 = p->W1 / 2;
-    const size_t ng = (size_t)p->T2 * p->H2 * p->W2;
-    p->conv1_tiles_x = rva_ceil_div(p->W1, PT);
-    p->conv1_tiles = p->conv1_tiles_x * rva_ceil_div(p->H1, PT);
-    p->conv2_tiles = (int)((ng + GROUPS - 1) / GROUPS);
-    p->conv3_tiles = (int)((ng + 255) / 256);
-    const size_t mc = (size_t)d.max_clips;
-    const size_t n_act1 = mc * T * p->H1 * p->W1 * C1, n_act2 = mc * ng * C2, n_part = mc * p->conv3_tiles * C3, n_feat = mc * C3;
-    const size_t n_w = (size_t)C1 * 3 * TAPS + C1 + (size_t)C2 * TAPS * C1 + C2 + (size_t)C3 * TAPS * C2 + C3 + (size_t)d.classes * (C3 + 1);
-    const size_t need = (n_act1 + n_act2 + n_part + n_feat + n_w) * sizeof(float);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
-        delete p;
-        return rva_fail(ctx, RVA_ERR_CAPACITY, "rva_cnn3d_plan_create: the workspace for %d clips of %d x %d x %d needs %zu MB, the "
-                        "device has %zu MB free", d.max_clips, T, d.height, d.width, need >> 20, free_b >> 20);
-    }
-    int rc = RVA_OK;
+    p->g = g;
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    step(p->mem.upload(ctx, &p->w1, wt->conv1_w, (size_t)C1 * 3 * TAPS));
+    step(p->mem.upload(ctx, &p->w1, wt->conv1_w, C3D_W1));
     step(p->mem.upload(ctx, &p->b1, wt->conv1_b, C1));
-    step(p->mem.upload(ctx, &p->w2, wt->conv2_w, (size_t)C2 * TAPS * C1));
+    step(p->mem.upload(ctx, &p->w2, wt->conv2_w, C3D_W2));
     step(p->mem.upload(ctx, &p->b2, wt->conv2_b, C2));
-    step(p->mem.upload(ctx, &p->w3, wt->conv3_w, (size_t)C3 * TAPS * C2));
+    step(p->mem.upload(ctx, &p->w3, wt->conv3_w, C3D_W3));
     step(p->mem.upload(ctx, &p->b3, wt->conv3_b, C3));
     step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * C3));
     step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    step(p->mem.alloc(ctx, &p->act1, n_act1));
-    step(p->mem.alloc(ctx, &p->act2, n_act2));
-    step(p->mem.alloc(ctx, &p->partial, n_part));
-    step(p->mem.alloc(ctx, &p->feat, n_feat));
+    for (int s = 0; s < 4; ++s) step(p->mem.alloc(ctx, &p->stage[s], mc * g.elems[s]));
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, C3);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
@@ -247,10 +227,7 @@ void rva_cnn3d_plan_destroy(rva_cnn3d_plan *p)
 int rva_cnn3d_plan_info(const rva_cnn3d_plan *p, int32_t *pool1, int32_t *pool2, int32_t *tiles, int32_t *n_launches)
 {
     if (!p) return RVA_ERR_ARG;
-    if (pool1) { pool1[0] = p->d.frames; pool1[1] = p->H1; pool1[2] = p->W1; }
-    if (pool2) { pool2[0] = p->T2; pool2[1] = p->H2; pool2[2] = p->W2; }
-    if (tiles) { tiles[0] = p->conv1_tiles; tiles[1] = p->conv2_tiles; tiles[2] = p->conv3_tiles; }
-    if (n_launches) *n_launches = 5;
+    rva_c3d_info(p->g, pool1, pool2, tiles, n_launches);
     return RVA_OK;
 }
 
@@ -262,17 +239,19 @@ int rva_cnn3d_plan_run(rva_cnn3d_plan *p, const void *frames, const int32_t *fra
     if (!frames || !frame_index || !logits || n_clips < 1 || n_clips > p->d.max_clips)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_run: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
     const hipStream_t st = (hipStream_t)stream_;
-    const int T = p->d.frames;
-    k_c3d_conv1<<<dim3(p->conv1_tiles, n_clips * T), CONV1_THREADS, 0, st>>>((const float *)frames, frame_index, p->w1, p->b1, p->act1,
-                                                                             T, p->d.height, p->d.width, p->H1, p->W1, p->conv1_tiles_x);
+    const rva_c3d_geom &g = p->g;
+    float *act1 = p->stage[RVA_CNN3D_STAGE_ACT1], *act2 = p->stage[RVA_CNN3D_STAGE_ACT2];
+    float *partial = p->stage[RVA_CNN3D_STAGE_PARTIAL], *feat = p->stage[RVA_CNN3D_STAGE_FEAT];
+    k_c3d_conv1<<<dim3(g.conv1_tiles, n_clips * g.T), CONV1_THREADS, 0, st>>>((const float *)frames, frame_index, p->w1, p->b1, act1, g.T,
+                                                                              p->d.height, p->d.width, g.H1, g.W1, g.conv1_tiles_x);
     RVA_HIP(ctx, hipGetLastError());
-    k_c3d_conv2<<<dim3(p->conv2_tiles, n_clips), 256, 0, st>>>(p->act1, p->w2, p->b2, p->act2, T, p->H1, p->W1, p->T2, p->H2, p->W2);
+    k_c3d_conv2<<<dim3(g.conv2_tiles, n_clips), 256, 0, st>>>(act1, p->w2, p->b2, act2, g.T, g.H1, g.W1, g.T2, g.H2, g.W2);
     RVA_HIP(ctx, hipGetLastError());
-    k_c3d_conv3<<<dim3(p->conv3_tiles, 2, n_clips), 256, 0, st>>>(p->act2, p->w3, p->b3, p->partial, p->T2, p->H2, p->W2, p->conv3_tiles);
+    k_c3d_conv3<<<dim3(g.conv3_tiles, 2, n_clips), 256, 0, st>>>(act2, p->w3, p->b3, partial, g.T2, g.H2, g.W2, g.conv3_tiles);
     RVA_HIP(ctx, hipGetLastError());
-    int rc = rva_clip_mean_launch(ctx, p->partial, p->conv3_tiles, (float)((size_t)p->T2 * p->H2 * p->W2), p->feat, n_clips, C3, st);
+    int rc = rva_clip_mean_launch(ctx, partial, g.conv3_tiles, (float)((size_t)g.T2 * g.H2 * g.W2), feat, n_clips, C3, st);
     if (rc != RVA_OK) return rc;
-    return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C3, p->d.classes, n_clips, st);
+    return rva_clip_head_launch(ctx, feat, p->wh, p->bh, (float *)logits, C3, p->d.classes, n_clips, st);
 }
 
 int rva_cnn3d_plan_run_post(rva_cnn3d_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
@@ -291,18 +270,9 @@ int rva_cnn3d_plan_stage(rva_cnn3d_plan *p, int stage, int n_clips, void *dst, i
     rva_ctx *ctx = p->ctx;
     if (n_clips < 1 || n_clips > p->d.max_clips)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
-    const int64_t ng = (int64_t)p->T2 * p->H2 * p->W2;
-    const float *src = nullptr;
-    int64_t count = 0;
-    switch (stage) {
-    case RVA_CNN3D_STAGE_ACT1: src = p->act1; count = (int64_t)n_clips * p->d.frames * p->H1 * p->W1 * C1; break;
-    case RVA_CNN3D_STAGE_ACT2: src = p->act2; count = (int64_t)n_clips * ng * C2; break;
-    case RVA_CNN3D_STAGE_PARTIAL: src = p->partial; count = (int64_t)n_clips * p->conv3_tiles * C3; break;
-    case RVA_CNN3D_STAGE_FEAT: src = p->feat; count = (int64_t)n_clips * C3; break;
-    default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: unknown stage %d", stage);
-    }
-    return rva_clip_stage_copy(ctx, "rva_cnn3d_plan_stage", stage, n_clips, src, count, 0, 0, 0, dst, dst_floats, n_floats,
-                               (hipStream_t)stream_);
+    if (stage < 0 || stage > RVA_CNN3D_STAGE_FEAT) return rva_fail(ctx, RVA_ERR_ARG, "rva_cnn3d_plan_stage: unknown stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_cnn3d_plan_stage", stage, n_clips, "clips", p->stage[stage], sizeof(float), "floats",
+                               n_clips * p->g.elems[stage], 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
 }
 
 }  // extern "C"

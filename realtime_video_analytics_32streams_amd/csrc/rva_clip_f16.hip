@@ -60,7 +60,7 @@ constexpr int KPS = KP + 8;                                // row of the packed 
 constexpr int STEM_WAVES = 5, STEM_THREADS = 64 * STEM_WAVES, STEM_MT = 2;   // 10 tiles of 32 positions cover 289
 constexpr int LSTM_U = 4, LSTM_S = 16, LSTM_G = 8;         // units per block, k-slices, clips per pass
 constexpr int LSTM_R = 4 * LSTM_U;                         // gate rows per block
-constexpr int MAX_HIDDEN = 1024, MAX_T = 64, MAX_CLASSES = 16384;
+constexpr int MAX_HIDDEN = 1024, MAX_T = 64, MAX_CLASSES = RVA_PLAN_MAX_CLASSES;
 
 static_assert(STEM_WAVES * STEM_MT * 32 >= NP, "the waves cover the conv tile");
 static_assert(ITW >= IW && ITW % 2 == 0 && CS % 4 == 0, "dword rows, 8-byte conv stores");
@@ -358,7 +358,7 @@ std::vector<_Float16> lstm_pack(const std::vector<_Float16> &a, int ka, const st
 
 }  // namespace
 
-// The internal entry points of K_stem (rva_internal.h), shared with rva_resnet_f16.hip.
+// The internal entry points of rva_internal.h: the weight rounding of every fp16 plan, and K_stem, shared with rva_resnet_f16.hip.
 bool rva_round_f16(const float *src, size_t n, std::vector<_Float16> &dst)
 {
     dst.resize(n);
@@ -388,8 +388,8 @@ int rva_clip16_stem_prepare(rva_ctx *ctx)
 int rva_clip16_stem_launch(rva_ctx *ctx, const _Float16 *frames, const int32_t *frame_index, const _Float16 *w1, const float *b1,
                            _Float16 *pooled, int H, int W, int n_frames, hipStream_t st)
 {
-    const int Hc = (H + 2 * 3 - K1) / 2 + 1, Wc = (W + 2 * 3 - K1) / 2 + 1;
-    const int Hp = (Hc + 2 - 3) / 2 + 1, Wp = (Wc + 2 - 3) / 2 + 1;
+    int Hc, Wc, Hp, Wp;
+    rva_stem_maps(H, W, &Hc, &Wc, &Hp, &Wp);
     const int tiles_x = rva_ceil_div(Wp, PT), tiles = tiles_x * rva_ceil_div(Hp, PT);
     k_clip16_stem<<<dim3(tiles, n_frames), STEM_THREADS, 0, st>>>(frames, frame_index, w1, b1, pooled, H, W, Hc, Wc, Hp, Wp, tiles_x);
     RVA_HIP(ctx, hipGetLastError());
@@ -405,16 +405,6 @@ struct rva_cnnlstm_f16_plan {
     float *partial = nullptr, *feat = nullptr, *gx = nullptr, *h1 = nullptr, *h2 = nullptr, *c1 = nullptr, *c2 = nullptr;
     bool wlds = true;                                // conv2 stages its weights through LDS (A/B switch RVA_CLIP16_WLDS)
     rva_dev_arena mem;
-
-    // the arena hands out floats: n fp16 elements take (n + 1) / 2 of them
-    int alloc_h(_Float16 **dst, size_t n) { return mem.alloc(ctx, reinterpret_cast<float **>(dst), (n + 1) / 2); }
-    int upload_h(_Float16 **dst, const std::vector<_Float16> &src)
-    {
-        const int rc = alloc_h(dst, src.size());
-        if (rc != RVA_OK) return rc;
-        RVA_HIP(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-        return RVA_OK;
-    }
 };
 
 extern "C" {
@@ -439,44 +429,39 @@ int rva_cnnlstm_f16_plan_create(rva_ctx *ctx, const rva_cnnlstm_desc *desc, cons
                       !rva_round_f16(wt->w_ih2, (size_t)G4 * h, ih2) ? "w_ih2" : !rva_round_f16(wt->w_hh2, (size_t)G4 * h, hh2) ? "w_hh2" : nullptr;
     if (bad) return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_create: a value of %s does not stay finite in fp16", bad);
     // conv1: the stem's packed layout; conv2: [co][ci][ky][kx] -> [co][tap][ci]
-    const std::vector<_Float16> w1 = rva_clip16_stem_pack(c1);
-    std::vector<_Float16> w2((size_t)C2 * 9 * C1);
-    for (int co = 0; co < C2; ++co)
-        for (int ci = 0; ci < C1; ++ci)
-            for (int t = 0; t < 9; ++t) w2[((size_t)co * 9 + t) * C1 + ci] = c2[((size_t)co * C1 + ci) * 9 + t];
+    const std::vector<_Float16> w1 = rva_clip16_stem_pack(c1), w2 = rva_pack_taps_major(c2.data(), C2, C1);
     const std::vector<_Float16> whh1 = lstm_pack(hh1, h, nullptr, 0, G4), wl2 = lstm_pack(ih2, h, &hh2, h, G4);
     auto *p = new rva_cnnlstm_f16_plan();
     p->ctx = ctx;
     p->d = d;
     if (const char *e = getenv("RVA_CLIP16_WLDS")) p->wlds = atoi(e) != 0;
-    p->Hc = (d.height + 2 * 3 - K1) / 2 + 1; p->Wc = (d.width + 2 * 3 - K1) / 2 + 1;
-    p->Hp = (p->Hc + 2 - 3) / 2 + 1; p->Wp = (p->Wc + 2 - 3) / 2 + 1;
+    rva_stem_maps(d.height, d.width, &p->Hc, &p->Wc, &p->Hp, &p->Wp);
     p->conv2_tiles = rva_ceil_div(p->Hp * p->Wp, 256);
     const size_t nf = (size_t)d.max_clips * T, mc = (size_t)d.max_clips;
     const size_t n_pooled = nf * p->Hp * p->Wp * C1, n_part = nf * p->conv2_tiles * C2;
     const size_t need = (n_pooled + w1.size() + w2.size() + ih1.size() + whh1.size() + wl2.size()) * sizeof(_Float16) +
                         (n_part + nf * C2 + nf * G4 + 2 * (size_t)T * mc * h + 2 * mc * h + C1 + C2 + 2 * (size_t)G4 +
                          (size_t)d.classes * (h + 1)) * sizeof(float);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d clips of %d x %d x %d", d.max_clips, T, d.height, d.width);
+    int rc = rva_plan_fits(ctx, "rva_cnnlstm_f16_plan_create", need, shape);
+    if (rc != RVA_OK) {
         delete p;
-        return rva_fail(ctx, RVA_ERR_CAPACITY, "rva_cnnlstm_f16_plan_create: the workspace for %d clips of %d x %d x %d needs %zu MB, the "
-                        "device has %zu MB free", d.max_clips, T, d.height, d.width, need >> 20, free_b >> 20);
+        return rc;
     }
-    int rc = RVA_OK;
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    step(p->upload_h(&p->w1, w1));
+    step(p->mem.upload(ctx, &p->w1, w1.data(), w1.size()));
     step(p->mem.upload(ctx, &p->b1, wt->conv1_b, C1));
-    step(p->upload_h(&p->w2, w2));
+    step(p->mem.upload(ctx, &p->w2, w2.data(), w2.size()));
     step(p->mem.upload(ctx, &p->b2, wt->conv2_b, C2));
-    step(p->upload_h(&p->wih1, ih1));
+    step(p->mem.upload(ctx, &p->wih1, ih1.data(), ih1.size()));
     step(p->mem.upload(ctx, &p->bl1, wt->b1, G4));
-    step(p->upload_h(&p->whh1, whh1));
-    step(p->upload_h(&p->wl2, wl2));
+    step(p->mem.upload(ctx, &p->whh1, whh1.data(), whh1.size()));
+    step(p->mem.upload(ctx, &p->wl2, wl2.data(), wl2.size()));
     step(p->mem.upload(ctx, &p->bl2, wt->b2, G4));
     step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * h));
     step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    step(p->alloc_h(&p->pooled, n_pooled));
+    step(p->mem.alloc(ctx, &p->pooled, n_pooled));
     step(p->mem.alloc(ctx, &p->partial, n_part));
     step(p->mem.alloc(ctx, &p->feat, nf * C2));
     step(p->mem.alloc(ctx, &p->gx, nf * G4));
@@ -550,7 +535,8 @@ int rva_cnnlstm_f16_plan_run_post(rva_cnnlstm_f16_plan *p, const void *logits, c
 }
 
 // Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  POOLED is fp16 elements, every other
-// stage fp32, and the counts are element counts; h1 / h2 of fewer clips than the capacity are one 2D copy, as in rva_clip.hip.
+// stage fp32, and the counts are element counts; h1 / h2 of fewer clips than the capacity are T rows of n_clips * hidden out of a
+// pitch of max_clips * hidden: one 2D copy.
 int rva_cnnlstm_f16_plan_stage(rva_cnnlstm_f16_plan *p, int stage, int n_clips, void *dst, int64_t dst_elems, int64_t *n_elems,
                                rva_stream_t stream_)
 {
@@ -559,19 +545,10 @@ int rva_cnnlstm_f16_plan_stage(rva_cnnlstm_f16_plan *p, int stage, int n_clips, 
     if (n_clips < 1 || n_clips > p->d.max_clips)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_stage: bad argument (n_clips %d, capacity %d)", n_clips, p->d.max_clips);
     const int64_t T = p->d.frames, h = p->d.hidden, nf = (int64_t)n_clips * T;
-    const float *src = nullptr;
+    const void *src = nullptr;
     int64_t count = 0;
     switch (stage) {
-    case RVA_CNNLSTM_STAGE_POOLED: {
-        count = nf * p->Hp * p->Wp * C1;
-        if (n_elems) *n_elems = count;
-        if (!dst) return RVA_OK;
-        if (dst_elems < count)
-            return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_stage: dst holds %lld elements, stage %d of %d clips has %lld",
-                            (long long)dst_elems, stage, n_clips, (long long)count);
-        RVA_HIP(ctx, hipMemcpyAsync(dst, p->pooled, (size_t)count * sizeof(_Float16), hipMemcpyDeviceToDevice, (hipStream_t)stream_));
-        return RVA_OK;
-    }
+    case RVA_CNNLSTM_STAGE_POOLED: src = p->pooled; count = nf * p->Hp * p->Wp * C1; break;
     case RVA_CNNLSTM_STAGE_PARTIAL: src = p->partial; count = nf * p->conv2_tiles * C2; break;
     case RVA_CNNLSTM_STAGE_FEAT: src = p->feat; count = nf * C2; break;
     case RVA_CNNLSTM_STAGE_GX: src = p->gx; count = nf * 4 * h; break;
@@ -580,8 +557,10 @@ int rva_cnnlstm_f16_plan_stage(rva_cnnlstm_f16_plan *p, int stage, int n_clips, 
     default: return rva_fail(ctx, RVA_ERR_ARG, "rva_cnnlstm_f16_plan_stage: unknown stage %d", stage);
     }
     const bool rows = (stage == RVA_CNNLSTM_STAGE_H1 || stage == RVA_CNNLSTM_STAGE_H2) && n_clips < p->d.max_clips;
-    return rva_clip_stage_copy(ctx, "rva_cnnlstm_f16_plan_stage", stage, n_clips, src, count, rows ? T : 0, n_clips * h, p->d.max_clips * h, dst,
-                               dst_elems, n_elems, (hipStream_t)stream_);
+    const bool f16 = stage == RVA_CNNLSTM_STAGE_POOLED;    // the size error of an fp32 stage says "floats", as the fp32 plan's
+    return rva_clip_stage_copy(ctx, "rva_cnnlstm_f16_plan_stage", stage, n_clips, "clips", src, f16 ? sizeof(_Float16) : sizeof(float),
+                               f16 ? "elements" : "floats", count, rows ? T : 0, n_clips * h, p->d.max_clips * h, dst, dst_elems, n_elems,
+                               (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -93,24 +93,31 @@ int rva_conv2d_nhwc_f16_sel(rva_ctx *ctx, const void *in, int ldi, const void *w
 // frees ctx->jpeg (rva_jpeg.hip); called by rva_destroy
 void rva_jpeg_free(rva_ctx *ctx);
 
-// Device memory of a clip plan: every buffer is a float array owned until release().
+// ---------------------------------------------------------------------------------------------------
+// The host scaffold of the clip and classifier plans (rva_clip*.hip, rva_clip3d*.hip, rva_resnet*.hip).  The fp32 and the fp16 form
+// of a plan share everything here; a plan file keeps only what differs by precision: element types, rounding, kernels, launches.
+// The networks' own shapes (ResNet-18 topology, 3D-CNN geometry) are in rva_plan_topo.h.
+
+// Device memory of a plan: every buffer is an array of `n` elements of T owned until release().
 struct rva_dev_arena {
     std::vector<void *> allocs;
 
-    int alloc(rva_ctx *ctx, float **dst, size_t n)
+    template <typename T>
+    int alloc(rva_ctx *ctx, T **dst, size_t n)
     {
         void *m = nullptr;
-        RVA_HIP(ctx, hipMalloc(&m, std::max<size_t>(n, 1) * sizeof(float)));
+        RVA_HIP(ctx, hipMalloc(&m, std::max<size_t>(n, 1) * sizeof(T)));
         allocs.push_back(m);
-        *dst = (float *)m;
+        *dst = (T *)m;
         return RVA_OK;
     }
 
-    int upload(rva_ctx *ctx, float **dst, const float *src, size_t n)
+    template <typename T>
+    int upload(rva_ctx *ctx, T **dst, const T *src, size_t n)
     {
         const int rc = alloc(ctx, dst, n);
         if (rc != RVA_OK) return rc;
-        RVA_HIP(ctx, hipMemcpy(*dst, src, n * sizeof(float), hipMemcpyHostToDevice));
+        RVA_HIP(ctx, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
         return RVA_OK;
     }
 
@@ -120,6 +127,31 @@ struct rva_dev_arena {
         allocs.clear();
     }
 };
+
+// What a plan's create refuses before it allocates anything: RVA_ERR_CAPACITY if `need` bytes exceed the free device memory (or
+// it cannot be read).  `shape` is the formatted phrase that names the capacity ("8 clips of 16 x 112 x 112").  In rva_clip.hip.
+int rva_plan_fits(rva_ctx *ctx, const char *who, size_t need, const char *shape);
+
+constexpr int RVA_PLAN_MAX_CLASSES = 16384;                // the top-k kernel keeps a row's logits in LDS
+
+// output length of a stride-2 window (k, pad) over n; the stem's maps: conv 7x7 s2 p3 (Hc x Wc), then max pool 3x3 s2 p1 (Hp x Wp)
+inline int rva_half_map(int n, int k, int pad) { return (n + 2 * pad - k) / 2 + 1; }
+inline void rva_stem_maps(int H, int W, int *Hc, int *Wc, int *Hp, int *Wp)
+{
+    *Hc = rva_half_map(H, 7, 3); *Wc = rva_half_map(W, 7, 3);
+    *Hp = rva_half_map(*Hc, 3, 1); *Wp = rva_half_map(*Wc, 3, 1);
+}
+
+// a 3x3 convolution's weights [co][ci][ky][kx] -> [co][tap][ci], what the MFMA tap loops read
+template <typename T>
+std::vector<T> rva_pack_taps_major(const T *w, int cout, int cin)
+{
+    std::vector<T> out((size_t)cout * 9 * cin);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < 9; ++t) out[((size_t)co * 9 + t) * cin + ci] = w[((size_t)co * cin + ci) * 9 + t];
+    return out;
+}
 
 // The stem (Conv 7x7 s2 p3 + bias + ReLU + MaxPool 3x3 s2 p1 from planar fp32 frames read through a frame-index table, NHWC
 // out: `pooled` = [n_frames][Hp][Wp][64]), mean (tile partials in tile order / n; `rows` blocks of `channels` threads), head
@@ -139,8 +171,8 @@ int rva_clip_post_launch(rva_ctx *ctx, const char *who, const float *logits, int
                          int max_det, float *scores, int32_t *cls, float *boxes, int32_t *counts, hipStream_t st);
 
 // The fp16 stem of rva_clip_f16.hip (K_stem: the same network stage on v_mfma_f32_32x32x16_f16 from planar fp16 frames, `pooled`
-// fp16 NHWC with one rounding), shared with rva_resnet_f16.hip.  rva_round_f16: `n` fp32 values rounded once to fp16 (to nearest
-// even), false if one does not stay finite.  rva_clip16_stem_pack: the rounded conv1 weights [64][3][7][7] in the kernel's layout
+// fp16 NHWC with one rounding), shared with rva_resnet_f16.hip.  rva_round_f16 (every fp16 plan's weight rounding): `n` fp32
+// values rounded once to fp16 (to nearest even), false if one does not stay finite.  rva_clip16_stem_pack: the rounded conv1 weights [64][3][7][7] in the kernel's layout
 // (what `w1` of the launch points to, on the device).
 bool rva_round_f16(const float *src, size_t n, std::vector<_Float16> &dst);
 std::vector<_Float16> rva_clip16_stem_pack(const std::vector<_Float16> &c1);
@@ -151,7 +183,9 @@ int rva_clip16_stem_launch(rva_ctx *ctx, const _Float16 *frames, const int32_t *
 // K_mean of the ResNet plans (rva_resnet.hip): feat[img][c] = (the image's P pixels of x [n][P][512] in raster order, from zero) / P
 int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st);
 
-// The tail of every *_plan_stage tap: reports `count` through n_floats, and if dst is given checks its size and copies `count`
-// floats device to device on `st` -- as `rows` rows of row_floats out of a pitch of pitch_floats if rows > 0, else flat.
-int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n_clips, const float *src, int64_t count, int64_t rows,
-                        int64_t row_floats, int64_t pitch_floats, void *dst, int64_t dst_floats, int64_t *n_floats, hipStream_t st);
+// The tail of every *_plan_stage tap: reports `count` through n_elems, and if dst is given checks its size and copies `count`
+// elements of `esize` bytes device to device on `st` -- as `rows` rows of row_elems out of a pitch of pitch_elems if rows > 0,
+// else flat.  `unit` ("floats" / "elements") and `items` ("clips" / "frames") are the words of the ABI entry's size error.
+int rva_clip_stage_copy(rva_ctx *ctx, const char *who, int stage, int n, const char *items, const void *src, size_t esize,
+                        const char *unit, int64_t count, int64_t rows, int64_t row_elems, int64_t pitch_elems, void *dst,
+                        int64_t dst_elems, int64_t *n_elems, hipStream_t st);

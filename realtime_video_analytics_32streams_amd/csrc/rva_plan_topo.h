@@ -1,0 +1,130 @@
+// Host-only descriptions of the networks that exist as an fp32 and an fp16 plan: the shapes, the order of the launches, what each
+// launch reads and writes, the argument checks, _info and the stage -> element count resolution.  The plan files walk these and add
+// what differs by precision (element sizes, rounding, kernels).  Nothing here is device code.
+#pragma once
+
+#include "rva_internal.h"
+
+// ---------------------------------------------------------------------------------------------------
+// ResNet-18 (rva_resnet.hip, rva_resnet_f16.hip): the stem, then 8 BasicBlocks of widths 64, 64, 128, 128, 256, 256, 512, 512; the
+// first block of the 128 / 256 / 512 stages has stride 2 and a 1x1 stride-2 shortcut convolution.
+constexpr int RES_C_STEM = 64, RES_C_FEAT = 512, RES_BLOCKS = 8, RES_CONVS = 19, RES_STAGES = RVA_RESNET_STAGE_FEAT + 1;
+constexpr int EPI_RELU = 0, EPI_BIAS = 1, EPI_RES_RELU = 2;     // max(acc + b, 0) | acc + b | max((acc + b) + res, 0)
+
+struct rva_res_conv {                // one block convolution
+    int cin, cout, k, stride, H, W, Ho, Wo, epi;
+    int in, res, out;                // the RVA_RESNET_STAGE_* it reads, adds as residual (-1: none) and writes
+    int wi;                          // its index in rva_resnet_weights::conv (the ABI's order of a block: conv1, conv2, shortcut)
+    size_t weights() const { return (size_t)cout * k * k * cin; }
+};
+
+struct rva_res_topo {
+    int maps[5][2];                  // (h, w) of the pooled map and of the four stages
+    rva_res_conv conv[RES_CONVS];    // in launch order: per block conv1, [shortcut], conv2
+    int launch_of[RES_CONVS];        // conv[launch_of[i]].wi == i
+    int64_t elems[RES_STAGES];       // elements of a stage per frame
+};
+
+inline rva_res_topo rva_res_topology(int height, int width)
+{
+    rva_res_topo t{};
+    int hc, wc;
+    rva_stem_maps(height, width, &hc, &wc, &t.maps[0][0], &t.maps[0][1]);
+    t.maps[1][0] = t.maps[0][0]; t.maps[1][1] = t.maps[0][1];
+    for (int s = 2; s <= 4; ++s) { t.maps[s][0] = rva_half_map(t.maps[s - 1][0], 3, 1); t.maps[s][1] = rva_half_map(t.maps[s - 1][1], 3, 1); }
+    t.elems[RVA_RESNET_STAGE_POOLED] = (int64_t)t.maps[0][0] * t.maps[0][1] * RES_C_STEM;
+    t.elems[RVA_RESNET_STAGE_FEAT] = RES_C_FEAT;
+    int x = RVA_RESNET_STAGE_POOLED, wi = 0, n = 0, hin = t.maps[0][0], win = t.maps[0][1];
+    for (int b = 0; b < RES_BLOCKS; ++b) {
+        const int s = 1 + b / 2, c = RES_C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c;
+        const bool shortcut = cin != c;
+        const int ho = t.maps[s][0], wo = t.maps[s][1];
+        const int mid = RVA_RESNET_STAGE_MID0 + b, out = RVA_RESNET_STAGE_OUT0 + b;
+        const int down = shortcut ? RVA_RESNET_STAGE_DOWN2 + (b - 2) / 2 : -1;
+        t.elems[mid] = t.elems[out] = (int64_t)ho * wo * c;
+        if (shortcut) t.elems[down] = t.elems[mid];
+        t.conv[n++] = {cin, c, 3, shortcut ? 2 : 1, hin, win, ho, wo, EPI_RELU, x, -1, mid, wi};
+        if (shortcut) t.conv[n++] = {cin, c, 1, 2, hin, win, ho, wo, EPI_BIAS, x, -1, down, wi + 2};
+        t.conv[n++] = {c, c, 3, 1, ho, wo, ho, wo, EPI_RES_RELU, mid, shortcut ? down : x, out, wi + 1};
+        wi += shortcut ? 3 : 2;
+        x = out; hin = ho; win = wo;
+    }
+    for (int i = 0; i < RES_CONVS; ++i) t.launch_of[t.conv[i].wi] = i;
+    return t;
+}
+
+// the argument checks of a create, under the entry's name; clears *out
+inline int rva_res_check_args(rva_ctx *ctx, const char *who, const rva_resnet_desc *d, const rva_resnet_weights *wt, void **out)
+{
+    if (!ctx || !d || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    if (d->height < 1 || d->width < 1 || d->classes < 1 || d->classes > RVA_PLAN_MAX_CLASSES || d->top_k < 1 || d->max_frames < 1 ||
+        d->max_frames > 65535 || (int64_t)d->height * d->width > (1 << 26))
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535)", who,
+                        RVA_PLAN_MAX_CLASSES);
+    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
+    for (int i = 0; i < RES_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
+    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    return RVA_OK;
+}
+
+inline void rva_res_info(const rva_res_topo &t, size_t workspace_bytes, int32_t *maps, int64_t *ws, int32_t *n_launches)
+{
+    if (maps)
+        for (int s = 0; s < 5; ++s) { maps[2 * s] = t.maps[s][0]; maps[2 * s + 1] = t.maps[s][1]; }
+    if (ws) *ws = (int64_t)workspace_bytes;
+    if (n_launches) *n_launches = 1 + RES_CONVS + 2;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// 3D-CNN (rva_clip3d.hip, rva_clip3d_f16.hip): conv1 + (1,2,2) pool, conv2 + (2,2,2) pool, conv3 + mean.  The pools floor.
+constexpr int C3D_C1 = 64, C3D_C2 = 128, C3D_C3 = 256, C3D_TAPS = 27;
+constexpr int C3D_PT = 8;                                  // pooled tile (PT x PT) of a K_conv1 block
+constexpr int C3D_GROUPS = 32;                             // pool groups (of 8 conv positions) of a K_conv2 block; K_conv3: 256 positions
+constexpr size_t C3D_W1 = (size_t)C3D_C1 * 3 * C3D_TAPS, C3D_W2 = (size_t)C3D_C2 * C3D_TAPS * C3D_C1, C3D_W3 = (size_t)C3D_C3 * C3D_TAPS * C3D_C2;
+
+struct rva_c3d_geom {
+    int T, H1, W1, T2, H2, W2;       // pool1 = (T, H1, W1), pool2 = (T2, H2, W2)
+    int conv1_tiles_x, conv1_tiles, conv2_tiles, conv3_tiles;
+    int64_t elems[4];                // elements of a RVA_CNN3D_STAGE_* per clip
+};
+
+inline rva_c3d_geom rva_c3d_geometry(const rva_cnn3d_desc &d)
+{
+    rva_c3d_geom g{};
+    g.T = d.frames; g.H1 = d.height / 2; g.W1 = d.width / 2;
+    g.T2 = g.T / 2; g.H2 = g.H1 / 2; g.W2 = g.W1 / 2;
+    const int64_t ng = (int64_t)g.T2 * g.H2 * g.W2;
+    g.conv1_tiles_x = rva_ceil_div(g.W1, C3D_PT);
+    g.conv1_tiles = g.conv1_tiles_x * rva_ceil_div(g.H1, C3D_PT);
+    g.conv2_tiles = (int)((ng + C3D_GROUPS - 1) / C3D_GROUPS);
+    g.conv3_tiles = (int)((ng + 255) / 256);
+    g.elems[RVA_CNN3D_STAGE_ACT1] = (int64_t)g.T * g.H1 * g.W1 * C3D_C1;
+    g.elems[RVA_CNN3D_STAGE_ACT2] = ng * C3D_C2;
+    g.elems[RVA_CNN3D_STAGE_PARTIAL] = (int64_t)g.conv3_tiles * C3D_C3;
+    g.elems[RVA_CNN3D_STAGE_FEAT] = C3D_C3;
+    return g;
+}
+
+// the argument checks of a create, under the entry's name; clears *out
+inline int rva_c3d_check_args(rva_ctx *ctx, const char *who, const rva_cnn3d_desc *d, const rva_cnn3d_weights *wt, void **out)
+{
+    if (!ctx || !d || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    // the pools floor: (1,2,2) then (2,2,2) leave nothing of fewer than 2 frames or 4 rows / columns (torch fails there too)
+    if (d->height < 4 || d->width < 4 || d->frames < 2 || d->classes < 1 || d->classes > RVA_PLAN_MAX_CLASSES || d->max_clips < 1 ||
+        (int64_t)d->max_clips * d->frames > 65535 || (int64_t)d->height * d->width > (1 << 26))
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 4, frames >= 2, classes 1..%d, max_clips >= 1, "
+                        "max_clips * frames <= 65535)", who, RVA_PLAN_MAX_CLASSES);
+    if (!wt->conv1_w || !wt->conv1_b || !wt->conv2_w || !wt->conv2_b || !wt->conv3_w || !wt->conv3_b || !wt->head_w || !wt->head_b)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    return RVA_OK;
+}
+
+inline void rva_c3d_info(const rva_c3d_geom &g, int32_t *pool1, int32_t *pool2, int32_t *tiles, int32_t *n_launches)
+{
+    if (pool1) { pool1[0] = g.T; pool1[1] = g.H1; pool1[2] = g.W1; }
+    if (pool2) { pool2[0] = g.T2; pool2[1] = g.H2; pool2[2] = g.W2; }
+    if (tiles) { tiles[0] = g.conv1_tiles; tiles[1] = g.conv2_tiles; tiles[2] = g.conv3_tiles; }
+    if (n_launches) *n_launches = 5;
+}

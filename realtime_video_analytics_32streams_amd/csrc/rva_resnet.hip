@@ -21,14 +21,12 @@
 //   K_post   (rva_resnet_plan_run_post) the top-k kernel of rva_clip.hip with the descriptor's k.
 //
 // Every stage keeps its own workspace buffer (rva_resnet_plan_stage reads them).
-#include "rva_internal.h"
 #include "rva_mfma_f32.h"
+#include "rva_plan_topo.h"
 
 namespace {
 
-constexpr int C_STEM = 64, C_FEAT = 512, N_BLOCKS = 8, N_CONVS = 19;
-constexpr int MAX_CLASSES = 16384;
-constexpr int EPI_RELU = 0, EPI_BIAS = 1, EPI_RES_RELU = 2;
+constexpr int C_FEAT = RES_C_FEAT;
 
 struct ResConvArgs {
     const float *in;                 // [n][H][W][Cin]
@@ -158,13 +156,6 @@ __global__ void __launch_bounds__(C_FEAT) k_res_mean(const float *x, int P, floa
     feat[(size_t)img * C_FEAT + c] = s / (float)P;
 }
 
-struct ResLayer {                    // one block convolution of the plan
-    int cin, cout, k, stride, H, W, Ho, Wo, epi;
-    float *w = nullptr, *b = nullptr;
-    const float *in = nullptr, *res = nullptr;
-    float *out = nullptr;
-};
-
 }  // namespace
 
 int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st)
@@ -178,11 +169,10 @@ struct rva_resnet_plan {
     rva_ctx *ctx = nullptr;
     rva_resnet_desc d{};
     int k = 0;                                             // min(top_k, classes)
-    int maps[5][2] = {};                                   // (h, w) of the pooled map and of the four stages
+    rva_res_topo t{};
     float *ws = nullptr, *bs = nullptr, *wh = nullptr, *bh = nullptr;
-    float *pooled = nullptr, *mid[N_BLOCKS] = {}, *down[N_BLOCKS] = {}, *outb[N_BLOCKS] = {}, *feat = nullptr;
-    ResLayer conv[N_CONVS];                                // in launch order: per block conv1, [shortcut], conv2
-    int n_convs = 0;
+    float *w[RES_CONVS] = {}, *b[RES_CONVS] = {};          // of t.conv[i], in launch order
+    float *stage[RES_STAGES] = {};                         // every stage keeps its own buffer, indexed by RVA_RESNET_STAGE_*
     size_t workspace_bytes = 0;
     rva_dev_arena mem;
 };
@@ -191,87 +181,38 @@ extern "C" {
 
 int rva_resnet_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *wt, rva_resnet_plan **out)
 {
-    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: null argument");
-    *out = nullptr;
+    int rc = rva_res_check_args(ctx, "rva_resnet_plan_create", desc, wt, (void **)out);
+    if (rc != RVA_OK) return rc;
     const rva_resnet_desc d = *desc;
-    if (d.height < 1 || d.width < 1 || d.classes < 1 || d.classes > MAX_CLASSES || d.top_k < 1 || d.max_frames < 1 ||
-        d.max_frames > 65535 || (int64_t)d.height * d.width > (1 << 26))
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, "
-                        "max_frames 1..65535)", MAX_CLASSES);
-    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
-    for (int i = 0; i < N_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
-    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_create: every weight array is required");
+    const rva_res_topo t = rva_res_topology(d.height, d.width);
+    const size_t mf = (size_t)d.max_frames;
+    // sizes first: the workspace must fit before anything is allocated
+    size_t n_act = 0, n_w = (size_t)RES_C_STEM * 147 + RES_C_STEM + (size_t)d.classes * (RES_C_FEAT + 1);
+    for (int64_t e : t.elems) n_act += mf * e;
+    for (const rva_res_conv &c : t.conv) n_w += c.weights() + c.cout;
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
+    rc = rva_plan_fits(ctx, "rva_resnet_plan_create", (n_act + n_w) * sizeof(float), shape);
+    if (rc != RVA_OK) return rc;
     auto *p = new rva_resnet_plan();
     p->ctx = ctx;
     p->d = d;
     p->k = std::min(d.top_k, d.classes);
-    auto half = [](int n, int k, int pad) { return (n + 2 * pad - k) / 2 + 1; };
-    p->maps[0][0] = half(half(d.height, 7, 3), 3, 1);
-    p->maps[0][1] = half(half(d.width, 7, 3), 3, 1);
-    p->maps[1][0] = p->maps[0][0]; p->maps[1][1] = p->maps[0][1];
-    for (int s = 2; s <= 4; ++s) { p->maps[s][0] = half(p->maps[s - 1][0], 3, 1); p->maps[s][1] = half(p->maps[s - 1][1], 3, 1); }
-    const size_t mf = (size_t)d.max_frames;
-    // sizes first: the workspace must fit before anything is allocated
-    size_t n_act = mf * p->maps[0][0] * p->maps[0][1] * C_STEM + mf * C_FEAT, n_w = (size_t)C_STEM * 147 + C_STEM + (size_t)d.classes * (C_FEAT + 1);
-    for (int b = 0; b < N_BLOCKS; ++b) {
-        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c;
-        const size_t px = mf * p->maps[s][0] * p->maps[s][1] * c;
-        n_act += px * (cin != c ? 3 : 2);
-        n_w += (size_t)c * 9 * cin + (size_t)c * 9 * c + 2 * c + (cin != c ? (size_t)c * cin + c : 0);
-    }
+    p->t = t;
     p->workspace_bytes = n_act * sizeof(float);
-    const size_t need = (n_act + n_w) * sizeof(float);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
-        delete p;
-        return rva_fail(ctx, RVA_ERR_CAPACITY, "rva_resnet_plan_create: the workspace for %d frames of %d x %d needs %zu MB, the "
-                        "device has %zu MB free", d.max_frames, d.height, d.width, need >> 20, free_b >> 20);
-    }
-    int rc = RVA_OK;
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    step(p->mem.upload(ctx, &p->ws, wt->stem_w, (size_t)C_STEM * 147));
-    step(p->mem.upload(ctx, &p->bs, wt->stem_b, C_STEM));
-    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * C_FEAT));
+    step(p->mem.upload(ctx, &p->ws, wt->stem_w, (size_t)RES_C_STEM * 147));
+    step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * RES_C_FEAT));
     step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    step(p->mem.alloc(ctx, &p->pooled, mf * p->maps[0][0] * p->maps[0][1] * C_STEM));
-    step(p->mem.alloc(ctx, &p->feat, mf * C_FEAT));
-    const float *x = p->pooled;
-    int wi = 0, hin = p->maps[0][0], win = p->maps[0][1];
-    for (int b = 0; b < N_BLOCKS; ++b) {
-        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c, stride = cin != c ? 2 : 1;
-        const int ho = p->maps[s][0], wo = p->maps[s][1];
-        const size_t px = mf * ho * wo * c;
-        step(p->mem.alloc(ctx, &p->mid[b], px));
-        step(p->mem.alloc(ctx, &p->outb[b], px));
-        if (cin != c) step(p->mem.alloc(ctx, &p->down[b], px));
-        // the ABI's weight order of a block: conv1, conv2, then the shortcut
-        float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *wd = nullptr, *bd = nullptr;
-        step(p->mem.upload(ctx, &w1, wt->conv[wi].w, (size_t)c * 9 * cin));
-        step(p->mem.upload(ctx, &b1, wt->conv[wi].b, c));
-        step(p->mem.upload(ctx, &w2, wt->conv[wi + 1].w, (size_t)c * 9 * c));
-        step(p->mem.upload(ctx, &b2, wt->conv[wi + 1].b, c));
-        wi += 2;
-        if (cin != c) {
-            step(p->mem.upload(ctx, &wd, wt->conv[wi].w, (size_t)c * cin));
-            step(p->mem.upload(ctx, &bd, wt->conv[wi].b, c));
-            ++wi;
-        }
-        ResLayer l1{cin, c, 3, stride, hin, win, ho, wo, EPI_RELU};
-        l1.w = w1; l1.b = b1; l1.in = x; l1.out = p->mid[b];
-        p->conv[p->n_convs++] = l1;
-        if (cin != c) {
-            ResLayer ld{cin, c, 1, 2, hin, win, ho, wo, EPI_BIAS};
-            ld.w = wd; ld.b = bd; ld.in = x; ld.out = p->down[b];
-            p->conv[p->n_convs++] = ld;
-        }
-        ResLayer l2{c, c, 3, 1, ho, wo, ho, wo, EPI_RES_RELU};
-        l2.w = w2; l2.b = b2; l2.in = p->mid[b]; l2.res = cin != c ? p->down[b] : x; l2.out = p->outb[b];
-        p->conv[p->n_convs++] = l2;
-        x = p->outb[b];
-        hin = ho; win = wo;
+    for (int s = 0; s < RES_STAGES; ++s) step(p->mem.alloc(ctx, &p->stage[s], mf * t.elems[s]));
+    for (int i = 0; i < RES_CONVS; ++i) {                  // in the ABI's weight order
+        const int n = t.launch_of[i];
+        step(p->mem.upload(ctx, &p->w[n], wt->conv[i].w, t.conv[n].weights()));
+        step(p->mem.upload(ctx, &p->b[n], wt->conv[i].b, t.conv[n].cout));
     }
     if (rc == RVA_OK) rc = rva_clip_stem_prepare(ctx);
-    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, C_FEAT);
+    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, RES_C_FEAT);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
         rva_resnet_plan_destroy(p);
@@ -291,10 +232,7 @@ void rva_resnet_plan_destroy(rva_resnet_plan *p)
 int rva_resnet_plan_info(const rva_resnet_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
 {
     if (!p) return RVA_ERR_ARG;
-    if (maps)
-        for (int s = 0; s < 5; ++s) { maps[2 * s] = p->maps[s][0]; maps[2 * s + 1] = p->maps[s][1]; }
-    if (workspace_bytes) *workspace_bytes = (int64_t)p->workspace_bytes;
-    if (n_launches) *n_launches = 1 + N_CONVS + 2;
+    rva_res_info(p->t, p->workspace_bytes, maps, workspace_bytes, n_launches);
     return RVA_OK;
 }
 
@@ -305,13 +243,15 @@ int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *f
     if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
     const hipStream_t st = (hipStream_t)stream_;
-    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->ws, p->bs, p->pooled, p->d.height, p->d.width, n, st);
+    float *const *buf = p->stage;
+    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->ws, p->bs, buf[RVA_RESNET_STAGE_POOLED], p->d.height,
+                                  p->d.width, n, st);
     if (rc != RVA_OK) return rc;
     const int cus = rva_num_cus(ctx);
-    for (int i = 0; i < p->n_convs; ++i) {
-        const ResLayer &l = p->conv[i];
+    for (int i = 0; i < RES_CONVS; ++i) {
+        const rva_res_conv &l = p->t.conv[i];
         ResConvArgs a{};
-        a.in = l.in; a.w = l.w; a.bias = l.b; a.res = l.res; a.out = l.out;
+        a.in = buf[l.in]; a.w = p->w[i]; a.bias = p->b[i]; a.res = l.res >= 0 ? buf[l.res] : nullptr; a.out = buf[l.out];
         a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
         a.M = (long)n * l.Ho * l.Wo;
         const int v = res_tile_for(a.M, l.cout, cus);
@@ -320,9 +260,9 @@ int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *f
         else launch_res_conv<1>(v, g, st, a);
         RVA_HIP(ctx, hipGetLastError());
     }
-    rc = rva_res_mean_launch(ctx, p->outb[N_BLOCKS - 1], p->maps[4][0] * p->maps[4][1], p->feat, n, st);
+    rc = rva_res_mean_launch(ctx, buf[RVA_RESNET_STAGE_OUT0 + RES_BLOCKS - 1], p->t.maps[4][0] * p->t.maps[4][1], buf[RVA_RESNET_STAGE_FEAT], n, st);
     if (rc != RVA_OK) return rc;
-    return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C_FEAT, p->d.classes, n, st);
+    return rva_clip_head_launch(ctx, buf[RVA_RESNET_STAGE_FEAT], p->wh, p->bh, (float *)logits, RES_C_FEAT, p->d.classes, n, st);
 }
 
 int rva_resnet_plan_run_post(rva_resnet_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
@@ -333,27 +273,17 @@ int rva_resnet_plan_run_post(rva_resnet_plan *p, const void *logits, const int32
                                 (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 
-// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is frame-major NHWC.
+// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is frame-major NHWC.  (The
+// size error counts "clips": this entry's text since it shared the clip plans' tap.)
 int rva_resnet_plan_stage(rva_resnet_plan *p, int stage, int n, void *dst, int64_t dst_floats, int64_t *n_floats, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
     rva_ctx *ctx = p->ctx;
     if (n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
-    const float *src = nullptr;
-    int64_t count = 0;
-    auto block = [&](float *const *bufs, int b) {
-        const int s = 1 + b / 2;
-        src = bufs[b];
-        count = (int64_t)n * p->maps[s][0] * p->maps[s][1] * (C_STEM << (s - 1));
-    };
-    if (stage == RVA_RESNET_STAGE_POOLED) { src = p->pooled; count = (int64_t)n * p->maps[0][0] * p->maps[0][1] * C_STEM; }
-    else if (stage >= RVA_RESNET_STAGE_MID0 && stage < RVA_RESNET_STAGE_MID0 + N_BLOCKS) block(p->mid, stage - RVA_RESNET_STAGE_MID0);
-    else if (stage >= RVA_RESNET_STAGE_DOWN2 && stage <= RVA_RESNET_STAGE_DOWN6) block(p->down, 2 * (stage - RVA_RESNET_STAGE_DOWN2) + 2);
-    else if (stage >= RVA_RESNET_STAGE_OUT0 && stage < RVA_RESNET_STAGE_OUT0 + N_BLOCKS) block(p->outb, stage - RVA_RESNET_STAGE_OUT0);
-    else if (stage == RVA_RESNET_STAGE_FEAT) { src = p->feat; count = (int64_t)n * C_FEAT; }
-    else return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: unknown stage %d", stage);
-    return rva_clip_stage_copy(ctx, "rva_resnet_plan_stage", stage, n, src, count, 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
+    if (stage < 0 || stage >= RES_STAGES) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: unknown stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_resnet_plan_stage", stage, n, "clips", p->stage[stage], sizeof(float), "floats",
+                               n * p->t.elems[stage], 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -35,16 +35,10 @@
 //   K_mean / K_head / K_post: k_res_mean (rva_resnet.hip) and the head and top-k kernels of rva_clip.hip, unchanged.
 //
 // Every stage keeps its own workspace buffer (rva_resnet_f16_plan_stage reads them).
-#include "rva_internal.h"
 #include "rva_mfma_f16.h"
-
-#include <cmath>
+#include "rva_plan_topo.h"
 
 namespace {
-
-constexpr int C_STEM = 64, C_FEAT = 512, N_BLOCKS = 8, N_CONVS = 19;
-constexpr int MAX_CLASSES = 16384;
-constexpr int EPI_RELU = 0, EPI_BIAS = 1, EPI_RES_RELU = 2;
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -242,13 +236,9 @@ void launch_res16_conv(int v, dim3 g, hipStream_t st, const Res16Args &a)
 #undef RES16_LAUNCH
 }
 
-struct Res16Layer {                  // one block convolution of the plan
-    int cin, cout, k, stride, H, W, Ho, Wo, epi, out_f32;
-    _Float16 *w = nullptr;
-    float *b = nullptr;
-    const _Float16 *in = nullptr, *res = nullptr;
-    void *out = nullptr;
-};
+// every stage is stored as fp16 but out7 (it feeds only the mean) and feat
+constexpr int STAGE_OUT7 = RVA_RESNET_STAGE_OUT0 + RES_BLOCKS - 1;
+size_t res16_esize(int stage) { return stage == STAGE_OUT7 || stage == RVA_RESNET_STAGE_FEAT ? sizeof(float) : sizeof(_Float16); }
 
 }  // namespace
 
@@ -256,132 +246,67 @@ struct rva_resnet_f16_plan {
     rva_ctx *ctx = nullptr;
     rva_resnet_desc d{};
     int k = 0;                                             // min(top_k, classes)
-    int maps[5][2] = {};                                   // (h, w) of the pooled map and of the four stages
+    rva_res_topo t{};
     int tile_force = -1;                                   // RVA_RES16_TILE at creation: every launch takes this tile (tests, tools)
-    _Float16 *ws = nullptr, *pooled = nullptr, *mid[N_BLOCKS] = {}, *down[N_BLOCKS] = {}, *outb[N_BLOCKS] = {};
-    float *bs = nullptr, *wh = nullptr, *bh = nullptr, *out7 = nullptr, *feat = nullptr;
-    Res16Layer conv[N_CONVS];                              // in launch order: per block conv1, [shortcut], conv2
-    int n_convs = 0;
+    _Float16 *ws = nullptr, *w[RES_CONVS] = {};            // w, b: of t.conv[i], in launch order
+    float *bs = nullptr, *wh = nullptr, *bh = nullptr, *b[RES_CONVS] = {};
+    void *stage[RES_STAGES] = {};                          // every stage keeps its own buffer, indexed by RVA_RESNET_STAGE_*
     size_t workspace_bytes = 0;
     rva_dev_arena mem;
-
-    // the arena hands out floats: n fp16 elements take (n + 1) / 2 of them
-    int alloc_h(_Float16 **dst, size_t n) { return mem.alloc(ctx, reinterpret_cast<float **>(dst), (n + 1) / 2); }
-    int upload_h(_Float16 **dst, const std::vector<_Float16> &src)
-    {
-        const int rc = alloc_h(dst, src.size());
-        if (rc != RVA_OK) return rc;
-        RVA_HIP(ctx, hipMemcpy(*dst, src.data(), src.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-        return RVA_OK;
-    }
 };
 
 extern "C" {
 
 int rva_resnet_f16_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *wt, rva_resnet_f16_plan **out)
 {
-    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_create: null argument");
-    *out = nullptr;
+    int rc = rva_res_check_args(ctx, "rva_resnet_f16_plan_create", desc, wt, (void **)out);
+    if (rc != RVA_OK) return rc;
     const rva_resnet_desc d = *desc;
-    if (d.height < 1 || d.width < 1 || d.classes < 1 || d.classes > MAX_CLASSES || d.top_k < 1 || d.max_frames < 1 ||
-        d.max_frames > 65535 || (int64_t)d.height * d.width > (1 << 26))
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_create: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, "
-                        "max_frames 1..65535)", MAX_CLASSES);
-    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
-    for (int i = 0; i < N_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
-    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_create: every weight array is required");
+    const rva_res_topo t = rva_res_topology(d.height, d.width);
+    const size_t mf = (size_t)d.max_frames;
+    // sizes first: the workspace must fit before anything is allocated
+    size_t act_bytes = 0;
+    size_t w_bytes = (size_t)RES_C_STEM * 192 * sizeof(_Float16) + RES_C_STEM * sizeof(float) + (size_t)d.classes * (RES_C_FEAT + 1) * sizeof(float);
+    for (int s = 0; s < RES_STAGES; ++s) act_bytes += mf * t.elems[s] * res16_esize(s);
+    for (const rva_res_conv &c : t.conv) w_bytes += c.weights() * sizeof(_Float16) + c.cout * sizeof(float);
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
+    rc = rva_plan_fits(ctx, "rva_resnet_f16_plan_create", act_bytes + w_bytes, shape);
+    if (rc != RVA_OK) return rc;
     auto *p = new rva_resnet_f16_plan();
     p->ctx = ctx;
     p->d = d;
     p->k = std::min(d.top_k, d.classes);
-    if (const char *e = getenv("RVA_RES16_TILE")) p->tile_force = std::max(-1, std::min(atoi(e), kNumTiles - 1));
-    auto half = [](int n, int k, int pad) { return (n + 2 * pad - k) / 2 + 1; };
-    p->maps[0][0] = half(half(d.height, 7, 3), 3, 1);
-    p->maps[0][1] = half(half(d.width, 7, 3), 3, 1);
-    p->maps[1][0] = p->maps[0][0]; p->maps[1][1] = p->maps[0][1];
-    for (int s = 2; s <= 4; ++s) { p->maps[s][0] = half(p->maps[s - 1][0], 3, 1); p->maps[s][1] = half(p->maps[s - 1][1], 3, 1); }
-    const size_t mf = (size_t)d.max_frames;
-    // sizes first: the workspace must fit before anything is allocated.  fp16 everywhere but out7 and feat.
-    size_t act_bytes = mf * p->maps[0][0] * p->maps[0][1] * C_STEM * sizeof(_Float16) + mf * C_FEAT * sizeof(float);
-    size_t w_bytes = (size_t)C_STEM * 192 * sizeof(_Float16) + C_STEM * sizeof(float) + (size_t)d.classes * (C_FEAT + 1) * sizeof(float);
-    for (int b = 0; b < N_BLOCKS; ++b) {
-        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c;
-        const size_t px = mf * p->maps[s][0] * p->maps[s][1] * c;
-        act_bytes += px * (cin != c ? 2 : 1) * sizeof(_Float16) + px * (b == N_BLOCKS - 1 ? sizeof(float) : sizeof(_Float16));
-        w_bytes += ((size_t)c * 9 * cin + (size_t)c * 9 * c + (cin != c ? (size_t)c * cin : 0)) * sizeof(_Float16) +
-                   (size_t)(cin != c ? 3 : 2) * c * sizeof(float);
-    }
+    p->t = t;
     p->workspace_bytes = act_bytes;
-    const size_t need = act_bytes + w_bytes;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || need > free_b) {
-        delete p;
-        return rva_fail(ctx, RVA_ERR_CAPACITY, "rva_resnet_f16_plan_create: the workspace for %d frames of %d x %d needs %zu MB, the "
-                        "device has %zu MB free", d.max_frames, d.height, d.width, need >> 20, free_b >> 20);
-    }
-    int rc = RVA_OK;
+    if (const char *e = getenv("RVA_RES16_TILE")) p->tile_force = std::max(-1, std::min(atoi(e), kNumTiles - 1));
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
     std::vector<_Float16> w16;
     char bad[24] = "";
-    // rounds one array and uploads it as it is ([Cout][k*k][Cin] is what the kernel reads); names the array that fails
-    auto upload_w = [&](_Float16 **dst, const float *src, size_t n, const char *name, int idx) {
-        if (rc != RVA_OK) return;
-        if (!rva_round_f16(src, n, w16)) {
-            if (idx >= 0) snprintf(bad, sizeof bad, "conv[%d].w", idx);
-            else snprintf(bad, sizeof bad, "%s", name);
-            rc = RVA_ERR_ARG;
-            return;
-        }
-        rc = p->upload_h(dst, w16);
-    };
-    if (!rva_round_f16(wt->stem_w, (size_t)C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
-    else step(p->upload_h(&p->ws, rva_clip16_stem_pack(w16)));
-    step(p->mem.upload(ctx, &p->bs, wt->stem_b, C_STEM));
-    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * C_FEAT));
+    if (!rva_round_f16(wt->stem_w, (size_t)RES_C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
+    else { w16 = rva_clip16_stem_pack(w16); step(p->mem.upload(ctx, &p->ws, w16.data(), w16.size())); }
+    step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * RES_C_FEAT));
     step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    step(p->alloc_h(&p->pooled, mf * p->maps[0][0] * p->maps[0][1] * C_STEM));
-    step(p->mem.alloc(ctx, &p->feat, mf * C_FEAT));
-    const _Float16 *x = p->pooled;
-    int wi = 0, hin = p->maps[0][0], win = p->maps[0][1];
-    for (int b = 0; b < N_BLOCKS; ++b) {
-        const int s = 1 + b / 2, c = C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c, stride = cin != c ? 2 : 1;
-        const int ho = p->maps[s][0], wo = p->maps[s][1];
-        const size_t px = mf * ho * wo * c;
-        const bool last = b == N_BLOCKS - 1;
-        step(p->alloc_h(&p->mid[b], px));
-        if (last) step(p->mem.alloc(ctx, &p->out7, px));
-        else step(p->alloc_h(&p->outb[b], px));
-        if (cin != c) step(p->alloc_h(&p->down[b], px));
-        // the ABI's weight order of a block: conv1, conv2, then the shortcut
-        _Float16 *w1 = nullptr, *w2 = nullptr, *wd = nullptr;
-        float *b1 = nullptr, *b2 = nullptr, *bd = nullptr;
-        upload_w(&w1, wt->conv[wi].w, (size_t)c * 9 * cin, nullptr, wi);
-        step(p->mem.upload(ctx, &b1, wt->conv[wi].b, c));
-        upload_w(&w2, wt->conv[wi + 1].w, (size_t)c * 9 * c, nullptr, wi + 1);
-        step(p->mem.upload(ctx, &b2, wt->conv[wi + 1].b, c));
-        wi += 2;
-        if (cin != c) {
-            upload_w(&wd, wt->conv[wi].w, (size_t)c * cin, nullptr, wi);
-            step(p->mem.upload(ctx, &bd, wt->conv[wi].b, c));
-            ++wi;
+    for (int s = 0; s < RES_STAGES; ++s) {
+        char *m = nullptr;
+        step(p->mem.alloc(ctx, &m, mf * t.elems[s] * res16_esize(s)));
+        p->stage[s] = m;
+    }
+    // in the ABI's weight order: rounds an array and uploads it as it is ([Cout][k*k][Cin] is what the kernel reads); names the
+    // first array that fails
+    for (int i = 0; i < RES_CONVS && rc == RVA_OK; ++i) {
+        const int n = t.launch_of[i];
+        if (!rva_round_f16(wt->conv[i].w, t.conv[n].weights(), w16)) {
+            snprintf(bad, sizeof bad, "conv[%d].w", i);
+            rc = RVA_ERR_ARG;
+            break;
         }
-        Res16Layer l1{cin, c, 3, stride, hin, win, ho, wo, EPI_RELU, 0};
-        l1.w = w1; l1.b = b1; l1.in = x; l1.out = p->mid[b];
-        p->conv[p->n_convs++] = l1;
-        if (cin != c) {
-            Res16Layer ld{cin, c, 1, 2, hin, win, ho, wo, EPI_BIAS, 0};
-            ld.w = wd; ld.b = bd; ld.in = x; ld.out = p->down[b];
-            p->conv[p->n_convs++] = ld;
-        }
-        Res16Layer l2{c, c, 3, 1, ho, wo, ho, wo, EPI_RES_RELU, last ? 1 : 0};
-        l2.w = w2; l2.b = b2; l2.in = p->mid[b]; l2.res = cin != c ? p->down[b] : x;
-        l2.out = last ? (void *)p->out7 : (void *)p->outb[b];
-        p->conv[p->n_convs++] = l2;
-        x = p->outb[b];
-        hin = ho; win = wo;
+        step(p->mem.upload(ctx, &p->w[n], w16.data(), w16.size()));
+        step(p->mem.upload(ctx, &p->b[n], wt->conv[i].b, t.conv[n].cout));
     }
     if (rc == RVA_OK) rc = rva_clip16_stem_prepare(ctx);
-    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, C_FEAT);
+    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, RES_C_FEAT);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
         rva_resnet_f16_plan_destroy(p);
@@ -402,10 +327,7 @@ void rva_resnet_f16_plan_destroy(rva_resnet_f16_plan *p)
 int rva_resnet_f16_plan_info(const rva_resnet_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
 {
     if (!p) return RVA_ERR_ARG;
-    if (maps)
-        for (int s = 0; s < 5; ++s) { maps[2 * s] = p->maps[s][0]; maps[2 * s + 1] = p->maps[s][1]; }
-    if (workspace_bytes) *workspace_bytes = (int64_t)p->workspace_bytes;
-    if (n_launches) *n_launches = 1 + N_CONVS + 2;
+    rva_res_info(p->t, p->workspace_bytes, maps, workspace_bytes, n_launches);
     return RVA_OK;
 }
 
@@ -416,15 +338,18 @@ int rva_resnet_f16_plan_run(rva_resnet_f16_plan *p, const void *frames, const in
     if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
     const hipStream_t st = (hipStream_t)stream_;
-    int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->ws, p->bs, p->pooled, p->d.height, p->d.width, n, st);
+    void *const *buf = p->stage;
+    int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->ws, p->bs, (_Float16 *)buf[RVA_RESNET_STAGE_POOLED],
+                                    p->d.height, p->d.width, n, st);
     if (rc != RVA_OK) return rc;
     const int cus = rva_num_cus(ctx);
-    for (int i = 0; i < p->n_convs; ++i) {
-        const Res16Layer &l = p->conv[i];
+    for (int i = 0; i < RES_CONVS; ++i) {
+        const rva_res_conv &l = p->t.conv[i];
         Res16Args a{};
-        a.in = l.in; a.w = l.w; a.bias = l.b; a.res = l.res; a.out = l.out;
+        a.in = (const _Float16 *)buf[l.in]; a.w = p->w[i]; a.bias = p->b[i]; a.out = buf[l.out];
+        a.res = l.res >= 0 ? (const _Float16 *)buf[l.res] : nullptr;
         a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
-        a.out_f32 = l.out_f32;
+        a.out_f32 = l.out == STAGE_OUT7;
         a.M = (long)n * l.Ho * l.Wo;
         const int v = p->tile_force >= 0 ? p->tile_force : res16_tile_for(a.M, l.cout, cus);
         const dim3 g = res16_grid(v, a.M, l.cout);
@@ -432,9 +357,10 @@ int rva_resnet_f16_plan_run(rva_resnet_f16_plan *p, const void *frames, const in
         else launch_res16_conv<1>(v, g, st, a);
         RVA_HIP(ctx, hipGetLastError());
     }
-    rc = rva_res_mean_launch(ctx, p->out7, p->maps[4][0] * p->maps[4][1], p->feat, n, st);
+    float *feat = (float *)buf[RVA_RESNET_STAGE_FEAT];
+    rc = rva_res_mean_launch(ctx, (const float *)buf[STAGE_OUT7], p->t.maps[4][0] * p->t.maps[4][1], feat, n, st);
     if (rc != RVA_OK) return rc;
-    return rva_clip_head_launch(ctx, p->feat, p->wh, p->bh, (float *)logits, C_FEAT, p->d.classes, n, st);
+    return rva_clip_head_launch(ctx, feat, p->wh, p->bh, (float *)logits, RES_C_FEAT, p->d.classes, n, st);
 }
 
 int rva_resnet_f16_plan_run_post(rva_resnet_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
@@ -453,30 +379,9 @@ int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *p, int stage, int n, void *ds
     rva_ctx *ctx = p->ctx;
     if (n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
-    const void *src = nullptr;
-    int64_t count = 0;
-    size_t elem = sizeof(_Float16);
-    auto block = [&](_Float16 *const *bufs, int b) {
-        const int s = 1 + b / 2;
-        src = bufs[b];
-        count = (int64_t)n * p->maps[s][0] * p->maps[s][1] * (C_STEM << (s - 1));
-    };
-    if (stage == RVA_RESNET_STAGE_POOLED) { src = p->pooled; count = (int64_t)n * p->maps[0][0] * p->maps[0][1] * C_STEM; }
-    else if (stage >= RVA_RESNET_STAGE_MID0 && stage < RVA_RESNET_STAGE_MID0 + N_BLOCKS) block(p->mid, stage - RVA_RESNET_STAGE_MID0);
-    else if (stage >= RVA_RESNET_STAGE_DOWN2 && stage <= RVA_RESNET_STAGE_DOWN6) block(p->down, 2 * (stage - RVA_RESNET_STAGE_DOWN2) + 2);
-    else if (stage >= RVA_RESNET_STAGE_OUT0 && stage < RVA_RESNET_STAGE_OUT0 + N_BLOCKS) {
-        block(p->outb, stage - RVA_RESNET_STAGE_OUT0);
-        if (stage == RVA_RESNET_STAGE_OUT0 + N_BLOCKS - 1) { src = p->out7; elem = sizeof(float); }
-    }
-    else if (stage == RVA_RESNET_STAGE_FEAT) { src = p->feat; count = (int64_t)n * C_FEAT; elem = sizeof(float); }
-    else return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: unknown stage %d", stage);
-    if (n_elems) *n_elems = count;
-    if (!dst) return RVA_OK;
-    if (dst_elems < count)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: dst holds %lld elements, stage %d of %d frames has %lld",
-                        (long long)dst_elems, stage, n, (long long)count);
-    RVA_HIP(ctx, hipMemcpyAsync(dst, src, (size_t)count * elem, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
-    return RVA_OK;
+    if (stage < 0 || stage >= RES_STAGES) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: unknown stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_resnet_f16_plan_stage", stage, n, "frames", p->stage[stage], res16_esize(stage), "elements",
+                               n * p->t.elems[stage], 0, 0, 0, dst, dst_elems, n_elems, (hipStream_t)stream_);
 }
 
 }  // extern "C"
