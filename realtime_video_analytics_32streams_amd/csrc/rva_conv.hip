@@ -24,6 +24,15 @@
 //   k_stem         3x3 stride-2 conv on the planar fp16 tensor K1 writes (Cin = 3), bias + SiLU, NHWC out
 //   k_sppf_pool3 / k_maxpool5 / k_upsample2 / k_head3 / k_head   SPPF pooling, FPN upsample, DFL + dist2bbox + sigmoid
 //
+// Shared around the K loops (the families differ in how they stage operands and walk K, nothing else):
+//   stage_tile / store_tile   the epilogue of the eight tile kernels above k_conv3_patch (bias, SiLU, fp16, LDS transpose; row ->
+//                             pixel mapping as a closure, residual at the mapped pixel, Cout tested per 8-channel group)
+//   ldsdma_tile / ldsdma_acc_bias / ldsdma_woff   tile decode (XCD order, padded grid), accumulator zero + early bias fetch and
+//                             the weight-piece offsets of the five LDS-DMA kernels
+//   launch_ldsdma             their launches: the 2^24 raster / 2^32 byte-offset refusals, tile counts, padded grid
+// k_conv3_patch, k_c2f_pair32 and k_conv3_patch2 keep their own epilogues: their stage rows are (tile row, x) and their stores walk
+// a 2-D tile with a run-time channel count.
+//
 // Numerics: fp16 operands, fp32 accumulation and epilogue, one rounding to fp16 per layer output
 // (PyTorch rounds after conv, after bias and after SiLU); the engine is therefore checked against the
 // torch module within an fp16 tolerance, never bit-for-bit.
@@ -114,6 +123,83 @@ __device__ __forceinline__ int div_s(int q, int d, float inv)
 // x * sigmoid(x) with v_exp_f32 + v_rcp_f32 (1 ulp): __fdividef / operator/ expand to the ~12-instruction IEEE
 // division sequence here, which dominated the epilogues (64-128 SiLUs per thread per tile)
 __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+
+// ---------------------------------------------------------------------------------------------------
+// The epilogue the eight tile kernels share (k_conv_mfma, k_conv3_row, k_conv_res; k_conv3_big / _run / _s2run / _chunk,
+// k_conv_gbig): accumulators -> stage[BM][BN + 8] at the start of LDS, over the dead operand buffers (stage_tile) ->
+// __syncthreads() at the call site -> 16-byte stores (store_tile).
+//
+// Both take the kernel's argument struct itself (ConvArgs / RowArgs / ResArgs / BigArgs / RunArgs: act, out, ldo, res, ldr,
+// Cout) and read the fields where the hand-written copies read them.  Tried and not kept: the fields as values read before
+// the call (the kernel-argument loads are then scheduled differently through the whole kernel) and closures that hold the
+// struct's address (the loads are no longer merged into wide scalar loads).
+
+// The lane's bias of fragment i: from the prefetched fragments, or from the n-tile's bias vector, loaded where it is used
+template <int FN> __device__ __forceinline__ float4 bias_frag(const float4 (&bvs)[FN], int i, int) { return bvs[i]; }
+__device__ __forceinline__ float4 bias_frag(const float *bias, int i, int lane) { return *reinterpret_cast<const float4 *>(bias + (16 * i + (lane >> 4) * 4)); }
+
+// stage_tile: + bias, SiLU (a.act), one rounding to fp16, transposed into the stage.  The wave owns fragments [FN][FM] of a
+// TM x TN sub-tile at pixel wm * TM, channel wn * TN (the 256-thread kernels: one wave column, wm = wave, wn = 0).  `bias` is
+// the lane's four channels of every fragment (bvs[FN]: the LDS-DMA kernels fetch them before their first DMA, ldsdma_acc_bias)
+// or the n-tile's bias vector (a.bias + n0: the 256-thread kernels load it here).
+template <int BN, int TM, int TN, int FM, int FN, class A, class Bias>
+__device__ __forceinline__ void stage_tile(const f4 (&acc)[FN][FM], const A &a, const Bias &bias, int wm, int wn, int lane)
+{
+    constexpr int SROW = BN + 8;                          // halfs per staged pixel row
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __half *stage = (__half *)smem;                       // [BM][SROW], reuses the operand buffers
+#pragma unroll
+    for (int i = 0; i < FN; ++i) {
+        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
+        const float4 bv = bias_frag(bias, i, lane);
+#pragma unroll
+        for (int j = 0; j < FM; ++j) {
+            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
+            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
+            const int px = wm * TM + 16 * j + (lane & 15);
+            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
+            uint2 pk;
+            pk.x = *reinterpret_cast<uint32_t *>(&lo);
+            pk.y = *reinterpret_cast<uint32_t *>(&hi);
+            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
+        }
+    }
+}
+
+// store_tile: the NT threads of the block walk the staged tile in 16-byte groups of 8 channels.  map(row, m) sets m, the
+// pixel index of tile row `row` in the output raster, and returns whether the row is stored -- it is what differs between
+// the families (P0 + row; rowmap[row] of the padded rasters; the row window of k_conv_gbig).  The two rules of the loop:
+//   * the residual (fp32 add, one more rounding) is read at the MAPPED pixel m, like the output;
+//   * co < Cout is tested per 8-channel group: the last n-tile stores the groups that exist, never a partial one.
+// The closures capture by value: one over mutable kernel state goes to scratch memory (see k_conv3_big), and one that holds the
+// address of the argument struct keeps the kernel-argument loads from being merged.
+template <int BM, int BN, int NT, class A, class Map>
+__device__ __forceinline__ void store_tile(const A &a, int n0, int tid, Map map)
+{
+    constexpr int SROW = BN + 8, CPR = BN / 8;            // CPR: 16-byte chunks per pixel row
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const __half *stage = (const __half *)smem;
+#pragma unroll 4
+    for (int q = tid; q < BM * CPR; q += NT) {
+        const int row = q / CPR, pc = q - row * CPR;
+        const int co = n0 + pc * 8;
+        size_t m;
+        if (map(row, m) && co < a.Cout) {
+            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
+            if (a.res) {
+                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + m * a.ldr + co);
+                __half2 *vh = reinterpret_cast<__half2 *>(&v);
+                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
+                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
+                }
+            }
+            *reinterpret_cast<uint4 *>(a.out + m * a.ldo + co) = v;
+        }
+    }
+}
 
 template <int BN, int WPX, int KS, int BK>
 __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a)
@@ -235,45 +321,10 @@ __global__ void __launch_bounds__(256) k_conv_mfma(ConvArgs a)
     }
 
     // epilogue: bias + SiLU in fp32, transpose through LDS, full-vector stores (+ residual)
-    constexpr int SROW = BN + 8;                          // halfs per staged pixel row
-    __half *stage = (__half *)smem;                       // [BM][SROW], reuses the operand buffers
-#pragma unroll
-    for (int i = 0; i < BN / 16; ++i) {
-        const int co = 16 * i + (lane >> 4) * 4;
-        const float4 bv = *reinterpret_cast<const float4 *>(a.bias + n0 + co);
-#pragma unroll
-        for (int j = 0; j < WPX / 16; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wv * WPX + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, WPX, BN>(acc, a, a.bias + n0, wv, 0, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;                           // 16-byte chunks per pixel row
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 256) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int m = m0 + row, co = n0 + pc * 8;
-        if (m < a.M && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const float2 x = __half22float2(vh[t]), y = __half22float2(rh[t]);
-                    vh[t] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+    const int M = a.M;
+    store_tile<BM, BN, 256>(a, n0, tid, [=](int row, size_t &m) { const int mi = m0 + row; m = (size_t)mi; return mi < M; });
 }
 
 template <int BN, int WPX, int KS, int BK>
@@ -446,47 +497,10 @@ __global__ void __launch_bounds__(256) k_conv3_row(RowArgs a)
         }
     }
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;
-#pragma unroll
-    for (int i = 0; i < BN / 16; ++i) {
-        const int co = 16 * i + (lane >> 4) * 4;
-        const float4 bv = *reinterpret_cast<const float4 *>(a.bias + n0 + co);
-#pragma unroll
-        for (int j = 0; j < WPX / 16; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wv * WPX + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, WPX, BN>(acc, a, a.bias + n0, wv, 0, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;
     const size_t mbase = (size_t)b * HW + p0;
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 256) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
-        if (p0 + row < HW && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            const size_t m = mbase + row;
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + m * a.ldo + co) = v;
-        }
-    }
+    store_tile<BM, BN, 256>(a, n0, tid, [=](int row, size_t &m) { m = mbase + row; return p0 + row < HW; });
     STAMP(6);
 }
 
@@ -668,49 +682,15 @@ __global__ void __launch_bounds__(256, 1) k_conv_res(ResArgs a)
         __syncthreads();                                   // every wave is done reading this item's operands
         if (cc == cpt - 1 && !RVA_DBG(a, 4)) {
             // ---- epilogue of the tile: bias + SiLU, transpose through LDS, vector stores (+ residual)
-            constexpr int SROW = BN + 8;
-            __half *stage = (__half *)smem;
+            stage_tile<BN, WPX, BN>(acc, a, a.bias + T.n0, wv, 0, lane);
 #pragma unroll
-            for (int i = 0; i < BN / 16; ++i) {
-                const int co = 16 * i + (lane >> 4) * 4;
-                const float4 bv = *reinterpret_cast<const float4 *>(a.bias + T.n0 + co);
+            for (int i = 0; i < BN / 16; ++i)
 #pragma unroll
-                for (int j = 0; j < WPX / 16; ++j) {
-                    float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-                    if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-                    acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-                    const int px = wv * WPX + 16 * j + (lane & 15);
-                    __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-                    uint2 pk;
-                    pk.x = *reinterpret_cast<uint32_t *>(&lo);
-                    pk.y = *reinterpret_cast<uint32_t *>(&hi);
-                    *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-                }
-            }
+                for (int j = 0; j < WPX / 16; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};      // for the block's next tile
             __syncthreads();
-            constexpr int CPR = BN / 8;
             const size_t mbase = KS == 3 ? (size_t)T.b * HW + T.p0 : (size_t)T.p0;
             const int valid = KS == 3 ? min(BM, HW - T.p0) : min(BM, a.M - T.p0);
-#pragma unroll 4
-            for (int q = tid; q < BM * CPR; q += 256) {
-                const int row = q / CPR, pc = q - row * CPR;
-                const int co = T.n0 + pc * 8;
-                if (row < valid && co < a.Cout) {
-                    uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-                    const size_t m = mbase + row;
-                    if (a.res) {
-                        const uint4 r = *reinterpret_cast<const uint4 *>(a.res + m * a.ldr + co);
-                        __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                        const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                            vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                        }
-                    }
-                    *reinterpret_cast<uint4 *>(a.out + m * a.ldo + co) = v;
-                }
-            }
+            store_tile<BM, BN, 256>(a, T.n0, tid, [=](int row, size_t &m) { m = mbase + row; return row < valid; });
             // staging area free again once every wave's LDS reads are done; the global stores stay in flight
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
@@ -1251,6 +1231,66 @@ __device__ __forceinline__ void wait_vm_n(int n)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// What the five LDS-DMA tile kernels (k_conv3_big / _run / _s2run / _chunk, k_conv_gbig: 512 threads, eight waves as
+// WGM x WGN sub-tiles of TM x TN) share around their K loops; the epilogue is stage_tile + store_tile.
+//
+// XCD-aware tile order: workgroups id and id + 8 land on the same XCD (round-robin dispatch; speed only, never
+// correctness), so the n-tiles of one m-tile -- which stage the same activation rows -- are given ids 8 apart: they
+// share that XCD's L2 instead of pulling the rows across the fabric once per n-tile.  Identity when n_tiles == 1.
+// The grid is padded to a multiple of 8 m-tiles (launch_ldsdma): false = this block is padding and returns at once.
+template <class A>
+__device__ __forceinline__ bool ldsdma_tile(const A &a, int &n_tile, int &m_tile)
+{
+    n_tile = (blockIdx.x >> 3) % a.n_tiles;
+    m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);
+    return m_tile < a.m_tiles;
+}
+
+// Zeroed accumulators and the bias of the epilogue (c0 = first channel of the wave's sub-tile), fetched BEFORE the first
+// LDS-DMA (so the counted vmcnt waits never include it) and long before its use: a dependent global load at the top of
+// the epilogue costs ~1.5 k cycles per block
+template <int FM, int FN, class A>
+__device__ __forceinline__ void ldsdma_acc_bias(f4 (&acc)[FN][FM], float4 (&bvs)[FN], const A &a, int c0, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < FN; ++i)
+#pragma unroll
+        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < FN; ++i) bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(c0 + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
+}
+
+// Per-lane byte offset, relative to a.w, of row rw = t * BN + (channel - n0) of a staged [taps][BN] weight image of a 3x3
+// kernel (64-byte rows, 16 per piece; lp = the lane's 16-byte chunk): the channel clamped into the padded tensor, tap `tap`,
+// chunk 0, + the inverse of swz32's rotation.  t is rw / BN; tap is t, or a clamp of it where a wave's last piece reaches
+// past the image (those rows are never issued).
+template <int BN, class A>
+__device__ __forceinline__ unsigned ldsdma_woff(const A &a, int n0, int rw, int t, int tap, int lp)
+{
+    const int co = min(n0 + rw - t * BN, a.CoutPad - 1);
+    return (unsigned)(co * (9 * a.Cin) + tap * a.Cin) * 2u + (unsigned)(((lp - 2 * (rw >> 2)) & 3) * 16);
+}
+
+// Host side: the refusals the five launches share, the tile counts and the padded grid of 512-thread blocks.
+//   raster        positions of the raster the kernel walks in tiles of BM and decodes with div_s (a.M, or the size of the padded
+//                 raster): below 2^24
+//   act_px * ld, w_halfs   halfs the activation / weight offsets range over: an LDS-DMA address is a 64-bit scalar base + a
+//                 32-bit per-lane BYTE offset
+//   smem_attr     dynamic-LDS limit to set for the kernel (>= smem, the bytes of this launch)
+// Family-specific limits (W <= 160, apieces, even H and W, the PADO raster, LDS budget) stay with the family, before the call.
+template <class A>
+hipError_t launch_ldsdma(void (*kernel)(A), A &a, int BM, int BN, long raster, size_t act_px, int ld, size_t w_halfs, size_t smem_attr,
+                         size_t smem, hipStream_t s)
+{
+    if (raster >= (1l << 24) || act_px * ld * 2 >= (1ull << 32) || w_halfs * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+    if (hipError_t e = rva_func_smem((const void *)kernel, smem_attr); e != hipSuccess) return e;
+    a.n_tiles = rva_ceil_div(a.Cout, BN);
+    a.m_tiles = (int)((raster + BM - 1) / BM);
+    kernel<<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
+    return hipGetLastError();
+}
+
 template <int BM, int BN, int WGM, int WGN, int NSLOT>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT == 2 ? 4 : 2))) k_conv3_big(BigArgs a)
 {
@@ -1268,16 +1308,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv % WGM, wn = wv / WGM;
-    // XCD-aware tile order: workgroups id and id + 8 land on the same XCD (round-robin dispatch; speed only, never
-    // correctness), so the n-tiles of one m-tile -- which stage the same activation rows -- are given ids 8 apart: they
-    // share that XCD's L2 instead of pulling the rows across the fabric once per n-tile.  Identity when n_tiles == 1.
-    const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);
-    if (m_tile >= a.m_tiles) return;                      // grid is padded to a multiple of 8 m-tiles
+    int n_tile, m_tile;
+    if (!ldsdma_tile(a, n_tile, m_tile)) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
     const int HW = a.H * a.W;
     const int cpt = a.Cin >> 5;
     const int nsteps = 3 * cpt;
-    const int wrow = 9 * a.Cin;
 
     // this wave's pieces: idx = wv + 8k.  Per-lane byte offsets of each piece, fixed for the whole kernel (see lds_dma16):
     // activation pieces: the lane's source row for dy = 0 / 1 / 2 (clamped into the tensor) + its swizzled chunk, relative to
@@ -1298,9 +1334,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
             poff2[k] = (unsigned)min(max(q1 + a.W, 0), a.M - 1) * (unsigned)(a.ldi * 2) + c;
         } else {
             const int rw = (idx - APIECES) * 16 + lrow;
-            const int dx = rw / BN, co = min(n0 + rw - dx * BN, a.CoutPad - 1);
-            poff0[k] = (unsigned)(co * wrow + dx * a.Cin) * 2u + (unsigned)(((lp - 2 * (rw >> 2)) & 3) * 16);
-            poff1[k] = poff2[k] = poff0[k];
+            poff0[k] = poff1[k] = poff2[k] = ldsdma_woff<BN>(a, n0, rw, rw / BN, rw / BN, lp);
         }
     }
     const unsigned ring0 = lds_addr(ring);
@@ -1345,17 +1379,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
 
 
     f4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-    // bias for the epilogue, fetched BEFORE the first LDS-DMA (so the counted vmcnt waits below never include it) and
-    // long before its use: a dependent global load at the top of the epilogue costs ~1.5 k cycles per block
     float4 bvs[FN];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-        bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(n0 + wn * TN + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
+    ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
+    const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
 
 #ifdef RVA_ROW_STAMPS
     const int st_stride = gridDim.x / 8;
@@ -1454,46 +1480,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
     }
     __syncthreads();     // all waves done with the ring: reuse it as the output staging tile
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;                       // [BM][SROW]
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
-        const float4 bv = bvs[i];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wm * TM + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, TM, TN>(acc, a, bvs, wm, wn, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 512) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
-        const int m = P0 + row;
-        if (m < a.M && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+    const int M = a.M;
+    store_tile<BM, BN, 512>(a, n0, tid, [=](int row, size_t &m) { const int mi = P0 + row; m = (size_t)mi; return mi < M; });
     STAMP(6);
 }
 
@@ -1508,14 +1498,8 @@ hipError_t launch_big(BigArgs &a, hipStream_t s)
     constexpr size_t st = (size_t)BM * (BN + 8) * 2;
     constexpr size_t smem = ring > st ? ring : st;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    if (a.Cin % 32 || a.CoutPad % 4 || a.M >= (1 << 24)) return hipErrorInvalidValue;     // (div_s: raster positions below 2^24)
-    // LDS-DMA addresses are a 64-bit scalar base + a 32-bit per-lane byte offset
-    if ((size_t)a.M * a.ldi * 2 >= (1ull << 32) || (size_t)a.CoutPad * 9 * a.Cin * 2 >= (1ull << 32)) return hipErrorInvalidValue;
-    if (hipError_t e = rva_func_smem((const void *)k_conv3_big<BM, BN, WGM, WGN, NSLOT>, smem); e != hipSuccess) return e;
-    a.n_tiles = rva_ceil_div(a.Cout, BN);
-    a.m_tiles = rva_ceil_div(a.M, BM);
-    k_conv3_big<BM, BN, WGM, WGN, NSLOT><<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
-    return hipGetLastError();
+    if (a.Cin % 32 || a.CoutPad % 4) return hipErrorInvalidValue;
+    return launch_ldsdma(k_conv3_big<BM, BN, WGM, WGN, NSLOT>, a, BM, BN, a.M, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, smem, smem, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1562,13 +1546,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv % WGM, wn = wv / WGM;
-    const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);   // XCD-aware, see k_conv3_big
-    if (m_tile >= a.m_tiles) return;
+    int n_tile, m_tile;
+    if (!ldsdma_tile(a, n_tile, m_tile)) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
     const int HW = a.H * a.W;
     const int cpt = a.Cin >> 5;
     const int nsteps = 3 * cpt;
-    const int wrow = 9 * a.Cin;
     const int apieces = a.apieces;                        // ceil((BM + 2W + 2) / 16)
     __half *act0 = (__half *)smem;                        // [2][apieces][16][32]
     __half *wt0 = act0 + (size_t)2 * apieces * 512;       // [2][WPIECES][16][32]
@@ -1609,19 +1592,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
 #pragma unroll
     for (int k = 0; k < NPW; ++k) {
         const int rw = (wv + 8 * k) * 16 + lrow;
-        const int dx = rw / BN, co = min(n0 + rw - dx * BN, a.CoutPad - 1);
-        woff[k] = (unsigned)(co * wrow + min(dx, 2) * a.Cin) * 2u + (unsigned)(((lp - 2 * (rw >> 2)) & 3) * 16);
+        woff[k] = ldsdma_woff<BN>(a, n0, rw, rw / BN, min(rw / BN, 2), lp);
     }
     f4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+    float4 bvs[FN];
+    ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-    float4 bvs[FN];                                       // before the first DMA (see k_conv3_big)
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-        bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(n0 + wn * TN + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
 
 #ifdef RVA_ROW_STAMPS
     const int st_stride = gridDim.x / 8;
@@ -1736,54 +1712,21 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
     }
     __syncthreads();     // all waves done with the buffers: reuse them as the output staging tile
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;                       // [BM][SROW]
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
-        const float4 bv = bvs[i];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wm * TM + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, TM, TN>(acc, a, bvs, wm, wn, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 512) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
-        const int m = PADO ? rowmap[row] : P0 + row;
-        if ((PADO ? m >= 0 : m < a.M) && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+    const int M = a.M;
+    store_tile<BM, BN, 512>(a, n0, tid, [=](int row, size_t &m) {
+        const int mi = PADO ? rowmap[row] : P0 + row;    // PADO: -1 = pad position of the padded raster
+        m = (size_t)mi;
+        return PADO ? mi >= 0 : mi < M;
+    });
     STAMP(6);
 }
 
 template <int BM, int BN, int WGM, int WGN, bool NOSEL = false, bool PADO = false>
 hipError_t launch_run(RunArgs &a, hipStream_t s)
 {
-    if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160 || a.M >= (1 << 24)) return hipErrorInvalidValue;
-    if ((size_t)a.M * a.ldi * 2 >= (1ull << 32) || (size_t)a.CoutPad * 9 * a.Cin * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+    if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160) return hipErrorInvalidValue;
     const int wp = PADO ? a.W + 1 : a.W;
     a.apieces = rva_ceil_div(BM + 2 * wp + 2, 16);
     if (a.apieces > 8 * 5) return hipErrorInvalidValue;   // MAXA pieces per wave
@@ -1793,17 +1736,14 @@ hipError_t launch_run(RunArgs &a, hipStream_t s)
     long mp = a.M;
     if (PADO) {
         const int batch = a.M / (a.H * a.W);
-        mp = (long)batch * (a.H + 1) * (a.W + 1);         // positions of the padded raster (div_s: below 2^24)
-        if (a.M % (a.H * a.W) || mp >= (1l << 24)) return hipErrorInvalidValue;
+        mp = (long)batch * (a.H + 1) * (a.W + 1);         // positions of the padded raster
+        if (a.M % (a.H * a.W)) return hipErrorInvalidValue;
         a.map_off = (int)smem;                            // per-row pixel index behind the rings / the output stage
         smem += (size_t)BM * 4;
     }
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = rva_func_smem((const void *)k_conv3_run<BM, BN, WGM, WGN, NOSEL, PADO>, 160 * 1024); e != hipSuccess) return e;
-    a.n_tiles = rva_ceil_div(a.Cout, BN);
-    a.m_tiles = (int)((mp + BM - 1) / BM);
-    k_conv3_run<BM, BN, WGM, WGN, NOSEL, PADO><<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
-    return hipGetLastError();
+    // raster = mp: the positions the kernel decodes (mp >= a.M, so a.M stays below 2^24 with it)
+    return launch_ldsdma(k_conv3_run<BM, BN, WGM, WGN, NOSEL, PADO>, a, BM, BN, mp, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1835,11 +1775,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM <= 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv % WGM, wn = wv / WGM;
-    const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);   // XCD-aware, see k_conv3_big
-    if (m_tile >= a.m_tiles) return;
+    int n_tile, m_tile;
+    if (!ldsdma_tile(a, n_tile, m_tile)) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
     const int Ho = a.H >> 1, Wo = a.W >> 1, Wp = Wo + 1, HWp = Ho * Wp;
-    const int cpt = a.Cin >> 5, nsteps = 3 * cpt, wrow = 9 * a.Cin;
+    const int cpt = a.Cin >> 5, nsteps = 3 * cpt;
     __half *act0 = (__half *)smem;                        // [3 dy][AP][16][32]
     __half *wt0 = act0 + (size_t)3 * AP * 512;            // [2][WPIECES][16][32]
     const unsigned lds_act = lds_addr(act0), lds_w = lds_addr(wt0);
@@ -1878,18 +1818,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM <= 
 #pragma unroll
     for (int k = 0; k < NPW; ++k) {
         const int rw = (wv + 8 * k) * 16 + lrow;
-        const int dx = rw / BN, co = min(n0 + rw - dx * BN, a.CoutPad - 1);
-        woff[k] = (unsigned)(co * wrow + min(dx, 2) * a.Cin) * 2u + (unsigned)(((lp - 2 * (rw >> 2)) & 3) * 16);
+        woff[k] = ldsdma_woff<BN>(a, n0, rw, rw / BN, min(rw / BN, 2), lp);
     }
     f4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
     float4 bvs[FN];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-        bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(n0 + wn * TN + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
+    ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const long long rowb = (long long)a.W * a.ldi * 2;    // bytes of an input row
     // step (cc, dy): activations into buffer dy, weights into buffer (step & 1)
     auto issue = [&](int step, int cc, int dy) {
@@ -1947,46 +1880,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM <= 
     }
     __syncthreads();     // all waves done with the buffers: reuse them as the output staging tile
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;                       // [BM][SROW]
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
-        const float4 bv = bvs[i];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wm * TM + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, TM, TN>(acc, a, bvs, wm, wn, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 512) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
-        const int m = rowmap[row];
-        if (m >= 0 && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+    store_tile<BM, BN, 512>(a, n0, tid, [=](int row, size_t &m) { const int mi = rowmap[row]; m = (size_t)mi; return mi >= 0; });
 }
 
 // a.H / a.W: INPUT size (even), a.M: output pixels
@@ -1998,21 +1894,14 @@ hipError_t launch_s2run(RunArgs &a, hipStream_t s)
     const int Ho = a.H / 2, Wo = a.W / 2;
     if (Ho <= 0 || Wo <= 0 || a.M % (Ho * Wo)) return hipErrorInvalidValue;
     const long batch = a.M / (Ho * Wo);
-    const long mp = batch * Ho * (Wo + 1);                // positions of the padded output raster (div_s: below 2^24)
-    if (mp >= (1l << 24)) return hipErrorInvalidValue;
-    // LDS-DMA addresses: a 64-bit scalar base + a 32-bit per-lane byte offset
-    if ((size_t)batch * a.H * a.W * a.ldi * 2 >= (1ull << 32) || (size_t)a.CoutPad * 9 * a.Cin * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+    const long mp = batch * Ho * (Wo + 1);                // positions of the padded output raster
     const size_t ring = (size_t)(3 * AP + 2 * (3 * BN / 16)) * 1024;
     const size_t st = (size_t)BM * (BN + 8) * 2;
     size_t smem = ring > st ? ring : st;
     a.map_off = (int)smem;
     smem += (size_t)BM * 4;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = rva_func_smem((const void *)k_conv3_s2run<BM, BN, WGM, WGN>, 160 * 1024); e != hipSuccess) return e;
-    a.n_tiles = rva_ceil_div(a.Cout, BN);
-    a.m_tiles = (int)((mp + BM - 1) / BM);
-    k_conv3_s2run<BM, BN, WGM, WGN><<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
-    return hipGetLastError();
+    return launch_ldsdma(k_conv3_s2run<BM, BN, WGM, WGN>, a, BM, BN, mp, (size_t)batch * a.H * a.W, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2043,12 +1932,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv % WGM, wn = wv / WGM;
-    const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);   // XCD-aware, see k_conv3_big
-    if (m_tile >= a.m_tiles) return;
+    int n_tile, m_tile;
+    if (!ldsdma_tile(a, n_tile, m_tile)) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
     const int HW = a.H * a.W;
     const int cpt = a.Cin >> 5;
-    const int wrow = 9 * a.Cin;
     const int apieces = a.apieces;                        // ceil((BM + 2W + 2) / 16)
     __half *act0 = (__half *)smem;                        // [2][apieces][16][32]
     __half *wt0 = act0 + (size_t)2 * apieces * 512;       // [2][WPIECES][16][32]
@@ -2065,19 +1953,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
 #pragma unroll
     for (int k = 0; k < NPW; ++k) {
         const int rw = (wv + 8 * k) * 16 + lrow;          // row of the [9][BN] weight image
-        const int tap = min(rw / BN, 8), co = min(n0 + rw - tap * BN, a.CoutPad - 1);
-        woff[k] = (unsigned)(co * wrow + tap * a.Cin) * 2u + (unsigned)(((lp - 2 * (rw >> 2)) & 3) * 16);
+        const int tap = min(rw / BN, 8);
+        woff[k] = ldsdma_woff<BN>(a, n0, rw, tap, tap, lp);
     }
     f4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+    float4 bvs[FN];
+    ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-    float4 bvs[FN];                                       // before the first DMA (see k_conv3_big)
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-        bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(n0 + wn * TN + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
 
 #define CHUNK_ISSUE(CC)                                                                                          \
     do {                                                                                                         \
@@ -2158,64 +2040,23 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
 #undef CHUNK_ISSUE
     __syncthreads();     // all waves done with the buffers: reuse them as the output staging tile
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;                       // [BM][SROW]
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
-        const float4 bv = bvs[i];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wm * TM + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, TM, TN>(acc, a, bvs, wm, wn, lane);
     __syncthreads();
-    constexpr int CPR = BN / 8;
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 512) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
-        const int m = P0 + row;
-        if (m < a.M && co < a.Cout) {
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+    const int M = a.M;
+    store_tile<BM, BN, 512>(a, n0, tid, [=](int row, size_t &m) { const int mi = P0 + row; m = (size_t)mi; return mi < M; });
 }
 
 template <int BM, int BN, int WGM, int WGN>
 hipError_t launch_chunk(RunArgs &a, hipStream_t s)
 {
-    if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160 || a.M >= (1 << 24)) return hipErrorInvalidValue;
-    if ((size_t)a.M * a.ldi * 2 >= (1ull << 32) || (size_t)a.CoutPad * 9 * a.Cin * 2 >= (1ull << 32)) return hipErrorInvalidValue;
+    if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160) return hipErrorInvalidValue;
     a.apieces = rva_ceil_div(BM + 2 * a.W + 2, 16);
     if (a.apieces > 8 * 5) return hipErrorInvalidValue;   // MAXA pieces per wave
     const size_t ring = (size_t)(2 * a.apieces + 2 * (9 * BN / 16)) * 1024;
     const size_t st = (size_t)BM * (BN + 8) * 2;
     const size_t smem = ring > st ? ring : st;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
-    if (hipError_t e = rva_func_smem((const void *)k_conv3_chunk<BM, BN, WGM, WGN>, 160 * 1024); e != hipSuccess) return e;
-    a.n_tiles = rva_ceil_div(a.Cout, BN);
-    a.m_tiles = rva_ceil_div(a.M, BM);
-    k_conv3_chunk<BM, BN, WGM, WGN><<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
-    return hipGetLastError();
+    return launch_ldsdma(k_conv3_chunk<BM, BN, WGM, WGN>, a, BM, BN, a.M, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2252,9 +2093,8 @@ __global__ void __launch_bounds__(512)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv % WGM, wn = wv / WGM;
-    // XCD-aware tile order (see k_conv3_big): the n-tiles of one m-tile get workgroup ids 8 apart
-    const int n_tile = (blockIdx.x >> 3) % a.n_tiles, m_tile = ((blockIdx.x >> 3) / a.n_tiles) * 8 + (blockIdx.x & 7);
-    if (m_tile >= a.m_tiles) return;
+    int n_tile, m_tile;
+    if (!ldsdma_tile(a, n_tile, m_tile)) return;
     const int P0 = m_tile * BM, n0 = n_tile * BN;
     const int HoWo = a.wrows * a.Wo;                               // raster positions per image: the row window's pixels
     const int cpt = a.Cin / BK;
@@ -2342,15 +2182,9 @@ __global__ void __launch_bounds__(512)
 
 
     f4 acc[FN][FM];
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+    float4 bvs[FN];
+    ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-    float4 bvs[FN];                                                // before the first DMA: see k_conv3_big
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-        bvs[i] = *reinterpret_cast<const float4 *>(a.bias + min(n0 + wn * TN + 16 * i + (lane >> 4) * 4, a.CoutPad - 4));
 
 #pragma unroll
     for (int t = 0; t < (NSLOT - 1) * SUB; ++t)
@@ -2418,26 +2252,11 @@ __global__ void __launch_bounds__(512)
 #undef GB_ISSUE
     __syncthreads();     // ring drained and no longer read: reuse it as the output staging tile
 
-    constexpr int SROW = BN + 8;
-    __half *stage = (__half *)smem;                                // [BM][SROW]
-#pragma unroll
-    for (int i = 0; i < FN; ++i) {
-        const int co = wn * TN + 16 * i + (lane >> 4) * 4;
-        const float4 bv = bvs[i];
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (a.act) { v0 = silu_f(v0); v1 = silu_f(v1); v2 = silu_f(v2); v3 = silu_f(v3); }
-            const int px = wm * TM + 16 * j + (lane & 15);
-            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-            uint2 pk;
-            pk.x = *reinterpret_cast<uint32_t *>(&lo);
-            pk.y = *reinterpret_cast<uint32_t *>(&hi);
-            *reinterpret_cast<uint2 *>(stage + (size_t)px * SROW + co) = pk;
-        }
-    }
+    stage_tile<BN, TM, TN>(acc, a, bvs, wm, wn, lane);
     __syncthreads();
     if constexpr (HEAD) {
+        constexpr int SROW = BN + 8;
+        const __half *stage = (const __half *)smem;                // [BM][SROW], as stage_tile wrote it
         // thread = pixel row of the staged tile (values rounded to fp16 exactly as the stand-alone path stores them);
         // same operation order as head_anchor, so the result is bit-identical to conv -> k_head
         for (int r = tid; r < BM; r += 512) {
@@ -2494,30 +2313,14 @@ __global__ void __launch_bounds__(512)
         }
         return;
     }
-    constexpr int CPR = BN / 8;
     const int wskip = (a.Ho - a.wrows) * a.Wo;                     // output pixels of an image outside the row window (uniform; 0 = whole image)
-#pragma unroll 4
-    for (int q = tid; q < BM * CPR; q += 512) {
-        const int row = q / CPR, pc = q - row * CPR;
-        const int co = n0 + pc * 8;
+    const int M = a.M, wfirst = a.wy0 * a.Wo;
+    store_tile<BM, BN, 512>(a, n0, tid, [=](int row, size_t &m) {
         const int mw = P0 + row;
-        if (mw < a.M && co < a.Cout) {
-            // pixel index in the whole output raster: the window's rows of image b start at (b * Ho + wy0) * Wo
-            const int m = wskip ? mw + div_s(mw, HoWo, inv_howo) * wskip + a.wy0 * a.Wo : mw;
-            uint4 v = *reinterpret_cast<const uint4 *>(stage + (size_t)row * SROW + pc * 8);
-            if (a.res) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(a.res + (size_t)m * a.ldr + co);
-                __half2 *vh = reinterpret_cast<__half2 *>(&v);
-                const __half2 *rh = reinterpret_cast<const __half2 *>(&r);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float2 x = __half22float2(vh[u]), y = __half22float2(rh[u]);
-                    vh[u] = __floats2half2_rn(x.x + y.x, x.y + y.y);
-                }
-            }
-            *reinterpret_cast<uint4 *>(a.out + (size_t)m * a.ldo + co) = v;
-        }
-    }
+        // pixel index in the whole output raster: the window's rows of image b start at (b * Ho + wy0) * Wo
+        m = (size_t)(wskip ? mw + div_s(mw, HoWo, inv_howo) * wskip + wfirst : mw);
+        return mw < M;
+    });
 }
 
 template <int BM, int BN, int WGM, int WGN, int NSLOT, int KS, int BK, bool UP = false, bool HEAD = false, int SUB = 1>
@@ -2527,16 +2330,9 @@ hipError_t launch_gbig1(ConvArgs &a, hipStream_t s)
     constexpr size_t st = (size_t)BM * (BN + 8) * 2;
     constexpr size_t smem = ring > st ? ring : st;
     static_assert(smem <= 160 * 1024, "LDS budget");
-    if (hipError_t e = rva_func_smem((const void *)k_conv_gbig<BM, BN, WGM, WGN, NSLOT, KS, BK, UP, HEAD, SUB>, smem); e != hipSuccess) return e;
-    a.n_tiles = rva_ceil_div(a.Cout, BN);
-    // LDS-DMA addresses are a 64-bit scalar base + a 32-bit per-lane byte offset
-    if ((size_t)a.H * a.W * (size_t)(a.M / (a.wrows * a.Wo) + 1) * (UP ? a.ldi2 : a.ldi) * 2 >= (1ull << 32) ||
-        (size_t)a.CoutPad * KS * KS * a.Cin * 2 >= (1ull << 32))
-        return hipErrorInvalidValue;
-    if (a.M >= (1 << 24)) return hipErrorInvalidValue;             // div_s: raster positions below 2^24
-    a.m_tiles = rva_ceil_div(a.M, BM);
-    k_conv_gbig<BM, BN, WGM, WGN, NSLOT, KS, BK, UP, HEAD, SUB><<<rva_ceil_div(a.m_tiles, 8) * 8 * a.n_tiles, 512, smem, s>>>(a);
-    return hipGetLastError();
+    // activation offsets range over the whole images the window's pixels lie in (UP: of the full-res source)
+    return launch_ldsdma(k_conv_gbig<BM, BN, WGM, WGN, NSLOT, KS, BK, UP, HEAD, SUB>, a, BM, BN, a.M, (size_t)a.H * a.W * (size_t)(a.M / (a.wrows * a.Wo) + 1),
+                         UP ? a.ldi2 : a.ldi, (size_t)a.CoutPad * KS * KS * a.Cin, smem, smem, s);
 }
 
 template <int BM, int BN, int WGM, int WGN, int NSLOT, int BK = 64, int SUB = 1>
