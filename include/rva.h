@@ -406,6 +406,28 @@ int rva_yolo_head_box32_f16(rva_ctx *ctx, const void *box_logits, int ldb, const
 int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
                              const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
                              int anchors_total, const float *strides, rva_stream_t stream);
+/* Any class count (a detector trained on its own class list: one, three, twenty classes): the three head launches above for
+ * 1 <= nc <= 1024 (K2's class-filter limit).  out stays exactly [batch, 4+nc, anchors_total] -- a 5-row head is read as plain
+ * scores by rva_postprocess_batch, a wider one as objectness times classes, so the tensor is never widened -- and the kernels
+ * are the ones of the entries above: they still load the class logits eight at a time and store only the class rows < nc, so
+ * for nc % 8 == 0 the result is bit-identical to those entries.  boxes32 may be NULL (no side tensor) or is written as by the
+ * _box32 forms.
+ *   rva_yolo_head_nc_f16 / rva_yolo_head3_nc_f16: ldb, ldc % 8 == 0 and ldc >= roundup(nc, 8): a class row holds the nc logits
+ *     and pad columns up to the next multiple of 8 at least.  The pad columns may hold anything, NaN included: nothing of them
+ *     reaches out.
+ *   rva_conv1x1_head_nc_f16: mode 1 (Cout = 64; boxes32 optional) and mode 2 (Cout = roundup(nc, 8), weights and bias of the
+ *     output channels >= nc are the caller's padding, zero in the plan; boxes32 must be NULL), Cin % 64 == 0, and the level
+ *     must lie inside the anchor range.
+ * Anything else returns RVA_ERR_ARG before any launch: nothing is written. */
+int rva_yolo_head_nc_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out,
+                         float *boxes32, int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride,
+                         rva_stream_t stream);
+int rva_yolo_head3_nc_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                          const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
+                          int anchors_total, const float *strides, rva_stream_t stream);
+int rva_conv1x1_head_nc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch,
+                            int H, int W, int Cin, int Cout, int mode, void *out, float *boxes32, int nc, int anchors_total,
+                            int anchor_offset, float stride_px, int variant, rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * fp32 detector primitives (NHWC float32) -- the reference's default precision (`half: false`: an fp32
@@ -502,6 +524,14 @@ int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void 
  *   zero-fills every buffer and every kernel writes finite values for finite inputs and weights, so the precondition holds as
  *   long as no run was fed non-finite input or weights; after such a run the images it covered must be run again with finite
  *   input (all rows: _set_static_rows first) before a smaller n is trusted.
+ * Class count: desc.nc is any 1 <= nc <= 1024 (1024: K2's class-filter limit), in fp16 and fp32 plans.  `convs` are the
+ *   module's own: the class branch with its real widths (interior max(c3, min(nc, 100)), last convolution Cout = nc).  Inside
+ *   the plan every channel count of that branch the kernels need aligned is rounded up -- to 8 (fp16), to 16 where an fp32
+ *   convolution reads it as Cin, the class logits to roundup(nc, 8) columns -- and weights and biases are zero-extended at
+ *   upload: a pad channel is SiLU(0) = 0 and meets zero weights, so the result equals, bit for bit, a plan of the padded module.
+ *   Output, _info (out_rows = 4 + nc) and _output_layout keep the real nc: the head tensor is exactly [batch, 4+nc, anchors].
+ *   Where the branch widths allow the fused decode (box and padded class width multiples of 64: every scale for nc <= 64) the
+ *   launch structure is the one of nc = 80; otherwise the plan ends in one rva_yolo_head3_nc_f16 launch.
  * -------------------------------------------------------------------------------------------- */
 #define RVA_PLAN_NO_STEM2 1   /* rva_yolov8_desc.flags: stem and first downsampling convolution as two launches (A/B switch) */
 #define RVA_PLAN_NO_CIN_PAD 2 /* ... convolutions with Cin % 32 != 0 keep their Cin (default: declared rounded up to 32, zero weights) */
@@ -514,7 +544,7 @@ typedef struct rva_yolov8_desc {
     int32_t widths[5];                /* c1..c5 (YOLOv8s: 32 64 128 256 512) */
     int32_t depth_backbone[4];        /* bottlenecks of the C2f blocks b2, b4, b6, b8 (YOLOv8s: 1 2 2 1) */
     int32_t depth_head;               /* bottlenecks of h12, h15, h18, h21 (YOLOv8s: 1) */
-    int32_t nc, reg_max;              /* classes (multiple of 8), DFL bins (16) */
+    int32_t nc, reg_max;              /* classes (1..1024, see "Class count" above), DFL bins (16) */
     int32_t n_convs;                  /* length of `convs` */
     int32_t flags;
 } rva_yolov8_desc;

@@ -226,6 +226,12 @@ def lib() -> C.CDLL:
                                               C.c_int, C.c_float, _P]),
         "rva_yolo_head3_box32_f16": (C.c_int, [_P, pp, i32p, pp, i32p, _P, _P, C.c_int, i32p, i32p, C.c_int, C.c_int,
                                                C.POINTER(C.c_float), _P]),
+        "rva_yolo_head_nc_f16": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_float, _P]),
+        "rva_yolo_head3_nc_f16": (C.c_int, [_P, pp, i32p, pp, i32p, _P, _P, C.c_int, i32p, i32p, C.c_int, C.c_int,
+                                            C.POINTER(C.c_float), _P]),
+        "rva_conv1x1_head_nc_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                              C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
         "rva_conv1x1_upcat_f16": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_int, _P]),
         "rva_yolo_head3_f16": (C.c_int, [_P, pp, i32p, pp, i32p, _P, C.c_int, i32p, i32p, C.c_int, C.c_int, C.POINTER(C.c_float), _P]),
@@ -327,6 +333,7 @@ EXPORTS = [
     "rva_conv_f32_num_variants", "rva_conv2d_nhwc_f32_v", "rva_stem_conv_f32", "rva_maxpool5_nhwc_f32", "rva_upsample2x_nhwc_f32",
     "rva_yolo_head_f32",
     "rva_postprocess_boxes_batch", "rva_conv1x1_head_box32_f16", "rva_yolo_head_box32_f16", "rva_yolo_head3_box32_f16",
+    "rva_yolo_head_nc_f16", "rva_yolo_head3_nc_f16", "rva_conv1x1_head_nc_f16",
     "rva_yolov8_plan_output_layout",
     "rva_yolov8_plan_create", "rva_yolov8_plan_destroy", "rva_yolov8_plan_info", "rva_yolov8_plan_run", "rva_yolov8_plan_run_lanes",
     "rva_yolov8_plan_run_range", "rva_yolov8_plan_tunable_desc", "rva_yolov8_plan_launch_tunable", "rva_yolov8_plan_set_variant",

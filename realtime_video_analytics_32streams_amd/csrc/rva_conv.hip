@@ -64,7 +64,7 @@ struct ConvArgs {
     int ldr;
     int CoutPad;
     // k_conv_gbig<..., HEAD>: the detect head's last 1x1 convolutions decode straight into out[B, 4+nc, A]
-    __half *hout; int hmode, hnc, hA, ha0, hW, hHW; float hstride;   // hmode 1 = box branch (DFL + dist2bbox), 2 = class branch (sigmoid)
+    __half *hout; int hmode, hnc, hA, ha0, hW, hHW; float hstride;   // hmode 1 = box branch (DFL + dist2bbox), 2 = class branch (sigmoid; Cout = roundup(hnc, 8), class rows < hnc stored)
     const __half *in2; int ldi2, c_split;   // k_conv_gbig<..., UP>: `in` = low-res tensor (nearest 2x upsampled on the fly,
                                             // channels [0, c_split)), `in2` = full-res tensor (channels [c_split, Cin))
     int H, W, Cin, CinPad, Ho, Wo, Cout, stride, M, act, n_tiles, m_tiles;   // CinPad = Cin rounded up to 32 (weight rows are zero-padded)
@@ -1068,6 +1068,20 @@ struct Head3Args { HeadArgs lv[3]; int blocks[3]; };     // blocks[l] = 256-anch
 template <bool BOX32 = false>
 __device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, float *box32 = nullptr);
 
+// Sigmoid of eight class logits of one anchor into eight consecutive class rows (row stride A halves) starting at `o`.  GUARD: only
+// the first `left` of the eight rows exist (the last group of a class count that is no multiple of 8; the other logits are padding).
+template <bool GUARD>
+__device__ __forceinline__ void store_scores8(__half *o, size_t A, const uint4 q, int left)
+{
+    const __half2 *hq = reinterpret_cast<const __half2 *>(&q);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float2 f = __half22float2(hq[t]);
+        if (!GUARD || 2 * t < left) o[(size_t)(2 * t) * A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.x)));
+        if (!GUARD || 2 * t + 1 < left) o[(size_t)(2 * t + 1) * A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.y)));
+    }
+}
+
 __global__ void __launch_bounds__(256) k_head(HeadArgs a)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1138,16 +1152,13 @@ __device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, flo
         o32[(size_t)2 * a.A] = (x2 - x1) * a.stride;
         o32[(size_t)3 * a.A] = (y2 - y1) * a.stride;
     }
+    // class logits eight at a time from a row of ldc >= roundup(nc, 8) halves; only the class rows < nc exist in `out` (a ragged
+    // nc: the row's pad columns are loaded and dropped, whatever they hold)
     const __half *cp = a.cls + pix * a.ldc;
-    for (int c = 0; c < a.nc; c += 8) {
+    for (int c = 0; c < a.nc; c += 8) {                  // (uniform branch: whole groups of eight take the unguarded stores)
         const uint4 q = *reinterpret_cast<const uint4 *>(cp + c);
-        const __half2 *hq = reinterpret_cast<const __half2 *>(&q);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float2 f = __half22float2(hq[t]);
-            o[(size_t)(4 + c + 2 * t) * a.A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.x)));
-            o[(size_t)(5 + c + 2 * t) * a.A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.y)));
-        }
+        if (c + 8 <= a.nc) store_scores8<false>(o + (size_t)(4 + c) * a.A, (size_t)a.A, q, 8);
+        else store_scores8<true>(o + (size_t)(4 + c) * a.A, (size_t)a.A, q, a.nc - c);
     }
 }
 
@@ -2301,13 +2312,9 @@ __global__ void __launch_bounds__(512)
                 const int cend = min(BN, a.Cout - n0);
                 for (int c = 0; c < cend; c += 8) {
                     const uint4 q = *reinterpret_cast<const uint4 *>(row + c);
-                    const __half2 *hq = reinterpret_cast<const __half2 *>(&q);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const float2 f = __half22float2(hq[t]);
-                        o[(size_t)(4 + n0 + c + 2 * t) * a.hA] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.x)));
-                        o[(size_t)(5 + n0 + c + 2 * t) * a.hA] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.y)));
-                    }
+                    const int k = n0 + c;                           // class rows >= hnc are padding of the convolution (Cout = roundup(hnc, 8))
+                    if (k + 8 <= a.hnc) store_scores8<false>(o + (size_t)(4 + k) * a.hA, (size_t)a.hA, q, 8);
+                    else store_scores8<true>(o + (size_t)(4 + k) * a.hA, (size_t)a.hA, q, a.hnc - k);
                 }
             }
         }
@@ -3764,15 +3771,19 @@ int rva_conv1x1_upcat_f16(rva_ctx *ctx, const void *low, int ld_low, int c_low, 
     return launch_gather64_1x1<true, false>(ctx, "rva_conv1x1_upcat_f16", a, variant, (hipStream_t)stream_);
 }
 
+// any_nc: the contract of rva_conv1x1_head_nc_f16 (1 <= nc <= 1024, class branch Cout = roundup(nc, 8)); else nc % 8 == 0
 static int conv1x1_head(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
                         int Cin, int Cout, int mode, void *out, float *boxes32, int nc, int anchors_total, int anchor_offset, float stride_px,
-                        int variant, rva_stream_t stream_)
+                        int variant, rva_stream_t stream_, bool any_nc = false)
 {
     if (!ctx) return RVA_ERR_ARG;
-    if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || Cin % 64 || Cout % 8 || ldi % 8 || nc % 8 ||
-        (mode != 1 && mode != 2) || (mode == 1 && Cout != 64) || (mode == 2 && Cout != nc) ||
+    if (any_nc && (nc < 1 || nc > 1024 || anchor_offset < 0 || H <= 0 || W <= 0 || anchor_offset + H * W > anchors_total ||
+                   (boxes32 && ((uintptr_t)boxes32 % 4 || mode != 1))))
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_nc_f16: 1 <= nc <= 1024, the level inside the anchor range, boxes32 (mode 1) a float tensor");
+    if (!in || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || Cin % 64 || Cout % 8 || ldi % 8 || (!any_nc && nc % 8) ||
+        (mode != 1 && mode != 2) || (mode == 1 && Cout != 64) || (mode == 2 && Cout != (nc + 7) / 8 * 8) ||
         ((uintptr_t)in | (uintptr_t)weights) % 16 || H > 2000 || W > 2000)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_f16: unsupported shape (Cin %% 64; box branch Cout = 64; class branch Cout = nc)");
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_f16: unsupported shape (Cin %% 64; box branch Cout = 64; class branch Cout = nc, rounded up to 8 by _nc)");
     ConvArgs a{};
     a.in = (const __half *)in; a.ldi = ldi; a.w = (const __half *)weights; a.bias = bias; a.out = nullptr; a.ldo = 0;
     a.H = H; a.W = W; a.Cin = Cin; a.CinPad = Cin; a.Cout = Cout; a.stride = 1; a.act = 0; a.Ho = H; a.Wo = W; a.M = batch * H * W;
@@ -3798,6 +3809,14 @@ int rva_conv1x1_head_box32_f16(rva_ctx *ctx, const void *in, int ldi, const void
     if (!boxes32 || (uintptr_t)boxes32 % 4 || anchor_offset < 0 || anchor_offset + H * W > anchors_total)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head_box32_f16: boxes32 must be a float tensor [batch, 4, anchors_total] and the level must lie inside it");
     return conv1x1_head(ctx, in, ldi, weights, bias, batch, H, W, Cin, 64, 1, out, boxes32, nc, anchors_total, anchor_offset, stride_px, variant, stream_);
+}
+
+int rva_conv1x1_head_nc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                            int Cin, int Cout, int mode, void *out, float *boxes32, int nc, int anchors_total, int anchor_offset,
+                            float stride_px, int variant, rva_stream_t stream_)
+{
+    return conv1x1_head(ctx, in, ldi, weights, bias, batch, H, W, Cin, Cout, mode, out, boxes32, nc, anchors_total, anchor_offset, stride_px, variant,
+                        stream_, true);
 }
 
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }
@@ -3920,14 +3939,15 @@ int rva_upsample2x_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, void *out, in
 
 static int yolo_head3(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
                       const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
-                      const float *strides, rva_stream_t stream_)
+                      const float *strides, rva_stream_t stream_, bool any_nc = false)
 {
-    if (!ctx || !box_logits || !cls_logits || !ldb || !ldc || !h || !w || !strides || !out || nc % 8)
+    if (!ctx || !box_logits || !cls_logits || !ldb || !ldc || !h || !w || !strides || !out ||
+        (any_nc ? nc < 1 || nc > 1024 || batch <= 0 : nc % 8 != 0))
         return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: bad argument");
     Head3Args a{};
     int a0 = 0, total = 0;
     for (int l = 0; l < 3; ++l) {
-        if (!box_logits[l] || !cls_logits[l] || ldb[l] % 8 || ldc[l] % 8 || h[l] <= 0 || w[l] <= 0)
+        if (!box_logits[l] || !cls_logits[l] || ldb[l] % 8 || ldc[l] % 8 || h[l] <= 0 || w[l] <= 0 || (any_nc && ldc[l] < (nc + 7) / 8 * 8))
             return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: bad level %d", l);
         a.lv[l] = HeadArgs{(const __half *)box_logits[l], ldb[l], (const __half *)cls_logits[l], ldc[l], (__half *)out, batch,
                            h[l], w[l], nc, anchors_total, a0, strides[l]};
@@ -3956,6 +3976,32 @@ int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const 
     if (!ctx) return RVA_ERR_ARG;
     if (!boxes32 || (uintptr_t)boxes32 % 4) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_box32_f16: boxes32 must be a float tensor [batch, 4, anchors_total]");
     return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, boxes32, batch, h, w, nc, anchors_total, strides, stream_);
+}
+
+int rva_yolo_head3_nc_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
+                          const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
+                          int anchors_total, const float *strides, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if ((uintptr_t)boxes32 % 4) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_nc_f16: boxes32 must be NULL or a float tensor [batch, 4, anchors_total]");
+    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, boxes32, batch, h, w, nc, anchors_total, strides, stream_, true);
+}
+
+int rva_yolo_head_nc_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, float *boxes32,
+                         int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!box_logits || !cls_logits || !out || (uintptr_t)boxes32 % 4 || nc < 1 || nc > 1024 || ldb % 8 || ldc % 8 || ldc < (nc + 7) / 8 * 8 ||
+        batch <= 0 || h <= 0 || w <= 0 || anchor_offset < 0 || anchor_offset + h * w > anchors_total)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_nc_f16: bad argument (1 <= nc <= 1024; ldb, ldc %% 8; ldc >= roundup(nc, 8); the level inside "
+                        "the anchor range)");
+    HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
+               anchors_total, anchor_offset, stride};
+    dim3 g(rva_ceil_div(h * w, 256), batch);
+    if (boxes32) k_head_box32<<<g, 256, 0, (hipStream_t)stream_>>>(a, boxes32);
+    else k_head<<<g, 256, 0, (hipStream_t)stream_>>>(a);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
 }
 
 int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, int batch,

@@ -27,10 +27,15 @@
 //   b0 stem 3x3 s2 | b1 3x3 s2 | b2 C2f | b3 3x3 s2 | b4 C2f | b5 3x3 s2 | b6 C2f | b7 3x3 s2 | b8 C2f | b9 SPPF |
 //   h12 C2f(cat[up(p5), p4]) | h15 C2f(cat[up(n4), p3]) | h16 3x3 s2 | h18 C2f(cat[h16, n4]) | h19 3x3 s2 | h21 C2f(cat[h19, p5]) |
 //   detect: per level box = 3x3, 3x3, 1x1 (4 reg_max) and cls = 3x3, 3x3, 1x1 (nc); DFL + dist2bbox + sigmoid -> [B, 4+nc, A].
+// Class count: any 1 <= nc <= 1024.  The class branch runs with its channel counts rounded up to what the kernels take (interior
+// width to 8, to 16 in an fp32 plan; the logits to ncp = roundup(nc, 8) columns), weights and biases zero-extended on the host
+// before they are packed (Builder::padded): a pad channel is SiLU(0) = 0 and meets zero weights.  The head kernels read rows of
+// ncp logits and store the nc real class rows, so the output is exactly [B, 4+nc, A].
 // Module order of `convs` (what create() consumes, checked against the descriptor): b0, b1, C2f(b2), b3, C2f(b4), b5, C2f(b6), b7,
 // C2f(b8), SPPF(b9) = cv1, cv2, C2f(h12), C2f(h15), h16, C2f(h18), h19, C2f(h21), then per level l = 0..2: box[l][0..2], then per
 // level: cls[l][0..2];  C2f(x) = cv1, cv2, then per bottleneck: cv1, cv2.
 #include <cstring>
+#include <deque>
 #include <memory>
 
 #include "rva_internal.h"
@@ -94,6 +99,8 @@ struct Builder {
     int next = 0;                         // next convolution of the module-order list
     int lane = 0;
     std::string err;
+    std::deque<std::vector<float>> pad_store;             // zero-extended host copies of the class branch (padded) ...
+    std::deque<rva_conv_weights> pad_convs;               // ... and their descriptors
 
     bool fail(const std::string &m) { if (err.empty()) err = m; return false; }
 
@@ -192,6 +199,24 @@ struct Builder {
             return nullptr;
         }
         return c;
+    }
+    // `c` with input / output channels zero-extended to cinp / coutp (the convolution itself where nothing is to pad)
+    const rva_conv_weights *padded(const rva_conv_weights *c, int cinp, int coutp)
+    {
+        if (!c || !c->weight || (c->cin == cinp && c->cout == coutp)) return c;
+        const int kk = c->k * c->k;
+        std::vector<float> &w = pad_store.emplace_back((size_t)coutp * cinp * kk, 0.f);
+        for (int oc = 0; oc < c->cout; ++oc)
+            for (int ic = 0; ic < c->cin; ++ic)
+                memcpy(&w[((size_t)oc * cinp + ic) * kk], &c->weight[((size_t)oc * c->cin + ic) * kk], sizeof(float) * kk);
+        rva_conv_weights q = *c;
+        q.weight = w.data(); q.cin = cinp; q.cout = coutp;
+        if (c->bias) {
+            std::vector<float> &b = pad_store.emplace_back((size_t)coutp, 0.f);
+            memcpy(b.data(), c->bias, sizeof(float) * c->cout);
+            q.bias = b.data();
+        }
+        return &pad_convs.emplace_back(q);
     }
     void push(Step &s, const char *desc_fmt, ...)
     {
@@ -406,7 +431,10 @@ struct Builder {
         const int rm4 = 4 * d.reg_max;
         int cb = c3 / 4 > rm4 ? c3 / 4 : rm4;
         if (cb < 16) cb = 16;
-        int cc = c3 > (d.nc < 100 ? d.nc : 100) ? c3 : (d.nc < 100 ? d.nc : 100);
+        const int cc_real = c3 > (d.nc < 100 ? d.nc : 100) ? c3 : (d.nc < 100 ? d.nc : 100);
+        // what the class branch runs with: interior width a multiple of 8 (16 where an fp32 convolution reads it), ncp logit columns
+        const int cal = p->f32 ? 16 : 8;
+        const int cc = (cc_real + cal - 1) / cal * cal, ncp = (d.nc + 7) / 8 * 8;
         p->A = h3 * w3 + h4 * w4 + h5 * w5;
         // module order: all box branches first, then all class branches
         const rva_conv_weights *box[3][3], *cls[3][3];
@@ -416,11 +444,13 @@ struct Builder {
             if (!box[l][0] || !box[l][1] || !box[l][2]) return false;
         }
         for (int l = 0; l < 3; ++l) {
-            cls[l][0] = take(chs[l], cc, 3, 1, "detect.cls.0"); cls[l][1] = take(cc, cc, 3, 1, "detect.cls.1"); cls[l][2] = take(cc, d.nc, 1, 1, "detect.cls.2");
+            cls[l][0] = take(chs[l], cc_real, 3, 1, "detect.cls.0"); cls[l][1] = take(cc_real, cc_real, 3, 1, "detect.cls.1");
+            cls[l][2] = take(cc_real, d.nc, 1, 1, "detect.cls.2");
             if (!cls[l][0] || !cls[l][1] || !cls[l][2]) return false;
+            cls[l][0] = padded(cls[l][0], chs[l], cc); cls[l][1] = padded(cls[l][1], cc, cc); cls[l][2] = padded(cls[l][2], cc, ncp);
         }
         if (next != d.n_convs) return fail("convolution list longer than the architecture");
-        p->fused_head = !p->f32 && cb % 64 == 0 && cc % 64 == 0 && rm4 == 64 && d.nc % 8 == 0;
+        p->fused_head = !p->f32 && cb % 64 == 0 && cc % 64 == 0 && rm4 == 64;
         const View feats[3] = {n3, m4, m5};
         const int hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
         const float strides[3] = {8.f, 16.f, 32.f};
@@ -440,7 +470,7 @@ struct Builder {
                 if (!conv1(box[l][1], first.sub(0, cb), b2, hs[l], ws[l], 1) || !head(box[l][2], b2, 1, hs[l], ws[l], a0, strides[l])) return false;
                 if (!conv1(cls[l][1], first.sub(cb, cc), k2, hs[l], ws[l], 1) || !head(cls[l][2], k2, 2, hs[l], ws[l], a0, strides[l])) return false;
             } else {
-                View bo = buf(m, rm4), ko = buf(m, d.nc);
+                View bo = buf(m, rm4), ko = buf(m, ncp);
                 if (!bo.base || !ko.base) return false;
                 if (!conv1(box[l][1], first.sub(0, cb), b2, hs[l], ws[l], 1) || !conv1(box[l][2], b2, bo, hs[l], ws[l], 0)) return false;
                 if (!conv1(cls[l][1], first.sub(cb, cc), k2, hs[l], ws[l], 1) || !conv1(cls[l][2], k2, ko, hs[l], ws[l], 0)) return false;
@@ -476,25 +506,21 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
         return rva_conv2d_nhwc_f16_sel(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act,
                                        variant, s.y0, s.y1, st);
     }
-    if (p->box32 && output) {             // the two launch forms that write box rows, with the side tensor of this output
-        float *boxes = (float *)((char *)output + p->box_off);
-        if (s.kind == K_HEAD && s.mode == 1)
-            return rva_conv1x1_head_box32_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, output, boxes, p->nc, p->A, s.a0, s.stride_px, variant, st);
-        if (s.kind == K_HEAD3)
-            return rva_yolo_head3_box32_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, boxes, n, s.hh, s.hw, p->nc, p->A, s.hs, st);
-    }
+    // the two launch forms that write box rows take the side tensor of this output (RVA_PLAN_BOX_F32), else none
+    float *boxes = p->box32 && output ? (float *)((char *)output + p->box_off) : nullptr;
     switch (s.kind) {
     case K_CONV: return rva_conv2d_nhwc_f16_sel(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant,
                                                 0, -1, st);     // variant 0 chooses as for the capacity
     case K_UPCAT: return rva_conv1x1_upcat_f16(c, s.in, s.ldi, s.c_in, s.in2, s.ldi2, s.c_in2, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, s.act, variant, st);
-    case K_HEAD: return rva_conv1x1_head_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, s.Cout, s.mode, output, p->nc, p->A, s.a0, s.stride_px, variant, st);
+    case K_HEAD: return rva_conv1x1_head_nc_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, s.Cout, s.mode, output, s.mode == 1 ? boxes : nullptr, p->nc,
+                                                p->A, s.a0, s.stride_px, variant, st);
     case K_PAIR32: return rva_c2f_pair32_f16(c, s.in, s.ldi, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, st);
     case K_STEM2: return rva_stem2_f16(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, st);
     case K_STEM: return rva_stem_conv_f16(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
     case K_SPPF3: return rva_sppf_pool3_nhwc_f16(c, s.in, s.ldi, s.out, s.out2, s.out3, s.ldo, n, s.H, s.W, s.Cin, st);
     case K_POOL5: return rva_maxpool5_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
     case K_UP2: return rva_upsample2x_nhwc_f16(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
-    case K_HEAD3: return rva_yolo_head3_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, n, s.hh, s.hw, p->nc, p->A, s.hs, st);
+    case K_HEAD3: return rva_yolo_head3_nc_f16(c, s.hb, s.hldb, s.hk, s.hldc, output, boxes, n, s.hh, s.hw, p->nc, p->A, s.hs, st);
     case K_CONV_F32: return rva_conv2d_nhwc_f32_v(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act, variant, st);
     case K_STEM_F32: return rva_stem_conv_f32(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
     case K_POOL5_F32: return rva_maxpool5_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
@@ -643,9 +669,9 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
 {
     if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
     *out = nullptr;
-    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc <= 0 ||
-        desc->nc % 8 || desc->reg_max != 16 || desc->n_convs <= 0)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: batch > 0, height and width multiples of 32, nc %% 8 == 0, reg_max 16");
+    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
+        desc->nc > 1024 || desc->reg_max != 16 || desc->n_convs <= 0)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024, reg_max 16");
     for (int i = 0; i < 5; ++i)
         if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: channel widths must be multiples of 8");
     RVA_HIP(ctx, hipSetDevice(ctx->device));

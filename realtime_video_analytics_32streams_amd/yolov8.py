@@ -289,10 +289,29 @@ def load_detector_state_dict(net: "YoloV8", sd) -> "YoloV8":
     return net
 
 
-def build_detector_net(scale: str = "s", seed: int = 0, weights: Optional[str] = None, nc: int = 80) -> YoloV8:
+_LAST_CLASS_CONV = ("detect.cls.0.2.weight", "model.22.cv3.0.2.weight", "22.cv3.0.2.weight")
+
+
+def checkpoint_class_count(sd) -> Optional[int]:
+    """Classes of a YOLOv8 state dict: the output channels of the class branch's last convolution (own or Ultralytics naming);
+    ``None`` where the dict has no such entry (the loader then reports what is wrong with it)."""
+    for key in _LAST_CLASS_CONV if hasattr(sd, "get") else ():
+        w = sd.get(key)
+        if w is not None and getattr(w, "dim", lambda: 0)() == 4:
+            return int(w.shape[0])
+    return None
+
+
+def build_detector_net(scale: str = "s", seed: int = 0, weights: Optional[str] = None, nc: Optional[int] = None) -> YoloV8:
     """Seeded random-init network (torch.manual_seed(seed), BN statistics randomised so that the
     folded convs are not trivial), or a local state-dict when ``weights`` names an existing file
-    (loaded with ``weights_only=True``; nothing is ever fetched by name)."""
+    (loaded with ``weights_only=True``; nothing is ever fetched by name).  ``nc=None``: the class count of that file (a
+    detector trained on its own class list), 80 without one; an explicit ``nc`` the file contradicts is the loader's shape error."""
+    sd = None
+    if weights and Path(weights).is_file():
+        sd = torch.load(weights, map_location="cpu", weights_only=True)     # never unpickles code
+    if nc is None:
+        nc = (checkpoint_class_count(sd) if sd is not None else None) or 80
     g = torch.Generator().manual_seed(seed)
     state = torch.random.get_rng_state()
     torch.manual_seed(seed)
@@ -306,8 +325,7 @@ def build_detector_net(scale: str = "s", seed: int = 0, weights: Optional[str] =
                 m.bias.data.copy_(torch.randn(m.num_features, generator=g) * 0.1)
     finally:
         torch.random.set_rng_state(state)
-    if weights and Path(weights).is_file():
-        sd = torch.load(weights, map_location="cpu", weights_only=True)     # never unpickles code
+    if sd is not None:
         load_detector_state_dict(net, sd)
     net.eval()
     return net
@@ -319,10 +337,20 @@ def density_shifts(class_logits: torch.Tensor, conf_thr: float, target_per_image
     """The two class-bias shifts (class 0, classes >= 1) under which about ``target_per_image`` anchors per image clear
     ``conf_thr`` with the reference's score rule (score = p[class0] * max_k p[class k>=1]).  Class 0
     acts as "objectness": the anchors above ``objectness_quantile`` of its logit are made confident (p = 0.9), the other
-    shift is bisected.  Nothing is modified."""
+    shift is bisected.  A one-class head (5 rows) is read as plain scores by the reference: its one shift is bisected and
+    returned first, the second is 0.  Nothing is modified."""
     z = class_logits.float()
-    z0, zr = z[:, 0], z[:, 1:].max(1).values
     want = target_per_image * z.shape[0]
+    if z.shape[1] == 1:
+        lo, hi = -40.0, 40.0
+        for _ in range(iters):
+            mid = 0.5 * (lo + hi)
+            if int((torch.sigmoid(z[:, 0] + mid) >= conf_thr).sum()) > want:
+                hi = mid
+            else:
+                lo = mid
+        return 0.5 * (lo + hi), 0.0
+    z0, zr = z[:, 0], z[:, 1:].max(1).values
 
     def count(s0, sr):
         return int(((torch.sigmoid(z0 + s0) * torch.sigmoid(zr + sr)) >= conf_thr).sum())
