@@ -575,6 +575,62 @@ int rva_yolov8_plan_primed_images(const rva_yolov8_plan *plan);
 int rva_yolov8_plan_step_rows(const rva_yolov8_plan *plan, int step, int32_t *y0, int32_t *y1);
 
 /* ----------------------------------------------------------------------------------------------
+ * YOLOv5 (v6.0 - v7.0 architecture, n / s / m / l; `model_type: yolov5`, whose objectness rule the reference's post-process
+ * applies, detector.py:294-305) as a second graph builder for the SAME plan object: every rva_yolov8_plan_* entry point above
+ * works on a plan made by rva_yolov5_plan_create unchanged.  fp16 only (RVA_PLAN_F32: RVA_ERR_ARG); RVA_PLAN_BOX_F32 and
+ * RVA_PLAN_NO_CIN_PAD as above; the other flags have no effect.  There are no detect lanes: _run_lanes is _run.
+ * Output: fp16 [batch, 5+nc, anchors], anchors = 3 * (H/8*W/8 + H/16*W/16 + H/32*W/32), anchor index = level offset +
+ * a * h * w + y * w + x -- the transpose of the exported graph's [batch, anchors, 5+nc], which rva_postprocess_batch reads
+ * through its strides.  _info reports out_rows = 5 + nc.
+ *
+ * Graph: b0 stem 6x6 s2 p2 | b1 3x3 s2 | b2 C3 | b3 3x3 s2 | b4 C3 | b5 3x3 s2 | b6 C3 | b7 3x3 s2 | b8 C3 | b9 SPPF | h10 1x1 |
+ *   h13 C3(cat[up(h10), p4]) | h14 1x1 | h17 C3(cat[up(h14), p3]) | h18 3x3 s2 | h20 C3(cat[h18, h14]) | h21 3x3 s2 |
+ *   h23 C3(cat[h21, h10]) | per level Conv2d(ch, 3 * (5 + nc), 1) fused with the anchor decode (rva_conv1x1_head5_f16).
+ * Module order of `convs`: b0, b1, C3(b2), b3, C3(b4), b5, C3(b6), b7, C3(b8), SPPF cv1 cv2, h10, C3(h13), h14, C3(h17), h18,
+ *   C3(h20), h21, C3(h23), detect.m[0..2];  C3(x) = cv1, cv2, cv3, then cv1 (1x1) cv2 (3x3) of every bottleneck.
+ * C3 inside the plan: cv1 and cv2 read the same input and run as ONE launch that writes [cv1 out | cv2 out]; the last
+ *   bottleneck writes behind them, and cv3 reads [cv2 out | m out] with its input channels swapped half for half on the host --
+ *   the concatenation never materialises, and only the summation order of cv3 differs from the module's.
+ *
+ * rva_stem6_conv_f16: the stem, 6x6 stride 2 pad 2 + bias + SiLU on the PLANAR tensor K1 writes ([batch,3,H,W] fp16), NHWC fp16
+ *   out [batch, H/2, W/2, Cout] with row stride ldo.  weights fp16 [64][128]: row = output channel (zero beyond Cout), column
+ *   k = (c*6 + ky)*6 + kx -- the checkpoint's own [Cout][3][6][6] order -- zero for k >= 108; bias fp32 [Cout].  Cout % 8 == 0,
+ *   8 <= Cout <= 64, W % 8 == 0, H even, ldo % 8 == 0.  fp32 accumulation of the 108 products in four MFMA steps of 32, one
+ *   rounding to fp16 after SiLU.  _rows: output rows [y0, y1) only (y1 < 0 = the last row), bit-identical to them; output row r
+ *   reads input rows 2r-2 .. 2r+3 (rva_conv_rows_through_pad(6, 2, 2, ...)).
+ * rva_conv_rows_through_pad: rva_conv_rows_through for any k >= 1, stride >= 1 and 0 <= pad < k.
+ * rva_conv1x1_head5_f16: one level's Conv2d(Cin, 3 * (5 + nc), 1) fused with the decode, written straight into
+ *   out[batch, 5+nc, anchors_total] at anchors [anchor_offset, anchor_offset + 3*H*W).  weights fp16
+ *   [rva_conv_cout_pad(Cout)][1][Cin] and bias fp32 [rva_conv_cout_pad(Cout)] with Cout = roundup(3 * (5 + nc), 8), rows >=
+ *   3 * (5 + nc) zero (never stored); channel a * (5 + nc) + j = anchor a, entry j.  anchors_px: DEVICE float [6], the level's
+ *   three (w, h) pairs in pixels.  Rounding points: the logit z (fp32 accumulator + bias) is rounded to fp16 once; then in fp32,
+ *   in this order, y = 1 / (1 + exp(-z)) (v_exp_f32 / v_rcp_f32); entry 0: ((y * 2 - 0.5) + x) * stride_px, entry 1 the same with
+ *   y of the grid; entries 2 / 3: t = y * 2, (t * t) * anchor w / h; entries >= 4: y; each rounded once to fp16.  boxes32 (NULL =
+ *   none): fp32 [batch, 4, anchors_total] receives the fp32 values of entries 0-3 before that last rounding, so (half)boxes32 ==
+ *   rows 0-3 bit for bit; nothing outside the level's anchor range is written in either tensor.  1 <= nc <= 1024,
+ *   Cin % 64 == 0; variant 0 or 33..39.  No split-K, no atomics: bit-identical across batch sizes.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_yolov5_desc {
+    int32_t batch, height, width;     /* input tensor; height and width multiples of 32 */
+    int32_t widths[5];                /* c1..c5 (YOLOv5s: 32 64 128 256 512); c1 <= 64, c3 and c4 multiples of 64 */
+    int32_t depth_backbone[4];        /* bottlenecks of the C3 blocks b2, b4, b6, b8 (YOLOv5s: 1 2 3 1) */
+    int32_t depth_head;               /* bottlenecks of h13, h17, h20, h23 (YOLOv5s: 1) */
+    int32_t nc;                       /* classes, 1..1024 */
+    float anchors[18];                /* [level][anchor][(w, h)] in input pixels */
+    int32_t n_convs;                  /* length of `convs` */
+    int32_t flags;
+} rva_yolov5_desc;
+int rva_yolov5_plan_create(rva_ctx *ctx, const rva_yolov5_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out);
+int rva_stem6_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
+                       int batch, int H, int W, int Cout, rva_stream_t stream);
+int rva_stem6_conv_f16_rows(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
+                            int batch, int H, int W, int Cout, int y0, int y1, rva_stream_t stream);
+int rva_conv_rows_through_pad(int k, int stride, int pad, int H_in, int lo, int hi, int32_t *out_lo, int32_t *out_hi);
+int rva_conv1x1_head5_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                          int Cin, int nc, const float *anchors_px, void *out, float *boxes32, int anchors_total, int anchor_offset,
+                          float stride_px, int variant, rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The CNN-LSTM clip network as ONE fp32 object -- replaces the network call of the reference's CNN-LSTM head
  * (the inference call of CNNLSTMDetector._predict_sequence, temporal_detector.py:382-388; the network is
  * DummyCNNLSTM of scripts/convert_temporal_model_to_onnx.py:34-88) and its top-5 (temporal_detector.py:392-424), for `half:

@@ -49,6 +49,13 @@ class YoloV8Desc(C.Structure):
                 ("n_convs", C.c_int32), ("flags", C.c_int32)]
 
 
+class YoloV5Desc(C.Structure):
+    """``rva_yolov5_desc`` (include/rva.h)."""
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("widths", C.c_int32 * 5),
+                ("depth_backbone", C.c_int32 * 4), ("depth_head", C.c_int32), ("nc", C.c_int32), ("anchors", C.c_float * 18),
+                ("n_convs", C.c_int32), ("flags", C.c_int32)]
+
+
 class ConvWeights(C.Structure):
     """``rva_conv_weights`` (include/rva.h): one convolution in the checkpoint's own fp32 layout."""
     _fields_ = [("weight", C.POINTER(C.c_float)), ("bias", C.POINTER(C.c_float)), ("cout", C.c_int32), ("cin", C.c_int32),
@@ -264,6 +271,12 @@ def lib() -> C.CDLL:
         "rva_yolov8_plan_run_lanes_n": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
         "rva_yolov8_plan_run_range_n": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
         "rva_yolov8_plan_primed_images": (C.c_int, [_P]),
+        "rva_yolov5_plan_create": (C.c_int, [_P, C.POINTER(YoloV5Desc), C.POINTER(ConvWeights), C.POINTER(_P)]),
+        "rva_stem6_conv_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_stem6_conv_f16_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_conv_rows_through_pad": (C.c_int, [C.c_int] * 6 + [i32p, i32p]),
+        "rva_conv1x1_head5_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                            C.c_int, C.c_int, C.c_float, C.c_int, _P]),
         "rva_cnnlstm_plan_create": (C.c_int, [_P, C.POINTER(CnnLstmDesc), C.POINTER(CnnLstmWeights), C.POINTER(_P)]),
         "rva_cnnlstm_plan_destroy": (None, [_P]),
         "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
@@ -347,6 +360,7 @@ EXPORTS = [
     "rva_resnet_plan_run", "rva_resnet_plan_run_post", "rva_resnet_plan_stage", "rva_resnet_f16_plan_create", "rva_resnet_f16_plan_destroy",
     "rva_resnet_f16_plan_info", "rva_resnet_f16_plan_run", "rva_resnet_f16_plan_run_post", "rva_resnet_f16_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
+    "rva_yolov5_plan_create", "rva_stem6_conv_f16", "rva_stem6_conv_f16_rows", "rva_conv_rows_through_pad", "rva_conv1x1_head5_f16",
 ]
 
 

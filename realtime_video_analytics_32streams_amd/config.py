@@ -19,11 +19,19 @@ resnet_plan.py; this head always runs float32, ``half`` has no effect on it).  T
 configured precision, or construction fails with ``ValueError`` (an ``infer_fn`` still overrides everything):
 
     head                    half: false                       half: true
-    yolov5 / yolov8         as plan: engine "fused-f32"       as plan: engine "fused"
+    yolov8 architecture     as plan: engine "fused-f32"       as plan: engine "fused"
+    yolov5 architecture     ValueError (no fp32 plan; also    as plan: engine "fused" (the fp16 YOLOv5 plan,
+                            under plan; auto: PyTorch-ROCm)   engine.FusedYoloV5)
     cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only) unless hip_lstm_fp16: true
     3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only) unless hip_clip_fp16: true
     conv_gru                ValueError (the reference defines no architecture, so there is no plan)
     resnet                  ValueError (no hand-written plan) ValueError (no hand-written plan) unless hip_resnet_fp16: true
+
+Which YOLO architecture a ``yolov5`` / ``yolov8`` detector builds is no key of its own: it follows what the user handed over
+(``detector.detector_architecture``).  YOLOv5 (v6.0 - v7.0, anchor-based head) when ``model_path`` is an existing state dict with
+the YOLOv5 detect convolution (``model.24.m.0.weight``), or when ``model_type`` is ``yolov5`` and the file name starts with
+``yolov5<n|s|m|l>`` while no such file exists (seeded weights, logged as such); YOLOv8 in every other case, as before -- ``model_type:
+yolov5`` with the default ``yolov8n.pt``, every ``yolov8*`` name, and the ``yolov5*u`` names (anchor-free re-exports with the v8 head).
 
 ``hip_clip_fp16`` (a bool, default ``false``: what a reference YAML gets) opts the 3D-CNN head into its fp16 plan: with
 ``hip_engine: native``, ``model_type: 3d_cnn`` / ``slow_fast`` and ``half: true`` the network runs as engine ``"clip3d-f16"``

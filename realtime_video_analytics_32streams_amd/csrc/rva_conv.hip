@@ -65,8 +65,13 @@ struct ConvArgs {
     int CoutPad;
     // k_conv_gbig<..., HEAD>: the detect head's last 1x1 convolutions decode straight into out[B, 4+nc, A]
     __half *hout; int hmode, hnc, hA, ha0, hW, hHW; float hstride;   // hmode 1 = box branch (DFL + dist2bbox), 2 = class branch (sigmoid; Cout = roundup(hnc, 8), class rows < hnc stored)
-    const __half *in2; int ldi2, c_split;   // k_conv_gbig<..., UP>: `in` = low-res tensor (nearest 2x upsampled on the fly,
-                                            // channels [0, c_split)), `in2` = full-res tensor (channels [c_split, Cin))
+                                                                     // hmode 3 = YOLOv5 level (anchor decode; Cout = roundup(3 * (5 + hnc), 8), out[B, 5+hnc, hA])
+    union {
+        const __half *in2;    // k_conv_gbig<..., UP>: `in` = low-res tensor (nearest 2x upsampled on the fly, channels [0, c_split)),
+                              // `in2` = full-res tensor (channels [c_split, Cin))
+        const float *hanc;    // k_conv_gbig<..., HEAD>, hmode 3: the level's three anchors (w, h) in pixels, device float [6]
+    };
+    int ldi2, c_split;
     int H, W, Cin, CinPad, Ho, Wo, Cout, stride, M, act, n_tiles, m_tiles;   // CinPad = Cin rounded up to 32 (weight rows are zero-padded)
     // k_conv_gbig, output row window [wy0, wy0 + wrows) of every image (rva_conv2d_nhwc_f16_rows): M counts the window's pixels
     // only, raster position m decodes to row wy0 + (m % (wrows * Wo)) / Wo.  The whole image: wy0 = 0, wrows = Ho.
@@ -891,6 +896,142 @@ __global__ void __launch_bounds__(256) k_stem(StemArgs a, const __half *__restri
         STAMP(6);
         // the next iteration's first barrier (after the tile fill) also orders these stage reads before the
         // next im2col writes; the tile buffer itself is not touched by the output copy
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// YOLOv5 stem: 6x6 stride-2 pad-2 conv on planar [B,3,H,W] fp16, Cout <= 64, NHWC out.  Structure of k_stem: persistent
+// blocks, a tile = 8 x 32 output pixels of one image (of the row window [y0, y1)), the 20 x 68 x 3 input patch of the next tile
+// prefetched into registers (three 16-byte loads per thread) under the current tile's MFMAs, weights [64][128] resident in LDS,
+// output staged and stored as whole NHWC rows.  Unlike k_stem there is no im2col pass: with K in the natural order
+// k = (c*6 + ky)*6 + kx the six taps of a patch row are three aligned dwords (input x of output pixel lx is 2 lx - 2 + kx and
+// the patch starts at x = 64 tx - 8, so half 2 lx + 6 + kx), and the eight halfs a lane owns of a 16x16x32 B fragment are four
+// such dwords, read straight from the patch (the 16 lanes of a fragment row read 16 consecutive dwords).  K = 108 padded to
+// 128 = four MFMA steps per 16x16 block.  Zero padding is decided per 16-byte chunk in the whole image (W % 8 == 0).
+struct Stem6Args {
+    const __half *in; const float *bias; __half *out;
+    int B, H, W, Ho, Wo, Cout, ldo, y0, y1;
+};
+
+__global__ void __launch_bounds__(256) k_stem6(Stem6Args a, const __half *__restrict__ gw)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int RS = 88, PR = 20, WROW = 136;                                 // halfs per patch row (80 used), patch rows, halfs per weight row
+    __half *tile = (__half *)smem;                                              // [3][PR][RS]
+    __half *wl = tile + 3 * PR * RS;                                            // [64][WROW]
+    __half *stage = wl + 64 * WROW;                                             // [256][Cout + 8]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tiles_x = (a.Wo + 31) >> 5, tiles_y = (a.y1 - a.y0 + 7) >> 3;
+    const int tiles_img = tiles_x * tiles_y, total = tiles_img * a.B;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                               // [64][128] halfs = 1024 16-byte chunks
+        const int q = tid + 256 * k;
+        *reinterpret_cast<u4 *>(wl + (q >> 4) * WROW + (q & 15) * 8) = *reinterpret_cast<const u4 *>(gw + q * 8);
+    }
+    const int nblk = (a.Cout + 15) >> 4;
+    float bv[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int co = 16 * i + (lane >> 4) * 4 + u;
+            bv[i][u] = co < a.Cout ? a.bias[co] : 0.f;
+        }
+    // the lane's four dwords of K-step s: dword index (s*4 + g)*4 + e of the 54 (= 18 patch rows x 3) that hold taps, g = lane >> 4
+    int koff[4][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int idx = (s * 4 + (lane >> 4)) * 4 + e;
+            const int jr = idx / 3, d = idx - jr * 3;                           // jr = c*6 + ky
+            koff[s][e] = idx < 54 ? ((jr / 6) * PR + (jr % 6)) * RS + 6 + 2 * d : -1;
+        }
+    u4 pv[3];
+    auto prefetch = [&](int t) {
+        const int bb = t / tiles_img, r2 = t - bb * tiles_img, tyy = r2 / tiles_x, txx = r2 - tyy * tiles_x;
+        const int x00 = txx * 64 - 8, iy0 = (a.y0 + tyy * 8) * 2 - 2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int q = tid + 256 * k;
+            const int row = q / 10, cx = q - row * 10;
+            const int c = row / PR, r = row - c * PR;
+            const int iy = iy0 + r, x0 = x00 + cx * 8;
+            pv[k] = u4{0u, 0u, 0u, 0u};
+            if (q < 3 * PR * 10 && (unsigned)iy < (unsigned)a.H && (unsigned)x0 < (unsigned)a.W)
+                pv[k] = *reinterpret_cast<const u4 *>(a.in + ((size_t)(bb * 3 + c) * a.H + iy) * a.W + x0);
+        }
+    };
+    int t = blockIdx.x;
+    if (t < total) prefetch(t);
+    for (; t < total; t += gridDim.x) {
+        const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / tiles_x, tx = r2 - ty * tiles_x;
+        const int ox0 = tx * 32, oy0 = a.y0 + ty * 8;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int q = tid + 256 * k;
+            const int row = q / 10, cx = q - row * 10;
+            if (q < 3 * PR * 10) *reinterpret_cast<u4 *>(tile + row * RS + cx * 8) = pv[k];
+        }
+        __syncthreads();                                    // (also: the weights are in place; the previous tile's stage has been read)
+        if (t + (int)gridDim.x < total) prefetch(t + gridDim.x);
+        f4 acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+        int pb[4];                                          // the lane's pixel of fragment j: px = wv*64 + 16 j + (lane & 15)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int px = wv * 64 + 16 * j + (lane & 15);
+            pb[j] = (px >> 5) * 2 * RS + (px & 31) * 2;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            h8 bf[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                u4 d;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) d[e] = koff[s][e] >= 0 ? *reinterpret_cast<const uint32_t *>(tile + pb[j] + koff[s][e]) : 0u;
+                bf[j] = __builtin_bit_cast(h8, d);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < nblk) {
+                    const h8 af = *reinterpret_cast<const h8 *>(wl + (size_t)(16 * i + (lane & 15)) * WROW + s * 32 + (lane >> 4) * 8);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[i][j], 0, 0, 0);
+                }
+            }
+        }
+        const int srow = a.Cout + 8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < nblk) {
+                const int co = 16 * i + (lane >> 4) * 4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int px = wv * 64 + 16 * j + (lane & 15);
+                    __half2 lo = __floats2half2_rn(silu_f(acc[i][j][0] + bv[i][0]), silu_f(acc[i][j][1] + bv[i][1]));
+                    __half2 hi = __floats2half2_rn(silu_f(acc[i][j][2] + bv[i][2]), silu_f(acc[i][j][3] + bv[i][3]));
+                    uint2 pk;
+                    pk.x = *reinterpret_cast<uint32_t *>(&lo);
+                    pk.y = *reinterpret_cast<uint32_t *>(&hi);
+                    if (co < a.Cout) *reinterpret_cast<uint2 *>(stage + (size_t)px * srow + co) = pk;
+                }
+            }
+        }
+        __syncthreads();                                    // stage complete; every wave is done reading the patch
+        const int cpr = a.Cout >> 3;
+        for (int q = tid; q < 256 * cpr; q += 256) {
+            const int px = q / cpr, pc = q - px * cpr;
+            const int ox = ox0 + (px & 31), oy = oy0 + (px >> 5);
+            if (ox < a.Wo && oy < a.y1)
+                *reinterpret_cast<uint4 *>(a.out + ((size_t)(b * a.Ho + oy) * a.Wo + ox) * a.ldo + pc * 8) =
+                    *reinterpret_cast<const uint4 *>(stage + (size_t)px * srow + pc * 8);
+        }
+        // the next iteration's barrier (after the patch fill) orders these stage reads before the next stage writes
     }
 }
 
@@ -2268,6 +2409,40 @@ __global__ void __launch_bounds__(512)
     if constexpr (HEAD) {
         constexpr int SROW = BN + 8;
         const __half *stage = (const __half *)smem;                // [BM][SROW], as stage_tile wrote it
+        if (a.hmode == 3) {
+            // YOLOv5 level: channel c = an * (5 + nc) + j of the staged logits (rounded to fp16 by stage_tile) is entry j of anchor
+            // an at this pixel; every entry is decoded on its own, in fp32 and in this order, and rounded once into
+            // out[b][j][ha0 + an * hHW + i].  Work item = (pixel row, 8 channels); consecutive threads take consecutive pixels, so
+            // the two-byte stores of a wave run along the contiguous anchor axis.
+            const int no = 5 + a.hnc, creal = 3 * no;
+            const float aw[3] = {a.hanc[0], a.hanc[2], a.hanc[4]}, ah[3] = {a.hanc[1], a.hanc[3], a.hanc[5]};
+            const int groups = (min(BN, a.Cout - n0) + 7) >> 3;
+            for (int q = tid; q < BM * groups; q += 512) {
+                const int cg = q / BM, r = q - cg * BM;
+                const int m = P0 + r;
+                if (m >= a.M) continue;
+                const int b = m / a.hHW, i = m - b * a.hHW;
+                const float gx = (float)(i % a.hW), gy = (float)(i / a.hW);
+                const uint4 qv = *reinterpret_cast<const uint4 *>(stage + (size_t)r * SROW + cg * 8);
+                const __half *zh = reinterpret_cast<const __half *>(&qv);
+                const int c0 = n0 + cg * 8;
+                int an = c0 / no, j = c0 - an * no;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    if (c0 + e < creal) {
+                        const float y = __builtin_amdgcn_rcpf(1.0f + __expf(-__half2float(zh[e])));
+                        float v = y;
+                        if (j < 2) v = (y * 2.0f - 0.5f + (j == 0 ? gx : gy)) * a.hstride;
+                        else if (j < 4) { const float t2 = y * 2.0f; v = t2 * t2 * (j == 2 ? (an == 0 ? aw[0] : an == 1 ? aw[1] : aw[2]) : (an == 0 ? ah[0] : an == 1 ? ah[1] : ah[2])); }
+                        const size_t at = (size_t)a.ha0 + (size_t)an * a.hHW + i;
+                        a.hout[((size_t)b * no + j) * a.hA + at] = __float2half_rn(v);
+                        if (j < 4 && a.hbox) a.hbox[((size_t)b * 4 + j) * a.hA + at] = v;
+                    }
+                    if (++j == no) { j = 0; ++an; }
+                }
+            }
+            return;
+        }
         // thread = pixel row of the staged tile (values rounded to fp16 exactly as the stand-alone path stores them);
         // same operation order as head_anchor, so the result is bit-identical to conv -> k_head
         for (int r = tid; r < BM; r += 512) {
@@ -3817,6 +3992,57 @@ int rva_conv1x1_head_nc_f16(rva_ctx *ctx, const void *in, int ldi, const void *w
 {
     return conv1x1_head(ctx, in, ldi, weights, bias, batch, H, W, Cin, Cout, mode, out, boxes32, nc, anchors_total, anchor_offset, stride_px, variant,
                         stream_, true);
+}
+
+int rva_conv1x1_head5_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
+                          int Cin, int nc, const float *anchors_px, void *out, float *boxes32, int anchors_total, int anchor_offset,
+                          float stride_px, int variant, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!in || !weights || !bias || !out || !anchors_px || batch <= 0 || H <= 0 || W <= 0 || H > 2000 || W > 2000 || Cin <= 0 || Cin % 64 ||
+        ldi % 8 || ldi < Cin || nc < 1 || nc > 1024 || anchor_offset < 0 || (long)anchor_offset + 3l * H * W > anchors_total ||
+        ((uintptr_t)in | (uintptr_t)weights) % 16 || (uintptr_t)out % 2 || ((uintptr_t)boxes32 | (uintptr_t)anchors_px | (uintptr_t)bias) % 4)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_conv1x1_head5_f16: Cin %% 64 == 0, ldi %% 8 == 0, 1 <= nc <= 1024, the level's 3*H*W anchors inside "
+                                          "the anchor range, 16-byte aligned input and weights");
+    const int Cout = (3 * (5 + nc) + 7) / 8 * 8;
+    ConvArgs a{};
+    a.in = (const __half *)in; a.ldi = ldi; a.w = (const __half *)weights; a.bias = bias; a.out = nullptr; a.ldo = 0;
+    a.H = H; a.W = W; a.Cin = Cin; a.CinPad = Cin; a.Cout = Cout; a.stride = 1; a.act = 0; a.Ho = H; a.Wo = W; a.M = batch * H * W;
+    a.CoutPad = rva_ceil_div(Cout, 64) * 64; a.wy0 = 0; a.wrows = H;
+    a.hout = (__half *)out; a.hmode = 3; a.hnc = nc; a.hA = anchors_total; a.ha0 = anchor_offset; a.hW = W; a.hHW = H * W;
+    a.hstride = stride_px;
+    a.hbox = boxes32;
+    a.hanc = anchors_px;
+    return launch_gather64_1x1<false, true>(ctx, "rva_conv1x1_head5_f16", a, variant, (hipStream_t)stream_);
+}
+
+int rva_stem6_conv_f16_rows(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
+                            int batch, int H, int W, int Cout, int y0, int y1, rva_stream_t stream_)
+{
+    if (!ctx) return RVA_ERR_ARG;
+    if (!in_planar || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || Cout < 8 || Cout % 8 || Cout > 64 || ldo % 8 || ldo < Cout ||
+        W % 8 || H % 2 || ((uintptr_t)in_planar | (uintptr_t)weights | (uintptr_t)out) % 16)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16: Cout %% 8 == 0 and <= 64, ldo %% 8 == 0, W %% 8 == 0, even H, 16-byte aligned tensors");
+    Stem6Args a{(const __half *)in_planar, bias, (__half *)out, batch, H, W, H / 2, W / 2, Cout, ldo, 0, 0};
+    if (y1 < 0) y1 = a.Ho;
+    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
+    a.y0 = y0; a.y1 = y1;
+    const long total_tiles = (long)rva_ceil_div(a.Wo, 32) * rva_ceil_div(y1 - y0, 8) * batch;
+    if (total_tiles >= (1l << 30)) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16: tensor too large");
+    const size_t smem = (size_t)(3 * 20 * 88 + 64 * 136 + 256 * (Cout + 8)) * 2;      // 39 .. 63 KB
+    // persistent: two blocks per CU.  As many as LDS holds (three at Cout = 32) measured slower: 124 against 115 us for
+    // 32 x 640 x 640 -> 320 x 320 x 32 (profiles/yolov5_plan.json is the two-block form)
+    int grid = 2 * rva_num_cus(ctx);
+    if (grid > total_tiles) grid = (int)total_tiles;
+    k_stem6<<<grid, 256, smem, (hipStream_t)stream_>>>(a, (const __half *)weights);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
+int rva_stem6_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
+                       int batch, int H, int W, int Cout, rva_stream_t stream_)
+{
+    return rva_stem6_conv_f16_rows(ctx, in_planar, weights, bias, out, ldo, batch, H, W, Cout, 0, -1, stream_);
 }
 
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }

@@ -43,7 +43,7 @@
 namespace {
 
 enum StepKind { K_CONV, K_UPCAT, K_HEAD, K_STEM2, K_STEM, K_SPPF3, K_POOL5, K_UP2, K_HEAD3, K_PAIR32,
-                K_CONV_F32, K_STEM_F32, K_POOL5_F32, K_UP2_F32, K_HEAD_F32 };
+                K_CONV_F32, K_STEM_F32, K_POOL5_F32, K_UP2_F32, K_HEAD_F32, K_STEM6, K_HEAD5 };
 
 struct View {           // a channel slice of an NHWC buffer (es = bytes per element: 2 fp16, 4 fp32)
     char *base = nullptr; int ld = 0, off = 0, ch = 0, es = 2;
@@ -76,6 +76,7 @@ struct rva_yolov8_plan {
     rva_ctx *ctx = nullptr;
     rva_yolov8_desc d{};
     int B = 0, H = 0, W = 0, nc = 0, A = 0;
+    int head_rows = 0;                    // rows of the head tensor: 4 + nc (YOLOv8), 5 + nc (YOLOv5)
     std::vector<void *> allocs;
     std::vector<Step> steps;
     std::vector<Tunable> tunables;
@@ -257,11 +258,11 @@ struct Builder {
     {
         return c && conv(&c, 1, src, dst, h, w, act, res);
     }
-    bool upcat(const rva_conv_weights *c, View low, View skip, View dst, int h, int w)
+    bool upcat(const rva_conv_weights *c, View low, View skip, View dst, int h, int w) { return c && upcat(&c, 1, low, skip, dst, h, w); }
+    bool upcat(const rva_conv_weights *const *cv, int n, View low, View skip, View dst, int h, int w)
     {
-        if (!c) return false;
         Step s{}; s.kind = K_UPCAT;
-        if (!pack(&c, 1, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
+        if (!pack(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
         if (s.k != 1 || s.stride != 1 || s.Cin != low.ch + skip.ch || s.Cout != dst.ch) return fail("upsample + concat convolution does not fit");
         s.in = low.ptr(); s.ldi = low.ld; s.c_in = low.ch; s.in2 = skip.ptr(); s.ldi2 = skip.ld; s.c_in2 = skip.ch;
         s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.act = 1;
@@ -310,6 +311,135 @@ struct Builder {
             if (!conv1(b2, tmp, cat.sub((2 + i) * c, c), h, w, 1, shortcut ? &x : nullptr)) return false;
         }
         return conv1(cv2, cat, dst, h, w, 1);
+    }
+
+    // YOLOv5's C3: src is one view, or (low, skip) standing for cat([upsample2x(low), skip]).  cv1 and cv2 read the same input:
+    // one sibling launch writes cat[0, 2c) = [cv1 out | cv2 out]; the bottlenecks x <- x + cv2_3x3(cv1_1x1(x)) start from cv1 out,
+    // the last one writes cat[2c, 3c), and cv3 reads cat[c, 3c) = [cv2 out | m out] with the halves of its input channels swapped
+    // on the host (the module concatenates [m out | cv2 out]).
+    bool c3(int c1, int c2, int n, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w, const char *what)
+    {
+        const int c = c2 / 2;
+        const long m = (long)p->B * h * w;
+        const rva_conv_weights *cv[2] = {take(c1, c, 1, 1, what), take(c1, c, 1, 1, what)};
+        const rva_conv_weights *cv3 = take(2 * c, c2, 1, 1, what);
+        if (!cv[0] || !cv[1] || !cv3 || n < 1) return n < 1 ? fail("a C3 block needs at least one bottleneck") : false;
+        View cat = buf(m, 3 * c);
+        if (!cat.base) return false;
+        if (low) { if (!upcat(cv, 2, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
+        else if (!conv(cv, 2, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
+        View x = cat.sub(0, c);
+        for (int i = 0; i < n; ++i) {
+            const rva_conv_weights *b1 = take(c, c, 1, 1, what), *b2 = take(c, c, 3, 1, what);
+            // intermediate and output of every bottleneck in buffers of their own: with row windows a step rewrites part of its
+            // output only, and the rest must still be what THIS bottleneck left there (see c2f)
+            View tmp = buf(m, c), y = i == n - 1 ? cat.sub(2 * c, c) : buf(m, c);
+            if (!tmp.base || !y.base) return false;
+            if (!conv1(b1, x, tmp, h, w, 1) || !conv1(b2, tmp, y, h, w, 1, shortcut ? &x : nullptr)) return false;
+            x = y;
+        }
+        if (!cv3->weight) return fail("convolution without weights");
+        std::vector<float> &sw = pad_store.emplace_back((size_t)c2 * 2 * c, 0.f);
+        for (int oc = 0; oc < c2; ++oc)
+            for (int ic = 0; ic < 2 * c; ++ic) sw[(size_t)oc * 2 * c + ic] = cv3->weight[(size_t)oc * 2 * c + (ic + c) % (2 * c)];
+        rva_conv_weights q = *cv3;
+        q.weight = sw.data();
+        return conv1(&pad_convs.emplace_back(q), cat.sub(c, 2 * c), dst, h, w, 1);
+    }
+
+    bool build_v5(const float *anchors)
+    {
+        const rva_yolov8_desc &d = p->d;
+        const int B = d.batch, H = d.height, W = d.width;
+        const int c1 = d.widths[0], c2 = d.widths[1], c3w = d.widths[2], c4 = d.widths[3], c5 = d.widths[4];
+        const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4, h3 = H / 8, w3 = W / 8, h4 = H / 16, w4 = W / 16, h5 = H / 32, w5 = W / 32;
+        const int nh = d.depth_head;
+        if (c1 > 64) return fail("stem wider than 64 channels");
+        if (c3w % 64 || c4 % 64 || c5 % 64) return fail("YOLOv5 plan: c3, c4 and c5 must be multiples of 64 (the upsample + concat and head kernels)");
+        const rva_conv_weights *b0 = take(3, c1, 6, 2, "b0");
+        if (!b0 || !b0->weight) return fail("b0: no stem convolution");
+        {   // stem (planar input from K1): weights [64][128] fp16 in the checkpoint's own (c, ky, kx) order, zero-padded
+            std::vector<_Float16> sw(64 * 128, (_Float16)0.f);
+            std::vector<float> sb(64, 0.f);
+            for (int co = 0; co < c1; ++co) {
+                for (int k = 0; k < 108; ++k) sw[co * 128 + k] = (_Float16)b0->weight[(size_t)co * 108 + k];
+                if (b0->bias) sb[co] = b0->bias[co];
+            }
+            Step s{}; s.kind = K_STEM6;
+            const void *db = nullptr;
+            if (!upload(sw.data(), sw.size() * 2, &s.w) || !upload(sb.data(), sb.size() * 4, &db)) return false;
+            s.b = (const float *)db;
+            View x0 = buf((long)B * h1 * w1, c1);
+            if (!x0.base) return false;
+            s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
+            push(s, nullptr);
+            View x1 = buf((long)B * h2 * w2, c2), x2 = buf((long)B * h2 * w2, c2);
+            if (!x1.base || !x2.base || !conv1(take(c1, c2, 3, 2, "b1"), x0, x1, h1, w1, 1)) return false;
+            if (!c3(c2, c2, d.depth_backbone[0], true, &x1, nullptr, nullptr, x2, h2, w2, "b2")) return false;
+            View t3 = buf((long)B * h3 * w3, c3w), p3 = buf((long)B * h3 * w3, c3w);
+            if (!t3.base || !p3.base || !conv1(take(c2, c3w, 3, 2, "b3"), x2, t3, h2, w2, 1)) return false;
+            if (!c3(c3w, c3w, d.depth_backbone[1], true, &t3, nullptr, nullptr, p3, h3, w3, "b4")) return false;
+            View t4 = buf((long)B * h4 * w4, c4), p4 = buf((long)B * h4 * w4, c4);
+            if (!t4.base || !p4.base || !conv1(take(c3w, c4, 3, 2, "b5"), p3, t4, h3, w3, 1)) return false;
+            if (!c3(c4, c4, d.depth_backbone[2], true, &t4, nullptr, nullptr, p4, h4, w4, "b6")) return false;
+            View t5 = buf((long)B * h5 * w5, c5), t5b = buf((long)B * h5 * w5, c5), p5 = buf((long)B * h5 * w5, c5);
+            p->quiet_step = (int)p->steps.size();
+            if (!t5.base || !t5b.base || !p5.base || !conv1(take(c4, c5, 3, 2, "b7"), p4, t5, h4, w4, 1)) return false;
+            if (!c3(c5, c5, d.depth_backbone[3], true, &t5, nullptr, nullptr, t5b, h5, w5, "b8")) return false;
+            {   // SPPF
+                const int c_ = c5 / 2;
+                const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
+                View cat = buf((long)B * h5 * w5, 4 * c_);
+                if (!cat.base || !conv1(cv1, t5b, cat.sub(0, c_), h5, w5, 1)) return false;
+                if (h5 * w5 <= 2400) {
+                    Step s3{}; s3.kind = K_SPPF3; s3.in = cat.sub(0, c_).ptr(); s3.ldi = cat.ld; s3.out = cat.sub(c_, c_).ptr(); s3.out2 = cat.sub(2 * c_, c_).ptr();
+                    s3.out3 = cat.sub(3 * c_, c_).ptr(); s3.ldo = cat.ld; s3.H = h5; s3.W = w5; s3.Cin = c_;
+                    push(s3, nullptr);
+                } else {
+                    for (int i = 0; i < 3; ++i) {
+                        Step sp{}; sp.kind = K_POOL5; sp.in = cat.sub(i * c_, c_).ptr(); sp.ldi = cat.ld; sp.out = cat.sub((i + 1) * c_, c_).ptr(); sp.ldo = cat.ld;
+                        sp.H = h5; sp.W = w5; sp.Cin = c_;
+                        push(sp, nullptr);
+                    }
+                }
+                if (!conv1(cv2, cat, p5, h5, w5, 1)) return false;
+            }
+            // neck: the two concat buffers of the bottom-up path; h10 / h14 write their slices directly
+            View cat20 = buf((long)B * h4 * w4, 2 * c3w), cat23 = buf((long)B * h5 * w5, 2 * c4);
+            if (!cat20.base || !cat23.base) return false;
+            View t10 = cat23.sub(c4, c4), t14 = cat20.sub(c3w, c3w);
+            View n4 = buf((long)B * h4 * w4, c4), n3 = buf((long)B * h3 * w3, c3w), m4 = buf((long)B * h4 * w4, c4), m5 = buf((long)B * h5 * w5, c5);
+            if (!n4.base || !n3.base || !m4.base || !m5.base) return false;
+            if (!conv1(take(c5, c4, 1, 1, "h10"), p5, t10, h5, w5, 1)) return false;
+            if (!c3(2 * c4, c4, nh, false, nullptr, &t10, &p4, n4, h4, w4, "h13")) return false;
+            if (!conv1(take(c4, c3w, 1, 1, "h14"), n4, t14, h4, w4, 1)) return false;
+            if (!c3(2 * c3w, c3w, nh, false, nullptr, &t14, &p3, n3, h3, w3, "h17")) return false;
+            if (!conv1(take(c3w, c3w, 3, 2, "h18"), n3, cat20.sub(0, c3w), h3, w3, 1)) return false;
+            if (!c3(2 * c3w, c4, nh, false, &cat20, nullptr, nullptr, m4, h4, w4, "h20")) return false;
+            if (!conv1(take(c4, c4, 3, 2, "h21"), m4, cat23.sub(0, c4), h4, w4, 1)) return false;
+            if (!c3(2 * c4, c5, nh, false, &cat23, nullptr, nullptr, m5, h5, w5, "h23")) return false;
+            // detect: one fused convolution + decode per level, into disjoint anchor ranges of the output
+            const int no = 5 + d.nc, co_real = 3 * no, co = (co_real + 7) / 8 * 8;
+            p->A = 3 * (h3 * w3 + h4 * w4 + h5 * w5);
+            const View feats[3] = {n3, m4, m5};
+            const int chs[3] = {c3w, c4, c5}, hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
+            const float strides[3] = {8.f, 16.f, 32.f};
+            const void *danc = nullptr;
+            if (!upload(anchors, sizeof(float) * 18, &danc)) return false;
+            int a0 = 0;
+            for (int l = 0; l < 3; ++l) {
+                const rva_conv_weights *hc = padded(take(chs[l], co_real, 1, 1, "detect.m"), chs[l], co);
+                if (!hc) return false;
+                Step s{}; s.kind = K_HEAD5;
+                if (!pack(&hc, 1, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
+                s.in = feats[l].ptr(); s.ldi = feats[l].ld; s.H = hs[l]; s.W = ws[l]; s.a0 = a0; s.stride_px = strides[l];
+                s.b2 = (const float *)danc + 6 * l;
+                push(s, "head5:%d->%d k1s1 %dx%d", s.Cin, s.Cout, hs[l], ws[l]);
+                a0 += 3 * hs[l] * ws[l];
+            }
+            if (next != d.n_convs) return fail("convolution list longer than the architecture");
+        }
+        return err.empty();
     }
 
     bool build()
@@ -492,7 +622,7 @@ struct Builder {
 // whether this step, run with this variant, can restrict its launch to a row window
 bool step_takes_rows(const Step &s, int variant)
 {
-    if (s.kind == K_STEM2) return true;
+    if (s.kind == K_STEM2 || s.kind == K_STEM6) return true;
     return s.kind == K_CONV && rva_conv_variant_rows(variant, s.Cin, s.k, s.stride);
 }
 
@@ -503,6 +633,7 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
     rva_ctx *c = p->ctx;
     if (win && (s.y0 > 0 || s.y1 < s.Ho) && step_takes_rows(s, variant)) {
         if (s.kind == K_STEM2) return rva_stem2_f16_rows(c, input, s.w, s.b, s.w2, s.b2, s.out, s.ldo, n, s.H, s.W, s.y0, s.y1, st);
+        if (s.kind == K_STEM6) return rva_stem6_conv_f16_rows(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, s.y0, s.y1, st);
         return rva_conv2d_nhwc_f16_sel(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, p->B, s.H, s.W, s.Cin, s.Cout, s.k, s.stride, s.act,
                                        variant, s.y0, s.y1, st);
     }
@@ -525,6 +656,8 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
     case K_STEM_F32: return rva_stem_conv_f32(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
     case K_POOL5_F32: return rva_maxpool5_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
     case K_UP2_F32: return rva_upsample2x_nhwc_f32(c, s.in, s.ldi, s.out, s.ldo, n, s.H, s.W, s.Cin, st);
+    case K_STEM6: return rva_stem6_conv_f16(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
+    case K_HEAD5: return rva_conv1x1_head5_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, p->nc, s.b2, output, boxes, p->A, s.a0, s.stride_px, variant, st);
     case K_HEAD_F32: return rva_yolo_head_f32(c, s.in, s.ldi, s.in2, s.ldi2, output, n, s.H, s.W, p->nc, p->A, s.a0, s.stride_px, st);
     }
     return RVA_ERR_ARG;
@@ -581,6 +714,12 @@ void propagate_rows(rva_yolov8_plan *p)
             Ho = through(3, 2, s.H, &lo, &hi);
             if (s.kind == K_STEM2) Ho = through(3, 2, Ho, &lo, &hi);
             break;
+        case K_STEM6: {
+            int32_t a = 0, b = 0;
+            (void)rva_conv_rows_through_pad(6, 2, 2, s.H, p->rows_top, p->rows_bottom, &a, &b);
+            lo = a; hi = b; known = true; Ho = s.H / 2;
+            break;
+        }
         case K_CONV:
             known = read(s.in, s.c_real, s.H, &lo, &hi);
             Ho = out_rows(s.H, s.k, s.stride);
@@ -611,7 +750,7 @@ void propagate_rows(rva_yolov8_plan *p)
         if (off || !known || lo >= hi) { lo = 0; hi = Ho; }
         s.y0 = lo; s.y1 = hi;
         if (lo > 0 || hi < Ho) p->windowed = true;
-        if (s.kind == K_STEM2 || s.kind == K_STEM || s.kind == K_CONV || s.kind == K_PAIR32 || s.kind == K_UPCAT) {
+        if (s.kind == K_STEM2 || s.kind == K_STEM || s.kind == K_STEM6 || s.kind == K_CONV || s.kind == K_PAIR32 || s.kind == K_UPCAT) {
             const int ch = s.kind == K_STEM2 ? 64 : s.kind == K_PAIR32 ? 32 : s.Cout;
             written.push_back(Slice{(const char *)s.out, (const char *)s.out + (size_t)ch * es, Ho, lo, hi});
         }
@@ -677,6 +816,7 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
     RVA_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
     p->ctx = ctx; p->d = *desc; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
+    p->head_rows = 4 + desc->nc;
     p->f32 = (desc->flags & RVA_PLAN_F32) != 0;
     p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
     if (p->f32 && p->box32)
@@ -701,6 +841,42 @@ int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_
     return RVA_OK;
 }
 
+int rva_yolov5_plan_create(rva_ctx *ctx, const rva_yolov5_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out)
+{
+    if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
+    *out = nullptr;
+    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
+        desc->nc > 1024 || desc->n_convs <= 0)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024");
+    if (desc->flags & RVA_PLAN_F32)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: there is no fp32 YOLOv5 plan (RVA_PLAN_F32); build the fp16 plan");
+    for (int i = 0; i < 5; ++i)
+        if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: channel widths must be multiples of 8");
+    for (int i = 0; i < 18; ++i)
+        if (!(desc->anchors[i] > 0.f) || !(desc->anchors[i] < 65504.f)) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: anchors must be positive pixel sizes");
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
+    p->ctx = ctx; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
+    p->d.batch = desc->batch; p->d.height = desc->height; p->d.width = desc->width; p->d.nc = desc->nc; p->d.reg_max = 0;
+    for (int i = 0; i < 5; ++i) p->d.widths[i] = desc->widths[i];
+    for (int i = 0; i < 4; ++i) p->d.depth_backbone[i] = desc->depth_backbone[i];
+    p->d.depth_head = desc->depth_head; p->d.n_convs = desc->n_convs; p->d.flags = desc->flags;
+    p->head_rows = 5 + desc->nc;
+    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
+    Builder b{p.get(), convs};
+    if (!b.build_v5(desc->anchors)) {
+        for (void *a : p->allocs) (void)hipFree(a);
+        return rva_fail(ctx, b.err.find("hip") == 0 || b.err.find("upload") != std::string::npos ? RVA_ERR_HIP : RVA_ERR_ARG,
+                        "rva_yolov5_plan_create: %s", b.err.c_str());
+    }
+    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
+    if (p->box32) p->box_off = ((size_t)p->B * p->head_rows * p->A * 2 + 255) / 256 * 256;
+    p->rows_top = 0; p->rows_bottom = p->H;
+    propagate_rows(p.get());
+    *out = p.release();
+    return RVA_OK;
+}
+
 void rva_yolov8_plan_destroy(rva_yolov8_plan *p)
 {
     if (!p) return;
@@ -716,7 +892,7 @@ int rva_yolov8_plan_info(const rva_yolov8_plan *p, int32_t *anchors, int32_t *ou
 {
     if (!p) return RVA_ERR_ARG;
     if (anchors) *anchors = p->A;
-    if (out_rows) *out_rows = 4 + p->nc;
+    if (out_rows) *out_rows = p->head_rows;
     if (n_steps) *n_steps = (int32_t)p->steps.size();
     if (n_tunable) *n_tunable = (int32_t)p->tunables.size();
     if (quiet_step) *quiet_step = p->quiet_step;
@@ -726,7 +902,7 @@ int rva_yolov8_plan_info(const rva_yolov8_plan *p, int32_t *anchors, int32_t *ou
 int rva_yolov8_plan_output_layout(const rva_yolov8_plan *p, int64_t *total_bytes, int64_t *boxes_offset)
 {
     if (!p) return RVA_ERR_ARG;
-    const size_t head = (size_t)p->B * (4 + p->nc) * p->A * (p->f32 ? 4 : 2);
+    const size_t head = (size_t)p->B * p->head_rows * p->A * (p->f32 ? 4 : 2);
     if (total_bytes) *total_bytes = (int64_t)(p->box32 ? p->box_off + (size_t)p->B * 4 * p->A * 4 : head);
     if (boxes_offset) *boxes_offset = p->box32 ? (int64_t)p->box_off : -1;
     return RVA_OK;
@@ -760,7 +936,7 @@ int rva_yolov8_plan_launch_tunable(rva_yolov8_plan *p, int index, int variant, v
     if (!p || index < 0 || index >= (int)p->tunables.size()) return RVA_ERR_ARG;
     const Step &s = p->steps[p->tunables[index].step];
     if (!variant_fits(s, variant)) return RVA_ERR_ARG;
-    if (s.kind == K_HEAD && !output) return RVA_ERR_ARG;
+    if ((s.kind == K_HEAD || s.kind == K_HEAD5) && !output) return RVA_ERR_ARG;
     return launch_step(p, s, variant, nullptr, output, p->B, stream, true);      // all images; the row window where the variant takes one: what a primed run launches
 }
 
@@ -815,8 +991,16 @@ int rva_yolov8_plan_step_rows(const rva_yolov8_plan *p, int step, int32_t *y0, i
 // Output rows of a k x k, pad k / 2 convolution that see an input row of [lo, hi): row o reads o * stride - k / 2 .. + k - 1
 int rva_conv_rows_through(int k, int stride, int H_in, int lo, int hi, int32_t *out_lo, int32_t *out_hi)
 {
-    if ((k != 1 && k != 3) || (stride != 1 && stride != 2) || H_in <= 0 || lo < 0 || hi > H_in || lo >= hi || !out_lo || !out_hi) return RVA_ERR_ARG;
-    const int pad = k / 2, Ho = out_rows(H_in, k, stride);
+    if ((k != 1 && k != 3) || (stride != 1 && stride != 2)) return RVA_ERR_ARG;
+    return rva_conv_rows_through_pad(k, stride, k / 2, H_in, lo, hi, out_lo, out_hi);
+}
+
+// The same for any padding (the 6x6 stride-2 pad-2 stem of YOLOv5): row o reads o * stride - pad .. + k - 1
+int rva_conv_rows_through_pad(int k, int stride, int pad, int H_in, int lo, int hi, int32_t *out_lo, int32_t *out_hi)
+{
+    if (k < 1 || stride < 1 || pad < 0 || pad >= k || H_in <= 0 || lo < 0 || hi > H_in || lo >= hi || !out_lo || !out_hi) return RVA_ERR_ARG;
+    if (H_in + 2 * pad < k) return RVA_ERR_ARG;
+    const int Ho = (H_in + 2 * pad - k) / stride + 1;
     // o * stride - pad + k - 1 >= lo  and  o * stride - pad <= hi - 1
     int a = lo + pad - (k - 1), b = hi - 1 + pad;
     a = a <= 0 ? 0 : (a + stride - 1) / stride;

@@ -84,6 +84,52 @@ def create_detector(config: DetectorConfig) -> BaseDetector:
     raise ValueError(f"Unsupported detector backend '{config.backend}'")
 
 
+def detector_architecture(model_type: str, model_path: str, net=None, state_dict=None) -> str:
+    """``"yolov5"`` or ``"yolov8"``: which network ``HipYoloDetector`` builds.  No configuration key: it follows what the user
+    handed over.  YOLOv5 when (1) ``net`` is a ``yolov5.YoloV5``; or (2) ``model_path`` is an existing file whose state dict
+    (``state_dict`` where the caller has loaded it already) has the YOLOv5 detect convolution (``model.24.m.0.weight`` /
+    ``24.m.0.weight`` / ``detect.m.0.weight``); or (3) ``model_type`` is ``"yolov5"`` and the file name starts with ``yolov5`` plus
+    a scale letter while no such file exists (seeded weights).  Everything else is YOLOv8 as before: ``model_type: yolov5`` with
+    the default ``yolov8n.pt``, every ``yolov8*`` name, and the ``yolov5*u`` names (anchor-free re-exports with the v8 head)."""
+    from .yolov5 import YoloV5, is_v5_state_dict, variant_from_path_v5
+    if net is not None:
+        return "yolov5" if isinstance(net, YoloV5) else "yolov8"
+    if _is_file(model_path):
+        if state_dict is None:
+            state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
+        return "yolov5" if is_v5_state_dict(state_dict) else "yolov8"
+    if str(model_type).lower() == "yolov5" and variant_from_path_v5(model_path) is not None:
+        return "yolov5"
+    return "yolov8"
+
+
+def v5_scale_of(model_path: str, state_dict=None) -> str:
+    """Scale letter of a YOLOv5 model: from the stem width of its state dict (16 n, 32 s, 48 m, 64 l, 80 x), else from the file
+    name, else ``"n"``."""
+    from .yolov5 import variant_from_path_v5
+    for key in ("b0.conv.weight", "model.0.conv.weight", "0.conv.weight") if state_dict is not None else ():
+        w = state_dict.get(key)
+        if w is not None:
+            s = {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}.get(int(w.shape[0]))
+            if s:
+                return s
+    return variant_from_path_v5(model_path) or "n"
+
+
+def select_yolo_engine(arch: str, half: bool, hip_engine: str = "auto") -> str:
+    """Engine of a ``HipYoloDetector``: ``"fused"`` (fp16 plan) for ``half: true``; for ``half: false`` the fp32 plan
+    (``"fused-f32"``) under ``hip_engine: plan / native`` and the module through PyTorch-ROCm (``"torch-fp32"``) under ``auto``.
+    YOLOv5 has no fp32 plan: ``half: false`` with ``plan`` / ``native`` is a ``ValueError``."""
+    if half:
+        return "fused"
+    if hip_engine in ("plan", "native"):
+        if arch == "yolov5":
+            raise ValueError(f"hip_engine: {hip_engine} with half: false needs an fp32 YOLOv5 plan, which does not exist; the "
+                             "hand-written YOLOv5 plan is fp16: set `half: true` (or `hip_engine: auto` for fp32 through PyTorch-ROCm)")
+        return "fused-f32"
+    return "torch-fp32"
+
+
 class HipYoloDetector(BaseDetector):
     """YOLO detector on MI355X: K1 pre-process -> PyTorch-ROCm network -> K2/K3 post-process.
 
@@ -104,6 +150,10 @@ class HipYoloDetector(BaseDetector):
         ``hip_box_rows: fp32`` (engine ``"fused"`` only) makes the plan keep the four box rows in fp32 beside its fp16 head
         (``engine.FusedYoloV8(box_rows="fp32")``); the side tensor travels from ``stage_net`` to ``stage_post`` as an
         ``ops.SplitHead`` and K2 reads its boxes from it.
+        The architecture (``self.arch``) is YOLOv5 where ``detector_architecture`` says so -- a ``yolov5.YoloV5`` as ``net``, a YOLOv5
+        state dict at ``model_path``, or ``model_type: yolov5`` with a ``yolov5<n|s|m|l>`` file name and no file -- and then ``half:
+        true`` runs ``engine.FusedYoloV5`` (engine ``"fused"``, head ``[B, 5+nc, A]``), ``half: false`` the module through PyTorch-ROCm
+        (``plan`` / ``native``: ``ValueError``, there is no fp32 YOLOv5 plan).
         ``hip_plan_capacity: N`` (engines ``"fused"`` and ``"fused-f32"``; default 0 = one plan and input buffer per batch size)
         keeps ONE plan and ONE input buffer of ``N`` images per input size and slot: a call with ``n <= N`` frames writes and
         runs the leading ``n`` images, with the kernels of a full run (config.py)."""
@@ -116,7 +166,12 @@ class HipYoloDetector(BaseDetector):
         else:
             self.input_hw = (640, 640)            # detector.py:582-583 default
         self.half = bool(config.half)
-        self.engine = "fused" if self.half else ("fused-f32" if getattr(config, "hip_engine", "auto") in ("plan", "native") else "torch-fp32")
+        # the architecture follows what the user handed over (detector_architecture); behind an infer_fn there is no network
+        sd = None
+        if infer_fn is None and net is None and _is_file(config.model_path):
+            sd = torch.load(config.model_path, map_location="cpu", weights_only=True)
+        self.arch = "yolov8" if infer_fn is not None else detector_architecture(config.model_type, config.model_path, net, sd)
+        self.engine = select_yolo_engine(self.arch, self.half, getattr(config, "hip_engine", "auto"))
         self._infer_fn = infer_fn
         # where the fp16 plan keeps its box rows; fp32 elsewhere already (half: false), and no plan behind an infer_fn
         self.box_rows = getattr(config, "hip_box_rows", "fp16") if (self.engine == "fused" and infer_fn is None) else "fp16"
@@ -126,7 +181,13 @@ class HipYoloDetector(BaseDetector):
         self._over_capacity_warned = False
         self.net = None
         if infer_fn is None:
-            if net is None:
+            if net is None and self.arch == "yolov5":
+                from .yolov5 import build_detector_net_v5
+                scale = v5_scale_of(config.model_path, sd)
+                net = build_detector_net_v5(scale, seed=seed, weights=config.model_path)
+                LOGGER.info("hip detector: YOLOv5%s, %s weights", scale,
+                            "local state-dict" if sd is not None else "seeded random (no weights offline)")
+            elif net is None:
                 scale = variant_from_path(config.model_path)
                 net = build_detector_net(scale, seed=seed, weights=config.model_path)
                 LOGGER.info("hip detector: YOLOv8%s, %s weights", scale,
@@ -233,16 +294,17 @@ class HipYoloDetector(BaseDetector):
         key = shape if self._slot == 0 else shape + (self._slot,)
         plan = self._plans.get(key)
         if plan is None:
-            from .engine import FusedYoloV8
+            from .engine import FusedYoloV5, FusedYoloV8
+            plan_cls = FusedYoloV5 if self.arch == "yolov5" else FusedYoloV8      # the same plan object and surface
             first = self._plans.get(shape) if self._slot else None
             # the static rows at construction: the tuner times the windowed launches, and a later slot's plan has the first
             # slot's windows, whose kernel selection it takes over
             n = shape[0] if self._slot == 0 else (shape[0], self._slot)
             rows = first.static_rows if first is not None else self._rows.get(n)
-            plan = self._plans[key] = FusedYoloV8(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
-                                                  autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
-                                                  precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows,
-                                                  static_rows=rows if self.engine == "fused" else None)
+            plan = self._plans[key] = plan_cls(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
+                                               autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
+                                               precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows,
+                                               static_rows=rows if self.engine == "fused" else None)
             if first is not None:
                 plan.copy_tuning(first)
         plan.n = batch

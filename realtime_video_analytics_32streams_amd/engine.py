@@ -92,6 +92,9 @@ class _VariantCell:
 
 
 class FusedYoloV8:
+    HEAD_ROWS_EXTRA = 4                   # rows of the head tensor beside the classes: xywh
+    ARCH_KEY = b""                        # joins the tuning key where it is not empty (YOLOv8 keys stay as they were)
+
     def __init__(self, net: YoloV8, batch: int, hw: Tuple[int, int] = (640, 640), device: Optional[torch.device] = None,
                  ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16",
                  box_rows: str = "fp16", static_rows: Optional[Tuple[int, int]] = None):
@@ -115,7 +118,7 @@ class FusedYoloV8:
         self._net = net                     # kept for the twin plans of the in-plan kernel selection
         self.nc = net.nc
         self.L = N.lib()
-        convs = module_order_convs(net)
+        convs = self._module_order(net)
         keep, arr = [], (N.ConvWeights * len(convs))()
         for i, c in enumerate(convs):
             w = np.ascontiguousarray(c.weight.detach().float().cpu().numpy())
@@ -124,21 +127,14 @@ class FusedYoloV8:
             arr[i].weight = w.ctypes.data_as(C.POINTER(C.c_float))
             arr[i].bias = b.ctypes.data_as(C.POINTER(C.c_float)) if b is not None else None
             arr[i].cout, arr[i].cin, arr[i].k, arr[i].stride = int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), int(c.stride[0])
-        d = N.YoloV8Desc()
-        d.batch, d.height, d.width = batch, hw[0], hw[1]
-        d.widths[:] = [net.b0.conv.out_channels, net.b1.conv.out_channels, net.b3.conv.out_channels, net.b5.conv.out_channels,
-                       net.b7.conv.out_channels]
-        d.depth_backbone[:] = [len(net.b2.m), len(net.b4.m), len(net.b6.m), len(net.b8.m)]
-        d.depth_head = len(net.h12.m)
-        assert len(net.h15.m) == len(net.h18.m) == len(net.h21.m) == d.depth_head
-        d.nc, d.reg_max, d.n_convs = net.nc, net.detect.reg_max, len(convs)
+        d, create = self._descriptor(net, batch, hw, len(convs))
         d.flags = (N.RVA_PLAN_NO_STEM2 if os.environ.get("RVA_NO_STEM2", "0") == "1" else 0) | \
                   (N.RVA_PLAN_NO_CIN_PAD if os.environ.get("RVA_NO_CIN_PAD", "0") == "1" else 0) | \
                   (0 if self._use_pair32() else N.RVA_PLAN_NO_PAIR32) | \
                   (N.RVA_PLAN_F32 if self.f32 else 0) | (N.RVA_PLAN_BOX_F32 if box_rows == "fp32" else 0)
         h = C.c_void_p()
         with torch.cuda.device(self.dev):
-            self.ctx.check(self.L.rva_yolov8_plan_create(self.ctx.handle, C.byref(d), arr, C.byref(h)), "rva_yolov8_plan_create")
+            self.ctx.check(getattr(self.L, create)(self.ctx.handle, C.byref(d), arr, C.byref(h)), create)
         self.handle = h
         del keep
         # row windows: set before the tuner runs, so that it times the windowed launches -- what will run
@@ -150,7 +146,7 @@ class FusedYoloV8:
         info = [C.c_int32() for _ in range(5)]
         self.ctx.check(self.L.rva_yolov8_plan_info(h, *[C.byref(v) for v in info]), "rva_yolov8_plan_info")
         self.A, rows, self._n_steps, n_tun, self.quiet_step = (int(v.value) for v in info)
-        assert rows == 4 + self.nc
+        assert rows == self.HEAD_ROWS_EXTRA + self.nc
         self.dtype = torch.float32 if self.f32 else torch.float16
         self.boxes32: Optional[torch.Tensor] = None       # box_rows="fp32": the side tensor of the current output slot
         self._boxes = {}
@@ -163,7 +159,7 @@ class FusedYoloV8:
         else:
             self.out = torch.empty((batch, rows, self.A), dtype=self.dtype, device=self.dev)
         self._outs = {0: self.out}
-        self.fused_stem = not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
+        self.fused_stem = isinstance(d, N.YoloV8Desc) and not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
         # (launch(stream, variant) -> rc, state["variant"], "Cin->Cout kKsS HxW") per convolution step, as the tuner and the tools use them
         self._n_tunable = n_tun
         self._read_tunables()
@@ -172,6 +168,23 @@ class FusedYoloV8:
         self.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1"      # A/B switch for measurements
         if autotune:
             self.autotune()
+
+    @staticmethod
+    def _module_order(net) -> list:
+        return module_order_convs(net)
+
+    @staticmethod
+    def _descriptor(net, batch: int, hw: Tuple[int, int], n_convs: int):
+        """The plan descriptor of ``net`` (flags left to the caller) and the name of the create entry point that takes it."""
+        d = N.YoloV8Desc()
+        d.batch, d.height, d.width = batch, hw[0], hw[1]
+        d.widths[:] = [net.b0.conv.out_channels, net.b1.conv.out_channels, net.b3.conv.out_channels, net.b5.conv.out_channels,
+                       net.b7.conv.out_channels]
+        d.depth_backbone[:] = [len(net.b2.m), len(net.b4.m), len(net.b6.m), len(net.b8.m)]
+        d.depth_head = len(net.h12.m)
+        assert len(net.h15.m) == len(net.h18.m) == len(net.h21.m) == d.depth_head
+        d.nc, d.reg_max, d.n_convs = net.nc, net.detect.reg_max, n_convs
+        return d, "rva_yolov8_plan_create"
 
     def _read_tunables(self) -> None:
         self._tunable = []
@@ -212,7 +225,7 @@ class FusedYoloV8:
     def _alloc_split(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """One allocation in the plan's output layout: the fp16 head, then ``boxes32`` at the offset the plan reports."""
         total, off = self._out_layout
-        rows = 4 + self.nc
+        rows = self.HEAD_ROWS_EXTRA + self.nc
         buf = torch.empty((total,), dtype=torch.uint8, device=self.dev)
         head = buf[:self.B * rows * self.A * 2].view(torch.float16).view(self.B, rows, self.A)
         boxes = buf[off:off + self.B * 4 * self.A * 4].view(torch.float32).view(self.B, 4, self.A)
@@ -248,6 +261,8 @@ class FusedYoloV8:
         h.update(repr(int(os.environ.get("RVA_TUNE_LAYER_OVERLAP", getattr(self, "tune_overlap", 1)))).encode())
         if getattr(self, "f32", False):
             h.update(b"precision fp32")                 # fp16 keys stay as they were: existing caches remain valid
+        if self.ARCH_KEY:
+            h.update(self.ARCH_KEY)
         return h.hexdigest()[:24]
 
     def _load_tuning(self) -> bool:
@@ -386,7 +401,7 @@ class FusedYoloV8:
         lanes = self.concurrent_heads
         n_over = int(os.environ.get("RVA_TUNE_OVERLAP", "3"))
         if n_over >= 2:
-            twins = [FusedYoloV8(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision,
+            twins = [type(self)(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision,
                                  box_rows=self.box_rows, static_rows=self.static_rows)
                      for _ in range(n_over - 1)]
             from .ops import chain_streams
@@ -520,3 +535,47 @@ class FusedYoloV8:
     @property
     def n_launches(self) -> int:
         return self._n_steps
+
+
+def module_order_convs_v5(net) -> list:
+    """The convolutions of a fused ``yolov5.YoloV5`` in the module order ``rva_yolov5_plan_create`` consumes (include/rva.h)."""
+    def c3(m):
+        out = [m.cv1, m.cv2, m.cv3]
+        for b in m.m:
+            out += [b.cv1, b.cv2]
+        return out
+    mods = [net.b0, net.b1, *c3(net.b2), net.b3, *c3(net.b4), net.b5, *c3(net.b6), net.b7, *c3(net.b8), net.b9.cv1, net.b9.cv2,
+            net.h10, *c3(net.h13), net.h14, *c3(net.h17), net.h18, *c3(net.h20), net.h21, *c3(net.h23), *net.detect.m]
+    return [m.conv if isinstance(m, ConvBnAct) else m for m in mods]
+
+
+class FusedYoloV5(FusedYoloV8):
+    """The fused fp16 plan of a ``yolov5.YoloV5`` (``rva_yolov5_plan_create``): the same plan object, tuner and surface as
+    ``FusedYoloV8`` -- ``__call__``, ``result()``, ``use_output``, ``n``, ``set_static_rows``, ``copy_tuning``, ``n_launches``,
+    ``boxes32`` -- with the head tensor ``[B, 5 + nc, A]`` (anchor axis contiguous; the transpose of the module's output).
+    There is no fp32 YOLOv5 plan: ``precision="fp32"`` is a ``ValueError``."""
+
+    HEAD_ROWS_EXTRA = 5                   # xywh + objectness
+    ARCH_KEY = b"arch yolov5"
+
+    def __init__(self, net, batch: int, hw: Tuple[int, int] = (640, 640), **kw):
+        if kw.get("precision", "fp16") != "fp16":
+            raise ValueError("there is no fp32 YOLOv5 plan: FusedYoloV5 runs precision='fp16' (half: true)")
+        super().__init__(net, batch, hw, **kw)
+
+    @staticmethod
+    def _module_order(net) -> list:
+        return module_order_convs_v5(net)
+
+    @staticmethod
+    def _descriptor(net, batch: int, hw: Tuple[int, int], n_convs: int):
+        d = N.YoloV5Desc()
+        d.batch, d.height, d.width = batch, hw[0], hw[1]
+        d.widths[:] = [net.b0.conv.out_channels, net.b1.conv.out_channels, net.b3.conv.out_channels, net.b5.conv.out_channels,
+                       net.b7.conv.out_channels]
+        d.depth_backbone[:] = [len(net.b2.m), len(net.b4.m), len(net.b6.m), len(net.b8.m)]
+        d.depth_head = len(net.h13.m)
+        assert len(net.h17.m) == len(net.h20.m) == len(net.h23.m) == d.depth_head
+        d.nc, d.n_convs = net.nc, n_convs
+        d.anchors[:] = [float(v) for v in net.detect.anchors_px.detach().float().cpu().flatten().tolist()]
+        return d, "rva_yolov5_plan_create"
