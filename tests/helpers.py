@@ -170,3 +170,24 @@ def fp16_error_report(tag, got16, want_fp32, matched, conf=0.25):
     if out.is_dir():
         (out / f"fp16_error_{tag}.json").write_text(json.dumps(rep, indent=1))
     return rep
+
+
+# The fused YOLOv5 plan's yardstick (tests/test_gpu_yolov5_plan.py, tests/test_gpu_conv_slices.py).  Head tensors are
+# ``[B, 5 + nc, A]``; per row group the plan's largest error against the float64 module may be at most twice the largest error
+# of the same module run by PyTorch fp16 channels-last: both store fp16 activations and differ only in summation order and
+# rounding points.
+V5_GROUPS = (("xy", slice(0, 2)), ("wh", slice(2, 4)), ("objectness", slice(4, 5)), ("classes", slice(5, None)))
+
+
+def v5_head_errors(got, tor, want):
+    """``got`` (the plan), ``tor`` (PyTorch fp16), ``want`` (the float64 module), all float64 ``[B, 5 + nc, A]`` on one device ->
+    ``{group: {"plan_max_err", "torch_fp16_max_err"}}``."""
+    assert got.shape == want.shape == tor.shape, (got.shape, want.shape, tor.shape)
+    return {name: {"plan_max_err": float((got[:, rows] - want[:, rows]).abs().max()),
+                   "torch_fp16_max_err": float((tor[:, rows] - want[:, rows]).abs().max())} for name, rows in V5_GROUPS}
+
+
+def v5_groups_over_twice_torch(rec):
+    """The groups of :func:`v5_head_errors` whose plan error exceeds twice PyTorch's (a NaN error counts as exceeding it)."""
+    return [(name, e["plan_max_err"], e["torch_fp16_max_err"]) for name, e in rec.items()
+            if not e["plan_max_err"] <= 2.0 * e["torch_fp16_max_err"]]

@@ -1,9 +1,15 @@
 """Every row of the fp16 convolution variant table (``kConvVariants``, csrc/rva_conv.hip) where the fused plan really calls
 it: on channel slices of concat buffers with the plan's row strides, offsets and rounded-up Cin (part 1, against float64), and
-forced on the steps of real plans (part 2, against the rounding-matched reference).  The autotuner picks rows by time alone;
-these tests are what makes "all variants compute the same layer" true for the layouts it picks them on."""
+forced on the steps of real plans (part 2: YOLOv8 plans against the rounding-matched reference, YOLOv5 plans against the float64
+module with PyTorch fp16's error as the yardstick).  The autotuner picks rows by time alone; these tests are what makes "all
+variants compute the same layer" true for the layouts it picks them on.  ``FusedYoloV5`` inherits the tuner unchanged, and
+``Builder::c3`` / ``build_v5`` produce layouts the YOLOv8 builder never does: both parts cover them."""
 import ctypes as C
-from typing import NamedTuple, Optional, Tuple
+import copy
+import functools
+import json
+import os
+from pathlib import Path
 
 import pytest
 import torch
@@ -11,9 +17,12 @@ import torch.nn.functional as F
 
 from realtime_video_analytics_32streams_amd import _native as N
 from realtime_video_analytics_32streams_amd import ops
-from realtime_video_analytics_32streams_amd.engine import FusedYoloV8
+from realtime_video_analytics_32streams_amd.engine import FusedYoloV5, FusedYoloV8
+from realtime_video_analytics_32streams_amd.yolov5 import build_detector_net_v5
 from realtime_video_analytics_32streams_amd.yolov8 import build_detector_net
-from tests.helpers import assert_conv_close, assert_matches_rounded_reference, plan_rounded_reference
+from tests.conv_slice_layouts import Layout, V5_STRIDE1_LAYOUTS, V5_STRIDE2_LAYOUTS
+from tests.helpers import (assert_conv_close, assert_matches_rounded_reference, plan_rounded_reference, v5_head_errors,
+                           v5_groups_over_twice_torch)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,19 +32,6 @@ SENTINEL = 7.0
 # ---------------------------------------------------------------------------------------------------
 # Part 1: rva_conv2d_nhwc_f16_v on the plan's slice layouts
 # ---------------------------------------------------------------------------------------------------
-class Layout(NamedTuple):
-    name: str
-    cin: int                                   # real input channels (the reference reads these)
-    cin_decl: int                              # what the step declares: Cin rounded up to 32 (Builder::conv), zero weight columns
-    cout: int
-    k: int
-    stride: int
-    act: int
-    inp: Tuple[int, int]                       # (row stride, channel offset) of the input slice
-    out: Tuple[int, int]                       # ... of the output slice
-    res: Optional[Tuple[int, int]] = None      # ... of the residual slice, which lives in the OUTPUT allocation (Builder::c2f)
-
-
 def _cv1(c, decl, n, i):
     """Bottleneck cv1: reads cat.sub((1+i)*c, c) of a (2+n)*c row, writes the contiguous tmp."""
     return Layout(f"cv1 c{c} n{n} i{i}", c, decl, c, 3, 1, 1, ((2 + n) * c, (1 + i) * c), (c, 0))
@@ -93,6 +89,12 @@ STRIDE2_LAYOUTS = [
     Layout("s2 32->64 front half", 32, 32, 64, 3, 2, 1, (32, 0), (64 + 128, 0)),
 ]
 
+# The YOLOv5 builder (rva_plan.hip:316-443, Builder::c3 and build_v5): residuals in another allocation with ldr != ldo, sibling
+# launches into the front of a 3c row, cv3 from its middle, padded Cin under a stride-2 3x3.  Generated from a restatement of the
+# builder (tests/conv_slice_layouts.py, which cites the line of each step), not typed by hand.
+STRIDE1_LAYOUTS += V5_STRIDE1_LAYOUTS
+STRIDE2_LAYOUTS += V5_STRIDE2_LAYOUTS
+
 # B, H, W: tiles that straddle rows and images, and an M tail (9 x 7: 189 pixels); stride 2 with even sizes (the s2run rows)
 STRIDE1_SHAPES = [(3, 12, 20), (3, 6, 10), (3, 9, 7)]
 STRIDE2_SHAPES = [(2, 12, 20)]
@@ -113,8 +115,8 @@ def _bits(t):
 @pytest.mark.parametrize("layout,shape", CASES, ids=[f"{lay.name} {b}x{h}x{w}".replace(" ", "_") for lay, (b, h, w) in CASES])
 def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
     """Each row of the variant table on one slice layout of the plan: within the fp16-ulp bound of the float64 convolution of the
-    real channels, nothing written outside the output slice, nothing taken from outside the declared input slice, and the same
-    rows accepted as for the contiguous tensor of that shape."""
+    real channels, nothing written outside the output slice (nor into a residual buffer of its own), nothing taken from outside the
+    declared input slice, and the same rows accepted as for the contiguous tensor of that shape."""
     lay, (B, H, W) = layout, shape
     k, s = lay.k, lay.stride
     Ho, Wo = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
@@ -126,12 +128,18 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
     w = (torch.randn((lay.cout, lay.cin, k, k), generator=g) / (lay.cin * k * k) ** 0.5).half()
     b = torch.randn((lay.cout,), generator=g) * 0.1
     out_rows = torch.full((Mo, ldo), SENTINEL, dtype=torch.float16)
-    res = None
+    res, res_init, ldr = None, None, 0
     if lay.res is not None:
         ldr, offr = lay.res
-        assert ldr == ldo and offr % 8 == 0 and (offr + lay.cout <= offo or offr >= offo + lay.cout)
-        res = (torch.randn((Mo, lay.cout), generator=g) * 0.5).half()
-        out_rows[:, offr:offr + lay.cout] = res
+        assert offr % 8 == 0 and offr + lay.cout <= ldr
+        if lay.res_own:                   # a buffer of its own, every channel of its rows random: row stride and offset are its own
+            res_rows = (torch.randn((Mo, ldr), generator=g) * 0.5).half()
+            res = res_rows[:, offr:offr + lay.cout].contiguous()
+            res_init = _plan_buffer(Mo, ldr, res_rows)
+        else:                             # a neighbouring slice of the output rows
+            assert ldr == ldo and (offr + lay.cout <= offo or offr >= offo + lay.cout)
+            res = (torch.randn((Mo, lay.cout), generator=g) * 0.5).half()
+            out_rows[:, offr:offr + lay.cout] = res
 
     # float64 reference on the fp16-rounded operands: the real Cin channels and the real Cout rows only
     xs = x_rows[:, offi:offi + lay.cin].reshape(B, H, W, lay.cin).double().permute(0, 3, 1, 2)
@@ -176,12 +184,20 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
                                        C.c_void_p(resid) if resid else None, ld_res, B, H, W, lay.cin_decl, lay.cout, k, s, lay.act,
                                        variant, stream)
 
+    res_buf = res_init.clone() if res_init is not None else None
+
+    def residual_of(out):
+        """Address of the residual slice for a launch that writes ``out``: in ``out`` itself, or in the separate buffer."""
+        if lay.res is None:
+            return 0
+        return (res_buf if lay.res_own else out).data_ptr() + 2 * lay.res[1]
+
     on_slice, on_contiguous = [], []
     for v in range(0, L.rva_conv_num_variants() + 1):
         name = (v, (L.rva_conv_variant_name(v) or b"?").decode())
         out = out_init.clone()
-        resid = out.data_ptr() + 2 * lay.res[1] if lay.res is not None else 0
-        rc = launch(v, x_buf, ldi, offi, out, ldo, offo, resid, ldo if resid else 0)
+        resid = residual_of(out)
+        rc = launch(v, x_buf, ldi, offi, out, ldo, offo, resid, ldr if resid else 0)
         if rc != N.RVA_ERR_ARG:
             assert rc == N.RVA_OK, (name, rc)
             torch.cuda.synchronize()                 # a HIP error ends the test here: nothing more is launched after it
@@ -189,10 +205,12 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
             got = out[:Mo * ldo].reshape(Mo, ldo)[:, offo:offo + lay.cout].double()
             assert_conv_close(got, want, res_dev, name)
             assert torch.equal(_bits(out)[untouched], _bits(out_init)[untouched]), (name, "wrote outside its output slice")
+            if res_buf is not None:
+                assert torch.equal(_bits(res_buf), _bits(res_init)), (name, "wrote to the residual buffer")
             if x_other is not None:
                 out2 = out_init.clone()
-                resid2 = out2.data_ptr() + 2 * lay.res[1] if lay.res is not None else 0
-                rc = launch(v, x_other, ldi, offi, out2, ldo, offo, resid2, ldo if resid2 else 0)
+                resid2 = residual_of(out2)
+                rc = launch(v, x_other, ldi, offi, out2, ldo, offo, resid2, ldr if resid2 else 0)
                 assert rc == N.RVA_OK, (name, rc)
                 torch.cuda.synchronize()
                 assert torch.equal(_bits(out2), _bits(out)), (name, "result depends on channels outside the declared slice")
@@ -227,13 +245,23 @@ NEVER_APPLIES = {}
 _forced = {}           # configuration -> [(desc, variant)] or the exception that ended it (never run twice)
 
 
-def _force_every_variant(key, monkeypatch):
+def _once(key, run):
+    """``run()`` for configuration ``key``, once per session: a configuration that failed is never run again."""
     if key in _forced:
         if isinstance(_forced[key], BaseException):
             pytest.fail(f"configuration {key} failed earlier in this session: {_forced[key]!r}")
         return _forced[key]
-    scale, batch, hw, env = CONFIGS[key]
     try:
+        _forced[key] = run()
+    except BaseException as exc:
+        _forced[key] = exc
+        raise
+    return _forced[key]
+
+
+def _force_every_variant(key, monkeypatch):
+    def run():
+        scale, batch, hw, env = CONFIGS[key]
         with monkeypatch.context() as mp:
             for name in _PLAN_ENV:
                 mp.delenv(name, raising=False)
@@ -243,14 +271,12 @@ def _force_every_variant(key, monkeypatch):
             plan = FusedYoloV8(net, batch, hw=hw, autotune=False)      # the tuning cache is not consulted
         x = torch.rand((batch, 3, *hw), device="cuda", generator=torch.Generator(device="cuda").manual_seed(17)).half()
         want = plan_rounded_reference(net, x)
-        _forced[key] = _run_forced(plan, x, want)
-    except BaseException as exc:
-        _forced[key] = exc
-        raise
-    return _forced[key]
+        return _run_forced(plan, x, lambda got: assert_matches_rounded_reference(got, want))
+    return _once(key, run)
 
 
-def _run_forced(plan, x, want):
+def _run_forced(plan, x, check):
+    """``check(got)`` raises AssertionError where the head tensor misses the configuration's condition; what it returns is printed."""
     L = N.lib()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -259,12 +285,12 @@ def _run_forced(plan, x, want):
         torch.cuda.synchronize()
         assert bool(torch.isfinite(got).all()), (what, "non-finite output")
         try:
-            return assert_matches_rounded_reference(got, want)
+            return check(got)
         except AssertionError as exc:
             raise AssertionError((what, *exc.args)) from None
 
     assert all(state["variant"] == 0 for _, state, _ in plan._tunable)
-    print("variant 0: box / score error", run_and_check("variant 0"))
+    print("variant 0:", run_and_check("variant 0"))
     ran = []
     try:
         for v in range(1, L.rva_conv_num_variants() + 1):
@@ -318,4 +344,107 @@ def test_forced_variants_cover_the_table(monkeypatch):
     assert rows - seen == set(NEVER_APPLIES), sorted(rows - seen)
     for v in range(33, 40):
         for prefix in ("up", "head1:", "head2:"):
+            assert any(pv == v and desc.startswith(prefix) for desc, pv in ran), (v, prefix)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Part 2 for the YOLOv5 builder: every row forced on the steps of real YOLOv5 plans
+# ---------------------------------------------------------------------------------------------------
+# scale, batch, (H, W).  Scale m is where c = 48 brings the padded Cin and the two-bottleneck neck blocks; 640 x 640 as above.
+V5_CONFIGS = {
+    "v5n": ("n", 3, (96, 160)),
+    "v5s": ("s", 3, (96, 160)),
+    "v5m": ("m", 3, (96, 160)),
+    "v5s-640": ("s", 1, (640, 640)),
+}
+
+# Rows that no convolution step of any YOLOv5 configuration above accepts, with the launcher's gate that keeps them out.
+NEVER_APPLIES_V5 = {}
+
+_v5_errors = {}        # configuration -> what is recorded as profiles/yolov5_variants.json
+
+
+@functools.lru_cache(maxsize=None)
+def _v5_net(scale):
+    """Seeded, BatchNorm folded, every parameter rounded to fp16 (kept as fp32), as ``_net()`` of tests/test_gpu_yolov5_plan.py:
+    the plan, the fp16 module and the float64 module hold the same numbers.  Shared, never modified."""
+    net = build_detector_net_v5(scale, seed=3).fuse()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(p.half().float())
+    return net
+
+
+def _record_v5(key, value):
+    out = os.environ.get("RVA_REPORT_DIR")
+    if out and Path(out).is_dir():
+        path = Path(out) / "yolov5_variants.json"
+        data = json.loads(path.read_text()) if path.exists() else {}
+        data[key] = value
+        path.write_text(json.dumps(data, indent=1, sort_keys=True))
+
+
+def _force_every_variant_v5(key, monkeypatch):
+    """The yardstick is the plan's own (tests/test_gpu_yolov5_plan.py): per row group at most twice the error of the same module
+    in PyTorch fp16 channels-last, both against the float64 module on the CPU.  Variant 0 is held to it first."""
+    def run():
+        scale, batch, hw = V5_CONFIGS[key]
+        net = _v5_net(scale)
+        with monkeypatch.context() as mp:
+            for name in _PLAN_ENV:
+                mp.delenv(name, raising=False)
+            plan = FusedYoloV5(copy.deepcopy(net), batch, hw=hw, autotune=False)      # the tuning cache is not consulted
+        x = torch.rand((batch, 3, *hw), generator=torch.Generator().manual_seed(17)).half()
+        with torch.inference_mode():
+            want = copy.deepcopy(net).double()(x.double()).transpose(1, 2).contiguous().cuda()
+            ref16 = copy.deepcopy(net).half().cuda().to(memory_format=torch.channels_last)
+            tor = ref16(x.cuda().contiguous(memory_format=torch.channels_last)).transpose(1, 2).double()
+        x = x.cuda()
+        rec = {}              # group -> the errors of variant 0, the largest error of any forced run and the row that gave it
+
+        def check(got):
+            errs = v5_head_errors(got.double(), tor, want)
+            for name, e in errs.items():
+                r = rec.setdefault(name, {"variant0_max_err": e["plan_max_err"], "torch_fp16_max_err": e["torch_fp16_max_err"],
+                                          "forced_max_err": 0.0, "forced_max_err_row": 0})
+                row = max((st["variant"] for _, st, _ in plan._tunable), default=0)
+                if row and e["plan_max_err"] > r["forced_max_err"]:
+                    r["forced_max_err"], r["forced_max_err_row"] = e["plan_max_err"], row
+            bad = v5_groups_over_twice_torch(errs)
+            assert not bad, ("plan error over twice PyTorch fp16's (group, plan, PyTorch)", bad)
+            return {name: (e["plan_max_err"], e["torch_fp16_max_err"]) for name, e in errs.items()}
+        try:
+            ran = _run_forced(plan, x, check)
+        finally:
+            for name, r in rec.items():
+                print(f"[{key}] {name}: variant 0 max |d| {r['variant0_max_err']:.4g}, forced rows max |d| {r['forced_max_err']:.4g} "
+                      f"(row {r['forced_max_err_row']}), PyTorch fp16 max |d| {r['torch_fp16_max_err']:.4g}")
+        _v5_errors[key] = {"scale": scale, "batch": batch, "hw": list(hw), "step_variant_pairs": len(ran),
+                           "distinct_rows": len({v for _, v in ran}), "groups": rec}
+        _record_v5(key, _v5_errors[key])
+        return ran
+    return _once(key, run)
+
+
+@pytest.mark.parametrize("key", list(V5_CONFIGS))
+def test_every_variant_forced_on_the_yolov5_plan_steps(key, monkeypatch):
+    """Variant v on every step of a YOLOv5 plan that accepts it (0 on the rest), for every v: each row group of the head tensor
+    stays within twice PyTorch fp16's error against the float64 module, as variant 0 must; non-finite output fails."""
+    ran = _force_every_variant_v5(key, monkeypatch)
+    print(f"{key}: {len(ran)} (step, variant) pairs forced, {len({v for _, v in ran})} distinct rows")
+    assert ran
+
+
+def test_forced_variants_cover_the_table_on_yolov5(monkeypatch):
+    """Over the YOLOv5 configurations every row ran on a real plan step, but for the rows listed in NEVER_APPLIES_V5; each
+    LDS-DMA gather tile (33..39) ran on an upsample + concat step and on a fused head step."""
+    per_key = {key: _force_every_variant_v5(key, monkeypatch) for key in V5_CONFIGS}
+    for key, ran in per_key.items():
+        print(f"{key}: {len(ran)} (step, variant) pairs")
+    ran = [pair for pairs in per_key.values() for pair in pairs]
+    rows = set(range(1, N.lib().rva_conv_num_variants() + 1))
+    seen = {v for _, v in ran}
+    assert rows - seen == set(NEVER_APPLIES_V5), sorted(rows - seen)
+    for v in range(33, 40):
+        for prefix in ("up", "head5:"):
             assert any(pv == v and desc.startswith(prefix) for desc, pv in ran), (v, prefix)
