@@ -573,6 +573,10 @@ int rva_yolov8_plan_run_lanes_n(rva_yolov8_plan *plan, const void *input, void *
 int rva_yolov8_plan_run_range_n(rva_yolov8_plan *plan, const void *input, void *output, int n, int first, int last, rva_stream_t stream);
 int rva_yolov8_plan_primed_images(const rva_yolov8_plan *plan);
 int rva_yolov8_plan_step_rows(const rva_yolov8_plan *plan, int step, int32_t *y0, int32_t *y1);
+/* What step `step` (0 .. n_steps - 1) of the launch list is, for reports and tests: the tunable description of a convolution
+ * step ("64->128 k3s2 80x80", with its row window), else the kernel and its shape: "attention heads 2 tokens 400",
+ * "dwconv3x3 64 act1 80x80", "sppf pool3 128 20x20", "stem 3->16 k3s2 640x640", "head3 decode". */
+int rva_yolov8_plan_step_desc(const rva_yolov8_plan *plan, int step, char *buf, int len);
 
 /* ----------------------------------------------------------------------------------------------
  * YOLOv5 (v6.0 - v7.0 architecture, n / s / m / l; `model_type: yolov5`, whose objectness rule the reference's post-process
@@ -629,6 +633,61 @@ int rva_conv_rows_through_pad(int k, int stride, int pad, int H_in, int lo, int 
 int rva_conv1x1_head5_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, int batch, int H, int W,
                           int Cin, int nc, const float *anchors_px, void *out, float *boxes32, int anchors_total, int anchor_offset,
                           float stride_px, int variant, rva_stream_t stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * YOLO11 (n / s / m / l of Ultralytics 8.3, the `yolo11<scale>` file names; there is no model_type of its own) as a third graph
+ * builder for the SAME plan object: every rva_yolov8_plan_* entry point above works on a plan made by rva_yolo11_plan_create
+ * unchanged.  fp16 only (RVA_PLAN_F32: RVA_ERR_ARG); RVA_PLAN_BOX_F32, RVA_PLAN_NO_STEM2 and RVA_PLAN_NO_CIN_PAD as above; the
+ * other flags have no effect.  There are no detect lanes: _run_lanes is _run.  Output: YOLOv8's fp16 [batch, 4+nc, anchors].
+ *
+ * Graph (layer numbers of yolo11.yaml; w1..w5 = widths):
+ *   0 stem 3x3 s2 w1 | 1 3x3 s2 w2 | 2 C3k2 w3 (e 0.25) | 3 3x3 s2 w3 | 4 C3k2 w4 (e 0.25) | 5 3x3 s2 w4 | 6 C3k2 w4 | 7 3x3 s2 w5 |
+ *   8 C3k2 w5 | 9 SPPF | 10 C2PSA | 13 C3k2(cat[up(10), 6]) w4 | 16 C3k2(cat[up(13), 4]) w3 | 17 3x3 s2 | 19 C3k2(cat[17, 13]) w4 |
+ *   20 3x3 s2 | 22 C3k2(cat[20, 10]) w5 | detect(16, 19, 22): box = 3x3, 3x3, 1x1 (64) as YOLOv8; cls = dw3x3, 1x1, dw3x3, 1x1, 1x1 (nc).
+ *   C3k2(c2, e): c = c2 * e; cv1 1x1 -> 2c; n inner blocks on the last chunk; cv2 1x1 (2 + n) c -> c2.  Inner block: a
+ *   bottleneck 3x3 c -> c/2, 3x3 c/2 -> c, or with c3k a C3 at width c/2 with two bottlenecks 3x3, 3x3 (it writes its cv3 into the
+ *   outer concat slice).  The shortcut is added in layers 2-8 and not behind them.
+ *   C2PSA: cv1 1x1 w5 -> [a | b] (two launches: `a` goes into cv2's input buffer, `b` into its own), psa_blocks times
+ *   b <- b + proj(attention(qkv(b)) + pe(v)); b <- b + ffn1(ffn0(b)), the last one into cv2's input buffer; cv2 1x1.
+ *   qkv / proj / ffn are rva_conv2d_nhwc_f16 (proj and ffn1 with act 0 and the residual); attention is rva_psa_attention_f16 on
+ *   the qkv buffer as the convolution wrote it; pe is rva_dwconv3x3_nhwc_f16 once per head on the head's v slice with the head's
+ *   attention output as the residual (a head's 64 v channels are contiguous, the heads' are not).
+ * Module order of `convs`: layers 0..22 in order, then per level box[l][0..2], then per level cls[l] = dw, 1x1, dw, 1x1, 1x1;
+ *   C3k2(x) = cv1, cv2, then per inner block cv1, cv2 (bottleneck) or cv1, cv2, cv3, m0.cv1, m0.cv2, m1.cv1, m1.cv2 (C3k);
+ *   SPPF = cv1, cv2; C2PSA = cv1, cv2, then per block qkv, proj, pe, ffn0, ffn1.  A depthwise convolution is an
+ *   rva_conv_weights with cin = 1: weight [C][1][3][3].
+ * Refused (RVA_ERR_ARG): height or width not a multiple of 32, nc outside 1..1024, widths not multiples of 8, RVA_PLAN_F32,
+ *   psa_heads * 64 != w5 / 2, w1 > 64 ("stem wider than 64 channels": scale x).
+ *
+ * rva_dwconv3x3_nhwc_f16: out[n,y,x,c] = [SiLU](sum_{ky,kx} in[n,y+ky-1,x+kx-1,c] * w[c][ky][kx] + bias[c]) [+ residual[n,y,x,c]]
+ *   on NHWC fp16 channel slices (row strides ldi, ldo, ldr in elements), stride 1, zero padding.  weights: fp16 [9][C], tap
+ *   ky * 3 + kx major (the transpose of the checkpoint's [C][1][3][3]: a lane's 8 channels of a tap are one 16-byte load);
+ *   bias fp32 [C]; residual NULL = none; act 1 = SiLU, 0 = none.  The nine products are added in fp32 from zero in the order
+ *   (ky, kx), then the bias, SiLU, the residual; one rounding to fp16.  RVA_ERR_ARG before any launch unless batch, H, W > 0,
+ *   C % 8 == 0, ldi / ldo / ldr >= C and multiples of 8, and every pointer 16-byte aligned.  `out` may not overlap `in`.
+ * rva_psa_attention_f16: multi-head self-attention over `tokens` positions.  qkv fp16 [batch, tokens, ld]: head h owns channels
+ *   [128 h, 128 h + 128) = q 32 | k 32 | v 64 -- what the qkv 1x1 convolution writes in NHWC.  out fp16 [batch, tokens, ldo], head
+ *   h at channels [64 h, 64 h + 64).  Per (image, head, query): S = q . k (v_mfma_f32_32x32x16_f16, fp32), * 32^-0.5 in fp32,
+ *   max-subtracted softmax in fp32 (online over key tiles of 32 in order; keys >= tokens are masked and never read), P rounded
+ *   to fp16, O = P V with fp32 accumulators, O / (fp32 row sum), one rounding to fp16.  The order of every sum depends on
+ *   `tokens` alone: an image's result does not depend on batch.  RVA_ERR_ARG before any launch unless batch, tokens, heads >= 1,
+ *   ld >= 128 heads, ldo >= 64 heads, ld and ldo multiples of 8, and both pointers 16-byte aligned.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_yolo11_desc {
+    int32_t batch, height, width;     /* input tensor; height and width multiples of 32 */
+    int32_t widths[5];                /* w1..w5 (YOLO11n: 16 32 64 128 256); w1 <= 64 */
+    int32_t repeats[8];               /* inner blocks of the C3k2 layers 2, 4, 6, 8, 13, 16, 19, 22 (YOLO11n: all 1) */
+    int32_t c3k[8];                   /* ... and whether they are C3k (YOLO11n / s: 0 0 1 1 0 0 0 1; m / l: all 1) */
+    int32_t psa_blocks, psa_heads;    /* C2PSA: blocks (1; l: 2) and heads = w5 / 128 */
+    int32_t nc;                       /* classes, 1..1024 */
+    int32_t n_convs;                  /* length of `convs` */
+    int32_t flags;
+} rva_yolo11_desc;
+int rva_yolo11_plan_create(rva_ctx *ctx, const rva_yolo11_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out);
+int rva_dwconv3x3_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out, int ldo,
+                           const void *residual, int ldr, int batch, int H, int W, int C, int act, rva_stream_t stream);
+int rva_psa_attention_f16(rva_ctx *ctx, const void *qkv, int ld, void *out, int ldo, int batch, int tokens, int heads,
+                          rva_stream_t stream);
 
 /* ----------------------------------------------------------------------------------------------
  * The CNN-LSTM clip network as ONE fp32 object -- replaces the network call of the reference's CNN-LSTM head

@@ -18,7 +18,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
-SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_plan.hip", "rva_clip.hip",
+SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_attn.hip", "rva_plan.hip", "rva_clip.hip",
            "rva_clip3d.hip", "rva_clip3d_f16.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -54,6 +54,13 @@ class YoloV5Desc(C.Structure):
     _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("widths", C.c_int32 * 5),
                 ("depth_backbone", C.c_int32 * 4), ("depth_head", C.c_int32), ("nc", C.c_int32), ("anchors", C.c_float * 18),
                 ("n_convs", C.c_int32), ("flags", C.c_int32)]
+
+
+class Yolo11Desc(C.Structure):
+    """``rva_yolo11_desc`` (include/rva.h)."""
+    _fields_ = [("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("widths", C.c_int32 * 5),
+                ("repeats", C.c_int32 * 8), ("c3k", C.c_int32 * 8), ("psa_blocks", C.c_int32), ("psa_heads", C.c_int32),
+                ("nc", C.c_int32), ("n_convs", C.c_int32), ("flags", C.c_int32)]
 
 
 class ConvWeights(C.Structure):
@@ -277,6 +284,10 @@ def lib() -> C.CDLL:
         "rva_conv_rows_through_pad": (C.c_int, [C.c_int] * 6 + [i32p, i32p]),
         "rva_conv1x1_head5_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
                                             C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+        "rva_yolov8_plan_step_desc": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int]),
+        "rva_yolo11_plan_create": (C.c_int, [_P, C.POINTER(Yolo11Desc), C.POINTER(ConvWeights), C.POINTER(_P)]),
+        "rva_dwconv3x3_nhwc_f16": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int] + [C.c_int] * 5 + [_P]),
+        "rva_psa_attention_f16": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
         "rva_cnnlstm_plan_create": (C.c_int, [_P, C.POINTER(CnnLstmDesc), C.POINTER(CnnLstmWeights), C.POINTER(_P)]),
         "rva_cnnlstm_plan_destroy": (None, [_P]),
         "rva_cnnlstm_plan_info": (C.c_int, [_P, i32p, i32p, i32p, i32p]),
@@ -361,6 +372,7 @@ EXPORTS = [
     "rva_resnet_f16_plan_info", "rva_resnet_f16_plan_run", "rva_resnet_f16_plan_run_post", "rva_resnet_f16_plan_stage", "rva_jpeg_max_bytes", "rva_jpeg_encode_bgr", "rva_jpeg_status",
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
     "rva_yolov5_plan_create", "rva_stem6_conv_f16", "rva_stem6_conv_f16_rows", "rva_conv_rows_through_pad", "rva_conv1x1_head5_f16",
+    "rva_yolo11_plan_create", "rva_dwconv3x3_nhwc_f16", "rva_psa_attention_f16", "rva_yolov8_plan_step_desc",
 ]
 
 

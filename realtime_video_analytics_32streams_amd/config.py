@@ -22,13 +22,18 @@ configured precision, or construction fails with ``ValueError`` (an ``infer_fn``
     yolov8 architecture     as plan: engine "fused-f32"       as plan: engine "fused"
     yolov5 architecture     ValueError (no fp32 plan; also    as plan: engine "fused" (the fp16 YOLOv5 plan,
                             under plan; auto: PyTorch-ROCm)   engine.FusedYoloV5)
+    yolo11 architecture     ValueError (no fp32 plan; also    as plan: engine "fused" (the fp16 YOLO11 plan,
+                            under plan; auto: PyTorch-ROCm)   engine.FusedYolo11)
     cnn_lstm                as plan: engine "clip-f32"        ValueError (the plan is fp32 only) unless hip_lstm_fp16: true
     3d_cnn / slow_fast      engine "clip3d-f32"               ValueError (the plan is fp32 only) unless hip_clip_fp16: true
     conv_gru                ValueError (the reference defines no architecture, so there is no plan)
     resnet                  ValueError (no hand-written plan) ValueError (no hand-written plan) unless hip_resnet_fp16: true
 
 Which YOLO architecture a ``yolov5`` / ``yolov8`` detector builds is no key of its own: it follows what the user handed over
-(``detector.detector_architecture``).  YOLOv5 (v6.0 - v7.0, anchor-based head) when ``model_path`` is an existing state dict with
+(``detector.detector_architecture``).  YOLO11 (the ``yolo11<n|s|m|l>`` files of Ultralytics 8.3; head tensor as YOLOv8's), checked
+first and under either ``model_type``, when ``model_path`` is an existing state dict with the attention convolution of C2PSA
+(``model.10.m.0.attn.qkv.conv.weight``), or when the file name starts with ``yolo11`` / ``yolov11`` plus a scale letter while no such
+file exists (seeded weights, logged as such; scale x has no plan).  YOLOv5 (v6.0 - v7.0, anchor-based head) when ``model_path`` is an existing state dict with
 the YOLOv5 detect convolution (``model.24.m.0.weight``), or when ``model_type`` is ``yolov5`` and the file name starts with
 ``yolov5<n|s|m|l>`` while no such file exists (seeded weights, logged as such); YOLOv8 in every other case, as before -- ``model_type:
 yolov5`` with the default ``yolov8n.pt``, every ``yolov8*`` name, and the ``yolov5*u`` names (anchor-free re-exports with the v8 head).

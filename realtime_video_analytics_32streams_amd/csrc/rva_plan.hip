@@ -34,6 +34,10 @@
 // Module order of `convs` (what create() consumes, checked against the descriptor): b0, b1, C2f(b2), b3, C2f(b4), b5, C2f(b6), b7,
 // C2f(b8), SPPF(b9) = cv1, cv2, C2f(h12), C2f(h15), h16, C2f(h18), h19, C2f(h21), then per level l = 0..2: box[l][0..2], then per
 // level: cls[l][0..2];  C2f(x) = cv1, cv2, then per bottleneck: cv1, cv2.
+//
+// rva_yolov5_plan_create and rva_yolo11_plan_create lay down the graphs of YOLOv5 and YOLO11 for the same plan object
+// (Builder::build_v5 / build_11; the graphs and module orders are in include/rva.h).  YOLO11 adds two step kinds, K_DWCONV and
+// K_ATTN (rva_attn.hip): fixed kernels like the pooling steps, and in propagate_rows always the whole map -- attention is global.
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -43,7 +47,7 @@
 namespace {
 
 enum StepKind { K_CONV, K_UPCAT, K_HEAD, K_STEM2, K_STEM, K_SPPF3, K_POOL5, K_UP2, K_HEAD3, K_PAIR32,
-                K_CONV_F32, K_STEM_F32, K_POOL5_F32, K_UP2_F32, K_HEAD_F32, K_STEM6, K_HEAD5 };
+                K_CONV_F32, K_STEM_F32, K_POOL5_F32, K_UP2_F32, K_HEAD_F32, K_STEM6, K_HEAD5, K_DWCONV, K_ATTN };
 
 struct View {           // a channel slice of an NHWC buffer (es = bytes per element: 2 fp16, 4 fp32)
     char *base = nullptr; int ld = 0, off = 0, ch = 0, es = 2;
@@ -317,7 +321,9 @@ struct Builder {
     // one sibling launch writes cat[0, 2c) = [cv1 out | cv2 out]; the bottlenecks x <- x + cv2_3x3(cv1_1x1(x)) start from cv1 out,
     // the last one writes cat[2c, 3c), and cv3 reads cat[c, 3c) = [cv2 out | m out] with the halves of its input channels swapped
     // on the host (the module concatenates [m out | cv2 out]).
-    bool c3(int c1, int c2, int n, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w, const char *what)
+    // k1: kernel of every bottleneck's first convolution (1: YOLOv5's C3; 3: YOLO11's C3k, whose bottlenecks are 3x3, 3x3)
+    bool c3(int c1, int c2, int n, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w, const char *what,
+            int k1 = 1)
     {
         const int c = c2 / 2;
         const long m = (long)p->B * h * w;
@@ -330,7 +336,7 @@ struct Builder {
         else if (!conv(cv, 2, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
         View x = cat.sub(0, c);
         for (int i = 0; i < n; ++i) {
-            const rva_conv_weights *b1 = take(c, c, 1, 1, what), *b2 = take(c, c, 3, 1, what);
+            const rva_conv_weights *b1 = take(c, c, k1, 1, what), *b2 = take(c, c, 3, 1, what);
             // intermediate and output of every bottleneck in buffers of their own: with row windows a step rewrites part of its
             // output only, and the rest must still be what THIS bottleneck left there (see c2f)
             View tmp = buf(m, c), y = i == n - 1 ? cat.sub(2 * c, c) : buf(m, c);
@@ -345,6 +351,258 @@ struct Builder {
         rva_conv_weights q = *cv3;
         q.weight = sw.data();
         return conv1(&pad_convs.emplace_back(q), cat.sub(c, 2 * c), dst, h, w, 1);
+    }
+
+    // fp16 stem from the planar input K1 writes, and the 3x3 s2 behind it: x1 = b1(b0(input)).  Stem weights [64][32] fp16, column
+    // order k = 2 j + kx (kx in {0, 1}), k = 18 + j (kx = 2), j = c*3 + ky
+    bool stem_f16(const rva_conv_weights *b0, const rva_conv_weights *b1, View *x1)
+    {
+        const rva_yolov8_desc &d = p->d;
+        const int B = d.batch, H = d.height, W = d.width, c1 = d.widths[0], c2 = d.widths[1];
+        const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4;
+        if (c1 > 64) return fail("stem wider than 64 channels");
+        if (!b0->weight) return fail("b0: no stem convolution");
+        std::vector<_Float16> sw(64 * 32, (_Float16)0.f);
+        std::vector<float> sb(64, 0.f);
+        for (int co = 0; co < c1; ++co) {
+            for (int j = 0; j < 9; ++j)                       // j = c*3 + ky;  weight[co][c][ky][kx]
+                for (int kx = 0; kx < 3; ++kx) {
+                    const float v = b0->weight[((size_t)co * 3 + j / 3) * 9 + (j % 3) * 3 + kx];
+                    sw[co * 32 + (kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)v;
+                }
+            if (b0->bias) sb[co] = b0->bias[co];
+        }
+        void *dsw = dev_alloc(sw.size() * 2, false), *dsb = dev_alloc(sb.size() * 4, false);
+        if (!dsw || !dsb) return false;
+        if (hipMemcpy(dsw, sw.data(), sw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dsb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("stem upload failed");
+        *x1 = buf((long)B * h2 * w2, c2);
+        if (!x1->base) return false;
+        p->fused_stem = c1 == 32 && c2 == 64 && !(d.flags & RVA_PLAN_NO_STEM2);
+        if (p->fused_stem) {
+            Step s{}; s.kind = K_STEM2; s.w = dsw; s.b = (const float *)dsb; s.out = x1->ptr(); s.ldo = x1->ld; s.H = H; s.W = W;
+            int ci, co, k, st;
+            if (!pack(&b1, 1, &s.w2, &s.b2, &ci, &co, &k, &st)) return false;
+            push(s, nullptr);
+            return true;
+        }
+        View x0 = buf((long)B * h1 * w1, c1);
+        if (!x0.base) return false;
+        Step s{}; s.kind = K_STEM; s.w = dsw; s.b = (const float *)dsb; s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
+        push(s, nullptr);
+        return conv1(b1, x0, *x1, h1, w1, 1);
+    }
+
+    // SPPF: cv1, three chained 5x5 max pools into the slices of one concat buffer, cv2
+    bool sppf(int c5, View src, View dst, int h5, int w5)
+    {
+        const int c_ = c5 / 2;
+        const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
+        View cat = buf((long)p->B * h5 * w5, 4 * c_);
+        if (!cat.base || !conv1(cv1, src, cat.sub(0, c_), h5, w5, 1)) return false;
+        if (h5 * w5 <= 2400 && !p->f32) {
+            Step s{}; s.kind = K_SPPF3; s.in = cat.sub(0, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub(c_, c_).ptr(); s.out2 = cat.sub(2 * c_, c_).ptr();
+            s.out3 = cat.sub(3 * c_, c_).ptr(); s.ldo = cat.ld; s.H = h5; s.W = w5; s.Cin = c_;
+            push(s, nullptr);
+        } else {
+            for (int i = 0; i < 3; ++i) {
+                Step s{}; s.kind = p->f32 ? K_POOL5_F32 : K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
+                s.H = h5; s.W = w5; s.Cin = c_;
+                push(s, nullptr);
+            }
+        }
+        return conv1(cv2, cat, dst, h5, w5, 1);
+    }
+
+    // Depthwise 3x3 (rva_dwconv3x3_nhwc_f16) over channels [c_off, c_off + dst.ch) of `c` (weight [C][1][3][3]): weights repacked
+    // [9][dst.ch] fp16 (tap major).  Untunable; always the whole map.
+    bool dwconv(const rva_conv_weights *c, int c_off, View src, View dst, int h, int w, int act, const View *res = nullptr)
+    {
+        const int C = dst.ch;
+        if (!c) return false;
+        if (!c->weight || c->cin != 1 || c->k != 3 || c->stride != 1 || c_off < 0 || c_off + C > c->cout || src.ch != C || C % 8)
+            return fail("depthwise convolution does not fit its buffers");
+        std::vector<_Float16> hw((size_t)9 * C);
+        std::vector<float> hb(C, 0.f);
+        for (int ch = 0; ch < C; ++ch) {
+            for (int t = 0; t < 9; ++t) hw[(size_t)t * C + ch] = (_Float16)c->weight[(size_t)(c_off + ch) * 9 + t];
+            if (c->bias) hb[ch] = c->bias[c_off + ch];
+        }
+        Step s{}; s.kind = K_DWCONV;
+        const void *db = nullptr;
+        if (!upload(hw.data(), hw.size() * 2, &s.w) || !upload(hb.data(), hb.size() * 4, &db)) return false;
+        s.b = (const float *)db;
+        s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.Cin = s.Cout = C; s.k = 3; s.stride = 1; s.act = act;
+        if (res) { s.res = res->ptr(); s.ldr = res->ld; }
+        push(s, nullptr);
+        return true;
+    }
+
+    // YOLO11's C3k2: a C2f with c = c2 / 4 (quarter) or c2 / 2 whose inner blocks are bottlenecks 3x3 c -> c/2, 3x3 c/2 -> c, or
+    // with c3k a C3 at width c / 2 with two 3x3, 3x3 bottlenecks, which writes its cv3 into the outer concat slice.  src as for c2f.
+    bool c3k2(int c1, int c2, int n, bool c3k, bool quarter, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w,
+              const char *what)
+    {
+        const int c = quarter ? c2 / 4 : c2 / 2;
+        const long m = (long)p->B * h * w;
+        if (n < 1 || c % 16) return fail("a C3k2 block needs at least one inner block and an inner width that is a multiple of 16");
+        const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, what), *cv2 = take((2 + n) * c, c2, 1, 1, what);
+        if (!cv1 || !cv2) return false;
+        View cat = buf(m, (2 + n) * c);
+        if (!cat.base) return false;
+        if (low) { if (!upcat(cv1, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
+        else if (!conv1(cv1, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
+        for (int i = 0; i < n; ++i) {
+            View x = cat.sub((1 + i) * c, c), y = cat.sub((2 + i) * c, c);
+            if (c3k) {
+                if (!c3(c, c, 2, shortcut, &x, nullptr, nullptr, y, h, w, what, 3)) return false;
+                continue;
+            }
+            const rva_conv_weights *b1 = take(c, c / 2, 3, 1, what), *b2 = take(c / 2, c, 3, 1, what);
+            View tmp = buf(m, c / 2);                       // one per bottleneck, as in c2f
+            if (!tmp.base || !conv1(b1, x, tmp, h, w, 1) || !conv1(b2, tmp, y, h, w, 1, shortcut ? &x : nullptr)) return false;
+        }
+        return conv1(cv2, cat, dst, h, w, 1);
+    }
+
+    // YOLO11's C2PSA.  Every buffer slice has ONE writer (a windowed convolution rewrites part of its output only, see c2f), so
+    // cv1 runs as two launches: `a` goes straight into cv2's input buffer, `b` into a buffer of its own, and the last block's
+    // ffn writes the other half of cv2's input.  Attention and the positional encoding always run the whole map.
+    bool c2psa(int c1, int n, int heads, View src, View dst, int h, int w)
+    {
+        const int c = c1 / 2;
+        const long m = (long)p->B * h * w;
+        if (n < 1 || heads * 64 != c) return fail("C2PSA: psa_heads * 64 must be half the width of the block, and psa_blocks >= 1");
+        const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, "10.cv1"), *cv2 = take(2 * c, c1, 1, 1, "10.cv2");
+        if (!cv1 || !cv2) return false;
+        if (!cv1->weight) return fail("convolution without weights");
+        rva_conv_weights qa = *cv1, qb = *cv1;
+        qa.cout = qb.cout = c;
+        qb.weight = cv1->weight + (size_t)c * c1;
+        if (cv1->bias) qb.bias = cv1->bias + c;
+        View cat = buf(m, 2 * c), x = buf(m, c);
+        if (!cat.base || !x.base) return false;
+        if (!conv1(&pad_convs.emplace_back(qa), src, cat.sub(0, c), h, w, 1) || !conv1(&pad_convs.emplace_back(qb), src, x, h, w, 1)) return false;
+        for (int i = 0; i < n; ++i) {
+            const rva_conv_weights *qkv = take(c, 2 * c, 1, 1, "10.attn.qkv"), *proj = take(c, c, 1, 1, "10.attn.proj"), *pe = take(1, c, 3, 1, "10.attn.pe"),
+                                   *f0 = take(c, 2 * c, 1, 1, "10.ffn.0"), *f1 = take(2 * c, c, 1, 1, "10.ffn.1");
+            if (!qkv || !proj || !pe || !f0 || !f1) return false;
+            View q = buf(m, 2 * c), ao = buf(m, c), xo = buf(m, c), x1 = buf(m, c), f = buf(m, 2 * c);
+            View y = i == n - 1 ? cat.sub(c, c) : buf(m, c);
+            if (!q.base || !ao.base || !xo.base || !x1.base || !f.base || !y.base) return false;
+            if (!conv1(qkv, x, q, h, w, 0)) return false;
+            Step s{}; s.kind = K_ATTN; s.in = q.ptr(); s.ldi = q.ld; s.out = ao.ptr(); s.ldo = ao.ld; s.H = h; s.W = w; s.Cin = 2 * c; s.Cout = c; s.mode = heads;
+            push(s, nullptr);
+            for (int hd = 0; hd < heads; ++hd) {            // a head's v slice is contiguous, the heads' are not: one launch per head
+                const View r = ao.sub(64 * hd, 64);
+                if (!dwconv(pe, 64 * hd, q.sub(128 * hd + 64, 64), xo.sub(64 * hd, 64), h, w, 0, &r)) return false;
+            }
+            if (!conv1(proj, xo, x1, h, w, 0, &x)) return false;
+            if (!conv1(f0, x1, f, h, w, 1) || !conv1(f1, f, y, h, w, 0, &x1)) return false;
+            x = y;
+        }
+        return conv1(cv2, cat, dst, h, w, 1);
+    }
+
+    bool build_11(const rva_yolo11_desc &e)
+    {
+        const rva_yolov8_desc &d = p->d;
+        const int B = d.batch, H = d.height, W = d.width;
+        const int c1 = d.widths[0], c2 = d.widths[1], c3w = d.widths[2], c4 = d.widths[3], c5 = d.widths[4];
+        const int h2 = H / 4, w2 = W / 4, h3 = H / 8, w3 = W / 8, h4 = H / 16, w4 = W / 16, h5 = H / 32, w5 = W / 32;
+        const rva_conv_weights *b0 = take(3, c1, 3, 2, "0"), *b1 = take(c1, c2, 3, 2, "1");
+        View x1;
+        if (!b0 || !b1 || !stem_f16(b0, b1, &x1)) return false;
+        auto block = [&](int i, int ci, int co, bool quarter, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w,
+                         const char *what) {
+            return c3k2(ci, co, e.repeats[i], e.c3k[i] != 0, quarter, shortcut, src, low, skip, dst, h, w, what);
+        };
+        // concat buffers of the neck: producers write their slice directly.  cat13 = [up(p5) | p4], cat16 = [up(n4) | p3],
+        // cat19 = [17 | n4], cat22 = [20 | p5]
+        View cat13 = buf((long)B * h4 * w4, c5 + c4), cat16 = buf((long)B * h3 * w3, c4 + c4), cat19 = buf((long)B * h4 * w4, c3w + c4),
+             cat22 = buf((long)B * h5 * w5, c4 + c5);
+        if (!cat13.base || !cat16.base || !cat19.base || !cat22.base) return false;
+        View p4 = cat13.sub(c5, c4), p3 = cat16.sub(c4, c4), n4 = cat19.sub(c3w, c4), p5 = cat22.sub(c4, c5);
+        View x2 = buf((long)B * h2 * w2, c3w), t3 = buf((long)B * h3 * w3, c3w), t4 = buf((long)B * h4 * w4, c4);
+        if (!x2.base || !t3.base || !t4.base) return false;
+        if (!block(0, c2, c3w, true, true, &x1, nullptr, nullptr, x2, h2, w2, "2")) return false;
+        if (!conv1(take(c3w, c3w, 3, 2, "3"), x2, t3, h2, w2, 1)) return false;
+        if (!block(1, c3w, c4, true, true, &t3, nullptr, nullptr, p3, h3, w3, "4")) return false;
+        if (!conv1(take(c4, c4, 3, 2, "5"), p3, t4, h3, w3, 1)) return false;
+        if (!block(2, c4, c4, false, true, &t4, nullptr, nullptr, p4, h4, w4, "6")) return false;
+        View t5 = buf((long)B * h5 * w5, c5), t5b = buf((long)B * h5 * w5, c5), t5c = buf((long)B * h5 * w5, c5);
+        p->quiet_step = (int)p->steps.size();
+        if (!t5.base || !t5b.base || !t5c.base || !conv1(take(c4, c5, 3, 2, "7"), p4, t5, h4, w4, 1)) return false;
+        if (!block(3, c5, c5, false, true, &t5, nullptr, nullptr, t5b, h5, w5, "8")) return false;
+        if (!sppf(c5, t5b, t5c, h5, w5)) return false;
+        if (!c2psa(c5, e.psa_blocks, e.psa_heads, t5c, p5, h5, w5)) return false;
+        View n3 = buf((long)B * h3 * w3, c3w);
+        if (!n3.base) return false;
+        if (c5 % 64 == 0 && c4 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4) {
+            // FPN top-down path: upsample + concat folded into the consuming 1x1 convolutions (rva_conv1x1_upcat_f16)
+            if (!block(4, c5 + c4, c4, false, false, nullptr, &p5, &p4, n4, h4, w4, "13")) return false;
+            if (!block(5, c4 + c4, c3w, false, false, nullptr, &n4, &p3, n3, h3, w3, "16")) return false;
+        } else {
+            Step u1{}; u1.kind = K_UP2; u1.in = p5.ptr(); u1.ldi = p5.ld; u1.out = cat13.sub(0, c5).ptr(); u1.ldo = cat13.ld; u1.H = h5; u1.W = w5; u1.Cin = c5;
+            push(u1, nullptr);
+            if (!block(4, c5 + c4, c4, false, false, &cat13, nullptr, nullptr, n4, h4, w4, "13")) return false;
+            Step u2{}; u2.kind = K_UP2; u2.in = n4.ptr(); u2.ldi = n4.ld; u2.out = cat16.sub(0, c4).ptr(); u2.ldo = cat16.ld; u2.H = h4; u2.W = w4; u2.Cin = c4;
+            push(u2, nullptr);
+            if (!block(5, c4 + c4, c3w, false, false, &cat16, nullptr, nullptr, n3, h3, w3, "16")) return false;
+        }
+        if (!conv1(take(c3w, c3w, 3, 2, "17"), n3, cat19.sub(0, c3w), h3, w3, 1)) return false;
+        View m4 = buf((long)B * h4 * w4, c4), m5 = buf((long)B * h5 * w5, c5);
+        if (!m4.base || !m5.base) return false;
+        if (!block(6, c3w + c4, c4, false, false, &cat19, nullptr, nullptr, m4, h4, w4, "19")) return false;
+        if (!conv1(take(c4, c4, 3, 2, "20"), m4, cat22.sub(0, c4), h4, w4, 1)) return false;
+        if (!block(7, c4 + c5, c5, false, false, &cat22, nullptr, nullptr, m5, h5, w5, "22")) return false;
+        // detect head: the box branch is YOLOv8's; the class branch is dw3x3, 1x1, dw3x3, 1x1, 1x1 with its interior width rounded
+        // up to 8 (zero-extended weights: a pad channel is SiLU(0) = 0 through the depthwise steps and meets zero weights)
+        int cb = c3w / 4 > 64 ? c3w / 4 : 64;
+        const int ncm = d.nc < 100 ? d.nc : 100, cc_real = c3w > ncm ? c3w : ncm;
+        const int cc = (cc_real + 7) / 8 * 8, ncp = (d.nc + 7) / 8 * 8;
+        p->A = h3 * w3 + h4 * w4 + h5 * w5;
+        const rva_conv_weights *box[3][3], *cls[3][5];
+        const int chs[3] = {c3w, c4, c5};
+        for (int l = 0; l < 3; ++l) {
+            box[l][0] = take(chs[l], cb, 3, 1, "detect.box.0"); box[l][1] = take(cb, cb, 3, 1, "detect.box.1"); box[l][2] = take(cb, 64, 1, 1, "detect.box.2");
+            if (!box[l][0] || !box[l][1] || !box[l][2]) return false;
+        }
+        for (int l = 0; l < 3; ++l) {
+            cls[l][0] = take(1, chs[l], 3, 1, "detect.cls.0.0"); cls[l][1] = take(chs[l], cc_real, 1, 1, "detect.cls.0.1");
+            cls[l][2] = take(1, cc_real, 3, 1, "detect.cls.1.0"); cls[l][3] = take(cc_real, cc_real, 1, 1, "detect.cls.1.1");
+            cls[l][4] = take(cc_real, d.nc, 1, 1, "detect.cls.2");
+            for (int i = 0; i < 5; ++i)
+                if (!cls[l][i]) return false;
+            cls[l][1] = padded(cls[l][1], chs[l], cc); cls[l][2] = padded(cls[l][2], 1, cc); cls[l][3] = padded(cls[l][3], cc, cc);
+            cls[l][4] = padded(cls[l][4], cc, ncp);
+        }
+        if (next != d.n_convs) return fail("convolution list longer than the architecture");
+        p->fused_head = cb % 64 == 0 && cc % 64 == 0;
+        const View feats[3] = {n3, m4, m5};
+        const int hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
+        const float strides[3] = {8.f, 16.f, 32.f};
+        Step h3s{}; h3s.kind = K_HEAD3;
+        int a0 = 0;
+        for (int l = 0; l < 3; ++l) {
+            const long m = (long)B * hs[l] * ws[l];
+            View bb1 = buf(m, cb), bb2 = buf(m, cb), d1 = buf(m, chs[l]), k1 = buf(m, cc), d2 = buf(m, cc), k2 = buf(m, cc);
+            if (!bb1.base || !bb2.base || !d1.base || !k1.base || !d2.base || !k2.base) return false;
+            if (!conv1(box[l][0], feats[l], bb1, hs[l], ws[l], 1) || !conv1(box[l][1], bb1, bb2, hs[l], ws[l], 1)) return false;
+            if (!dwconv(cls[l][0], 0, feats[l], d1, hs[l], ws[l], 1) || !conv1(cls[l][1], d1, k1, hs[l], ws[l], 1) ||
+                !dwconv(cls[l][2], 0, k1, d2, hs[l], ws[l], 1) || !conv1(cls[l][3], d2, k2, hs[l], ws[l], 1)) return false;
+            if (p->fused_head) {
+                if (!head(box[l][2], bb2, 1, hs[l], ws[l], a0, strides[l]) || !head(cls[l][4], k2, 2, hs[l], ws[l], a0, strides[l])) return false;
+            } else {
+                View bo = buf(m, 64), ko = buf(m, ncp);
+                if (!bo.base || !ko.base) return false;
+                if (!conv1(box[l][2], bb2, bo, hs[l], ws[l], 0) || !conv1(cls[l][4], k2, ko, hs[l], ws[l], 0)) return false;
+                h3s.hb[l] = bo.ptr(); h3s.hldb[l] = bo.ld; h3s.hk[l] = ko.ptr(); h3s.hldc[l] = ko.ld; h3s.hh[l] = hs[l]; h3s.hw[l] = ws[l]; h3s.hs[l] = strides[l];
+            }
+            a0 += hs[l] * ws[l];
+        }
+        if (!p->fused_head) push(h3s, nullptr);
+        return err.empty();
     }
 
     bool build_v5(const float *anchors)
@@ -386,24 +644,7 @@ struct Builder {
             p->quiet_step = (int)p->steps.size();
             if (!t5.base || !t5b.base || !p5.base || !conv1(take(c4, c5, 3, 2, "b7"), p4, t5, h4, w4, 1)) return false;
             if (!c3(c5, c5, d.depth_backbone[3], true, &t5, nullptr, nullptr, t5b, h5, w5, "b8")) return false;
-            {   // SPPF
-                const int c_ = c5 / 2;
-                const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
-                View cat = buf((long)B * h5 * w5, 4 * c_);
-                if (!cat.base || !conv1(cv1, t5b, cat.sub(0, c_), h5, w5, 1)) return false;
-                if (h5 * w5 <= 2400) {
-                    Step s3{}; s3.kind = K_SPPF3; s3.in = cat.sub(0, c_).ptr(); s3.ldi = cat.ld; s3.out = cat.sub(c_, c_).ptr(); s3.out2 = cat.sub(2 * c_, c_).ptr();
-                    s3.out3 = cat.sub(3 * c_, c_).ptr(); s3.ldo = cat.ld; s3.H = h5; s3.W = w5; s3.Cin = c_;
-                    push(s3, nullptr);
-                } else {
-                    for (int i = 0; i < 3; ++i) {
-                        Step sp{}; sp.kind = K_POOL5; sp.in = cat.sub(i * c_, c_).ptr(); sp.ldi = cat.ld; sp.out = cat.sub((i + 1) * c_, c_).ptr(); sp.ldo = cat.ld;
-                        sp.H = h5; sp.W = w5; sp.Cin = c_;
-                        push(sp, nullptr);
-                    }
-                }
-                if (!conv1(cv2, cat, p5, h5, w5, 1)) return false;
-            }
+            if (!sppf(c5, t5b, p5, h5, w5)) return false;
             // neck: the two concat buffers of the bottom-up path; h10 / h14 write their slices directly
             View cat20 = buf((long)B * h4 * w4, 2 * c3w), cat23 = buf((long)B * h5 * w5, 2 * c4);
             if (!cat20.base || !cat23.base) return false;
@@ -467,38 +708,7 @@ struct Builder {
             s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
             push(s, nullptr);
             if (!conv1(b1, x0, x1, h1, w1, 1)) return false;
-        } else {
-            if (c1 > 64) return fail("stem wider than 64 channels");
-            std::vector<_Float16> sw(64 * 32, (_Float16)0.f);
-            std::vector<float> sb(64, 0.f);
-            for (int co = 0; co < c1; ++co) {
-                for (int j = 0; j < 9; ++j)                       // j = c*3 + ky;  weight[co][c][ky][kx]
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float v = b0->weight[((size_t)co * 3 + j / 3) * 9 + (j % 3) * 3 + kx];
-                        sw[co * 32 + (kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)v;
-                    }
-                if (b0->bias) sb[co] = b0->bias[co];
-            }
-            void *dsw = dev_alloc(sw.size() * 2, false), *dsb = dev_alloc(sb.size() * 4, false);
-            if (!dsw || !dsb) return false;
-            if (hipMemcpy(dsw, sw.data(), sw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(dsb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("stem upload failed");
-            x1 = buf((long)B * h2 * w2, c2);
-            if (!x1.base) return false;
-            p->fused_stem = c1 == 32 && c2 == 64 && !(d.flags & RVA_PLAN_NO_STEM2);
-            if (p->fused_stem) {
-                Step s{}; s.kind = K_STEM2; s.w = dsw; s.b = (const float *)dsb; s.out = x1.ptr(); s.ldo = x1.ld; s.H = H; s.W = W;
-                int ci, co, k, st;
-                if (!pack(&b1, 1, &s.w2, &s.b2, &ci, &co, &k, &st)) return false;
-                push(s, nullptr);
-            } else {
-                View x0 = buf((long)B * h1 * w1, c1);
-                if (!x0.base) return false;
-                Step s{}; s.kind = K_STEM; s.w = dsw; s.b = (const float *)dsb; s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
-                push(s, nullptr);
-                if (!conv1(b1, x0, x1, h1, w1, 1)) return false;
-            }
-        }
+        } else if (!stem_f16(b0, b1, &x1)) return false;
         View x2 = buf((long)B * h2 * w2, c2);
         if (!x2.base || !c2f(c2, c2, d.depth_backbone[0], true, &x1, nullptr, nullptr, x2, h2, w2, "b2")) return false;
         // concat buffers of the neck: producers write their slice directly
@@ -517,24 +727,7 @@ struct Builder {
         if (!t5.base || !conv1(take(c4, c5, 3, 2, "b7"), p4, t5, h4, w4, 1)) return false;
         View t5b = buf((long)B * h5 * w5, c5);
         if (!t5b.base || !c2f(c5, c5, d.depth_backbone[3], true, &t5, nullptr, nullptr, t5b, h5, w5, "b8")) return false;
-        {   // SPPF
-            const int c_ = c5 / 2;
-            const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
-            View cat = buf((long)B * h5 * w5, 4 * c_);
-            if (!cat.base || !conv1(cv1, t5b, cat.sub(0, c_), h5, w5, 1)) return false;
-            if (h5 * w5 <= 2400 && !p->f32) {
-                Step s{}; s.kind = K_SPPF3; s.in = cat.sub(0, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub(c_, c_).ptr(); s.out2 = cat.sub(2 * c_, c_).ptr();
-                s.out3 = cat.sub(3 * c_, c_).ptr(); s.ldo = cat.ld; s.H = h5; s.W = w5; s.Cin = c_;
-                push(s, nullptr);
-            } else {
-                for (int i = 0; i < 3; ++i) {
-                    Step s{}; s.kind = p->f32 ? K_POOL5_F32 : K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
-                    s.H = h5; s.W = w5; s.Cin = c_;
-                    push(s, nullptr);
-                }
-            }
-            if (!conv1(cv2, cat, p5, h5, w5, 1)) return false;
-        }
+        if (!sppf(c5, t5b, p5, h5, w5)) return false;
         const bool fuse_up = !p->f32 && c5 % 64 == 0 && c4 % 64 == 0 && c3 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4;
         View n3 = buf((long)B * h3 * w3, c3);
         if (!n3.base) return false;
@@ -659,6 +852,8 @@ int launch_step(rva_yolov8_plan *p, const Step &s, int variant, const void *inpu
     case K_STEM6: return rva_stem6_conv_f16(c, input, s.w, s.b, s.out, s.ldo, n, s.H, s.W, s.Cout, st);
     case K_HEAD5: return rva_conv1x1_head5_f16(c, s.in, s.ldi, s.w, s.b, n, s.H, s.W, s.Cin, p->nc, s.b2, output, boxes, p->A, s.a0, s.stride_px, variant, st);
     case K_HEAD_F32: return rva_yolo_head_f32(c, s.in, s.ldi, s.in2, s.ldi2, output, n, s.H, s.W, p->nc, p->A, s.a0, s.stride_px, st);
+    case K_DWCONV: return rva_dwconv3x3_nhwc_f16(c, s.in, s.ldi, s.w, s.b, s.out, s.ldo, s.res, s.ldr, n, s.H, s.W, s.Cin, s.act, st);
+    case K_ATTN: return rva_psa_attention_f16(c, s.in, s.ldi, s.out, s.ldo, n, s.H * s.W, s.mode, st);      // mode = heads
     }
     return RVA_ERR_ARG;
 }
@@ -877,6 +1072,41 @@ int rva_yolov5_plan_create(rva_ctx *ctx, const rva_yolov5_desc *desc, const rva_
     return RVA_OK;
 }
 
+int rva_yolo11_plan_create(rva_ctx *ctx, const rva_yolo11_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out)
+{
+    if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
+    *out = nullptr;
+    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
+        desc->nc > 1024 || desc->n_convs <= 0)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024");
+    if (desc->flags & RVA_PLAN_F32)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: there is no fp32 YOLO11 plan (RVA_PLAN_F32); build the fp16 plan");
+    for (int i = 0; i < 5; ++i)
+        if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: channel widths must be multiples of 8");
+    if (desc->psa_heads < 1 || desc->psa_heads * 128 != desc->widths[4])
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: psa_heads * 64 = %d is not half the C2PSA width %d", desc->psa_heads * 64, desc->widths[4]);
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
+    p->ctx = ctx; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
+    p->d.batch = desc->batch; p->d.height = desc->height; p->d.width = desc->width; p->d.nc = desc->nc; p->d.reg_max = 16;
+    for (int i = 0; i < 5; ++i) p->d.widths[i] = desc->widths[i];
+    p->d.n_convs = desc->n_convs; p->d.flags = desc->flags;
+    p->head_rows = 4 + desc->nc;
+    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
+    Builder b{p.get(), convs};
+    if (!b.build_11(*desc)) {
+        for (void *a : p->allocs) (void)hipFree(a);
+        return rva_fail(ctx, b.err.find("hip") == 0 || b.err.find("upload") != std::string::npos ? RVA_ERR_HIP : RVA_ERR_ARG,
+                        "rva_yolo11_plan_create: %s", b.err.c_str());
+    }
+    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
+    if (p->box32) p->box_off = ((size_t)p->B * p->head_rows * p->A * 2 + 255) / 256 * 256;
+    p->rows_top = 0; p->rows_bottom = p->H;
+    propagate_rows(p.get());
+    *out = p.release();
+    return RVA_OK;
+}
+
 void rva_yolov8_plan_destroy(rva_yolov8_plan *p)
 {
     if (!p) return;
@@ -912,6 +1142,29 @@ int rva_yolov8_plan_tunable_desc(const rva_yolov8_plan *p, int index, char *buf,
 {
     if (!p || index < 0 || index >= (int)p->tunables.size() || !buf || len <= 0) return RVA_ERR_ARG;
     snprintf(buf, (size_t)len, "%s", p->tunables[index].desc.c_str());
+    return RVA_OK;
+}
+
+// What step `step` of the list is: a tunable step's description, else the kernel's name and the shape it runs.
+int rva_yolov8_plan_step_desc(const rva_yolov8_plan *p, int step, char *buf, int len)
+{
+    if (!p || step < 0 || step >= (int)p->steps.size() || !buf || len <= 0) return RVA_ERR_ARG;
+    const Step &s = p->steps[step];
+    if (s.tunable >= 0) { snprintf(buf, (size_t)len, "%s", p->tunables[s.tunable].desc.c_str()); return RVA_OK; }
+    switch (s.kind) {
+    case K_ATTN: snprintf(buf, (size_t)len, "attention heads %d tokens %d", s.mode, s.H * s.W); break;
+    case K_DWCONV: snprintf(buf, (size_t)len, "dwconv3x3 %d act%d%s %dx%d", s.Cin, s.act, s.res ? " +res" : "", s.H, s.W); break;
+    case K_STEM2: snprintf(buf, (size_t)len, "stem2 3->32->64 %dx%d", s.H, s.W); break;
+    case K_STEM: case K_STEM_F32: snprintf(buf, (size_t)len, "stem 3->%d k3s2 %dx%d", s.Cout, s.H, s.W); break;
+    case K_STEM6: snprintf(buf, (size_t)len, "stem6 3->%d k6s2 %dx%d", s.Cout, s.H, s.W); break;
+    case K_PAIR32: snprintf(buf, (size_t)len, "pair32 %dx%d", s.H, s.W); break;
+    case K_SPPF3: snprintf(buf, (size_t)len, "sppf pool3 %d %dx%d", s.Cin, s.H, s.W); break;
+    case K_POOL5: case K_POOL5_F32: snprintf(buf, (size_t)len, "maxpool5 %d %dx%d", s.Cin, s.H, s.W); break;
+    case K_UP2: case K_UP2_F32: snprintf(buf, (size_t)len, "upsample2x %d %dx%d", s.Cin, s.H, s.W); break;
+    case K_HEAD3: snprintf(buf, (size_t)len, "head3 decode"); break;
+    case K_HEAD_F32: snprintf(buf, (size_t)len, "head decode %dx%d", s.H, s.W); break;
+    default: snprintf(buf, (size_t)len, "step kind %d", (int)s.kind); break;
+    }
     return RVA_OK;
 }
 

@@ -85,19 +85,25 @@ def create_detector(config: DetectorConfig) -> BaseDetector:
 
 
 def detector_architecture(model_type: str, model_path: str, net=None, state_dict=None) -> str:
-    """``"yolov5"`` or ``"yolov8"``: which network ``HipYoloDetector`` builds.  No configuration key: it follows what the user
-    handed over.  YOLOv5 when (1) ``net`` is a ``yolov5.YoloV5``; or (2) ``model_path`` is an existing file whose state dict
+    """``"yolo11"``, ``"yolov5"`` or ``"yolov8"``: which network ``HipYoloDetector`` builds.  No configuration key: it follows what
+    the user handed over.  YOLO11, checked first and under either ``model_type``, when (1) ``net`` is a ``yolo11.Yolo11``; or (2)
+    ``model_path`` is an existing file whose state dict has the attention convolution of C2PSA (``model.10.m.0.attn.qkv.conv.weight`` /
+    ``10.m.0...`` / ``l10.m.0...``): the file decides, whatever its name; or (3) no such file exists and the file name starts with
+    ``yolo11`` / ``yolov11`` plus a scale letter (seeded weights).  YOLOv5 when (1) ``net`` is a ``yolov5.YoloV5``; or (2) ``model_path`` is an existing file whose state dict
     (``state_dict`` where the caller has loaded it already) has the YOLOv5 detect convolution (``model.24.m.0.weight`` /
     ``24.m.0.weight`` / ``detect.m.0.weight``); or (3) ``model_type`` is ``"yolov5"`` and the file name starts with ``yolov5`` plus
     a scale letter while no such file exists (seeded weights).  Everything else is YOLOv8 as before: ``model_type: yolov5`` with
     the default ``yolov8n.pt``, every ``yolov8*`` name, and the ``yolov5*u`` names (anchor-free re-exports with the v8 head)."""
+    from .yolo11 import Yolo11, is_11_state_dict, variant_from_path_11
     from .yolov5 import YoloV5, is_v5_state_dict, variant_from_path_v5
     if net is not None:
-        return "yolov5" if isinstance(net, YoloV5) else "yolov8"
+        return "yolo11" if isinstance(net, Yolo11) else "yolov5" if isinstance(net, YoloV5) else "yolov8"
     if _is_file(model_path):
         if state_dict is None:
             state_dict = torch.load(model_path, map_location="cpu", weights_only=True)
-        return "yolov5" if is_v5_state_dict(state_dict) else "yolov8"
+        return "yolo11" if is_11_state_dict(state_dict) else "yolov5" if is_v5_state_dict(state_dict) else "yolov8"
+    if variant_from_path_11(model_path) is not None:
+        return "yolo11"
     if str(model_type).lower() == "yolov5" and variant_from_path_v5(model_path) is not None:
         return "yolov5"
     return "yolov8"
@@ -119,13 +125,14 @@ def v5_scale_of(model_path: str, state_dict=None) -> str:
 def select_yolo_engine(arch: str, half: bool, hip_engine: str = "auto") -> str:
     """Engine of a ``HipYoloDetector``: ``"fused"`` (fp16 plan) for ``half: true``; for ``half: false`` the fp32 plan
     (``"fused-f32"``) under ``hip_engine: plan / native`` and the module through PyTorch-ROCm (``"torch-fp32"``) under ``auto``.
-    YOLOv5 has no fp32 plan: ``half: false`` with ``plan`` / ``native`` is a ``ValueError``."""
+    YOLOv5 and YOLO11 have no fp32 plan: ``half: false`` with ``plan`` / ``native`` is a ``ValueError``."""
     if half:
         return "fused"
     if hip_engine in ("plan", "native"):
-        if arch == "yolov5":
-            raise ValueError(f"hip_engine: {hip_engine} with half: false needs an fp32 YOLOv5 plan, which does not exist; the "
-                             "hand-written YOLOv5 plan is fp16: set `half: true` (or `hip_engine: auto` for fp32 through PyTorch-ROCm)")
+        if arch in ("yolov5", "yolo11"):
+            name = "YOLOv5" if arch == "yolov5" else "YOLO11"
+            raise ValueError(f"hip_engine: {hip_engine} with half: false needs an fp32 {name} plan, which does not exist; the "
+                             f"hand-written {name} plan is fp16: set `half: true` (or `hip_engine: auto` for fp32 through PyTorch-ROCm)")
         return "fused-f32"
     return "torch-fp32"
 
@@ -153,7 +160,9 @@ class HipYoloDetector(BaseDetector):
         The architecture (``self.arch``) is YOLOv5 where ``detector_architecture`` says so -- a ``yolov5.YoloV5`` as ``net``, a YOLOv5
         state dict at ``model_path``, or ``model_type: yolov5`` with a ``yolov5<n|s|m|l>`` file name and no file -- and then ``half:
         true`` runs ``engine.FusedYoloV5`` (engine ``"fused"``, head ``[B, 5+nc, A]``), ``half: false`` the module through PyTorch-ROCm
-        (``plan`` / ``native``: ``ValueError``, there is no fp32 YOLOv5 plan).
+        (``plan`` / ``native``: ``ValueError``, there is no fp32 YOLOv5 plan).  YOLO11 -- a ``yolo11.Yolo11`` as ``net``, a YOLO11 state
+        dict at ``model_path``, or a ``yolo11<n|s|m|l>`` file name and no file, under either ``model_type`` -- runs the same way on
+        ``engine.FusedYolo11`` (head ``[B, 4+nc, A]``, as YOLOv8's).
         ``hip_plan_capacity: N`` (engines ``"fused"`` and ``"fused-f32"``; default 0 = one plan and input buffer per batch size)
         keeps ONE plan and ONE input buffer of ``N`` images per input size and slot: a call with ``n <= N`` frames writes and
         runs the leading ``n`` images, with the kernels of a full run (config.py)."""
@@ -181,7 +190,13 @@ class HipYoloDetector(BaseDetector):
         self._over_capacity_warned = False
         self.net = None
         if infer_fn is None:
-            if net is None and self.arch == "yolov5":
+            if net is None and self.arch == "yolo11":
+                from .yolo11 import build_detector_net_11, scale_of_11
+                scale = scale_of_11(config.model_path, sd)
+                net = build_detector_net_11(scale, seed=seed, weights=config.model_path)
+                LOGGER.info("hip detector: YOLO11%s, %s weights", scale,
+                            "local state-dict" if sd is not None else "seeded random (no weights offline)")
+            elif net is None and self.arch == "yolov5":
                 from .yolov5 import build_detector_net_v5
                 scale = v5_scale_of(config.model_path, sd)
                 net = build_detector_net_v5(scale, seed=seed, weights=config.model_path)
@@ -294,8 +309,8 @@ class HipYoloDetector(BaseDetector):
         key = shape if self._slot == 0 else shape + (self._slot,)
         plan = self._plans.get(key)
         if plan is None:
-            from .engine import FusedYoloV5, FusedYoloV8
-            plan_cls = FusedYoloV5 if self.arch == "yolov5" else FusedYoloV8      # the same plan object and surface
+            from .engine import FusedYolo11, FusedYoloV5, FusedYoloV8
+            plan_cls = {"yolov5": FusedYoloV5, "yolo11": FusedYolo11}.get(self.arch, FusedYoloV8)      # the same plan object and surface
             first = self._plans.get(shape) if self._slot else None
             # the static rows at construction: the tuner times the windowed launches, and a later slot's plan has the first
             # slot's windows, whose kernel selection it takes over

@@ -159,7 +159,7 @@ class FusedYoloV8:
         else:
             self.out = torch.empty((batch, rows, self.A), dtype=self.dtype, device=self.dev)
         self._outs = {0: self.out}
-        self.fused_stem = isinstance(d, N.YoloV8Desc) and not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
+        self.fused_stem = isinstance(d, (N.YoloV8Desc, N.Yolo11Desc)) and not self.f32 and not (d.flags & N.RVA_PLAN_NO_STEM2) and tuple(d.widths[:2]) == (32, 64)
         # (launch(stream, variant) -> rc, state["variant"], "Cin->Cout kKsS HxW") per convolution step, as the tuner and the tools use them
         self._n_tunable = n_tun
         self._read_tunables()
@@ -221,6 +221,13 @@ class FusedYoloV8:
         y0, y1 = C.c_int32(), C.c_int32()
         self.ctx.check(self.L.rva_yolov8_plan_step_rows(self.handle, int(step), C.byref(y0), C.byref(y1)), "rva_yolov8_plan_step_rows")
         return int(y0.value), int(y1.value)
+
+    def step_desc(self, step: int) -> str:
+        """What step ``step`` of the launch list is (``rva_yolov8_plan_step_desc``): a convolution's tunable description, else
+        the kernel and its shape."""
+        buf = C.create_string_buffer(96)
+        self.ctx.check(self.L.rva_yolov8_plan_step_desc(self.handle, int(step), buf, 96), "rva_yolov8_plan_step_desc")
+        return buf.value.decode()
 
     def _alloc_split(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """One allocation in the plan's output layout: the fp16 head, then ``boxes32`` at the offset the plan reports."""
@@ -579,3 +586,72 @@ class FusedYoloV5(FusedYoloV8):
         d.nc, d.n_convs = net.nc, n_convs
         d.anchors[:] = [float(v) for v in net.detect.anchors_px.detach().float().cpu().flatten().tolist()]
         return d, "rva_yolov5_plan_create"
+
+
+def module_order_convs_11(net) -> list:
+    """The convolutions of a fused ``yolo11.Yolo11`` in the module order ``rva_yolo11_plan_create`` consumes (include/rva.h).
+    The depthwise ones (``groups == channels``) have weights ``[C, 1, 3, 3]`` and travel as ``cin = 1``."""
+    from .yolo11 import C3k
+
+    def bottleneck(b):
+        return [b.cv1, b.cv2]
+
+    def c3k2(m):
+        out = [m.cv1, m.cv2]
+        for b in m.m:
+            if isinstance(b, C3k):
+                out += [b.cv1, b.cv2, b.cv3]
+                for bb in b.m:
+                    out += bottleneck(bb)
+            else:
+                out += bottleneck(b)
+        return out
+
+    def c2psa(m):
+        out = [m.cv1, m.cv2]
+        for b in m.m:
+            out += [b.attn.qkv, b.attn.proj, b.attn.pe, b.ffn[0], b.ffn[1]]
+        return out
+    mods = [net.l0, net.l1, *c3k2(net.l2), net.l3, *c3k2(net.l4), net.l5, *c3k2(net.l6), net.l7, *c3k2(net.l8), net.l9.cv1, net.l9.cv2,
+            *c2psa(net.l10), *c3k2(net.l13), *c3k2(net.l16), net.l17, *c3k2(net.l19), net.l20, *c3k2(net.l22)]
+    for seq in net.detect.box:
+        mods += [seq[0], seq[1], seq[2]]
+    for seq in net.detect.cls:
+        mods += [seq[0][0], seq[0][1], seq[1][0], seq[1][1], seq[2]]
+    return [m.conv if isinstance(m, ConvBnAct) else m for m in mods]
+
+
+class FusedYolo11(FusedYoloV8):
+    """The fused fp16 plan of a ``yolo11.Yolo11`` (``rva_yolo11_plan_create``): the same plan object, tuner and surface as
+    ``FusedYoloV8``, and the same head tensor ``[B, 4 + nc, A]``.  The depthwise convolutions and the attention of C2PSA are fixed
+    kernels (``rva_dwconv3x3_nhwc_f16``, ``rva_psa_attention_f16``): the tuner sees the ordinary convolutions only, the qkv / proj /
+    ffn 1x1 among them.  The detect branches run in line (no side lanes).  There is no fp32 YOLO11 plan: ``precision="fp32"`` is a
+    ``ValueError``."""
+
+    HEAD_ROWS_EXTRA = 4
+    ARCH_KEY = b"arch yolo11"
+
+    def __init__(self, net, batch: int, hw: Tuple[int, int] = (640, 640), **kw):
+        if kw.get("precision", "fp16") != "fp16":
+            raise ValueError("there is no fp32 YOLO11 plan: FusedYolo11 runs precision='fp16' (half: true)")
+        super().__init__(net, batch, hw, **kw)
+
+    @staticmethod
+    def _module_order(net) -> list:
+        return module_order_convs_11(net)
+
+    @staticmethod
+    def _descriptor(net, batch: int, hw: Tuple[int, int], n_convs: int):
+        d = N.Yolo11Desc()
+        d.batch, d.height, d.width = batch, hw[0], hw[1]
+        d.widths[:] = [net.l0.conv.out_channels, net.l1.conv.out_channels, net.l3.conv.out_channels, net.l5.conv.out_channels,
+                       net.l7.conv.out_channels]
+        blocks = (net.l2, net.l4, net.l6, net.l8, net.l13, net.l16, net.l19, net.l22)
+        d.repeats[:] = [len(m.m) for m in blocks]
+        d.c3k[:] = [int(m.c3k) for m in blocks]
+        d.psa_blocks, d.psa_heads = len(net.l10.m), net.l10.m[0].attn.num_heads
+        d.nc, d.n_convs = net.nc, n_convs
+        return d, "rva_yolo11_plan_create"
+
+    def fused_head_lanes(self) -> bool:
+        return False                      # the plan has no fork points: rva_yolov8_plan_run_lanes_n is _run_n

@@ -159,6 +159,65 @@ def context(device: Optional[int] = None) -> N.Context:
     return _CTX[dev]
 
 
+# ------------------------------------------------------------------------------------------ YOLO11 primitives
+def pack_dwconv_weights(weight: torch.Tensor) -> torch.Tensor:
+    """A depthwise 3x3 convolution's ``[C, 1, 3, 3]`` weights in the layout ``rva_dwconv3x3_nhwc_f16`` reads: fp16 ``[9, C]``, tap
+    ``ky * 3 + kx`` major (a lane's 8 channels of a tap are one 16-byte load).  One rounding to fp16."""
+    c = int(weight.shape[0])
+    if tuple(weight.shape) != (c, 1, 3, 3):
+        raise ValueError(f"a depthwise 3x3 weight is [C, 1, 3, 3], not {tuple(weight.shape)}")
+    return weight.detach().reshape(c, 9).t().contiguous().to(torch.float16)
+
+
+def _nhwc_slice(t: torch.Tensor, name: str, dims: int) -> int:
+    """Row stride (elements) of a channel slice ``[..., C]`` of a contiguous channels-last fp16 buffer ``[..., ld]``."""
+    _require_cuda(t, name)
+    if t.dtype != torch.float16 or t.dim() != dims or t.stride(-1) != 1:
+        raise ValueError(f"{name} must be an fp16 [{'B, H, W' if dims == 4 else 'B, T'}, C] channel slice with unit channel stride")
+    ld, n = int(t.stride(-2)), 1
+    for d in range(dims - 2, -1, -1):                     # pixel (token) p of the buffer lies at p * ld
+        if t.shape[d] > 1 and t.stride(d) != ld * n:
+            raise ValueError(f"{name} is not a channel slice of a contiguous channels-last buffer (strides {t.stride()})")
+        n *= int(t.shape[d])
+    return ld
+
+
+def dwconv3x3_f16(x: torch.Tensor, weights: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, act: bool = True,
+                  residual: Optional[torch.Tensor] = None, ctx: Optional[N.Context] = None) -> torch.Tensor:
+    """``rva_dwconv3x3_nhwc_f16``: ``out = [SiLU](dw3x3(x) + bias) [+ residual]`` on ``[B, H, W, C]`` channel slices of NHWC fp16
+    buffers (``buf[..., c0:c0 + C]``).  ``weights`` from ``pack_dwconv_weights``, ``bias`` fp32 ``[C]``.  What the library refuses
+    (``C % 8``, alignment, sizes) raises ``RuntimeError`` before any launch."""
+    ctx = ctx or context()
+    ldi, ldo = _nhwc_slice(x, "x", 4), _nhwc_slice(out, "out", 4)
+    ldr = _nhwc_slice(residual, "residual", 4) if residual is not None else 0
+    b, h, w, c = (int(v) for v in x.shape)
+    if tuple(out.shape) != (b, h, w, c) or (residual is not None and tuple(residual.shape) != (b, h, w, c)):
+        raise ValueError("x, out and residual must have one shape")
+    if weights.dtype != torch.float16 or tuple(weights.shape) != (9, c) or not weights.is_contiguous() or bias.dtype != torch.float32 or \
+            tuple(bias.shape) != (c,) or not bias.is_contiguous():
+        raise ValueError("weights must be fp16 [9, C] (pack_dwconv_weights) and bias fp32 [C], both contiguous")
+    _require_cuda(weights, "weights")
+    _require_cuda(bias, "bias")
+    ctx.check(N.lib().rva_dwconv3x3_nhwc_f16(ctx.handle, C.c_void_p(x.data_ptr()), ldi, C.c_void_p(weights.data_ptr()),
+                                             C.c_void_p(bias.data_ptr()), C.c_void_p(out.data_ptr()), ldo,
+                                             C.c_void_p(residual.data_ptr()) if residual is not None else None, ldr, b, h, w, c,
+                                             1 if act else 0, _stream_ptr()), "rva_dwconv3x3_nhwc_f16")
+    return out
+
+
+def psa_attention_f16(qkv: torch.Tensor, out: torch.Tensor, heads: int, ctx: Optional[N.Context] = None) -> torch.Tensor:
+    """``rva_psa_attention_f16``: ``qkv`` fp16 ``[B, T, >= 128 heads]`` (head ``h`` at channels ``[128 h, 128 h + 128)`` = q 32 | k 32
+    | v 64), ``out`` fp16 ``[B, T, >= 64 heads]`` (head ``h`` at ``[64 h, 64 h + 64)``); both may be slices of wider buffers."""
+    ctx = ctx or context()
+    ld, ldo = _nhwc_slice(qkv, "qkv", 3), _nhwc_slice(out, "out", 3)
+    b, t = int(qkv.shape[0]), int(qkv.shape[1])
+    if tuple(out.shape[:2]) != (b, t) or qkv.shape[2] < 128 * heads or out.shape[2] < 64 * heads:
+        raise ValueError("qkv [B, T, >= 128 heads] and out [B, T, >= 64 heads] do not fit each other")
+    ctx.check(N.lib().rva_psa_attention_f16(ctx.handle, C.c_void_p(qkv.data_ptr()), ld, C.c_void_p(out.data_ptr()), ldo, b, t, int(heads),
+                                            _stream_ptr()), "rva_psa_attention_f16")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K1
 @dataclass
 class Nv12Surface:

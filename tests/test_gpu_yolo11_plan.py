@@ -1,0 +1,359 @@
+"""The fused fp16 YOLO11 plan (``engine.FusedYolo11`` / ``rva_yolo11_plan_create``), the detector and the pipeline on top of it.
+
+Accuracy: the head tensor ``[B, 4 + nc, A]`` against the float64 module fed the same fp16-rounded input and the same
+folded-then-rounded weights, per row group (boxes, classes).  The yardstick is the error of the SAME module run by PyTorch-ROCm in
+fp16 (channels-last) against that float64 output: both pipelines store fp16 activations and differ only in summation order and
+rounding points, so the plan's largest error may be at most twice PyTorch's -- the project's condition for its fp16 plans, not a
+measurement.  Both errors are printed, and recorded where ``RVA_REPORT_DIR`` names a directory.  Every test but one runs variant 0
+on every step (``_no_tuner``); that one runs the real tuner once and holds the tuned plan to the same condition.
+Bit-identity: ``run_n(1)`` == image 0 of a full run; eager == a hipGraph replay; a primed windowed run == a fresh plan (the stem is
+windowed, every step of the stride-32 stage -- attention among them -- runs whole); ``box_rows="fp32"`` == the default head.
+End to end: ``create_detector`` with ``model_path: yolo11n.pt`` against the oracle's post-process of the plan's own head tensor,
+and ``PipelinedTicks`` against ``TickPipeline.tick``."""
+import copy
+import functools
+import json
+import os
+from pathlib import Path
+
+import pytest
+import torch
+
+from oracle import oracle as orc
+from realtime_video_analytics_32streams_amd import ops, synth
+from realtime_video_analytics_32streams_amd.config import DetectorConfig, StreamConfig, TrackerConfig
+from realtime_video_analytics_32streams_amd.detector import HipYoloDetector, create_detector
+from realtime_video_analytics_32streams_amd.engine import FusedYolo11, FusedYoloV8
+from realtime_video_analytics_32streams_amd.pipeline import PipelinedTicks, TickPipeline
+from realtime_video_analytics_32streams_amd.tracker import IouTracker
+from realtime_video_analytics_32streams_amd.video_stream import FramePacket, SyntheticNv12Stream
+from realtime_video_analytics_32streams_amd.yolo11 import Yolo11, build_detector_net_11, calibrate_detection_density_11
+
+pytestmark = pytest.mark.gpu
+
+# scale, classes, input (batch, height, width): 6 tokens and 2 heads; 20 tokens and 4 heads, a three-class head; C3k in every C3k2
+# and two PSA blocks; a class branch whose width (85) the plan pads to 88 with zero-extended depthwise and pointwise weights
+CASES = {"n": ("n", 80, (2, 64, 96)), "s-nc3": ("s", 3, (1, 128, 160)), "l-nc20": ("l", 20, (1, 64, 64)), "n-nc85": ("n", 85, (1, 64, 64))}
+
+
+def _with_tuner(test):
+    """Marks the one test that runs the real tuner."""
+    test.uses_tuner = True
+    return test
+
+
+@pytest.fixture(autouse=True)
+def _no_tuner(request, monkeypatch):
+    """The detector's plans run every layer with the library's own choice (variant 0): the tuner only picks among kernels."""
+    if not getattr(request.function, "uses_tuner", False):
+        monkeypatch.setattr(FusedYoloV8, "autotune", lambda self, reps=5: None)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.float16 else torch.int32)
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+
+
+@functools.lru_cache(maxsize=None)
+def _net(case):
+    """Seeded, BatchNorm folded, every parameter rounded to fp16 (kept as fp32): the plan, the fp16 module and the float64 module
+    then hold the same numbers, biases included (the plan keeps biases in fp32).  Shared, never modified."""
+    scale, nc, _ = CASES[case]
+    net = build_detector_net_11(scale, seed=7, nc=nc).fuse()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(p.half().float())
+    return net
+
+
+@functools.lru_cache(maxsize=None)
+def _input(case):
+    b, h, w = CASES[case][2]
+    return torch.rand((b, 3, h, w), generator=torch.Generator().manual_seed(11)).half()
+
+
+@functools.lru_cache(maxsize=None)
+def _float64_head(case):
+    with torch.inference_mode():
+        return copy.deepcopy(_net(case)).double()(_input(case).double()).contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def _torch_fp16_head(case):
+    """``[B, 4 + nc, A]`` float64 on the CPU: the same module run by PyTorch-ROCm in fp16, channels-last."""
+    ref16 = copy.deepcopy(_net(case)).half().cuda().to(memory_format=torch.channels_last)
+    with torch.inference_mode():
+        return ref16(_input(case).cuda().contiguous(memory_format=torch.channels_last)).double().cpu()
+
+
+def _check_against_float64(case, got, tag):
+    """The condition of this file: per row group the plan's error is at most twice PyTorch fp16's.  Returns what was measured and
+    the groups that miss it (a NaN error counts as a miss)."""
+    want, tor = _float64_head(case), _torch_fp16_head(case)
+    assert bool(torch.isfinite(got).all()) and got.shape == want.shape == tor.shape
+    rec = {}
+    for name, rows in (("boxes", slice(0, 4)), ("classes", slice(4, None))):
+        rec[name] = {"plan_max_err": float((got[:, rows] - want[:, rows]).abs().max()),
+                     "torch_fp16_max_err": float((tor[:, rows] - want[:, rows]).abs().max())}
+        e = rec[name]
+        print(f"[yolo11 {tag}] {name}: plan max |d| {e['plan_max_err']:.4g}, PyTorch fp16 max |d| {e['torch_fp16_max_err']:.4g}, "
+              f"ratio {e['plan_max_err'] / max(e['torch_fp16_max_err'], 1e-30):.2f}")
+    bad = [(name, e["plan_max_err"], e["torch_fp16_max_err"]) for name, e in rec.items()
+           if not e["plan_max_err"] <= 2.0 * e["torch_fp16_max_err"]]
+    return rec, bad
+
+
+def _plan(case, **kw):
+    b, h, w = CASES[case][2]
+    kw.setdefault("autotune", False)
+    return FusedYolo11(copy.deepcopy(_net(case)), b, (h, w), **kw)
+
+
+def _record(key, value):
+    out = os.environ.get("RVA_REPORT_DIR")
+    if out and Path(out).is_dir():
+        path = Path(out) / "yolo11_accuracy.json"
+        data = json.loads(path.read_text()) if path.exists() else {}
+        data[key] = value
+        path.write_text(json.dumps(data, indent=1, sort_keys=True))
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_head_tensor_against_the_float64_module(case):
+    scale, nc, (b, h, w) = CASES[case]
+    A = sum((h // s) * (w // s) for s in (8, 16, 32))
+    plan = _plan(case)
+    assert isinstance(plan, FusedYoloV8) and plan.nc == nc and plan.A == A and tuple(plan.out.shape) == (b, 4 + nc, A)
+    assert not plan.fused_head_lanes() and plan.n_launches == plan._n_steps
+    net = _net(case)
+    assert (h // 32) * (w // 32) == {"n": 6, "s-nc3": 20, "l-nc20": 4, "n-nc85": 4}[case]
+    assert (net.l10.m[0].attn.num_heads, len(net.l10.m)) == {"n": (2, 1), "s-nc3": (4, 1), "l-nc20": (4, 2), "n-nc85": (2, 1)}[case]
+    assert net.detect.cls[0][1][0].conv.out_channels == {"n": 80, "s-nc3": 128, "l-nc20": 256, "n-nc85": 85}[case]
+    got = plan(_input(case).cuda()).double().cpu()
+    torch.cuda.synchronize()
+    rec, bad = _check_against_float64(case, got, case)
+    _record(case, rec)
+    assert not bad, bad
+
+
+@_with_tuner
+def test_autotuned_plan_meets_the_float64_condition(monkeypatch):
+    """The real tuner, once: ``autotune(reps=1)`` on the YOLO11n plan with the selection cache off (nothing read, nothing written)
+    moves steps off variant 0 by time alone, and the head tensor still meets the condition of the test above."""
+    case = "n"
+    monkeypatch.setenv("RVA_TUNE_CACHE", "0")
+    for name in ("RVA_SKIP_VARIANTS", "RVA_TUNE_IN_PLAN", "RVA_TUNE_LAYER_OVERLAP"):
+        monkeypatch.delenv(name, raising=False)
+    plan = _plan(case)
+    assert all(st["variant"] == 0 for _, st, _ in plan._tunable)
+    plan.autotune(reps=1)
+    torch.cuda.synchronize()
+    picks = [(desc, st["variant"]) for _, st, desc in plan._tunable]
+    print("[yolo11 n tuned] selection:", picks)
+    assert plan.tuning_source == "measured" and any(v for _, v in picks), picks
+    got = plan(_input(case).cuda()).double().cpu()
+    torch.cuda.synchronize()
+    rec, bad = _check_against_float64(case, got, "n tuned")
+    assert not bad, (bad, picks)
+
+
+def test_bit_identity_of_partial_runs_graphs_and_windows():
+    case = "n"
+    b, h, w = CASES[case][2]
+    x = _input(case).cuda()
+    plan = _plan(case)
+    full = plan(x).clone()
+    torch.cuda.synchronize()
+    # one image on the two-image plan
+    plan.out.fill_(-3.0)
+    one = plan(x[:1].contiguous())
+    torch.cuda.synchronize()
+    assert _same(one, full[:1]) and bool((plan.out[1] == -3.0).all()), "run_n, n = 1"
+    # a hipGraph replay
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        plan(x)
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, stream=s):
+            plan(x)
+    plan.out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert _same(plan.out, full), "hipGraph replay"
+    del plan
+    # static rows: prime on x, then only rows 10..49 of the input change
+    x2 = x.clone()
+    x2[:, :, 10:50] = torch.rand((b, 3, 40, w), generator=torch.Generator().manual_seed(5)).half().cuda()
+    want2 = _plan(case)(x2).clone()
+    rows = _plan(case, static_rows=(10, 50))
+    assert rows.static_rows == (10, 50) and rows.step_rows(0) == (5, 26)          # stem: output row r reads input rows 2r-1 .. 2r+1
+    assert rows.step_rows(1)[0] > 0, "layer 1 is not windowed"
+    # attention and the depthwise steps have no window, whatever the rows: one attention and two positional encodings (one per
+    # head) in C2PSA, two depthwise steps per detect level
+    descs = [rows.step_desc(i) for i in range(rows.n_launches)]
+    assert descs[0] == f"stem 3->16 k3s2 {h}x{w}"
+    fixed = [(i, d) for i, d in enumerate(descs) if d.split()[0] in ("attention", "dwconv3x3")]
+    assert [d for _, d in fixed if d.startswith("attention")] == [f"attention heads 2 tokens {(h // 32) * (w // 32)}"]
+    assert sum(d.startswith("dwconv3x3") for _, d in fixed) == 2 + 6
+    for i, d in fixed:
+        map_rows = int(d.split()[-1].split("x")[0]) if d.startswith("dwconv3x3") else h // 32
+        assert rows.step_rows(i) == (0, map_rows), (i, d, rows.step_rows(i))
+    assert " r[" in descs[1], "layer 1's description does not carry its window"
+    rows(x)
+    assert rows.primed
+    got2 = rows(x2).clone()
+    torch.cuda.synchronize()
+    assert _same(got2, want2), "static rows"
+
+
+def test_box_rows_fp32_and_refusals():
+    case = "n"
+    x = _input(case).cuda()
+    want = _plan(case)(x).clone()
+    side = _plan(case, box_rows="fp32")
+    side.boxes32.fill_(float("nan"))
+    got = side(x).clone()
+    torch.cuda.synchronize()
+    assert _same(got, want) and tuple(side.boxes32.shape) == (2, 4, side.A) and bool(torch.isfinite(side.boxes32).all())
+    assert _same(side.boxes32.half(), got[:, :4])
+    assert isinstance(side.result(), ops.SplitHead)
+    with pytest.raises(ValueError, match="no fp32 YOLO11 plan"):
+        _plan(case, precision="fp32")
+    with pytest.raises(RuntimeError, match="rva_yolo11_plan_create: stem wider than 64 channels"):
+        FusedYolo11(Yolo11("x", 2).eval(), 1, (64, 64), autotune=False)
+    # what the library itself refuses, below the Python class: each names the entry
+    for match, fields in (("height and width multiples of 32", dict(height=72)), ("1 <= nc <= 1024", dict(nc=1025)),
+                          ("widths must be multiples of 8", dict(w2=36)), ("no fp32 YOLO11 plan", dict(flags=8)),
+                          ("psa_heads \\* 64 = 192 is not half the C2PSA width 256", dict(psa_heads=3))):
+        with pytest.raises(RuntimeError, match="rva_yolo11_plan_create: .*" + match):
+            _create_raw(**fields)
+
+
+def _create_raw(height=64, nc=80, w2=32, flags=0, psa_heads=2):
+    """``rva_yolo11_plan_create`` on a YOLO11n descriptor with one field off (it refuses before it reads a convolution)."""
+    import ctypes as C
+    from realtime_video_analytics_32streams_amd import _native as N
+    ctx = ops.context()
+    d = N.Yolo11Desc()
+    d.batch, d.height, d.width, d.nc, d.n_convs, d.flags = 1, height, 64, nc, 87, flags
+    d.widths[:] = [16, w2, 64, 128, 256]
+    d.repeats[:] = [1] * 8
+    d.psa_blocks, d.psa_heads = 1, psa_heads
+    arr, h = (N.ConvWeights * 87)(), C.c_void_p()
+    ctx.check(N.lib().rva_yolo11_plan_create(ctx.handle, C.byref(d), arr, C.byref(h)), "rva_yolo11_plan_create")
+
+
+# ------------------------------------------------------------------------------------------------ detector and pipeline
+def _cfg(**kw):
+    base = dict(backend="hip", model_type="yolov8", model_path="yolo11n.pt", half=True, warmup=False, confidence_threshold=0.25,
+                iou_threshold=0.5)
+    base.update(kw)
+    return DetectorConfig(**base)
+
+
+def _calibrated(sample, target=60, **kw):
+    det = create_detector(_cfg(**kw))
+    assert isinstance(det, HipYoloDetector) and isinstance(det.net, Yolo11) and det.arch == "yolo11" and det.engine == "fused"
+    with torch.inference_mode():
+        calibrate_detection_density_11(det.net, sample.contiguous(memory_format=torch.channels_last), 0.25, target)
+    det.invalidate_engine()
+    return det
+
+
+@functools.lru_cache(maxsize=None)
+def _frames():
+    W, H = 640, 360
+    return tuple(ops.Nv12Surface.from_numpy(*synth.make_nv12(40 + i, W, H), W, H) for i in range(2))
+
+
+def _packets(frames):
+    stream = StreamConfig(name="cam", url="x")
+    return [FramePacket(stream=stream, frame=f, frame_id=i, timestamp=0.0) for i, f in enumerate(frames)]
+
+
+def _predict(det, frames):
+    raws = []
+    infer = det._infer
+    det._infer = lambda t: raws.append(infer(t)) or raws[-1]
+    dets = det.predict_batch(_packets(frames))
+    det._infer = infer
+    return dets, raws[0]
+
+
+def test_create_detector_yolo11_matches_the_oracle_at_640():
+    """Two 640 x 360 NV12 frames at 640 x 640: 400 tokens in C2PSA, 8400 anchors.  The Detection objects == the oracle's
+    post-process of the head tensor the plan produced; ``hip_plan_capacity: 4`` gives the exact-size plan's detections."""
+    frames = list(_frames())
+    with torch.inference_mode():
+        sample, _ = ops.preprocess_nv12(frames, (640, 640), half=True)
+    sample = sample.clone()
+    det = _calibrated(sample)
+    dets, head = _predict(det, frames)
+    plan = det._plans[(2, 640, 640)]
+    assert isinstance(plan, FusedYolo11) and tuple(head.shape) == (2, 84, 8400) and head.dtype == torch.float16
+    assert ops.post_status(det.ctx) == 0, "K2 / K3 overflow flag"
+    total = 0
+    for i in range(2):
+        r = orc.postprocess(head[i].float().cpu().numpy(), 0.25, 0.5, None, (640, 360))
+        assert [d.class_id for d in dets[i]] == [int(v) for v in r["cls"]], i
+        assert [d.confidence for d in dets[i]] == [float(v) for v in r["conf"]], i
+        assert [list(d.bbox_xyxy) for d in dets[i]] == [[float(v) for v in b] for b in r["boxes"]], i
+        total += len(dets[i])
+    assert total > 0, "the calibrated detector produced nothing"
+    # one plan of four images serving two frames
+    cap = _calibrated(sample, hip_plan_capacity=4)
+    dets4, head4 = _predict(cap, frames)
+    assert (4, 640, 640) in cap._plans and tuple(head4.shape) == (2, 84, 8400)
+    assert dets4 == dets
+    # model_type: yolov5 with the same name builds the same network
+    assert isinstance(create_detector(_cfg(model_type="yolov5")).net, Yolo11)
+
+
+def test_half_false_engines():
+    det = create_detector(_cfg(half=False))
+    assert det.engine == "torch-fp32" and det.arch == "yolo11" and isinstance(det.net, Yolo11)
+    for eng in ("plan", "native"):
+        with pytest.raises(ValueError, match="half: true"):
+            create_detector(_cfg(half=False, hip_engine=eng))
+    # what stays YOLOv8
+    from realtime_video_analytics_32streams_amd.yolov8 import YoloV8
+    assert isinstance(create_detector(_cfg(model_path="yolov8n.pt")).net, YoloV8)
+    assert isinstance(create_detector(_cfg(model_path="yolo11.pt")).net, YoloV8)
+
+
+def _tab(tracks):
+    return [(t.track_id, t.class_id, t.age, t.hits, t.confidence, t.bbox_xyxy) for t in tracks]
+
+
+def test_pipelined_ticks_equal_synchronous_ticks():
+    """Four synthetic 1080p NV12 streams: ``PipelinedTicks(depth=2)`` gives the tracks of ``TickPipeline.tick(device_gates=True)``."""
+    S, T = 4, 4
+    streams = [StreamConfig(name=f"cam{i}", url="synthetic://1920x1080", warmup_seconds=0.0) for i in range(S)]
+
+    def sources():
+        out = [SyntheticNv12Stream(s, index=i, n_unique=3) for i, s in enumerate(streams)]
+        for s in out:
+            s.open_sync()
+        return out
+    with torch.inference_mode():
+        sample, _ = ops.preprocess_nv12([s._ring[0] for s in sources()], (640, 640), half=True)
+    det = _calibrated(sample.clone())
+    tcfg = TrackerConfig(max_age=3, max_iou_distance=0.5, min_hits=1)
+
+    pipe = TickPipeline(streams, det, IouTracker(tcfg, max_streams=S, capacity=512), sources=sources())
+    want = [{n: _tab(v) for n, v in pipe.tick(device_gates=True).tracks.items()} for _ in range(T)]
+    assert sum(len(v) for t in want for v in t.values()) > 0
+    runner = PipelinedTicks(TickPipeline(streams, det, IouTracker(tcfg, max_streams=S, capacity=512), sources=sources()), depth=2)
+    got, inflight = [], 0
+    for _ in range(T):
+        if inflight == 2:
+            got.append({n: _tab(v) for n, v in runner.collect_result().tracks.items()}); inflight -= 1
+        runner.submit(); inflight += 1
+    while inflight:
+        got.append({n: _tab(v) for n, v in runner.collect_result().tracks.items()}); inflight -= 1
+    assert got == want
