@@ -35,9 +35,21 @@
 // C2f(b8), SPPF(b9) = cv1, cv2, C2f(h12), C2f(h15), h16, C2f(h18), h19, C2f(h21), then per level l = 0..2: box[l][0..2], then per
 // level: cls[l][0..2];  C2f(x) = cv1, cv2, then per bottleneck: cv1, cv2.
 //
-// rva_yolov5_plan_create and rva_yolo11_plan_create lay down the graphs of YOLOv5 and YOLO11 for the same plan object
-// (Builder::build_v5 / build_11; the graphs and module orders are in include/rva.h).  YOLO11 adds two step kinds, K_DWCONV and
-// K_ATTN (rva_attn.hip): fixed kernels like the pooling steps, and in propagate_rows always the whole map -- attention is global.
+// rva_yolov5_plan_create and rva_yolo11_plan_create lay down the graphs of YOLOv5 and YOLO11 for the same plan object (the graphs
+// and module orders are in include/rva.h).  YOLO11 adds two step kinds, K_DWCONV and K_ATTN (rva_attn.hip): fixed kernels like the
+// pooling steps, and in propagate_rows always the whole map -- attention is global.
+//
+// How a graph is laid down.  The three entry points check what is their architecture's, fill the internal descriptor and hand
+// create_plan() the graph to build; everything else of a create (common checks, ownership, error codes, events, the starting
+// state) is there once.  Builder::build / build_v5 / build_11 are compositions of the same parts, each a member of Builder that
+// takes the family's block as a callable `block(i, src, dst, level, name)`:
+//   stem (3x3 or 6x6; fp16 two launches, fp16 fused with b1, fp32) | backbone (block, 3 x [3x3 s2, block], SPPF; sets quiet_step) |
+//   top_down (the fold-the-upsampling decision, else upsampling steps; YOLOv8, YOLO11) | bottom_up (2 x [3x3 s2, block]; notes the
+//   fork points) | head_open / head_last / head_close (YOLOv8, YOLO11: widths, box branches, last 1x1 with or without the decode).
+// The blocks: c2f (the C2f skeleton: YOLOv8's C2f with `pair` inside, YOLO11's C3k2 with `bottleneck` at half width or `c3` inside),
+// c3 (YOLOv5's C3, YOLO11's C3k), sppf, c2psa.  A block's input is a Src: a view, or (low, skip) for cat[up(low), skip]; conv_in
+// emits the one or the other.  Geo holds the batch, the widths and the five pyramid levels: buffers and steps name a level.
+#include <algorithm>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -98,81 +110,98 @@ struct rva_yolov8_plan {
 
 namespace {
 
+struct Geo {            // computed once per plan: the batch, the widths c[1..5] and the pyramid levels l = 1..5 (the input at stride 2^l)
+    int B = 0, H = 0, W = 0, c[6] = {}, h[6] = {}, w[6] = {};
+    explicit Geo(const rva_yolov8_desc &d) : B(d.batch), H(d.height), W(d.width)
+    {
+        for (int l = 1; l <= 5; ++l) { c[l] = d.widths[l - 1]; h[l] = H >> l; w[l] = W >> l; }
+    }
+    float stride(int l) const { return (float)(1 << l); }
+    int a0(int l) const { return l <= 3 ? 0 : a0(l - 1) + h[l - 1] * w[l - 1]; }      // grid cells of the detect levels 3 .. l - 1
+};
+
+struct Src {            // what a block reads: one view, or (low, skip) standing for cat([upsample2x(low), skip])
+    View v, low; bool up = false;
+    Src(View x) : v(x) {}
+    Src(View l, View skip) : v(skip), low(l), up(true) {}
+    int ch() const { return up ? low.ch + v.ch : v.ch; }
+};
+
+struct Head {           // the detect head of YOLOv8 and YOLO11: widths, the box branches' convolutions, the decode step over all levels
+    int rm4, cb, cc_real, cc, ncp;        // 4 reg_max | box branch | class branch as the checkpoint has it, as it runs | logit columns
+    const rva_conv_weights *box[3][3];
+    Step h3s;
+};
+
 struct Builder {
     rva_yolov8_plan *p;
     const rva_conv_weights *convs;
+    const Geo g;
     int next = 0;                         // next convolution of the module-order list
     int lane = 0;
-    std::string err;
+    int fork_at[2] = {-1, -1};            // the steps in front of which n3 / m4 are complete (bottom_up)
+    std::string err;                      // the first failure; nothing is launched and every builder returns false once it is set
+    bool hip_failed = false;              // ... and whether it was a HIP call that failed
     std::deque<std::vector<float>> pad_store;             // zero-extended host copies of the class branch (padded) ...
     std::deque<rva_conv_weights> pad_convs;               // ... and their descriptors
 
-    bool fail(const std::string &m) { if (err.empty()) err = m; return false; }
+    Builder(rva_yolov8_plan *plan, const rva_conv_weights *cv) : p(plan), convs(cv), g(plan->d) {}
+
+    bool fail(const std::string &m, bool hip = false)
+    {
+        if (err.empty()) { err = m; hip_failed = hip; }
+        return false;
+    }
 
     void *dev_alloc(size_t bytes, bool zero)
     {
         void *ptr = nullptr;
-        if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) { fail("hipMalloc failed"); return nullptr; }
+        if (hipMalloc(&ptr, bytes ? bytes : 16) != hipSuccess) { fail("hipMalloc failed", true); return nullptr; }
         p->allocs.push_back(ptr);
-        if (zero && hipMemset(ptr, 0, bytes) != hipSuccess) { fail("hipMemset failed"); return nullptr; }
+        if (zero && hipMemset(ptr, 0, bytes) != hipSuccess) { fail("hipMemset failed", true); return nullptr; }
         return ptr;
     }
-    View buf(long m, int ch)
+    // a zeroed activation buffer of level l, ch channels wide (a failed allocation is in `err`: the next pack() stops the builder)
+    View buf(int l, int ch)
     {
         View v;
         // + 64 B: a convolution whose Cin is not a multiple of 32 runs with Cin rounded up (zero weights for the extra channels, see
         // conv()) and reads up to 31 channels past its slice -- the next slice of the row, the next row, or, behind the last row, this slack
         v.es = p->f32 ? 4 : 2;
-        v.base = (char *)dev_alloc((size_t)m * ch * v.es + 64, true);
+        v.base = (char *)dev_alloc((size_t)g.B * g.h[l] * g.w[l] * ch * v.es + 64, true);
         v.ld = ch; v.off = 0; v.ch = ch;
         return v;
     }
-    // Pack sibling convolutions (equal Cin / kernel / stride, outputs concatenated) as [CoutPad][k*k][CinPad] fp16 + [CoutPad] fp32
-    bool upload(const void *host, size_t bytes, const void **dev)
+    bool upload(const void *host, size_t bytes, const void **dev, const char *what = "weight")
     {
         void *d = dev_alloc(bytes, false);
         if (!d) return false;
-        if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("weight upload failed");
+        if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(std::string(what) + " upload failed", true);
         *dev = d;
         return true;
     }
-    // fp32 plan: sibling convolutions packed as [Cout][k*k][Cin] fp32 (no padding: rva_conv2d_nhwc_f32_v masks the tile edges) + [Cout] fp32
-    bool pack_f32(const rva_conv_weights *const *cv, int n, const void **w_dev, const float **b_dev, int *cin, int *cout, int *k, int *stride)
+    // a weight / bias pair
+    bool upload(const void *w, size_t w_bytes, const std::vector<float> &b, const void **dw, const float **db, const char *what = "weight")
     {
-        const rva_conv_weights &c0 = *cv[0];
-        int co = 0;
-        for (int i = 0; i < n; ++i) {
-            if (!cv[i]->weight || cv[i]->cin != c0.cin || cv[i]->k != c0.k || cv[i]->stride != c0.stride) return fail("sibling convolutions differ");
-            co += cv[i]->cout;
-        }
-        const int kk = c0.k * c0.k;
-        std::vector<float> hw((size_t)co * kk * c0.cin, 0.f), hb(co, 0.f);
-        int o = 0;
-        for (int i = 0; i < n; ++i) {
-            const rva_conv_weights &c = *cv[i];
-            for (int oc = 0; oc < c.cout; ++oc) {
-                for (int ic = 0; ic < c.cin; ++ic)
-                    for (int t = 0; t < kk; ++t)
-                        hw[((size_t)(o + oc) * kk + t) * c.cin + ic] = c.weight[((size_t)oc * c.cin + ic) * kk + t];
-                if (c.bias) hb[o + oc] = c.bias[oc];
-            }
-            o += c.cout;
-        }
-        const void *db = nullptr;
-        if (!upload(hw.data(), hw.size() * 4, w_dev) || !upload(hb.data(), hb.size() * 4, &db)) return false;
-        *b_dev = (const float *)db; *cin = c0.cin; *cout = co; *k = c0.k; *stride = c0.stride;
+        const void *d = nullptr;
+        if (!upload(w, w_bytes, dw, what) || !upload(b.data(), b.size() * sizeof(float), &d, what)) return false;
+        *db = (const float *)d;
         return true;
     }
-    bool pack(const rva_conv_weights *const *cv, int n, const void **w_dev, const float **b_dev, int *cin, int *cout, int *k, int *stride)
+    // Pack sibling convolutions (equal Cin / kernel / stride, outputs concatenated) as [CoutPad][k*k][CinPad] T + [CoutPad] fp32 into
+    // (s.w, s.b) with the shape, or with `second` into (s.w2, s.b2) alone.  pad: Cout up to rva_conv_cout_pad, Cin up to 32
+    template <typename T>
+    bool pack_as(const rva_conv_weights *const *cv, int n, bool pad, Step &s, bool second)
     {
+        if (!err.empty()) return false;   // a take() or a buffer in front of this step failed
         const rva_conv_weights &c0 = *cv[0];
         int co = 0;
         for (int i = 0; i < n; ++i) {
             if (!cv[i]->weight || cv[i]->cin != c0.cin || cv[i]->k != c0.k || cv[i]->stride != c0.stride) return fail("sibling convolutions differ");
             co += cv[i]->cout;
         }
-        const int kk = c0.k * c0.k, cpad = rva_conv_cout_pad(co), cinp = (c0.cin + 31) / 32 * 32;
-        std::vector<_Float16> hw((size_t)cpad * kk * cinp, (_Float16)0.f);
+        const int kk = c0.k * c0.k, cpad = pad ? rva_conv_cout_pad(co) : co, cinp = pad ? (c0.cin + 31) / 32 * 32 : c0.cin;
+        std::vector<T> hw((size_t)cpad * kk * cinp, (T)0.f);
         std::vector<float> hb(cpad, 0.f);
         int o = 0;
         for (int i = 0; i < n; ++i) {
@@ -180,17 +209,19 @@ struct Builder {
             for (int oc = 0; oc < c.cout; ++oc) {
                 for (int ic = 0; ic < c.cin; ++ic)
                     for (int t = 0; t < kk; ++t)
-                        hw[((size_t)(o + oc) * kk + t) * cinp + ic] = (_Float16)c.weight[((size_t)oc * c.cin + ic) * kk + t];
+                        hw[((size_t)(o + oc) * kk + t) * cinp + ic] = (T)c.weight[((size_t)oc * c.cin + ic) * kk + t];
                 if (c.bias) hb[o + oc] = c.bias[oc];
             }
             o += c.cout;
         }
-        void *dw = dev_alloc(hw.size() * 2, false), *db = dev_alloc(hb.size() * 4, false);
-        if (!dw || !db) return false;
-        if (hipMemcpy(dw, hw.data(), hw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(db, hb.data(), hb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("weight upload failed");
-        *w_dev = dw; *b_dev = (const float *)db; *cin = c0.cin; *cout = co; *k = c0.k; *stride = c0.stride;
+        if (!upload(hw.data(), hw.size() * sizeof(T), hb, second ? &s.w2 : &s.w, second ? &s.b2 : &s.b)) return false;
+        if (!second) { s.Cin = c0.cin; s.Cout = co; s.k = c0.k; s.stride = c0.stride; }
         return true;
+    }
+    // fp16 padded for the kernels of rva_conv.hip; an fp32 plan as it is (rva_conv2d_nhwc_f32_v masks the tile edges)
+    bool pack(const rva_conv_weights *const *cv, int n, Step &s, bool second = false)
+    {
+        return p->f32 ? pack_as<float>(cv, n, false, s, second) : pack_as<_Float16>(cv, n, true, s, second);
     }
     const rva_conv_weights *take(int cin, int cout, int k, int stride, const char *what)
     {
@@ -205,6 +236,7 @@ struct Builder {
         }
         return c;
     }
+    bool all_taken() { return next == p->d.n_convs || fail("convolution list longer than the architecture"); }
     // `c` with input / output channels zero-extended to cinp / coutp (the convolution itself where nothing is to pad)
     const rva_conv_weights *padded(const rva_conv_weights *c, int cinp, int coutp)
     {
@@ -234,189 +266,66 @@ struct Builder {
         }
         p->steps.push_back(s);
     }
-    // one Conv-BN-SiLU (or a fused group of siblings); returns false on error
-    bool conv(const rva_conv_weights *const *cv, int n, View src, View dst, int h, int w, int act, const View *res = nullptr)
+
+    // ---------------------------------------------------------------------------------------------- steps
+    // one Conv-BN-SiLU (or a fused group of siblings) on a level-l input; returns false on error
+    bool conv(const rva_conv_weights *const *cv, int n, View src, View dst, int l, int act, const View *res = nullptr)
     {
         Step s{}; s.kind = p->f32 ? K_CONV_F32 : K_CONV;
-        const bool packed = p->f32 ? pack_f32(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)
-                                   : pack(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride);
-        if (!packed) return false;
+        if (!pack(cv, n, s)) return false;
         if (s.Cin != src.ch || s.Cout != dst.ch) return fail("convolution does not fit its buffers");
-        s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.act = act;
+        s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = g.h[l]; s.W = g.w[l]; s.act = act;
         if (res) { s.res = res->ptr(); s.ldr = res->ld; }
-        const int cin_real = s.Cin;
-        s.c_real = cin_real;
+        s.c_real = s.Cin;
         if (p->f32) {                     // every channel count is read as it is: the kernel never reads past its slice
             if (s.Cin % 16) return fail("fp32 plan: convolution input channels must be multiples of 16");
-            push(s, "%d->%d k%ds%d %dx%d", cin_real, s.Cout, s.k, s.stride, h, w);
-            return true;
+        } else if (s.Cin % 32 && !(p->d.flags & RVA_PLAN_NO_CIN_PAD)) {
+            // Cin 48 / 16 (YOLOv8m / n): the LDS-DMA kernels want whole 32-channel chunks.  The packed weights already carry zero
+            // columns up to the next multiple of 32, so the step simply declares the padded Cin: the extra channels it reads are whatever
+            // follows the slice (finite activations of the neighbouring slice / pixel, or the buffer's zero slack) times zero.
+            s.Cin = (s.Cin + 31) / 32 * 32;
         }
-        // Cin 48 / 16 (YOLOv8m / n): the LDS-DMA kernels want whole 32-channel chunks.  The packed weights already carry zero
-        // columns up to the next multiple of 32, so the step simply declares the padded Cin: the extra channels it reads are whatever
-        // follows the slice (finite activations of the neighbouring slice / pixel, or the buffer's zero slack) times zero.
-        if (s.Cin % 32 && !(p->d.flags & RVA_PLAN_NO_CIN_PAD)) s.Cin = (s.Cin + 31) / 32 * 32;
-        push(s, "%d->%d k%ds%d %dx%d", cin_real, s.Cout, s.k, s.stride, h, w);
+        push(s, "%d->%d k%ds%d %dx%d", s.c_real, s.Cout, s.k, s.stride, s.H, s.W);
         return true;
     }
-    bool conv1(const rva_conv_weights *c, View src, View dst, int h, int w, int act, const View *res = nullptr)
+    bool conv1(const rva_conv_weights *c, View src, View dst, int l, int act, const View *res = nullptr)
     {
-        return c && conv(&c, 1, src, dst, h, w, act, res);
+        return c && conv(&c, 1, src, dst, l, act, res);
     }
-    bool upcat(const rva_conv_weights *c, View low, View skip, View dst, int h, int w) { return c && upcat(&c, 1, low, skip, dst, h, w); }
-    bool upcat(const rva_conv_weights *const *cv, int n, View low, View skip, View dst, int h, int w)
+    // the 1x1 convolution(s) a block opens with: plain, or with the upsample + concat folded in (rva_conv1x1_upcat_f16)
+    bool conv_in(const rva_conv_weights *const *cv, int n, const Src &src, View dst, int l)
     {
+        if (!src.up) return conv(cv, n, src.v, dst, l, 1);
+        const View &low = src.low, &skip = src.v;
         Step s{}; s.kind = K_UPCAT;
-        if (!pack(cv, n, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
-        if (s.k != 1 || s.stride != 1 || s.Cin != low.ch + skip.ch || s.Cout != dst.ch) return fail("upsample + concat convolution does not fit");
+        if (!pack(cv, n, s)) return false;
+        if (s.k != 1 || s.stride != 1 || s.Cin != src.ch() || s.Cout != dst.ch) return fail("upsample + concat convolution does not fit");
         s.in = low.ptr(); s.ldi = low.ld; s.c_in = low.ch; s.in2 = skip.ptr(); s.ldi2 = skip.ld; s.c_in2 = skip.ch;
-        s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.act = 1;
-        push(s, "up%d+%d->%d k1s1 %dx%d", low.ch, skip.ch, s.Cout, h, w);
+        s.out = dst.ptr(); s.ldo = dst.ld; s.H = g.h[l]; s.W = g.w[l]; s.act = 1;
+        push(s, "up%d+%d->%d k1s1 %dx%d", low.ch, skip.ch, s.Cout, s.H, s.W);
         return true;
     }
-    bool head(const rva_conv_weights *c, View src, int mode, int h, int w, int a0, float stride_px)
+    // 1x1 convolution + decode of a detect branch (mode 1: box, 2: class) at level l, into the level's anchor range of the output
+    bool head(const rva_conv_weights *c, View src, int mode, int l)
     {
         if (!c) return false;
         Step s{}; s.kind = K_HEAD;
-        if (!pack(&c, 1, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
+        if (!pack(&c, 1, s)) return false;
         if (s.k != 1 || s.stride != 1 || s.Cin != src.ch) return fail("head convolution does not fit");
-        s.in = src.ptr(); s.ldi = src.ld; s.H = h; s.W = w; s.mode = mode; s.a0 = a0; s.stride_px = stride_px;
-        push(s, "head%d:%d->%d k1s1 %dx%d", mode, s.Cin, s.Cout, h, w);
+        s.in = src.ptr(); s.ldi = src.ld; s.H = g.h[l]; s.W = g.w[l]; s.mode = mode; s.a0 = g.a0(l); s.stride_px = g.stride(l);
+        push(s, "head%d:%d->%d k1s1 %dx%d", mode, s.Cin, s.Cout, s.H, s.W);
         return true;
     }
-    // C2f: src is one view, or (low, skip) standing for cat([upsample2x(low), skip])
-    bool c2f(int c1, int c2, int n, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w, const char *what)
+    // nearest 2x upsampling of the level-l map src into dst (level l - 1)
+    void up2(View src, View dst, int l)
     {
-        const int c = c2 / 2;
-        const long m = (long)p->B * h * w;
-        const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, what), *cv2 = take((2 + n) * c, c2, 1, 1, what);
-        if (!cv1 || !cv2) return false;
-        View cat = buf(m, (2 + n) * c);
-        if (!cat.base) return false;
-        if (low) { if (!upcat(cv1, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
-        else if (!conv1(cv1, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
-        for (int i = 0; i < n; ++i) {
-            const rva_conv_weights *b1 = take(c, c, 3, 1, what), *b2 = take(c, c, 3, 1, what);
-            View x = cat.sub((1 + i) * c, c);
-            if (c == 32 && shortcut && !p->f32 && !(p->d.flags & RVA_PLAN_NO_PAIR32)) {
-                // both 3x3 convolutions and the shortcut in one launch, the intermediate in LDS (rva_c2f_pair32_f16)
-                Step s{}; s.kind = K_PAIR32;
-                int ci, co, kk, st;
-                if (!pack(&b1, 1, &s.w, &s.b, &ci, &co, &kk, &st) || !pack(&b2, 1, &s.w2, &s.b2, &ci, &co, &kk, &st)) return false;
-                View y = cat.sub((2 + i) * c, c);
-                s.in = x.ptr(); s.ldi = x.ld; s.out = y.ptr(); s.ldo = y.ld; s.H = h; s.W = w; s.Cin = s.Cout = c; s.k = 3; s.stride = 1; s.act = 1;
-                push(s, nullptr);
-                continue;
-            }
-            // the intermediate, one buffer per bottleneck: with row windows a step rewrites part of its output only, and the rest must
-            // still be what THIS bottleneck's first convolution left there (the second one reads it as halo)
-            View tmp = buf(m, c);
-            if (!tmp.base) return false;
-            if (!conv1(b1, x, tmp, h, w, 1)) return false;
-            if (!conv1(b2, tmp, cat.sub((2 + i) * c, c), h, w, 1, shortcut ? &x : nullptr)) return false;
-        }
-        return conv1(cv2, cat, dst, h, w, 1);
-    }
-
-    // YOLOv5's C3: src is one view, or (low, skip) standing for cat([upsample2x(low), skip]).  cv1 and cv2 read the same input:
-    // one sibling launch writes cat[0, 2c) = [cv1 out | cv2 out]; the bottlenecks x <- x + cv2_3x3(cv1_1x1(x)) start from cv1 out,
-    // the last one writes cat[2c, 3c), and cv3 reads cat[c, 3c) = [cv2 out | m out] with the halves of its input channels swapped
-    // on the host (the module concatenates [m out | cv2 out]).
-    // k1: kernel of every bottleneck's first convolution (1: YOLOv5's C3; 3: YOLO11's C3k, whose bottlenecks are 3x3, 3x3)
-    bool c3(int c1, int c2, int n, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w, const char *what,
-            int k1 = 1)
-    {
-        const int c = c2 / 2;
-        const long m = (long)p->B * h * w;
-        const rva_conv_weights *cv[2] = {take(c1, c, 1, 1, what), take(c1, c, 1, 1, what)};
-        const rva_conv_weights *cv3 = take(2 * c, c2, 1, 1, what);
-        if (!cv[0] || !cv[1] || !cv3 || n < 1) return n < 1 ? fail("a C3 block needs at least one bottleneck") : false;
-        View cat = buf(m, 3 * c);
-        if (!cat.base) return false;
-        if (low) { if (!upcat(cv, 2, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
-        else if (!conv(cv, 2, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
-        View x = cat.sub(0, c);
-        for (int i = 0; i < n; ++i) {
-            const rva_conv_weights *b1 = take(c, c, k1, 1, what), *b2 = take(c, c, 3, 1, what);
-            // intermediate and output of every bottleneck in buffers of their own: with row windows a step rewrites part of its
-            // output only, and the rest must still be what THIS bottleneck left there (see c2f)
-            View tmp = buf(m, c), y = i == n - 1 ? cat.sub(2 * c, c) : buf(m, c);
-            if (!tmp.base || !y.base) return false;
-            if (!conv1(b1, x, tmp, h, w, 1) || !conv1(b2, tmp, y, h, w, 1, shortcut ? &x : nullptr)) return false;
-            x = y;
-        }
-        if (!cv3->weight) return fail("convolution without weights");
-        std::vector<float> &sw = pad_store.emplace_back((size_t)c2 * 2 * c, 0.f);
-        for (int oc = 0; oc < c2; ++oc)
-            for (int ic = 0; ic < 2 * c; ++ic) sw[(size_t)oc * 2 * c + ic] = cv3->weight[(size_t)oc * 2 * c + (ic + c) % (2 * c)];
-        rva_conv_weights q = *cv3;
-        q.weight = sw.data();
-        return conv1(&pad_convs.emplace_back(q), cat.sub(c, 2 * c), dst, h, w, 1);
-    }
-
-    // fp16 stem from the planar input K1 writes, and the 3x3 s2 behind it: x1 = b1(b0(input)).  Stem weights [64][32] fp16, column
-    // order k = 2 j + kx (kx in {0, 1}), k = 18 + j (kx = 2), j = c*3 + ky
-    bool stem_f16(const rva_conv_weights *b0, const rva_conv_weights *b1, View *x1)
-    {
-        const rva_yolov8_desc &d = p->d;
-        const int B = d.batch, H = d.height, W = d.width, c1 = d.widths[0], c2 = d.widths[1];
-        const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4;
-        if (c1 > 64) return fail("stem wider than 64 channels");
-        if (!b0->weight) return fail("b0: no stem convolution");
-        std::vector<_Float16> sw(64 * 32, (_Float16)0.f);
-        std::vector<float> sb(64, 0.f);
-        for (int co = 0; co < c1; ++co) {
-            for (int j = 0; j < 9; ++j)                       // j = c*3 + ky;  weight[co][c][ky][kx]
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float v = b0->weight[((size_t)co * 3 + j / 3) * 9 + (j % 3) * 3 + kx];
-                    sw[co * 32 + (kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)v;
-                }
-            if (b0->bias) sb[co] = b0->bias[co];
-        }
-        void *dsw = dev_alloc(sw.size() * 2, false), *dsb = dev_alloc(sb.size() * 4, false);
-        if (!dsw || !dsb) return false;
-        if (hipMemcpy(dsw, sw.data(), sw.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dsb, sb.data(), sb.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("stem upload failed");
-        *x1 = buf((long)B * h2 * w2, c2);
-        if (!x1->base) return false;
-        p->fused_stem = c1 == 32 && c2 == 64 && !(d.flags & RVA_PLAN_NO_STEM2);
-        if (p->fused_stem) {
-            Step s{}; s.kind = K_STEM2; s.w = dsw; s.b = (const float *)dsb; s.out = x1->ptr(); s.ldo = x1->ld; s.H = H; s.W = W;
-            int ci, co, k, st;
-            if (!pack(&b1, 1, &s.w2, &s.b2, &ci, &co, &k, &st)) return false;
-            push(s, nullptr);
-            return true;
-        }
-        View x0 = buf((long)B * h1 * w1, c1);
-        if (!x0.base) return false;
-        Step s{}; s.kind = K_STEM; s.w = dsw; s.b = (const float *)dsb; s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
+        Step s{}; s.kind = p->f32 ? K_UP2_F32 : K_UP2; s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld;
+        s.H = g.h[l]; s.W = g.w[l]; s.Cin = src.ch;
         push(s, nullptr);
-        return conv1(b1, x0, *x1, h1, w1, 1);
     }
-
-    // SPPF: cv1, three chained 5x5 max pools into the slices of one concat buffer, cv2
-    bool sppf(int c5, View src, View dst, int h5, int w5)
-    {
-        const int c_ = c5 / 2;
-        const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
-        View cat = buf((long)p->B * h5 * w5, 4 * c_);
-        if (!cat.base || !conv1(cv1, src, cat.sub(0, c_), h5, w5, 1)) return false;
-        if (h5 * w5 <= 2400 && !p->f32) {
-            Step s{}; s.kind = K_SPPF3; s.in = cat.sub(0, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub(c_, c_).ptr(); s.out2 = cat.sub(2 * c_, c_).ptr();
-            s.out3 = cat.sub(3 * c_, c_).ptr(); s.ldo = cat.ld; s.H = h5; s.W = w5; s.Cin = c_;
-            push(s, nullptr);
-        } else {
-            for (int i = 0; i < 3; ++i) {
-                Step s{}; s.kind = p->f32 ? K_POOL5_F32 : K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
-                s.H = h5; s.W = w5; s.Cin = c_;
-                push(s, nullptr);
-            }
-        }
-        return conv1(cv2, cat, dst, h5, w5, 1);
-    }
-
     // Depthwise 3x3 (rva_dwconv3x3_nhwc_f16) over channels [c_off, c_off + dst.ch) of `c` (weight [C][1][3][3]): weights repacked
     // [9][dst.ch] fp16 (tap major).  Untunable; always the whole map.
-    bool dwconv(const rva_conv_weights *c, int c_off, View src, View dst, int h, int w, int act, const View *res = nullptr)
+    bool dwconv(const rva_conv_weights *c, int c_off, View src, View dst, int l, int act, const View *res = nullptr)
     {
         const int C = dst.ch;
         if (!c) return false;
@@ -429,49 +338,102 @@ struct Builder {
             if (c->bias) hb[ch] = c->bias[c_off + ch];
         }
         Step s{}; s.kind = K_DWCONV;
-        const void *db = nullptr;
-        if (!upload(hw.data(), hw.size() * 2, &s.w) || !upload(hb.data(), hb.size() * 4, &db)) return false;
-        s.b = (const float *)db;
-        s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = h; s.W = w; s.Cin = s.Cout = C; s.k = 3; s.stride = 1; s.act = act;
+        if (!upload(hw.data(), hw.size() * 2, hb, &s.w, &s.b)) return false;
+        s.in = src.ptr(); s.ldi = src.ld; s.out = dst.ptr(); s.ldo = dst.ld; s.H = g.h[l]; s.W = g.w[l]; s.Cin = s.Cout = C; s.k = 3; s.stride = 1; s.act = act;
         if (res) { s.res = res->ptr(); s.ldr = res->ld; }
         push(s, nullptr);
         return true;
     }
 
-    // YOLO11's C3k2: a C2f with c = c2 / 4 (quarter) or c2 / 2 whose inner blocks are bottlenecks 3x3 c -> c/2, 3x3 c/2 -> c, or
-    // with c3k a C3 at width c / 2 with two 3x3, 3x3 bottlenecks, which writes its cv3 into the outer concat slice.  src as for c2f.
-    bool c3k2(int c1, int c2, int n, bool c3k, bool quarter, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w,
-              const char *what)
+    // ---------------------------------------------------------------------------------------------- blocks
+    // Bottleneck y = cv2_3x3(cv1_k1xk1(x)) (+ x) through cmid channels.  The intermediate is a buffer of this bottleneck alone: with
+    // row windows a step rewrites part of its output only, and the rest must still be what THIS bottleneck's first convolution left
+    // there (the second one reads it as halo)
+    bool bottleneck(View x, View y, int cmid, bool shortcut, int l, const char *what, int k1 = 3)
     {
-        const int c = quarter ? c2 / 4 : c2 / 2;
-        const long m = (long)p->B * h * w;
-        if (n < 1 || c % 16) return fail("a C3k2 block needs at least one inner block and an inner width that is a multiple of 16");
-        const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, what), *cv2 = take((2 + n) * c, c2, 1, 1, what);
-        if (!cv1 || !cv2) return false;
-        View cat = buf(m, (2 + n) * c);
-        if (!cat.base) return false;
-        if (low) { if (!upcat(cv1, *low, *skip, cat.sub(0, 2 * c), h, w)) return false; }
-        else if (!conv1(cv1, *src, cat.sub(0, 2 * c), h, w, 1)) return false;
-        for (int i = 0; i < n; ++i) {
-            View x = cat.sub((1 + i) * c, c), y = cat.sub((2 + i) * c, c);
-            if (c3k) {
-                if (!c3(c, c, 2, shortcut, &x, nullptr, nullptr, y, h, w, what, 3)) return false;
-                continue;
-            }
-            const rva_conv_weights *b1 = take(c, c / 2, 3, 1, what), *b2 = take(c / 2, c, 3, 1, what);
-            View tmp = buf(m, c / 2);                       // one per bottleneck, as in c2f
-            if (!tmp.base || !conv1(b1, x, tmp, h, w, 1) || !conv1(b2, tmp, y, h, w, 1, shortcut ? &x : nullptr)) return false;
-        }
-        return conv1(cv2, cat, dst, h, w, 1);
+        const rva_conv_weights *b1 = take(x.ch, cmid, k1, 1, what), *b2 = take(cmid, y.ch, 3, 1, what);
+        View tmp = buf(l, cmid);
+        return conv1(b1, x, tmp, l, 1) && conv1(b2, tmp, y, l, 1, shortcut ? &x : nullptr);
     }
-
-    // YOLO11's C2PSA.  Every buffer slice has ONE writer (a windowed convolution rewrites part of its output only, see c2f), so
-    // cv1 runs as two launches: `a` goes straight into cv2's input buffer, `b` into a buffer of its own, and the last block's
-    // ffn writes the other half of cv2's input.  Attention and the positional encoding always run the whole map.
-    bool c2psa(int c1, int n, int heads, View src, View dst, int h, int w)
+    // C2f's bottleneck, 3x3 and 3x3 at full width; 32 channels wide with a shortcut both convolutions and the shortcut are one
+    // launch, the intermediate in LDS (rva_c2f_pair32_f16)
+    bool pair(View x, View y, bool shortcut, int l, const char *what)
     {
-        const int c = c1 / 2;
-        const long m = (long)p->B * h * w;
+        const int c = x.ch;
+        if (c != 32 || !shortcut || p->f32 || (p->d.flags & RVA_PLAN_NO_PAIR32)) return bottleneck(x, y, c, shortcut, l, what);
+        const rva_conv_weights *b1 = take(c, c, 3, 1, what), *b2 = take(c, c, 3, 1, what);
+        Step s{}; s.kind = K_PAIR32;
+        if (!b1 || !b2 || !pack(&b1, 1, s) || !pack(&b2, 1, s, true)) return false;
+        s.in = x.ptr(); s.ldi = x.ld; s.out = y.ptr(); s.ldo = y.ld; s.H = g.h[l]; s.W = g.w[l]; s.act = 1;
+        push(s, nullptr);
+        return true;
+    }
+    // The C2f skeleton (YOLOv8's C2f, YOLO11's C3k2): cv1 into the front 2c channels of one concat buffer, n inner blocks
+    // inner(x = cat[(1 + i) c, c), y = cat[(2 + i) c, c)), cv2 over the whole buffer
+    template <typename Inner>
+    bool c2f(int c, int n, const Src &src, View dst, int l, const char *what, Inner inner)
+    {
+        const rva_conv_weights *cv1 = take(src.ch(), 2 * c, 1, 1, what), *cv2 = take((2 + n) * c, dst.ch, 1, 1, what);
+        if (!cv1 || !cv2) return false;
+        View cat = buf(l, (2 + n) * c);
+        if (!conv_in(&cv1, 1, src, cat.sub(0, 2 * c), l)) return false;
+        for (int i = 0; i < n; ++i)
+            if (!inner(cat.sub((1 + i) * c, c), cat.sub((2 + i) * c, c))) return false;
+        return conv1(cv2, cat, dst, l, 1);
+    }
+    // YOLOv5's C3 and, with k1 = 3, YOLO11's C3k (k1: kernel of every bottleneck's first convolution).  cv1 and cv2 read the same
+    // input: one sibling launch writes cat[0, 2c) = [cv1 out | cv2 out]; the bottlenecks x <- x + cv2_3x3(cv1(x)) start from cv1 out,
+    // every one but the last writes a buffer of its own (one writer per slice, see bottleneck), the last one cat[2c, 3c), and cv3
+    // reads cat[c, 3c) = [cv2 out | m out] with the halves of its input channels swapped on the host (the module concatenates
+    // [m out | cv2 out]).
+    bool c3(int n, bool shortcut, const Src &src, View dst, int l, const char *what, int k1 = 1)
+    {
+        const int c2 = dst.ch, c = c2 / 2;
+        const rva_conv_weights *cv[2] = {take(src.ch(), c, 1, 1, what), take(src.ch(), c, 1, 1, what)};
+        const rva_conv_weights *cv3 = take(2 * c, c2, 1, 1, what);
+        if (!cv[0] || !cv[1] || !cv3 || n < 1) return n < 1 ? fail("a C3 block needs at least one bottleneck") : false;
+        View cat = buf(l, 3 * c);
+        if (!conv_in(cv, 2, src, cat.sub(0, 2 * c), l)) return false;
+        View x = cat.sub(0, c);
+        for (int i = 0; i < n; ++i) {
+            View y = i == n - 1 ? cat.sub(2 * c, c) : buf(l, c);
+            if (!bottleneck(x, y, c, shortcut, l, what, k1)) return false;
+            x = y;
+        }
+        if (!cv3->weight) return fail("convolution without weights");
+        std::vector<float> &sw = pad_store.emplace_back((size_t)c2 * 2 * c, 0.f);
+        for (int oc = 0; oc < c2; ++oc)
+            for (int ic = 0; ic < 2 * c; ++ic) sw[(size_t)oc * 2 * c + ic] = cv3->weight[(size_t)oc * 2 * c + (ic + c) % (2 * c)];
+        rva_conv_weights q = *cv3;
+        q.weight = sw.data();
+        return conv1(&pad_convs.emplace_back(q), cat.sub(c, 2 * c), dst, l, 1);
+    }
+    // SPPF at level 5: cv1, three chained 5x5 max pools into the slices of one concat buffer, cv2
+    bool sppf(View src, View dst)
+    {
+        const int c5 = src.ch, c_ = c5 / 2, h5 = g.h[5], w5 = g.w[5];
+        const rva_conv_weights *cv1 = take(c5, c_, 1, 1, "b9.cv1"), *cv2 = take(4 * c_, c5, 1, 1, "b9.cv2");
+        View cat = buf(5, 4 * c_);
+        if (!conv1(cv1, src, cat.sub(0, c_), 5, 1)) return false;
+        if (h5 * w5 <= 2400 && !p->f32) {
+            Step s{}; s.kind = K_SPPF3; s.in = cat.sub(0, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub(c_, c_).ptr(); s.out2 = cat.sub(2 * c_, c_).ptr();
+            s.out3 = cat.sub(3 * c_, c_).ptr(); s.ldo = cat.ld; s.H = h5; s.W = w5; s.Cin = c_;
+            push(s, nullptr);
+        } else {
+            for (int i = 0; i < 3; ++i) {
+                Step s{}; s.kind = p->f32 ? K_POOL5_F32 : K_POOL5; s.in = cat.sub(i * c_, c_).ptr(); s.ldi = cat.ld; s.out = cat.sub((i + 1) * c_, c_).ptr(); s.ldo = cat.ld;
+                s.H = h5; s.W = w5; s.Cin = c_;
+                push(s, nullptr);
+            }
+        }
+        return conv1(cv2, cat, dst, 5, 1);
+    }
+    // YOLO11's C2PSA at level 5.  Every buffer slice has ONE writer (a windowed convolution rewrites part of its output only, see
+    // bottleneck), so cv1 runs as two launches: `a` goes straight into cv2's input buffer, `b` into a buffer of its own, and the last
+    // block's ffn writes the other half of cv2's input.  Attention and the positional encoding always run the whole map.
+    bool c2psa(int n, int heads, View src, View dst)
+    {
+        const int c1 = src.ch, c = c1 / 2, l = 5;
         if (n < 1 || heads * 64 != c) return fail("C2PSA: psa_heads * 64 must be half the width of the block, and psa_blocks >= 1");
         const rva_conv_weights *cv1 = take(c1, 2 * c, 1, 1, "10.cv1"), *cv2 = take(2 * c, c1, 1, 1, "10.cv2");
         if (!cv1 || !cv2) return false;
@@ -480,335 +442,288 @@ struct Builder {
         qa.cout = qb.cout = c;
         qb.weight = cv1->weight + (size_t)c * c1;
         if (cv1->bias) qb.bias = cv1->bias + c;
-        View cat = buf(m, 2 * c), x = buf(m, c);
-        if (!cat.base || !x.base) return false;
-        if (!conv1(&pad_convs.emplace_back(qa), src, cat.sub(0, c), h, w, 1) || !conv1(&pad_convs.emplace_back(qb), src, x, h, w, 1)) return false;
+        View cat = buf(l, 2 * c), x = buf(l, c);
+        if (!conv1(&pad_convs.emplace_back(qa), src, cat.sub(0, c), l, 1) || !conv1(&pad_convs.emplace_back(qb), src, x, l, 1)) return false;
         for (int i = 0; i < n; ++i) {
             const rva_conv_weights *qkv = take(c, 2 * c, 1, 1, "10.attn.qkv"), *proj = take(c, c, 1, 1, "10.attn.proj"), *pe = take(1, c, 3, 1, "10.attn.pe"),
                                    *f0 = take(c, 2 * c, 1, 1, "10.ffn.0"), *f1 = take(2 * c, c, 1, 1, "10.ffn.1");
             if (!qkv || !proj || !pe || !f0 || !f1) return false;
-            View q = buf(m, 2 * c), ao = buf(m, c), xo = buf(m, c), x1 = buf(m, c), f = buf(m, 2 * c);
-            View y = i == n - 1 ? cat.sub(c, c) : buf(m, c);
-            if (!q.base || !ao.base || !xo.base || !x1.base || !f.base || !y.base) return false;
-            if (!conv1(qkv, x, q, h, w, 0)) return false;
-            Step s{}; s.kind = K_ATTN; s.in = q.ptr(); s.ldi = q.ld; s.out = ao.ptr(); s.ldo = ao.ld; s.H = h; s.W = w; s.Cin = 2 * c; s.Cout = c; s.mode = heads;
+            View q = buf(l, 2 * c), ao = buf(l, c), xo = buf(l, c), x1 = buf(l, c), f = buf(l, 2 * c);
+            View y = i == n - 1 ? cat.sub(c, c) : buf(l, c);
+            if (!conv1(qkv, x, q, l, 0)) return false;
+            Step s{}; s.kind = K_ATTN; s.in = q.ptr(); s.ldi = q.ld; s.out = ao.ptr(); s.ldo = ao.ld; s.H = g.h[l]; s.W = g.w[l]; s.Cin = 2 * c; s.Cout = c; s.mode = heads;
             push(s, nullptr);
             for (int hd = 0; hd < heads; ++hd) {            // a head's v slice is contiguous, the heads' are not: one launch per head
                 const View r = ao.sub(64 * hd, 64);
-                if (!dwconv(pe, 64 * hd, q.sub(128 * hd + 64, 64), xo.sub(64 * hd, 64), h, w, 0, &r)) return false;
+                if (!dwconv(pe, 64 * hd, q.sub(128 * hd + 64, 64), xo.sub(64 * hd, 64), l, 0, &r)) return false;
             }
-            if (!conv1(proj, xo, x1, h, w, 0, &x)) return false;
-            if (!conv1(f0, x1, f, h, w, 1) || !conv1(f1, f, y, h, w, 0, &x1)) return false;
+            if (!conv1(proj, xo, x1, l, 0, &x)) return false;
+            if (!conv1(f0, x1, f, l, 1) || !conv1(f1, f, y, l, 0, &x1)) return false;
             x = y;
         }
-        return conv1(cv2, cat, dst, h, w, 1);
+        return conv1(cv2, cat, dst, l, 1);
     }
 
-    bool build_11(const rva_yolo11_desc &e)
+    // ---------------------------------------------------------------------------------------------- graph parts
+    // In every part `block(i, src, dst, l, what)` lays down the family's block i = 0 .. 7 (four of the backbone, two top-down, two
+    // bottom-up) from src into dst at level l, and `what` names the convolutions in the family's module numbering.
+    //
+    // x1 = b1(b0(input)): the stem from the planar input K1 writes (k0 x k0, stride 2) and the 3x3 s2 behind it.
+    bool stem(int k0, const char *what0, const char *what1, View *x1)
+    {
+        const int c1 = g.c[1], c2 = g.c[2];
+        const rva_conv_weights *b0 = take(3, c1, k0, 2, what0), *b1 = take(c1, c2, 3, 2, what1);
+        if (!b0 || !b1) return false;
+        if (!b0->weight) return fail("b0: no stem convolution");
+        Step s{}; s.H = g.H; s.W = g.W;
+        if (p->f32) {                     // rva_stem_conv_f32: the checkpoint's [c1][3][3][3] weights as they are
+            std::vector<float> sb(c1, 0.f);
+            if (b0->bias) memcpy(sb.data(), b0->bias, sizeof(float) * c1);
+            if (!upload(b0->weight, sizeof(float) * c1 * 27, sb, &s.w, &s.b)) return false;
+        } else {
+            // [64][128] fp16 in the checkpoint's own (c, ky, kx) order (6x6), or [64][32] fp16 in the column order k = 2 j + kx
+            // (kx in {0, 1}), k = 18 + j (kx = 2), j = c*3 + ky (3x3); zero-padded
+            if (c1 > 64) return fail("stem wider than 64 channels");
+            const int cols = k0 == 6 ? 128 : 32;
+            std::vector<_Float16> sw(64 * cols, (_Float16)0.f);
+            std::vector<float> sb(64, 0.f);
+            for (int co = 0; co < c1; ++co) {
+                for (int k = 0; k < 3 * k0 * k0; ++k) {
+                    const int j = k / 3, kx = k % 3;           // 3x3: weight[co][c][ky][kx] at k = 3 j + kx
+                    sw[co * cols + (k0 == 6 ? k : kx < 2 ? 2 * j + kx : 18 + j)] = (_Float16)b0->weight[(size_t)co * 3 * k0 * k0 + k];
+                }
+                if (b0->bias) sb[co] = b0->bias[co];
+            }
+            if (!upload(sw.data(), sw.size() * 2, sb, &s.w, &s.b, k0 == 6 ? "weight" : "stem")) return false;
+        }
+        *x1 = buf(2, c2);
+        p->fused_stem = !p->f32 && k0 == 3 && c1 == 32 && c2 == 64 && !(p->d.flags & RVA_PLAN_NO_STEM2);
+        if (p->fused_stem) {              // both convolutions in one launch (rva_stem2_f16)
+            s.kind = K_STEM2; s.out = x1->ptr(); s.ldo = x1->ld;
+            if (!pack(&b1, 1, s, true)) return false;
+            push(s, nullptr);
+            return true;
+        }
+        View x0 = buf(1, c1);
+        s.kind = p->f32 ? K_STEM_F32 : k0 == 6 ? K_STEM6 : K_STEM; s.out = x0.ptr(); s.ldo = x0.ld; s.Cout = c1;
+        push(s, nullptr);
+        return conv1(b1, x0, *x1, 1, 1);
+    }
+    // The backbone behind the stem: block 0 at level 2 into x2, then three times a 3x3 s2 and a block (into p3, p4 and a buffer of
+    // level 5), and SPPF into p5.  what: the seven names b2 .. b8.  From the last 3x3 s2 on the pass is in its stride-32 phase.
+    template <typename Block>
+    bool backbone(Block block, View x, View x2, View p3, View p4, View p5, const char *const what[7])
+    {
+        const View dst[4] = {x2, p3, p4, buf(5, g.c[5])};
+        for (int i = 0; i < 4; ++i) {
+            if (i) {
+                if (i == 3) p->quiet_step = (int)p->steps.size();
+                View t = buf(2 + i, g.c[2 + i]);
+                if (!conv1(take(x.ch, t.ch, 3, 2, what[2 * i - 1]), x, t, 1 + i, 1)) return false;
+                x = t;
+            }
+            if (!block(i, x, dst[i], 2 + i, what[2 * i])) return false;
+            x = dst[i];
+        }
+        return sppf(x, p5);
+    }
+    // FPN top-down path: n4 = block 4(cat[up(p5), p4]) and n3 = block 5(cat[up(n4), p3]), where cat4 = [. | p4] and cat3 = [. | p3]
+    // are the concat buffers of level 4 and 3.  Upsample + concat are folded into the blocks' first 1x1 (conv_in) where every part
+    // is a multiple of 64 channels wide; else an upsampling step fills the front of the concat buffer and the block reads it whole.
+    template <typename Block>
+    bool top_down(Block block, View p5, View cat4, View cat3, View n4, View n3, const char *what4, const char *what3)
+    {
+        const View p4 = cat4.sub(p5.ch, cat4.ch - p5.ch), p3 = cat3.sub(n4.ch, cat3.ch - n4.ch);
+        const bool fuse_up = !p->f32 && p5.ch % 64 == 0 && p4.ch % 64 == 0 && n4.ch % 64 == 0 && p3.ch % 64 == 0 && g.h[4] == 2 * g.h[5] &&
+                             g.w[4] == 2 * g.w[5] && g.h[3] == 2 * g.h[4] && g.w[3] == 2 * g.w[4];
+        if (fuse_up) return block(4, Src(p5, p4), n4, 4, what4) && block(5, Src(n4, p3), n3, 3, what3);
+        up2(p5, cat4.sub(0, p5.ch), 5);
+        if (!block(4, cat4, n4, 4, what4)) return false;
+        up2(n4, cat3.sub(0, n4.ch), 4);
+        return block(5, cat3, n3, 3, what3);
+    }
+    // PAN bottom-up path: a 3x3 s2 of n3 into the front of cat4, m4 = block 6(cat4), a 3x3 s2 of m4 into the front of cat5,
+    // m5 = block 7(cat5).  what: the four names in this order.  feats = {n3, m4, m5}: what the detect head reads.
+    template <typename Block>
+    bool bottom_up(Block block, View n3, View cat4, View cat5, View feats[3], const char *const what[4])
+    {
+        const View cat[2] = {cat4, cat5};
+        feats[0] = n3; feats[1] = buf(4, g.c[4]); feats[2] = buf(5, g.c[5]);
+        for (int i = 0; i < 2; ++i) {
+            const View x = feats[i];
+            fork_at[i] = (int)p->steps.size();             // x is complete here: its detect branch may start
+            if (!conv1(take(x.ch, x.ch, 3, 2, what[2 * i]), x, cat[i].sub(0, x.ch), 3 + i, 1)) return false;
+            if (!block(6 + i, cat[i], feats[i + 1], 4 + i, what[2 * i + 1])) return false;
+        }
+        return true;
+    }
+    // Detect head of YOLOv8 / YOLO11, opening: the widths, the anchors, whether the decode is fused into the last 1x1s, and the box
+    // branches' convolutions (module order: all box branches first, then all class branches).  The class branch runs with its
+    // interior width a multiple of 8 (16 where an fp32 convolution reads it) and ncp logit columns.
+    bool head_open(Head &hd)
+    {
+        const int nc = p->d.nc, ncm = nc < 100 ? nc : 100, cal = p->f32 ? 16 : 8;
+        hd.rm4 = 4 * p->d.reg_max;
+        hd.cb = std::max(g.c[3] / 4, hd.rm4);
+        hd.cc_real = std::max(g.c[3], ncm);
+        hd.cc = (hd.cc_real + cal - 1) / cal * cal; hd.ncp = (nc + 7) / 8 * 8;
+        hd.h3s = Step{}; hd.h3s.kind = K_HEAD3;
+        p->A = g.a0(6);
+        p->fused_head = !p->f32 && hd.cb % 64 == 0 && hd.cc % 64 == 0 && hd.rm4 == 64;
+        for (int l = 0; l < 3; ++l) {
+            hd.box[l][0] = take(g.c[3 + l], hd.cb, 3, 1, "detect.box.0"); hd.box[l][1] = take(hd.cb, hd.cb, 3, 1, "detect.box.1");
+            hd.box[l][2] = take(hd.cb, hd.rm4, 1, 1, "detect.box.2");
+            if (!hd.box[l][0] || !hd.box[l][1] || !hd.box[l][2]) return false;
+        }
+        return true;
+    }
+    // The last 1x1 of a detect branch at level l (mode 1: box, then mode 2: class): convolution + decode in one launch (fused head), or
+    // the convolution into a buffer of its own that a decode step reads -- in an fp32 plan the level's own (rva_yolo_head_f32, on the
+    // level's lane, behind its class branch), else the one step over all levels that head_close() pushes
+    bool head_last(Head &hd, int l, int mode, const rva_conv_weights *c, View src)
+    {
+        if (p->fused_head) return head(c, src, mode, l);
+        View o = buf(l, mode == 1 ? hd.rm4 : hd.ncp);
+        if (!conv1(c, src, o, l, 0)) return false;
+        Step &h = hd.h3s;
+        const int i = l - 3;
+        (mode == 1 ? h.hb : h.hk)[i] = o.ptr(); (mode == 1 ? h.hldb : h.hldc)[i] = o.ld; h.hh[i] = g.h[l]; h.hw[i] = g.w[l]; h.hs[i] = g.stride(l);
+        if (p->f32 && mode == 2) {
+            Step s{}; s.kind = K_HEAD_F32; s.in = h.hb[i]; s.ldi = h.hldb[i]; s.in2 = h.hk[i]; s.ldi2 = h.hldc[i];
+            s.H = g.h[l]; s.W = g.w[l]; s.a0 = g.a0(l); s.stride_px = g.stride(l);
+            push(s, nullptr);
+        }
+        return true;
+    }
+    bool head_close(Head &hd)
+    {
+        lane = 0;
+        if (!p->fused_head && !p->f32) push(hd.h3s, nullptr);
+        return err.empty();
+    }
+
+    // ---------------------------------------------------------------------------------------------- the three graphs
+    bool build()
     {
         const rva_yolov8_desc &d = p->d;
-        const int B = d.batch, H = d.height, W = d.width;
-        const int c1 = d.widths[0], c2 = d.widths[1], c3w = d.widths[2], c4 = d.widths[3], c5 = d.widths[4];
-        const int h2 = H / 4, w2 = W / 4, h3 = H / 8, w3 = W / 8, h4 = H / 16, w4 = W / 16, h5 = H / 32, w5 = W / 32;
-        const rva_conv_weights *b0 = take(3, c1, 3, 2, "0"), *b1 = take(c1, c2, 3, 2, "1");
-        View x1;
-        if (!b0 || !b1 || !stem_f16(b0, b1, &x1)) return false;
-        auto block = [&](int i, int ci, int co, bool quarter, bool shortcut, const View *src, const View *low, const View *skip, View dst, int h, int w,
-                         const char *what) {
-            return c3k2(ci, co, e.repeats[i], e.c3k[i] != 0, quarter, shortcut, src, low, skip, dst, h, w, what);
+        const int c3 = g.c[3], c4 = g.c[4], c5 = g.c[5];
+        auto block = [&](int i, const Src &src, View dst, int l, const char *what) {
+            const bool shortcut = i < 4;
+            return c2f(dst.ch / 2, shortcut ? d.depth_backbone[i] : d.depth_head, src, dst, l, what,
+                       [&](View x, View y) { return pair(x, y, shortcut, l, what); });
         };
-        // concat buffers of the neck: producers write their slice directly.  cat13 = [up(p5) | p4], cat16 = [up(n4) | p3],
-        // cat19 = [17 | n4], cat22 = [20 | p5]
-        View cat13 = buf((long)B * h4 * w4, c5 + c4), cat16 = buf((long)B * h3 * w3, c4 + c4), cat19 = buf((long)B * h4 * w4, c3w + c4),
-             cat22 = buf((long)B * h5 * w5, c4 + c5);
-        if (!cat13.base || !cat16.base || !cat19.base || !cat22.base) return false;
-        View p4 = cat13.sub(c5, c4), p3 = cat16.sub(c4, c4), n4 = cat19.sub(c3w, c4), p5 = cat22.sub(c4, c5);
-        View x2 = buf((long)B * h2 * w2, c3w), t3 = buf((long)B * h3 * w3, c3w), t4 = buf((long)B * h4 * w4, c4);
-        if (!x2.base || !t3.base || !t4.base) return false;
-        if (!block(0, c2, c3w, true, true, &x1, nullptr, nullptr, x2, h2, w2, "2")) return false;
-        if (!conv1(take(c3w, c3w, 3, 2, "3"), x2, t3, h2, w2, 1)) return false;
-        if (!block(1, c3w, c4, true, true, &t3, nullptr, nullptr, p3, h3, w3, "4")) return false;
-        if (!conv1(take(c4, c4, 3, 2, "5"), p3, t4, h3, w3, 1)) return false;
-        if (!block(2, c4, c4, false, true, &t4, nullptr, nullptr, p4, h4, w4, "6")) return false;
-        View t5 = buf((long)B * h5 * w5, c5), t5b = buf((long)B * h5 * w5, c5), t5c = buf((long)B * h5 * w5, c5);
-        p->quiet_step = (int)p->steps.size();
-        if (!t5.base || !t5b.base || !t5c.base || !conv1(take(c4, c5, 3, 2, "7"), p4, t5, h4, w4, 1)) return false;
-        if (!block(3, c5, c5, false, true, &t5, nullptr, nullptr, t5b, h5, w5, "8")) return false;
-        if (!sppf(c5, t5b, t5c, h5, w5)) return false;
-        if (!c2psa(c5, e.psa_blocks, e.psa_heads, t5c, p5, h5, w5)) return false;
-        View n3 = buf((long)B * h3 * w3, c3w);
-        if (!n3.base) return false;
-        if (c5 % 64 == 0 && c4 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4) {
-            // FPN top-down path: upsample + concat folded into the consuming 1x1 convolutions (rva_conv1x1_upcat_f16)
-            if (!block(4, c5 + c4, c4, false, false, nullptr, &p5, &p4, n4, h4, w4, "13")) return false;
-            if (!block(5, c4 + c4, c3w, false, false, nullptr, &n4, &p3, n3, h3, w3, "16")) return false;
-        } else {
-            Step u1{}; u1.kind = K_UP2; u1.in = p5.ptr(); u1.ldi = p5.ld; u1.out = cat13.sub(0, c5).ptr(); u1.ldo = cat13.ld; u1.H = h5; u1.W = w5; u1.Cin = c5;
-            push(u1, nullptr);
-            if (!block(4, c5 + c4, c4, false, false, &cat13, nullptr, nullptr, n4, h4, w4, "13")) return false;
-            Step u2{}; u2.kind = K_UP2; u2.in = n4.ptr(); u2.ldi = n4.ld; u2.out = cat16.sub(0, c4).ptr(); u2.ldo = cat16.ld; u2.H = h4; u2.W = w4; u2.Cin = c4;
-            push(u2, nullptr);
-            if (!block(5, c4 + c4, c3w, false, false, &cat16, nullptr, nullptr, n3, h3, w3, "16")) return false;
-        }
-        if (!conv1(take(c3w, c3w, 3, 2, "17"), n3, cat19.sub(0, c3w), h3, w3, 1)) return false;
-        View m4 = buf((long)B * h4 * w4, c4), m5 = buf((long)B * h5 * w5, c5);
-        if (!m4.base || !m5.base) return false;
-        if (!block(6, c3w + c4, c4, false, false, &cat19, nullptr, nullptr, m4, h4, w4, "19")) return false;
-        if (!conv1(take(c4, c4, 3, 2, "20"), m4, cat22.sub(0, c4), h4, w4, 1)) return false;
-        if (!block(7, c4 + c5, c5, false, false, &cat22, nullptr, nullptr, m5, h5, w5, "22")) return false;
-        // detect head: the box branch is YOLOv8's; the class branch is dw3x3, 1x1, dw3x3, 1x1, 1x1 with its interior width rounded
-        // up to 8 (zero-extended weights: a pad channel is SiLU(0) = 0 through the depthwise steps and meets zero weights)
-        int cb = c3w / 4 > 64 ? c3w / 4 : 64;
-        const int ncm = d.nc < 100 ? d.nc : 100, cc_real = c3w > ncm ? c3w : ncm;
-        const int cc = (cc_real + 7) / 8 * 8, ncp = (d.nc + 7) / 8 * 8;
-        p->A = h3 * w3 + h4 * w4 + h5 * w5;
-        const rva_conv_weights *box[3][3], *cls[3][5];
-        const int chs[3] = {c3w, c4, c5};
+        static const char *const backbone_names[7] = {"b2", "b3", "b4", "b5", "b6", "b7", "b8"}, *const up_names[4] = {"h16", "h18", "h19", "h21"};
+        // concat buffers of the neck: producers write their slice directly
+        View cat12 = buf(4, c5 + c4), cat15 = buf(3, c4 + c3), cat18 = buf(4, c3 + c4), cat21 = buf(5, c4 + c5);      // [up(p5) | p4], [up(n4) | p3], [h16 | n4], [h19 | p5]
+        View p4 = cat12.sub(c5, c4), p3 = cat15.sub(c4, c3), n4 = cat18.sub(c3, c4), p5 = cat21.sub(c4, c5), n3 = buf(3, c3), x1, feats[3];
+        if (!stem(3, "b0", "b1", &x1) || !backbone(block, x1, buf(2, g.c[2]), p3, p4, p5, backbone_names) ||
+            !top_down(block, p5, cat12, cat15, n4, n3, "h12", "h15") || !bottom_up(block, n3, cat18, cat21, feats, up_names)) return false;
+        // detect: per level one sibling launch for the first 3x3 of both branches (Cout = cb + cc), then each branch's 3x3 and last 1x1
+        Head hd;
+        if (!head_open(hd)) return false;
+        const int cb = hd.cb, cc = hd.cc;
+        const rva_conv_weights *cls[3][3];
         for (int l = 0; l < 3; ++l) {
-            box[l][0] = take(chs[l], cb, 3, 1, "detect.box.0"); box[l][1] = take(cb, cb, 3, 1, "detect.box.1"); box[l][2] = take(cb, 64, 1, 1, "detect.box.2");
-            if (!box[l][0] || !box[l][1] || !box[l][2]) return false;
+            cls[l][0] = take(g.c[3 + l], hd.cc_real, 3, 1, "detect.cls.0"); cls[l][1] = take(hd.cc_real, hd.cc_real, 3, 1, "detect.cls.1");
+            cls[l][2] = take(hd.cc_real, d.nc, 1, 1, "detect.cls.2");
+            if (!cls[l][0] || !cls[l][1] || !cls[l][2]) return false;
+            cls[l][0] = padded(cls[l][0], g.c[3 + l], cc); cls[l][1] = padded(cls[l][1], cc, cc); cls[l][2] = padded(cls[l][2], cc, hd.ncp);
         }
+        if (!all_taken()) return false;
         for (int l = 0; l < 3; ++l) {
-            cls[l][0] = take(1, chs[l], 3, 1, "detect.cls.0.0"); cls[l][1] = take(chs[l], cc_real, 1, 1, "detect.cls.0.1");
-            cls[l][2] = take(1, cc_real, 3, 1, "detect.cls.1.0"); cls[l][3] = take(cc_real, cc_real, 1, 1, "detect.cls.1.1");
-            cls[l][4] = take(cc_real, d.nc, 1, 1, "detect.cls.2");
-            for (int i = 0; i < 5; ++i)
-                if (!cls[l][i]) return false;
-            cls[l][1] = padded(cls[l][1], chs[l], cc); cls[l][2] = padded(cls[l][2], 1, cc); cls[l][3] = padded(cls[l][3], cc, cc);
-            cls[l][4] = padded(cls[l][4], cc, ncp);
+            // the three detect branches only depend on their own feature map and write disjoint anchor ranges: the stride-8 and
+            // stride-16 branches may run on side streams beside the rest of the neck (rva_yolov8_plan_run_lanes)
+            lane = ((p->fused_head || p->f32) && l < 2) ? l + 1 : 0;
+            if (lane) p->fork_step[lane] = fork_at[l];
+            View first = buf(3 + l, cb + cc), b2 = buf(3 + l, cb), k2 = buf(3 + l, cc);
+            const rva_conv_weights *sib[2] = {hd.box[l][0], cls[l][0]};
+            if (!conv(sib, 2, feats[l], first, 3 + l, 1)) return false;
+            if (!conv1(hd.box[l][1], first.sub(0, cb), b2, 3 + l, 1) || !head_last(hd, 3 + l, 1, hd.box[l][2], b2)) return false;
+            if (!conv1(cls[l][1], first.sub(cb, cc), k2, 3 + l, 1) || !head_last(hd, 3 + l, 2, cls[l][2], k2)) return false;
         }
-        if (next != d.n_convs) return fail("convolution list longer than the architecture");
-        p->fused_head = cb % 64 == 0 && cc % 64 == 0;
-        const View feats[3] = {n3, m4, m5};
-        const int hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
-        const float strides[3] = {8.f, 16.f, 32.f};
-        Step h3s{}; h3s.kind = K_HEAD3;
-        int a0 = 0;
-        for (int l = 0; l < 3; ++l) {
-            const long m = (long)B * hs[l] * ws[l];
-            View bb1 = buf(m, cb), bb2 = buf(m, cb), d1 = buf(m, chs[l]), k1 = buf(m, cc), d2 = buf(m, cc), k2 = buf(m, cc);
-            if (!bb1.base || !bb2.base || !d1.base || !k1.base || !d2.base || !k2.base) return false;
-            if (!conv1(box[l][0], feats[l], bb1, hs[l], ws[l], 1) || !conv1(box[l][1], bb1, bb2, hs[l], ws[l], 1)) return false;
-            if (!dwconv(cls[l][0], 0, feats[l], d1, hs[l], ws[l], 1) || !conv1(cls[l][1], d1, k1, hs[l], ws[l], 1) ||
-                !dwconv(cls[l][2], 0, k1, d2, hs[l], ws[l], 1) || !conv1(cls[l][3], d2, k2, hs[l], ws[l], 1)) return false;
-            if (p->fused_head) {
-                if (!head(box[l][2], bb2, 1, hs[l], ws[l], a0, strides[l]) || !head(cls[l][4], k2, 2, hs[l], ws[l], a0, strides[l])) return false;
-            } else {
-                View bo = buf(m, 64), ko = buf(m, ncp);
-                if (!bo.base || !ko.base) return false;
-                if (!conv1(box[l][2], bb2, bo, hs[l], ws[l], 0) || !conv1(cls[l][4], k2, ko, hs[l], ws[l], 0)) return false;
-                h3s.hb[l] = bo.ptr(); h3s.hldb[l] = bo.ld; h3s.hk[l] = ko.ptr(); h3s.hldc[l] = ko.ld; h3s.hh[l] = hs[l]; h3s.hw[l] = ws[l]; h3s.hs[l] = strides[l];
-            }
-            a0 += hs[l] * ws[l];
-        }
-        if (!p->fused_head) push(h3s, nullptr);
-        return err.empty();
+        return head_close(hd);
     }
 
     bool build_v5(const float *anchors)
     {
         const rva_yolov8_desc &d = p->d;
-        const int B = d.batch, H = d.height, W = d.width;
-        const int c1 = d.widths[0], c2 = d.widths[1], c3w = d.widths[2], c4 = d.widths[3], c5 = d.widths[4];
-        const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4, h3 = H / 8, w3 = W / 8, h4 = H / 16, w4 = W / 16, h5 = H / 32, w5 = W / 32;
-        const int nh = d.depth_head;
-        if (c1 > 64) return fail("stem wider than 64 channels");
+        const int c3w = g.c[3], c4 = g.c[4], c5 = g.c[5];
         if (c3w % 64 || c4 % 64 || c5 % 64) return fail("YOLOv5 plan: c3, c4 and c5 must be multiples of 64 (the upsample + concat and head kernels)");
-        const rva_conv_weights *b0 = take(3, c1, 6, 2, "b0");
-        if (!b0 || !b0->weight) return fail("b0: no stem convolution");
-        {   // stem (planar input from K1): weights [64][128] fp16 in the checkpoint's own (c, ky, kx) order, zero-padded
-            std::vector<_Float16> sw(64 * 128, (_Float16)0.f);
-            std::vector<float> sb(64, 0.f);
-            for (int co = 0; co < c1; ++co) {
-                for (int k = 0; k < 108; ++k) sw[co * 128 + k] = (_Float16)b0->weight[(size_t)co * 108 + k];
-                if (b0->bias) sb[co] = b0->bias[co];
-            }
-            Step s{}; s.kind = K_STEM6;
-            const void *db = nullptr;
-            if (!upload(sw.data(), sw.size() * 2, &s.w) || !upload(sb.data(), sb.size() * 4, &db)) return false;
-            s.b = (const float *)db;
-            View x0 = buf((long)B * h1 * w1, c1);
-            if (!x0.base) return false;
-            s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
-            push(s, nullptr);
-            View x1 = buf((long)B * h2 * w2, c2), x2 = buf((long)B * h2 * w2, c2);
-            if (!x1.base || !x2.base || !conv1(take(c1, c2, 3, 2, "b1"), x0, x1, h1, w1, 1)) return false;
-            if (!c3(c2, c2, d.depth_backbone[0], true, &x1, nullptr, nullptr, x2, h2, w2, "b2")) return false;
-            View t3 = buf((long)B * h3 * w3, c3w), p3 = buf((long)B * h3 * w3, c3w);
-            if (!t3.base || !p3.base || !conv1(take(c2, c3w, 3, 2, "b3"), x2, t3, h2, w2, 1)) return false;
-            if (!c3(c3w, c3w, d.depth_backbone[1], true, &t3, nullptr, nullptr, p3, h3, w3, "b4")) return false;
-            View t4 = buf((long)B * h4 * w4, c4), p4 = buf((long)B * h4 * w4, c4);
-            if (!t4.base || !p4.base || !conv1(take(c3w, c4, 3, 2, "b5"), p3, t4, h3, w3, 1)) return false;
-            if (!c3(c4, c4, d.depth_backbone[2], true, &t4, nullptr, nullptr, p4, h4, w4, "b6")) return false;
-            View t5 = buf((long)B * h5 * w5, c5), t5b = buf((long)B * h5 * w5, c5), p5 = buf((long)B * h5 * w5, c5);
-            p->quiet_step = (int)p->steps.size();
-            if (!t5.base || !t5b.base || !p5.base || !conv1(take(c4, c5, 3, 2, "b7"), p4, t5, h4, w4, 1)) return false;
-            if (!c3(c5, c5, d.depth_backbone[3], true, &t5, nullptr, nullptr, t5b, h5, w5, "b8")) return false;
-            if (!sppf(c5, t5b, p5, h5, w5)) return false;
-            // neck: the two concat buffers of the bottom-up path; h10 / h14 write their slices directly
-            View cat20 = buf((long)B * h4 * w4, 2 * c3w), cat23 = buf((long)B * h5 * w5, 2 * c4);
-            if (!cat20.base || !cat23.base) return false;
-            View t10 = cat23.sub(c4, c4), t14 = cat20.sub(c3w, c3w);
-            View n4 = buf((long)B * h4 * w4, c4), n3 = buf((long)B * h3 * w3, c3w), m4 = buf((long)B * h4 * w4, c4), m5 = buf((long)B * h5 * w5, c5);
-            if (!n4.base || !n3.base || !m4.base || !m5.base) return false;
-            if (!conv1(take(c5, c4, 1, 1, "h10"), p5, t10, h5, w5, 1)) return false;
-            if (!c3(2 * c4, c4, nh, false, nullptr, &t10, &p4, n4, h4, w4, "h13")) return false;
-            if (!conv1(take(c4, c3w, 1, 1, "h14"), n4, t14, h4, w4, 1)) return false;
-            if (!c3(2 * c3w, c3w, nh, false, nullptr, &t14, &p3, n3, h3, w3, "h17")) return false;
-            if (!conv1(take(c3w, c3w, 3, 2, "h18"), n3, cat20.sub(0, c3w), h3, w3, 1)) return false;
-            if (!c3(2 * c3w, c4, nh, false, &cat20, nullptr, nullptr, m4, h4, w4, "h20")) return false;
-            if (!conv1(take(c4, c4, 3, 2, "h21"), m4, cat23.sub(0, c4), h4, w4, 1)) return false;
-            if (!c3(2 * c4, c5, nh, false, &cat23, nullptr, nullptr, m5, h5, w5, "h23")) return false;
-            // detect: one fused convolution + decode per level, into disjoint anchor ranges of the output
-            const int no = 5 + d.nc, co_real = 3 * no, co = (co_real + 7) / 8 * 8;
-            p->A = 3 * (h3 * w3 + h4 * w4 + h5 * w5);
-            const View feats[3] = {n3, m4, m5};
-            const int chs[3] = {c3w, c4, c5}, hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
-            const float strides[3] = {8.f, 16.f, 32.f};
-            const void *danc = nullptr;
-            if (!upload(anchors, sizeof(float) * 18, &danc)) return false;
-            int a0 = 0;
-            for (int l = 0; l < 3; ++l) {
-                const rva_conv_weights *hc = padded(take(chs[l], co_real, 1, 1, "detect.m"), chs[l], co);
-                if (!hc) return false;
-                Step s{}; s.kind = K_HEAD5;
-                if (!pack(&hc, 1, &s.w, &s.b, &s.Cin, &s.Cout, &s.k, &s.stride)) return false;
-                s.in = feats[l].ptr(); s.ldi = feats[l].ld; s.H = hs[l]; s.W = ws[l]; s.a0 = a0; s.stride_px = strides[l];
-                s.b2 = (const float *)danc + 6 * l;
-                push(s, "head5:%d->%d k1s1 %dx%d", s.Cin, s.Cout, hs[l], ws[l]);
-                a0 += 3 * hs[l] * ws[l];
-            }
-            if (next != d.n_convs) return fail("convolution list longer than the architecture");
+        auto block = [&](int i, const Src &src, View dst, int l, const char *what) {
+            return c3(i < 4 ? d.depth_backbone[i] : d.depth_head, i < 4, src, dst, l, what);
+        };
+        static const char *const backbone_names[7] = {"b2", "b3", "b4", "b5", "b6", "b7", "b8"}, *const up_names[4] = {"h18", "h20", "h21", "h23"};
+        // the two concat buffers of the bottom-up path; h14 / h10 write their slices directly
+        View cat20 = buf(4, 2 * c3w), cat23 = buf(5, 2 * c4), t14 = cat20.sub(c3w, c3w), t10 = cat23.sub(c4, c4);
+        View p3 = buf(3, c3w), p4 = buf(4, c4), p5 = buf(5, c5), n4 = buf(4, c4), n3 = buf(3, c3w), x1, feats[3];
+        if (!stem(6, "b0", "b1", &x1) || !backbone(block, x1, buf(2, g.c[2]), p3, p4, p5, backbone_names)) return false;
+        // top-down: a 1x1 in front of each upsampling, which is always folded into the block behind it
+        if (!conv1(take(c5, c4, 1, 1, "h10"), p5, t10, 5, 1) || !block(4, Src(t10, p4), n4, 4, "h13") ||
+            !conv1(take(c4, c3w, 1, 1, "h14"), n4, t14, 4, 1) || !block(5, Src(t14, p3), n3, 3, "h17")) return false;
+        if (!bottom_up(block, n3, cat20, cat23, feats, up_names)) return false;
+        // detect: one fused convolution + decode per level (three anchors per cell), into disjoint anchor ranges of the output
+        const int co_real = 3 * (5 + d.nc), co = (co_real + 7) / 8 * 8;
+        p->A = 3 * g.a0(6);
+        const void *danc = nullptr;
+        if (!upload(anchors, sizeof(float) * 18, &danc)) return false;
+        for (int l = 3; l <= 5; ++l) {
+            const rva_conv_weights *hc = padded(take(g.c[l], co_real, 1, 1, "detect.m"), g.c[l], co);
+            Step s{}; s.kind = K_HEAD5;
+            if (!hc || !pack(&hc, 1, s)) return false;
+            const View &f = feats[l - 3];
+            s.in = f.ptr(); s.ldi = f.ld; s.H = g.h[l]; s.W = g.w[l]; s.a0 = 3 * g.a0(l); s.stride_px = g.stride(l);
+            s.b2 = (const float *)danc + 6 * (l - 3);
+            push(s, "head5:%d->%d k1s1 %dx%d", s.Cin, s.Cout, s.H, s.W);
         }
-        return err.empty();
+        return all_taken() && err.empty();
     }
 
-    bool build()
+    bool build_11(const rva_yolo11_desc &e)
     {
-        const rva_yolov8_desc &d = p->d;
-        const int B = d.batch, H = d.height, W = d.width;
-        const int c1 = d.widths[0], c2 = d.widths[1], c3 = d.widths[2], c4 = d.widths[3], c5 = d.widths[4];
-        const int h1 = H / 2, w1 = W / 2, h2 = H / 4, w2 = W / 4, h3 = H / 8, w3 = W / 8, h4 = H / 16, w4 = W / 16, h5 = H / 32, w5 = W / 32;
-        const int nh = d.depth_head;
-        // stem (planar input from K1): weights [64][32] fp16, column order k = 2 j + kx (kx in {0, 1}), k = 18 + j (kx = 2), j = c*3 + ky
-        const rva_conv_weights *b0 = take(3, c1, 3, 2, "b0"), *b1 = take(c1, c2, 3, 2, "b1");
-        if (!b0 || !b1) return false;
-        View x1;
-        if (p->f32) {
-            // stem from the planar fp32 input (rva_stem_conv_f32): the checkpoint's [c1][3][3][3] weights as they are
-            Step s{}; s.kind = K_STEM_F32;
-            std::vector<float> sb(c1, 0.f);
-            if (b0->bias) memcpy(sb.data(), b0->bias, sizeof(float) * c1);
-            const void *db = nullptr;
-            if (!b0->weight || !upload(b0->weight, sizeof(float) * c1 * 27, &s.w) || !upload(sb.data(), sizeof(float) * c1, &db)) return false;
-            s.b = (const float *)db;
-            View x0 = buf((long)B * h1 * w1, c1);
-            x1 = buf((long)B * h2 * w2, c2);
-            if (!x0.base || !x1.base) return false;
-            s.out = x0.ptr(); s.ldo = x0.ld; s.H = H; s.W = W; s.Cout = c1;
-            push(s, nullptr);
-            if (!conv1(b1, x0, x1, h1, w1, 1)) return false;
-        } else if (!stem_f16(b0, b1, &x1)) return false;
-        View x2 = buf((long)B * h2 * w2, c2);
-        if (!x2.base || !c2f(c2, c2, d.depth_backbone[0], true, &x1, nullptr, nullptr, x2, h2, w2, "b2")) return false;
+        const int c3w = g.c[3], c4 = g.c[4], c5 = g.c[5];
+        // C3k2: a C2f of inner width c = a quarter (blocks 0, 1) or half of its output whose inner blocks are bottlenecks 3x3 c -> c/2,
+        // 3x3 c/2 -> c, or with c3k a C3k at width c with two bottlenecks, which writes its cv3 into the outer concat slice
+        auto block = [&](int i, const Src &src, View dst, int l, const char *what) {
+            const int c = i < 2 ? dst.ch / 4 : dst.ch / 2;
+            const bool shortcut = i < 4;
+            if (e.repeats[i] < 1 || c % 16) return fail("a C3k2 block needs at least one inner block and an inner width that is a multiple of 16");
+            return c2f(c, e.repeats[i], src, dst, l, what, [&](View x, View y) {
+                return e.c3k[i] ? c3(2, shortcut, x, y, l, what, 3) : bottleneck(x, y, c / 2, shortcut, l, what);
+            });
+        };
+        static const char *const backbone_names[7] = {"2", "3", "4", "5", "6", "7", "8"}, *const up_names[4] = {"17", "19", "20", "22"};
         // concat buffers of the neck: producers write their slice directly
-        View cat15 = buf((long)B * h3 * w3, c4 + c3), cat12 = buf((long)B * h4 * w4, c5 + c4), cat18 = buf((long)B * h4 * w4, c3 + c4),
-             cat21 = buf((long)B * h5 * w5, c4 + c5);
-        if (!cat15.base || !cat12.base || !cat18.base || !cat21.base) return false;
-        View p3 = cat15.sub(c4, c3), p4 = cat12.sub(c5, c4), n4 = cat18.sub(c3, c4), p5 = cat21.sub(c4, c5);
-        View t3 = buf((long)B * h3 * w3, c3);
-        if (!t3.base || !conv1(take(c2, c3, 3, 2, "b3"), x2, t3, h2, w2, 1)) return false;
-        if (!c2f(c3, c3, d.depth_backbone[1], true, &t3, nullptr, nullptr, p3, h3, w3, "b4")) return false;
-        View t4 = buf((long)B * h4 * w4, c4);
-        if (!t4.base || !conv1(take(c3, c4, 3, 2, "b5"), p3, t4, h3, w3, 1)) return false;
-        if (!c2f(c4, c4, d.depth_backbone[2], true, &t4, nullptr, nullptr, p4, h4, w4, "b6")) return false;
-        View t5 = buf((long)B * h5 * w5, c5);
-        p->quiet_step = (int)p->steps.size();
-        if (!t5.base || !conv1(take(c4, c5, 3, 2, "b7"), p4, t5, h4, w4, 1)) return false;
-        View t5b = buf((long)B * h5 * w5, c5);
-        if (!t5b.base || !c2f(c5, c5, d.depth_backbone[3], true, &t5, nullptr, nullptr, t5b, h5, w5, "b8")) return false;
-        if (!sppf(c5, t5b, p5, h5, w5)) return false;
-        const bool fuse_up = !p->f32 && c5 % 64 == 0 && c4 % 64 == 0 && c3 % 64 == 0 && h4 == 2 * h5 && w4 == 2 * w5 && h3 == 2 * h4 && w3 == 2 * w4;
-        View n3 = buf((long)B * h3 * w3, c3);
-        if (!n3.base) return false;
-        if (fuse_up) {    // FPN top-down path: upsample + concat folded into the consuming 1x1 convolutions
-            if (!c2f(c5 + c4, c4, nh, false, nullptr, &p5, &p4, n4, h4, w4, "h12")) return false;
-            if (!c2f(c4 + c3, c3, nh, false, nullptr, &n4, &p3, n3, h3, w3, "h15")) return false;
-        } else {
-            Step u1{}; u1.kind = p->f32 ? K_UP2_F32 : K_UP2; u1.in = p5.ptr(); u1.ldi = p5.ld; u1.out = cat12.sub(0, c5).ptr(); u1.ldo = cat12.ld; u1.H = h5; u1.W = w5; u1.Cin = c5;
-            push(u1, nullptr);
-            if (!c2f(c5 + c4, c4, nh, false, &cat12, nullptr, nullptr, n4, h4, w4, "h12")) return false;
-            Step u2{}; u2.kind = p->f32 ? K_UP2_F32 : K_UP2; u2.in = n4.ptr(); u2.ldi = n4.ld; u2.out = cat15.sub(0, c4).ptr(); u2.ldo = cat15.ld; u2.H = h4; u2.W = w4; u2.Cin = c4;
-            push(u2, nullptr);
-            if (!c2f(c4 + c3, c3, nh, false, &cat15, nullptr, nullptr, n3, h3, w3, "h15")) return false;
-        }
-        const int fork_n3 = (int)p->steps.size();            // n3 is complete here: the stride-8 detect branch may start
-        if (!conv1(take(c3, c3, 3, 2, "h16"), n3, cat18.sub(0, c3), h3, w3, 1)) return false;
-        View m4 = buf((long)B * h4 * w4, c4);
-        if (!m4.base || !c2f(c3 + c4, c4, nh, false, &cat18, nullptr, nullptr, m4, h4, w4, "h18")) return false;
-        const int fork_m4 = (int)p->steps.size();            // m4 is complete: the stride-16 detect branch may start
-        if (!conv1(take(c4, c4, 3, 2, "h19"), m4, cat21.sub(0, c4), h4, w4, 1)) return false;
-        View m5 = buf((long)B * h5 * w5, c5);
-        if (!m5.base || !c2f(c4 + c5, c5, nh, false, &cat21, nullptr, nullptr, m5, h5, w5, "h21")) return false;
-        // detect head
-        const int rm4 = 4 * d.reg_max;
-        int cb = c3 / 4 > rm4 ? c3 / 4 : rm4;
-        if (cb < 16) cb = 16;
-        const int cc_real = c3 > (d.nc < 100 ? d.nc : 100) ? c3 : (d.nc < 100 ? d.nc : 100);
-        // what the class branch runs with: interior width a multiple of 8 (16 where an fp32 convolution reads it), ncp logit columns
-        const int cal = p->f32 ? 16 : 8;
-        const int cc = (cc_real + cal - 1) / cal * cal, ncp = (d.nc + 7) / 8 * 8;
-        p->A = h3 * w3 + h4 * w4 + h5 * w5;
-        // module order: all box branches first, then all class branches
-        const rva_conv_weights *box[3][3], *cls[3][3];
-        const int chs[3] = {c3, c4, c5};
+        View cat13 = buf(4, c5 + c4), cat16 = buf(3, c4 + c4), cat19 = buf(4, c3w + c4), cat22 = buf(5, c4 + c5);      // [up(p5) | p4], [up(n4) | p3], [17 | n4], [20 | p5]
+        View p4 = cat13.sub(c5, c4), p3 = cat16.sub(c4, c4), n4 = cat19.sub(c3w, c4), p5 = cat22.sub(c4, c5), t5 = buf(5, c5), n3 = buf(3, c3w), x1, feats[3];
+        if (!stem(3, "0", "1", &x1) || !backbone(block, x1, buf(2, c3w), p3, p4, t5, backbone_names) || !c2psa(e.psa_blocks, e.psa_heads, t5, p5) ||
+            !top_down(block, p5, cat13, cat16, n4, n3, "13", "16") || !bottom_up(block, n3, cat19, cat22, feats, up_names)) return false;
+        // detect: the box branch is YOLOv8's; the class branch is dw3x3, 1x1, dw3x3, 1x1, 1x1 with its interior width rounded up to 8
+        // (zero-extended weights: a pad channel is SiLU(0) = 0 through the depthwise steps and meets zero weights).  No lanes.
+        Head hd;
+        if (!head_open(hd)) return false;
+        const int cb = hd.cb, cr = hd.cc_real, cc = hd.cc;
+        const rva_conv_weights *cls[3][5];
         for (int l = 0; l < 3; ++l) {
-            box[l][0] = take(chs[l], cb, 3, 1, "detect.box.0"); box[l][1] = take(cb, cb, 3, 1, "detect.box.1"); box[l][2] = take(cb, rm4, 1, 1, "detect.box.2");
-            if (!box[l][0] || !box[l][1] || !box[l][2]) return false;
+            const int ch = g.c[3 + l];
+            cls[l][0] = take(1, ch, 3, 1, "detect.cls.0.0"); cls[l][1] = take(ch, cr, 1, 1, "detect.cls.0.1");
+            cls[l][2] = take(1, cr, 3, 1, "detect.cls.1.0"); cls[l][3] = take(cr, cr, 1, 1, "detect.cls.1.1");
+            cls[l][4] = take(cr, p->d.nc, 1, 1, "detect.cls.2");
+            for (int i = 0; i < 5; ++i)
+                if (!cls[l][i]) return false;
+            cls[l][1] = padded(cls[l][1], ch, cc); cls[l][2] = padded(cls[l][2], 1, cc); cls[l][3] = padded(cls[l][3], cc, cc);
+            cls[l][4] = padded(cls[l][4], cc, hd.ncp);
         }
+        if (!all_taken()) return false;
         for (int l = 0; l < 3; ++l) {
-            cls[l][0] = take(chs[l], cc_real, 3, 1, "detect.cls.0"); cls[l][1] = take(cc_real, cc_real, 3, 1, "detect.cls.1");
-            cls[l][2] = take(cc_real, d.nc, 1, 1, "detect.cls.2");
-            if (!cls[l][0] || !cls[l][1] || !cls[l][2]) return false;
-            cls[l][0] = padded(cls[l][0], chs[l], cc); cls[l][1] = padded(cls[l][1], cc, cc); cls[l][2] = padded(cls[l][2], cc, ncp);
+            const int L = 3 + l;
+            const View &f = feats[l];
+            View bb1 = buf(L, cb), bb2 = buf(L, cb), d1 = buf(L, f.ch), k1 = buf(L, cc), d2 = buf(L, cc), k2 = buf(L, cc);
+            if (!conv1(hd.box[l][0], f, bb1, L, 1) || !conv1(hd.box[l][1], bb1, bb2, L, 1)) return false;
+            if (!dwconv(cls[l][0], 0, f, d1, L, 1) || !conv1(cls[l][1], d1, k1, L, 1) || !dwconv(cls[l][2], 0, k1, d2, L, 1) ||
+                !conv1(cls[l][3], d2, k2, L, 1)) return false;
+            if (!head_last(hd, L, 1, hd.box[l][2], bb2) || !head_last(hd, L, 2, cls[l][4], k2)) return false;
         }
-        if (next != d.n_convs) return fail("convolution list longer than the architecture");
-        p->fused_head = !p->f32 && cb % 64 == 0 && cc % 64 == 0 && rm4 == 64;
-        const View feats[3] = {n3, m4, m5};
-        const int hs[3] = {h3, h4, h5}, ws[3] = {w3, w4, w5};
-        const float strides[3] = {8.f, 16.f, 32.f};
-        Step h3s{}; h3s.kind = K_HEAD3;
-        int a0 = 0;
-        for (int l = 0; l < 3; ++l) {
-            // the three detect branches only depend on their own feature map and write disjoint anchor ranges: the stride-8 and
-            // stride-16 branches may run on side streams beside the rest of the neck (rva_yolov8_plan_run_lanes)
-            lane = ((p->fused_head || p->f32) && l < 2) ? l + 1 : 0;
-            if (lane) p->fork_step[lane] = l == 0 ? fork_n3 : fork_m4;
-            const long m = (long)B * hs[l] * ws[l];
-            View first = buf(m, cb + cc), b2 = buf(m, cb), k2 = buf(m, cc);
-            if (!first.base || !b2.base || !k2.base) return false;
-            const rva_conv_weights *sib[2] = {box[l][0], cls[l][0]};
-            if (!conv(sib, 2, feats[l], first, hs[l], ws[l], 1)) return false;      // one launch, Cout = cb + cc
-            if (p->fused_head) {
-                if (!conv1(box[l][1], first.sub(0, cb), b2, hs[l], ws[l], 1) || !head(box[l][2], b2, 1, hs[l], ws[l], a0, strides[l])) return false;
-                if (!conv1(cls[l][1], first.sub(cb, cc), k2, hs[l], ws[l], 1) || !head(cls[l][2], k2, 2, hs[l], ws[l], a0, strides[l])) return false;
-            } else {
-                View bo = buf(m, rm4), ko = buf(m, ncp);
-                if (!bo.base || !ko.base) return false;
-                if (!conv1(box[l][1], first.sub(0, cb), b2, hs[l], ws[l], 1) || !conv1(box[l][2], b2, bo, hs[l], ws[l], 0)) return false;
-                if (!conv1(cls[l][1], first.sub(cb, cc), k2, hs[l], ws[l], 1) || !conv1(cls[l][2], k2, ko, hs[l], ws[l], 0)) return false;
-                h3s.hb[l] = bo.ptr(); h3s.hldb[l] = bo.ld; h3s.hk[l] = ko.ptr(); h3s.hldc[l] = ko.ld; h3s.hh[l] = hs[l]; h3s.hw[l] = ws[l]; h3s.hs[l] = strides[l];
-                if (p->f32) {             // the level's decode on its own lane (rva_yolo_head_f32): disjoint anchor range of the output
-                    Step hs1{}; hs1.kind = K_HEAD_F32; hs1.in = bo.ptr(); hs1.ldi = bo.ld; hs1.in2 = ko.ptr(); hs1.ldi2 = ko.ld;
-                    hs1.H = hs[l]; hs1.W = ws[l]; hs1.a0 = a0; hs1.stride_px = strides[l];
-                    push(hs1, nullptr);
-                }
-            }
-            a0 += hs[l] * ws[l];
-        }
-        lane = 0;
-        if (!p->fused_head && !p->f32) push(h3s, nullptr);
-        return err.empty();
+        return head_close(hd);
     }
 };
 
@@ -995,6 +910,52 @@ void note_complete_run(rva_yolov8_plan *p, int n, bool win, rva_stream_t stream)
     if (!win && !stream_is_capturing(stream)) p->primed = n;
 }
 
+// The internal descriptor from the fields every public descriptor has (reg_max 16: what the plan runs with)
+template <typename D>
+rva_yolov8_desc internal_desc(const D &e)
+{
+    rva_yolov8_desc d{};
+    d.batch = e.batch; d.height = e.height; d.width = e.width; d.nc = e.nc; d.reg_max = 16; d.n_convs = e.n_convs; d.flags = e.flags;
+    memcpy(d.widths, e.widths, sizeof d.widths);
+    return d;
+}
+
+struct PlanDeleter { void operator()(rva_yolov8_plan *p) const { rva_yolov8_plan_destroy(p); } };
+
+// What the create entry points share.  `d`: the internal descriptor the entry filled; `also`: what its rule adds to the common
+// one; `refuse()`: the architecture's own refusals (RVA_OK: none); `build(builder)`: the graph to lay down.  The plan under
+// construction is held so that every return releases its device allocations and events, as rva_yolov8_plan_destroy does.
+template <typename Refuse, typename Build>
+int create_plan(rva_ctx *ctx, const char *who, const char *also, const rva_yolov8_desc &d, int head_rows, const rva_conv_weights *convs,
+                rva_yolov8_plan **out, Refuse refuse, Build build)
+{
+    *out = nullptr;
+    if (d.batch <= 0 || d.height <= 0 || d.width <= 0 || d.height % 32 || d.width % 32 || d.nc < 1 || d.nc > 1024 || d.reg_max != 16 || d.n_convs <= 0)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: batch > 0, height and width multiples of 32, 1 <= nc <= 1024%s", who, also);
+    for (int i = 0; i < 5; ++i)
+        if (d.widths[i] <= 0 || d.widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "%s: channel widths must be multiples of 8", who);
+    if (const int rc = refuse(); rc != RVA_OK) return rc;
+    RVA_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<rva_yolov8_plan, PlanDeleter> p(new rva_yolov8_plan());
+    p->ctx = ctx; p->d = d; p->B = d.batch; p->H = d.height; p->W = d.width; p->nc = d.nc;
+    p->head_rows = head_rows;
+    p->f32 = (d.flags & RVA_PLAN_F32) != 0;
+    p->box32 = (d.flags & RVA_PLAN_BOX_F32) != 0;
+    Builder b(p.get(), convs);
+    if (!build(b)) return rva_fail(ctx, b.hip_failed ? RVA_ERR_HIP : RVA_ERR_ARG, "%s: %s", who, b.err.c_str());
+    for (int l = 1; l <= 2; ++l)
+        if (p->fork_step[l] >= 0) {
+            RVA_HIP(ctx, hipEventCreateWithFlags(&p->fork_ev[l], hipEventDisableTiming));
+            RVA_HIP(ctx, hipEventCreateWithFlags(&p->join_ev[l], hipEventDisableTiming));
+        }
+    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
+    if (p->box32) p->box_off = ((size_t)p->B * p->head_rows * p->A * 2 + 255) / 256 * 256;
+    p->rows_top = 0; p->rows_bottom = p->H;
+    propagate_rows(p.get());
+    *out = p.release();
+    return RVA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1002,109 +963,39 @@ extern "C" {
 int rva_yolov8_plan_create(rva_ctx *ctx, const rva_yolov8_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out)
 {
     if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
-    *out = nullptr;
-    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
-        desc->nc > 1024 || desc->reg_max != 16 || desc->n_convs <= 0)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024, reg_max 16");
-    for (int i = 0; i < 5; ++i)
-        if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: channel widths must be multiples of 8");
-    RVA_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
-    p->ctx = ctx; p->d = *desc; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
-    p->head_rows = 4 + desc->nc;
-    p->f32 = (desc->flags & RVA_PLAN_F32) != 0;
-    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
-    if (p->f32 && p->box32)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov8_plan_create: RVA_PLAN_BOX_F32 belongs to fp16 plans (the output of an RVA_PLAN_F32 plan is fp32 already)");
-    Builder b{p.get(), convs};
-    const bool ok = b.build();
-    if (!ok) {
-        for (void *a : p->allocs) (void)hipFree(a);
-        return rva_fail(ctx, b.err.find("hip") == 0 || b.err.find("upload") != std::string::npos ? RVA_ERR_HIP : RVA_ERR_ARG,
-                        "rva_yolov8_plan_create: %s", b.err.c_str());
-    }
-    for (int l = 1; l <= 2; ++l)
-        if (p->fork_step[l] >= 0) {
-            RVA_HIP(ctx, hipEventCreateWithFlags(&p->fork_ev[l], hipEventDisableTiming));
-            RVA_HIP(ctx, hipEventCreateWithFlags(&p->join_ev[l], hipEventDisableTiming));
-        }
-    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
-    if (p->box32) p->box_off = ((size_t)p->B * (4 + p->nc) * p->A * 2 + 255) / 256 * 256;
-    p->rows_top = 0; p->rows_bottom = p->H;
-    propagate_rows(p.get());
-    *out = p.release();
-    return RVA_OK;
+    const char *who = "rva_yolov8_plan_create";
+    return create_plan(ctx, who, ", reg_max 16", *desc, 4 + desc->nc, convs, out, [&] {
+        if ((desc->flags & RVA_PLAN_F32) && (desc->flags & RVA_PLAN_BOX_F32))
+            return rva_fail(ctx, RVA_ERR_ARG, "%s: RVA_PLAN_BOX_F32 belongs to fp16 plans (the output of an RVA_PLAN_F32 plan is fp32 already)", who);
+        return (int)RVA_OK;
+    }, [](Builder &b) { return b.build(); });
 }
 
 int rva_yolov5_plan_create(rva_ctx *ctx, const rva_yolov5_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out)
 {
     if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
-    *out = nullptr;
-    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
-        desc->nc > 1024 || desc->n_convs <= 0)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024");
-    if (desc->flags & RVA_PLAN_F32)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: there is no fp32 YOLOv5 plan (RVA_PLAN_F32); build the fp16 plan");
-    for (int i = 0; i < 5; ++i)
-        if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: channel widths must be multiples of 8");
-    for (int i = 0; i < 18; ++i)
-        if (!(desc->anchors[i] > 0.f) || !(desc->anchors[i] < 65504.f)) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolov5_plan_create: anchors must be positive pixel sizes");
-    RVA_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
-    p->ctx = ctx; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
-    p->d.batch = desc->batch; p->d.height = desc->height; p->d.width = desc->width; p->d.nc = desc->nc; p->d.reg_max = 0;
-    for (int i = 0; i < 5; ++i) p->d.widths[i] = desc->widths[i];
-    for (int i = 0; i < 4; ++i) p->d.depth_backbone[i] = desc->depth_backbone[i];
-    p->d.depth_head = desc->depth_head; p->d.n_convs = desc->n_convs; p->d.flags = desc->flags;
-    p->head_rows = 5 + desc->nc;
-    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
-    Builder b{p.get(), convs};
-    if (!b.build_v5(desc->anchors)) {
-        for (void *a : p->allocs) (void)hipFree(a);
-        return rva_fail(ctx, b.err.find("hip") == 0 || b.err.find("upload") != std::string::npos ? RVA_ERR_HIP : RVA_ERR_ARG,
-                        "rva_yolov5_plan_create: %s", b.err.c_str());
-    }
-    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
-    if (p->box32) p->box_off = ((size_t)p->B * p->head_rows * p->A * 2 + 255) / 256 * 256;
-    p->rows_top = 0; p->rows_bottom = p->H;
-    propagate_rows(p.get());
-    *out = p.release();
-    return RVA_OK;
+    const char *who = "rva_yolov5_plan_create";
+    rva_yolov8_desc d = internal_desc(*desc);
+    memcpy(d.depth_backbone, desc->depth_backbone, sizeof d.depth_backbone);
+    d.depth_head = desc->depth_head;
+    return create_plan(ctx, who, "", d, 5 + desc->nc, convs, out, [&] {
+        if (desc->flags & RVA_PLAN_F32) return rva_fail(ctx, RVA_ERR_ARG, "%s: there is no fp32 YOLOv5 plan (RVA_PLAN_F32); build the fp16 plan", who);
+        for (int i = 0; i < 18; ++i)
+            if (!(desc->anchors[i] > 0.f) || !(desc->anchors[i] < 65504.f)) return rva_fail(ctx, RVA_ERR_ARG, "%s: anchors must be positive pixel sizes", who);
+        return (int)RVA_OK;
+    }, [&](Builder &b) { return b.build_v5(desc->anchors); });
 }
 
 int rva_yolo11_plan_create(rva_ctx *ctx, const rva_yolo11_desc *desc, const rva_conv_weights *convs, rva_yolov8_plan **out)
 {
     if (!ctx || !desc || !convs || !out) return RVA_ERR_ARG;
-    *out = nullptr;
-    if (desc->batch <= 0 || desc->height <= 0 || desc->width <= 0 || desc->height % 32 || desc->width % 32 || desc->nc < 1 ||
-        desc->nc > 1024 || desc->n_convs <= 0)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: batch > 0, height and width multiples of 32, 1 <= nc <= 1024");
-    if (desc->flags & RVA_PLAN_F32)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: there is no fp32 YOLO11 plan (RVA_PLAN_F32); build the fp16 plan");
-    for (int i = 0; i < 5; ++i)
-        if (desc->widths[i] <= 0 || desc->widths[i] % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: channel widths must be multiples of 8");
-    if (desc->psa_heads < 1 || desc->psa_heads * 128 != desc->widths[4])
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo11_plan_create: psa_heads * 64 = %d is not half the C2PSA width %d", desc->psa_heads * 64, desc->widths[4]);
-    RVA_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<rva_yolov8_plan> p(new rva_yolov8_plan());
-    p->ctx = ctx; p->B = desc->batch; p->H = desc->height; p->W = desc->width; p->nc = desc->nc;
-    p->d.batch = desc->batch; p->d.height = desc->height; p->d.width = desc->width; p->d.nc = desc->nc; p->d.reg_max = 16;
-    for (int i = 0; i < 5; ++i) p->d.widths[i] = desc->widths[i];
-    p->d.n_convs = desc->n_convs; p->d.flags = desc->flags;
-    p->head_rows = 4 + desc->nc;
-    p->box32 = (desc->flags & RVA_PLAN_BOX_F32) != 0;
-    Builder b{p.get(), convs};
-    if (!b.build_11(*desc)) {
-        for (void *a : p->allocs) (void)hipFree(a);
-        return rva_fail(ctx, b.err.find("hip") == 0 || b.err.find("upload") != std::string::npos ? RVA_ERR_HIP : RVA_ERR_ARG,
-                        "rva_yolo11_plan_create: %s", b.err.c_str());
-    }
-    RVA_HIP(ctx, hipDeviceSynchronize());                  // weights are in place before the first run on any stream
-    if (p->box32) p->box_off = ((size_t)p->B * p->head_rows * p->A * 2 + 255) / 256 * 256;
-    p->rows_top = 0; p->rows_bottom = p->H;
-    propagate_rows(p.get());
-    *out = p.release();
-    return RVA_OK;
+    const char *who = "rva_yolo11_plan_create";
+    return create_plan(ctx, who, "", internal_desc(*desc), 4 + desc->nc, convs, out, [&] {
+        if (desc->flags & RVA_PLAN_F32) return rva_fail(ctx, RVA_ERR_ARG, "%s: there is no fp32 YOLO11 plan (RVA_PLAN_F32); build the fp16 plan", who);
+        if (desc->psa_heads < 1 || desc->psa_heads * 128 != desc->widths[4])
+            return rva_fail(ctx, RVA_ERR_ARG, "%s: psa_heads * 64 = %d is not half the C2PSA width %d", who, desc->psa_heads * 64, desc->widths[4]);
+        return (int)RVA_OK;
+    }, [&](Builder &b) { return b.build_11(*desc); });
 }
 
 void rva_yolov8_plan_destroy(rva_yolov8_plan *p)
