@@ -18,7 +18,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
-SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_conv_f32.hip", "rva_attn.hip", "rva_plan.hip", "rva_clip.hip",
+SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_stem.hip", "rva_yolo_ops.hip", "rva_conv_f32.hip", "rva_attn.hip", "rva_plan.hip", "rva_clip.hip",
            "rva_clip3d.hip", "rva_clip3d_f16.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
@@ -118,12 +118,16 @@ RVA_PLAN_F32 = 8
 RVA_PLAN_BOX_F32 = 16
 
 
+def build_deps() -> list:
+    """Every file librva.so is compiled from: the sources, every header beside them, and the public header."""
+    return [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [ROOT / "include" / "rva.h"]
+
+
 def _stale() -> bool:
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "rva_internal.h", CSRC / "rva_plan_topo.h", CSRC / "rva_mfma_f32.h", CSRC / "rva_mfma_f16.h", ROOT / "include" / "rva.h"]
-    return any(d.exists() and d.stat().st_mtime > t for d in deps)
+    return any(d.exists() and d.stat().st_mtime > t for d in build_deps())
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:

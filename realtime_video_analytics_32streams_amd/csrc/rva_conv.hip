@@ -1,4 +1,7 @@
-// Fused detector primitives (NHWC fp16) for the YOLOv8 network of the hot path.
+// The fp16 convolutions (NHWC) of the detectors' fused plans: the kernel families, the variant table that dispatches to them, and
+// the convolution entry points of rva.h.  The other detector kernels are in files of their own, each beside its entry point: the
+// stems in rva_stem.hip; SPPF / max pool / upsample and the detect head's decode in rva_yolo_ops.hip.  What the three files share
+// (vector types, swz32, silu_f, the LDS-DMA pointer types, store_scores8, the diagnostic stamps) is in rva_conv_dev.h.
 //
 // Why these exist: profiling the PyTorch/MIOpen network (profiles/r01_a_*) shows four kernels per
 // convolution (zero-fill for split-K atomics, implicit GEMM, broadcast bias add, SiLU) plus chunk /
@@ -20,9 +23,8 @@
 //                  ring (counted vmcnt, raw s_barrier)
 //   k_conv_gbig    LDS-DMA gather for 1x1 and strided 3x3 (64- or 32-channel K-steps), optionally with the
 //                  "upsample2x + concat" source folded in (rva_conv1x1_upcat_f16)
-//   k_conv3_patch  resident weights + input patch staged once per output tile, for the small-channel layers
-//   k_stem         3x3 stride-2 conv on the planar fp16 tensor K1 writes (Cin = 3), bias + SiLU, NHWC out
-//   k_sppf_pool3 / k_maxpool5 / k_upsample2 / k_head3 / k_head   SPPF pooling, FPN upsample, DFL + dist2bbox + sigmoid
+//   k_conv3_patch / k_conv3_patch2   resident weights + input patch staged once per output tile, for the small-channel layers
+// and k_c2f_pair32 (rva_c2f_pair32_f16), a C2f block's two 32-channel 3x3 convolutions in one launch on the patch kernels' staging.
 //
 // Shared around the K loops (the families differ in how they stage operands and walk K, nothing else):
 //   stage_tile / store_tile   the epilogue of the eight tile kernels above k_conv3_patch (bias, SiLU, fp16, LDS transpose; row ->
@@ -36,20 +38,9 @@
 // Numerics: fp16 operands, fp32 accumulation and epilogue, one rounding to fp16 per layer output
 // (PyTorch rounds after conv, after bias and after SiLU); the engine is therefore checked against the
 // torch module within an fp16 tolerance, never bit-for-bit.
-#include <hip/hip_fp16.h>
-
-#include <cstdlib>
-
-#include "rva_internal.h"
+#include "rva_conv_dev.h"
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-// NOTE: staging registers use this native vector, not HIP's uint4 struct: assigning a dereferenced
-// `const uint4*` into an array element lowers to a memcpy that SROA does not split, the array then lives in
-// scratch and every prefetch load is followed by vmcnt(0) + scratch_store (serialised loads).
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
     const __half *in; int ldi;
@@ -78,39 +69,6 @@ struct ConvArgs {
     int wy0, wrows;
 };
 
-// Timing-only ablation switches (skip the MFMA phase / the prefetch loads / the epilogue) exist in the private diagnostic
-// build only (tools/row_stamps.py compiles with -DRVA_ROW_STAMPS); the shipped library has neither the fields nor the reads.
-#ifdef RVA_ROW_STAMPS
-#define RVA_DBG_FIELD int dbg;
-#define RVA_DBG(a, bit) ((a).dbg & (bit))
-#else
-#define RVA_DBG_FIELD
-#define RVA_DBG(a, bit) 0
-#endif
-#ifdef RVA_ROW_STAMPS
-// tuning aid (tools/row_stamps.py builds a private library with this macro): per-phase s_memtime stamps of a few blocks
-__device__ unsigned long long g_stamps[8][256];
-__device__ __forceinline__ unsigned long long stamp_now()
-{
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    return t;
-}
-#define STAMP(k) do { if (st_on && st_n < 256) g_stamps[st_slot][st_n++] = stamp_now(); } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
-
-constexpr int LDSROW = 40;  // halfs per staged row, padded layout (stem, resident kernel, K-step-64 rows use BK+8)
-
-// Swizzled layout for 32-channel (64-byte) rows, no padding: the 16-byte chunk c of row r lives at physical chunk
-// (c + 2*(r>>2)) & 3.  ds_read_b128 serves a wave in groups of 16 lanes that mix rows {0-3,12-15} at chunk c with
-// rows {4-11} at chunk c+1 (MI355X_MICROARCH.md, LDS table); with 80-byte padded rows 3 of the 16 lanes of every
-// group collide (PMC: SQ_LDS_BANK_CONFLICT = 50 % of SQ_LDS_IDX_ACTIVE on the 3x3 kernels).  For this mapping the four
-// rows of a group that share (r & 3) get physical chunks {2q, 2q+2, 2q+3, 2q+1} mod 4 -- distinct for any row base --
-// and the staging ds_write_b128 (4 lanes per row, consecutive rows) alternates 16-bank halves: both conflict-free.
-__device__ __forceinline__ int swz32(int row, int chunk) { return row * 32 + (((chunk + 2 * (row >> 2)) & 3) << 3); }
-
 // q / d for 0 <= q < 2^24 and d > 0, with inv = 1.0f / d: a float multiply and a one-step correction (~8 instructions) instead
 // of the ~40-instruction 32-bit division.  The LDS-DMA kernels turn raster positions into image coordinates once per lane
 // before their main loop, and that start-up arithmetic is not free: with the per-fragment tap masks compiled out (and with
@@ -125,9 +83,20 @@ __device__ __forceinline__ int div_s(int q, int d, float inv)
     return t;
 }
 
-// x * sigmoid(x) with v_exp_f32 + v_rcp_f32 (1 ulp): __fdividef / operator/ expand to the ~12-instruction IEEE
-// division sequence here, which dominated the epilogues (64-128 SiLUs per thread per tile)
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+// 9-bit tap validity of the pixel (ox, oy) of a 3x3 stride-1 convolution: bit dy*3+dx is set when tap (dy, dx) lies inside the
+// W x H image.  The kernels zero the B fragments of the other taps instead of staging zeros (LDS-DMA cannot write zeros).
+__device__ __forceinline__ int tap_mask9(int ox, int oy, int W, int H)
+{
+    const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= W - 2 ? 4 : 0);
+    return (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= H - 2 ? hv << 6 : 0);
+}
+// The same for position p of the flat raster of M pixels (HW = H * W, inv_hw = 1 / HW, inv_w = 1 / W); 0 beyond the raster.
+__device__ __forceinline__ int raster_tap_mask9(int p, int M, int HW, int W, int H, float inv_hw, float inv_w)
+{
+    if (p >= M) return 0;
+    const int rem = p - div_s(p, HW, inv_hw) * HW, oy = div_s(rem, W, inv_w), ox = rem - oy * W;
+    return tap_mask9(ox, oy, W, H);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // The epilogue the eight tile kernels share (k_conv_mfma, k_conv3_row, k_conv_res; k_conv3_big / _run / _s2run / _chunk,
@@ -458,12 +427,7 @@ __global__ void __launch_bounds__(256) k_conv3_row(RowArgs a)
     };
     auto step_of = [&](int s, int &dy, int &cc) { dy = s / cpt; cc = s - dy * cpt; };
     int dy, cc;
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = tid == 0 && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 8;
-    const int st_slot = st_on ? blockIdx.x / st_stride : 0;
-    int st_n = 0;
-#endif
+    STAMP_BEGIN();
     if (!PF2) {
         STAMP(0);
         gload_to(ra, rw, 0, 0);
@@ -739,571 +703,6 @@ hipError_t launch_res(ResArgs &a, int batch, int num_cus, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Stem: 3x3 stride-2 pad-1 conv on planar [B,3,H,W] fp16 (what K1 writes), Cout <= 64, NHWC out.
-struct StemArgs {
-    const __half *in; const float *w; const float *bias; __half *out;   // w: [Cout][27] (c, ky, kx)
-    int B, H, W, Ho, Wo, Cout, ldo;
-    RVA_DBG_FIELD
-};
-
-__global__ void __launch_bounds__(256) k_stem(StemArgs a, const __half *__restrict__ gw, const float *__restrict__ gb)
-{
-    // Persistent blocks; a tile = 8 x 32 output pixels of one image.  Per tile: the 17 x 65 x 3 input patch
-    // (prefetched into registers while the previous tile computes) is staged in LDS, each thread writes its
-    // pixel's 27 taps (padded to K = 32) as one im2col row, and the 27-deep dot products run as ONE
-    // v_mfma_f32_16x16x32_f16 step per 16x16 output block (weights = A operand, loaded once per block;
-    // pixels = B operand).  A VALU formulation needs 864 FMAs per pixel and saturated the scalar unit.
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RS = 88;                                                      // halfs per patch row: 80 used (x = 64*tx-8 ...) + 8 pad
-    __half *tile = (__half *)smem;                                              // [3][17][RS]
-    __half *col = (__half *)(smem + 3 * 17 * RS * 2);                           // [256][LDSROW] im2col rows / output stage
-    __half *wl = col + 256 * (a.Cout + 8 > LDSROW ? a.Cout + 8 : LDSROW);       // [64][LDSROW] weights (fp16, K padded)
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tiles_x = (a.Wo + 31) >> 5, tiles_y = (a.Ho + 7) >> 3;
-    const int tiles_img = tiles_x * tiles_y, total = tiles_img * a.B;
-    {   // packed fp16 weights [64][32] (API column order: k = 2j + kx for kx in {0,1}, 18 + j for kx = 2, j = c*3 + ky):
-        // one 16-byte load per thread, once per block, scattered into the kernel's own K order
-        //   k' = 2j + (kx - 1) for kx in {1,2}  (one aligned dword of the patch row),  k' = 18 + j for kx = 0
-        const u4 wv4 = *reinterpret_cast<const u4 *>(gw + tid * 8);
-        const unsigned short *wh = reinterpret_cast<const unsigned short *>(&wv4);
-        unsigned short *wrow_l = reinterpret_cast<unsigned short *>(wl) + (size_t)(tid >> 2) * LDSROW;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int k = (tid & 3) * 8 + e;
-            int kn = k;                                           // k >= 27: zero padding stays in place
-            if (k < 18) { const int j = k >> 1; kn = (k & 1) ? 2 * j : 18 + j; }        // kx = 1 -> 2j ; kx = 0 -> 18 + j
-            else if (k < 27) kn = 2 * (k - 18) + 1;                                      // kx = 2 -> 2j + 1
-            wrow_l[kn] = wh[e];
-        }
-    }
-    const int nblk = (a.Cout + 15) >> 4;                   // 16-channel blocks (<= 4)
-    float bv[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int co = 16 * i + (lane >> 4) * 4 + u;
-            bv[i][u] = co < a.Cout ? gb[co] : 0.f;
-        }
-    // patch of a tile: 3 planes x 17 rows x 80 halfs starting at x = 64*tx - 8 (so that every row is a run of ten aligned
-    // 16-byte chunks; W % 8 == 0).  510 chunks per tile = two 16-byte loads per thread -- the earlier form issued 26
-    // two-byte loads per thread and spent a third of the tile time in the issue of those loads (tools/stem_stamps.py).
-    u4 pv[2];
-    auto prefetch = [&](int t) {
-        const int bb = t / tiles_img, r2 = t - bb * tiles_img, tyy = r2 / tiles_x, txx = r2 - tyy * tiles_x;
-        const int x00 = txx * 64 - 8, iy0 = tyy * 16 - 1;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int q = tid + 256 * k;
-            const int row = q / 10, cx = q - row * 10;
-            const int c = row / 17, r = row - c * 17;
-            const int iy = iy0 + r, x0 = x00 + cx * 8;
-            pv[k] = u4{0u, 0u, 0u, 0u};
-            if (!RVA_DBG(a, 1) && q < 510 && (unsigned)iy < (unsigned)a.H && (unsigned)x0 < (unsigned)a.W)
-                pv[k] = *reinterpret_cast<const u4 *>(a.in + ((size_t)(bb * 3 + c) * a.H + iy) * a.W + x0);
-        }
-    };
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = tid == 0 && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 8;
-    const int st_slot = st_on ? blockIdx.x / st_stride : 0;
-    int st_n = 0;
-#endif
-    int t = blockIdx.x;
-    if (t < total) prefetch(t);
-    for (; t < total; t += gridDim.x) {
-        STAMP(0);
-        const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / tiles_x, tx = r2 - ty * tiles_x;
-        const int ox0 = tx * 32, oy0 = ty * 8;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int q = tid + 256 * k;
-            const int row = q / 10, cx = q - row * 10;
-            if (q < 510) *reinterpret_cast<u4 *>(tile + row * RS + cx * 8) = pv[k];
-        }
-        __syncthreads();
-        STAMP(1);
-        if (t + (int)gridDim.x < total) prefetch(t + gridDim.x);   // next tile's patch flies under this tile's work
-        STAMP(2);
-        {   // im2col row of this thread's pixel.  K order (the weights were scattered into it above):
-            //   k' = 2*j + (kx - 1) for kx in {1,2}  (j = c*3 + ky): halfs 2*lx+8, 2*lx+9 of the patch row = one aligned dword,
-            //   k' = 18 + j for kx = 0 (half 2*lx+7), k' = 27..31 zero.
-            const int lx = tid & 31, ly = tid >> 5;
-            uint32_t d[16];
-            unsigned short sgl[9];
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                const __half *p = tile + ((j / 3) * 17 + ly * 2 + (j % 3)) * RS + lx * 2 + 8;
-                d[j] = *reinterpret_cast<const uint32_t *>(p);                 // kx = 1, 2
-                sgl[j] = *reinterpret_cast<const unsigned short *>(p - 1);     // kx = 0
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) d[9 + j] = (uint32_t)sgl[2 * j] | ((uint32_t)sgl[2 * j + 1] << 16);
-            d[13] = sgl[8];
-            d[14] = 0; d[15] = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<u4 *>(col + (size_t)tid * LDSROW + q * 8) = u4{d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-        }
-        __syncthreads();
-        STAMP(3);
-        f4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-        h8 bf[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const h8 *>(col + (size_t)(wv * 64 + 16 * j + (lane & 15)) * LDSROW + (lane >> 4) * 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < nblk) {
-                const h8 af = *reinterpret_cast<const h8 *>(wl + (size_t)(16 * i + (lane & 15)) * LDSROW + (lane >> 4) * 8);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[i][j], 0, 0, 0);
-            }
-        }
-        STAMP(4);
-        __syncthreads();                                    // im2col rows are dead: reuse them as the output stage
-        const int srow = a.Cout + 8;
-        __half *stage = col;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < nblk) {
-                const int co = 16 * i + (lane >> 4) * 4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int px = wv * 64 + 16 * j + (lane & 15);
-                    __half2 lo = __floats2half2_rn(silu_f(acc[i][j][0] + bv[i][0]), silu_f(acc[i][j][1] + bv[i][1]));
-                    __half2 hi = __floats2half2_rn(silu_f(acc[i][j][2] + bv[i][2]), silu_f(acc[i][j][3] + bv[i][3]));
-                    uint2 pk;
-                    pk.x = *reinterpret_cast<uint32_t *>(&lo);
-                    pk.y = *reinterpret_cast<uint32_t *>(&hi);
-                    if (co < a.Cout) *reinterpret_cast<uint2 *>(stage + (size_t)px * srow + co) = pk;
-                }
-            }
-        }
-        __syncthreads();
-        STAMP(5);
-        const int cpr = a.Cout >> 3;
-        for (int q = tid; q < 256 * cpr; q += 256) {
-            const int px = q / cpr, pc = q - px * cpr;
-            const int ox = ox0 + (px & 31), oy = oy0 + (px >> 5);
-            if (ox < a.Wo && oy < a.Ho && !RVA_DBG(a, 4))
-                *reinterpret_cast<uint4 *>(a.out + ((size_t)(b * a.Ho + oy) * a.Wo + ox) * a.ldo + pc * 8) =
-                    *reinterpret_cast<const uint4 *>(stage + (size_t)px * srow + pc * 8);
-        }
-        STAMP(6);
-        // the next iteration's first barrier (after the tile fill) also orders these stage reads before the
-        // next im2col writes; the tile buffer itself is not touched by the output copy
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// YOLOv5 stem: 6x6 stride-2 pad-2 conv on planar [B,3,H,W] fp16, Cout <= 64, NHWC out.  Structure of k_stem: persistent
-// blocks, a tile = 8 x 32 output pixels of one image (of the row window [y0, y1)), the 20 x 68 x 3 input patch of the next tile
-// prefetched into registers (three 16-byte loads per thread) under the current tile's MFMAs, weights [64][128] resident in LDS,
-// output staged and stored as whole NHWC rows.  Unlike k_stem there is no im2col pass: with K in the natural order
-// k = (c*6 + ky)*6 + kx the six taps of a patch row are three aligned dwords (input x of output pixel lx is 2 lx - 2 + kx and
-// the patch starts at x = 64 tx - 8, so half 2 lx + 6 + kx), and the eight halfs a lane owns of a 16x16x32 B fragment are four
-// such dwords, read straight from the patch (the 16 lanes of a fragment row read 16 consecutive dwords).  K = 108 padded to
-// 128 = four MFMA steps per 16x16 block.  Zero padding is decided per 16-byte chunk in the whole image (W % 8 == 0).
-struct Stem6Args {
-    const __half *in; const float *bias; __half *out;
-    int B, H, W, Ho, Wo, Cout, ldo, y0, y1;
-};
-
-__global__ void __launch_bounds__(256) k_stem6(Stem6Args a, const __half *__restrict__ gw)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int RS = 88, PR = 20, WROW = 136;                                 // halfs per patch row (80 used), patch rows, halfs per weight row
-    __half *tile = (__half *)smem;                                              // [3][PR][RS]
-    __half *wl = tile + 3 * PR * RS;                                            // [64][WROW]
-    __half *stage = wl + 64 * WROW;                                             // [256][Cout + 8]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tiles_x = (a.Wo + 31) >> 5, tiles_y = (a.y1 - a.y0 + 7) >> 3;
-    const int tiles_img = tiles_x * tiles_y, total = tiles_img * a.B;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                               // [64][128] halfs = 1024 16-byte chunks
-        const int q = tid + 256 * k;
-        *reinterpret_cast<u4 *>(wl + (q >> 4) * WROW + (q & 15) * 8) = *reinterpret_cast<const u4 *>(gw + q * 8);
-    }
-    const int nblk = (a.Cout + 15) >> 4;
-    float bv[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int co = 16 * i + (lane >> 4) * 4 + u;
-            bv[i][u] = co < a.Cout ? a.bias[co] : 0.f;
-        }
-    // the lane's four dwords of K-step s: dword index (s*4 + g)*4 + e of the 54 (= 18 patch rows x 3) that hold taps, g = lane >> 4
-    int koff[4][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int idx = (s * 4 + (lane >> 4)) * 4 + e;
-            const int jr = idx / 3, d = idx - jr * 3;                           // jr = c*6 + ky
-            koff[s][e] = idx < 54 ? ((jr / 6) * PR + (jr % 6)) * RS + 6 + 2 * d : -1;
-        }
-    u4 pv[3];
-    auto prefetch = [&](int t) {
-        const int bb = t / tiles_img, r2 = t - bb * tiles_img, tyy = r2 / tiles_x, txx = r2 - tyy * tiles_x;
-        const int x00 = txx * 64 - 8, iy0 = (a.y0 + tyy * 8) * 2 - 2;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int q = tid + 256 * k;
-            const int row = q / 10, cx = q - row * 10;
-            const int c = row / PR, r = row - c * PR;
-            const int iy = iy0 + r, x0 = x00 + cx * 8;
-            pv[k] = u4{0u, 0u, 0u, 0u};
-            if (q < 3 * PR * 10 && (unsigned)iy < (unsigned)a.H && (unsigned)x0 < (unsigned)a.W)
-                pv[k] = *reinterpret_cast<const u4 *>(a.in + ((size_t)(bb * 3 + c) * a.H + iy) * a.W + x0);
-        }
-    };
-    int t = blockIdx.x;
-    if (t < total) prefetch(t);
-    for (; t < total; t += gridDim.x) {
-        const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / tiles_x, tx = r2 - ty * tiles_x;
-        const int ox0 = tx * 32, oy0 = a.y0 + ty * 8;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int q = tid + 256 * k;
-            const int row = q / 10, cx = q - row * 10;
-            if (q < 3 * PR * 10) *reinterpret_cast<u4 *>(tile + row * RS + cx * 8) = pv[k];
-        }
-        __syncthreads();                                    // (also: the weights are in place; the previous tile's stage has been read)
-        if (t + (int)gridDim.x < total) prefetch(t + gridDim.x);
-        f4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-        int pb[4];                                          // the lane's pixel of fragment j: px = wv*64 + 16 j + (lane & 15)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int px = wv * 64 + 16 * j + (lane & 15);
-            pb[j] = (px >> 5) * 2 * RS + (px & 31) * 2;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            h8 bf[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                u4 d;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = koff[s][e] >= 0 ? *reinterpret_cast<const uint32_t *>(tile + pb[j] + koff[s][e]) : 0u;
-                bf[j] = __builtin_bit_cast(h8, d);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i < nblk) {
-                    const h8 af = *reinterpret_cast<const h8 *>(wl + (size_t)(16 * i + (lane & 15)) * WROW + s * 32 + (lane >> 4) * 8);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[i][j], 0, 0, 0);
-                }
-            }
-        }
-        const int srow = a.Cout + 8;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < nblk) {
-                const int co = 16 * i + (lane >> 4) * 4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int px = wv * 64 + 16 * j + (lane & 15);
-                    __half2 lo = __floats2half2_rn(silu_f(acc[i][j][0] + bv[i][0]), silu_f(acc[i][j][1] + bv[i][1]));
-                    __half2 hi = __floats2half2_rn(silu_f(acc[i][j][2] + bv[i][2]), silu_f(acc[i][j][3] + bv[i][3]));
-                    uint2 pk;
-                    pk.x = *reinterpret_cast<uint32_t *>(&lo);
-                    pk.y = *reinterpret_cast<uint32_t *>(&hi);
-                    if (co < a.Cout) *reinterpret_cast<uint2 *>(stage + (size_t)px * srow + co) = pk;
-                }
-            }
-        }
-        __syncthreads();                                    // stage complete; every wave is done reading the patch
-        const int cpr = a.Cout >> 3;
-        for (int q = tid; q < 256 * cpr; q += 256) {
-            const int px = q / cpr, pc = q - px * cpr;
-            const int ox = ox0 + (px & 31), oy = oy0 + (px >> 5);
-            if (ox < a.Wo && oy < a.y1)
-                *reinterpret_cast<uint4 *>(a.out + ((size_t)(b * a.Ho + oy) * a.Wo + ox) * a.ldo + pc * 8) =
-                    *reinterpret_cast<const uint4 *>(stage + (size_t)px * srow + pc * 8);
-        }
-        // the next iteration's barrier (after the patch fill) orders these stage reads before the next stage writes
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The three chained 5x5 max pools of SPPF in one launch.  pool5(pool5(x)) = pool9(x) and pool5^3(x) = pool13(x)
-// (stride 1, -inf padding: the windows just grow), so all three outputs are separable running maxima of the same tile:
-// a block holds one image x 8 channels in LDS, does the row pass for window radii 2 / 4 / 6, then the column pass,
-// and writes y1, y2, y3 into their channel slices.  Replaces three dependent launches that each re-read 25 taps from L2.
-__global__ void __launch_bounds__(256) k_sppf_pool3(const __half *in, int ldi, __half *o1, __half *o2, __half *o3, int ldo,
-                                                    int H, int W, int C)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int HW = H * W, cg = C >> 3;
-    h8 *x = (h8 *)smem;                  // [HW]
-    h8 *r5 = x + HW, *r9 = r5 + HW, *r13 = r9 + HW;
-    const int b = blockIdx.x / cg, g = blockIdx.x - b * cg;
-    const size_t base = (size_t)b * HW;
-    for (int p = threadIdx.x; p < HW; p += 256) x[p] = *reinterpret_cast<const h8 *>(in + (base + p) * ldi + g * 8);
-    __syncthreads();
-    for (int p = threadIdx.x; p < HW; p += 256) {
-        const int y = p / W, xx = p - y * W;
-        h8 m = x[p];
-#pragma unroll
-        for (int d = 1; d <= 6; ++d) {
-            if (xx - d >= 0) m = __builtin_elementwise_max(m, x[p - d]);
-            if (xx + d < W) m = __builtin_elementwise_max(m, x[p + d]);
-            if (d == 2) r5[p] = m;
-            if (d == 4) r9[p] = m;
-        }
-        r13[p] = m;
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < HW; p += 256) {
-        const int y = p / W;
-        h8 m5 = r5[p], m9 = r9[p], m13 = r13[p];
-#pragma unroll
-        for (int d = 1; d <= 6; ++d) {
-            if (y - d >= 0) {
-                if (d <= 2) m5 = __builtin_elementwise_max(m5, r5[p - d * W]);
-                if (d <= 4) m9 = __builtin_elementwise_max(m9, r9[p - d * W]);
-                m13 = __builtin_elementwise_max(m13, r13[p - d * W]);
-            }
-            if (y + d < H) {
-                if (d <= 2) m5 = __builtin_elementwise_max(m5, r5[p + d * W]);
-                if (d <= 4) m9 = __builtin_elementwise_max(m9, r9[p + d * W]);
-                m13 = __builtin_elementwise_max(m13, r13[p + d * W]);
-            }
-        }
-        const size_t o = (base + p) * ldo + g * 8;
-        *reinterpret_cast<h8 *>(o1 + o) = m5;
-        *reinterpret_cast<h8 *>(o2 + o) = m9;
-        *reinterpret_cast<h8 *>(o3 + o) = m13;
-    }
-}
-
-// The same with G groups of 8 channels per block (round 4): consecutive lanes take the G 16-byte pieces of one pixel and then the
-// next pixel, so a wave touches whole 64-byte (G = 4) runs of the NHWC rows instead of one 16-byte piece per 512-byte row, for the
-// loads and for the three stores alike.  1024 threads; the 13-wide row maxima replace the input tile in LDS (they are held in
-// registers across a barrier), so a block needs 3 x HW x G x 16 bytes.  Used when the launch still fills the chip that way.
-template <int G>
-__global__ void __launch_bounds__(1024) k_sppf_pool3g(const __half *in, int ldi, __half *o1, __half *o2, __half *o3, int ldo,
-                                                      int H, int W, int C)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int MAXIT = 4;             // items per thread: HW * G <= 4096
-    const int HW = H * W, n = HW * G, cgb = C / (8 * G);
-    h8 *x = (h8 *)smem;                  // [HW][G]; holds the 13-wide row maxima after the row pass
-    h8 *r5 = x + n, *r9 = r5 + n;
-    const int b = blockIdx.x / cgb, gb = blockIdx.x - b * cgb;
-    const size_t base = (size_t)b * HW;
-    const int c0 = gb * 8 * G;
-    for (int q = threadIdx.x; q < n; q += 1024) x[q] = *reinterpret_cast<const h8 *>(in + (base + q / G) * ldi + c0 + (q % G) * 8);
-    __syncthreads();
-    h8 m13[MAXIT];
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-        const int q = threadIdx.x + it * 1024;
-        if (q < n) {
-            const int p = q / G, xx = p % W;
-            h8 m = x[q];
-#pragma unroll
-            for (int d = 1; d <= 6; ++d) {
-                if (xx - d >= 0) m = __builtin_elementwise_max(m, x[q - d * G]);
-                if (xx + d < W) m = __builtin_elementwise_max(m, x[q + d * G]);
-                if (d == 2) r5[q] = m;
-                if (d == 4) r9[q] = m;
-            }
-            m13[it] = m;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-        const int q = threadIdx.x + it * 1024;
-        if (q < n) x[q] = m13[it];
-    }
-    __syncthreads();
-    const int WG = W * G;
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-        const int q = threadIdx.x + it * 1024;
-        if (q < n) {
-            const int p = q / G, y = p / W;
-            h8 m5 = r5[q], m9 = r9[q], m = x[q];
-#pragma unroll
-            for (int d = 1; d <= 6; ++d) {
-                if (y - d >= 0) {
-                    if (d <= 2) m5 = __builtin_elementwise_max(m5, r5[q - d * WG]);
-                    if (d <= 4) m9 = __builtin_elementwise_max(m9, r9[q - d * WG]);
-                    m = __builtin_elementwise_max(m, x[q - d * WG]);
-                }
-                if (y + d < H) {
-                    if (d <= 2) m5 = __builtin_elementwise_max(m5, r5[q + d * WG]);
-                    if (d <= 4) m9 = __builtin_elementwise_max(m9, r9[q + d * WG]);
-                    m = __builtin_elementwise_max(m, x[q + d * WG]);
-                }
-            }
-            const size_t o = (base + p) * ldo + c0 + (q % G) * 8;
-            *reinterpret_cast<h8 *>(o1 + o) = m5;
-            *reinterpret_cast<h8 *>(o2 + o) = m9;
-            *reinterpret_cast<h8 *>(o3 + o) = m;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// 5x5 stride-1 pad-2 max pool over a channel slice (C % 8 == 0): thread = (pixel, 8 channels)
-__global__ void __launch_bounds__(256) k_maxpool5(const __half *in, int ldi, __half *out, int ldo, int B, int H, int W, int C)
-{
-    const int cg = C >> 3;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)B * H * W * cg) return;
-    const int g = (int)(idx % cg);
-    const long pix = idx / cg;
-    const int x = (int)(pix % W), y = (int)((pix / W) % H), b = (int)(pix / ((long)W * H));
-    h8 mx;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) mx[t] = (_Float16)-65504.f;
-    for (int dy = -2; dy <= 2; ++dy) {
-        const int yy = y + dy;
-        if ((unsigned)yy >= (unsigned)H) continue;
-        for (int dx = -2; dx <= 2; ++dx) {
-            const int xx = x + dx;
-            if ((unsigned)xx >= (unsigned)W) continue;
-            const h8 v = *reinterpret_cast<const h8 *>(in + ((size_t)(b * H + yy) * W + xx) * ldi + g * 8);
-            mx = __builtin_elementwise_max(mx, v);
-        }
-    }
-    *reinterpret_cast<h8 *>(out + (size_t)pix * ldo + g * 8) = mx;
-}
-
-// nearest 2x upsample: out pixel (y, x) <- in pixel (y/2, x/2); thread = (out pixel, 8 channels)
-__global__ void __launch_bounds__(256) k_upsample2(const __half *in, int ldi, __half *out, int ldo, int B, int H, int W, int C)
-{
-    const int cg = C >> 3, Ho = H * 2, Wo = W * 2;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)B * Ho * Wo * cg) return;
-    const int g = (int)(idx % cg);
-    const long pix = idx / cg;
-    const int x = (int)(pix % Wo), y = (int)((pix / Wo) % Ho), b = (int)(pix / ((long)Wo * Ho));
-    const uint4 v = *reinterpret_cast<const uint4 *>(in + ((size_t)(b * H + (y >> 1)) * W + (x >> 1)) * ldi + g * 8);
-    *reinterpret_cast<uint4 *>(out + (size_t)pix * ldo + g * 8) = v;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Detect head: box logits [B, hw, 4*16] + class logits [B, hw, nc] of one level ->
-// out[B, 4+nc, A] at anchor offset a0 (xywh * stride, sigmoid scores).  Thread = anchor.
-struct HeadArgs {
-    const __half *box; int ldb; const __half *cls; int ldc; __half *out;
-    int B, h, w, nc, A, a0; float stride;
-};
-
-struct Head3Args { HeadArgs lv[3]; int blocks[3]; };     // blocks[l] = 256-anchor blocks of level l
-
-template <bool BOX32 = false>
-__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, float *box32 = nullptr);
-
-// Sigmoid of eight class logits of one anchor into eight consecutive class rows (row stride A halves) starting at `o`.  GUARD: only
-// the first `left` of the eight rows exist (the last group of a class count that is no multiple of 8; the other logits are padding).
-template <bool GUARD>
-__device__ __forceinline__ void store_scores8(__half *o, size_t A, const uint4 q, int left)
-{
-    const __half2 *hq = reinterpret_cast<const __half2 *>(&q);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const float2 f = __half22float2(hq[t]);
-        if (!GUARD || 2 * t < left) o[(size_t)(2 * t) * A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.x)));
-        if (!GUARD || 2 * t + 1 < left) o[(size_t)(2 * t + 1) * A] = __float2half_rn(__builtin_amdgcn_rcpf(1.0f + __expf(-f.y)));
-    }
-}
-
-__global__ void __launch_bounds__(256) k_head(HeadArgs a)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < a.h * a.w) head_anchor(a, i, blockIdx.y);
-}
-
-// the three pyramid levels in one launch: the two small levels no longer run as separate, under-filled kernels
-__global__ void __launch_bounds__(256) k_head3(Head3Args a)
-{
-    int blk = blockIdx.x, l = 0;
-    if (blk >= a.blocks[0]) { blk -= a.blocks[0]; l = 1; if (blk >= a.blocks[1]) { blk -= a.blocks[1]; l = 2; } }
-    const HeadArgs &h = a.lv[l];
-    const int i = blk * 256 + threadIdx.x;
-    if (i < h.h * h.w) head_anchor(h, i, blockIdx.y);
-}
-
-// the same launches with the fp32 side tensor box32[B, 4, A] of the box rows (rva_yolo_head_box32_f16 / rva_yolo_head3_box32_f16)
-__global__ void __launch_bounds__(256) k_head_box32(HeadArgs a, float *box32)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < a.h * a.w) head_anchor<true>(a, i, blockIdx.y, box32);
-}
-
-__global__ void __launch_bounds__(256) k_head3_box32(Head3Args a, float *box32)
-{
-    int blk = blockIdx.x, l = 0;
-    if (blk >= a.blocks[0]) { blk -= a.blocks[0]; l = 1; if (blk >= a.blocks[1]) { blk -= a.blocks[1]; l = 2; } }
-    const HeadArgs &h = a.lv[l];
-    const int i = blk * 256 + threadIdx.x;
-    if (i < h.h * h.w) head_anchor<true>(h, i, blockIdx.y, box32);
-}
-
-template <bool BOX32>
-__device__ __forceinline__ void head_anchor(const HeadArgs &a, int i, int b, float *box32)
-{
-    const int hw = a.h * a.w;
-    const size_t pix = (size_t)b * hw + i;
-    const __half *bp = a.box + pix * a.ldb;
-    float d[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        float v[16], mx = -1e30f;
-        const uint4 q0 = *reinterpret_cast<const uint4 *>(bp + s * 16), q1 = *reinterpret_cast<const uint4 *>(bp + s * 16 + 8);
-        const __half2 *h0 = reinterpret_cast<const __half2 *>(&q0), *h1 = reinterpret_cast<const __half2 *>(&q1);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            float2 f = __half22float2(h0[t]); v[2 * t] = f.x; v[2 * t + 1] = f.y;
-            f = __half22float2(h1[t]); v[8 + 2 * t] = f.x; v[9 + 2 * t] = f.y;
-        }
-#pragma unroll
-        for (int t = 0; t < 16; ++t) mx = fmaxf(mx, v[t]);
-        float se = 0.f, sw = 0.f;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) { const float e = __expf(v[t] - mx); se += e; sw += e * (float)t; }
-        d[s] = sw / se;                                  // DFL expectation
-    }
-    const float ax = (float)(i % a.w) + 0.5f, ay = (float)(i / a.w) + 0.5f;
-    const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
-    __half *o = a.out + (size_t)b * (4 + a.nc) * a.A + a.a0 + i;
-    o[0] = __float2half_rn((x1 + x2) * 0.5f * a.stride);
-    o[(size_t)a.A] = __float2half_rn((y1 + y2) * 0.5f * a.stride);
-    o[(size_t)2 * a.A] = __float2half_rn((x2 - x1) * a.stride);
-    o[(size_t)3 * a.A] = __float2half_rn((y2 - y1) * a.stride);
-    if constexpr (BOX32) {    // the four values the roundings above took (the same fp32 operations: one value each), anchor axis
-        float *o32 = box32 + (size_t)b * 4 * a.A + a.a0 + i;      // contiguous like the fp16 rows
-        o32[0] = (x1 + x2) * 0.5f * a.stride;
-        o32[(size_t)a.A] = (y1 + y2) * 0.5f * a.stride;
-        o32[(size_t)2 * a.A] = (x2 - x1) * a.stride;
-        o32[(size_t)3 * a.A] = (y2 - y1) * a.stride;
-    }
-    // class logits eight at a time from a row of ldc >= roundup(nc, 8) halves; only the class rows < nc exist in `out` (a ragged
-    // nc: the row's pad columns are loaded and dropped, whatever they hold)
-    const __half *cp = a.cls + pix * a.ldc;
-    for (int c = 0; c < a.nc; c += 8) {                  // (uniform branch: whole groups of eight take the unguarded stores)
-        const uint4 q = *reinterpret_cast<const uint4 *>(cp + c);
-        if (c + 8 <= a.nc) store_scores8<false>(o + (size_t)(4 + c) * a.A, (size_t)a.A, q, 8);
-        else store_scores8<true>(o + (size_t)(4 + c) * a.A, (size_t)a.A, q, a.nc - c);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // 3x3 stride-1 convolution, large-tile LDS-DMA variant ("big").
 //
 // Why: s_memtime stamps of k_conv3_row (tools/row_stamps.py) show that ~45 % of every K-step is spent ISSUING the
@@ -1327,11 +726,6 @@ struct BigArgs {
     const __half *res; int ldr;
     int H, W, Cin, Cout, CoutPad, act, n_tiles, M, m_tiles;
 };
-
-typedef __attribute__((address_space(3))) void *lds_vptr;
-typedef const __attribute__((address_space(1))) void *glb_vptr;
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // One 1 KiB LDS-DMA piece: 64 lanes x 16 bytes from  sbase + voff  (wave-uniform 64-bit base in an SGPR pair, per-lane
 // 32-bit byte offset in ONE VGPR) to LDS address m0v + 16 * lane.  Written as asm so that the address really takes the
@@ -1431,6 +825,9 @@ __device__ __forceinline__ unsigned ldsdma_woff(const A &a, int n0, int rw, int 
 //                 32-bit per-lane BYTE offset
 //   smem_attr     dynamic-LDS limit to set for the kernel (>= smem, the bytes of this launch)
 // Family-specific limits (W <= 160, apieces, even H and W, the PADO raster, LDS budget) stay with the family, before the call.
+// Their dynamic LDS: the operand ring, reused as the output stage [BM][BN + 8] of stage_tile.
+constexpr size_t ldsdma_smem(size_t ring, int BM, int BN) { return ring > (size_t)BM * (BN + 8) * 2 ? ring : (size_t)BM * (BN + 8) * 2; }
+
 template <class A>
 hipError_t launch_ldsdma(void (*kernel)(A), A &a, int BM, int BN, long raster, size_t act_px, int ld, size_t w_halfs, size_t smem_attr,
                          size_t smem, hipStream_t s)
@@ -1529,18 +926,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
         BIG_ISSUE_ADVANCE();                                                                                  \
     } while (0)
 
-
     f4 acc[FN][FM];
     float4 bvs[FN];
     ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
 
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = tid == 0 && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 8;
-    const int st_slot = st_on ? blockIdx.x / st_stride : 0;
-    int st_n = 0;
-#endif
+    STAMP_BEGIN();
     STAMP(0);
 #pragma unroll
     for (int t = 0; t < NSLOT - 1; ++t)
@@ -1551,16 +942,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
     {
         const float inv_hw = 1.0f / (float)HW, inv_w = 1.0f / (float)a.W;
 #pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            const int p = P0 + wm * TM + 16 * j + (lane & 15);
-            int m = 0;
-            if (p < a.M) {
-                const int rem = p - div_s(p, HW, inv_hw) * HW, oy = div_s(rem, a.W, inv_w), ox = rem - oy * a.W;
-                const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= a.W - 2 ? 4 : 0);
-                m = (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= a.H - 2 ? hv << 6 : 0);
-            }
-            vm[j] = m;
-        }
+        for (int j = 0; j < FM; ++j) vm[j] = raster_tap_mask9(P0 + wm * TM + 16 * j + (lane & 15), a.M, HW, a.W, a.H, inv_hw, inv_w);
     }
     STAMP(1);
     for (int s = 0; s < nsteps; ++s) {
@@ -1646,9 +1028,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NSLOT 
 template <int BM, int BN, int WGM, int WGN, int NSLOT>
 hipError_t launch_big(BigArgs &a, hipStream_t s)
 {
-    constexpr size_t ring = (size_t)NSLOT * ((BM + 2 + 15) / 16 + 3 * BN / 16) * 1024;
-    constexpr size_t st = (size_t)BM * (BN + 8) * 2;
-    constexpr size_t smem = ring > st ? ring : st;
+    constexpr size_t smem = ldsdma_smem((size_t)NSLOT * ((BM + 2 + 15) / 16 + 3 * BN / 16) * 1024, BM, BN);
     static_assert(smem <= 160 * 1024, "LDS budget");
     if (a.Cin % 32 || a.CoutPad % 4) return hipErrorInvalidValue;
     return launch_ldsdma(k_conv3_big<BM, BN, WGM, WGN, NSLOT>, a, BM, BN, a.M, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, smem, smem, s);
@@ -1673,6 +1053,29 @@ struct RunArgs {
     const __half *res; int ldr;
     int H, W, Cin, Cout, CoutPad, act, n_tiles, M, m_tiles, apieces, map_off;
 };
+
+// One tap of a K-step of the three RunArgs kernels (k_conv3_run, k_conv3_s2run, k_conv3_chunk; #undef'ed below them): tap T's
+// fragments are read into register set S (the lane's swizzled bases abase[T] / wlane + instruction immediates) while the MFMAs
+// of the tap before run on the other set; fragments whose bit BIT of the tap mask vm[j] is clear are zeroed where they are
+// consumed.  Macros, not closures: a closure over the mutable register sets sends them to scratch memory.
+#define RUN_LOAD(S, T)                                                                                           \
+    do {                                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                           \
+            bfx[S][j] = *reinterpret_cast<const h8 *>(ab + abase[T] + j * (16 * 32));                            \
+        _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                           \
+            afx[S][i] = *reinterpret_cast<const h8 *>(wb + wlane + ((T) * BN + i * 16) * 32);                    \
+    } while (0)
+#define RUN_ZERO(S, BIT)                                                                                         \
+    do {                                                                                                         \
+        _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                           \
+            if (!((vm[j] >> (BIT)) & 1)) bfx[S][j] = hz;                                                         \
+    } while (0)
+#define RUN_MFMA(S)                                                                                              \
+    do {                                                                                                         \
+        _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                           \
+            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afx[S][i], bfx[S][j], acc[i][j], 0, 0, 0);    \
+    } while (0)
 
 // NOSEL: timing-only experiment (private build, -DRVA_EXPERIMENTS: profiles/r04_experiments_not_kept.txt) -- the padding selects
 // compiled out, i.e. what a zero-halo activation layout could save at most; border pixels are then wrong.
@@ -1751,12 +1154,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
     ldsdma_acc_bias(acc, bvs, a, n0 + wn * TN, lane);
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
 
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = tid == 0 && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 8;
-    const int st_slot = st_on ? blockIdx.x / st_stride : 0;
-    int st_n = 0;
-#endif
+    STAMP_BEGIN();
     STAMP(0);
     // prologue: the whole run of chunk 0 and the weights of step 0
 #pragma unroll
@@ -1774,16 +1172,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
     {
         const float inv_hw = 1.0f / (float)HW, inv_w = 1.0f / (float)a.W;
 #pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            const int p = P0 + wm * TM + 16 * j + (lane & 15);
-            int m = 0;
-            if (!PADO && p < a.M) {
-                const int rem = p - div_s(p, HW, inv_hw) * HW, oy = div_s(rem, a.W, inv_w), ox = rem - oy * a.W;
-                const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= a.W - 2 ? 4 : 0);
-                m = (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= a.H - 2 ? hv << 6 : 0);
-            }
-            vm[j] = m;
-        }
+        for (int j = 0; j < FM; ++j) vm[j] = PADO ? 0 : raster_tap_mask9(P0 + wm * TM + 16 * j + (lane & 15), a.M, HW, a.W, a.H, inv_hw, inv_w);
     }
 
     int cc = 0, dy = 0;
@@ -1833,31 +1222,17 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
         // the fragments of the next horizontal tap are read while the MFMAs of this one run (two register sets); the padding
         // taps are zeroed where a fragment is consumed, a select right behind the load would wait for it at once
         h8 bfx[2][FM], afx[2][FN];
-#define RUN_LOAD(S, DX)                                                                                          \
-        do {                                                                                                     \
-            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
-                bfx[S][j] = *reinterpret_cast<const h8 *>(ab + abase[DX] + j * (16 * 32));                       \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                afx[S][i] = *reinterpret_cast<const h8 *>(wb + wlane + ((DX) * BN + i * 16) * 32);               \
-        } while (0)
-#define RUN_MFMA(S, DX)                                                                                          \
-        do {                                                                                                     \
-            if (!NOSEL && !PADO)                                                                                 \
-            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
-                if (!((vm[j] >> (vsh + (DX))) & 1)) bfx[S][j] = hz;                                              \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                   \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afx[S][i], bfx[S][j], acc[i][j], 0, 0, 0); \
-        } while (0)
+        constexpr bool SEL = !NOSEL && !PADO;
         RUN_LOAD(0, 0);
         RUN_LOAD(1, 1);
-        RUN_MFMA(0, 0);
+        if (SEL) RUN_ZERO(0, vsh);
+        RUN_MFMA(0);
         if (!early) RUN_ISSUE();
         RUN_LOAD(0, 2);
-        RUN_MFMA(1, 1);
-        RUN_MFMA(0, 2);
-#undef RUN_LOAD
-#undef RUN_MFMA
+        if (SEL) RUN_ZERO(1, vsh + 1);
+        RUN_MFMA(1);
+        if (SEL) RUN_ZERO(0, vsh + 2);
+        RUN_MFMA(0);
 #undef RUN_ISSUE
         cc = ncc; dy = ndy;
         STAMP(5);
@@ -1882,9 +1257,7 @@ hipError_t launch_run(RunArgs &a, hipStream_t s)
     const int wp = PADO ? a.W + 1 : a.W;
     a.apieces = rva_ceil_div(BM + 2 * wp + 2, 16);
     if (a.apieces > 8 * 5) return hipErrorInvalidValue;   // MAXA pieces per wave
-    const size_t ring = (size_t)(2 * a.apieces + 2 * (3 * BN / 16)) * 1024;
-    const size_t st = (size_t)BM * (BN + 8) * 2;
-    size_t smem = ring > st ? ring : st;
+    size_t smem = ldsdma_smem((size_t)(2 * a.apieces + 2 * (3 * BN / 16)) * 1024, BM, BN);
     long mp = a.M;
     if (PADO) {
         const int batch = a.M / (a.H * a.W);
@@ -2006,28 +1379,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM <= 
         const __half *ab = act0 + (size_t)dy * AP * 512;
         const __half *wb = wt0 + (size_t)(s & 1) * WPIECES * 512;
         h8 bfx[2][FM], afx[2][FN];
-#define S2_LOAD(S, DX)                                                                                           \
-        do {                                                                                                     \
-            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
-                bfx[S][j] = *reinterpret_cast<const h8 *>(ab + abase[DX] + j * (16 * 32));                       \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                afx[S][i] = *reinterpret_cast<const h8 *>(wb + wlane + ((DX) * BN + i * 16) * 32);               \
-        } while (0)
-#define S2_MFMA(S)                                                                                               \
-        do {                                                                                                     \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                   \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afx[S][i], bfx[S][j], acc[i][j], 0, 0, 0); \
-        } while (0)
-        S2_LOAD(0, 0);
-        S2_LOAD(1, 1);
-        S2_MFMA(0);
+        RUN_LOAD(0, 0);                                   // (no padding selects: the padded raster's pad positions hold zeros)
+        RUN_LOAD(1, 1);
+        RUN_MFMA(0);
         if (!early && s + 1 < nsteps) issue(s + 1, ncc, ndy);
-        S2_LOAD(0, 2);
-        S2_MFMA(1);
-        S2_MFMA(0);
-#undef S2_LOAD
-#undef S2_MFMA
+        RUN_LOAD(0, 2);
+        RUN_MFMA(1);
+        RUN_MFMA(0);
         cc = ncc; dy = ndy;
     }
     __syncthreads();     // all waves done with the buffers: reuse them as the output staging tile
@@ -2047,9 +1405,7 @@ hipError_t launch_s2run(RunArgs &a, hipStream_t s)
     if (Ho <= 0 || Wo <= 0 || a.M % (Ho * Wo)) return hipErrorInvalidValue;
     const long batch = a.M / (Ho * Wo);
     const long mp = batch * Ho * (Wo + 1);                // positions of the padded output raster
-    const size_t ring = (size_t)(3 * AP + 2 * (3 * BN / 16)) * 1024;
-    const size_t st = (size_t)BM * (BN + 8) * 2;
-    size_t smem = ring > st ? ring : st;
+    size_t smem = ldsdma_smem((size_t)(3 * AP + 2 * (3 * BN / 16)) * 1024, BM, BN);
     a.map_off = (int)smem;
     smem += (size_t)BM * 4;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
@@ -2130,16 +1486,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
     {
         const float inv_hw = 1.0f / (float)HW, inv_w = 1.0f / (float)a.W;
 #pragma unroll
-        for (int j = 0; j < FM; ++j) {
-            const int p = P0 + wm * TM + 16 * j + (lane & 15);
-            int m = 0;
-            if (p < a.M) {
-                const int rem = p - div_s(p, HW, inv_hw) * HW, oy = div_s(rem, a.W, inv_w), ox = rem - oy * a.W;
-                const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= a.W - 2 ? 4 : 0);
-                m = (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= a.H - 2 ? hv << 6 : 0);
-            }
-            vm[j] = m;
-        }
+        for (int j = 0; j < FM; ++j) vm[j] = raster_tap_mask9(P0 + wm * TM + 16 * j + (lane & 15), a.M, HW, a.W, a.H, inv_hw, inv_w);
     }
     // per-lane fragment bases, fixed for the whole kernel: the run row of the lane's first pixel for each of the nine taps
     // (swizzled; 16 rows further the rotation repeats, so the other fragments are immediates) and its first weight row
@@ -2159,35 +1506,18 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) k
         const __half *ab = act0 + (size_t)(cc & 1) * apieces * 512;
         const __half *wb = wt0 + (size_t)(cc & 1) * WPIECES * 512;
         h8 bfx[2][FM], afx[2][FN];
-#define CHUNK_LOAD(S, T)                                                                                         \
-        do {                                                                                                     \
-            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
-                bfx[S][j] = *reinterpret_cast<const h8 *>(ab + abase[T] + j * (16 * 32));                        \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                afx[S][i] = *reinterpret_cast<const h8 *>(wb + wlane + ((T) * BN + i * 16) * 32);                \
-        } while (0)
-#define CHUNK_MFMA(S, T)                                                                                         \
-        do {                                                                                                     \
-            _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                       \
-                if (!((vm[j] >> (T)) & 1)) bfx[S][j] = hz;                                                       \
-            _Pragma("unroll") for (int i = 0; i < FN; ++i)                                                       \
-                _Pragma("unroll") for (int j = 0; j < FM; ++j)                                                   \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afx[S][i], bfx[S][j], acc[i][j], 0, 0, 0); \
-        } while (0)
-        CHUNK_LOAD(0, 0);
-        CHUNK_LOAD(1, 1);
-        CHUNK_MFMA(0, 0);
+        RUN_LOAD(0, 0);
+        RUN_LOAD(1, 1);
+        RUN_ZERO(0, 0); RUN_MFMA(0);
         if (!early && cc + 1 < cpt) CHUNK_ISSUE(cc + 1);
-        CHUNK_LOAD(0, 2); CHUNK_MFMA(1, 1);
-        CHUNK_LOAD(1, 3); CHUNK_MFMA(0, 2);
-        CHUNK_LOAD(0, 4); CHUNK_MFMA(1, 3);
-        CHUNK_LOAD(1, 5); CHUNK_MFMA(0, 4);
-        CHUNK_LOAD(0, 6); CHUNK_MFMA(1, 5);
-        CHUNK_LOAD(1, 7); CHUNK_MFMA(0, 6);
-        CHUNK_LOAD(0, 8); CHUNK_MFMA(1, 7);
-        CHUNK_MFMA(0, 8);
-#undef CHUNK_LOAD
-#undef CHUNK_MFMA
+        RUN_LOAD(0, 2); RUN_ZERO(1, 1); RUN_MFMA(1);
+        RUN_LOAD(1, 3); RUN_ZERO(0, 2); RUN_MFMA(0);
+        RUN_LOAD(0, 4); RUN_ZERO(1, 3); RUN_MFMA(1);
+        RUN_LOAD(1, 5); RUN_ZERO(0, 4); RUN_MFMA(0);
+        RUN_LOAD(0, 6); RUN_ZERO(1, 5); RUN_MFMA(1);
+        RUN_LOAD(1, 7); RUN_ZERO(0, 6); RUN_MFMA(0);
+        RUN_LOAD(0, 8); RUN_ZERO(1, 7); RUN_MFMA(1);
+        RUN_ZERO(0, 8); RUN_MFMA(0);
     }
 #undef CHUNK_ISSUE
     __syncthreads();     // all waves done with the buffers: reuse them as the output staging tile
@@ -2204,12 +1534,14 @@ hipError_t launch_chunk(RunArgs &a, hipStream_t s)
     if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160) return hipErrorInvalidValue;
     a.apieces = rva_ceil_div(BM + 2 * a.W + 2, 16);
     if (a.apieces > 8 * 5) return hipErrorInvalidValue;   // MAXA pieces per wave
-    const size_t ring = (size_t)(2 * a.apieces + 2 * (9 * BN / 16)) * 1024;
-    const size_t st = (size_t)BM * (BN + 8) * 2;
-    const size_t smem = ring > st ? ring : st;
+    const size_t smem = ldsdma_smem((size_t)(2 * a.apieces + 2 * (9 * BN / 16)) * 1024, BM, BN);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     return launch_ldsdma(k_conv3_chunk<BM, BN, WGM, WGN>, a, BM, BN, a.M, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
 }
+
+#undef RUN_LOAD
+#undef RUN_ZERO
+#undef RUN_MFMA
 
 // ---------------------------------------------------------------------------------------------------
 // Large-tile LDS-DMA kernel for the gathered cases: 1x1 convolutions and 3x3 stride-2 (or stride-1) convolutions.
@@ -2331,7 +1663,6 @@ __global__ void __launch_bounds__(512)
         is_wbase = (const char *)a.w + (size_t)(is_tap * a.Cin + is_cc * BK) * 2;                                   \
         is_lds = ring0 + (unsigned)is_slot * (unsigned)(SLOTH * 2);                                                 \
     } while (0)
-
 
     f4 acc[FN][FM];
     float4 bvs[FN];
@@ -2508,9 +1839,7 @@ __global__ void __launch_bounds__(512)
 template <int BM, int BN, int WGM, int WGN, int NSLOT, int KS, int BK, bool UP = false, bool HEAD = false, int SUB = 1>
 hipError_t launch_gbig1(ConvArgs &a, hipStream_t s)
 {
-    constexpr size_t ring = (size_t)NSLOT * SUB * (BM + BN) * BK * 2;
-    constexpr size_t st = (size_t)BM * (BN + 8) * 2;
-    constexpr size_t smem = ring > st ? ring : st;
+    constexpr size_t smem = ldsdma_smem((size_t)NSLOT * SUB * (BM + BN) * BK * 2, BM, BN);
     static_assert(smem <= 160 * 1024, "LDS budget");
     // activation offsets range over the whole images the window's pixels lie in (UP: of the full-res source)
     return launch_ldsdma(k_conv_gbig<BM, BN, WGM, WGN, NSLOT, KS, BK, UP, HEAD, SUB>, a, BM, BN, a.M, (size_t)a.H * a.W * (size_t)(a.M / (a.wrows * a.Wo) + 1),
@@ -2624,12 +1953,7 @@ __global__ void __launch_bounds__(NWV * 64) k_conv3_patch(S2Args a)
     };
 
     const h8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = tid == 0 && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 8;
-    const int st_slot = st_on ? blockIdx.x / st_stride : 0;
-    int st_n = 0;
-#endif
+    STAMP_BEGIN();
     int pb = 0;
     if (NBUF == 2 && bid < a.total) issue_patch(bid, 0);
     for (int t = bid; t < a.total; t += nblk) {
@@ -2931,6 +2255,28 @@ __global__ void __launch_bounds__(256) k_c2f_pair32(PairArgs a)
     }
 }
 
+}  // namespace
+
+extern "C" int rva_c2f_pair32_f16(rva_ctx *ctx, const void *in, int ldi, const void *w1, const float *b1, const void *w2, const float *b2, void *out,
+                                  int ldo, int batch, int H, int W, rva_stream_t stream_)
+{
+    if (!ctx || !in || !w1 || !b1 || !w2 || !b2 || !out || batch <= 0 || H <= 0 || W <= 0 || ldi % 8 || ldo % 8 || ldi < 32 || ldo < 32)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: bad argument");
+    if ((((size_t)in) | ((size_t)out) | ((size_t)w1) | ((size_t)w2)) & 15) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: 16-byte aligned tensors");
+    if ((size_t)batch * H * W >= (1ull << 31)) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: tensor too large");
+    PairArgs a{(const __half *)in, ldi, (const __half *)w1, b1, (const __half *)w2, b2, (__half *)out, ldo, batch, H, W,
+               rva_ceil_div(W, PR_TW), rva_ceil_div(H, PR_TH), 0};
+    a.total = a.tiles_x * a.tiles_y * batch;
+    RVA_HIP(ctx, rva_func_smem((const void *)k_c2f_pair32, PR_SMEM));
+    int grid = 2 * rva_num_cus(ctx);
+    if (grid > a.total) grid = a.total;
+    k_c2f_pair32<<<grid, 256, PR_SMEM, (hipStream_t)stream_>>>(a);
+    RVA_HIP(ctx, hipGetLastError());
+    return RVA_OK;
+}
+
+namespace {
+
 // ---------------------------------------------------------------------------------------------------
 // Patch kernel, two wave sets half a tile period apart (3x3 stride 1, Cin = 64, Cout <= 64; weights resident in LDS).
 //
@@ -3028,12 +2374,7 @@ __global__ void __launch_bounds__(2 * SW * 64) __attribute__((amdgpu_waves_per_e
     const int nblk_tiles = (int)blockIdx.x < a.total ? (a.total - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
     const int nmine = (nblk_tiles - set + 1) / 2;          // tiles of this set
     const int niter = (nblk_tiles + 1) / 2;                // iterations both sets run (set 0 has the larger share)
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 4;
-    const bool st_on = (tid == 0 || tid == SW * 64) && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 4;
-    const int st_slot = st_on ? (blockIdx.x / st_stride) * 2 + (tid >= SW * 64 ? 1 : 0) : 0;
-    int st_n = 0;
-#endif
+    STAMP_BEGIN_ON(tid == 0 || tid == SW * 64, 4, 4, (blockIdx.x / st_stride) * 2 + (tid >= SW * 64 ? 1 : 0));      // one thread of each wave set
     if (nmine > 0) issue_patch(blockIdx.x + set * gridDim.x);
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();                          // weights and both first patches are in LDS
@@ -3049,12 +2390,7 @@ __global__ void __launch_bounds__(2 * SW * 64) __attribute__((amdgpu_waves_per_e
 #pragma unroll
             for (int j = 0; j < FMW; ++j) {
                 const int oy = a.y0 + ty * TH + ws * RPW + (j >> 1), ox = tx * TW + 16 * (j & 1) + n;
-                int m = 0;
-                if (oy < a.y1 && ox < a.Wo) {
-                    const int hv = (ox >= 1 ? 1 : 0) | 2 | (ox <= a.W - 2 ? 4 : 0);
-                    m = (oy >= 1 ? hv : 0) | (hv << 3) | (oy <= a.H - 2 ? hv << 6 : 0);
-                }
-                vm[j] = m;
+                vm[j] = oy < a.y1 && ox < a.Wo ? tap_mask9(ox, oy, a.W, a.H) : 0;
             }
             // taps that some lane of this wave has to zero (wave-uniform): most tiles need none, the selects are skipped
             int vall = 0x1ff;
@@ -3187,259 +2523,6 @@ hipError_t launch_patch2(S2Args &g, int num_cus, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Stem + first downsampling convolution in ONE launch, for the YOLOv8s widths (3 -> 32 -> 64, both 3x3 stride 2, SiLU).
-//
-// As two launches the pair moves 78 MB in, 210 MB out (stem), 210 MB in again and 105 MB out: 600 MB per 32-frame batch,
-// 160 us of an HBM-bound 1.9 ms tick.  Fused, the 32-channel half-resolution tensor never leaves the CU.  Persistent
-// blocks (one per CU, sixteen waves) walk 4 x 32 output tiles as a two-stage pipeline of wave groups, two waves of each
-// group per SIMD, ONE workgroup barrier per tile:
-//   waves 0-7 (stage S, vector-ALU bound: 585 x 32 SiLUs per tile)   tile k+1
-//      the 3 x 19 x 136 planar input patch (prefetched into registers one tile ahead) sits in LDS; the 9 x 65 stem pixels
-//      under the tile are computed by MFMA straight from it -- no im2col buffer: the K order is  k' = 4 * (c*3 + ky) + s
-//      with s = 0 a zero-weight slot and s = 1..3 = kx 0..2, so a pixel's four slots of a (c, ky) row are two aligned
-//      dwords of the patch row and a lane's eight K values are two such rows (K = 36 padded to 64: a second MFMA whose only
-//      live row is (c, ky) = (2, 2)); bias + SiLU, stem pixels outside the image written as zeros (they are the second
-//      convolution's padding), into the column-parity patch layout of k_conv3_patch<2, 32, 64>;
-//   waves 8-15 (stage C, MFMA bound: 36 MFMAs per wave)             tile k
-//      the second convolution on the patch the other group finished one tile ago, exactly as k_conv3_patch does it
-//      (weights resident, tap-major), then bias + SiLU -> a wave-private stage -> 16-byte row stores.
-// Patch and input buffers are double-buffered between the groups.
-struct Stem2Args {
-    const __half *in; const __half *w1; const float *b1; const __half *w2; const float *b2; __half *out; int ldo;
-    int B, H, W, H1, W1, Ho, Wo, tiles_x, tiles_y, total;
-    int y0, y1;               // output row window (see S2Args)
-};
-
-constexpr int S2_TH = 4, S2_TW = 32;
-constexpr int S2_PROWS = (2 * S2_TH + 1) * 2 * (S2_TW + 1);                  // 9 x 65 stem pixels as two column-parity planes
-constexpr int S2_IR = 4 * S2_TH + 3, S2_IC = 136;                            // input patch: rows per plane, halfs per row
-constexpr int S2_SROW = 64 + 8;
-constexpr size_t S2_SMEM = (size_t)36 * 1024 + 2 * (size_t)(S2_PROWS + 1) * 64 + 2 * (size_t)3 * S2_IR * S2_IC * 2 + (size_t)S2_TH * S2_TW * S2_SROW * 2;
-static_assert(S2_SMEM <= 160 * 1024, "LDS budget");
-
-__global__ void __launch_bounds__(1024) k_stem2(Stem2Args a)
-{
-    constexpr int TH = S2_TH, TW = S2_TW, CW = TW + 1, PROWS = S2_PROWS, WPIECES = 9 * 64 / 16;
-    constexpr int IR = S2_IR, IC = S2_IC;
-    constexpr int NCH = 3 * IR * (IC / 8), NPV = (NCH + 511) / 512;           // 16-byte chunks of the input patch, per thread of group S
-    constexpr int SPX = (2 * TH + 1) * (2 * TW + 1), NFR = (SPX + 15) / 16;   // stem pixels / fragments of a patch
-    constexpr int SROW = S2_SROW, FN = 4;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __half *wl = (__half *)smem;                           // [9 taps][64][32]   second convolution, swizzled rows
-    __half *patch0 = wl + WPIECES * 512;                   // [2][PROWS + 1][32] stem output (+ a dump row for lanes without a pixel)
-    __half *inp0 = patch0 + 2 * (PROWS + 1) * 32;                // [2][3][IR][IC]     planar input patch
-    __half *stage0 = inp0 + 2 * 3 * IR * IC;               // [TH*TW][SROW]      output stage, rows private to a wave
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = lane & 15, q = lane >> 4;
-    const int tiles_img = a.tiles_x * a.tiles_y;
-    const int nk = ((int)a.total - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;      // tiles of this block
-
-    // second convolution's weights: once per block, by LDS-DMA (row = tap * 64 + co)
-    {
-        const int lrow = lane >> 2, lp = lane & 3;
-#pragma unroll
-        for (int k = 0; k < (WPIECES + 15) / 16; ++k) {
-            const int idx = wv + 16 * k;
-            if (idx < WPIECES) {
-                const int row = idx * 16 + lrow;
-                const int tap = row >> 6, co = row & 63;
-                const __half *src = a.w2 + (size_t)(co * 9 + tap) * 32 + ((lp - 2 * (row >> 2)) & 3) * 8;
-                __builtin_amdgcn_global_load_lds((glb_vptr)src, (lds_vptr)(wl + idx * 512), 16, 0, 0);
-            }
-        }
-    }
-#ifdef RVA_ROW_STAMPS
-    const int st_stride = gridDim.x / 8;
-    const bool st_on = (tid == 0 || tid == 512) && st_stride > 0 && blockIdx.x % st_stride == 0 && blockIdx.x / st_stride < 4;
-    const int st_slot = st_on ? (blockIdx.x / st_stride) * 2 + (tid >> 9) : 0;
-    int st_n = 0;
-#endif
-
-    if (wv < 8) {
-        // ---------------- stage S: input patch -> stem pixels -> patch[k & 1] ----------------
-        // stem weights as A fragments in registers.  API column order of w1 (see rva_stem_conv_f16): k = 2j + kx for kx in
-        // {0,1}, 18 + j for kx = 2, j = c*3 + ky.  The bias is the accumulator's initial value.
-        h8 af1[2], af2[2];
-        f4 bias1[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const __half *wr = a.w1 + (size_t)(16 * i + n) * 32;
-            const __half zero = __float2half(0.f);
-            __half t1[8], t2[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int j = 2 * q + (e >> 2), sl = e & 3, kx = sl - 1;
-                t1[e] = sl == 0 ? zero : wr[kx < 2 ? 2 * j + kx : 18 + j];
-                t2[e] = (q == 0 && e >= 1 && e < 4) ? wr[e - 1 < 2 ? 16 + (e - 1) : 26] : zero;
-            }
-            af1[i] = *reinterpret_cast<const h8 *>(t1);
-            af2[i] = *reinterpret_cast<const h8 *>(t2);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) bias1[i][u] = a.b1[16 * i + 4 * q + u];
-        }
-        // this lane's two (c, ky) rows of the first K step, as half offsets into the input patch
-        const int ro0 = (((2 * q) / 3) * IR + (2 * q) % 3) * IC, ro1 = (((2 * q + 1) / 3) * IR + (2 * q + 1) % 3) * IC;
-        constexpr int ro8 = (2 * IR + 2) * IC;
-        u4 pv[NPV];
-        auto prefetch = [&](int t) {
-            const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-            const int iy0 = 4 * (a.y0 + ty * TH) - 3, x00 = 4 * tx * TW - 8;
-#pragma unroll
-            for (int k = 0; k < NPV; ++k) {
-                const int c16 = tid + 512 * k;
-                const int row = c16 / 17, cx = c16 - row * 17;
-                const int c = row / IR, r = row - c * IR;
-                const int iy = iy0 + r, x0 = x00 + cx * 8;
-                pv[k] = u4{0u, 0u, 0u, 0u};
-                if (c16 < NCH && (unsigned)iy < (unsigned)a.H && (unsigned)x0 < (unsigned)a.W)
-                    pv[k] = *reinterpret_cast<const u4 *>(a.in + ((size_t)(b * 3 + c) * a.H + iy) * a.W + x0);
-            }
-        };
-        auto stage_input = [&](int buf) {
-            __half *inp = inp0 + (size_t)buf * 3 * IR * IC;
-#pragma unroll
-            for (int k = 0; k < NPV; ++k) {
-                const int c16 = tid + 512 * k;
-                if (c16 < NCH) *reinterpret_cast<u4 *>(inp + (size_t)(c16 / 17) * IC + (c16 % 17) * 8) = pv[k];
-            }
-        };
-        // geometry of this lane's pixel in each of the wave's fragments (the same for every tile): read offset into the input
-        // patch, (py << 8 | px), and the write offset of channel group 0 in the stem patch (group 1 = that ^ 16)
-        constexpr int FPW = (NFR + 7) / 8, UNR = FPW;
-        static_assert(FPW % UNR == 0, "fragments per wave");
-        int frd[FPW], fpp[FPW], fw[FPW];
-#pragma unroll
-        for (int e = 0; e < FPW; ++e) {
-            const int f = wv + 8 * e;
-            const int p = min(16 * f + n, SPX - 1);
-            const int py = p / (2 * TW + 1), px = p - py * (2 * TW + 1);
-            const int prow = (py * 2 + (px & 1)) * CW + (px >> 1);
-            frd[e] = (2 * py) * IC + 2 * px + 4;
-            fpp[e] = (py << 8) | px;
-            fw[e] = 16 * f + n < SPX ? swz32(prow, q >> 1) + 4 * (q & 1) : PROWS * 32 + 4 * (q & 1);      // no pixel: the dump row behind the patch
-        }
-        if (nk > 0) { prefetch(blockIdx.x); stage_input(0); }
-        __syncthreads();                                       // input patch of the first tile visible to the group
-        for (int k = 0; k <= nk; ++k) {                        // iteration k: this group works on tile k, the other on tile k - 1
-            STAMP(0);
-            if (k < nk) {
-                const int t = blockIdx.x + k * gridDim.x;
-                const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-                (void)b;
-                if (k + 1 < nk) prefetch(t + gridDim.x);
-                const __half *inp = inp0 + (size_t)(k & 1) * 3 * IR * IC;
-                __half *patch = patch0 + (size_t)(k & 1) * (PROWS + 1) * 32;
-                const int sy0 = 2 * (a.y0 + ty * TH) - 1, sx0 = 2 * tx * TW - 1;
-                // fragments in pairs: the chain  LDS read -> 2 dependent MFMAs -> exp / rcp -> LDS write  of one fragment is
-                // ~700 cycles of latency (tools/stem2_stamps.py); independent chains overlap
-                const int pyb = -sy0, pxb = -sx0;                     // first in-image patch row / column
-                const int pye = a.H1 - sy0, pxe = a.W1 - sx0;         // one past the last
-#pragma unroll
-                for (int g = 0; g < FPW / UNR; ++g) {
-                    h8 bf1[UNR], bf2[UNR];
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
-                        const __half *base = inp + frd[g * UNR + u];
-                        const uint32_t *d0 = reinterpret_cast<const uint32_t *>(base + ro0), *d1 = reinterpret_cast<const uint32_t *>(base + ro1);
-                        const uint32_t *d8 = reinterpret_cast<const uint32_t *>(base + ro8);
-                        uint32_t b1w[4] = {d0[0], d0[1], d1[0], d1[1]};
-                        uint32_t b2w[4] = {d8[0], d8[1], 0u, 0u};       // lanes q > 0 carry zero weights in af2: their (finite) data is ignored
-                        bf1[u] = *reinterpret_cast<const h8 *>(b1w);
-                        bf2[u] = *reinterpret_cast<const h8 *>(b2w);
-                    }
-                    f4 sacc[UNR][2];
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) sacc[u][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af1[i], bf1[u], bias1[i], 0, 0, 0);
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) sacc[u][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af2[i], bf2[u], sacc[u][i], 0, 0, 0);
-#pragma unroll
-                    for (int u = 0; u < UNR; ++u) {
-                        const int py = fpp[g * UNR + u] >> 8, px = fpp[g * UNR + u] & 255;
-                        const bool inimg = py >= pyb && py < pye && px >= pxb && px < pxe;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) {
-                            const float v0 = silu_f(sacc[u][i][0]), v1 = silu_f(sacc[u][i][1]), v2 = silu_f(sacc[u][i][2]), v3 = silu_f(sacc[u][i][3]);
-                            __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-                            uint2 pk;
-                            pk.x = inimg ? *reinterpret_cast<uint32_t *>(&lo) : 0u;
-                            pk.y = inimg ? *reinterpret_cast<uint32_t *>(&hi) : 0u;
-                            *reinterpret_cast<uint2 *>(patch + (fw[g * UNR + u] ^ (16 * i))) = pk;     // lanes without a pixel: the dump row
-                        }
-                    }
-                }
-                STAMP(1);
-                if (k + 1 < nk) stage_input((k + 1) & 1);      // its last readers finished in iteration k - 1
-            } else { STAMP(1); }
-            STAMP(2);
-            __syncthreads();
-            STAMP(3);
-        }
-    } else {
-        // ---------------- stage C: patch[(k - 1) & 1] -> second convolution -> output tile ----------------
-        const int wb = wv - 8, orow = wb >> 1, ohalf = wb & 1;          // output row of the tile / 16-pixel half of it
-        float4 bvs[FN];
-#pragma unroll
-        for (int i = 0; i < FN; ++i) bvs[i] = *reinterpret_cast<const float4 *>(a.b2 + 16 * i + q * 4);
-        wait_vm<0>();                                          // this wave's share of the weights
-        __syncthreads();
-        __half *stage = stage0 + (size_t)wb * 16 * SROW;
-        for (int k = 0; k <= nk; ++k) {
-            STAMP(0);
-            if (k > 0) {
-                const int t = blockIdx.x + (k - 1) * gridDim.x;
-                const int b = t / tiles_img, r2 = t - b * tiles_img, ty = r2 / a.tiles_x, tx = r2 - ty * a.tiles_x;
-                const __half *patch = patch0 + (size_t)((k - 1) & 1) * (PROWS + 1) * 32;
-                f4 acc[FN];
-#pragma unroll
-                for (int i = 0; i < FN; ++i) acc[i] = f4{bvs[i].x, bvs[i].y, bvs[i].z, bvs[i].w};
-#pragma unroll
-                for (int tp = 0; tp < 9; ++tp) {
-                    const int dy = tp / 3, dx = tp % 3;
-                    const int rb = ((2 * orow + dy) * 2 + (dx & 1)) * CW + (dx >> 1) + 16 * ohalf + n;
-                    const h8 bf = *reinterpret_cast<const h8 *>(patch + swz32(rb, q));
-#pragma unroll
-                    for (int i = 0; i < FN; ++i) {
-                        const h8 af = *reinterpret_cast<const h8 *>(wl + swz32(tp * 64 + 16 * i + n, q));
-                        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc[i], 0, 0, 0);
-                    }
-                }
-                STAMP(1);
-#pragma unroll
-                for (int i = 0; i < FN; ++i) {
-                    const int co = 16 * i + q * 4;
-                    const float v0 = silu_f(acc[i][0]), v1 = silu_f(acc[i][1]), v2 = silu_f(acc[i][2]), v3 = silu_f(acc[i][3]);
-                    __half2 lo = __floats2half2_rn(v0, v1), hi = __floats2half2_rn(v2, v3);
-                    uint2 pk;
-                    pk.x = *reinterpret_cast<uint32_t *>(&lo);
-                    pk.y = *reinterpret_cast<uint32_t *>(&hi);
-                    *reinterpret_cast<uint2 *>(stage + (size_t)n * SROW + co) = pk;
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the stage rows are this wave's own: no barrier, just ordering
-                const int yy = a.y0 + ty * TH + orow;
-#pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    const int c16 = lane + 64 * it;
-                    const int opx = c16 >> 3, pc = c16 & 7;
-                    const int xx = tx * TW + 16 * ohalf + opx;
-                    if (yy < a.y1 && xx < a.Wo)
-                        *reinterpret_cast<uint4 *>(a.out + ((size_t)(b * a.Ho + yy) * a.Wo + xx) * a.ldo + pc * 8) =
-                            *reinterpret_cast<const uint4 *>(stage + (size_t)opx * SROW + pc * 8);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // stage reads done before the next tile's stage writes
-            } else { STAMP(1); }
-            STAMP(2);
-            __syncthreads();
-            STAMP(3);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
 // Dispatch: from a variant number to a launch.
 //
 // rva_conv2d_nhwc_f16_v validates its arguments once and hands every variant the same ConvCall.  A family's adapter (v_*)
@@ -3474,6 +2557,14 @@ G dma3_args(const ConvCall &c)
 {
     G g = family_args<G>(c);
     g.Cin = c.a.Cin; g.CoutPad = c.cpad; g.M = c.a.M;
+    return g;
+}
+
+// S2Args: the patch families, on the row window
+inline S2Args patch_args(const ConvCall &c)
+{
+    S2Args g = family_args<S2Args>(c);
+    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad; g.y0 = c.y0; g.y1 = c.y1;
     return g;
 }
 
@@ -3551,8 +2642,7 @@ template <int STRIDE, int CIN, int CO, int NWV, int NBUF, int RPW = 1>
 hipError_t v_patch(const ConvCall &c)
 {
     if (!is_3x3(c, STRIDE) || c.a.Cin != CIN || c.a.Cout > (CIN == 64 ? 64 : CO)) return hipErrorInvalidValue;
-    S2Args g = family_args<S2Args>(c);
-    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad; g.y0 = c.y0; g.y1 = c.y1;
+    S2Args g = patch_args(c);
     return launch_patch<STRIDE, CIN, CO, NWV, NBUF, RPW>(g, c.num_cus, c.s);
 }
 
@@ -3561,8 +2651,7 @@ template <int CIN, int CO, int SW, int RPW>
 hipError_t v_patch2(const ConvCall &c)
 {
     if (!is_3x3(c, 1) || c.a.Cin != CIN || c.a.Cout > CO) return hipErrorInvalidValue;
-    S2Args g = family_args<S2Args>(c);
-    g.B = c.batch; g.Ho = c.a.Ho; g.Wo = c.a.Wo; g.CoutPad = c.cpad; g.y0 = c.y0; g.y1 = c.y1;
+    S2Args g = patch_args(c);
     return launch_patch2<CIN, CO, SW, RPW>(g, c.num_cus, c.s);
 }
 
@@ -3856,10 +2945,11 @@ bool rva_conv_variant_is_gather64(int variant)
 #undef RVA_IS
 }
 
-extern "C" {
 #ifdef RVA_ROW_STAMPS
-int rva_dbg_read_stamps(unsigned long long *host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 8 * 256); }
+RVA_STAMP_READER(rva_dbg_read_stamps)
 #endif
+
+extern "C" {
 
 int rva_conv2d_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, const void *weights, const float *bias, void *out,
                         int ldo, const void *residual, int ldr, int batch, int H, int W, int Cin, int Cout, int ksize,
@@ -3913,8 +3003,7 @@ int rva_conv2d_nhwc_f16_sel(rva_ctx *ctx, const void *in, int ldi, const void *w
     a.Wo = (W + 2 * pad - ksize) / stride + 1;
     a.M = batch * a.Ho * a.Wo;
     a.wy0 = 0; a.wrows = a.Ho;
-    if (y1 < 0) y1 = a.Ho;
-    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_conv2d_nhwc_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
+    if (rva_row_window(ctx, "rva_conv2d_nhwc_f16_rows", y0, y1, a.Ho)) return RVA_ERR_ARG;
     c.y0 = y0; c.y1 = y1;
     c.batch = batch; c.sel_batch = sel_batch; c.ksize = ksize;
     c.cpad = rva_ceil_div(Cout, 64) * 64;
@@ -4016,35 +3105,6 @@ int rva_conv1x1_head5_f16(rva_ctx *ctx, const void *in, int ldi, const void *wei
     return launch_gather64_1x1<false, true>(ctx, "rva_conv1x1_head5_f16", a, variant, (hipStream_t)stream_);
 }
 
-int rva_stem6_conv_f16_rows(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
-                            int batch, int H, int W, int Cout, int y0, int y1, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if (!in_planar || !weights || !bias || !out || batch <= 0 || H <= 0 || W <= 0 || Cout < 8 || Cout % 8 || Cout > 64 || ldo % 8 || ldo < Cout ||
-        W % 8 || H % 2 || ((uintptr_t)in_planar | (uintptr_t)weights | (uintptr_t)out) % 16)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16: Cout %% 8 == 0 and <= 64, ldo %% 8 == 0, W %% 8 == 0, even H, 16-byte aligned tensors");
-    Stem6Args a{(const __half *)in_planar, bias, (__half *)out, batch, H, W, H / 2, W / 2, Cout, ldo, 0, 0};
-    if (y1 < 0) y1 = a.Ho;
-    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
-    a.y0 = y0; a.y1 = y1;
-    const long total_tiles = (long)rva_ceil_div(a.Wo, 32) * rva_ceil_div(y1 - y0, 8) * batch;
-    if (total_tiles >= (1l << 30)) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem6_conv_f16: tensor too large");
-    const size_t smem = (size_t)(3 * 20 * 88 + 64 * 136 + 256 * (Cout + 8)) * 2;      // 39 .. 63 KB
-    // persistent: two blocks per CU.  As many as LDS holds (three at Cout = 32) measured slower: 124 against 115 us for
-    // 32 x 640 x 640 -> 320 x 320 x 32 (profiles/yolov5_plan.json is the two-block form)
-    int grid = 2 * rva_num_cus(ctx);
-    if (grid > total_tiles) grid = (int)total_tiles;
-    k_stem6<<<grid, 256, smem, (hipStream_t)stream_>>>(a, (const __half *)weights);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_stem6_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
-                       int batch, int H, int W, int Cout, rva_stream_t stream_)
-{
-    return rva_stem6_conv_f16_rows(ctx, in_planar, weights, bias, out, ldo, batch, H, W, Cout, 0, -1, stream_);
-}
-
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }
 
 int rva_conv_num_variants(void) { return kConvVariantsMax; }
@@ -4053,211 +3113,6 @@ const char *rva_conv_variant_name(int variant)
 {
     const ConvVariant *row = find_variant(variant);
     return row ? row->name : nullptr;
-}
-
-int rva_stem_conv_f16(rva_ctx *ctx, const void *in_planar, const void *weights, const float *bias, void *out, int ldo,
-                      int batch, int H, int W, int Cout, rva_stream_t stream_)
-{
-    if (!ctx || !in_planar || !weights || !bias || !out || Cout % 8 || Cout > 64 || ldo % 8)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_stem_conv_f16: bad argument");
-    StemArgs a{(const __half *)in_planar, nullptr, bias, (__half *)out, batch, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Cout, ldo};
-#ifdef RVA_ROW_STAMPS
-    { const char *e = getenv("RVA_STEM_DBG"); a.dbg = e ? atoi(e) : 0; }
-#endif
-    const int total_tiles = rva_ceil_div(a.Wo, 32) * rva_ceil_div(a.Ho, 8) * batch;
-    int grid = 256 * 4;                                     // persistent: ~4 blocks per CU (LDS-limited)
-    if (grid > total_tiles) grid = total_tiles;
-    if (W % 8 || ((uintptr_t)in_planar & 15)) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem_conv_f16: W %% 8 == 0 and a 16-byte aligned input are required");
-    k_stem<<<grid, 256, (size_t)(3 * 17 * 88 * 2) + (size_t)(256 * (Cout + 8 > LDSROW ? Cout + 8 : LDSROW) + 64 * LDSROW) * 2, (hipStream_t)stream_>>>(a, (const __half *)weights, bias);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_c2f_pair32_f16(rva_ctx *ctx, const void *in, int ldi, const void *w1, const float *b1, const void *w2, const float *b2, void *out,
-                       int ldo, int batch, int H, int W, rva_stream_t stream_)
-{
-    if (!ctx || !in || !w1 || !b1 || !w2 || !b2 || !out || batch <= 0 || H <= 0 || W <= 0 || ldi % 8 || ldo % 8 || ldi < 32 || ldo < 32)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: bad argument");
-    if ((((size_t)in) | ((size_t)out) | ((size_t)w1) | ((size_t)w2)) & 15) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: 16-byte aligned tensors");
-    if ((size_t)batch * H * W >= (1ull << 31)) return rva_fail(ctx, RVA_ERR_ARG, "rva_c2f_pair32_f16: tensor too large");
-    PairArgs a{(const __half *)in, ldi, (const __half *)w1, b1, (const __half *)w2, b2, (__half *)out, ldo, batch, H, W,
-               rva_ceil_div(W, PR_TW), rva_ceil_div(H, PR_TH), 0};
-    a.total = a.tiles_x * a.tiles_y * batch;
-    RVA_HIP(ctx, rva_func_smem((const void *)k_c2f_pair32, PR_SMEM));
-    int grid = 2 * rva_num_cus(ctx);
-    if (grid > a.total) grid = a.total;
-    k_c2f_pair32<<<grid, 256, PR_SMEM, (hipStream_t)stream_>>>(a);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_stem2_f16(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
-                  void *out, int ldo, int batch, int H, int W, rva_stream_t stream_)
-{
-    return rva_stem2_f16_rows(ctx, in_planar, w1, b1, w2, b2, out, ldo, batch, H, W, 0, -1, stream_);
-}
-
-// rows [y0, y1) of the quarter-resolution output only (y1 < 0 = the last row): the 4 x 32 tiles are laid over the window
-int rva_stem2_f16_rows(rva_ctx *ctx, const void *in_planar, const void *w1, const float *b1, const void *w2, const float *b2,
-                       void *out, int ldo, int batch, int H, int W, int y0, int y1, rva_stream_t stream_)
-{
-    if (!ctx || !in_planar || !w1 || !b1 || !w2 || !b2 || !out || ldo % 8 || ldo < 64 || batch <= 0 || H < 4 || W < 4)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16: bad argument");
-    if (W % 8 || ((uintptr_t)in_planar & 15)) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16: W %% 8 == 0 and a 16-byte aligned input are required");
-    Stem2Args a{(const __half *)in_planar, (const __half *)w1, b1, (const __half *)w2, b2, (__half *)out, ldo, batch, H, W};
-    a.H1 = (H - 1) / 2 + 1; a.W1 = (W - 1) / 2 + 1;
-    a.Ho = (a.H1 - 1) / 2 + 1; a.Wo = (a.W1 - 1) / 2 + 1;
-    if (y1 < 0) y1 = a.Ho;
-    if (y0 < 0 || y0 >= y1 || y1 > a.Ho) return rva_fail(ctx, RVA_ERR_ARG, "rva_stem2_f16_rows: rows [%d, %d) are not a window of %d output rows", y0, y1, a.Ho);
-    a.y0 = y0; a.y1 = y1;
-    a.tiles_x = rva_ceil_div(a.Wo, S2_TW); a.tiles_y = rva_ceil_div(y1 - y0, S2_TH);
-    a.total = a.tiles_x * a.tiles_y * batch;
-    constexpr size_t smem = S2_SMEM;
-    RVA_HIP(ctx, rva_func_smem((const void *)k_stem2, smem));
-    int grid = rva_num_cus(ctx);                           // persistent: one block per CU (159 KB of LDS each)
-    if (grid > a.total) grid = a.total;
-    k_stem2<<<grid, 1024, smem, (hipStream_t)stream_>>>(a);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_maxpool5_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, void *out, int ldo, int batch, int H, int W, int C,
-                          rva_stream_t stream_)
-{
-    if (!ctx || !in || !out || C % 8 || ldi % 8 || ldo % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_maxpool5_nhwc_f16: bad argument");
-    const long n = (long)batch * H * W * (C / 8);
-    k_maxpool5<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream_>>>((const __half *)in, ldi, (__half *)out, ldo, batch, H, W, C);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_sppf_pool3_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, void *out1, void *out2, void *out3, int ldo, int batch,
-                            int H, int W, int C, rva_stream_t stream_)
-{
-    if (!ctx || !in || !out1 || !out2 || !out3 || C % 8 || ldi % 8 || ldo % 8 || batch <= 0 || H <= 0 || W <= 0)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_sppf_pool3_nhwc_f16: bad argument");
-    const size_t smem = (size_t)H * W * 16 * 4;
-    if (smem > 150 * 1024) return rva_fail(ctx, RVA_ERR_ARG, "rva_sppf_pool3_nhwc_f16: H*W too large for one LDS tile (use rva_maxpool5_nhwc_f16 x3)");
-    // whole 64-byte runs per wave where that still fills the chip (32 frames of YOLOv8s: 256 blocks of 1024 threads)
-    if (C % 32 == 0 && (long)batch * (C / 32) >= 192 && (size_t)H * W * 4 <= 4096 && (size_t)H * W * 4 * 16 * 3 <= 150 * 1024 && !getenv("RVA_SPPF_G1")) {
-        RVA_HIP(ctx, rva_func_smem((const void *)k_sppf_pool3g<4>, 150 * 1024));
-        k_sppf_pool3g<4><<<batch * (C / 32), 1024, (size_t)H * W * 4 * 16 * 3, (hipStream_t)stream_>>>((const __half *)in, ldi, (__half *)out1,
-                                                                                              (__half *)out2, (__half *)out3, ldo, H, W, C);
-        RVA_HIP(ctx, hipGetLastError());
-        return RVA_OK;
-    }
-    RVA_HIP(ctx, rva_func_smem((const void *)k_sppf_pool3, 150 * 1024));
-    k_sppf_pool3<<<batch * (C / 8), 256, smem, (hipStream_t)stream_>>>((const __half *)in, ldi, (__half *)out1, (__half *)out2,
-                                                                       (__half *)out3, ldo, H, W, C);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_upsample2x_nhwc_f16(rva_ctx *ctx, const void *in, int ldi, void *out, int ldo, int batch, int H, int W, int C,
-                            rva_stream_t stream_)
-{
-    if (!ctx || !in || !out || C % 8 || ldi % 8 || ldo % 8) return rva_fail(ctx, RVA_ERR_ARG, "rva_upsample2x_nhwc_f16: bad argument");
-    const long n = (long)batch * H * 2 * W * 2 * (C / 8);
-    k_upsample2<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream_>>>((const __half *)in, ldi, (__half *)out, ldo, batch, H, W, C);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-static int yolo_head3(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
-                      const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
-                      const float *strides, rva_stream_t stream_, bool any_nc = false)
-{
-    if (!ctx || !box_logits || !cls_logits || !ldb || !ldc || !h || !w || !strides || !out ||
-        (any_nc ? nc < 1 || nc > 1024 || batch <= 0 : nc % 8 != 0))
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: bad argument");
-    Head3Args a{};
-    int a0 = 0, total = 0;
-    for (int l = 0; l < 3; ++l) {
-        if (!box_logits[l] || !cls_logits[l] || ldb[l] % 8 || ldc[l] % 8 || h[l] <= 0 || w[l] <= 0 || (any_nc && ldc[l] < (nc + 7) / 8 * 8))
-            return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: bad level %d", l);
-        a.lv[l] = HeadArgs{(const __half *)box_logits[l], ldb[l], (const __half *)cls_logits[l], ldc[l], (__half *)out, batch,
-                           h[l], w[l], nc, anchors_total, a0, strides[l]};
-        a.blocks[l] = rva_ceil_div(h[l] * w[l], 256);
-        total += a.blocks[l];
-        a0 += h[l] * w[l];
-    }
-    if (a0 != anchors_total) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_f16: anchors_total != sum of h*w");
-    if (boxes32) k_head3_box32<<<dim3(total, batch), 256, 0, (hipStream_t)stream_>>>(a, boxes32);
-    else k_head3<<<dim3(total, batch), 256, 0, (hipStream_t)stream_>>>(a);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_yolo_head3_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
-                       const int32_t *ldc, void *out, int batch, const int32_t *h, const int32_t *w, int nc, int anchors_total,
-                       const float *strides, rva_stream_t stream_)
-{
-    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, nullptr, batch, h, w, nc, anchors_total, strides, stream_);
-}
-
-int rva_yolo_head3_box32_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
-                             const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
-                             int anchors_total, const float *strides, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if (!boxes32 || (uintptr_t)boxes32 % 4) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_box32_f16: boxes32 must be a float tensor [batch, 4, anchors_total]");
-    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, boxes32, batch, h, w, nc, anchors_total, strides, stream_);
-}
-
-int rva_yolo_head3_nc_f16(rva_ctx *ctx, const void *const *box_logits, const int32_t *ldb, const void *const *cls_logits,
-                          const int32_t *ldc, void *out, float *boxes32, int batch, const int32_t *h, const int32_t *w, int nc,
-                          int anchors_total, const float *strides, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if ((uintptr_t)boxes32 % 4) return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head3_nc_f16: boxes32 must be NULL or a float tensor [batch, 4, anchors_total]");
-    return yolo_head3(ctx, box_logits, ldb, cls_logits, ldc, out, boxes32, batch, h, w, nc, anchors_total, strides, stream_, true);
-}
-
-int rva_yolo_head_nc_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, float *boxes32,
-                         int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if (!box_logits || !cls_logits || !out || (uintptr_t)boxes32 % 4 || nc < 1 || nc > 1024 || ldb % 8 || ldc % 8 || ldc < (nc + 7) / 8 * 8 ||
-        batch <= 0 || h <= 0 || w <= 0 || anchor_offset < 0 || anchor_offset + h * w > anchors_total)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_nc_f16: bad argument (1 <= nc <= 1024; ldb, ldc %% 8; ldc >= roundup(nc, 8); the level inside "
-                        "the anchor range)");
-    HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
-               anchors_total, anchor_offset, stride};
-    dim3 g(rva_ceil_div(h * w, 256), batch);
-    if (boxes32) k_head_box32<<<g, 256, 0, (hipStream_t)stream_>>>(a, boxes32);
-    else k_head<<<g, 256, 0, (hipStream_t)stream_>>>(a);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_yolo_head_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, int batch,
-                      int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if (!box_logits || !cls_logits || !out || nc % 8 || ldb % 8 || ldc % 8 || batch <= 0 || h <= 0 || w <= 0 || anchor_offset < 0 ||
-        anchor_offset + h * w > anchors_total)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_f16: bad argument (nc, ldb, ldc %% 8; the level inside the anchor range)");
-    HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
-               anchors_total, anchor_offset, stride};
-    dim3 g(rva_ceil_div(h * w, 256), batch);
-    k_head<<<g, 256, 0, (hipStream_t)stream_>>>(a);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
-}
-
-int rva_yolo_head_box32_f16(rva_ctx *ctx, const void *box_logits, int ldb, const void *cls_logits, int ldc, void *out, float *boxes32,
-                            int batch, int h, int w, int nc, int anchors_total, int anchor_offset, float stride, rva_stream_t stream_)
-{
-    if (!ctx) return RVA_ERR_ARG;
-    if (!box_logits || !cls_logits || !out || !boxes32 || (uintptr_t)boxes32 % 4 || nc % 8 || ldb % 8 || ldc % 8 || batch <= 0 || h <= 0 || w <= 0 ||
-        anchor_offset < 0 || anchor_offset + h * w > anchors_total)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_yolo_head_box32_f16: bad argument (boxes32 [batch, 4, anchors_total] float, the level inside the anchor range)");
-    HeadArgs a{(const __half *)box_logits, ldb, (const __half *)cls_logits, ldc, (__half *)out, batch, h, w, nc,
-               anchors_total, anchor_offset, stride};
-    dim3 g(rva_ceil_div(h * w, 256), batch);
-    k_head_box32<<<g, 256, 0, (hipStream_t)stream_>>>(a, boxes32);
-    RVA_HIP(ctx, hipGetLastError());
-    return RVA_OK;
 }
 
 }  // extern "C"

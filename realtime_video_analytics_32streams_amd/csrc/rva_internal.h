@@ -70,6 +70,14 @@ int rva_get_taps(rva_ctx *ctx, int src, int dst, bool is_x, rva_resize_table *ou
 
 static inline int rva_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The output row window [y0, y1) of entry point `who` (a *_rows function) in an image of Ho output rows: y1 < 0 = the last row.
+inline int rva_row_window(rva_ctx *ctx, const char *who, int y0, int &y1, int Ho)
+{
+    if (y1 < 0) y1 = Ho;
+    if (y0 < 0 || y0 >= y1 || y1 > Ho) return rva_fail(ctx, RVA_ERR_ARG, "%s: rows [%d, %d) are not a window of %d output rows", who, y0, y1, Ho);
+    return RVA_OK;
+}
+
 // Raise a kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) to at least `bytes` on the CURRENT
 // device.  The attribute belongs to the (device, function) pair, so the bookkeeping is keyed by both: a second context
 // on another device of the same process gets its own call (a process-global `static bool` would skip it).  Must not be

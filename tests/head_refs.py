@@ -1,6 +1,7 @@
 """Float64 reference, designed logits and derived rounding bounds for the YOLOv8 detect head, shared by
 tests/test_head_refs_host.py (CPU: the bounds see the bugs) and tests/test_gpu_head_f64.py (the three copies of the head:
-``head_anchor`` and the ``HEAD`` epilogue of the 1x1 convolution in csrc/rva_conv.hip, ``k_head_f32`` in csrc/rva_conv_f32.hip).
+``head_anchor`` in csrc/rva_yolo_ops.hip, the ``HEAD`` epilogue of the 1x1 convolution in csrc/rva_conv.hip, ``k_head_f32`` in
+csrc/rva_conv_f32.hip).
 
 Reference: ``head_ref`` is ``yolov8.DetectHead.forward`` written out in float64: softmax over the 16 bins of each of the 4 sides,
 expectation against 0..15, anchor (x + 0.5, y + 0.5) in raster order i = y*w + x, xywh = ((x1y1 + x2y2) / 2, x2y2 - x1y1) * stride,

@@ -25,7 +25,7 @@ for _ in range(3):
     assert L.rva_stem2_f16(ctx, p(x), p(sw), p(sb), p(wp), p(bp), p(out), 64, B, H, W, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
 torch.cuda.synchronize()
 host = np.zeros((8, 256), dtype=np.uint64)
-assert L.rva_dbg_read_stamps(host.ctypes.data_as(C.c_void_p)) == 0
+assert L.rva_dbg_read_stem_stamps(host.ctypes.data_as(C.c_void_p)) == 0
 for slot in range(8):
     t = host[slot].astype(np.int64)
     n = int((t > 0).sum()) // 4

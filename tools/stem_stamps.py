@@ -21,7 +21,7 @@ for _ in range(3):
     assert L.rva_stem_conv_f16(ctx, x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), 32, B, H, H, 32, s) == 0
 torch.cuda.synchronize()
 host = np.zeros((8, 256), dtype=np.uint64)
-assert L.rva_dbg_read_stamps(host.ctypes.data_as(C.c_void_p)) == 0
+assert L.rva_dbg_read_stem_stamps(host.ctypes.data_as(C.c_void_p)) == 0
 names = ["tile store+sync", "prefetch issue", "im2col+sync", "frag reads+MFMA", "sync", "silu+stage+sync", "global stores"]
 for slot in (0, 3, 7):
     t = host[slot].astype(np.int64)
