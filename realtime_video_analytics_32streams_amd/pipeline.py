@@ -29,6 +29,7 @@ Multi-GPU: each rank owns a contiguous slice of the streams; the only exchange i
 """
 from __future__ import annotations
 
+import gc
 import os
 import time
 from dataclasses import dataclass, field
@@ -560,7 +561,22 @@ class PipelinedTicks:
 
     def _capture(self, plan, pres, motion):
         """Record the networks (per group and head-tensor parity) and the stream-B part (per parity) of a tick of this
-        shape.  Nothing executes here; every kernel of the shape has already run eagerly once."""
+        shape.  Nothing executes here; every kernel of the shape has already run eagerly once.
+
+        The cyclic garbage collector stays off while a stream captures.  A dead plan or context waits in a reference cycle (a
+        plan's tunables hold closures over the plan) until some collection finalises it, ``torch.cuda.graph`` does not collect on
+        entry, and a finaliser that frees device memory inside a capture invalidates the capture -- with the HIP error swallowed
+        by ``__del__``, so that only ``capture_end`` reports "a previous error during capture".  So: collect first, then record."""
+        gc.collect()
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            self._capture_graphs(plan, pres, motion)
+        finally:
+            if was_enabled:
+                gc.enable()
+
+    def _capture_graphs(self, plan, pres, motion):
         p = self.pipe
         torch.cuda.synchronize()
         self._net_graphs = []

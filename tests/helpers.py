@@ -172,19 +172,20 @@ def fp16_error_report(tag, got16, want_fp32, matched, conf=0.25):
     return rep
 
 
-# The fused YOLOv5 plan's yardstick (tests/test_gpu_yolov5_plan.py, tests/test_gpu_conv_slices.py).  Head tensors are
-# ``[B, 5 + nc, A]``; per row group the plan's largest error against the float64 module may be at most twice the largest error
+# The yardstick of the fused YOLOv5 and YOLO11 plans (tests/test_gpu_yolov5_plan.py, tests/test_gpu_conv_slices.py).  Head tensors
+# are ``[B, 5 + nc, A]`` (YOLOv5) or ``[B, 4 + nc, A]`` (YOLO11: four box rows, no objectness); per row group the plan's largest error against the float64 module may be at most twice the largest error
 # of the same module run by PyTorch fp16 channels-last: both store fp16 activations and differ only in summation order and
 # rounding points.
 V5_GROUPS = (("xy", slice(0, 2)), ("wh", slice(2, 4)), ("objectness", slice(4, 5)), ("classes", slice(5, None)))
+V11_GROUPS = (("boxes", slice(0, 4)), ("classes", slice(4, None)))
 
 
-def v5_head_errors(got, tor, want):
-    """``got`` (the plan), ``tor`` (PyTorch fp16), ``want`` (the float64 module), all float64 ``[B, 5 + nc, A]`` on one device ->
-    ``{group: {"plan_max_err", "torch_fp16_max_err"}}``."""
+def v5_head_errors(got, tor, want, groups=V5_GROUPS):
+    """``got`` (the plan), ``tor`` (PyTorch fp16), ``want`` (the float64 module), all float64 ``[B, rows, A]`` on one device ->
+    ``{group: {"plan_max_err", "torch_fp16_max_err"}}`` over the row ``groups`` of the family's head tensor."""
     assert got.shape == want.shape == tor.shape, (got.shape, want.shape, tor.shape)
     return {name: {"plan_max_err": float((got[:, rows] - want[:, rows]).abs().max()),
-                   "torch_fp16_max_err": float((tor[:, rows] - want[:, rows]).abs().max())} for name, rows in V5_GROUPS}
+                   "torch_fp16_max_err": float((tor[:, rows] - want[:, rows]).abs().max())} for name, rows in groups}
 
 
 def v5_groups_over_twice_torch(rec):

@@ -70,4 +70,5 @@ def test_bound_accepts_the_restatement_and_rejects_slice_mutants(key):
 
 
 def test_every_mutant_is_exercised():
-    assert {m for _, _, muts in CASES.values() for m in muts} == set(S.MUTANTS)
+    # no convolution step of a YOLOv5 plan runs without activation: that mutant is planted on YOLO11's (test_conv_slices_11_host.py)
+    assert {m for _, _, muts in CASES.values() for m in muts} == set(S.MUTANTS) - {"silu_despite_act0"}

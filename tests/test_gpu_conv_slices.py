@@ -1,12 +1,17 @@
 """Every row of the fp16 convolution variant table (``kConvVariants``, csrc/rva_conv.hip) where the fused plan really calls
 it: on channel slices of concat buffers with the plan's row strides, offsets and rounded-up Cin (part 1, against float64), and
-forced on the steps of real plans (part 2: YOLOv8 plans against the rounding-matched reference, YOLOv5 plans against the float64
-module with PyTorch fp16's error as the yardstick).  The autotuner picks rows by time alone; these tests are what makes "all
-variants compute the same layer" true for the layouts it picks them on.  ``FusedYoloV5`` inherits the tuner unchanged, and
-``Builder::c3`` / ``build_v5`` produce layouts the YOLOv8 builder never does: both parts cover them."""
+forced on the steps of real plans (part 2: YOLOv8 plans against the rounding-matched reference, YOLOv5 and YOLO11 plans against
+the float64 module with PyTorch fp16's error as the yardstick).  The autotuner picks rows by time alone; these tests are what
+makes "all variants compute the same layer" true for the layouts it picks them on.  ``FusedYoloV5`` and ``FusedYolo11`` inherit
+the tuner unchanged, and their builders produce layouts the YOLOv8 builder never does -- ``Builder::c3`` / ``build_v5``:
+residuals in another allocation, cv3 from the middle of a row; ``Builder::build_11`` / ``c2psa``: 8-channel buffers, bottlenecks
+with Cin != Cout, a C3k nested in a slice of a C2f row, a residual without activation, a zero-extended class branch.  Both parts
+cover all three builders."""
+import collections
 import ctypes as C
 import copy
 import functools
+import gc
 import json
 import os
 from pathlib import Path
@@ -17,11 +22,13 @@ import torch.nn.functional as F
 
 from realtime_video_analytics_32streams_amd import _native as N
 from realtime_video_analytics_32streams_amd import ops
-from realtime_video_analytics_32streams_amd.engine import FusedYoloV5, FusedYoloV8
+from realtime_video_analytics_32streams_amd.engine import FusedYolo11, FusedYoloV5, FusedYoloV8
+from realtime_video_analytics_32streams_amd.yolo11 import build_detector_net_11
 from realtime_video_analytics_32streams_amd.yolov5 import build_detector_net_v5
 from realtime_video_analytics_32streams_amd.yolov8 import build_detector_net
-from tests.conv_slice_layouts import Layout, V5_STRIDE1_LAYOUTS, V5_STRIDE2_LAYOUTS
-from tests.helpers import (assert_conv_close, assert_matches_rounded_reference, plan_rounded_reference, v5_head_errors,
+from tests.conv_slice_layouts import (Layout, V5_STRIDE1_LAYOUTS, V5_STRIDE2_LAYOUTS, V11_STRIDE1_LAYOUTS, V11_STRIDE2_LAYOUTS,
+                                      zero_extend)
+from tests.helpers import (V5_GROUPS, V11_GROUPS, assert_conv_close, assert_matches_rounded_reference, plan_rounded_reference, v5_head_errors,
                            v5_groups_over_twice_torch)
 
 pytestmark = pytest.mark.gpu
@@ -45,7 +52,7 @@ def _cv2(c, decl, n, i, shortcut=True):
 
 
 STRIDE1_LAYOUTS = [
-    # rva_plan.hip:250,261 (Builder::c2f, `conv1(b1, x, tmp, ...)` with x = cat.sub((1+i)*c, c)).
+    # Builder::c2f / Builder::bottleneck (`conv1(b1, x, tmp, ...)` with x = cat.sub((1+i)*c, c)).
     _cv1(16, 32, 1, 0),        # YOLOv8n b2: Cin 16 declared 32; the 16 channels read past the slice are the row's last slice
     _cv1(16, 32, 2, 0),        # ... are a real neighbour in the middle of the row
     _cv1(48, 64, 1, 0),        # YOLOv8m b2 widths: Cin 48 declared 64, past = last slice
@@ -53,7 +60,7 @@ STRIDE1_LAYOUTS = [
     _cv1(48, 64, 2, 1),        # ... past = the last slice, behind two slices
     _cv1(64, 64, 2, 1),        # YOLOv8n b6 / s b4: nothing read past the slice
     _cv1(128, 128, 1, 0),      # YOLOv8n b8 / s b6
-    # rva_plan.hip:262 (Builder::c2f, `conv1(b2, tmp, cat.sub((2+i)*c, c), ..., shortcut ? &x : nullptr)`): contiguous tmp in --
+    # Builder::c2f / Builder::bottleneck (`conv1(b2, tmp, y, ..., shortcut ? &x : nullptr)` with y = cat.sub((2+i)*c, c)): contiguous tmp in --
     # with c = 16 / 48 the declared Cin reaches into the next pixel and, behind the last pixel, into the 64-byte slack --
     # output slice and residual slice side by side in one allocation, ldr = ldo = (2+n)*c
     _cv2(16, 32, 1, 0),
@@ -61,39 +68,46 @@ STRIDE1_LAYOUTS = [
     _cv2(64, 64, 2, 0),
     _cv2(128, 128, 1, 0),
     _cv2(32, 32, 1, 0, shortcut=False),        # neck C2f (h15 of YOLOv8n): no shortcut
-    # rva_plan.hip:264,333 (C2f closing 1x1 `conv1(cv2, cat, dst, ...)` with dst = p3 = cat15.sub(c4, c3)): whole cat row in, back
+    # Builder::c2f / Builder::build (C2f closing 1x1 `conv1(cv2, cat, dst, ...)` with dst = p3 = cat15.sub(c4, c3)): whole cat row in, back
     # half of a neck concat buffer out, ldo = c4 + c3 and offset c4 (YOLOv8n b4: c = 32, n = 2)
     Layout("c2f close -> p3", 128, 128, 64, 1, 1, 1, (128, 0), (128 + 64, 128)),
-    # rva_plan.hip:264,325 (the same of YOLOv8n b2: cat of 3 x 16 channels declared 64, read into the next pixel / the slack)
+    # Builder::c2f (the same of YOLOv8n b2: cat of 3 x 16 channels declared 64, read into the next pixel / the slack)
     Layout("c2f close c16", 48, 64, 32, 1, 1, 1, (48, 0), (32, 0)),
-    # rva_plan.hip:417 (`conv1(box[l][1], first.sub(0, cb), b2, ...)`): row stride cb + cc = 144 halves = 288 bytes (YOLOv8n)
+    # Builder::build (`conv1(hd.box[l][1], first.sub(0, cb), b2, ...)`): row stride cb + cc = 144 halves = 288 bytes (YOLOv8n)
     Layout("detect box.1 n", 64, 64, 64, 3, 1, 1, (64 + 80, 0), (64, 0)),
-    # rva_plan.hip:418,423 (`conv1(cls[l][1], first.sub(cb, cc), k2, ...)`).  YOLOv8n: cc = 80 declared 96, so the step reads 16
+    # Builder::build (`conv1(cls[l][1], first.sub(cb, cc), k2, ...)`).  YOLOv8n: cc = 80 declared 96, so the step reads 16
     # channels of the NEXT pixel's box half; YOLOv8s: cc = 128, row stride 192
     Layout("detect cls.1 n", 80, 96, 80, 3, 1, 1, (64 + 80, 64), (80, 0)),
     Layout("detect cls.1 s", 128, 128, 128, 3, 1, 1, (64 + 128, 64), (128, 0)),
-    # rva_plan.hip:423 (`conv1(cls[l][2], k2, ko, ..., 0)`, the unfused head of YOLOv8n): no activation, Cin 80 declared 96 on a
+    # Builder::head_last (`conv1(c, src, o, l, 0)`, the unfused head of YOLOv8n): no activation, Cin 80 declared 96 on a
     # contiguous 80-channel buffer
     Layout("detect cls.2 n", 80, 96, 80, 1, 1, 0, (80, 0), (80, 0)),
-    # rva_plan.hip:415 (sibling launch `conv(sib, 2, feats[l], first, ...)`): Cout = cb + cc = 144 across the 64- and 96-channel tiles
+    # Builder::build (sibling launch `conv(sib, 2, feats[l], first, ...)`): Cout = cb + cc = 144 across the 64- and 96-channel tiles
     Layout("detect first n", 64, 64, 64 + 80, 3, 1, 1, (64, 0), (64 + 80, 0)),
 ]
 
 STRIDE2_LAYOUTS = [
-    # rva_plan.hip:335 (`conv1(take(c3, c4, 3, 2, "b5"), p3, t4, ...)`, p3 = cat15.sub(c4, c3)): reads a back-half slice
+    # Builder::backbone (`conv1(take(x.ch, t.ch, 3, 2, "b5"), x, t, ...)`, x = p3 = cat15.sub(c4, c3)): reads a back-half slice
     Layout("b5 n", 64, 64, 128, 3, 2, 1, (128 + 64, 128), (128, 0)),
     Layout("b5 m", 192, 192, 384, 3, 2, 1, (384 + 192, 384), (384, 0)),
-    # rva_plan.hip:375 (`conv1(take(c3, c3, 3, 2, "h16"), n3, cat18.sub(0, c3), ...)`): writes a front-half slice
+    # Builder::bottom_up (`conv1(take(x.ch, x.ch, 3, 2, "h16"), x, cat[i].sub(0, x.ch), ...)`, x = n3, cat18): writes a front-half slice
     Layout("h16 n", 64, 64, 64, 3, 2, 1, (64, 0), (64 + 128, 0)),
-    # rva_plan.hip:332 (`b3` of YOLOv8n, 32 -> 64: the Cin = 32 stride-2 patch kernel) into a front-half slice as h16 writes it
+    # Builder::backbone (`b3` of YOLOv8n, 32 -> 64: the Cin = 32 stride-2 patch kernel) into a front-half slice as h16 writes it
     Layout("s2 32->64 front half", 32, 32, 64, 3, 2, 1, (32, 0), (64 + 128, 0)),
 ]
 
-# The YOLOv5 builder (rva_plan.hip:316-443, Builder::c3 and build_v5): residuals in another allocation with ldr != ldo, sibling
-# launches into the front of a 3c row, cv3 from its middle, padded Cin under a stride-2 3x3.  Generated from a restatement of the
-# builder (tests/conv_slice_layouts.py, which cites the line of each step), not typed by hand.
+# The YOLOv5 builder (Builder::c3 and Builder::build_v5): residuals in another allocation with ldr != ldo, sibling launches into
+# the front of a 3c row, cv3 from its middle, padded Cin under a stride-2 3x3.  Generated from a restatement of the builder
+# (tests/conv_slice_layouts.py, which cites the statement of each step), not typed by hand.
 STRIDE1_LAYOUTS += V5_STRIDE1_LAYOUTS
 STRIDE2_LAYOUTS += V5_STRIDE2_LAYOUTS
+
+# The YOLO11 builder (Builder::build_11 through Builder::c2f, Builder::bottleneck with cmid = c / 2, Builder::c3 with k1 = 3, and
+# Builder::c2psa): Cout = 8 and Cin = 8 declared 32 on a 16-byte row, bottlenecks with Cin != Cout on concat slices, a C3k nested in
+# a slice of the outer row, act = 0 with a residual (ldr = ldo and ldr != ldo), cv1 of C2PSA as two launches, the class branch's
+# zero-extended pointwise convolutions.  Generated like the YOLOv5 ones; build_11 has no stride-2 step of a new kind.
+STRIDE1_LAYOUTS += V11_STRIDE1_LAYOUTS
+STRIDE2_LAYOUTS += V11_STRIDE2_LAYOUTS
 
 # B, H, W: tiles that straddle rows and images, and an M tail (9 x 7: 189 pixels); stride 2 with even sizes (the s2run rows)
 STRIDE1_SHAPES = [(3, 12, 20), (3, 6, 10), (3, 9, 7)]
@@ -127,6 +141,7 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
     x_rows = (torch.randn((Mi, ldi), generator=g) * 0.5).half()
     w = (torch.randn((lay.cout, lay.cin, k, k), generator=g) / (lay.cin * k * k) ** 0.5).half()
     b = torch.randn((lay.cout,), generator=g) * 0.1
+    w, b = zero_extend(lay, w, b)             # the class branch of YOLO11: zero past the checkpoint's channels, as Builder::padded
     out_rows = torch.full((Mo, ldo), SENTINEL, dtype=torch.float16)
     res, res_init, ldr = None, None, 0
     if lay.res is not None:
@@ -203,6 +218,8 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
             torch.cuda.synchronize()                 # a HIP error ends the test here: nothing more is launched after it
             on_slice.append(v)
             got = out[:Mo * ldo].reshape(Mo, ldo)[:, offo:offo + lay.cout].double()
+            # a residual without activation (Builder::c2psa) is rounded like one behind SiLU: conv + bias to fp16, the sum in
+            # fp32, to fp16 again, and the first rounded value is at most |want| + |res|: the bound's `res` term holds as it is
             assert_conv_close(got, want, res_dev, name)
             assert torch.equal(_bits(out)[untouched], _bits(out_init)[untouched]), (name, "wrote outside its output slice")
             if res_buf is not None:
@@ -219,6 +236,7 @@ def test_every_variant_on_a_plan_slice_matches_float64(layout, shape):
             assert rc == N.RVA_OK, (name, "contiguous", rc)
             torch.cuda.synchronize()
             on_contiguous.append(v)
+    print(f"[{lay.name} {B}x{H}x{W}] rows that applied: {len(on_slice)}")
     assert 0 in on_slice and len(on_slice) >= 3, on_slice
     assert on_slice == on_contiguous, ("applicability depends on strides", sorted(set(on_slice) ^ set(on_contiguous)))
 
@@ -375,18 +393,49 @@ def _v5_net(scale):
     return net
 
 
-def _record_v5(key, value):
+def _record_variants(fname, key, value):
     out = os.environ.get("RVA_REPORT_DIR")
     if out and Path(out).is_dir():
-        path = Path(out) / "yolov5_variants.json"
+        path = Path(out) / fname
         data = json.loads(path.read_text()) if path.exists() else {}
         data[key] = value
         path.write_text(json.dumps(data, indent=1, sort_keys=True))
 
 
+def _forced_against_float64(key, plan, net, x, head, groups):
+    """Every row forced on ``plan`` (``_run_forced``) under the yardstick of the fp16 plans: per row group of ``groups`` at most
+    twice the error of the same module in PyTorch fp16 channels-last, both against the float64 module on the CPU; variant 0 is held
+    to it first.  ``head`` turns the module's output into the plan's ``[B, rows, A]``.  Returns the forced pairs and, per group, the
+    errors of variant 0, of PyTorch, the largest error of any forced run and the row that gave it."""
+    with torch.inference_mode():
+        want = head(copy.deepcopy(net).double()(x.double())).contiguous().cuda()
+        ref16 = copy.deepcopy(net).half().cuda().to(memory_format=torch.channels_last)
+        tor = head(ref16(x.cuda().contiguous(memory_format=torch.channels_last))).double()
+    x = x.cuda()
+    rec = {}
+
+    def check(got):
+        errs = v5_head_errors(got.double(), tor, want, groups)
+        for name, e in errs.items():
+            r = rec.setdefault(name, {"variant0_max_err": e["plan_max_err"], "torch_fp16_max_err": e["torch_fp16_max_err"],
+                                      "forced_max_err": 0.0, "forced_max_err_row": 0})
+            row = max((st["variant"] for _, st, _ in plan._tunable), default=0)
+            if row and e["plan_max_err"] > r["forced_max_err"]:
+                r["forced_max_err"], r["forced_max_err_row"] = e["plan_max_err"], row
+        bad = v5_groups_over_twice_torch(errs)
+        assert not bad, ("plan error over twice PyTorch fp16's (group, plan, PyTorch)", bad)
+        return {name: (e["plan_max_err"], e["torch_fp16_max_err"]) for name, e in errs.items()}
+    try:
+        ran = _run_forced(plan, x, check)
+    finally:
+        for name, r in rec.items():
+            print(f"[{key}] {name}: variant 0 max |d| {r['variant0_max_err']:.4g}, forced rows max |d| {r['forced_max_err']:.4g} "
+                  f"(row {r['forced_max_err_row']}), PyTorch fp16 max |d| {r['torch_fp16_max_err']:.4g}")
+    return ran, rec
+
+
 def _force_every_variant_v5(key, monkeypatch):
-    """The yardstick is the plan's own (tests/test_gpu_yolov5_plan.py): per row group at most twice the error of the same module
-    in PyTorch fp16 channels-last, both against the float64 module on the CPU.  Variant 0 is held to it first."""
+    """The yardstick is the plan's own (tests/test_gpu_yolov5_plan.py), see ``_forced_against_float64``."""
     def run():
         scale, batch, hw = V5_CONFIGS[key]
         net = _v5_net(scale)
@@ -395,33 +444,10 @@ def _force_every_variant_v5(key, monkeypatch):
                 mp.delenv(name, raising=False)
             plan = FusedYoloV5(copy.deepcopy(net), batch, hw=hw, autotune=False)      # the tuning cache is not consulted
         x = torch.rand((batch, 3, *hw), generator=torch.Generator().manual_seed(17)).half()
-        with torch.inference_mode():
-            want = copy.deepcopy(net).double()(x.double()).transpose(1, 2).contiguous().cuda()
-            ref16 = copy.deepcopy(net).half().cuda().to(memory_format=torch.channels_last)
-            tor = ref16(x.cuda().contiguous(memory_format=torch.channels_last)).transpose(1, 2).double()
-        x = x.cuda()
-        rec = {}              # group -> the errors of variant 0, the largest error of any forced run and the row that gave it
-
-        def check(got):
-            errs = v5_head_errors(got.double(), tor, want)
-            for name, e in errs.items():
-                r = rec.setdefault(name, {"variant0_max_err": e["plan_max_err"], "torch_fp16_max_err": e["torch_fp16_max_err"],
-                                          "forced_max_err": 0.0, "forced_max_err_row": 0})
-                row = max((st["variant"] for _, st, _ in plan._tunable), default=0)
-                if row and e["plan_max_err"] > r["forced_max_err"]:
-                    r["forced_max_err"], r["forced_max_err_row"] = e["plan_max_err"], row
-            bad = v5_groups_over_twice_torch(errs)
-            assert not bad, ("plan error over twice PyTorch fp16's (group, plan, PyTorch)", bad)
-            return {name: (e["plan_max_err"], e["torch_fp16_max_err"]) for name, e in errs.items()}
-        try:
-            ran = _run_forced(plan, x, check)
-        finally:
-            for name, r in rec.items():
-                print(f"[{key}] {name}: variant 0 max |d| {r['variant0_max_err']:.4g}, forced rows max |d| {r['forced_max_err']:.4g} "
-                      f"(row {r['forced_max_err_row']}), PyTorch fp16 max |d| {r['torch_fp16_max_err']:.4g}")
+        ran, rec = _forced_against_float64(key, plan, net, x, lambda t: t.transpose(1, 2), V5_GROUPS)
         _v5_errors[key] = {"scale": scale, "batch": batch, "hw": list(hw), "step_variant_pairs": len(ran),
                            "distinct_rows": len({v for _, v in ran}), "groups": rec}
-        _record_v5(key, _v5_errors[key])
+        _record_variants("yolov5_variants.json", key, _v5_errors[key])
         return ran
     return _once(key, run)
 
@@ -448,3 +474,89 @@ def test_forced_variants_cover_the_table_on_yolov5(monkeypatch):
     for v in range(33, 40):
         for prefix in ("up", "head5:"):
             assert any(pv == v and desc.startswith(prefix) for desc, pv in ran), (v, prefix)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Part 2 for the YOLO11 builder: every row forced on the steps of real YOLO11 plans
+# ---------------------------------------------------------------------------------------------------
+# scale, classes, batch, (H, W).  n has the 8-channel steps (`2`: 16 -> 8 -> 16) and an unfused head, s and m the fused head steps,
+# m and l a C3k in every C3k2 (widths 64 to 512), l two inner blocks per C3k2 and two PSA blocks; nc 85 pads the class branch to 88
+# with zero-extended weights; 640 x 640 at batch 1 puts the W <= 160 and 2^24 gates where production has them (400 tokens in C2PSA).
+V11_CONFIGS = {
+    "11n": ("n", 80, 3, (96, 160)),
+    "11s": ("s", 80, 3, (96, 160)),
+    "11m": ("m", 80, 3, (96, 160)),
+    "11n-nc85": ("n", 85, 3, (96, 160)),
+    "11n-640": ("n", 80, 1, (640, 640)),
+    "11l": ("l", 80, 1, (96, 160)),
+}
+
+# Rows that no convolution step of any YOLO11 configuration above accepts, with the launcher's gate that keeps them out.
+NEVER_APPLIES_11 = {}
+
+_v11_errors = {}       # configuration -> what is recorded as profiles/yolo11_variants.json
+
+
+@functools.lru_cache(maxsize=None)
+def _v11_net(scale, nc):
+    """Seeded, BatchNorm folded, every parameter rounded to fp16 (kept as fp32), as ``_net()`` of tests/test_gpu_yolo11_plan.py.
+    Shared, never modified."""
+    net = build_detector_net_11(scale, seed=7, nc=nc).fuse()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.copy_(p.half().float())
+    return net
+
+
+def _force_every_variant_11(key, monkeypatch):
+    """The yardstick is the plan's own (tests/test_gpu_yolo11_plan.py), see ``_forced_against_float64``."""
+    def run():
+        scale, nc, batch, hw = V11_CONFIGS[key]
+        net = _v11_net(scale, nc)
+        with monkeypatch.context() as mp:
+            for name in _PLAN_ENV:
+                mp.delenv(name, raising=False)
+            plan = FusedYolo11(copy.deepcopy(net), batch, hw, autotune=False)         # the tuning cache is not consulted
+        x = torch.rand((batch, 3, *hw), generator=torch.Generator().manual_seed(17)).half()
+        ran, rec = _forced_against_float64(key, plan, net, x, lambda t: t, V11_GROUPS)
+        _v11_errors[key] = {"scale": scale, "nc": nc, "batch": batch, "hw": list(hw), "step_variant_pairs": len(ran),
+                            "distinct_rows": len({v for _, v in ran}), "groups": rec}
+        _record_variants("yolo11_variants.json", key, _v11_errors[key])
+        del plan
+        gc.collect()          # a plan is in a reference cycle with its tunables: free its device buffers now, not in some later test
+        return ran
+    return _once(key, run)
+
+
+@pytest.mark.parametrize("key", list(V11_CONFIGS))
+def test_every_variant_forced_on_the_yolo11_plan_steps(key, monkeypatch):
+    """Variant v on every step of a YOLO11 plan that accepts it (0 on the rest), for every v: each row group of the head tensor
+    (boxes, classes) stays within twice PyTorch fp16's error against the float64 module, as variant 0 must; non-finite output
+    fails."""
+    ran = _force_every_variant_11(key, monkeypatch)
+    print(f"{key}: {len(ran)} (step, variant) pairs forced, {len({v for _, v in ran})} distinct rows")
+    assert ran
+
+
+def test_forced_variants_cover_the_table_on_yolo11(monkeypatch):
+    """Over the YOLO11 configurations every row ran on a real plan step, but for the rows listed in NEVER_APPLIES_11; each LDS-DMA
+    gather tile (33..39) ran on an upsample + concat step and on a fused head step of each mode; and the steps only this builder
+    produces were among the forced pairs of YOLO11n: the 8-channel bottleneck, the 3x3 -> 3x3 bottlenecks of the nested C3k, and a
+    1x1 without activation.  A description does not carry the activation: ``128->256 k1s1`` at stride 32 is qkv (none) and ffn.0
+    (SiLU) of ``Builder::c2psa`` and nothing else, so a row forced on two steps of that description ran on qkv."""
+    per_key = {key: _force_every_variant_11(key, monkeypatch) for key in V11_CONFIGS}
+    for key, ran in per_key.items():
+        print(f"{key}: {len(ran)} (step, variant) pairs")
+    ran = [pair for pairs in per_key.values() for pair in pairs]
+    rows = set(range(1, N.lib().rva_conv_num_variants() + 1))
+    seen = {v for _, v in ran}
+    assert rows - seen == set(NEVER_APPLIES_11), sorted(rows - seen)
+    for v in range(33, 40):
+        for prefix in ("up", "head1:", "head2:"):
+            assert any(pv == v and desc.startswith(prefix) for desc, pv in ran), (v, prefix)
+    pairs = collections.Counter((desc.split(" r[")[0], v) for desc, v in per_key["11n"])
+    forced_on = {desc for desc, _ in pairs}
+    h5, w5 = 96 // 32, 160 // 32
+    for desc in (f"16->8 k3s1 {8 * h5}x{8 * w5}", f"8->16 k3s1 {8 * h5}x{8 * w5}", f"64->64 k3s1 {h5}x{w5}", f"128->256 k1s1 {h5}x{w5}"):
+        assert desc in forced_on, (desc, sorted(forced_on))
+    assert max(n for (desc, _), n in pairs.items() if desc == f"128->256 k1s1 {h5}x{w5}") == 2
