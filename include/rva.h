@@ -973,6 +973,62 @@ int rva_resnet_f16_plan_run_post(rva_resnet_f16_plan *plan, const void *logits, 
 int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *plan, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems,
                               rva_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The fp16 plan for any ResNet of the torchvision family (csrc/rva_resnet_f16.hip): the stem of rva_resnet_plan, then four
+ * stages of desc.blocks[s] blocks of width 64 << s -- BasicBlocks (3x3, 3x3: ResNet-18 / 34) or Bottlenecks (1x1, 3x3, 1x1 with
+ * expansion 4 and the stride on the 3x3: ResNet-50 / 101 / 152) --, the mean over H,W and Linear(512 * expansion -> classes).  The
+ * first block of stages 1..3 has stride 2.  A block whose stride is not 1 or whose input width differs from its output width has a
+ * 1x1 shortcut convolution (the first block of stage 0 of a Bottleneck net has one with stride 1).  Numeric contract, kernels and
+ * tile table are those of rva_resnet_f16_plan.
+ *
+ * rva_resnetx_f16_plan_create: weights as for rva_resnet_f16_plan_create; `convs` holds desc.n_convs convolutions, block by block
+ *   in the order conv1, conv2[, conv3], then the block's shortcut where it has one, each [Cout][k*k][Cin] with bias [Cout];
+ *   head_w is [classes][512 * expansion].  desc.n_convs is checked against the topology (RVA_ERR_ARG).  Limits: those of
+ *   rva_resnet_desc, bottleneck 0 or 1, blocks[s] 1..64, flags 0 or RVA_RESX_SPLIT_SHORTCUT.  stem_w and every convs[i].w are
+ *   rounded once to fp16; RVA_ERR_ARG naming "stem_w" / "conv[i].w" if a value does not stay finite.  RVA_ERR_CAPACITY before
+ *   anything is allocated.
+ *   Without RVA_RESX_SPLIT_SHORTCUT a block's shortcut convolution runs inside the launch of its closing convolution, as further
+ *   steps of the same fp32 sum (taps of the closing convolution in order, then the shortcut's input channels in order):
+ *   out = ReLU(conv_close(mid) + conv_short(x) + b), and the CLOSING convolution's `b` must hold b_close + b_short (added by the
+ *   caller in float64, rounded once to fp32); the shortcut's own `b` is not read.  With the flag the shortcut is a launch of its
+ *   own into its own fp16 stage and the closing convolution adds it as the residual: the launches and the order of
+ *   rva_resnet_f16_plan, and every `b` is the convolution's own.
+ * rva_resnetx_f16_plan_run / _run_post / _info: as rva_resnet_f16_plan_*.
+ * rva_resnetx_f16_plan_stage: the tap of rva_resnet_f16_plan_stage with these stage codes, b = the block's index over all stages:
+ *     RVA_RESX_POOLED                       [n][Hp][Wp][64]
+ *     RVA_RESX_FEAT                         [n][512 * expansion], fp32
+ *     RVA_RESX_BLOCK0 + 4 b + 0             after conv1 (a Bottleneck's is on the block's INPUT map: the stride is on the 3x3)
+ *     RVA_RESX_BLOCK0 + 4 b + 1             after conv2, Bottleneck only
+ *     RVA_RESX_BLOCK0 + 4 b + 2             the shortcut convolution, split plans only
+ *     RVA_RESX_BLOCK0 + 4 b + 3             the block's output; fp32 for the last block, fp16 otherwise
+ *   A stage the plan does not have is RVA_ERR_ARG.  Every stage keeps its own buffer.
+ * -------------------------------------------------------------------------------------------- */
+#define RVA_RESX_SPLIT_SHORTCUT 1     /* flags: shortcut convolutions as launches of their own (A/B and cross-check) */
+typedef struct rva_resnetx_f16_plan rva_resnetx_f16_plan;
+typedef struct rva_resnetx_desc {
+    int32_t height, width, classes, top_k, max_frames;   /* limits of rva_resnet_desc */
+    int32_t bottleneck;                                   /* 0 BasicBlock, 1 Bottleneck */
+    int32_t blocks[4];                                    /* 1..64 each */
+    int32_t n_convs;                                      /* length of convs: checked against the topology */
+    int32_t flags;
+} rva_resnetx_desc;
+typedef struct rva_resnetx_weights {
+    const float *stem_w, *stem_b;
+    const rva_resnet_conv *convs;    /* per block conv1, conv2[, conv3], then its shortcut where it has one; [Cout][k*k][Cin] */
+    const float *head_w, *head_b;    /* [classes][512 * expansion] */
+} rva_resnetx_weights;
+enum rva_resx_stage { RVA_RESX_POOLED = 0, RVA_RESX_FEAT = 1, RVA_RESX_BLOCK0 = 2 };
+int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, const rva_resnetx_weights *weights,
+                                rva_resnetx_f16_plan **out);
+void rva_resnetx_f16_plan_destroy(rva_resnetx_f16_plan *plan);
+int rva_resnetx_f16_plan_info(const rva_resnetx_f16_plan *plan, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches);
+int rva_resnetx_f16_plan_run(rva_resnetx_f16_plan *plan, const void *frames, const int32_t *frame_index, int n, void *logits,
+                             rva_stream_t stream);
+int rva_resnetx_f16_plan_run_post(rva_resnetx_f16_plan *plan, const void *logits, const int32_t *rows, int n_rows, int max_det,
+                                  void *scores, void *cls, void *boxes, void *counts, rva_stream_t stream);
+int rva_resnetx_f16_plan_stage(rva_resnetx_f16_plan *plan, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems,
+                               rva_stream_t stream);
+
 /* ----------------------------------------------------------------------------------------------
  * K5 motion gate -- replaces MotionFilter.should_process (utils/frame_filter.py:26-40)
  * for a tick of NV12 surfaces: gray -> 5x5 Gaussian -> |diff| against prev_blur[i] -> counts[i] = number of

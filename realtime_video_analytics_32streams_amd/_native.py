@@ -105,6 +105,28 @@ class ResNetWeights(C.Structure):
     _fields_ = [(n, C.POINTER(C.c_float)) for n in NAMES]
 
 
+class ResNetConv(C.Structure):
+    """``rva_resnet_conv`` (include/rva.h)."""
+    _fields_ = [("w", C.POINTER(C.c_float)), ("b", C.POINTER(C.c_float))]
+
+
+class ResNetXDesc(C.Structure):
+    """``rva_resnetx_desc`` (include/rva.h)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("classes", C.c_int32), ("top_k", C.c_int32), ("max_frames", C.c_int32),
+                ("bottleneck", C.c_int32), ("blocks", C.c_int32 * 4), ("n_convs", C.c_int32), ("flags", C.c_int32)]
+
+
+class ResNetXWeights(C.Structure):
+    """``rva_resnetx_weights`` (include/rva.h): ``convs`` points to ``n_convs`` :class:`ResNetConv` in the order
+    ``resnet_plan.pack_resnet`` writes ``c<i>_w`` / ``c<i>_b``."""
+    _fields_ = [("stem_w", C.POINTER(C.c_float)), ("stem_b", C.POINTER(C.c_float)), ("convs", C.POINTER(ResNetConv)),
+                ("head_w", C.POINTER(C.c_float)), ("head_b", C.POINTER(C.c_float))]
+
+
+RVA_RESX_SPLIT_SHORTCUT = 1
+RVA_RESX_POOLED, RVA_RESX_FEAT, RVA_RESX_BLOCK0 = 0, 1, 2
+
+
 class PreviewItem(C.Structure):
     """``rva_preview_item`` (include/rva.h): one surface of ``rva_preview_nv12_batch``."""
     _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("out_bgr", C.c_void_p)] + [
@@ -328,6 +350,12 @@ def lib() -> C.CDLL:
         "rva_resnet_f16_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
         "rva_resnet_f16_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
         "rva_resnet_f16_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
+        "rva_resnetx_f16_plan_create": (C.c_int, [_P, C.POINTER(ResNetXDesc), C.POINTER(ResNetXWeights), C.POINTER(_P)]),
+        "rva_resnetx_f16_plan_destroy": (None, [_P]),
+        "rva_resnetx_f16_plan_info": (C.c_int, [_P, i32p, i64p, i32p]),
+        "rva_resnetx_f16_plan_run": (C.c_int, [_P, _P, _P, C.c_int, _P, _P]),
+        "rva_resnetx_f16_plan_run_post": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+        "rva_resnetx_f16_plan_stage": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, i64p, _P]),
         "rva_jpeg_max_bytes": (C.c_int, [C.c_int, C.c_int]),
         "rva_jpeg_encode_bgr": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
         "rva_jpeg_status": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
@@ -377,6 +405,8 @@ EXPORTS = [
     "rva_jpeg_batch_create", "rva_jpeg_batch_destroy", "rva_jpeg_batch_encode", "rva_preview_nv12_batch",
     "rva_yolov5_plan_create", "rva_stem6_conv_f16", "rva_stem6_conv_f16_rows", "rva_conv_rows_through_pad", "rva_conv1x1_head5_f16",
     "rva_yolo11_plan_create", "rva_dwconv3x3_nhwc_f16", "rva_psa_attention_f16", "rva_yolov8_plan_step_desc",
+    "rva_resnetx_f16_plan_create", "rva_resnetx_f16_plan_destroy", "rva_resnetx_f16_plan_info", "rva_resnetx_f16_plan_run",
+    "rva_resnetx_f16_plan_run_post", "rva_resnetx_f16_plan_stage",
 ]
 
 

@@ -65,6 +65,17 @@ refused, as it does with ``half: false``; ``auto`` is PyTorch-ROCm:
     resnet, plan            engine "resnet-f32" (half has no effect)      half: true -> engine "resnet-f16"
     resnet, native          ValueError (no hand-written plan)             half: true -> engine "resnet-f16"
 
+Which ResNet the head builds is no key of its own either: it follows ``model_path`` (``classify.HipResNetDetector``).  An existing
+state dict of the torchvision family there (ResNet-18 / 34 with BasicBlocks, ResNet-50 / 101 / 152 with Bottlenecks, any 1..64
+blocks per stage; ``resnet_num_classes`` must agree with its ``fc.weight``) builds a ``classify.ResNet`` of what the file says;
+with no such file, a name that starts with ``resnet34`` / ``resnet50`` / ``resnet101`` / ``resnet152`` builds the seeded network
+of that depth; every other name keeps the seeded ``classify.ResNet18``.  Engine ``"resnet-f16"`` runs either module
+(``classify.ResNet`` on resnet_plan.FusedResNetF16); the fp32 plan exists for ``classify.ResNet18`` only:
+
+    module                  auto              plan / native, half: true, hip_resnet_fp16: true    plan otherwise
+    classify.ResNet18       PyTorch-ROCm      engine "resnet-f16" (FusedResNet18F16)              engine "resnet-f32"
+    classify.ResNet         PyTorch-ROCm      engine "resnet-f16" (FusedResNetF16)                ValueError at construction
+
 ``hip_box_rows`` picks where the fp16 YOLO plan (engine ``"fused"``: ``half: true``) keeps the four box
 rows of its head: ``"fp16"`` (default; what a reference YAML gets) = rows 0-3 of the fp16 head tensor, whose ulp is
 0.25 px between 256 and 512; ``"fp32"`` = the head kernels also write them as an fp32 side tensor and the post-process

@@ -77,6 +77,83 @@ inline void rva_res_info(const rva_res_topo &t, size_t workspace_bytes, int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Any ResNet of the torchvision family (rva_resnetx_f16_plan_* in rva_resnet_f16.hip): the stem, then four stages of blocks[s]
+// BasicBlocks or Bottlenecks (expansion 4, stride on the 3x3) of width 64 << s.  Stage codes: RVA_RESX_BLOCK0 + 4 b + slot.
+struct rva_resx_conv {               // one launch
+    int cin, cout, k, stride, H, W, Ho, Wo, epi;
+    int in, res, out;                // the stage codes it reads, adds as residual (-1: none) and writes
+    int wi;                          // its index in rva_resnetx_weights::convs
+    int in2, wi2, cin2, stride2, H2, W2;   // in2 >= 0: the shortcut convolution convs[wi2] runs inside this launch, on stage in2
+    size_t weights() const { return (size_t)cout * k * k * cin; }
+};
+
+struct rva_resx_topo {
+    int maps[5][2];                  // (h, w) of the pooled map and of the four stages
+    int c_feat = 0, n_blocks = 0, n_convs = 0, last_out = 0;
+    std::vector<rva_resx_conv> conv; // in launch order
+    std::vector<size_t> conv_weights;  // of convs[i], in the ABI's order
+    std::vector<int> conv_cout;
+    std::vector<int64_t> elems;      // elements of a stage per frame; 0: the plan has no such stage
+};
+
+inline rva_resx_topo rva_resx_topology(const rva_resnetx_desc &d)
+{
+    rva_resx_topo t;
+    int hc, wc;
+    rva_stem_maps(d.height, d.width, &hc, &wc, &t.maps[0][0], &t.maps[0][1]);
+    t.maps[1][0] = t.maps[0][0]; t.maps[1][1] = t.maps[0][1];
+    for (int s = 2; s <= 4; ++s) { t.maps[s][0] = rva_half_map(t.maps[s - 1][0], 3, 1); t.maps[s][1] = rva_half_map(t.maps[s - 1][1], 3, 1); }
+    const bool bott = d.bottleneck != 0, split = (d.flags & RVA_RESX_SPLIT_SHORTCUT) != 0;
+    const int exp = bott ? 4 : 1;
+    t.n_blocks = d.blocks[0] + d.blocks[1] + d.blocks[2] + d.blocks[3];
+    t.c_feat = RES_C_FEAT * exp;
+    t.elems.assign(RVA_RESX_BLOCK0 + 4 * (size_t)t.n_blocks, 0);
+    t.elems[RVA_RESX_POOLED] = (int64_t)t.maps[0][0] * t.maps[0][1] * RES_C_STEM;
+    t.elems[RVA_RESX_FEAT] = t.c_feat;
+    int x = RVA_RESX_POOLED, cin = RES_C_STEM, wi = 0, b = 0, hin = t.maps[0][0], win = t.maps[0][1];
+    auto weights = [&](int co, int k, int ci) { t.conv_weights.push_back((size_t)co * k * k * ci); t.conv_cout.push_back(co); };
+    for (int s = 0; s < 4; ++s)
+        for (int j = 0; j < d.blocks[s]; ++j, ++b) {
+            const int width = RES_C_STEM << s, cout = width * exp, stride = (j == 0 && s > 0) ? 2 : 1;
+            const bool shortcut = stride != 1 || cin != cout;
+            const int ho = t.maps[1 + s][0], wo = t.maps[1 + s][1];
+            const int base = RVA_RESX_BLOCK0 + 4 * b, mid1 = base, mid2 = base + 1, down = base + 2, out = base + 3;
+            const int n_own = bott ? 3 : 2, wi_short = wi + n_own;
+            int close_in, close_cin, close_k;
+            if (bott) {
+                t.elems[mid1] = (int64_t)hin * win * width;
+                t.elems[mid2] = (int64_t)ho * wo * width;
+                t.conv.push_back({cin, width, 1, 1, hin, win, hin, win, EPI_RELU, x, -1, mid1, wi, -1, -1, 0, 0, 0, 0});
+                t.conv.push_back({width, width, 3, stride, hin, win, ho, wo, EPI_RELU, mid1, -1, mid2, wi + 1, -1, -1, 0, 0, 0, 0});
+                weights(width, 1, cin); weights(width, 3, width); weights(cout, 1, width);
+                close_in = mid2; close_cin = width; close_k = 1;
+            } else {
+                t.elems[mid1] = (int64_t)ho * wo * width;
+                t.conv.push_back({cin, width, 3, stride, hin, win, ho, wo, EPI_RELU, x, -1, mid1, wi, -1, -1, 0, 0, 0, 0});
+                weights(width, 3, cin); weights(cout, 3, width);
+                close_in = mid1; close_cin = width; close_k = 3;
+            }
+            t.elems[out] = (int64_t)ho * wo * cout;
+            const int wi_close = wi + n_own - 1;
+            if (shortcut) weights(cout, 1, cin);
+            if (shortcut && split) {
+                t.elems[down] = t.elems[out];
+                t.conv.push_back({cin, cout, 1, stride, hin, win, ho, wo, EPI_BIAS, x, -1, down, wi_short, -1, -1, 0, 0, 0, 0});
+                t.conv.push_back({close_cin, cout, close_k, 1, ho, wo, ho, wo, EPI_RES_RELU, close_in, down, out, wi_close, -1, -1, 0, 0, 0, 0});
+            } else if (shortcut) {
+                t.conv.push_back({close_cin, cout, close_k, 1, ho, wo, ho, wo, EPI_RELU, close_in, -1, out, wi_close, x, wi_short, cin, stride, hin, win});
+            } else {
+                t.conv.push_back({close_cin, cout, close_k, 1, ho, wo, ho, wo, EPI_RES_RELU, close_in, x, out, wi_close, -1, -1, 0, 0, 0, 0});
+            }
+            wi += n_own + (shortcut ? 1 : 0);
+            x = out; cin = cout; hin = ho; win = wo;
+        }
+    t.n_convs = wi;
+    t.last_out = x;
+    return t;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // 3D-CNN (rva_clip3d.hip, rva_clip3d_f16.hip): conv1 + (1,2,2) pool, conv2 + (2,2,2) pool, conv3 + mean.  The pools floor.
 constexpr int C3D_C1 = 64, C3D_C2 = 128, C3D_C3 = 256, C3D_TAPS = 27;
 constexpr int C3D_PT = 8;                                  // pooled tile (PT x PT) of a K_conv1 block

@@ -35,6 +35,22 @@
 //   K_mean / K_head / K_post: k_res_mean (rva_resnet.hip) and the head and top-k kernels of rva_clip.hip, unchanged.
 //
 // Every stage keeps its own workspace buffer (rva_resnet_f16_plan_stage reads them).
+//
+// The second plan of this file, rva_resnetx_f16_plan, walks the same kernels over any ResNet of the torchvision family
+// (rva_resx_topology in rva_plan_topo.h: BasicBlocks or Bottlenecks, 1..64 blocks per stage) under the same numeric contract.  Two
+// pieces of device code are its own:
+//
+//   K_conv, DUAL   a block that has a shortcut convolution computes ReLU(conv_close(mid) + b_close + conv_short(x) + b_short): as a
+//            GEMM, one accumulator chain over [taps of conv_close | channels of x].  k_res16_conv<..., DUAL = true> runs, after the
+//            TAPS * Cin / KB steps of the closing convolution, Cin2 / KB further steps whose activation operand is x at (y * s2,
+//            x * s2) of its own H2 x W2 map (1x1, pad 0: always in range; create checks Ho == (H2 - 1) / s2 + 1) and whose weights
+//            come from the shortcut's [Cout][Cin2] array through the same LDS double buffer and swizzle.  Steps of 128 channels only
+//            where both Cin and Cin2 allow them; the 16-channel chunks run in the same order for either step, so tile and step still
+//            change no bit.  The bias is b_close + b_short (added in float64 by the packer, rounded once), the epilogue EPI_RELU.
+//            One launch, one fp16 rounding and the write and re-read of the `down` tensor fewer per such block.  A plan created with
+//            RVA_RESX_SPLIT_SHORTCUT launches the shortcut on its own (EPI_BIAS) and adds it as the residual (EPI_RES_RELU): the
+//            launches and bits of the ResNet-18 plan above.
+//   K_mean   k_resx_mean: k_res_mean's order (pixels in raster order from zero, then one division by P) for 512 or 2048 channels.
 #include "rva_mfma_f16.h"
 #include "rva_plan_topo.h"
 
@@ -50,6 +66,10 @@ struct Res16Args {
     void *out;                       // [n][Ho][Wo][Cout], fp16 or (out_f32) fp32
     int H, W, Ho, Wo, Cin, Cout, stride, epi, out_f32;
     long M;                          // n * Ho * Wo
+    // DUAL only: the block's shortcut convolution (1x1, pad 0) as further steps of the same sum
+    const _Float16 *in2;             // [n][H2][W2][Cin2], read at (y * stride2, x * stride2) of output pixel (y, x)
+    const _Float16 *w2;              // [Cout][Cin2]
+    int H2, W2, Cin2, stride2;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -57,7 +77,10 @@ struct Res16Args {
 // weights go through LDS once per block) and take consecutive runs of 32 MT pixels: block = 32 MT WM pixels x 32 NT channels.
 // A step is KB = 64 or 128 input channels (four or eight MFMA chunks); Cin is a multiple of KB and Cout of 32 NT: no K tail and no
 // channel tail.  The chunks run in the same order for either KB.
-template <int MT, int NT, int WM, int KS, int KB>
+// DUAL: after the TAPS * Cin / KB steps of the convolution itself, Cin2 / KB further steps of the block's shortcut convolution on
+// the block's input -- one accumulator chain over [taps of w | channels of in2], the weights of the further steps through the same
+// LDS double buffer and swizzle.  Cin2 is a multiple of KB too.
+template <int MT, int NT, int WM, int KS, int KB, bool DUAL = false>
 __global__ void __launch_bounds__(64 * WM) k_res16_conv(Res16Args a)
 {
     constexpr int TAPS = KS * KS, PAD = KS / 2, ROWS = 32 * NT, THREADS = 64 * WM;
@@ -70,10 +93,13 @@ __global__ void __launch_bounds__(64 * WM) k_res16_conv(Res16Args a)
     const int swz = (r >> SW) & SM;                          // of rows nt * 32 + r, for every nt
     const long m0 = ((long)blockIdx.x * WM + wave) * (32 * MT);
     const int n0 = blockIdx.y * ROWS;
-    const int nkb = a.Cin / KB, steps = TAPS * nkb;
+    const int nkb = a.Cin / KB, steps1 = TAPS * nkb;
+    int steps = steps1;
+    if constexpr (DUAL) steps += a.Cin2 / KB;
 
     int py[MT], px[MT];
     size_t pimg[MT];
+    [[maybe_unused]] size_t p2[MT];                          // DUAL: the pixel of in2 a column reads
     bool pv[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -83,6 +109,9 @@ __global__ void __launch_bounds__(64 * WM) k_res16_conv(Res16Args a)
         px[mt] = (int)(p % a.Wo) * a.stride - PAD;
         py[mt] = (int)((p / a.Wo) % a.Ho) * a.stride - PAD;
         pimg[mt] = (size_t)(p / ((long)a.Wo * a.Ho)) * a.H * a.W;
+        if constexpr (DUAL)
+            p2[mt] = ((size_t)(p / ((long)a.Wo * a.Ho)) * a.H2 + (size_t)((p / a.Wo) % a.Ho) * a.stride2) * a.W2 +
+                     (size_t)(p % a.Wo) * a.stride2;
     }
     const _Float16 *wblk = a.w + (size_t)n0 * TAPS * a.Cin;
 
@@ -113,6 +142,23 @@ __global__ void __launch_bounds__(64 * WM) k_res16_conv(Res16Args a)
         }
     };
 
+    // DUAL: step steps1 + k2 = channels k2 * KB .. of the shortcut convolution, always in range (1x1, pad 0)
+    [[maybe_unused]] auto load_w2 = [&](int k2) {
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int s = tid + THREADS * j, row = s / (KB / 8), q = s % (KB / 8);
+            st[j] = *reinterpret_cast<const f16x8 *>(a.w2 + (size_t)(n0 + row) * a.Cin2 + k2 * KB + q * 8);
+        }
+    };
+    [[maybe_unused]] auto load_x2 = [&](int k2, f16x8 (&f)[KB / 16][MT]) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const _Float16 *arow = a.in2 + (pv[mt] ? p2[mt] : 0) * a.Cin2 + k2 * KB + 8 * h;
+#pragma unroll
+            for (int c = 0; c < KB / 16; ++c) f[c][mt] = pv[mt] ? *reinterpret_cast<const f16x8 *>(arow + 16 * c) : f16x8{};
+        }
+    };
+
     f32x16 acc[MT][NT] = {};
     load_w(0, 0);
     load_x(0, 0, fx);
@@ -123,8 +169,18 @@ __global__ void __launch_bounds__(64 * WM) k_res16_conv(Res16Args a)
         const bool more = step + 1 < steps;
         if (++kb == nkb) { kb = 0; ++tap; }
         if (more) {
-            load_w(tap, kb);
-            load_x(tap, kb, fn);
+            if constexpr (DUAL) {
+                if (step + 1 >= steps1) {
+                    load_w2(step + 1 - steps1);
+                    load_x2(step + 1 - steps1, fn);
+                } else {
+                    load_w(tap, kb);
+                    load_x(tap, kb, fn);
+                }
+            } else {
+                load_w(tap, kb);
+                load_x(tap, kb, fn);
+            }
         }
         const _Float16 *wb = wl[step & 1];
 #pragma unroll
@@ -234,6 +290,38 @@ void launch_res16_conv(int v, dim3 g, hipStream_t st, const Res16Args &a)
     default: RES16_LAUNCH(1, 1, 1); break;
     }
 #undef RES16_LAUNCH
+}
+
+// The same table for a closing convolution that carries its block's shortcut convolution (DUAL): steps of 128 channels only where
+// both Cin and Cin2 allow them.
+template <int KS>
+void launch_res16_dual(int v, dim3 g, hipStream_t st, const Res16Args &a)
+{
+    const bool wide = a.Cin % 128 == 0 && a.Cin2 % 128 == 0;
+#define RES16_LAUNCH(MT, NT, WM) \
+    do { \
+        if (wide) k_res16_conv<MT, NT, WM, KS, 128, true><<<g, 64 * WM, 0, st>>>(a); \
+        else k_res16_conv<MT, NT, WM, KS, 64, true><<<g, 64 * WM, 0, st>>>(a); \
+    } while (0)
+    switch (v) {
+    case 0: k_res16_conv<2, 2, 4, KS, 64, true><<<g, 256, 0, st>>>(a); break;
+    case 1: RES16_LAUNCH(1, 2, 4); break;
+    case 2: RES16_LAUNCH(1, 2, 2); break;
+    case 3: RES16_LAUNCH(1, 1, 2); break;
+    default: RES16_LAUNCH(1, 1, 1); break;
+    }
+#undef RES16_LAUNCH
+}
+
+// K_mean for any channel count (a multiple of 256): per image and channel the pixels in raster order from zero, then one division
+// by P -- the order of k_res_mean (rva_resnet.hip), which stays the ResNet-18 plans' kernel.
+__global__ void __launch_bounds__(256) k_resx_mean(const float *x, int P, int C, float *feat)
+{
+    const int img = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    const float *xp = x + (size_t)img * P * C + c;
+    float s = 0.f;
+    for (int p = 0; p < P; ++p) s = s + xp[(size_t)p * C];
+    feat[(size_t)img * C + c] = s / (float)P;
 }
 
 // every stage is stored as fp16 but out7 (it feeds only the mean) and feat
@@ -381,6 +469,187 @@ int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *p, int stage, int n, void *ds
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
     if (stage < 0 || stage >= RES_STAGES) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: unknown stage %d", stage);
     return rva_clip_stage_copy(ctx, "rva_resnet_f16_plan_stage", stage, n, "frames", p->stage[stage], res16_esize(stage), "elements",
+                               n * p->t.elems[stage], 0, 0, 0, dst, dst_elems, n_elems, (hipStream_t)stream_);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// rva_resnetx_f16_plan: the same kernels walked over the topology of any ResNet of the family (rva_resx_topology).  A block's
+// shortcut convolution runs inside its closing convolution's launch (DUAL) unless the plan was created with
+// RVA_RESX_SPLIT_SHORTCUT, which gives the launches of the ResNet-18 plan above.
+struct rva_resnetx_f16_plan {
+    rva_ctx *ctx = nullptr;
+    rva_resnetx_desc d{};
+    int k = 0;                                             // min(top_k, classes)
+    rva_resx_topo t;
+    int tile_force = -1;                                   // RVA_RES16_TILE at creation
+    _Float16 *ws = nullptr;
+    float *bs = nullptr, *wh = nullptr, *bh = nullptr;
+    std::vector<_Float16 *> w;                             // of convs[i], in the ABI's order
+    std::vector<float *> b;
+    std::vector<void *> stage;                             // indexed by stage code; null: the plan has no such stage
+    size_t workspace_bytes = 0;
+    rva_dev_arena mem;
+    size_t esize(int s) const { return s == t.last_out || s == RVA_RESX_FEAT ? sizeof(float) : sizeof(_Float16); }
+};
+
+extern "C" {
+
+int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, const rva_resnetx_weights *wt, rva_resnetx_f16_plan **out)
+{
+    const char *who = "rva_resnetx_f16_plan_create";
+    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    const rva_resnetx_desc d = *desc;
+    bool ok = d.height >= 1 && d.width >= 1 && d.classes >= 1 && d.classes <= RVA_PLAN_MAX_CLASSES && d.top_k >= 1 && d.max_frames >= 1 &&
+              d.max_frames <= 65535 && (int64_t)d.height * d.width <= (1 << 26) && (d.bottleneck == 0 || d.bottleneck == 1) &&
+              (d.flags & ~RVA_RESX_SPLIT_SHORTCUT) == 0;
+    for (int s = 0; s < 4; ++s) ok = ok && d.blocks[s] >= 1 && d.blocks[s] <= 64;
+    if (!ok)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535, "
+                        "bottleneck 0 or 1, blocks 1..64 each, flags 0 or RVA_RESX_SPLIT_SHORTCUT)", who, RVA_PLAN_MAX_CLASSES);
+    rva_resx_topo t = rva_resx_topology(d);
+    if (d.n_convs != t.n_convs)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (n_convs %d, the topology has %d convolutions)", who, d.n_convs, t.n_convs);
+    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b && wt->convs;
+    for (int i = 0; all && i < t.n_convs; ++i) all = wt->convs[i].w && wt->convs[i].b;
+    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    for (const rva_resx_conv &c : t.conv) {                // what the kernel takes; holds for every net of the family
+        const bool dual = c.in2 >= 0;
+        if (c.cin % 64 || c.cout % 64 || (dual && (c.cin2 % 64 || c.Ho != (c.H2 - 1) / c.stride2 + 1 || c.Wo != (c.W2 - 1) / c.stride2 + 1)))
+            return rva_fail(ctx, RVA_ERR_ARG, "%s: a convolution of %d -> %d channels does not fit the kernel", who, c.cin, c.cout);
+    }
+    const size_t mf = (size_t)d.max_frames;
+    auto esize = [&](int s) { return s == t.last_out || s == RVA_RESX_FEAT ? sizeof(float) : sizeof(_Float16); };
+    // sizes first: the workspace must fit before anything is allocated
+    size_t act_bytes = 0;
+    size_t w_bytes = (size_t)RES_C_STEM * 192 * sizeof(_Float16) + RES_C_STEM * sizeof(float) + (size_t)d.classes * (t.c_feat + 1) * sizeof(float);
+    for (size_t s = 0; s < t.elems.size(); ++s) act_bytes += mf * t.elems[s] * esize((int)s);
+    for (int i = 0; i < t.n_convs; ++i) w_bytes += t.conv_weights[i] * sizeof(_Float16) + t.conv_cout[i] * sizeof(float);
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
+    int rc = rva_plan_fits(ctx, who, act_bytes + w_bytes, shape);
+    if (rc != RVA_OK) return rc;
+    auto *p = new rva_resnetx_f16_plan();
+    p->ctx = ctx;
+    p->d = d;
+    p->k = std::min(d.top_k, d.classes);
+    p->t = t;
+    p->workspace_bytes = act_bytes;
+    p->w.assign(t.n_convs, nullptr);
+    p->b.assign(t.n_convs, nullptr);
+    p->stage.assign(t.elems.size(), nullptr);
+    if (const char *e = getenv("RVA_RES16_TILE")) p->tile_force = std::max(-1, std::min(atoi(e), kNumTiles - 1));
+    auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
+    std::vector<_Float16> w16;
+    char bad[24] = "";
+    if (!rva_round_f16(wt->stem_w, (size_t)RES_C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
+    else { w16 = rva_clip16_stem_pack(w16); step(p->mem.upload(ctx, &p->ws, w16.data(), w16.size())); }
+    step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
+    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * t.c_feat));
+    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
+    for (size_t s = 0; s < t.elems.size(); ++s) {
+        if (!t.elems[s]) continue;
+        char *m = nullptr;
+        step(p->mem.alloc(ctx, &m, mf * t.elems[s] * esize((int)s)));
+        p->stage[s] = m;
+    }
+    for (int i = 0; i < t.n_convs && rc == RVA_OK; ++i) {
+        if (!rva_round_f16(wt->convs[i].w, t.conv_weights[i], w16)) {
+            snprintf(bad, sizeof bad, "conv[%d].w", i);
+            rc = RVA_ERR_ARG;
+            break;
+        }
+        step(p->mem.upload(ctx, &p->w[i], w16.data(), w16.size()));
+        step(p->mem.upload(ctx, &p->b[i], wt->convs[i].b, t.conv_cout[i]));
+    }
+    if (rc == RVA_OK) rc = rva_clip16_stem_prepare(ctx);
+    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, t.c_feat);
+    if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
+    if (rc != RVA_OK) {
+        rva_resnetx_f16_plan_destroy(p);
+        if (bad[0]) return rva_fail(ctx, RVA_ERR_ARG, "%s: a value of %s does not stay finite in fp16", who, bad);
+        return rc;
+    }
+    *out = p;
+    return RVA_OK;
+}
+
+void rva_resnetx_f16_plan_destroy(rva_resnetx_f16_plan *p)
+{
+    if (!p) return;
+    p->mem.release();
+    delete p;
+}
+
+int rva_resnetx_f16_plan_info(const rva_resnetx_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
+{
+    if (!p) return RVA_ERR_ARG;
+    if (maps)
+        for (int s = 0; s < 5; ++s) { maps[2 * s] = p->t.maps[s][0]; maps[2 * s + 1] = p->t.maps[s][1]; }
+    if (workspace_bytes) *workspace_bytes = (int64_t)p->workspace_bytes;
+    if (n_launches) *n_launches = 1 + (int32_t)p->t.conv.size() + 2;
+    return RVA_OK;
+}
+
+int rva_resnetx_f16_plan_run(rva_resnetx_f16_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+    const hipStream_t st = (hipStream_t)stream_;
+    void *const *buf = p->stage.data();
+    int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->ws, p->bs, (_Float16 *)buf[RVA_RESX_POOLED], p->d.height,
+                                    p->d.width, n, st);
+    if (rc != RVA_OK) return rc;
+    const int cus = rva_num_cus(ctx);
+    for (const rva_resx_conv &l : p->t.conv) {
+        Res16Args a{};
+        a.in = (const _Float16 *)buf[l.in]; a.w = p->w[l.wi]; a.bias = p->b[l.wi]; a.out = buf[l.out];
+        a.res = l.res >= 0 ? (const _Float16 *)buf[l.res] : nullptr;
+        a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
+        a.out_f32 = l.out == p->t.last_out;
+        a.M = (long)n * l.Ho * l.Wo;
+        const int v = p->tile_force >= 0 ? p->tile_force : res16_tile_for(a.M, l.cout, cus);
+        const dim3 g = res16_grid(v, a.M, l.cout);
+        if (l.in2 >= 0) {
+            a.in2 = (const _Float16 *)buf[l.in2]; a.w2 = p->w[l.wi2];
+            a.H2 = l.H2; a.W2 = l.W2; a.Cin2 = l.cin2; a.stride2 = l.stride2;
+            if (l.k == 3) launch_res16_dual<3>(v, g, st, a);
+            else launch_res16_dual<1>(v, g, st, a);
+        } else if (l.k == 3) {
+            launch_res16_conv<3>(v, g, st, a);
+        } else {
+            launch_res16_conv<1>(v, g, st, a);
+        }
+        RVA_HIP(ctx, hipGetLastError());
+    }
+    float *feat = (float *)buf[RVA_RESX_FEAT];
+    k_resx_mean<<<dim3(n, p->t.c_feat / 256), 256, 0, st>>>((const float *)buf[p->t.last_out], p->t.maps[4][0] * p->t.maps[4][1], p->t.c_feat, feat);
+    RVA_HIP(ctx, hipGetLastError());
+    return rva_clip_head_launch(ctx, feat, p->wh, p->bh, (float *)logits, p->t.c_feat, p->d.classes, n, st);
+}
+
+int rva_resnetx_f16_plan_run_post(rva_resnetx_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
+                                  void *cls, void *boxes, void *counts, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    return rva_clip_post_launch(p->ctx, "rva_resnetx_f16_plan_run_post", (const float *)logits, p->d.classes, p->k, rows, n_rows, max_det,
+                                (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
+}
+
+// Read-only tap on the workspace, as rva_resnet_f16_plan_stage; a stage code the plan has no buffer for is refused.
+int rva_resnetx_f16_plan_stage(rva_resnetx_f16_plan *p, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream_)
+{
+    if (!p) return RVA_ERR_ARG;
+    rva_ctx *ctx = p->ctx;
+    if (n < 1 || n > p->d.max_frames)
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+    if (stage < 0 || stage >= (int)p->stage.size() || !p->stage[stage])
+        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_stage: the plan has no stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_resnetx_f16_plan_stage", stage, n, "frames", p->stage[stage], p->esize(stage), "elements",
                                n * p->t.elems[stage], 0, 0, 0, dst, dst_elems, n_elems, (hipStream_t)stream_);
 }
 

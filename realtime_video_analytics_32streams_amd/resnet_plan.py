@@ -14,6 +14,11 @@ planar fp32 frames (what K1 writes) through a device table of frame indices.  Wh
 With ``half: true`` and the detector key ``hip_resnet_fp16: true`` (``hip_engine: plan`` or ``native``) the same head runs as the
 fp16 MFMA plan ``rva_resnet_f16_plan_*`` (``csrc/rva_resnet_f16.hip``, engine ``"resnet-f16"``): ``pack_resnet18(net, half=True)``
 and :class:`FusedResNet18F16`.
+
+Any other ResNet of the torchvision family (:class:`classify.ResNet`: BasicBlock or Bottleneck, 1..64 blocks per stage) runs as the
+same engine ``"resnet-f16"`` on ``rva_resnetx_f16_plan_*`` (the same file and kernels): :func:`pack_resnet`,
+:func:`resnet_any_flops` and :class:`FusedResNetF16`.  There a block's shortcut convolution runs inside the launch of the block's
+closing convolution (one fp32 sum over both), unless ``split_shortcut=True`` asks for the ResNet-18 plan's separate launches.
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .clip_plan import _ClipPlan, _fold, _fold_f16, conv_out
+from .clip_plan import _ClipPlan, _fold, _fold64, _fold_f16, _round_f16, conv_out
 
 ENGINE = "resnet-f32"        # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
 ENGINE_F16 = "resnet-f16"    # its fp16 MFMA form (half: true, hip_engine: plan / native, hip_resnet_fp16: true)
@@ -197,3 +202,185 @@ class FusedResNet18F16(FusedResNet18):
         """``ResNet18.forward`` of frames ``[B, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
         ``[B, classes]`` tensor."""
         return super().__call__(frames.to(torch.float16))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# any ResNet of the torchvision family (classify.ResNet) on rva_resnetx_f16_plan_*
+def resnet_blocks(bottleneck: bool, blocks) -> List[Dict[str, int]]:
+    """One dict per block over all stages, in order: ``s`` (stage 0..3), ``cin``, ``width``, ``cout``, ``stride``, ``shortcut``
+    (whether it has a shortcut convolution: stride != 1 or cin != cout)."""
+    out, cin, exp = [], 64, 4 if bottleneck else 1
+    for s, n in enumerate(blocks):
+        for j in range(int(n)):
+            width, stride = WIDTHS[s], 2 if (j == 0 and s > 0) else 1
+            cout = width * exp
+            out.append({"s": s, "cin": cin, "width": width, "cout": cout, "stride": stride, "shortcut": int(stride != 1 or cin != cout)})
+            cin = cout
+    return out
+
+
+def _is_resnet(net) -> bool:
+    from .classify import ResNet
+    return isinstance(net, ResNet)
+
+
+def pack_resnet(net, half: bool = True, fused: bool = True) -> Dict[str, np.ndarray]:
+    """The ``rva_resnetx_weights`` arrays of a :class:`classify.ResNet`, contiguous fp32, in the ABI's order: ``stem_w`` ``[64, 3,
+    7, 7]`` / ``stem_b``; ``c<i>_w`` ``[Cout, k*k, Cin]`` / ``c<i>_b`` block by block -- conv1, conv2[, conv3], then the block's
+    shortcut where it has one; ``head_w`` ``[classes, 512 * expansion]`` / ``head_b``.  Every BatchNorm is folded in float64 and
+    rounded once: the weights to fp16 with ``half`` (widened to fp32; a value beyond fp16 raises ``ValueError`` naming the array),
+    the biases to fp32.  ``fused`` (what a plan without ``split_shortcut`` reads): the bias of a block's closing convolution is
+    ``b_close + b_short``, added in float64 and rounded once to fp32; the shortcut keeps its own bias, which that plan does not read."""
+    if not _is_resnet(net):
+        raise ValueError(f"pack_resnet: not a classify.ResNet ({type(net).__name__}; classify.ResNet18 is packed by pack_resnet18)")
+    taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)  # noqa: E731  [co,ci,kk] -> [co,kk,ci]
+
+    def fold(conv, bn, what):
+        wf, bf = _fold64(conv, bn)
+        w = _round_f16(wf.numpy(), what, "pack_resnet") if half else wf.float().numpy()
+        return w, bf
+
+    out = {}
+    w, b = fold(net.conv1, net.bn1, "stem_w")
+    out["stem_w"], out["stem_b"] = w, b.float().numpy()
+    i = 0
+    for s in range(4):
+        for blk in getattr(net, f"layer{s + 1}"):
+            pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)] + ([(blk.conv3, blk.bn3)] if net.block == "bottleneck" else [])
+            if blk.downsample is not None:
+                pairs.append((blk.downsample[0], blk.downsample[1]))
+            first, biases = i, []
+            for conv, bn in pairs:
+                w, b = fold(conv, bn, f"c{i}_w")
+                out[f"c{i}_w"] = taps_last(w)
+                biases.append(b)
+                i += 1
+            if fused and blk.downsample is not None:
+                biases[-2] = biases[-2] + biases[-1]                   # float64; rounded once below
+            for k, b in enumerate(biases):
+                out[f"c{first + k}_b"] = b.float().numpy()
+    fc = net.fc
+    out["head_w"] = fc.weight.detach().float().cpu().numpy()
+    out["head_b"] = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
+    names = ["stem_w", "stem_b"] + [f"c{j}_{x}" for j in range(i) for x in "wb"] + ["head_w", "head_b"]
+    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in names}
+
+
+def resnet_any_flops(bottleneck: bool, blocks, h: int, w: int, classes: int = 1000, split_shortcut: bool = False) -> Dict[str, object]:
+    """FLOP (multiply + add = 2) and the bytes the fp16 plan must at least move per frame, from the shapes alone.  ``launches``:
+    the block convolutions in launch order as ``(name, flop, bytes, output pixels, K, Cout)`` with ``K`` the length of an output's
+    sum (taps x Cin, plus Cin2 where the launch carries the shortcut) and bytes = the input map(s) and weights read once and the
+    output written (fp16; the last block's output fp32), plus the residual a split or identity block reads.  ``stem``, ``head``,
+    ``frame`` (all FLOP) and ``workspace_bytes`` (what a frame keeps in the plan's workspace)."""
+    hc, wc = conv_out(h, 7, 2, 3), conv_out(w, 7, 2, 3)
+    maps = resnet_maps(h, w)
+    table = resnet_blocks(bottleneck, blocks)
+    launches, ws = [], 2 * maps[0][0] * maps[0][1] * 64 + 4 * table[-1]["cout"]
+    hin, win = maps[0]
+    for b, t in enumerate(table):
+        ho, wo = maps[1 + t["s"]]
+        px_in, px = hin * win, ho * wo
+        cin, width, cout, last = t["cin"], t["width"], t["cout"], b == len(table) - 1
+        e_out = 4 if last else 2
+
+        def conv(name, pin, ci, pout, co, k, extra_k=0, extra_bytes=0, e=2):
+            K = k * k * ci + extra_k
+            launches.append((name, 2.0 * pout * co * K, 2.0 * (pin * ci + K * co) + e * pout * co + extra_bytes, pout, K, co))
+            return e * pout * co
+
+        if bottleneck:
+            ws += conv(f"b{b}.mid1", px_in, cin, px_in, width, 1)
+            ws += conv(f"b{b}.mid2", px_in, width, px, width, 3)
+            close_k = 1
+        else:
+            ws += conv(f"b{b}.mid1", px_in, cin, px, width, 3)
+            close_k = 3
+        if t["shortcut"] and split_shortcut:
+            ws += conv(f"b{b}.down", px_in, cin, px, cout, 1)
+            ws += conv(f"b{b}.out", px, width, px, cout, close_k, extra_bytes=2.0 * px * cout, e=e_out)
+        elif t["shortcut"]:
+            ws += conv(f"b{b}.out", px, width, px, cout, close_k, extra_k=cin, extra_bytes=2.0 * px * cin, e=e_out)
+        else:
+            ws += conv(f"b{b}.out", px, width, px, cout, close_k, extra_bytes=2.0 * px * cout, e=e_out)
+        hin, win = ho, wo
+    stem, head = 2.0 * hc * wc * 64 * 147, 2.0 * table[-1]["cout"] * classes
+    return {"stem": stem, "launches": launches, "head": head, "frame": stem + sum(c[1] for c in launches) + head,
+            "workspace_bytes": ws, "frame_bytes": 2.0 * 3 * h * w}
+
+
+class FusedResNetF16(_ClipPlan):
+    """One ``rva_resnetx_f16_plan``: the network of ``net`` (a :class:`classify.ResNet` of any depth) for ``half: true`` with the
+    numeric contract and the surface of :class:`FusedResNet18F16` (``run`` on fp16 frames, ``post``, ``stage``, ``__call__``,
+    ``maps``, ``workspace_bytes``, ``n_launches``, ``classes``, ``logits``).  A block's shortcut convolution runs inside the launch
+    of its closing convolution; ``split_shortcut=True`` launches it on its own, as the ResNet-18 plan does.  Stages: ``"pooled"``,
+    ``"b<k>.mid1"``, ``"b<k>.mid2"`` (Bottleneck), ``"b<k>.down"`` (split plans, blocks with a shortcut convolution),
+    ``"b<k>.out"`` and ``"feat"``, ``k`` counting the blocks over all stages; fp16 but the last block's ``out`` and ``feat``."""
+
+    ABI = "rva_resnetx_f16_plan"
+    RING_DTYPE = torch.float16
+
+    def __init__(self, net, hw: Tuple[int, int], max_frames: int, top_k: int = 5, split_shortcut: bool = False,
+                 ctx: Optional[N.Context] = None, device: Optional[torch.device] = None):
+        self.split_shortcut = bool(split_shortcut)
+        packed = pack_resnet(net, half=True, fused=not self.split_shortcut)   # refusals come before the device is touched
+        self.bottleneck, self.blocks = net.block == "bottleneck", tuple(net.blocks)
+        self.table = resnet_blocks(self.bottleneck, self.blocks)
+        self.c_feat = self.table[-1]["cout"]
+        self._open(hw, 1, max_frames, net.fc.out_features, ctx, device)
+        self.top_k = int(top_k)
+        self.k = min(self.top_k, self.classes)
+        n_convs = (len(packed) - 4) // 2
+        fp = C.POINTER(C.c_float)
+        convs = (N.ResNetConv * n_convs)(*[N.ResNetConv(packed[f"c{i}_w"].ctypes.data_as(fp), packed[f"c{i}_b"].ctypes.data_as(fp))
+                                           for i in range(n_convs)])
+        wt = N.ResNetXWeights(packed["stem_w"].ctypes.data_as(fp), packed["stem_b"].ctypes.data_as(fp), convs,
+                              packed["head_w"].ctypes.data_as(fp), packed["head_b"].ctypes.data_as(fp))
+        desc = N.ResNetXDesc(self.H, self.W, self.classes, self.top_k, self.max_clips, int(self.bottleneck), (C.c_int32 * 4)(*self.blocks),
+                             n_convs, N.RVA_RESX_SPLIT_SHORTCUT if self.split_shortcut else 0)
+        h = C.c_void_p()
+        with torch.cuda.device(self.dev):
+            self.ctx.check(self._fn("create")(self.ctx.handle, C.byref(desc), C.byref(wt), C.byref(h)), f"{self.ABI}_create")
+        self.handle = h
+        self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
+        maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
+        self.ctx.check(self._fn("info")(self.handle, maps, C.byref(ws), C.byref(nl)), f"{self.ABI}_info")
+        self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
+        self.workspace_bytes, self.n_launches = ws.value, nl.value
+        self._stages = self._stage_table()
+        last = f"b{len(self.table) - 1}.out"
+        self.TAP_DTYPES = {n: torch.float16 for n in self._stages if n not in (last, "feat")}
+
+    def _stage_table(self) -> Dict[str, tuple]:
+        """name -> (stage code, per-frame shape) of every stage this plan has."""
+        out = {"pooled": (N.RVA_RESX_POOLED, (*self.maps[0], 64))}
+        hw_in = self.maps[0]
+        for b, t in enumerate(self.table):
+            hw_out, base = self.maps[1 + t["s"]], N.RVA_RESX_BLOCK0 + 4 * b
+            out[f"b{b}.mid1"] = (base, (*(hw_in if self.bottleneck else hw_out), t["width"]))
+            if self.bottleneck:
+                out[f"b{b}.mid2"] = (base + 1, (*hw_out, t["width"]))
+            if t["shortcut"] and self.split_shortcut:
+                out[f"b{b}.down"] = (base + 2, (*hw_out, t["cout"]))
+            out[f"b{b}.out"] = (base + 3, (*hw_out, t["cout"]))
+            hw_in = hw_out
+        out["feat"] = (N.RVA_RESX_FEAT, (self.c_feat,))
+        return out
+
+    @property
+    def stage_names(self) -> Tuple[str, ...]:
+        """Every stage of this plan in launch order (``feat`` last)."""
+        return tuple(self._stages)
+
+    def stage(self, name: str, n: int) -> torch.Tensor:
+        """A copy of one intermediate tensor of the last :meth:`run` (of at least ``n`` frames, on the current stream), NHWC, as
+        ``rva_resnetx_f16_plan_stage`` documents (include/rva.h).  A read-only tap for tests and tools."""
+        n = int(n)
+        return self._tap({k: (code, (n, *shape)) for k, (code, shape) in self._stages.items()}, name, n)
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """``ResNet.forward`` of frames ``[B, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
+        ``[B, classes]`` tensor."""
+        b = int(frames.shape[0])
+        if tuple(frames.shape[1:]) != (3, self.H, self.W):
+            raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
+        return self._run_frames(frames.to(torch.float16).contiguous(), b)
