@@ -941,7 +941,8 @@ int rva_resnet_plan_stage(rva_resnet_plan *plan, int stage, int n, void *dst, in
 /* ------------------------------------------------------------------------------------------------
  * The fp16 ResNet-18 plan (csrc/rva_resnet_f16.hip): the network of rva_resnet_plan for `half: true` -- fp16 frames, fp16
  * convolution weights and fp16 stored activations on v_mfma_f32_32x32x16_f16, every sum in fp32.  It shares rva_resnet_desc,
- * rva_resnet_weights and enum rva_resnet_stage.
+ * rva_resnet_weights and enum rva_resnet_stage.  These entries are a front door of the one fp16 ResNet plan (rva_resnetx_f16_plan
+ * below): BasicBlocks 2, 2, 2, 2 with RVA_RESX_SPLIT_SHORTCUT, conv[19] passed on as `convs`, every stage code translated.
  *
  * rva_resnet_f16_plan_create: `weights` = fp32 host arrays in the layouts of rva_resnet_plan_create (BatchNorm folded by the
  *   caller).  stem_w and the 19 conv[i].w are rounded ONCE to fp16, round to nearest even; RVA_ERR_ARG, naming the array
@@ -979,7 +980,8 @@ int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *plan, int stage, int n, void 
  * expansion 4 and the stride on the 3x3: ResNet-50 / 101 / 152) --, the mean over H,W and Linear(512 * expansion -> classes).  The
  * first block of stages 1..3 has stride 2.  A block whose stride is not 1 or whose input width differs from its output width has a
  * 1x1 shortcut convolution (the first block of stage 0 of a Bottleneck net has one with stride 1).  Numeric contract, kernels and
- * tile table are those of rva_resnet_f16_plan.
+ * tile table are those of rva_resnet_f16_plan: both sets of entries run the same plan code over one description of the network,
+ * which the fp32 rva_resnet_plan walks too.
  *
  * rva_resnetx_f16_plan_create: weights as for rva_resnet_f16_plan_create; `convs` holds desc.n_convs convolutions, block by block
  *   in the order conv1, conv2[, conv3], then the block's shortcut where it has one, each [Cout][k*k][Cin] with bias [Cout];

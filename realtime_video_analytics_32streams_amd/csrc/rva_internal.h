@@ -188,8 +188,9 @@ int rva_clip16_stem_prepare(rva_ctx *ctx);
 int rva_clip16_stem_launch(rva_ctx *ctx, const _Float16 *frames, const int32_t *frame_index, const _Float16 *w1, const float *b1,
                            _Float16 *pooled, int H, int W, int n_frames, hipStream_t st);
 
-// K_mean of the ResNet plans (rva_resnet.hip): feat[img][c] = (the image's P pixels of x [n][P][512] in raster order, from zero) / P
-int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st);
+// K_mean of the ResNet plans (rva_resnet.hip): feat[img][c] = (the image's P pixels of x [n][P][C] in raster order, from zero) / P;
+// C a multiple of 256
+int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, int C, float *feat, int n, hipStream_t st);
 
 // The tail of every *_plan_stage tap: reports `count` through n_elems, and if dst is given checks its size and copies `count`
 // elements of `esize` bytes device to device on `st` -- as `rows` rows of row_elems out of a pitch of pitch_elems if rows > 0,

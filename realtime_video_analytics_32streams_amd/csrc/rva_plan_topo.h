@@ -6,80 +6,15 @@
 #include "rva_internal.h"
 
 // ---------------------------------------------------------------------------------------------------
-// ResNet-18 (rva_resnet.hip, rva_resnet_f16.hip): the stem, then 8 BasicBlocks of widths 64, 64, 128, 128, 256, 256, 512, 512; the
-// first block of the 128 / 256 / 512 stages has stride 2 and a 1x1 stride-2 shortcut convolution.
-constexpr int RES_C_STEM = 64, RES_C_FEAT = 512, RES_BLOCKS = 8, RES_CONVS = 19, RES_STAGES = RVA_RESNET_STAGE_FEAT + 1;
+// ResNet (rva_resnet.hip: fp32 ResNet-18; rva_resnet_f16.hip: fp16, any depth): ONE topology, that of any ResNet of the torchvision
+// family -- the stem, then four stages of blocks[s] BasicBlocks or Bottlenecks (expansion 4, stride on the 3x3) of width 64 << s; a
+// block whose stride is not 1 or whose input width differs from its output width has a 1x1 shortcut convolution.  Stage codes:
+// RVA_RESX_POOLED, RVA_RESX_FEAT, RVA_RESX_BLOCK0 + 4 b + slot.  ResNet-18 is a case of it (rva_res18_desc, rva_res18_stage below).
+constexpr int RES_C_STEM = 64, RES_C_FEAT = 512;
+constexpr int RES_CONVS = 19;                                   // of rva_resnet_weights::conv (ResNet-18)
 constexpr int EPI_RELU = 0, EPI_BIAS = 1, EPI_RES_RELU = 2;     // max(acc + b, 0) | acc + b | max((acc + b) + res, 0)
 
-struct rva_res_conv {                // one block convolution
-    int cin, cout, k, stride, H, W, Ho, Wo, epi;
-    int in, res, out;                // the RVA_RESNET_STAGE_* it reads, adds as residual (-1: none) and writes
-    int wi;                          // its index in rva_resnet_weights::conv (the ABI's order of a block: conv1, conv2, shortcut)
-    size_t weights() const { return (size_t)cout * k * k * cin; }
-};
-
-struct rva_res_topo {
-    int maps[5][2];                  // (h, w) of the pooled map and of the four stages
-    rva_res_conv conv[RES_CONVS];    // in launch order: per block conv1, [shortcut], conv2
-    int launch_of[RES_CONVS];        // conv[launch_of[i]].wi == i
-    int64_t elems[RES_STAGES];       // elements of a stage per frame
-};
-
-inline rva_res_topo rva_res_topology(int height, int width)
-{
-    rva_res_topo t{};
-    int hc, wc;
-    rva_stem_maps(height, width, &hc, &wc, &t.maps[0][0], &t.maps[0][1]);
-    t.maps[1][0] = t.maps[0][0]; t.maps[1][1] = t.maps[0][1];
-    for (int s = 2; s <= 4; ++s) { t.maps[s][0] = rva_half_map(t.maps[s - 1][0], 3, 1); t.maps[s][1] = rva_half_map(t.maps[s - 1][1], 3, 1); }
-    t.elems[RVA_RESNET_STAGE_POOLED] = (int64_t)t.maps[0][0] * t.maps[0][1] * RES_C_STEM;
-    t.elems[RVA_RESNET_STAGE_FEAT] = RES_C_FEAT;
-    int x = RVA_RESNET_STAGE_POOLED, wi = 0, n = 0, hin = t.maps[0][0], win = t.maps[0][1];
-    for (int b = 0; b < RES_BLOCKS; ++b) {
-        const int s = 1 + b / 2, c = RES_C_STEM << (s - 1), cin = (b % 2 == 0 && s > 1) ? c / 2 : c;
-        const bool shortcut = cin != c;
-        const int ho = t.maps[s][0], wo = t.maps[s][1];
-        const int mid = RVA_RESNET_STAGE_MID0 + b, out = RVA_RESNET_STAGE_OUT0 + b;
-        const int down = shortcut ? RVA_RESNET_STAGE_DOWN2 + (b - 2) / 2 : -1;
-        t.elems[mid] = t.elems[out] = (int64_t)ho * wo * c;
-        if (shortcut) t.elems[down] = t.elems[mid];
-        t.conv[n++] = {cin, c, 3, shortcut ? 2 : 1, hin, win, ho, wo, EPI_RELU, x, -1, mid, wi};
-        if (shortcut) t.conv[n++] = {cin, c, 1, 2, hin, win, ho, wo, EPI_BIAS, x, -1, down, wi + 2};
-        t.conv[n++] = {c, c, 3, 1, ho, wo, ho, wo, EPI_RES_RELU, mid, shortcut ? down : x, out, wi + 1};
-        wi += shortcut ? 3 : 2;
-        x = out; hin = ho; win = wo;
-    }
-    for (int i = 0; i < RES_CONVS; ++i) t.launch_of[t.conv[i].wi] = i;
-    return t;
-}
-
-// the argument checks of a create, under the entry's name; clears *out
-inline int rva_res_check_args(rva_ctx *ctx, const char *who, const rva_resnet_desc *d, const rva_resnet_weights *wt, void **out)
-{
-    if (!ctx || !d || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
-    *out = nullptr;
-    if (d->height < 1 || d->width < 1 || d->classes < 1 || d->classes > RVA_PLAN_MAX_CLASSES || d->top_k < 1 || d->max_frames < 1 ||
-        d->max_frames > 65535 || (int64_t)d->height * d->width > (1 << 26))
-        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535)", who,
-                        RVA_PLAN_MAX_CLASSES);
-    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
-    for (int i = 0; i < RES_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
-    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
-    return RVA_OK;
-}
-
-inline void rva_res_info(const rva_res_topo &t, size_t workspace_bytes, int32_t *maps, int64_t *ws, int32_t *n_launches)
-{
-    if (maps)
-        for (int s = 0; s < 5; ++s) { maps[2 * s] = t.maps[s][0]; maps[2 * s + 1] = t.maps[s][1]; }
-    if (ws) *ws = (int64_t)workspace_bytes;
-    if (n_launches) *n_launches = 1 + RES_CONVS + 2;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Any ResNet of the torchvision family (rva_resnetx_f16_plan_* in rva_resnet_f16.hip): the stem, then four stages of blocks[s]
-// BasicBlocks or Bottlenecks (expansion 4, stride on the 3x3) of width 64 << s.  Stage codes: RVA_RESX_BLOCK0 + 4 b + slot.
-struct rva_resx_conv {               // one launch
+struct rva_res_conv {                // one launch
     int cin, cout, k, stride, H, W, Ho, Wo, epi;
     int in, res, out;                // the stage codes it reads, adds as residual (-1: none) and writes
     int wi;                          // its index in rva_resnetx_weights::convs
@@ -87,18 +22,18 @@ struct rva_resx_conv {               // one launch
     size_t weights() const { return (size_t)cout * k * k * cin; }
 };
 
-struct rva_resx_topo {
+struct rva_res_topo {
     int maps[5][2];                  // (h, w) of the pooled map and of the four stages
     int c_feat = 0, n_blocks = 0, n_convs = 0, last_out = 0;
-    std::vector<rva_resx_conv> conv; // in launch order
+    std::vector<rva_res_conv> conv;  // in launch order
     std::vector<size_t> conv_weights;  // of convs[i], in the ABI's order
     std::vector<int> conv_cout;
     std::vector<int64_t> elems;      // elements of a stage per frame; 0: the plan has no such stage
 };
 
-inline rva_resx_topo rva_resx_topology(const rva_resnetx_desc &d)
+inline rva_res_topo rva_res_topology(const rva_resnetx_desc &d)
 {
-    rva_resx_topo t;
+    rva_res_topo t;
     int hc, wc;
     rva_stem_maps(d.height, d.width, &hc, &wc, &t.maps[0][0], &t.maps[0][1]);
     t.maps[1][0] = t.maps[0][0]; t.maps[1][1] = t.maps[0][1];
@@ -151,6 +86,48 @@ inline rva_resx_topo rva_resx_topology(const rva_resnetx_desc &d)
     t.n_convs = wi;
     t.last_out = x;
     return t;
+}
+
+inline void rva_res_info(const rva_res_topo &t, size_t workspace_bytes, int32_t *maps, int64_t *ws, int32_t *n_launches)
+{
+    if (maps)
+        for (int s = 0; s < 5; ++s) { maps[2 * s] = t.maps[s][0]; maps[2 * s + 1] = t.maps[s][1]; }
+    if (ws) *ws = (int64_t)workspace_bytes;
+    if (n_launches) *n_launches = 1 + (int32_t)t.conv.size() + 2;
+}
+
+// ResNet-18 (rva_resnet_plan_*, rva_resnet_f16_plan_*) as a case of it: BasicBlocks 2, 2, 2, 2 with the shortcut convolutions as
+// launches of their own.  rva_resnet_weights::conv is already in the order of `convs` (per block conv1, conv2, shortcut).
+inline rva_resnetx_desc rva_res18_desc(const rva_resnet_desc &d)
+{
+    return {d.height, d.width, d.classes, d.top_k, d.max_frames, 0, {2, 2, 2, 2}, RES_CONVS, RVA_RESX_SPLIT_SHORTCUT};
+}
+
+// the argument checks of a ResNet-18 create, under the entry's name; clears *out
+inline int rva_res_check_args(rva_ctx *ctx, const char *who, const rva_resnet_desc *d, const rva_resnet_weights *wt, void **out)
+{
+    if (!ctx || !d || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    if (d->height < 1 || d->width < 1 || d->classes < 1 || d->classes > RVA_PLAN_MAX_CLASSES || d->top_k < 1 || d->max_frames < 1 ||
+        d->max_frames > 65535 || (int64_t)d->height * d->width > (1 << 26))
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535)", who,
+                        RVA_PLAN_MAX_CLASSES);
+    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b;
+    for (int i = 0; i < RES_CONVS; ++i) all = all && wt->conv[i].w && wt->conv[i].b;
+    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    return RVA_OK;
+}
+
+// an RVA_RESNET_STAGE_* code as the stage code of that topology; -1: no such code
+inline int rva_res18_stage(int stage)
+{
+    const auto slot = [](int b, int s) { return RVA_RESX_BLOCK0 + 4 * b + s; };
+    if (stage == RVA_RESNET_STAGE_POOLED) return RVA_RESX_POOLED;
+    if (stage == RVA_RESNET_STAGE_FEAT) return RVA_RESX_FEAT;
+    if (stage >= RVA_RESNET_STAGE_MID0 && stage < RVA_RESNET_STAGE_DOWN2) return slot(stage - RVA_RESNET_STAGE_MID0, 0);
+    if (stage >= RVA_RESNET_STAGE_DOWN2 && stage < RVA_RESNET_STAGE_OUT0) return slot(2 + 2 * (stage - RVA_RESNET_STAGE_DOWN2), 2);
+    if (stage >= RVA_RESNET_STAGE_OUT0 && stage < RVA_RESNET_STAGE_FEAT) return slot(stage - RVA_RESNET_STAGE_OUT0, 3);
+    return -1;
 }
 
 // ---------------------------------------------------------------------------------------------------

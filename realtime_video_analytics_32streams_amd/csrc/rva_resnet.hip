@@ -16,17 +16,17 @@
 //            rva_mfma_f32.h (which defines the reduction order: what rva_conv2d_nhwc_f32_v runs on the same input).  Rows = output
 //            pixels of the whole batch, columns = output channels.  Per block: mid = ReLU(conv1(x) + b), [down = conv_d(x) + b],
 //            out = ReLU((conv2(mid) + b) + (down or x)).
-//   K_mean   k_res_mean: per image and channel the pixels in raster order from zero, then one division by h*w.
+//   K_mean   k_res_mean through rva_res_mean_launch (shared with rva_resnet_f16.hip): per image and channel the pixels in raster
+//            order from zero, then one division by h*w.
 //   K_head   Linear: the head kernel of rva_clip.hip (one thread per class, k in order), hidden = 512.
 //   K_post   (rva_resnet_plan_run_post) the top-k kernel of rva_clip.hip with the descriptor's k.
 //
-// Every stage keeps its own workspace buffer (rva_resnet_plan_stage reads them).
+// Every stage keeps its own workspace buffer (rva_resnet_plan_stage reads them).  The launches come from the one ResNet topology
+// of rva_plan_topo.h with the ResNet-18 descriptor (rva_res18_desc); the tap translates its stage code (rva_res18_stage).
 #include "rva_mfma_f32.h"
 #include "rva_plan_topo.h"
 
 namespace {
-
-constexpr int C_FEAT = RES_C_FEAT;
 
 struct ResConvArgs {
     const float *in;                 // [n][H][W][Cin]
@@ -146,21 +146,22 @@ void launch_res_conv(int v, dim3 g, hipStream_t st, const ResConvArgs &a)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// K_mean.  Block = image, thread = channel (512): feat[img][c] = (sum of the image's P pixels in raster order, from zero) / P.
-__global__ void __launch_bounds__(C_FEAT) k_res_mean(const float *x, int P, float *feat)
+// K_mean for any channel count that is a multiple of 256.  Block = (image, 256 channels), thread = channel:
+// feat[img][c] = (sum of the image's P pixels in raster order, from zero) / P.
+__global__ void __launch_bounds__(256) k_res_mean(const float *x, int P, int C, float *feat)
 {
-    const int img = blockIdx.x, c = threadIdx.x;
-    const float *xp = x + (size_t)img * P * C_FEAT + c;
+    const int img = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+    const float *xp = x + (size_t)img * P * C + c;
     float s = 0.f;
-    for (int p = 0; p < P; ++p) s = s + xp[(size_t)p * C_FEAT];
-    feat[(size_t)img * C_FEAT + c] = s / (float)P;
+    for (int p = 0; p < P; ++p) s = s + xp[(size_t)p * C];
+    feat[(size_t)img * C + c] = s / (float)P;
 }
 
 }  // namespace
 
-int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, float *feat, int n, hipStream_t st)
+int rva_res_mean_launch(rva_ctx *ctx, const float *x, int P, int C, float *feat, int n, hipStream_t st)
 {
-    k_res_mean<<<n, C_FEAT, 0, st>>>(x, P, feat);
+    k_res_mean<<<dim3(n, C / 256), 256, 0, st>>>(x, P, C, feat);
     RVA_HIP(ctx, hipGetLastError());
     return RVA_OK;
 }
@@ -169,10 +170,10 @@ struct rva_resnet_plan {
     rva_ctx *ctx = nullptr;
     rva_resnet_desc d{};
     int k = 0;                                             // min(top_k, classes)
-    rva_res_topo t{};
+    rva_res_topo t;                                        // of rva_res18_desc(d)
     float *ws = nullptr, *bs = nullptr, *wh = nullptr, *bh = nullptr;
-    float *w[RES_CONVS] = {}, *b[RES_CONVS] = {};          // of t.conv[i], in launch order
-    float *stage[RES_STAGES] = {};                         // every stage keeps its own buffer, indexed by RVA_RESNET_STAGE_*
+    float *w[RES_CONVS] = {}, *b[RES_CONVS] = {};          // of rva_resnet_weights::conv[i]
+    std::vector<float *> stage;                            // every stage keeps its own buffer, indexed by the topology's stage code
     size_t workspace_bytes = 0;
     rva_dev_arena mem;
 };
@@ -184,12 +185,12 @@ int rva_resnet_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_
     int rc = rva_res_check_args(ctx, "rva_resnet_plan_create", desc, wt, (void **)out);
     if (rc != RVA_OK) return rc;
     const rva_resnet_desc d = *desc;
-    const rva_res_topo t = rva_res_topology(d.height, d.width);
+    const rva_res_topo t = rva_res_topology(rva_res18_desc(d));
     const size_t mf = (size_t)d.max_frames;
     // sizes first: the workspace must fit before anything is allocated
     size_t n_act = 0, n_w = (size_t)RES_C_STEM * 147 + RES_C_STEM + (size_t)d.classes * (RES_C_FEAT + 1);
     for (int64_t e : t.elems) n_act += mf * e;
-    for (const rva_res_conv &c : t.conv) n_w += c.weights() + c.cout;
+    for (int i = 0; i < RES_CONVS; ++i) n_w += t.conv_weights[i] + t.conv_cout[i];
     char shape[64];
     snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
     rc = rva_plan_fits(ctx, "rva_resnet_plan_create", (n_act + n_w) * sizeof(float), shape);
@@ -200,16 +201,17 @@ int rva_resnet_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_
     p->k = std::min(d.top_k, d.classes);
     p->t = t;
     p->workspace_bytes = n_act * sizeof(float);
+    p->stage.assign(t.elems.size(), nullptr);
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
     step(p->mem.upload(ctx, &p->ws, wt->stem_w, (size_t)RES_C_STEM * 147));
     step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
     step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * RES_C_FEAT));
     step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    for (int s = 0; s < RES_STAGES; ++s) step(p->mem.alloc(ctx, &p->stage[s], mf * t.elems[s]));
-    for (int i = 0; i < RES_CONVS; ++i) {                  // in the ABI's weight order
-        const int n = t.launch_of[i];
-        step(p->mem.upload(ctx, &p->w[n], wt->conv[i].w, t.conv[n].weights()));
-        step(p->mem.upload(ctx, &p->b[n], wt->conv[i].b, t.conv[n].cout));
+    for (size_t s = 0; s < t.elems.size(); ++s)
+        if (t.elems[s]) step(p->mem.alloc(ctx, &p->stage[s], mf * t.elems[s]));
+    for (int i = 0; i < RES_CONVS; ++i) {
+        step(p->mem.upload(ctx, &p->w[i], wt->conv[i].w, t.conv_weights[i]));
+        step(p->mem.upload(ctx, &p->b[i], wt->conv[i].b, t.conv_cout[i]));
     }
     if (rc == RVA_OK) rc = rva_clip_stem_prepare(ctx);
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, RES_C_FEAT);
@@ -243,15 +245,13 @@ int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *f
     if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
     const hipStream_t st = (hipStream_t)stream_;
-    float *const *buf = p->stage;
-    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->ws, p->bs, buf[RVA_RESNET_STAGE_POOLED], p->d.height,
-                                  p->d.width, n, st);
+    float *const *buf = p->stage.data();
+    int rc = rva_clip_stem_launch(ctx, (const float *)frames, frame_index, p->ws, p->bs, buf[RVA_RESX_POOLED], p->d.height, p->d.width, n, st);
     if (rc != RVA_OK) return rc;
     const int cus = rva_num_cus(ctx);
-    for (int i = 0; i < RES_CONVS; ++i) {
-        const rva_res_conv &l = p->t.conv[i];
+    for (const rva_res_conv &l : p->t.conv) {
         ResConvArgs a{};
-        a.in = buf[l.in]; a.w = p->w[i]; a.bias = p->b[i]; a.res = l.res >= 0 ? buf[l.res] : nullptr; a.out = buf[l.out];
+        a.in = buf[l.in]; a.w = p->w[l.wi]; a.bias = p->b[l.wi]; a.res = l.res >= 0 ? buf[l.res] : nullptr; a.out = buf[l.out];
         a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
         a.M = (long)n * l.Ho * l.Wo;
         const int v = res_tile_for(a.M, l.cout, cus);
@@ -260,9 +260,9 @@ int rva_resnet_plan_run(rva_resnet_plan *p, const void *frames, const int32_t *f
         else launch_res_conv<1>(v, g, st, a);
         RVA_HIP(ctx, hipGetLastError());
     }
-    rc = rva_res_mean_launch(ctx, buf[RVA_RESNET_STAGE_OUT0 + RES_BLOCKS - 1], p->t.maps[4][0] * p->t.maps[4][1], buf[RVA_RESNET_STAGE_FEAT], n, st);
+    rc = rva_res_mean_launch(ctx, buf[p->t.last_out], p->t.maps[4][0] * p->t.maps[4][1], RES_C_FEAT, buf[RVA_RESX_FEAT], n, st);
     if (rc != RVA_OK) return rc;
-    return rva_clip_head_launch(ctx, buf[RVA_RESNET_STAGE_FEAT], p->wh, p->bh, (float *)logits, RES_C_FEAT, p->d.classes, n, st);
+    return rva_clip_head_launch(ctx, buf[RVA_RESX_FEAT], p->wh, p->bh, (float *)logits, RES_C_FEAT, p->d.classes, n, st);
 }
 
 int rva_resnet_plan_run_post(rva_resnet_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
@@ -281,9 +281,11 @@ int rva_resnet_plan_stage(rva_resnet_plan *p, int stage, int n, void *dst, int64
     rva_ctx *ctx = p->ctx;
     if (n < 1 || n > p->d.max_frames)
         return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
-    if (stage < 0 || stage >= RES_STAGES) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: unknown stage %d", stage);
-    return rva_clip_stage_copy(ctx, "rva_resnet_plan_stage", stage, n, "clips", p->stage[stage], sizeof(float), "floats",
-                               n * p->t.elems[stage], 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
+    const int code = rva_res18_stage(stage);
+    if (code < 0) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_plan_stage: unknown stage %d", stage);
+    return rva_clip_stage_copy(ctx, "rva_resnet_plan_stage", stage, n, "clips", p->stage[code], sizeof(float), "floats",
+                               n * p->t.elems[code], 0, 0, 0, dst, dst_floats, n_floats, (hipStream_t)stream_);
 }
 
 }  // extern "C"
+

@@ -1,6 +1,10 @@
-// The ResNet-18 classifier of rva_resnet.hip for `half: true` (engine "resnet-f16"): the same network, launches and taps, with
-// fp16 frames, fp16 convolution weights and fp16 stored activations, and every sum in fp32.  The numeric contract is that of
-// clip-f16 / clip3d-f16:
+// The ResNet classifiers for `half: true` (engine "resnet-f16"): ONE plan that walks rva_res_topology (rva_plan_topo.h: any ResNet
+// of the torchvision family, BasicBlocks or Bottlenecks, 1..64 blocks per stage) with fp16 frames, fp16 convolution weights and
+// fp16 stored activations, and every sum in fp32.  It has two front doors: rva_resnet_f16_plan_* (the ResNet-18 of rva_resnet.hip:
+// its descriptor, weights struct, stage codes and texts, mapped by rva_res18_desc / rva_res18_stage onto BasicBlocks 2, 2, 2, 2
+// with split shortcuts -- the same launches and taps as the fp32 plan) and rva_resnetx_f16_plan_* (any depth).  Below, the stage
+// names and counts are ResNet-18's (19 convolutions, mid0..7, down2/4/6, out0..7; "out7" = the last block's output in general).
+// The numeric contract is that of clip-f16 / clip3d-f16:
 //
 //   * input: planar fp16 frames [3][H][W] (what rva_preprocess_frames_* writes for RVA_F16 with RVA_NORM_IMAGENET_F32), read
 //     through the device table of frame indices, element by element: nothing is assumed about the alignment of a frame row
@@ -32,13 +36,12 @@
 //            consecutive channels of its pixel: the epilogue is one 8-byte fp16 store (16-byte fp32 for out7) per group, and the
 //            residual one 8-byte load.  Epilogues, in fp32: max(acc + b, 0) | acc + b | max((acc + b) + res, 0) with res read as
 //            fp16 and widened; then one conversion to fp16, or none for out7.
-//   K_mean / K_head / K_post: k_res_mean (rva_resnet.hip) and the head and top-k kernels of rva_clip.hip, unchanged.
+//   K_mean / K_head / K_post: k_res_mean through rva_res_mean_launch (rva_resnet.hip; 512 or 2048 channels) and the head and top-k
+//            kernels of rva_clip.hip, unchanged.
 //
-// Every stage keeps its own workspace buffer (rva_resnet_f16_plan_stage reads them).
+// Every stage keeps its own workspace buffer (the _stage entries read them).
 //
-// The second plan of this file, rva_resnetx_f16_plan, walks the same kernels over any ResNet of the torchvision family
-// (rva_resx_topology in rva_plan_topo.h: BasicBlocks or Bottlenecks, 1..64 blocks per stage) under the same numeric contract.  Two
-// pieces of device code are its own:
+// One piece of device code serves only plans without RVA_RESX_SPLIT_SHORTCUT (never ResNet-18's entries):
 //
 //   K_conv, DUAL   a block that has a shortcut convolution computes ReLU(conv_close(mid) + b_close + conv_short(x) + b_short): as a
 //            GEMM, one accumulator chain over [taps of conv_close | channels of x].  k_res16_conv<..., DUAL = true> runs, after the
@@ -49,8 +52,7 @@
 //            change no bit.  The bias is b_close + b_short (added in float64 by the packer, rounded once), the epilogue EPI_RELU.
 //            One launch, one fp16 rounding and the write and re-read of the `down` tensor fewer per such block.  A plan created with
 //            RVA_RESX_SPLIT_SHORTCUT launches the shortcut on its own (EPI_BIAS) and adds it as the residual (EPI_RES_RELU): the
-//            launches and bits of the ResNet-18 plan above.
-//   K_mean   k_resx_mean: k_res_mean's order (pixels in raster order from zero, then one division by P) for 512 or 2048 channels.
+//            launches and bits of the ResNet-18 entries.
 #include "rva_mfma_f16.h"
 #include "rva_plan_topo.h"
 
@@ -313,177 +315,16 @@ void launch_res16_dual(int v, dim3 g, hipStream_t st, const Res16Args &a)
 #undef RES16_LAUNCH
 }
 
-// K_mean for any channel count (a multiple of 256): per image and channel the pixels in raster order from zero, then one division
-// by P -- the order of k_res_mean (rva_resnet.hip), which stays the ResNet-18 plans' kernel.
-__global__ void __launch_bounds__(256) k_resx_mean(const float *x, int P, int C, float *feat)
-{
-    const int img = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
-    const float *xp = x + (size_t)img * P * C + c;
-    float s = 0.f;
-    for (int p = 0; p < P; ++p) s = s + xp[(size_t)p * C];
-    feat[(size_t)img * C + c] = s / (float)P;
-}
-
-// every stage is stored as fp16 but out7 (it feeds only the mean) and feat
-constexpr int STAGE_OUT7 = RVA_RESNET_STAGE_OUT0 + RES_BLOCKS - 1;
-size_t res16_esize(int stage) { return stage == STAGE_OUT7 || stage == RVA_RESNET_STAGE_FEAT ? sizeof(float) : sizeof(_Float16); }
-
 }  // namespace
 
-struct rva_resnet_f16_plan {
-    rva_ctx *ctx = nullptr;
-    rva_resnet_desc d{};
-    int k = 0;                                             // min(top_k, classes)
-    rva_res_topo t{};
-    int tile_force = -1;                                   // RVA_RES16_TILE at creation: every launch takes this tile (tests, tools)
-    _Float16 *ws = nullptr, *w[RES_CONVS] = {};            // w, b: of t.conv[i], in launch order
-    float *bs = nullptr, *wh = nullptr, *bh = nullptr, *b[RES_CONVS] = {};
-    void *stage[RES_STAGES] = {};                          // every stage keeps its own buffer, indexed by RVA_RESNET_STAGE_*
-    size_t workspace_bytes = 0;
-    rva_dev_arena mem;
-};
-
-extern "C" {
-
-int rva_resnet_f16_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *wt, rva_resnet_f16_plan **out)
-{
-    int rc = rva_res_check_args(ctx, "rva_resnet_f16_plan_create", desc, wt, (void **)out);
-    if (rc != RVA_OK) return rc;
-    const rva_resnet_desc d = *desc;
-    const rva_res_topo t = rva_res_topology(d.height, d.width);
-    const size_t mf = (size_t)d.max_frames;
-    // sizes first: the workspace must fit before anything is allocated
-    size_t act_bytes = 0;
-    size_t w_bytes = (size_t)RES_C_STEM * 192 * sizeof(_Float16) + RES_C_STEM * sizeof(float) + (size_t)d.classes * (RES_C_FEAT + 1) * sizeof(float);
-    for (int s = 0; s < RES_STAGES; ++s) act_bytes += mf * t.elems[s] * res16_esize(s);
-    for (const rva_res_conv &c : t.conv) w_bytes += c.weights() * sizeof(_Float16) + c.cout * sizeof(float);
-    char shape[64];
-    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
-    rc = rva_plan_fits(ctx, "rva_resnet_f16_plan_create", act_bytes + w_bytes, shape);
-    if (rc != RVA_OK) return rc;
-    auto *p = new rva_resnet_f16_plan();
-    p->ctx = ctx;
-    p->d = d;
-    p->k = std::min(d.top_k, d.classes);
-    p->t = t;
-    p->workspace_bytes = act_bytes;
-    if (const char *e = getenv("RVA_RES16_TILE")) p->tile_force = std::max(-1, std::min(atoi(e), kNumTiles - 1));
-    auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
-    std::vector<_Float16> w16;
-    char bad[24] = "";
-    if (!rva_round_f16(wt->stem_w, (size_t)RES_C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
-    else { w16 = rva_clip16_stem_pack(w16); step(p->mem.upload(ctx, &p->ws, w16.data(), w16.size())); }
-    step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
-    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * RES_C_FEAT));
-    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
-    for (int s = 0; s < RES_STAGES; ++s) {
-        char *m = nullptr;
-        step(p->mem.alloc(ctx, &m, mf * t.elems[s] * res16_esize(s)));
-        p->stage[s] = m;
-    }
-    // in the ABI's weight order: rounds an array and uploads it as it is ([Cout][k*k][Cin] is what the kernel reads); names the
-    // first array that fails
-    for (int i = 0; i < RES_CONVS && rc == RVA_OK; ++i) {
-        const int n = t.launch_of[i];
-        if (!rva_round_f16(wt->conv[i].w, t.conv[n].weights(), w16)) {
-            snprintf(bad, sizeof bad, "conv[%d].w", i);
-            rc = RVA_ERR_ARG;
-            break;
-        }
-        step(p->mem.upload(ctx, &p->w[n], w16.data(), w16.size()));
-        step(p->mem.upload(ctx, &p->b[n], wt->conv[i].b, t.conv[n].cout));
-    }
-    if (rc == RVA_OK) rc = rva_clip16_stem_prepare(ctx);
-    if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, RES_C_FEAT);
-    if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
-    if (rc != RVA_OK) {
-        rva_resnet_f16_plan_destroy(p);
-        if (bad[0]) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_create: a value of %s does not stay finite in fp16", bad);
-        return rc;
-    }
-    *out = p;
-    return RVA_OK;
-}
-
-void rva_resnet_f16_plan_destroy(rva_resnet_f16_plan *p)
-{
-    if (!p) return;
-    p->mem.release();
-    delete p;
-}
-
-int rva_resnet_f16_plan_info(const rva_resnet_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
-{
-    if (!p) return RVA_ERR_ARG;
-    rva_res_info(p->t, p->workspace_bytes, maps, workspace_bytes, n_launches);
-    return RVA_OK;
-}
-
-int rva_resnet_f16_plan_run(rva_resnet_f16_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream_)
-{
-    if (!p) return RVA_ERR_ARG;
-    rva_ctx *ctx = p->ctx;
-    if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
-    const hipStream_t st = (hipStream_t)stream_;
-    void *const *buf = p->stage;
-    int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->ws, p->bs, (_Float16 *)buf[RVA_RESNET_STAGE_POOLED],
-                                    p->d.height, p->d.width, n, st);
-    if (rc != RVA_OK) return rc;
-    const int cus = rva_num_cus(ctx);
-    for (int i = 0; i < RES_CONVS; ++i) {
-        const rva_res_conv &l = p->t.conv[i];
-        Res16Args a{};
-        a.in = (const _Float16 *)buf[l.in]; a.w = p->w[i]; a.bias = p->b[i]; a.out = buf[l.out];
-        a.res = l.res >= 0 ? (const _Float16 *)buf[l.res] : nullptr;
-        a.H = l.H; a.W = l.W; a.Ho = l.Ho; a.Wo = l.Wo; a.Cin = l.cin; a.Cout = l.cout; a.stride = l.stride; a.epi = l.epi;
-        a.out_f32 = l.out == STAGE_OUT7;
-        a.M = (long)n * l.Ho * l.Wo;
-        const int v = p->tile_force >= 0 ? p->tile_force : res16_tile_for(a.M, l.cout, cus);
-        const dim3 g = res16_grid(v, a.M, l.cout);
-        if (l.k == 3) launch_res16_conv<3>(v, g, st, a);
-        else launch_res16_conv<1>(v, g, st, a);
-        RVA_HIP(ctx, hipGetLastError());
-    }
-    float *feat = (float *)buf[RVA_RESNET_STAGE_FEAT];
-    rc = rva_res_mean_launch(ctx, (const float *)buf[STAGE_OUT7], p->t.maps[4][0] * p->t.maps[4][1], feat, n, st);
-    if (rc != RVA_OK) return rc;
-    return rva_clip_head_launch(ctx, feat, p->wh, p->bh, (float *)logits, RES_C_FEAT, p->d.classes, n, st);
-}
-
-int rva_resnet_f16_plan_run_post(rva_resnet_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
-                                 void *cls, void *boxes, void *counts, rva_stream_t stream_)
-{
-    if (!p) return RVA_ERR_ARG;
-    return rva_clip_post_launch(p->ctx, "rva_resnet_f16_plan_run_post", (const float *)logits, p->d.classes, p->k, rows, n_rows, max_det,
-                                (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
-}
-
-// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is frame-major NHWC; the
-// counts are ELEMENT counts of the stage's stored type (fp16 for every stage but OUT0 + 7 and FEAT).
-int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *p, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream_)
-{
-    if (!p) return RVA_ERR_ARG;
-    rva_ctx *ctx = p->ctx;
-    if (n < 1 || n > p->d.max_frames)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
-    if (stage < 0 || stage >= RES_STAGES) return rva_fail(ctx, RVA_ERR_ARG, "rva_resnet_f16_plan_stage: unknown stage %d", stage);
-    return rva_clip_stage_copy(ctx, "rva_resnet_f16_plan_stage", stage, n, "frames", p->stage[stage], res16_esize(stage), "elements",
-                               n * p->t.elems[stage], 0, 0, 0, dst, dst_elems, n_elems, (hipStream_t)stream_);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------
-// rva_resnetx_f16_plan: the same kernels walked over the topology of any ResNet of the family (rva_resx_topology).  A block's
-// shortcut convolution runs inside its closing convolution's launch (DUAL) unless the plan was created with
-// RVA_RESX_SPLIT_SHORTCUT, which gives the launches of the ResNet-18 plan above.
+// The one plan of this file.  rva_resnet_f16_plan (ResNet-18) is the same object under its own handle type: created with
+// rva_res18_desc, tapped through rva_res18_stage.
 struct rva_resnetx_f16_plan {
     rva_ctx *ctx = nullptr;
     rva_resnetx_desc d{};
     int k = 0;                                             // min(top_k, classes)
-    rva_resx_topo t;
-    int tile_force = -1;                                   // RVA_RES16_TILE at creation
+    rva_res_topo t;
+    int tile_force = -1;                                   // RVA_RES16_TILE at creation: every launch takes this tile (tests, tools)
     _Float16 *ws = nullptr;
     float *bs = nullptr, *wh = nullptr, *bh = nullptr;
     std::vector<_Float16 *> w;                             // of convs[i], in the ABI's order
@@ -491,51 +332,49 @@ struct rva_resnetx_f16_plan {
     std::vector<void *> stage;                             // indexed by stage code; null: the plan has no such stage
     size_t workspace_bytes = 0;
     rva_dev_arena mem;
+    // every stage is stored as fp16 but the last block's output (it feeds only the mean) and feat
     size_t esize(int s) const { return s == t.last_out || s == RVA_RESX_FEAT ? sizeof(float) : sizeof(_Float16); }
 };
 
-extern "C" {
+namespace {
 
-int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, const rva_resnetx_weights *wt, rva_resnetx_f16_plan **out)
+typedef rva_resnetx_f16_plan Plan;
+Plan *plan_of(rva_resnet_f16_plan *p) { return reinterpret_cast<Plan *>(p); }
+const Plan *plan_of(const rva_resnet_f16_plan *p) { return reinterpret_cast<const Plan *>(p); }
+
+void res16_destroy(Plan *p)
 {
-    const char *who = "rva_resnetx_f16_plan_create";
-    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
-    *out = nullptr;
-    const rva_resnetx_desc d = *desc;
-    bool ok = d.height >= 1 && d.width >= 1 && d.classes >= 1 && d.classes <= RVA_PLAN_MAX_CLASSES && d.top_k >= 1 && d.max_frames >= 1 &&
-              d.max_frames <= 65535 && (int64_t)d.height * d.width <= (1 << 26) && (d.bottleneck == 0 || d.bottleneck == 1) &&
-              (d.flags & ~RVA_RESX_SPLIT_SHORTCUT) == 0;
-    for (int s = 0; s < 4; ++s) ok = ok && d.blocks[s] >= 1 && d.blocks[s] <= 64;
-    if (!ok)
-        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535, "
-                        "bottleneck 0 or 1, blocks 1..64 each, flags 0 or RVA_RESX_SPLIT_SHORTCUT)", who, RVA_PLAN_MAX_CLASSES);
-    rva_resx_topo t = rva_resx_topology(d);
-    if (d.n_convs != t.n_convs)
-        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (n_convs %d, the topology has %d convolutions)", who, d.n_convs, t.n_convs);
-    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b && wt->convs;
-    for (int i = 0; all && i < t.n_convs; ++i) all = wt->convs[i].w && wt->convs[i].b;
-    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
-    for (const rva_resx_conv &c : t.conv) {                // what the kernel takes; holds for every net of the family
+    if (!p) return;
+    p->mem.release();
+    delete p;
+}
+
+// a create after the entry's own argument checks: d, t = rva_res_topology(d) and every array of wt are good
+int res16_create(rva_ctx *ctx, const char *who, const rva_resnetx_desc &d, const rva_res_topo &t, const rva_resnetx_weights &wt, Plan **out)
+{
+    for (const rva_res_conv &c : t.conv) {                 // what the kernel takes; holds for every net of the family
         const bool dual = c.in2 >= 0;
         if (c.cin % 64 || c.cout % 64 || (dual && (c.cin2 % 64 || c.Ho != (c.H2 - 1) / c.stride2 + 1 || c.Wo != (c.W2 - 1) / c.stride2 + 1)))
             return rva_fail(ctx, RVA_ERR_ARG, "%s: a convolution of %d -> %d channels does not fit the kernel", who, c.cin, c.cout);
     }
-    const size_t mf = (size_t)d.max_frames;
-    auto esize = [&](int s) { return s == t.last_out || s == RVA_RESX_FEAT ? sizeof(float) : sizeof(_Float16); };
-    // sizes first: the workspace must fit before anything is allocated
-    size_t act_bytes = 0;
-    size_t w_bytes = (size_t)RES_C_STEM * 192 * sizeof(_Float16) + RES_C_STEM * sizeof(float) + (size_t)d.classes * (t.c_feat + 1) * sizeof(float);
-    for (size_t s = 0; s < t.elems.size(); ++s) act_bytes += mf * t.elems[s] * esize((int)s);
-    for (int i = 0; i < t.n_convs; ++i) w_bytes += t.conv_weights[i] * sizeof(_Float16) + t.conv_cout[i] * sizeof(float);
-    char shape[64];
-    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
-    int rc = rva_plan_fits(ctx, who, act_bytes + w_bytes, shape);
-    if (rc != RVA_OK) return rc;
-    auto *p = new rva_resnetx_f16_plan();
+    auto *p = new Plan();
     p->ctx = ctx;
     p->d = d;
     p->k = std::min(d.top_k, d.classes);
     p->t = t;
+    const size_t mf = (size_t)d.max_frames;
+    // sizes first: the workspace must fit before anything is allocated
+    size_t act_bytes = 0;
+    size_t w_bytes = (size_t)RES_C_STEM * 192 * sizeof(_Float16) + RES_C_STEM * sizeof(float) + (size_t)d.classes * (t.c_feat + 1) * sizeof(float);
+    for (size_t s = 0; s < t.elems.size(); ++s) act_bytes += mf * t.elems[s] * p->esize((int)s);
+    for (int i = 0; i < t.n_convs; ++i) w_bytes += t.conv_weights[i] * sizeof(_Float16) + t.conv_cout[i] * sizeof(float);
+    char shape[64];
+    snprintf(shape, sizeof shape, "%d frames of %d x %d", d.max_frames, d.height, d.width);
+    int rc = rva_plan_fits(ctx, who, act_bytes + w_bytes, shape);
+    if (rc != RVA_OK) {
+        res16_destroy(p);                                  // nothing on the device yet
+        return rc;
+    }
     p->workspace_bytes = act_bytes;
     p->w.assign(t.n_convs, nullptr);
     p->b.assign(t.n_convs, nullptr);
@@ -544,31 +383,33 @@ int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, cons
     auto step = [&](int r) { if (rc == RVA_OK) rc = r; };
     std::vector<_Float16> w16;
     char bad[24] = "";
-    if (!rva_round_f16(wt->stem_w, (size_t)RES_C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
+    if (!rva_round_f16(wt.stem_w, (size_t)RES_C_STEM * 147, w16)) { snprintf(bad, sizeof bad, "stem_w"); rc = RVA_ERR_ARG; }
     else { w16 = rva_clip16_stem_pack(w16); step(p->mem.upload(ctx, &p->ws, w16.data(), w16.size())); }
-    step(p->mem.upload(ctx, &p->bs, wt->stem_b, RES_C_STEM));
-    step(p->mem.upload(ctx, &p->wh, wt->head_w, (size_t)d.classes * t.c_feat));
-    step(p->mem.upload(ctx, &p->bh, wt->head_b, d.classes));
+    step(p->mem.upload(ctx, &p->bs, wt.stem_b, RES_C_STEM));
+    step(p->mem.upload(ctx, &p->wh, wt.head_w, (size_t)d.classes * t.c_feat));
+    step(p->mem.upload(ctx, &p->bh, wt.head_b, d.classes));
     for (size_t s = 0; s < t.elems.size(); ++s) {
         if (!t.elems[s]) continue;
         char *m = nullptr;
-        step(p->mem.alloc(ctx, &m, mf * t.elems[s] * esize((int)s)));
+        step(p->mem.alloc(ctx, &m, mf * t.elems[s] * p->esize((int)s)));
         p->stage[s] = m;
     }
+    // in the ABI's weight order: rounds an array and uploads it as it is ([Cout][k*k][Cin] is what the kernel reads); names the
+    // first array that fails
     for (int i = 0; i < t.n_convs && rc == RVA_OK; ++i) {
-        if (!rva_round_f16(wt->convs[i].w, t.conv_weights[i], w16)) {
+        if (!rva_round_f16(wt.convs[i].w, t.conv_weights[i], w16)) {
             snprintf(bad, sizeof bad, "conv[%d].w", i);
             rc = RVA_ERR_ARG;
             break;
         }
         step(p->mem.upload(ctx, &p->w[i], w16.data(), w16.size()));
-        step(p->mem.upload(ctx, &p->b[i], wt->convs[i].b, t.conv_cout[i]));
+        step(p->mem.upload(ctx, &p->b[i], wt.convs[i].b, t.conv_cout[i]));
     }
     if (rc == RVA_OK) rc = rva_clip16_stem_prepare(ctx);
     if (rc == RVA_OK) rc = rva_clip_head_prepare(ctx, t.c_feat);
     if (rc == RVA_OK) rc = rva_clip_post_prepare(ctx, d.classes);
     if (rc != RVA_OK) {
-        rva_resnetx_f16_plan_destroy(p);
+        res16_destroy(p);
         if (bad[0]) return rva_fail(ctx, RVA_ERR_ARG, "%s: a value of %s does not stay finite in fp16", who, bad);
         return rc;
     }
@@ -576,36 +417,19 @@ int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, cons
     return RVA_OK;
 }
 
-void rva_resnetx_f16_plan_destroy(rva_resnetx_f16_plan *p)
-{
-    if (!p) return;
-    p->mem.release();
-    delete p;
-}
-
-int rva_resnetx_f16_plan_info(const rva_resnetx_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
-{
-    if (!p) return RVA_ERR_ARG;
-    if (maps)
-        for (int s = 0; s < 5; ++s) { maps[2 * s] = p->t.maps[s][0]; maps[2 * s + 1] = p->t.maps[s][1]; }
-    if (workspace_bytes) *workspace_bytes = (int64_t)p->workspace_bytes;
-    if (n_launches) *n_launches = 1 + (int32_t)p->t.conv.size() + 2;
-    return RVA_OK;
-}
-
-int rva_resnetx_f16_plan_run(rva_resnetx_f16_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream_)
+int res16_run(Plan *p, const char *who, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
     rva_ctx *ctx = p->ctx;
     if (!frames || !frame_index || !logits || n < 1 || n > p->d.max_frames)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_run: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad argument (n %d, capacity %d)", who, n, p->d.max_frames);
     const hipStream_t st = (hipStream_t)stream_;
     void *const *buf = p->stage.data();
     int rc = rva_clip16_stem_launch(ctx, (const _Float16 *)frames, frame_index, p->ws, p->bs, (_Float16 *)buf[RVA_RESX_POOLED], p->d.height,
                                     p->d.width, n, st);
     if (rc != RVA_OK) return rc;
     const int cus = rva_num_cus(ctx);
-    for (const rva_resx_conv &l : p->t.conv) {
+    for (const rva_res_conv &l : p->t.conv) {
         Res16Args a{};
         a.in = (const _Float16 *)buf[l.in]; a.w = p->w[l.wi]; a.bias = p->b[l.wi]; a.out = buf[l.out];
         a.res = l.res >= 0 ? (const _Float16 *)buf[l.res] : nullptr;
@@ -627,30 +451,128 @@ int rva_resnetx_f16_plan_run(rva_resnetx_f16_plan *p, const void *frames, const 
         RVA_HIP(ctx, hipGetLastError());
     }
     float *feat = (float *)buf[RVA_RESX_FEAT];
-    k_resx_mean<<<dim3(n, p->t.c_feat / 256), 256, 0, st>>>((const float *)buf[p->t.last_out], p->t.maps[4][0] * p->t.maps[4][1], p->t.c_feat, feat);
-    RVA_HIP(ctx, hipGetLastError());
+    rc = rva_res_mean_launch(ctx, (const float *)buf[p->t.last_out], p->t.maps[4][0] * p->t.maps[4][1], p->t.c_feat, feat, n, st);
+    if (rc != RVA_OK) return rc;
     return rva_clip_head_launch(ctx, feat, p->wh, p->bh, (float *)logits, p->t.c_feat, p->d.classes, n, st);
 }
 
-int rva_resnetx_f16_plan_run_post(rva_resnetx_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
-                                  void *cls, void *boxes, void *counts, rva_stream_t stream_)
+int res16_run_post(Plan *p, const char *who, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores, void *cls,
+                   void *boxes, void *counts, rva_stream_t stream_)
 {
     if (!p) return RVA_ERR_ARG;
-    return rva_clip_post_launch(p->ctx, "rva_resnetx_f16_plan_run_post", (const float *)logits, p->d.classes, p->k, rows, n_rows, max_det,
-                                (float *)scores, (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
+    return rva_clip_post_launch(p->ctx, who, (const float *)logits, p->d.classes, p->k, rows, n_rows, max_det, (float *)scores,
+                                (int32_t *)cls, (float *)boxes, (int32_t *)counts, (hipStream_t)stream_);
 }
 
-// Read-only tap on the workspace, as rva_resnet_f16_plan_stage; a stage code the plan has no buffer for is refused.
-int rva_resnetx_f16_plan_stage(rva_resnetx_f16_plan *p, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream_)
+int res16_info(const Plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
 {
     if (!p) return RVA_ERR_ARG;
+    rva_res_info(p->t, p->workspace_bytes, maps, workspace_bytes, n_launches);
+    return RVA_OK;
+}
+
+// Read-only tap on the workspace (tests and tools): one device-to-device copy, no kernel.  Every tensor is frame-major NHWC; the
+// counts are ELEMENT counts of the stage's stored type.  `stage` is the plan's code of what the entry's caller named `asked`.
+int res16_stage(Plan *p, const char *who, int asked, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream_)
+{
     rva_ctx *ctx = p->ctx;
-    if (n < 1 || n > p->d.max_frames)
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_stage: bad argument (n %d, capacity %d)", n, p->d.max_frames);
+    if (n < 1 || n > p->d.max_frames) return rva_fail(ctx, RVA_ERR_ARG, "%s: bad argument (n %d, capacity %d)", who, n, p->d.max_frames);
     if (stage < 0 || stage >= (int)p->stage.size() || !p->stage[stage])
-        return rva_fail(ctx, RVA_ERR_ARG, "rva_resnetx_f16_plan_stage: the plan has no stage %d", stage);
-    return rva_clip_stage_copy(ctx, "rva_resnetx_f16_plan_stage", stage, n, "frames", p->stage[stage], p->esize(stage), "elements",
-                               n * p->t.elems[stage], 0, 0, 0, dst, dst_elems, n_elems, (hipStream_t)stream_);
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: the plan has no stage %d", who, asked);
+    return rva_clip_stage_copy(ctx, who, asked, n, "frames", p->stage[stage], p->esize(stage), "elements", n * p->t.elems[stage], 0, 0, 0,
+                               dst, dst_elems, n_elems, (hipStream_t)stream_);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ResNet-18: the checks and texts of its own entries, then the plan of BasicBlocks 2, 2, 2, 2 with split shortcuts.
+int rva_resnet_f16_plan_create(rva_ctx *ctx, const rva_resnet_desc *desc, const rva_resnet_weights *wt, rva_resnet_f16_plan **out)
+{
+    const char *who = "rva_resnet_f16_plan_create";
+    const int rc = rva_res_check_args(ctx, who, desc, wt, (void **)out);
+    if (rc != RVA_OK) return rc;
+    const rva_resnetx_desc d = rva_res18_desc(*desc);
+    return res16_create(ctx, who, d, rva_res_topology(d), {wt->stem_w, wt->stem_b, wt->conv, wt->head_w, wt->head_b}, (Plan **)out);
+}
+
+void rva_resnet_f16_plan_destroy(rva_resnet_f16_plan *p) { res16_destroy(plan_of(p)); }
+
+int rva_resnet_f16_plan_info(const rva_resnet_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
+{
+    return res16_info(plan_of(p), maps, workspace_bytes, n_launches);
+}
+
+int rva_resnet_f16_plan_run(rva_resnet_f16_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream)
+{
+    return res16_run(plan_of(p), "rva_resnet_f16_plan_run", frames, frame_index, n, logits, stream);
+}
+
+int rva_resnet_f16_plan_run_post(rva_resnet_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
+                                 void *cls, void *boxes, void *counts, rva_stream_t stream)
+{
+    return res16_run_post(plan_of(p), "rva_resnet_f16_plan_run_post", logits, rows, n_rows, max_det, scores, cls, boxes, counts, stream);
+}
+
+// the tap by RVA_RESNET_STAGE_* code: fp16 elements for every stage but OUT0 + 7 and FEAT
+int rva_resnet_f16_plan_stage(rva_resnet_f16_plan *p, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream)
+{
+    if (!p) return RVA_ERR_ARG;
+    const char *who = "rva_resnet_f16_plan_stage";
+    const int code = rva_res18_stage(stage);
+    if (code < 0) return rva_fail(plan_of(p)->ctx, RVA_ERR_ARG, "%s: unknown stage %d", who, stage);
+    return res16_stage(plan_of(p), who, stage, code, n, dst, dst_elems, n_elems, stream);
+}
+
+// Any ResNet of the family: a block's shortcut convolution runs inside its closing convolution's launch (DUAL) unless the plan
+// was created with RVA_RESX_SPLIT_SHORTCUT.
+int rva_resnetx_f16_plan_create(rva_ctx *ctx, const rva_resnetx_desc *desc, const rva_resnetx_weights *wt, rva_resnetx_f16_plan **out)
+{
+    const char *who = "rva_resnetx_f16_plan_create";
+    if (!ctx || !desc || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    const rva_resnetx_desc d = *desc;
+    bool ok = d.height >= 1 && d.width >= 1 && d.classes >= 1 && d.classes <= RVA_PLAN_MAX_CLASSES && d.top_k >= 1 && d.max_frames >= 1 &&
+              d.max_frames <= 65535 && (int64_t)d.height * d.width <= (1 << 26) && (d.bottleneck == 0 || d.bottleneck == 1) &&
+              (d.flags & ~RVA_RESX_SPLIT_SHORTCUT) == 0;
+    for (int s = 0; s < 4; ++s) ok = ok && d.blocks[s] >= 1 && d.blocks[s] <= 64;
+    if (!ok)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (height, width >= 1, classes 1..%d, top_k >= 1, max_frames 1..65535, "
+                        "bottleneck 0 or 1, blocks 1..64 each, flags 0 or RVA_RESX_SPLIT_SHORTCUT)", who, RVA_PLAN_MAX_CLASSES);
+    const rva_res_topo t = rva_res_topology(d);
+    if (d.n_convs != t.n_convs)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (n_convs %d, the topology has %d convolutions)", who, d.n_convs, t.n_convs);
+    bool all = wt->stem_w && wt->stem_b && wt->head_w && wt->head_b && wt->convs;
+    for (int i = 0; all && i < t.n_convs; ++i) all = wt->convs[i].w && wt->convs[i].b;
+    if (!all) return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    return res16_create(ctx, who, d, t, *wt, out);
+}
+
+void rva_resnetx_f16_plan_destroy(rva_resnetx_f16_plan *p) { res16_destroy(p); }
+
+int rva_resnetx_f16_plan_info(const rva_resnetx_f16_plan *p, int32_t *maps, int64_t *workspace_bytes, int32_t *n_launches)
+{
+    return res16_info(p, maps, workspace_bytes, n_launches);
+}
+
+int rva_resnetx_f16_plan_run(rva_resnetx_f16_plan *p, const void *frames, const int32_t *frame_index, int n, void *logits, rva_stream_t stream)
+{
+    return res16_run(p, "rva_resnetx_f16_plan_run", frames, frame_index, n, logits, stream);
+}
+
+int rva_resnetx_f16_plan_run_post(rva_resnetx_f16_plan *p, const void *logits, const int32_t *rows, int n_rows, int max_det, void *scores,
+                                  void *cls, void *boxes, void *counts, rva_stream_t stream)
+{
+    return res16_run_post(p, "rva_resnetx_f16_plan_run_post", logits, rows, n_rows, max_det, scores, cls, boxes, counts, stream);
+}
+
+// the tap by RVA_RESX_* code; a stage code the plan has no buffer for is refused
+int rva_resnetx_f16_plan_stage(rva_resnetx_f16_plan *p, int stage, int n, void *dst, int64_t dst_elems, int64_t *n_elems, rva_stream_t stream)
+{
+    if (!p) return RVA_ERR_ARG;
+    return res16_stage(p, "rva_resnetx_f16_plan_stage", stage, stage, n, dst, dst_elems, n_elems, stream);
 }
 
 }  // extern "C"
+

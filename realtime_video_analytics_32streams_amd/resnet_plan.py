@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .clip_plan import _ClipPlan, _fold, _fold64, _fold_f16, _round_f16, conv_out
+from .clip_plan import _ClipPlan, _fold64, _round_f16, conv_out
 
 ENGINE = "resnet-f32"        # NOT "fused" / "fused-f32": PipelinedTicks reads those names as YOLO plans
 ENGINE_F16 = "resnet-f16"    # its fp16 MFMA form (half: true, hip_engine: plan / native, hip_resnet_fp16: true)
@@ -125,24 +125,61 @@ def pack_resnet18(net, half: bool = False) -> Dict[str, np.ndarray]:
     then converts exactly); a value beyond fp16 raises ``ValueError`` naming the array.  The biases and the head stay fp32."""
     if not _is_resnet18(net):
         raise ValueError("pack_resnet18: not the ResNet18 architecture")
-    fold = (lambda conv, bn, what: _fold_f16(conv, bn, what, "pack_resnet18")) if half else (lambda conv, bn, what: _fold(conv, bn))  # noqa: E731
-    taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)  # noqa: E731  [co,ci,kk] -> [co,kk,ci]
+    blocks = ([(blk.c1, blk.b1), (blk.c2, blk.b2)] + ([(blk.down[0], blk.down[1])] if blk.down is not None else []) for blk in net.layers)
+    return _pack("pack_resnet18", half, (net.stem[0], net.stem[1]), blocks, net.fc)
+
+
+def _pack(who: str, half: bool, stem, blocks, fc, fuse: int = 0) -> Dict[str, np.ndarray]:
+    """What :func:`pack_resnet18` and :func:`pack_resnet` return, from the ``(conv, bn)`` pair of the stem, per block the list of
+    its pairs in the ABI's order (the shortcut last) and the head: every pair folded in float64, the weight rounded once to fp16
+    (``half``; ``who`` names the refusal) or to fp32 and laid out ``[Cout, k*k, Cin]``, the bias rounded once to fp32.  ``fuse``:
+    a block of more than ``fuse`` pairs has a shortcut whose bias is added, in float64, to that of the pair before it."""
+    def fold(conv, bn, what):
+        wf, bf = _fold64(conv, bn)
+        return (_round_f16(wf.numpy(), what, who) if half else wf.float().numpy()), bf
+
     out = {}
-    out["stem_w"], out["stem_b"] = fold(net.stem[0], net.stem[1], "stem_w")
+    out["stem_w"], b = fold(*stem, "stem_w")
+    out["stem_b"] = b.float().numpy()
     i = 0
-    for blk in net.layers:
-        pairs = [(blk.c1, blk.b1), (blk.c2, blk.b2)] + ([(blk.down[0], blk.down[1])] if blk.down is not None else [])
+    for pairs in blocks:
+        first, biases = i, []
         for conv, bn in pairs:
             w, b = fold(conv, bn, f"c{i}_w")
-            out[f"c{i}_w"], out[f"c{i}_b"] = taps_last(w), b
+            out[f"c{i}_w"] = w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)    # [co,ci,kk] -> [co,kk,ci]
+            biases.append(b)
             i += 1
-    fc = net.fc
+        if fuse and len(pairs) > fuse:
+            biases[-2] = biases[-2] + biases[-1]                       # float64; rounded once below
+        for k, b in enumerate(biases):
+            out[f"c{first + k}_b"] = b.float().numpy()
     out["head_w"] = fc.weight.detach().float().cpu().numpy()
     out["head_b"] = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
-    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in N.ResNetWeights.NAMES}
+    names = ["stem_w", "stem_b"] + [f"c{j}_{x}" for j in range(i) for x in "wb"] + ["head_w", "head_b"]
+    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in names}
 
 
-class FusedResNet18(_ClipPlan):
+class _ResNetPlan(_ClipPlan):
+    """What the ResNet plans share over :class:`_ClipPlan`: reading ``_info`` and ``__call__``."""
+
+    def _read_info(self) -> None:
+        maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
+        self.ctx.check(self._fn("info")(self.handle, maps, C.byref(ws), C.byref(nl)), f"{self.ABI}_info")
+        self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
+        self.workspace_bytes, self.n_launches = ws.value, nl.value
+
+    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
+        """The network's ``forward`` of frames ``[B, 3, H, W]``: a fresh fp32 ``[B, classes]`` tensor.  An fp32 plan takes fp32
+        frames; an fp16 plan takes fp16 frames, or fp32 ones that are rounded to fp16 here."""
+        b = int(frames.shape[0])
+        if tuple(frames.shape[1:]) != (3, self.H, self.W):
+            raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
+        if self.RING_DTYPE == torch.float16:
+            frames = frames.to(torch.float16)
+        return self._run_frames(frames.contiguous(), b)
+
+
+class FusedResNet18(_ResNetPlan):
     """One ``rva_resnet_plan``: the fp32 network of ``net`` (a :class:`classify.ResNet18`) for frames of ``hw``, up to
     ``max_frames`` frames per call, with the top ``top_k`` in :meth:`post`.  The surface of the clip plans with ``T = 1``
     (``max_clips`` = frames, ``classes``, ``logits``, ``run``, ``post``, ``stage``, ``__call__``).  No host synchronisation and
@@ -158,10 +195,7 @@ class FusedResNet18(_ClipPlan):
         self.top_k = int(top_k)
         self.k = min(self.top_k, self.classes)
         self._create(N.ResNetDesc(self.H, self.W, self.classes, self.top_k, self.max_clips), N.ResNetWeights, packed)
-        maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
-        self.ctx.check(self._fn("info")(self.handle, maps, C.byref(ws), C.byref(nl)), f"{self.ABI}_info")
-        self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
-        self.workspace_bytes, self.n_launches = ws.value, nl.value
+        self._read_info()
 
     def stage_shape(self, name: str, n: int) -> tuple:
         if name == "feat":
@@ -179,13 +213,6 @@ class FusedResNet18(_ClipPlan):
         stages = {k: (code, self.stage_shape(k, n)) for k, code in STAGE_CODES.items()}
         return self._tap(stages, name, n)
 
-    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
-        """``ResNet18.forward`` of frames ``[B, 3, H, W]`` fp32: a fresh ``[B, classes]`` tensor."""
-        b = int(frames.shape[0])
-        if tuple(frames.shape[1:]) != (3, self.H, self.W):
-            raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
-        return self._run_frames(frames.contiguous(), b)
-
 
 class FusedResNet18F16(FusedResNet18):
     """One ``rva_resnet_f16_plan``: the network of :class:`FusedResNet18` for ``half: true`` -- fp16 frames, fp16 convolution
@@ -197,11 +224,6 @@ class FusedResNet18F16(FusedResNet18):
     HALF = True
     RING_DTYPE = torch.float16
     TAP_DTYPES = {n: torch.float16 for n in STAGE_CODES if n not in ("out7", "feat")}
-
-    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
-        """``ResNet18.forward`` of frames ``[B, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
-        ``[B, classes]`` tensor."""
-        return super().__call__(frames.to(torch.float16))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -233,37 +255,11 @@ def pack_resnet(net, half: bool = True, fused: bool = True) -> Dict[str, np.ndar
     ``b_close + b_short``, added in float64 and rounded once to fp32; the shortcut keeps its own bias, which that plan does not read."""
     if not _is_resnet(net):
         raise ValueError(f"pack_resnet: not a classify.ResNet ({type(net).__name__}; classify.ResNet18 is packed by pack_resnet18)")
-    taps_last = lambda w: w.reshape(w.shape[0], w.shape[1], -1).transpose(0, 2, 1)  # noqa: E731  [co,ci,kk] -> [co,kk,ci]
-
-    def fold(conv, bn, what):
-        wf, bf = _fold64(conv, bn)
-        w = _round_f16(wf.numpy(), what, "pack_resnet") if half else wf.float().numpy()
-        return w, bf
-
-    out = {}
-    w, b = fold(net.conv1, net.bn1, "stem_w")
-    out["stem_w"], out["stem_b"] = w, b.float().numpy()
-    i = 0
-    for s in range(4):
-        for blk in getattr(net, f"layer{s + 1}"):
-            pairs = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)] + ([(blk.conv3, blk.bn3)] if net.block == "bottleneck" else [])
-            if blk.downsample is not None:
-                pairs.append((blk.downsample[0], blk.downsample[1]))
-            first, biases = i, []
-            for conv, bn in pairs:
-                w, b = fold(conv, bn, f"c{i}_w")
-                out[f"c{i}_w"] = taps_last(w)
-                biases.append(b)
-                i += 1
-            if fused and blk.downsample is not None:
-                biases[-2] = biases[-2] + biases[-1]                   # float64; rounded once below
-            for k, b in enumerate(biases):
-                out[f"c{first + k}_b"] = b.float().numpy()
-    fc = net.fc
-    out["head_w"] = fc.weight.detach().float().cpu().numpy()
-    out["head_b"] = fc.bias.detach().float().cpu().numpy() if fc.bias is not None else np.zeros(fc.out_features, np.float32)
-    names = ["stem_w", "stem_b"] + [f"c{j}_{x}" for j in range(i) for x in "wb"] + ["head_w", "head_b"]
-    return {n: np.ascontiguousarray(out[n], dtype=np.float32) for n in names}
+    own = 3 if net.block == "bottleneck" else 2
+    blocks = ([(blk.conv1, blk.bn1), (blk.conv2, blk.bn2)] + ([(blk.conv3, blk.bn3)] if own == 3 else []) +
+              ([(blk.downsample[0], blk.downsample[1])] if blk.downsample is not None else [])
+              for s in range(4) for blk in getattr(net, f"layer{s + 1}"))
+    return _pack("pack_resnet", half, (net.conv1, net.bn1), blocks, net.fc, fuse=own if fused else 0)
 
 
 def resnet_any_flops(bottleneck: bool, blocks, h: int, w: int, classes: int = 1000, split_shortcut: bool = False) -> Dict[str, object]:
@@ -308,7 +304,7 @@ def resnet_any_flops(bottleneck: bool, blocks, h: int, w: int, classes: int = 10
             "workspace_bytes": ws, "frame_bytes": 2.0 * 3 * h * w}
 
 
-class FusedResNetF16(_ClipPlan):
+class FusedResNetF16(_ResNetPlan):
     """One ``rva_resnetx_f16_plan``: the network of ``net`` (a :class:`classify.ResNet` of any depth) for ``half: true`` with the
     numeric contract and the surface of :class:`FusedResNet18F16` (``run`` on fp16 frames, ``post``, ``stage``, ``__call__``,
     ``maps``, ``workspace_bytes``, ``n_launches``, ``classes``, ``logits``).  A block's shortcut convolution runs inside the launch
@@ -342,10 +338,7 @@ class FusedResNetF16(_ClipPlan):
             self.ctx.check(self._fn("create")(self.ctx.handle, C.byref(desc), C.byref(wt), C.byref(h)), f"{self.ABI}_create")
         self.handle = h
         self.logits = torch.empty((self.max_clips, self.classes), dtype=torch.float32, device=self.dev)
-        maps, ws, nl = (C.c_int32 * 10)(), C.c_int64(), C.c_int32()
-        self.ctx.check(self._fn("info")(self.handle, maps, C.byref(ws), C.byref(nl)), f"{self.ABI}_info")
-        self.maps = [(maps[2 * s], maps[2 * s + 1]) for s in range(5)]
-        self.workspace_bytes, self.n_launches = ws.value, nl.value
+        self._read_info()
         self._stages = self._stage_table()
         last = f"b{len(self.table) - 1}.out"
         self.TAP_DTYPES = {n: torch.float16 for n in self._stages if n not in (last, "feat")}
@@ -376,11 +369,3 @@ class FusedResNetF16(_ClipPlan):
         ``rva_resnetx_f16_plan_stage`` documents (include/rva.h).  A read-only tap for tests and tools."""
         n = int(n)
         return self._tap({k: (code, (n, *shape)) for k, (code, shape) in self._stages.items()}, name, n)
-
-    def __call__(self, frames: torch.Tensor) -> torch.Tensor:
-        """``ResNet.forward`` of frames ``[B, 3, H, W]`` of fp16, or of fp32 that is rounded to fp16 here: a fresh fp32
-        ``[B, classes]`` tensor."""
-        b = int(frames.shape[0])
-        if tuple(frames.shape[1:]) != (3, self.H, self.W):
-            raise ValueError(f"frames must be [B, 3, {self.H}, {self.W}], got {tuple(frames.shape)}")
-        return self._run_frames(frames.to(torch.float16).contiguous(), b)

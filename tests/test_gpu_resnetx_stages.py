@@ -69,7 +69,10 @@ def test_every_stage_against_float64(case, fused):
 
 @pytest.mark.parametrize("hw", [(34, 34), (40, 72)], ids=lambda v: f"{v[0]}x{v[1]}")
 def test_a_split_plan_with_resnet18s_weights_leaves_the_resnet18_plans_bits(hw):
-    """The same kernels in the same order on the same weights: logits and every block output are bit-identical."""
+    """The same kernels in the same order on the same weights: logits and every block output are bit-identical.  Both sides now
+    run the one plan of csrc/rva_resnet_f16.hip (``rva_resnet_f16_plan_*`` creates it with the ResNet-18 descriptor), so this
+    checks the two front doors -- the packers, the descriptor and the stage-code translation -- against each other; that the bits
+    are still those of the separate ResNet-18 plan was shown when it was deleted (profiles/resnet_one_topology.json)."""
     old = synth.seeded_module(lambda: ResNet18(10), 77)
     new = ResNet("basic", (2, 2, 2, 2), 10)
     sd = {"conv1.weight": old.stem[0].weight, **{f"bn1.{k}": v for k, v in old.stem[1].state_dict().items()},

@@ -145,7 +145,7 @@ def launch_table(trace_dir, n: int, split: bool, depth: int = 50):
     with open(files[0]) as fh:
         for r in csv.DictReader(fh):
             name = r.get("Kernel_Name") or r.get("Name") or ""
-            if re.search(r"k_clip16_stem|k_res16_conv|k_resx_mean|k_clip_head", name):
+            if re.search(r"k_clip16_stem|k_res16_conv|k_res_mean|k_clip_head", name):
                 rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name))
     rows.sort()
     f = _flops(depth, split)
