@@ -19,7 +19,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
 SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_stem.hip", "rva_yolo_ops.hip", "rva_conv_f32.hip", "rva_attn.hip", "rva_plan.hip", "rva_clip.hip",
-           "rva_clip3d.hip", "rva_clip3d_f16.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+           "rva_clip3d.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]

@@ -14,7 +14,7 @@ from the detector's HBM ring through a device table of frame indices.  What stay
 The 3D-CNN head (:class:`temporal.Cnn3dNet`; ``3d_cnn`` and ``slow_fast``) has the same pieces for ``rva_cnn3d_plan_*``
 (``csrc/rva_clip3d.hip``, selected by ``hip_engine: native``): :func:`pack_cnn3d`, :func:`clip3d_flops`, :class:`Fused3dCnn`.
 With ``half: true`` and the detector key ``hip_clip_fp16: true`` the same head runs as the fp16 MFMA plan ``rva_cnn3d_f16_plan_*``
-(``csrc/rva_clip3d_f16.hip``, engine ``"clip3d-f16"``): ``pack_cnn3d(net, half=True)`` and :class:`Fused3dCnnF16`.
+(``csrc/rva_clip3d.hip``, engine ``"clip3d-f16"``): ``pack_cnn3d(net, half=True)`` and :class:`Fused3dCnnF16`.
 The CNN-LSTM head has its fp16 form too: with ``half: true`` and the detector key ``hip_lstm_fp16: true`` it runs as
 ``rva_cnnlstm_f16_plan_*`` (``csrc/rva_clip_f16.hip``, engine ``"clip-f16"``): ``pack_cnn_lstm(net, half=True)`` and
 :class:`FusedCnnLstmF16`.

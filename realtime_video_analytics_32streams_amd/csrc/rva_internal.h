@@ -102,9 +102,10 @@ int rva_conv2d_nhwc_f16_sel(rva_ctx *ctx, const void *in, int ldi, const void *w
 void rva_jpeg_free(rva_ctx *ctx);
 
 // ---------------------------------------------------------------------------------------------------
-// The host scaffold of the clip and classifier plans (rva_clip*.hip, rva_clip3d*.hip, rva_resnet*.hip).  The fp32 and the fp16 form
-// of a plan share everything here; a plan file keeps only what differs by precision: element types, rounding, kernels, launches.
-// The networks' own shapes (ResNet-18 topology, 3D-CNN geometry) are in rva_plan_topo.h.
+// The host scaffold of the clip and classifier plans (rva_clip.hip, rva_clip_f16.hip, rva_clip3d.hip, rva_resnet*.hip).  The fp32
+// and the fp16 form of a plan share everything here; a plan file keeps only what differs by precision: element types, rounding,
+// kernels, launches.  The networks' own shapes (ResNet topology, 3D-CNN geometry, CNN-LSTM maps and stages) are in rva_plan_topo.h;
+// the CNN-LSTM's host plan over both precisions is rva_clip_host.h, the bodies of its K_xproj / K_lstm rva_lstm_dev.h.
 
 // Device memory of a plan: every buffer is an array of `n` elements of T owned until release().
 struct rva_dev_arena {

@@ -1,5 +1,5 @@
 // The fp16-input counterpart of f32_chunk / f32_conv_taps (rva_mfma_f32.h) on v_mfma_f32_32x32x16_f16, included by
-// rva_clip3d_f16.hip (device code only).  A wave owns MT x NT tiles of 32 GEMM rows (output positions) x 32 columns (output
+// rva_clip3d.hip (device code only).  A wave owns MT x NT tiles of 32 GEMM rows (output positions) x 32 columns (output
 // channels); lane & 31 = row of an A tile and column of a B tile, lane >> 5 = lane half h.  Operands are fp16, every sum is fp32.
 //
 // THE reduction order of an output element, for every kernel built on this header: taps in order; inside a tap the input

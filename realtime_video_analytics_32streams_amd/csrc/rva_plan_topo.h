@@ -131,7 +131,7 @@ inline int rva_res18_stage(int stage)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 3D-CNN (rva_clip3d.hip, rva_clip3d_f16.hip): conv1 + (1,2,2) pool, conv2 + (2,2,2) pool, conv3 + mean.  The pools floor.
+// 3D-CNN (rva_clip3d.hip, both precisions): conv1 + (1,2,2) pool, conv2 + (2,2,2) pool, conv3 + mean.  The pools floor.
 constexpr int C3D_C1 = 64, C3D_C2 = 128, C3D_C3 = 256, C3D_TAPS = 27;
 constexpr int C3D_PT = 8;                                  // pooled tile (PT x PT) of a K_conv1 block
 constexpr int C3D_GROUPS = 32;                             // pool groups (of 8 conv positions) of a K_conv2 block; K_conv3: 256 positions
@@ -181,4 +181,63 @@ inline void rva_c3d_info(const rva_c3d_geom &g, int32_t *pool1, int32_t *pool2, 
     if (pool2) { pool2[0] = g.T2; pool2[1] = g.H2; pool2[2] = g.W2; }
     if (tiles) { tiles[0] = g.conv1_tiles; tiles[1] = g.conv2_tiles; tiles[2] = g.conv3_tiles; }
     if (n_launches) *n_launches = 5;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// CNN-LSTM (rva_clip.hip, rva_clip_f16.hip; the host plan over both is rva_clip_host.h): per frame the stem (conv1 7x7 s2 p3 + pool
+// 3x3 s2 p1) and conv2 3x3 p1 + mean, per clip a 2-layer LSTM and the head.
+constexpr int CL_C1 = 64, CL_C2 = 128, CL_K1 = 7;          // stem widths of the architecture
+constexpr int CL_PT = 8;                                   // pooled tile (PT x PT) of a K_stem block; K_conv2: 256 pixels
+constexpr int CL_MAX_HIDDEN = 1024, CL_MAX_T = 64;
+constexpr int CL_STAGES = RVA_CNNLSTM_STAGE_H2 + 1;
+
+struct rva_cl_geom {
+    int Hc, Wc, Hp, Wp;              // conv1's map and the pooled map
+    int conv2_tiles;
+    int64_t elems[CL_STAGES];        // elements of a RVA_CNNLSTM_STAGE_* per clip
+    bool pitched[CL_STAGES];         // stored [T][max_clips][hidden]: fewer clips than the capacity are T rows out of that pitch
+};
+
+inline rva_cl_geom rva_cl_geometry(const rva_cnnlstm_desc &d)
+{
+    rva_cl_geom g{};
+    rva_stem_maps(d.height, d.width, &g.Hc, &g.Wc, &g.Hp, &g.Wp);
+    g.conv2_tiles = rva_ceil_div(g.Hp * g.Wp, 256);
+    const int64_t T = d.frames;
+    g.elems[RVA_CNNLSTM_STAGE_POOLED] = T * g.Hp * g.Wp * CL_C1;
+    g.elems[RVA_CNNLSTM_STAGE_PARTIAL] = T * g.conv2_tiles * CL_C2;
+    g.elems[RVA_CNNLSTM_STAGE_FEAT] = T * CL_C2;
+    g.elems[RVA_CNNLSTM_STAGE_GX] = T * 4 * d.hidden;
+    g.elems[RVA_CNNLSTM_STAGE_H1] = g.elems[RVA_CNNLSTM_STAGE_H2] = T * d.hidden;
+    g.pitched[RVA_CNNLSTM_STAGE_H1] = g.pitched[RVA_CNNLSTM_STAGE_H2] = true;
+    return g;
+}
+
+// The argument checks of a create, under the entry's name; clears *out.  `refuse_large`: the fp16 entry also refuses what its
+// 16-bit grid rows and 32-bit frame offsets cannot hold.  The fp32 entry has never refused it, and a new refusal is a change of
+// behaviour that wants its own change.
+inline int rva_cl_check_args(rva_ctx *ctx, const char *who, bool refuse_large, const rva_cnnlstm_desc *d, const rva_cnnlstm_weights *wt,
+                             void **out)
+{
+    if (!ctx || !d || !wt || !out) return rva_fail(ctx, RVA_ERR_ARG, "%s: null argument", who);
+    *out = nullptr;
+    if (d->height < 2 || d->width < 2 || d->frames < 1 || d->frames > CL_MAX_T || d->hidden < 1 || d->hidden > CL_MAX_HIDDEN ||
+        d->classes < 1 || d->classes > RVA_PLAN_MAX_CLASSES || d->max_clips < 1 ||
+        (refuse_large && ((int64_t)d->max_clips * d->frames > 65535 || (int64_t)d->height * d->width > (1 << 26))))
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: bad descriptor (frames 1..%d, hidden 1..%d, classes 1..%d, max_clips >= 1%s)", who, CL_MAX_T,
+                        CL_MAX_HIDDEN, RVA_PLAN_MAX_CLASSES, refuse_large ? ", max_clips * frames <= 65535" : "");
+    if (!wt->conv1_w || !wt->conv1_b || !wt->conv2_w || !wt->conv2_b || !wt->w_ih1 || !wt->b1 || !wt->w_hh1 || !wt->w_ih2 ||
+        !wt->w_hh2 || !wt->b2 || !wt->head_w || !wt->head_b)
+        return rva_fail(ctx, RVA_ERR_ARG, "%s: every weight array is required", who);
+    return RVA_OK;
+}
+
+// stem, conv2, mean, xproj; the frames + 1 diagonal LSTM launches; head
+inline void rva_cl_info(const rva_cnnlstm_desc &d, const rva_cl_geom &g, int32_t *pooled_h, int32_t *pooled_w, int32_t *conv2_tiles,
+                        int32_t *n_launches)
+{
+    if (pooled_h) *pooled_h = g.Hp;
+    if (pooled_w) *pooled_w = g.Wp;
+    if (conv2_tiles) *conv2_tiles = g.conv2_tiles;
+    if (n_launches) *n_launches = 4 + (d.frames + 1) + 1;
 }

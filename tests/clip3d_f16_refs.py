@@ -1,4 +1,4 @@
-"""Float64 references and derived bounds for the fp16 3D-CNN clip plan (csrc/rva_clip3d_f16.hip, engine ``clip3d-f16``), shared by
+"""Float64 references and derived bounds for the fp16 3D-CNN clip plan (csrc/rva_clip3d.hip, engine ``clip3d-f16``), shared by
 tests/test_clip3d_f16_host.py (CPU) and the GPU tests.  Built on tests/clip_stage_refs.py: the same per-stage references, each
 computed from the tap of the stage before it, on the fp16 frames and the fp16-rounded convolution weights the plan itself holds.
 

@@ -1,4 +1,4 @@
-"""The fp16 3D-CNN clip plan (clip_plan.Fused3dCnnF16, csrc/rva_clip3d_f16.hip, engine ``clip3d-f16``) on the GPU: golden, odd and
+"""The fp16 3D-CNN clip plan (clip_plan.Fused3dCnnF16, csrc/rva_clip3d.hip, engine ``clip3d-f16``) on the GPU: golden, odd and
 ragged logits against the float64 quantised network and the original module, bit-reproducibility, the top-5 rule, the create
 refusals, the detector and the pipeline with ``half: true`` + ``hip_engine: native`` + ``hip_clip_fp16: true``, the unchanged
 routing of every neighbouring combination, and the sample YAML's ``slow_fast`` section (256 x 256, T = 32).

@@ -1,4 +1,4 @@
-"""Every stage of the fp16 3D-CNN clip plan (csrc/rva_clip3d_f16.hip) against float64 on the GPU, through the read-only workspace
+"""Every stage of the fp16 3D-CNN clip plan (csrc/rva_clip3d.hip) against float64 on the GPU, through the read-only workspace
 tap ``rva_cnn3d_f16_plan_stage``: conv1's pooled fp16 map (fp16 frames with an odd row length, zero temporal padding), conv2's
 pooled fp16 map (the fp16 MFMA's lane-half operand layout, the pool-in-epilogue shuffle), conv3's fp32 tile partials, the mean
 and the logits.  Each stage's reference is computed from the tap of the stage before it with the bounds of
