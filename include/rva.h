@@ -1163,6 +1163,63 @@ int rva_jpeg_batch_encode(rva_jpeg_batch *enc, int n, const void *const *bgr, co
                           const int32_t *height, const int32_t *quality, void *out, int64_t out_capacity, int32_t *out_sizes,
                           rva_stream_t stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * K8 device JPEG decoder -- stands where VideoStream.open() / frames() sit on cv2.VideoCapture(url) (video_stream.py:76,173)
+ * for Motion-JPEG sources: baseline JPEG pictures in HOST memory -> frames in HBM.  Accepted: SOF0, 8-bit samples, Huffman
+ * coding, one interleaved scan; 1 component, or Y/Cb/Cr with chroma 1x1 and luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0);
+ * 8-bit DQT, any DHT, optional DRI; JFIF or no APP marker, Adobe APP14 with transform 1.  Everything else is refused on the
+ * host by the marker walk, before anything is launched, with a message that names what was found.
+ * Output formats: RVA_JPEG_DEC_BGR -- uint8 [h][w][3] with the given pitch, libjpeg's own picture (islow IDCT, fancy
+ * upsampling, jdcolor.c), bit for bit what cv2.imdecode and Pillow's libjpeg-turbo give for streams a real encoder made (where
+ * libjpeg's range-limit table wraps for sums far outside 0..255, this decoder saturates).  RVA_JPEG_DEC_NV12 -- dst0 a
+ * pitch-linear Y plane, dst1 an interleaved CbCr plane of the same pitch, in the BT.601 limited range that
+ * rva_preprocess_nv12_batch assumes: Y' = 16 + (219 Y + 127) / 255, C' = 128 + (224 (C - 128) +- 127) / 255 (the sign of the 127
+ * follows C - 128, the division truncates); the chroma pair is the decoded 4:2:0 sample, (a + b + 1) >> 1 of the two 4:2:2 rows,
+ * (a + b + c + d + 2) >> 2 of the 4:4:4 group, 128 for grayscale.  Even width and height only in this format.
+ * One lane decodes one restart interval: a stream without DRI is decoded by ONE lane per picture.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct rva_jpeg_dec rva_jpeg_dec;
+enum rva_jpeg_dec_format { RVA_JPEG_DEC_BGR = 0, RVA_JPEG_DEC_NV12 = 1 };
+enum rva_jpeg_dec_result { RVA_JPEG_DEC_OK = 0, RVA_JPEG_DEC_REFUSED = -1, RVA_JPEG_DEC_FAILED = -2 };
+typedef struct rva_jpeg_dec_info {
+    int32_t width, height, components;
+    int32_t h_samp, v_samp;          /* luma sampling factors (chroma is 1x1): 1 1 = 4:4:4 or grayscale, 2 1 = 4:2:2, 2 2 = 4:2:0 */
+    int32_t restart_interval;        /* MCUs per restart interval (DRI), 0: none */
+    int32_t intervals;               /* restart intervals of the scan: the lanes that decode it */
+    int32_t mcus;
+} rva_jpeg_dec_info;
+
+/* video_stream.py:76,173 (what cap.isOpened() / cap.read() find out about a source): host only, no context.  RVA_OK and *info,
+ * or RVA_ERR_ARG and the refusal in msg (msg_len bytes, always terminated). */
+int rva_jpeg_dec_probe(const uint8_t *data, int64_t len, rva_jpeg_dec_info *info, char *msg, int msg_len);
+
+/* video_stream.py:76,173: the decoder object owns every buffer a decode touches, device and pinned, for up to max_images
+ * pictures of up to max_width x max_height whose entropy segments hold up to max_bytes_per_image bytes each.  After _create
+ * nothing allocates. */
+int rva_jpeg_dec_create(rva_ctx *ctx, int max_images, int max_width, int max_height, int max_bytes_per_image, rva_jpeg_dec **out);
+void rva_jpeg_dec_destroy(rva_jpeg_dec *dec);
+
+/* video_stream.py:76,173: n streams (HOST arrays of n host pointers / lengths) -> dst0[i] (and dst1[i] for NV12), device
+ * pointers with pitch[i] bytes per row; sizes and sampling mixed freely.  One async copy of a pinned blob (descriptors,
+ * restart-interval table, entropy segments) and a fixed number of launches whatever n, all on `stream`; the host memory is
+ * free to reuse on return.  RVA_ERR_ARG (nothing launched): n outside 1..max_images, a missing destination or a short pitch
+ * for a picture the parser accepts, an odd size with NV12.  A stream the parser refuses, or one beyond the object's limits,
+ * does not fail the call: that picture is skipped (its destination may be NULL), rva_jpeg_dec_status reports it, and
+ * rva_last_error holds the first such refusal. */
+int rva_jpeg_dec_decode(rva_jpeg_dec *dec, int n, const uint8_t *const *data, const int64_t *len, int format, void *const *dst0,
+                        void *const *dst1, const int32_t *pitch, rva_stream_t stream);
+
+/* video_stream.py:76,173 (the `ok` of cap.read()): waits for the stream of the last _decode, then status[i] of its n pictures:
+ * RVA_JPEG_DEC_OK, RVA_JPEG_DEC_REFUSED (by the parser, nothing was launched for it) or RVA_JPEG_DEC_FAILED (on the device:
+ * a code in no table, a run past coefficient 63, broken byte stuffing, an interval that ran dry or had bytes left over).  A
+ * failed picture's destination holds nothing a caller may rely on; its neighbours are intact. */
+int rva_jpeg_dec_status(rva_jpeg_dec *dec, int32_t *status);
+
+/* video_stream.py:76,173 (where the time of a cap.read() goes): device time of the last _decode's four steps in milliseconds,
+ * from events the call records on its stream -- ms[0] the blob's copy, ms[1] entropy decoding, ms[2] IDCT, ms[3] the output
+ * kernel.  Waits for that call.  RVA_ERR_ARG if it launched nothing (every picture refused). */
+int rva_jpeg_dec_times(rva_jpeg_dec *dec, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

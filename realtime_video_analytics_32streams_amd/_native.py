@@ -19,7 +19,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB_PATH = Path(os.environ["RVA_LIB_PATH"]) if os.environ.get("RVA_LIB_PATH") else PKG / "librva.so"   # override: diagnostic builds (tools/)
 SOURCES = ["rva_ctx.hip", "rva_preprocess.hip", "rva_postprocess.hip", "rva_tracker.hip", "rva_conv.hip", "rva_stem.hip", "rva_yolo_ops.hip", "rva_conv_f32.hip", "rva_attn.hip", "rva_plan.hip", "rva_clip.hip",
-           "rva_clip3d.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip"]
+           "rva_clip3d.hip", "rva_clip_f16.hip", "rva_resnet.hip", "rva_resnet_f16.hip", "rva_gates.hip", "rva_decode.hip", "rva_preview.hip", "rva_jpeg.hip", "rva_jpeg_dec.hip"]
 # -ffp-contract=off: parity kernels must not fuse a*b+c (SURVEY.md hard part 4)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function"]
@@ -30,6 +30,8 @@ NORM_IMAGENET_F32, NORM_VIDEO_F32, NORM_IMAGENET_F64 = 0, 1, 2      # enum rva_f
 LAYOUT_NCHW, LAYOUT_CNHW = 0, 1                                    # enum rva_frame_layout
 RVA_MAX_BATCH = 64
 RVA_CODEC_H264, RVA_CODEC_HEVC = 0, 1
+RVA_JPEG_DEC_BGR, RVA_JPEG_DEC_NV12 = 0, 1                          # enum rva_jpeg_dec_format
+RVA_JPEG_DEC_OK, RVA_JPEG_DEC_REFUSED, RVA_JPEG_DEC_FAILED = 0, -1, -2   # enum rva_jpeg_dec_result
 
 
 class Letterbox(C.Structure):
@@ -131,6 +133,11 @@ class PreviewItem(C.Structure):
     """``rva_preview_item`` (include/rva.h): one surface of ``rva_preview_nv12_batch``."""
     _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("out_bgr", C.c_void_p)] + [
         (n, C.c_int32) for n in ("pitch", "src_w", "src_h", "ratio", "dst_w", "dst_h", "rect_first", "n_rects", "glyph_first", "n_glyphs")]
+
+
+class JpegDecInfo(C.Structure):
+    """``rva_jpeg_dec_info`` (include/rva.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "intervals", "mcus")]
 
 
 RVA_PLAN_NO_STEM2 = 1
@@ -363,6 +370,12 @@ def lib() -> C.CDLL:
         "rva_jpeg_batch_destroy": (None, [_P]),
         "rva_jpeg_batch_encode": (C.c_int, [_P, C.c_int, pp, i32p, i32p, i32p, i32p, _P, C.c_int64, _P, _P]),
         "rva_preview_nv12_batch": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+        "rva_jpeg_dec_probe": (C.c_int, [C.c_char_p, C.c_int64, C.POINTER(JpegDecInfo), C.c_char_p, C.c_int]),
+        "rva_jpeg_dec_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+        "rva_jpeg_dec_destroy": (None, [_P]),
+        "rva_jpeg_dec_decode": (C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), i64p, C.c_int, pp, pp, i32p, _P]),
+        "rva_jpeg_dec_status": (C.c_int, [_P, i32p]),
+        "rva_jpeg_dec_times": (C.c_int, [_P, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == header/library mismatch: fail loudly
@@ -407,6 +420,7 @@ EXPORTS = [
     "rva_yolo11_plan_create", "rva_dwconv3x3_nhwc_f16", "rva_psa_attention_f16", "rva_yolov8_plan_step_desc",
     "rva_resnetx_f16_plan_create", "rva_resnetx_f16_plan_destroy", "rva_resnetx_f16_plan_info", "rva_resnetx_f16_plan_run",
     "rva_resnetx_f16_plan_run_post", "rva_resnetx_f16_plan_stage",
+    "rva_jpeg_dec_probe", "rva_jpeg_dec_create", "rva_jpeg_dec_destroy", "rva_jpeg_dec_decode", "rva_jpeg_dec_status", "rva_jpeg_dec_times",
 ]
 
 

@@ -803,6 +803,143 @@ class JpegBatchEncoder:
             pass
 
 
+# ------------------------------------------------------------------------------------------ K8
+def jpeg_probe(data: bytes) -> dict:
+    """``rva_jpeg_dec_probe``: the marker walk of K8's host half (no GPU, no context).  Geometry, components, luma sampling
+    factors, restart interval and the number of restart intervals (= lanes that decode the scan) of a baseline JPEG stream;
+    ``ValueError`` with the parser's refusal for anything K8 does not take."""
+    data = bytes(data)
+    info, msg = N.JpegDecInfo(), C.create_string_buffer(256)
+    if N.lib().rva_jpeg_dec_probe(data, len(data), C.byref(info), msg, 256) != N.RVA_OK:
+        raise ValueError(f"jpeg_probe: {msg.value.decode(errors='replace')}")
+    sampling = "gray" if info.components == 1 else {(1, 1): "4:4:4", (2, 1): "4:2:2", (2, 2): "4:2:0"}[(info.h_samp, info.v_samp)]
+    return dict(width=info.width, height=info.height, components=info.components, h_samp=info.h_samp, v_samp=info.v_samp,
+                sampling=sampling, restart_interval=info.restart_interval, intervals=info.intervals, mcus=info.mcus)
+
+
+class JpegBatchDecoder:
+    """Batched K8 (``rva_jpeg_dec_*``): ``n <= max_images`` baseline JPEG streams (host bytes), each up to ``max_wh`` pixels and
+    ``max_bytes`` bytes, sizes and sampling mixed, decoded on the device by ONE launch set.  ``decode`` returns, per stream, a
+    uint8 BGR tensor ``[h, w, 3]`` (``fmt="bgr"``: libjpeg's own picture) or an :class:`Nv12Surface` (``fmt="nv12"``: BT.601
+    limited range, even sizes only), or ``None`` for a stream the parser refuses or that fails on the device; ``status`` keeps the
+    codes of the last call and ``errors`` the parser's words.  One object serves one stream at a time; distinct objects are
+    independent on distinct streams and threads."""
+
+    def __init__(self, max_images: int, max_wh: Tuple[int, int] = (1920, 1080), max_bytes: int = 1 << 20, ctx: Optional[N.Context] = None):
+        self.ctx = ctx or context()
+        self.max_images, self.max_wh, self.max_bytes = int(max_images), (int(max_wh[0]), int(max_wh[1])), int(max_bytes)
+        h = C.c_void_p()
+        self.ctx.check(N.lib().rva_jpeg_dec_create(self.ctx.handle, self.max_images, self.max_wh[0], self.max_wh[1], self.max_bytes,
+                                                   C.byref(h)), "rva_jpeg_dec_create")
+        self.handle = h
+        self.status: List[int] = []
+        self.errors: List[Optional[str]] = []
+
+    def _probe(self, data: bytes) -> Optional[dict]:
+        try:
+            info = jpeg_probe(data)
+        except ValueError as exc:
+            self.errors.append(str(exc))
+            return None
+        if info["width"] > self.max_wh[0] or info["height"] > self.max_wh[1]:
+            self.errors.append(f"a picture of {info['width']}x{info['height']}, the decoder was created for up to {self.max_wh[0]}x{self.max_wh[1]}")
+            return None
+        self.errors.append(None)
+        return info
+
+    def decode(self, datas: Sequence[bytes], fmt: str = "bgr", out: Optional[Sequence] = None, pitch: Optional[int] = None) -> list:
+        """``out``: optional destinations, one per stream (BGR tensors / :class:`Nv12Surface` of the stream's size), else they are
+        allocated here with ``pitch`` bytes per row (default: packed)."""
+        if fmt not in ("bgr", "nv12"):
+            raise ValueError("fmt is 'bgr' or 'nv12'")
+        datas = [bytes(d) for d in datas]
+        n = len(datas)
+        nv12 = fmt == "nv12"
+        dev = torch.device("cuda", self.ctx.device)
+        self.errors = []
+        infos = [self._probe(d) for d in datas]
+        res: list = []
+        for i, info in enumerate(infos):
+            if info is None:
+                res.append(None)
+                continue
+            w, h = info["width"], info["height"]
+            if nv12 and (w | h) & 1:
+                raise RuntimeError(f"JpegBatchDecoder: image {i} is {w}x{h}, NV12 output takes even sizes only")
+            if out is not None:
+                res.append(out[i])
+            elif nv12:
+                p = int(pitch or w)
+                res.append(Nv12Surface(torch.empty((h, p), dtype=torch.uint8, device=dev), torch.empty((h // 2, p), dtype=torch.uint8, device=dev), w, h))
+            else:
+                p = int(pitch or 3 * w)
+                res.append(torch.empty((h, p), dtype=torch.uint8, device=dev)[:, :3 * w].unflatten(1, (w, 3)))
+            o = res[-1]
+            if nv12 and (not isinstance(o, Nv12Surface) or (o.width, o.height) != (w, h) or o.uv.stride(0) != o.y.stride(0)):
+                raise ValueError(f"JpegBatchDecoder: image {i} needs an Nv12Surface of {w}x{h} with one pitch for both planes")
+            if not nv12:
+                _require_cuda(o, "out")
+                if o.dtype != torch.uint8 or tuple(o.shape) != (h, w, 3) or o.stride(2) != 1 or o.stride(1) != 3:
+                    raise ValueError(f"JpegBatchDecoder: image {i} needs a uint8 [{h}, {w}, 3] device tensor with packed pixels")
+        ptrs = (C.c_char_p * n)(*datas)
+        lens = (C.c_int64 * n)(*[len(d) for d in datas])
+        d0, keep0 = N.ptr_array([0 if o is None else (o.y.data_ptr() if nv12 else o.data_ptr()) for o in res])
+        d1, keep1 = N.ptr_array([0 if o is None or not nv12 else o.uv.data_ptr() for o in res])
+        pt, keep2 = N.i32_array([0 if o is None else (o.y.stride(0) if nv12 else o.stride(0)) for o in res])
+        L = N.lib()
+        self.ctx.check(L.rva_jpeg_dec_decode(self.handle, n, ptrs, lens, N.RVA_JPEG_DEC_NV12 if nv12 else N.RVA_JPEG_DEC_BGR, d0, d1, pt,
+                                             _stream_ptr()), "rva_jpeg_dec_decode")
+        st = (C.c_int32 * n)()
+        self.ctx.check(L.rva_jpeg_dec_status(self.handle, st), "rva_jpeg_dec_status")
+        self.status = list(st)
+        for i, v in enumerate(self.status):
+            if v != N.RVA_JPEG_DEC_OK:
+                if self.errors[i] is None:
+                    self.errors[i] = "refused by the decoder object's limits" if v == N.RVA_JPEG_DEC_REFUSED else "the entropy segment is damaged"
+                res[i] = None
+        return res
+
+    def times(self) -> dict:
+        """Device milliseconds of the last ``decode``'s steps (``rva_jpeg_dec_times``): copy, entropy, idct, output."""
+        ms = (C.c_float * 4)()
+        self.ctx.check(N.lib().rva_jpeg_dec_times(self.handle, ms), "rva_jpeg_dec_times")
+        return dict(zip(("copy_ms", "entropy_ms", "idct_ms", "output_ms"), (float(v) for v in ms)))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            torch.cuda.synchronize(self.ctx.device)
+            N.lib().rva_jpeg_dec_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def jpeg_decode_bgr(data: bytes, ctx: Optional[N.Context] = None) -> torch.Tensor:
+    """K8 for one picture: baseline JPEG bytes -> the uint8 BGR image ``[h, w, 3]`` in HBM that ``cv2.imdecode`` gives on the host,
+    bit for bit.  ``ValueError`` for a stream the parser refuses, ``RuntimeError`` for one that fails on the device.  The decoder
+    object is kept per context and regrown for a larger picture (streams in a steady state take a :class:`JpegBatchDecoder`)."""
+    ctx = ctx or context()
+    data = bytes(data)
+    info = jpeg_probe(data)
+    with _JPEG_LOCK:
+        dec = ctx.__dict__.get("_jpeg_dec")
+        if dec is None or info["width"] > dec.max_wh[0] or info["height"] > dec.max_wh[1] or len(data) > dec.max_bytes:
+            w = max(info["width"], dec.max_wh[0] if dec else 0)
+            h = max(info["height"], dec.max_wh[1] if dec else 0)
+            nb = max(len(data), dec.max_bytes if dec else 1 << 16)
+            if dec is not None:
+                dec.close()
+            dec = ctx.__dict__["_jpeg_dec"] = JpegBatchDecoder(1, (w, h), nb, ctx)
+        img = dec.decode([data], "bgr")[0]
+        if img is None:
+            raise RuntimeError(f"device JPEG decoder: {dec.errors[0]}")
+        return img
+
+
 class PreviewStaging:
     """Pinned host table + its device copy for :func:`preview_nv12_batch` (grown on demand, outside the steady path)."""
 

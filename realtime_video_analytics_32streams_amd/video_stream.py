@@ -16,6 +16,8 @@ Sources:
     images, so ``open()`` raises ``RuntimeError`` there -- exactly as the reference raises when a stream
     cannot be opened (video_stream.py:78-79) -- and decode throughput is reported as "not measured",
     never substituted.
+  * :class:`MjpegStream` -- Motion-JPEG files and JPEG stills through K8, the device JPEG decoder of
+    ``csrc/rva_jpeg_dec.hip``: the one path from compressed bytes to frames that runs on every machine of this project.
 """
 from __future__ import annotations
 
@@ -366,10 +368,193 @@ def _annexb_access_units(data: bytes, codec: int):
         yield b"".join(mp4.START_CODE + x for x in cur), n * 333_667, True
 
 
+def iter_jpeg_frames(data: bytes):
+    """The JPEG pictures of a file of concatenated JPEGs (a Motion-JPEG stream), split by walking markers: from SOI, every marker
+    segment is skipped by its length -- so an embedded thumbnail inside an APPn segment does not split a frame -- and inside
+    the entropy data after SOS ``0xFF`` is followed only by ``0x00`` (a stuffed byte), ``0xFF`` (fill) or ``RSTn``; any other
+    marker ends the scan.  Bytes between pictures, and trailing bytes that start no picture, are dropped; a picture cut off by the
+    end of the file is yielded as it is (the decoder refuses or fails it)."""
+    data = bytes(data)
+    n, p = len(data), 0
+    while True:
+        p = data.find(b"\xff\xd8", p)
+        if p < 0:
+            return
+        start, p = p, p + 2
+        while True:
+            # a marker: 0xFF, fill 0xFF, the code
+            while p < n and data[p] != 0xFF:
+                p += 1                                    # (junk where a marker should be: resynchronise)
+            while p < n and data[p] == 0xFF:
+                p += 1
+            if p >= n:
+                yield data[start:]
+                return
+            m = data[p]
+            p += 1
+            if m == 0xD9:
+                yield data[start:p]
+                break
+            if m in (0x00, 0x01, 0xD8) or 0xD0 <= m <= 0xD7:
+                continue
+            if p + 2 > n:
+                yield data[start:]
+                return
+            p += (data[p] << 8) | data[p + 1]
+            if m != 0xDA:
+                continue
+            while True:                                   # entropy data: to the next marker that is not RSTn
+                p = data.find(b"\xff", p)
+                if p < 0 or p + 1 >= n:
+                    yield data[start:]
+                    return
+                if data[p + 1] == 0x00 or 0xD0 <= data[p + 1] <= 0xD7:
+                    p += 2
+                elif data[p + 1] == 0xFF:
+                    p += 1
+                else:
+                    break
+
+
+class MjpegStream(_BaseStream):
+    """Motion-JPEG -> NV12 in HBM through K8 (``csrc/rva_jpeg_dec.hip``): the capture plugin for JPEG camera streams, what
+    ``cv2.VideoCapture(url)`` is to the reference for such a source (video_stream.py:76,173).
+
+    Sources: a local ``.mjpeg`` / ``.mjpg`` file of concatenated baseline JPEGs (with or without ``file://``), or one ``.jpg`` /
+    ``.jpeg`` still, a one-frame stream.  ``open_sync`` raises ``RuntimeError("Unable to open stream ...")`` for a missing or empty
+    file and for a first frame the parser refuses (or whose size is odd: NV12 takes even sizes).  ``next_surface`` decodes the
+    next frame into a ring of ``hold + 1`` NV12 surfaces of the stream's own, so a surface handed out stays valid for ``hold``
+    further frames.  It returns ``None`` at the end of the file and for a frame that fails: a failed read, which the inherited
+    capture loop turns into back-off and, after three of them, a reopen from frame 0.
+    """
+
+    SUFFIXES = (".mjpeg", ".mjpg", ".jpg", ".jpeg")
+
+    def __init__(self, stream_config: StreamConfig, device: Optional[int] = None, hold: int = 4):
+        super().__init__(stream_config)
+        self.device_index, self.hold = device, int(hold)
+        self._frames: list = []
+        self._pos = 0
+        self._ring: list = []
+        self._dec = None
+        self.info: dict = {}
+
+    def _fail(self, why: str):
+        return RuntimeError(f"Unable to open stream {self.config.name}: {why}")
+
+    def _read_source(self) -> None:
+        from pathlib import Path
+        from . import ops
+        url = self.config.url
+        if "://" in url and not url.startswith("file://"):
+            raise self._fail("network sources are not Motion-JPEG files (local .mjpeg / .mjpg / .jpg / .jpeg only)")
+        path = Path(url[7:] if url.startswith("file://") else url)
+        if not path.is_file():
+            raise self._fail(f"{path} does not exist")
+        try:
+            data = path.read_bytes()
+        except OSError as exc:
+            raise self._fail(str(exc)) from exc
+        if not data:
+            raise self._fail(f"{path} is empty")
+        frames = list(iter_jpeg_frames(data))
+        if not frames:
+            raise self._fail(f"{path} holds no JPEG picture")
+        try:
+            info = ops.jpeg_probe(frames[0])
+        except ValueError as exc:
+            raise self._fail(f"first frame: {exc}") from exc
+        if (info["width"] | info["height"]) & 1:
+            raise self._fail(f"first frame is {info['width']}x{info['height']}: NV12 surfaces take even sizes")
+        self._frames, self.info = frames, dict(info, codec="mjpeg", frames=len(frames))
+
+    def open_sync(self) -> None:
+        from . import ops
+        self._read_source()
+        if self._dec is None:
+            ctx = ops.context(self.device_index)
+            w, h = self.info["width"], self.info["height"]
+            self._dec = ops.JpegBatchDecoder(1, (w, h), max(len(f) for f in self._frames), ctx)
+        self._pos = 0
+        super().open_sync()
+
+    def close_sync(self) -> None:
+        self._frames = []
+        super().close_sync()
+
+    def _slot(self) -> Nv12Surface:
+        """The ring surface the next frame decodes into (allocated on first use, then recycled every hold + 1 frames)."""
+        w, h = self.info["width"], self.info["height"]
+        if len(self._ring) <= self.hold:
+            dev = torch.device("cuda", self._dec.ctx.device)
+            pitch = ((w + 255) // 256) * 256
+            self._ring.append(Nv12Surface(torch.zeros((h, pitch), dtype=torch.uint8, device=dev),
+                                          torch.zeros((h // 2, pitch), dtype=torch.uint8, device=dev), w, h))
+            return self._ring[-1]
+        self._ring.append(self._ring.pop(0))
+        return self._ring[-1]
+
+    def _take(self):
+        """(bytes, surface) of the next frame, or None: the file is at its end, or the frame does not fit the stream's surfaces."""
+        if not self._opened or self._pos >= len(self._frames):
+            return None
+        from . import ops
+        data = self._frames[self._pos]
+        self._pos += 1
+        try:
+            info = ops.jpeg_probe(data)
+        except ValueError as exc:
+            LOGGER.warning("stream '%s': frame %d refused (%s)", self.config.name, self._pos - 1, exc)
+            return None
+        if (info["width"], info["height"]) != (self.info["width"], self.info["height"]):
+            LOGGER.warning("stream '%s': frame %d is %dx%d, the stream opened as %dx%d", self.config.name, self._pos - 1, info["width"],
+                           info["height"], self.info["width"], self.info["height"])
+            return None
+        return data, self._slot()
+
+    def next_surface(self) -> Optional[Nv12Surface]:
+        item = self._take()
+        if item is None:
+            return None
+        return self._dec.decode([item[0]], "nv12", out=[item[1]])[0]
+
+    @staticmethod
+    def next_packets(streams, decoder=None) -> list:
+        """The next frame of every stream with ONE ``decode`` call on a shared decoder (``decoder``, or one kept for this set of
+        streams): the packets ``[s.next_packet() for s in streams]`` would give, ``None`` for a stream at its end or whose frame
+        fails."""
+        from . import ops
+        streams = list(streams)
+        for s in streams:
+            if not s._opened:
+                s.open_sync()
+        items = [s._take() for s in streams]
+        live = [i for i, it in enumerate(items) if it is not None]
+        out: list = [None] * len(streams)
+        if not live:
+            return out
+        if decoder is None:
+            w = max(s.info["width"] for s in streams)
+            h = max(s.info["height"] for s in streams)
+            nb = max(len(f) for s in streams for f in s._frames)
+            owner = streams[0]
+            shared = getattr(owner, "_shared_dec", None)
+            if shared is None or shared.max_images < len(streams) or shared.max_wh[0] < w or shared.max_wh[1] < h or shared.max_bytes < nb:
+                shared = owner._shared_dec = ops.JpegBatchDecoder(len(streams), (w, h), nb, owner._dec.ctx)
+            decoder = shared
+        surfs = decoder.decode([items[i][0] for i in live], "nv12", out=[items[i][1] for i in live])
+        for i, surf in zip(live, surfs):
+            out[i] = None if surf is None else streams[i]._packet(surf)
+        return out
+
+
 def open_stream(cfg: StreamConfig, index: int = 0, **kw) -> _BaseStream:
-    """``synthetic://WxH`` urls select the generator; anything else is a bitstream for rocDecode."""
+    """``synthetic://WxH`` urls select the generator, ``.mjpeg`` / ``.mjpg`` / ``.jpg`` / ``.jpeg`` files the device JPEG decoder;
+    anything else is a bitstream for rocDecode."""
     if cfg.url.startswith("synthetic://"):
         spec = cfg.url[len("synthetic://"):] or "1920x1080"
         w, h = (int(v) for v in spec.lower().split("x"))
         return SyntheticNv12Stream(cfg, index=index, width=w, height=h, **kw)
+    if cfg.url.lower().endswith(MjpegStream.SUFFIXES) and ("://" not in cfg.url or cfg.url.startswith("file://")):
+        return MjpegStream(cfg)
     return RocDecodeStream(cfg)
