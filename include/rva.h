@@ -1167,7 +1167,8 @@ int rva_jpeg_batch_encode(rva_jpeg_batch *enc, int n, const void *const *bgr, co
  * K8 device JPEG decoder -- stands where VideoStream.open() / frames() sit on cv2.VideoCapture(url) (video_stream.py:76,173)
  * for Motion-JPEG sources: baseline JPEG pictures in HOST memory -> frames in HBM.  Accepted: SOF0, 8-bit samples, Huffman
  * coding, one interleaved scan; 1 component, or Y/Cb/Cr with chroma 1x1 and luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0);
- * 8-bit DQT, any DHT, optional DRI; JFIF or no APP marker, Adobe APP14 with transform 1.  Everything else is refused on the
+ * 8-bit DQT, any DHT, optional DRI; JFIF, Adobe APP14 with transform 1 or neither -- three components are YCbCr as libjpeg
+ * decides it: RGB samples (ids 'R','G','B' without JFIF or Adobe; Adobe transform 0) are refused.  Everything else is refused on the
  * host by the marker walk, before anything is launched, with a message that names what was found.
  * Output formats: RVA_JPEG_DEC_BGR -- uint8 [h][w][3] with the given pitch, libjpeg's own picture (islow IDCT, fancy
  * upsampling, jdcolor.c), bit for bit what cv2.imdecode and Pillow's libjpeg-turbo give for streams a real encoder made (where

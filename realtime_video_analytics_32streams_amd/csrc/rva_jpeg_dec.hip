@@ -16,8 +16,9 @@
 //               jinit_upsampler chooses) and jdcolor.c's 16-bit fixed-point YCbCr -> RGB.
 //   k8_nv12     one thread per 2x2 pixels: Y' = 16 + (219 Y + 127) / 255, C' = 128 + (224 (C - 128) +- 127) / 255 (truncating), the
 //               chroma pair the decoded 4:2:0 sample, the rounded mean of the two 4:2:2 rows or of the 2x2 4:4:4 group, 128 for gray.
-// libjpeg's range-limit table WRAPS for sums far outside 0..255 where these kernels saturate; streams from a real encoder never
-// get there, and the tests use encoder-made streams.
+// libjpeg's range-limit table WRAPS for IDCT sums outside [-512, 511] (before the +128) where these kernels saturate; streams
+// from a real encoder never get there.  The tests use encoder-made streams and hand-built ones (tests/jpeg_craft.py: every table
+// selection, 9..16-bit codes, block shapes and stuffing no encoder writes, each failure below on its own) that stay inside it.
 //
 // k8_entropy reads bytes from the outside world.  What keeps it in range whatever they hold:
 //   * a byte is fetched only at pos < end of the lane's interval (K8Bits::fill); past the end the reader feeds zero bits and

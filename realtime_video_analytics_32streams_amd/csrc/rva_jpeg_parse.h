@@ -8,8 +8,14 @@
 // natural order -- and the byte range of every restart interval of the entropy segment (an image without DRI is one interval).
 //
 // Accepted: SOF0, 8-bit samples, Huffman coding, ONE interleaved scan; 1 component, or Y/Cb/Cr with chroma 1x1 and luma 1x1
-// (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); 8-bit DQT; any DHT (ids 0 and 1); optional DRI; JFIF or no APP marker; Adobe APP14 with
-// transform 1.  Everything else is refused with a message that names what was found.
+// (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); 8-bit DQT, ids 0..3; any DHT (ids 0 and 1); a table defined again (the last definition
+// before SOS holds) and several tables in one segment; tables and DRI before or after SOF0; optional DRI (the last one holds, 0
+// or a count >= the MCUs: one interval); fill 0xFF in front of any marker; APPn / COM of any content (skipped by their length).
+// The colour space of three components follows libjpeg's default_decompress_parms, which is what cv2.imdecode and Pillow show:
+// a JFIF APP0 says YCbCr; else an Adobe APP14 decides by its transform (1: YCbCr); else component ids 1,2,3 are YCbCr, ids
+// 'R','G','B' are RGB samples, any other ids YCbCr.  RGB samples are refused (there is no colour conversion to leave out here),
+// and so is every Adobe transform but 1, also beside a JFIF marker, where libjpeg would believe JFIF: the two contradict each
+// other.  Everything else is refused with a message that names what was found.
 #pragma once
 
 #include <cstdarg>
@@ -121,6 +127,7 @@ inline int parse(const uint8_t *s, size_t len, rva_jpeg_desc &d, uint32_t *ivals
     uint16_t qt[4][64];
     bool have_q[4] = {}, have_h[4] = {}, have_sof = false;
     int comp_id[3] = {}, comp_tq[3] = {}, adobe = -1;
+    bool jfif = false;
     size_t p = 2;
     for (;;) {
         // a marker: 0xFF, any number of fill 0xFF, the code
@@ -199,6 +206,8 @@ inline int parse(const uint8_t *s, size_t len, rva_jpeg_desc &d, uint32_t *ivals
             return refuse(msg, msg_len, "DNL marker (the number of lines must be in SOF0)");
         } else if (m == 0xEE && n >= 12 && memcmp(b, "Adobe", 5) == 0) {
             adobe = b[11];
+        } else if (m == 0xE0 && n >= 14 && memcmp(b, "JFIF", 5) == 0) {                  // (libjpeg's lengths: examine_app0 / examine_app14)
+            jfif = true;
         } else if (m == 0xDA) {
             if (!have_sof) return refuse(msg, msg_len, "SOS before SOF0");
             if (n < 1) return refuse(msg, msg_len, "SOS of 0 bytes");
@@ -221,6 +230,8 @@ inline int parse(const uint8_t *s, size_t len, rva_jpeg_desc &d, uint32_t *ivals
                               b[2 + 2 * ns], b[3 + 2 * ns]);
             if (d.ncomp == 3 && adobe == 0) return refuse(msg, msg_len, "Adobe transform 0 (RGB samples; YCbCr only)");
             if (d.ncomp == 3 && adobe > 1) return refuse(msg, msg_len, "Adobe transform %d (YCbCr only)", adobe);
+            if (d.ncomp == 3 && !jfif && adobe < 0 && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B')
+                return refuse(msg, msg_len, "component ids 'R','G','B' without a JFIF or Adobe marker (RGB samples; YCbCr only)");
             break;
         }
         // every other segment (APPn, COM, ...) is skipped by its length: an embedded thumbnail cannot be taken for the frame

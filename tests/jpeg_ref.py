@@ -81,9 +81,9 @@ def _huff_table(counts, syms):
     return tbl
 
 
-def _symbol(br, tbl):
+def _symbol(br, tbl, longest=16):
     code = 0
-    for length in range(1, 17):
+    for length in range(1, longest + 1):
         code = (code << 1) | br.get(1)
         if (length, code) in tbl:
             return tbl[(length, code)]
@@ -94,13 +94,19 @@ def _extend(v, s):
     return v - (1 << s) + 1 if v < (1 << (s - 1)) else v
 
 
-def parse(data):
+FAULTS = ("ac-by-dc-id", "q-min-c-1", "cb-cr-swapped", "first-definition", "first-of-segment", "pred-kept", "zrl-64-error", "search-15")
+
+
+def parse(data, fault=None):
     """Markers of a baseline stream -> dict(w, h, comps [(id, h, v, tq)], q {id: [64] natural}, huff {(class, id): table}, ri,
-    sel [(td, ta)], intervals [bytes])."""
+    sel [(td, ta)], intervals [bytes]).  Any number of fill 0xFF may stand in front of a marker, in the header and in the scan.
+    `fault` plants one of FAULTS (tests/test_jpeg_craft_host.py: what a decoder gets wrong without the stream grid noticing)."""
     assert data[:2] == b"\xff\xd8"
     p, q, huff, ri, frame = 2, {}, {}, 0, None
     while True:
         assert data[p] == 0xFF
+        while data[p + 1] == 0xFF:
+            p += 1
         m = data[p + 1]
         n = (data[p + 2] << 8) | data[p + 3]
         b = data[p + 4:p + 2 + n]
@@ -110,13 +116,15 @@ def parse(data):
                 assert b[0] >> 4 == 0
                 t = np.zeros(64, np.int64)
                 t[ZIGZAG] = list(b[1:65])
-                q[b[0] & 15] = t
-                b = b[65:]
+                if not (fault == "first-definition" and b[0] & 15 in q):
+                    q[b[0] & 15] = t
+                b = b[65:] if fault != "first-of-segment" else b""
         elif m == 0xC4:
             while b:
                 counts = list(b[1:17])
-                huff[(b[0] >> 4, b[0] & 15)] = _huff_table(counts, list(b[17:17 + sum(counts)]))
-                b = b[17 + sum(counts):]
+                if not (fault == "first-definition" and (b[0] >> 4, b[0] & 15) in huff):
+                    huff[(b[0] >> 4, b[0] & 15)] = _huff_table(counts, list(b[17:17 + sum(counts)]))
+                b = b[17 + sum(counts):] if fault != "first-of-segment" else b""
         elif m == 0xC0:
             assert b[0] == 8
             frame = dict(h=(b[1] << 8) | b[2], w=(b[3] << 8) | b[4],
@@ -132,12 +140,14 @@ def parse(data):
     while True:
         if data[i] == 0xFF and data[i + 1] != 0:
             intervals.append(data[start:i])
+            while data[i + 1] == 0xFF:             # fill bytes belong to the marker
+                i += 1
             if 0xD0 <= data[i + 1] <= 0xD7:
                 i += 2
                 start = i
                 continue
             break
-        i += 1
+        i += 2 if data[i] == 0xFF else 1
     return dict(frame, q=q, huff=huff, ri=ri, sel=sel, intervals=intervals)
 
 
@@ -158,11 +168,15 @@ def _idct_1d(x, shift):
     return np.stack([tmp10 + tmp3, tmp11 + tmp2, tmp12 + tmp1, tmp13 + tmp0, tmp13 - tmp0, tmp12 - tmp1, tmp11 - tmp2, tmp10 - tmp3]) + r >> shift
 
 
+def idct_raw(block):
+    """Dequantised coefficients [8, 8] (natural order) -> the IDCT's output before the level shift and the clamp."""
+    ws = _idct_1d(block.astype(np.int64), 11)             # columns: rows of the array are the vertical frequency
+    return _idct_1d(ws.T, 18).T                           # rows
+
+
 def idct(block):
     """Dequantised coefficients [8, 8] (natural order) -> samples 0..255."""
-    ws = _idct_1d(block.astype(np.int64), 11)             # columns: rows of the array are the vertical frequency
-    out = _idct_1d(ws.T, 18).T                            # rows
-    return np.clip(out + 128, 0, 255)
+    return np.clip(idct_raw(block) + 128, 0, 255)
 
 
 def _fancy_h(a, even_bias, odd_bias, shift, w3):
@@ -195,30 +209,42 @@ def upsample(plane, hs, vs, w, h):
     return _fancy_h(s, 8, 7, 4, 3)[:h, :w]
 
 
-def decode(data):
-    """-> dict(w, h, ncomp, hs, vs, planes [Y(, Cb, Cr)] padded to whole MCUs, rgb [h, w, 3] uint8)."""
-    f = parse(data)
+def decode(data, fault=None):
+    """-> dict(w, h, ncomp, hs, vs, planes [Y(, Cb, Cr)] padded to whole MCUs, rgb [h, w, 3] uint8).  `fault`: see parse()."""
+    assert fault is None or fault in FAULTS
+    f = parse(data, fault)
     w, h, comps = f["w"], f["h"], f["comps"]
     nc = len(comps)
+    sel, tq = list(f["sel"]), [c[3] for c in comps]
+    if fault == "ac-by-dc-id":
+        sel = [(td, td) for td, _ in sel]
+    if fault == "q-min-c-1":
+        tq = [tq[min(c, 1)] for c in range(nc)]
+    if fault == "cb-cr-swapped" and nc == 3:
+        sel, tq = [sel[0], sel[2], sel[1]], [tq[0], tq[2], tq[1]]
+    longest = 15 if fault == "search-15" else 16
     hs, vs = (comps[0][1], comps[0][2]) if nc == 3 else (1, 1)
     mw, mh = -(-w // (8 * hs)), -(-h // (8 * vs))
     planes = [np.zeros((mh * vs * 8, mw * hs * 8), np.int64)] + [np.zeros((mh * 8, mw * 8), np.int64) for _ in range(nc - 1)]
     per = f["ri"] or mw * mh
     assert len(f["intervals"]) == -(-mw * mh // per)
+    pred = [0] * nc
     for iv, seg in enumerate(f["intervals"]):
-        br, pred = _Bits(seg), [0] * nc
+        br = _Bits(seg)
+        if fault != "pred-kept":
+            pred = [0] * nc
         for mcu in range(iv * per, min((iv + 1) * per, mw * mh)):
             my, mx = divmod(mcu, mw)
             for c in range(nc):
-                dc, ac = f["huff"][(0, f["sel"][c][0])], f["huff"][(1, f["sel"][c][1])]
+                dc, ac = f["huff"][(0, sel[c][0])], f["huff"][(1, sel[c][1])]
                 for k in range(hs * vs if c == 0 else 1):
                     coef = np.zeros(64, np.int64)
-                    s = _symbol(br, dc)
+                    s = _symbol(br, dc, longest)
                     pred[c] += _extend(br.get(s), s) if s else 0
                     coef[0] = pred[c]
                     i = 1
                     while i < 64:
-                        rs = _symbol(br, ac)
+                        rs = _symbol(br, ac, longest)
                         r, s = rs >> 4, rs & 15
                         if s:
                             i += r
@@ -226,10 +252,11 @@ def decode(data):
                             i += 1
                         elif r == 15:
                             i += 16
+                            assert i <= 64 and not (fault == "zrl-64-error" and i == 64), "a ZRL passes index 63"
                         else:
                             break
                     by, bx = (my * vs + k // hs, mx * hs + k % hs) if c == 0 else (my, mx)
-                    planes[c][by * 8:by * 8 + 8, bx * 8:bx * 8 + 8] = idct((coef * f["q"][comps[c][3]]).reshape(8, 8))
+                    planes[c][by * 8:by * 8 + 8, bx * 8:bx * 8 + 8] = idct((coef * f["q"][tq[c]]).reshape(8, 8))
     y = planes[0][:h, :w]
     if nc == 1:
         rgb = np.stack([y, y, y], -1)
