@@ -476,8 +476,8 @@ int rva_yolo_head_f32(rva_ctx *ctx, const void *box_logits, int ldb, const void 
  *   [batch, 4+nc, anchors] (fp32 input and output for an RVA_PLAN_F32 plan; what rva_postprocess_batch reads; anchors = H/8*W/8 + H/16*W/16 + H/32*W/32); every launch of the
  *   forward pass goes to `stream`, no host synchronisation, no allocation: capturable.  _run_lanes additionally forks the
  *   stride-8 / stride-16 detect branches onto two side streams (events inside the plan) and joins them at the end: +6 % for one
- *   pass at a time; with several passes in flight use _run.  _run_range(first, last) replays steps [first, last) (a caller that
- *   wants an event at `quiet_step`, where the pass enters its 20x20 layers).
+ *   pass at a time; with several passes in flight use _run.  _run_range(first, last) replays steps [first, last)
+ *   (`quiet_step`: where the pass enters its 20x20 layers).
  * Kernel selection: every convolution step ("tunable") carries a kernel variant of rva_conv2d_nhwc_f16_v (0 = heuristic).
  *   A tuner times rva_yolov8_plan_launch_tunable(index, variant) on the plan's own buffers (RVA_ERR_ARG = variant does not
  *   apply to that layer) and fixes its choice with _set_variant; _tunable_desc gives "Cin->Cout kKsS HxW" (the key of a

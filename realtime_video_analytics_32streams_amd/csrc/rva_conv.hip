@@ -1077,9 +1077,6 @@ struct RunArgs {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(afx[S][i], bfx[S][j], acc[i][j], 0, 0, 0);    \
     } while (0)
 
-// NOSEL: timing-only experiment (private build, -DRVA_EXPERIMENTS: profiles/r04_experiments_not_kept.txt) -- the padding selects
-// compiled out, i.e. what a zero-halo activation layout could save at most; border pixels are then wrong.
-//
 // PADO (round 4): the padding selects leave the MFMA phase by making the tile a run of PADDED positions.  The raster the
 // kernel walks has row pitch W + 1 (one pad position after every image row: right pad of row y, left pad of row y + 1) and one
 // pad row after every image; a tile is BM consecutive positions of it, the LDS run holds positions [P0 - (W+1) - 1,
@@ -1089,7 +1086,7 @@ struct RunArgs {
 // before the first step, are never written again.  The price: the MFMAs also run for the pad positions among the tile's
 // outputs (1 / W + 1 / H of the work: 5 % at 40 x 40, 2.5 % at 80 x 80, 10 % at 20 x 20), whose rows the epilogue skips (a
 // per-row pixel index in LDS).
-template <int BM, int BN, int WGM, int WGN, bool NOSEL = false, bool PADO = false>
+template <int BM, int BN, int WGM, int WGN, bool PADO = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 64 && BM <= 320 ? 4 : 2))) k_conv3_run(RunArgs a)
 {
     static_assert(WGM * WGN == 8, "eight waves");
@@ -1222,7 +1219,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
         // the fragments of the next horizontal tap are read while the MFMAs of this one run (two register sets); the padding
         // taps are zeroed where a fragment is consumed, a select right behind the load would wait for it at once
         h8 bfx[2][FM], afx[2][FN];
-        constexpr bool SEL = !NOSEL && !PADO;
+        constexpr bool SEL = !PADO;
         RUN_LOAD(0, 0);
         RUN_LOAD(1, 1);
         if (SEL) RUN_ZERO(0, vsh);
@@ -1250,7 +1247,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BN <= 
     STAMP(6);
 }
 
-template <int BM, int BN, int WGM, int WGN, bool NOSEL = false, bool PADO = false>
+template <int BM, int BN, int WGM, int WGN, bool PADO = false>
 hipError_t launch_run(RunArgs &a, hipStream_t s)
 {
     if (a.Cin % 32 || a.CoutPad % 4 || a.W > 160) return hipErrorInvalidValue;
@@ -1268,7 +1265,7 @@ hipError_t launch_run(RunArgs &a, hipStream_t s)
     }
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     // raster = mp: the positions the kernel decodes (mp >= a.M, so a.M stays below 2^24 with it)
-    return launch_ldsdma(k_conv3_run<BM, BN, WGM, WGN, NOSEL, PADO>, a, BM, BN, mp, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
+    return launch_ldsdma(k_conv3_run<BM, BN, WGM, WGN, PADO>, a, BM, BN, mp, (size_t)a.M, a.ldi, (size_t)a.CoutPad * 9 * a.Cin, 160 * 1024, smem, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2666,19 +2663,6 @@ hipError_t v_run(const ConvCall &c)
     return LAUNCH(g, c.s);
 }
 
-#ifdef RVA_EXPERIMENTS
-// run<BM,BN> without the padding selects.  The select-free kernels give wrong border pixels: opt-in per process, and any
-// failure reads as "not applicable"
-template <int BM, int BN, int WGM, int WGN>
-hipError_t v_run_nosel(const ConvCall &c)
-{
-    const char *nosel = getenv("RVA_NOSEL");
-    if (!is_3x3(c, 1) || !nosel || nosel[0] != '1') return hipErrorInvalidValue;
-    RunArgs g = dma3_args<RunArgs>(c);
-    return launch_run<BM, BN, WGM, WGN, true>(g, c.s) == hipSuccess ? hipSuccess : hipErrorInvalidValue;
-}
-#endif
-
 hipError_t launch_variant(int variant, const ConvCall &c);
 
 // variant 0's first choice is the LDS-DMA gather tile gb2<128,128> (37): 1x1 stride 1 and 3x3 stride 2 with whole 64-channel steps
@@ -2869,30 +2853,21 @@ constexpr ConvVariant kConvVariants[] = {
     {78, "gbs<64,128>x3", v_gbig<64, 128, 2, 4, 2, 64, 3>, true},   // 144 KB
     {79, "gbs<64,64>x2", v_gbig<64, 64, 2, 4, 2, 64, 2>, true},     // 64 KB: two blocks per CU
     // "long run" kernels on the padded raster (k_conv3_run<..., PADO>: no padding selects)
-    {80, "runp<256,64>", v_run<launch_run<256, 64, 4, 2, false, true>>},
-    {81, "runp<256,128>", v_run<launch_run<256, 128, 4, 2, false, true>>},
-    {82, "runp<224,128>", v_run<launch_run<224, 128, 2, 4, false, true>>},
-    {83, "runp<320,64>", v_run<launch_run<320, 64, 4, 2, false, true>>},
-    {84, "runp<192,128>", v_run<launch_run<192, 128, 4, 2, false, true>>},
-    {85, "runp<128,64>", v_run<launch_run<128, 64, 2, 4, false, true>>},
+    {80, "runp<256,64>", v_run<launch_run<256, 64, 4, 2, true>>},
+    {81, "runp<256,128>", v_run<launch_run<256, 128, 4, 2, true>>},
+    {82, "runp<224,128>", v_run<launch_run<224, 128, 2, 4, true>>},
+    {83, "runp<320,64>", v_run<launch_run<320, 64, 4, 2, true>>},
+    {84, "runp<192,128>", v_run<launch_run<192, 128, 4, 2, true>>},
+    {85, "runp<128,64>", v_run<launch_run<128, 64, 2, 4, true>>},
     // stride-2 "long run" kernels on the padded output raster
     {86, "s2run<256,128>", v_run<launch_s2run<256, 128, 4, 2>, 2>},      // 147 KB
     {87, "s2run<256,64>", v_run<launch_s2run<256, 64, 4, 2>, 2>},        // 123 KB
     {88, "s2run<128,128>", v_run<launch_s2run<128, 128, 2, 4>, 2>},      // 99 KB
     {89, "s2run<128,64>", v_run<launch_s2run<128, 64, 2, 4>, 2>},        // 75 KB: two blocks per CU
-#ifdef RVA_EXPERIMENTS
-    // 96..: timing-only experiment kernels of a private build (tools/exp_build.py), never in librva.so; 90..95 are unassigned
-    {96, "run<256,128> nosel", v_run_nosel<256, 128, 4, 2>},
-    {97, "run<256,64> nosel", v_run_nosel<256, 64, 4, 2>},
-#endif
 };
 
 constexpr int kConvRows = (int)(sizeof kConvVariants / sizeof kConvVariants[0]);
-#ifdef RVA_EXPERIMENTS
-constexpr int RVA_CONV_VARIANTS = kConvRows - 3, kConvVariantsMax = 99;       // two experiment rows
-#else
-constexpr int RVA_CONV_VARIANTS = kConvRows - 1, kConvVariantsMax = RVA_CONV_VARIANTS;      // 89, by rva_conv_num_variants()
-#endif
+constexpr int RVA_CONV_VARIANTS = kConvRows - 1;      // 89, by rva_conv_num_variants()
 
 constexpr bool conv_rows_numbered()
 {
@@ -2904,10 +2879,7 @@ static_assert(conv_rows_numbered(), "row i of kConvVariants carries variant numb
 
 const ConvVariant *find_variant(int variant)
 {
-    if (variant >= 0 && variant <= RVA_CONV_VARIANTS) return &kConvVariants[variant];
-    for (int i = RVA_CONV_VARIANTS + 1; i < kConvRows; ++i)
-        if (kConvVariants[i].number == variant) return &kConvVariants[i];
-    return nullptr;
+    return variant >= 0 && variant <= RVA_CONV_VARIANTS ? &kConvVariants[variant] : nullptr;
 }
 
 hipError_t launch_variant(int variant, const ConvCall &c) { return find_variant(variant)->launch(c); }
@@ -3107,7 +3079,7 @@ int rva_conv1x1_head5_f16(rva_ctx *ctx, const void *in, int ldi, const void *wei
 
 int rva_conv_cout_pad(int Cout) { return rva_ceil_div(Cout, 64) * 64; }
 
-int rva_conv_num_variants(void) { return kConvVariantsMax; }
+int rva_conv_num_variants(void) { return RVA_CONV_VARIANTS; }
 
 const char *rva_conv_variant_name(int variant)
 {

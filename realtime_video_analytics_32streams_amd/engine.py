@@ -28,9 +28,11 @@ No host synchronisation and no allocation after construction: a whole tick can b
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
 import os
-import time
-from typing import Dict, List, Optional, Tuple
+from pathlib import Path
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -47,14 +49,11 @@ def _lib_digest() -> str:
     """sha256 of librva.so: a rebuilt library never inherits another build's kernel selection."""
     global _LIB_DIGEST
     if _LIB_DIGEST is None:
-        import hashlib
         _LIB_DIGEST = hashlib.sha256(N.LIB_PATH.read_bytes()).hexdigest()
     return _LIB_DIGEST
 
 
 def _tuning_dir():
-    import os
-    from pathlib import Path
     d = os.environ.get("RVA_TUNE_CACHE_DIR")
     return Path(d) if d else Path(os.environ.get("XDG_CACHE_HOME", str(Path.home() / ".cache"))) / "rva_amd" / "autotune"
 
@@ -98,7 +97,6 @@ class FusedYoloV8:
     def __init__(self, net: YoloV8, batch: int, hw: Tuple[int, int] = (640, 640), device: Optional[torch.device] = None,
                  ctx: Optional[N.Context] = None, autotune: bool = True, tune_overlap: int = 1, precision: str = "fp16",
                  box_rows: str = "fp16", static_rows: Optional[Tuple[int, int]] = None):
-        import os
         if precision not in ("fp16", "fp32"):
             raise ValueError(f"precision must be 'fp16' or 'fp32', not {precision!r}")
         if box_rows not in ("fp16", "fp32"):
@@ -115,7 +113,6 @@ class FusedYoloV8:
         self.n = batch                     # images of the last run (or of the tensor a caller announced): what result() hands out
         assert hw[0] % 32 == 0 and hw[1] % 32 == 0
         net = net.fuse()
-        self._net = net                     # kept for the twin plans of the in-plan kernel selection
         self.nc = net.nc
         self.L = N.lib()
         convs = self._module_order(net)
@@ -256,15 +253,14 @@ class FusedYoloV8:
     def _tuning_key(self) -> str:
         """What a kernel selection depends on: the device, the library build, the layer shapes of the plan (batch included)
         and the switches that change how the selection is made."""
-        import hashlib
-        import os
         h = hashlib.sha256()
         h.update(torch.cuda.get_device_name(self.dev).encode())
         h.update(_lib_digest().encode())
         h.update(repr((self.B, self.H, self.W, [d for _, _, d in self._tunable])).encode())
         h.update(b"per-layer times; in-plan pass opt-in, three overlapping passes")
-        h.update(repr([os.environ.get(k, "") for k in ("RVA_SKIP_VARIANTS", "RVA_TUNE_IN_PLAN", "RVA_TUNE_OVERLAP", "RVA_TUNE_TOP",
-                                                       "RVA_TUNE_WITHIN", "RVA_NO_STEM2", "RVA_HEAD_SPLIT", "RVA_NO_CIN_PAD")]).encode())
+        # "" where RVA_TUNE_IN_PLAN, _OVERLAP, _TOP, _WITHIN and RVA_HEAD_SPLIT were hashed: retired switches, and old keys stay valid
+        skip, no_stem2, no_cin_pad = (os.environ.get(k, "") for k in ("RVA_SKIP_VARIANTS", "RVA_NO_STEM2", "RVA_NO_CIN_PAD"))
+        h.update(repr([skip, "", "", "", "", no_stem2, "", no_cin_pad]).encode())
         h.update(repr(int(os.environ.get("RVA_TUNE_LAYER_OVERLAP", getattr(self, "tune_overlap", 1)))).encode())
         if getattr(self, "f32", False):
             h.update(b"precision fp32")                 # fp16 keys stay as they were: existing caches remain valid
@@ -273,7 +269,6 @@ class FusedYoloV8:
         return h.hexdigest()[:24]
 
     def _load_tuning(self) -> bool:
-        import json
         f = _tuning_dir() / f"{self._tuning_key()}.json"
         try:
             rec = json.loads(f.read_text())
@@ -294,8 +289,6 @@ class FusedYoloV8:
         return True
 
     def _store_tuning(self) -> None:
-        import json
-        import os
         d = _tuning_dir()
         try:
             d.mkdir(parents=True, exist_ok=True)
@@ -313,14 +306,12 @@ class FusedYoloV8:
         per-chunk order of K, so the choice does not change results beyond fp32 summation order.  The selection is
         persisted per (device, library build, plan shape): a later process takes it over instead of timing again
         (``RVA_TUNE_CACHE=0`` disables, ``RVA_TUNE_CACHE_DIR`` moves it)."""
-        import os
         self.tuning_source = "measured"
         use_cache = os.environ.get("RVA_TUNE_CACHE", "1") == "1"
         if use_cache and self._load_tuning():
             return
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         self.tuning = []
-        self._candidates = {}
         self._n_variants = int(N.lib().rva_conv_num_variants())
         skip = {int(v) for v in os.environ.get("RVA_SKIP_VARIANTS", "").replace(",", " ").split()}      # tuning aid: same-box A/B of kernel families
         cache = {}
@@ -364,22 +355,15 @@ class FusedYoloV8:
                 state["variant"] = cache[desc][0]
                 continue
             best = (0, float("inf"))
-            timed = []
             for variant in range(1, self._n_variants + 1):
                 if variant in skip or launch(stream, variant) != N.RVA_OK:
                     continue
                 us = time_variant(variant)
-                timed.append((us, variant))
                 if us < best[1]:
                     best = (variant, us)
             state["variant"] = best[0]
             cache[desc] = best
-            self._candidates[desc] = sorted(timed)[:int(os.environ.get('RVA_TUNE_TOP', '5'))]
             self.tuning.append((desc, best[0], round(best[1], 1)))
-        # The second pass (whole forward passes, three in flight, candidates within 25 % swapped in one by one) is opt-in since
-        # round 3: with an honest base timing it moves the three-chain pipeline by -0.8 % +- 1 % (profiles/r03_experiments_not_kept.txt #8)
-        if os.environ.get("RVA_TUNE_IN_PLAN", "0") == "1":
-            self._refine_in_plan()
         if use_cache:
             self._store_tuning()
 
@@ -392,88 +376,6 @@ class FusedYoloV8:
         self.tuning = list(getattr(other, "tuning", []))
         self.tuning_source = "copied from the first slot's plan"
 
-    def _refine_in_plan(self, reps: int = 12, within: float = 1.25) -> None:
-        import os
-        within = float(os.environ.get('RVA_TUNE_WITHIN', within))
-        """Second pass of the kernel selection, on the real objective: a layer's launch time in isolation is not its cost inside
-        the plan -- the detect branches run on side streams beside the neck, and a kernel that wants every CU for itself (one
-        128-KB workgroup per CU) shares worse than a two-workgroups-per-CU one that is a few per cent slower alone.  For the
-        layers with runners-up within 25 % the whole forward pass is timed with each candidate (coordinate descent, most
-        expensive layers first) and a candidate is kept when the pass gets faster by more than the timing noise."""
-        x = torch.zeros((self.B, 3, self.H, self.W), dtype=self.dtype, device=self.dev)
-        # The objective is what the pipeline does with the plan: forward passes of consecutive ticks rotate over three streams
-        # and overlap (PipelinedTicks, depth 3), so the pass is timed as a group -- this plan on one stream, twins with the same
-        # kernel selection on the others.  RVA_TUNE_OVERLAP=n: n passes in flight (0 / 1: a single pass alone).
-        twins: list = []
-        lanes = self.concurrent_heads
-        n_over = int(os.environ.get("RVA_TUNE_OVERLAP", "3"))
-        if n_over >= 2:
-            twins = [type(self)(self._net, self.B, (self.H, self.W), device=self.dev, ctx=self.ctx, autotune=False, precision=self.precision,
-                                 box_rows=self.box_rows, static_rows=self.static_rows)
-                     for _ in range(n_over - 1)]
-            from .ops import chain_streams
-            streams = chain_streams(self.dev, n_over)                  # the streams the pipeline's tick chains will run on
-            self.concurrent_heads = False                              # as PipelinedTicks runs overlapping passes: branches in line
-            for t in twins:
-                t.concurrent_heads = False
-
-        def forward_us() -> float:
-            best = float("inf")
-            for t in twins:
-                t.copy_tuning(self)
-            group = [self] + twins
-            rounds = max(reps // len(group), 2)
-            for _ in range(2):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                if not twins:
-                    for _ in range(reps):
-                        self(x)
-                else:
-                    for _ in range(rounds):
-                        for pl, st in zip(group, streams):
-                            with torch.cuda.stream(st):
-                                pl(x)
-                torch.cuda.synchronize()
-                best = min(best, (time.perf_counter() - t0) / (rounds * len(group) if twins else reps) * 1e6)
-            return best
-        by_desc: Dict[str, list] = {}
-        for _, state, desc in self._tunable:
-            by_desc.setdefault(desc, []).append(state)
-        cost = {d: v[0][0] * len(by_desc[d]) for d, v in self._candidates.items() if v}
-        order = [d for d in sorted(cost, key=cost.get, reverse=True)
-                 if len(self._candidates[d]) > 1 and self._candidates[d][1][0] <= within * self._candidates[d][0][0]][:24]
-        if not order:
-            self.concurrent_heads = lanes
-            return
-        self(x); self(x)
-        forward_us()                                               # the twins' first passes (lazy buffers, cold caches) stay out of the base
-        base = forward_us()
-        self.refined = []
-        for _sweep in range(2):
-            changed = False
-            for d in order:
-                cur = by_desc[d][0]["variant"]
-                for us, v in self._candidates[d]:
-                    if us > within * self._candidates[d][0][0]:
-                        break
-                    if v == cur:
-                        continue
-                    for st in by_desc[d]:
-                        st["variant"] = v
-                    t = forward_us()
-                    if t < base * 0.997:
-                        self.refined.append((d, cur, v, round(base, 1), round(t, 1)))
-                        base, cur, changed = t, v, True
-                    else:
-                        for st in by_desc[d]:
-                            st["variant"] = cur
-            if not changed:
-                break
-        self.concurrent_heads = lanes
-        iso = {d: {v: us for us, v in c} for d, c in self._candidates.items()}
-        self.tuning = [(d, by_desc[d][0]["variant"], round(iso[d].get(by_desc[d][0]["variant"], us), 1)) for d, _, us in self.tuning]
-
     # -- run ------------------------------------------------------------------------------------------
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         """``x``: fp16 (fp32 for an fp32 plan) planar ``[n,3,H,W]`` contiguous (what K1 writes), ``1 <= n <= B``.  Returns
@@ -482,8 +384,7 @@ class FusedYoloV8:
         n = int(x.shape[0])
         assert 1 <= n <= self.B, f"{n} images on a plan of capacity {self.B}"
         self.n = n
-        main = torch.cuda.current_stream()
-        stream = C.c_void_p(main.cuda_stream)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         xin, out = C.c_void_p(x.data_ptr()), C.c_void_p(self.out.data_ptr())
         if self.concurrent_heads and self._forks:
             # fork / join over events inside the plan: works eagerly and inside a stream capture
@@ -492,14 +393,7 @@ class FusedYoloV8:
             self.ctx.check(self.L.rva_yolov8_plan_run_lanes_n(self.handle, xin, out, n, stream, C.c_void_p(self._side[0].cuda_stream),
                                                               C.c_void_p(self._side[1].cuda_stream)), "rva_yolov8_plan_run_lanes_n")
             return self._head()
-        ev = getattr(self, "phase_event", None)
-        if ev is not None:
-            self.ctx.check(self.L.rva_yolov8_plan_run_range_n(self.handle, xin, out, n, 0, self.quiet_step, stream), "rva_yolov8_plan_run_range_n")
-            ev.record(main)                                # the pass enters its 20x20 phase
-            self.ctx.check(self.L.rva_yolov8_plan_run_range_n(self.handle, xin, out, n, self.quiet_step, self._n_steps, stream),
-                           "rva_yolov8_plan_run_range_n")
-        else:
-            self.ctx.check(self.L.rva_yolov8_plan_run_n(self.handle, xin, out, n, stream), "rva_yolov8_plan_run_n")
+        self.ctx.check(self.L.rva_yolov8_plan_run_n(self.handle, xin, out, n, stream), "rva_yolov8_plan_run_n")
         return self._head()
 
     def _head(self) -> torch.Tensor:

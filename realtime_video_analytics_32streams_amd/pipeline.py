@@ -477,7 +477,6 @@ class PipelinedTicks:
         # head of the next one (stem, 160x160 / 80x80 layers).  Measured with the plan alone: 1.73 -> 1.54 ms per 32-frame
         # forward pass (tools/two_streams.py).  A tick's K1 still waits for the previous tick's K1 / K5 (gate state, source
         # rings), and its network for the tick two before it to have released the head tensors of its parity.
-        import os
         net_streams = int(os.environ.get("RVA_NET_STREAMS", net_streams))      # A/B switch for measurements
         self.net_streams = depth if (net_streams >= 2 and self.two_streams and depth >= 2) else 1
         if depth > 2 and self.net_streams == 1:
@@ -498,18 +497,11 @@ class PipelinedTicks:
         else:
             self.sAs = [self.sA] * self.nslots
             self.sB = torch.cuda.Stream(device=self.det.device) if self.two_streams else self.sA
-        # K1 of tick k+1 beside the 20x20 phase of tick k's forward pass (most CUs and most of the HBM bandwidth idle there)
-        # instead of beside its stem / 80x80 layers: RVA_K1_GATE=1.  Off by default: see DESIGN.md (K1 in the pipeline).
-        self.k1_gate = os.environ.get("RVA_K1_GATE", "0") == "1" and self.net_streams >= 2
-        self.k1_prio = os.environ.get("RVA_K1_PRIO", "0") == "1" and self.net_streams >= 2
-        if self.k1_prio:
-            self._k1_stream = torch.cuda.Stream(device=self.det.device, priority=-1)
         # kernel selection objective of plans built from now on: launches timed `net_streams` at a time (see FusedYoloV8.autotune)
         for d in pipe.detectors:
             if is_fused(d) and not getattr(d, "_plans", None):
                 d.tune_overlap = max(self.net_streams, 1)
         ns = self.nslots
-        self._phase_ev = [torch.cuda.Event() for _ in range(ns)]
         self._pending = [None] * ns           # per slot: what the stream-B part of that tick needs
         self._meta = [None] * ns              # per slot: (packets, t0) for collect_result
         self._next, self._oldest = 0, 0
@@ -529,8 +521,7 @@ class PipelinedTicks:
     def _plan_of(self, det, tensor):
         plan = det.plan_for(tensor)                                # builds + autotunes the plan of det's current slot (outside any capture)
         # detect branches in line when two passes overlap (see __init__), on side streams when one pass runs at a time
-        plan.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1" and \
-            (self.net_streams < 2 or os.environ.get("RVA_NET2_LANES", "0") == "1")
+        plan.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1" and self.net_streams < 2
         return plan
 
     def _set_slot(self, par):
@@ -666,22 +657,17 @@ class PipelinedTicks:
         t0 = time.perf_counter()
         if packets is None:
             packets = [src.next_packet() for src in p.sources]
-        sa = self.sAs[par]
-        sk = sa                                                    # roi / downsample / K5 / K1 ride on the tick's own stream (a separate,
+        sa = self.sAs[par]                                         # roi / downsample / K5 / K1 ride on the tick's own stream (a separate,
                                                                    # even high-priority, stream for them cost 20 % of the throughput)
-        if self.k1_prio and self.net_streams >= 2:                 # experiment (RVA_K1_PRIO=1): K1 on ONE high-priority stream of its own
-            sk = self._k1_stream
         self._set_slot(par)
         if self.net_streams >= 2:
             sa.wait_stream(torch.cuda.current_stream())            # whatever the caller queued before this tick (frame sources)
-        with torch.cuda.stream(sk):
+        with torch.cuda.stream(sa):
             if self.net_streams >= 2:
                 if k >= 1:
-                    sk.wait_event(self._k1_done[prev])             # the previous tick's K5 / K1 (gate state, source rings) first
+                    sa.wait_event(self._k1_done[prev])             # the previous tick's K5 / K1 (gate state, source rings) first
                 if k >= self.nslots:
-                    sk.wait_event(self._net_done[par])             # the slot's previous tick's network has read its input tensors
-                if self.k1_gate and k >= 1:
-                    sk.wait_event(self._phase_ev[prev])            # ... and tick k-1's forward pass has reached its 20x20 phase
+                    sa.wait_event(self._net_done[par])             # the slot's previous tick's network has read its input tensors
             packets = p._frames_for_detection(packets)             # roi / downsample (device work)
             plan = p.plan_tick(packets, process)
             motion = p._device_gates(packets, par) if p.has_gates else None       # K5 + gate parameters (no sync)
@@ -692,7 +678,7 @@ class PipelinedTicks:
         for gi, g in enumerate(plan.groups):
             det = p.detectors[g.det]
             plan_det = hasattr(det, "plan_for") and getattr(det, "engine", None) in ("fused", "fused-f32") and det._infer_fn is None
-            with torch.cuda.stream(sk), torch.inference_mode():
+            with torch.cuda.stream(sa), torch.inference_mode():
                 if events and gi == 0: events[0].record()
                 if before_k1 and gi == 0: before_k1()
                 with ops.roctx(f"tick{k}:K1"):
@@ -700,9 +686,7 @@ class PipelinedTicks:
                 p._note_clips(g, getattr(pre, "infos", None))
                 if events and gi == 0: events[1].record()
                 if self.two_streams and gi == len(plan.groups) - 1:
-                    self._k1_done[par].record(sk)
-                    if sk is not sa:
-                        sa.wait_event(self._k1_done[par])          # the network of this tick follows its K1 on another stream
+                    self._k1_done[par].record(sa)
             with torch.cuda.stream(sa):
                 if self.two_streams and gi == 0 and k >= self.nslots:
                     sa.wait_event(self._done[par])                 # the slot's previous tick has finished reading its head tensors
@@ -714,7 +698,6 @@ class PipelinedTicks:
                         if plan_det and self.two_streams:
                             fp = self._plan_of(det, pre[0])
                             fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
-                            fp.phase_event = self._phase_ev[par] if (self.k1_gate and gi == 0) else None
                         elif plan_det:
                             self._plan_of(det, pre[0])             # sets the plan's branch mode for this runner's layout
                         with ops.roctx(f"tick{k}:network"):
@@ -729,20 +712,20 @@ class PipelinedTicks:
             self._meta[par] = (packets, t0, clips)
             if self.two_streams:
                 if not plan.groups:
-                    self._k1_done[par].record(sk)
+                    self._k1_done[par].record(sa)
                 self._net_done[par].record(sa)
         self._set_slot(0)
         if self.two_streams:
             if self.depth == 1:
                 self._issue_post(k, None)
-            elif self.net_streams >= 2 and os.environ.get("RVA_TAIL_INLINE", "1") == "1":
+            elif self.net_streams >= 2:
                 # two network streams: the tail goes right behind its own network on the same stream -- a tick is one chain
                 # K1 -> network -> K2/K3 -> K4 -> ids -> snapshot, even and odd ticks on two streams (a third stream for the
                 # tails measured 3 % slower: 19.06 k against 19.70 k frames/s, and made the result depend on how the runtime
                 # spreads streams over its hardware queues)
                 self._issue_post(k, None, stream=sa)
             elif k >= 1 and self._posted < k - 1:
-                self._issue_post(k - 1, self._k1_done[par])        # K1 of this tick first, then the previous tail
+                self._issue_post(k - 1, self._k1_done[par])        # one network stream: K1 of this tick first, then the previous tail
         else:
             _, pl, rw, prs, mo, ev = self._pending[par]
             self._post_part(pl, rw, prs, mo, ev)

@@ -28,12 +28,15 @@ def test_reference_yaml_loads_with_hip_engine_auto(name):
     assert dets and all(d.hip_engine == "auto" for d in dets)
 
 
+# switches of removed experiments: their names keep their (empty) places in the key and no longer fork the cache
+RETIRED = ("RVA_TUNE_IN_PLAN", "RVA_TUNE_OVERLAP", "RVA_TUNE_TOP", "RVA_TUNE_WITHIN", "RVA_HEAD_SPLIT")
+
+
 def _fake_plan(monkeypatch, precision):
     """A FusedYoloV8 with just what _tuning_key reads (no GPU here)."""
     monkeypatch.setattr(torch.cuda, "get_device_name", lambda *a, **k: "AMD Instinct MI355X")
     monkeypatch.setattr(E, "_lib_digest", lambda: "0" * 64)
-    for k in ("RVA_SKIP_VARIANTS", "RVA_TUNE_IN_PLAN", "RVA_TUNE_OVERLAP", "RVA_TUNE_TOP", "RVA_TUNE_WITHIN", "RVA_NO_STEM2",
-              "RVA_HEAD_SPLIT", "RVA_NO_CIN_PAD", "RVA_TUNE_LAYER_OVERLAP"):
+    for k in ("RVA_SKIP_VARIANTS", "RVA_NO_STEM2", "RVA_NO_CIN_PAD", "RVA_TUNE_LAYER_OVERLAP") + RETIRED:
         monkeypatch.delenv(k, raising=False)
     p = object.__new__(E.FusedYoloV8)
     p.dev, p.B, p.H, p.W, p.tune_overlap = torch.device("cpu"), 32, 640, 640, 4
@@ -49,6 +52,17 @@ def test_tuning_key_carries_precision_only_for_fp32(monkeypatch):
     k32 = _fake_plan(monkeypatch, "fp32")._tuning_key()
     assert k16 == legacy == "1b6d28b490bf74f328c79149"                 # the parent's key for this input: fp16 caches stay valid
     assert k32 != k16
+
+
+def test_tuning_key_ignores_retired_switches(monkeypatch):
+    plan = _fake_plan(monkeypatch, "fp16")
+    clean = plan._tuning_key()
+    for name in RETIRED:
+        with monkeypatch.context() as m:
+            m.setenv(name, "1")
+            assert plan._tuning_key() == clean, name
+    monkeypatch.setenv("RVA_SKIP_VARIANTS", "3")
+    assert plan._tuning_key() != clean                                  # a switch the tuner still reads does fork it
 
 
 def test_plan_flag_and_bindings():

@@ -140,7 +140,7 @@ def test_autotuned_plan_meets_the_float64_condition(monkeypatch):
     moves steps off variant 0 by time alone, and the head tensor still meets the condition of the test above."""
     case = "n"
     monkeypatch.setenv("RVA_TUNE_CACHE", "0")
-    for name in ("RVA_SKIP_VARIANTS", "RVA_TUNE_IN_PLAN", "RVA_TUNE_LAYER_OVERLAP"):
+    for name in ("RVA_SKIP_VARIANTS", "RVA_TUNE_LAYER_OVERLAP"):
         monkeypatch.delenv(name, raising=False)
     assert CASES[case][3] == (2, 64, 96)
     plan = _plan(case)

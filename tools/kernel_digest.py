@@ -3,6 +3,7 @@
 
     python tools/kernel_digest.py build OUT.json [-DNAME ...]   compile every source device-only and write the digests
     python tools/kernel_digest.py diff A.json B.json            print what appeared, vanished or differs; exit 1 if anything does
+                                                                (a vanished and an appeared kernel with equal records: "renamed", no difference)
 
 ``build`` compiles each of ``_native.SOURCES`` with ``_native.HIPCC_FLAGS`` plus ``--cuda-device-only
 --no-gpu-bundle-output -c`` into a scratch directory, which yields one plain elf64-amdgpu object per source, and records
@@ -11,7 +12,9 @@ code entry offset, which only says where in the object the linker put the code),
 kernel-argument sizes of the object's metadata note.  It hashes and compares; it does not look at the instructions.  The
 kernels live in unnamed namespaces, so a kernel keeps its name when it moves to another file.  A kernel that addresses a
 ``__device__`` variable (k_c2f_pair32 and g_zero_line) holds the distance to it in its code, so its hash changes whenever
-the object's layout does; compare such a kernel's ``llvm-objdump -d --no-show-raw-insn`` text instead.
+the object's layout does; compare such a kernel's ``llvm-objdump -d --no-show-raw-insn`` text instead.  A template that loses a
+parameter renames its instantiations: ``diff`` pairs a vanished kernel with an appeared one when their records are equal in every
+field but ``source`` and exactly one candidate exists on either side, and prints the pair as renamed.
 """
 from __future__ import annotations
 
@@ -88,10 +91,24 @@ def build(out_json: str, defines: list) -> int:
     return 0
 
 
+def _by_record(kernels: dict, names) -> dict:
+    """{a record without its ``source``, as text: the names among ``names`` that carry it}"""
+    out = {}
+    for name in sorted(names):
+        out.setdefault(json.dumps({k: v for k, v in kernels[name].items() if k != "source"}, sort_keys=True), []).append(name)
+    return out
+
+
 def diff(a_json: str, b_json: str) -> int:
     a, b = (json.loads(Path(p).read_text())["kernels"] for p in (a_json, b_json))
     bad = 0
+    gone, new = _by_record(a, set(a) - set(b)), _by_record(b, set(b) - set(a))
+    renamed = {v[0]: new[k][0] for k, v in gone.items() if len(v) == 1 and len(new.get(k, ())) == 1}
+    for old, name in sorted(renamed.items()):
+        print(f"renamed: {old} -> {name}")
     for name in sorted(set(a) | set(b)):
+        if name in renamed or name in renamed.values():
+            continue
         if name not in b or name not in a:
             print(f"{'vanished' if name in a else 'appeared'}: {name}")
             bad += 1
@@ -101,7 +118,7 @@ def diff(a_json: str, b_json: str) -> int:
             print(f"differs: {name}: " + ", ".join(f"{k} {a[name].get(k)} -> {b[name].get(k)}" if k in META or k == "text_size" else k for k in keys))
             bad += 1
     moved = sum(1 for n in a if n in b and a[n]["source"] != b[n]["source"])
-    print(f"{len(a)} kernels before, {len(b)} after, {moved} in another source, {bad} appeared, vanished or differing")
+    print(f"{len(a)} kernels before, {len(b)} after, {moved} in another source, {len(renamed)} renamed, {bad} appeared, vanished or differing")
     return 1 if bad else 0
 
 
