@@ -341,7 +341,6 @@ class HipResNetDetector(BaseDetector):
                                  "for the PyTorch-ROCm fp32 network")
             self.net = net.eval().float().to(self.device).to(memory_format=torch.channels_last)
         # batched device path
-        self._slot = 0                         # set by PipelinedTicks: tick parity -> which buffers a tick uses
         self.two_chain_ok = True               # every buffer of a tick exists per slot: consecutive ticks may run as two chains
         self._streams = 0                      # streams the pipeline announced (reserve_streams): the slots' capacity
         self._slots: Dict[int, _ResSlot] = {}
@@ -399,11 +398,7 @@ class HipResNetDetector(BaseDetector):
         return self.predict_batch([packet])[0]
 
     # -- batched device path: a whole tick of this head without a host round trip ----------------------------------------
-    @staticmethod
-    def geometry_key(frame) -> tuple:
-        if isinstance(frame, ops.Nv12Surface):
-            return (int(frame.width), int(frame.height), "nv12")
-        return (int(frame.shape[1]), int(frame.shape[0]), "bgr")
+    geometry_key = staticmethod(ops.geometry_key)
 
     def reserve_streams(self, names: Sequence[str]) -> None:
         """The most frames a tick can bring (TickPipeline calls this once): the slots are sized for it and never regrown."""
@@ -420,12 +415,12 @@ class HipResNetDetector(BaseDetector):
                                               self._in_dtype)
         return rs
 
-    def stage_pre(self, packets: Sequence[FramePacket]) -> _ResTick:
-        """K1 of the tick: the group's frames (one geometry) pre-processed into the slot's input buffer."""
-        rs = self._tick_slot(self._slot, len(packets))
+    def stage_pre(self, packets: Sequence[FramePacket], slot: int = 0) -> _ResTick:
+        """K1 of the tick: the group's frames (one geometry) pre-processed into the input buffer of ``slot`` (the tick's parity)."""
+        rs = self._tick_slot(slot, len(packets))
         x = self._preprocess([p.frame for p in packets], out=rs.input[:len(packets)])
         w, h, _ = self.geometry_key(packets[0].frame)
-        return _ResTick(len(packets), (w, h), self._slot, x)
+        return _ResTick(len(packets), (w, h), slot, x)
 
     def stage_net(self, pre: _ResTick) -> torch.Tensor:
         """The group's frames as ONE network batch: ``[rows, classes]`` raw outputs (no softmax)."""

@@ -18,7 +18,7 @@ from __future__ import annotations
 import abc
 import logging
 from dataclasses import dataclass
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -137,6 +137,21 @@ def select_yolo_engine(arch: str, half: bool, hip_engine: str = "auto") -> str:
     return "torch-fp32"
 
 
+class _YoloTick(NamedTuple):
+    """What ``HipYoloDetector.stage_pre`` hands to ``stage_net`` / ``stage_post`` for one tick of one frame group."""
+    tensor: torch.Tensor                        # [n, 3, H, W]: the slot's input buffer, or its leading n images
+    meta: N.Letterbox
+    slot: int                                   # pipeline slot (tick parity) whose input buffer and plan this tick uses
+
+
+@dataclass
+class _InputState:
+    """What K1 last left in one input buffer of a ``HipYoloDetector``."""
+    border: tuple                               # (frame geometry, leading images) whose letterbox border the buffer holds
+    rows: tuple                                 # content rows (top, bottom): the plan may skip the others (FusedYoloV8.set_static_rows)
+    told: bool                                  # the slot's plan already runs with these rows
+
+
 class HipYoloDetector(BaseDetector):
     """YOLO detector on MI355X: K1 pre-process -> PyTorch-ROCm network -> K2/K3 post-process.
 
@@ -216,17 +231,11 @@ class HipYoloDetector(BaseDetector):
         # buffers are cached per shape and never reallocated: captured hipGraphs (pipeline.PipelinedTicks) keep raw
         # pointers to them, and an interleaved predict() with another batch size must not free what a graph replays on
         self._post_bufs: dict = {}
-        self._in_bufs: dict = {}
-        self._in_border: dict = {}                        # buffer key -> (frame geometry, leading images) whose letterbox border the buffer holds
-        # The same border lets the plan skip the rows of its early layers that only see it (FusedYoloV8.set_static_rows): per
-        # input buffer the content rows (top, bottom) of the geometry it holds, and whether the slot's plan has been told
-        self._rows: dict = {}                             # buffer key -> (top, bottom); the whole image where nothing is static
-        self._rows_told: dict = {}                        # buffer key -> the plan already runs with these rows
+        self._in_bufs: dict = {}                          # buffer key (_buf_key: images[, slot]) -> the input tensor K1 writes
+        self._in_state: dict = {}                         # buffer key -> _InputState, once K1 has written the buffer
         self._post: Optional[ops.PostBuffers] = None      # result buffers of the latest call
         self._in: Optional[torch.Tensor] = None           # input tensor of the latest call
-        # PipelinedTicks runs the networks of consecutive ticks on two streams: input tensor, letterbox-border state and
-        # fused plan (its activation buffers) exist once per slot; everything else keeps using slot 0
-        self._slot = 0
+        self.tune_overlap = 1                             # launches the tuner of a new plan times at once (PipelinedTicks: its chains)
         if config.warmup and self.net is not None:  # detector.py:588-593
             with torch.inference_mode():
                 self._infer(torch.zeros((1, 3, *self.input_hw), device=self.device,
@@ -247,77 +256,75 @@ class HipYoloDetector(BaseDetector):
             return batch
         return cap
 
-    def _buf_key(self, batch: int):
+    def _buf_key(self, batch: int, slot: int = 0):
         """Key of the input buffer (and of its border / static-rows state): images of the buffer (, slot)."""
         m = self._images(batch)
-        return m if self._slot == 0 else (m, self._slot)
+        return m if slot == 0 else (m, slot)
 
-    def input_tensor(self, batch: int) -> torch.Tensor:
-        """The input tensor K1 writes for this batch size and the current slot (cached for the life of the detector); with
+    def input_tensor(self, batch: int, slot: int = 0) -> torch.Tensor:
+        """The input tensor K1 writes for this batch size and slot (cached for the life of the detector); with
         ``hip_plan_capacity`` the leading ``batch`` images of the slot's one buffer."""
-        n, m = self._buf_key(batch), self._images(batch)
+        n, m = self._buf_key(batch, slot), self._images(batch)
         t = self._in_bufs.get(n)
         if t is None:
             dt = torch.float16 if self.half else torch.float32
             t = self._in_bufs[n] = torch.empty((m, 3, *self.input_hw), dtype=dt, device=self.device)
         return t if m == batch else t[:batch]
 
-    def _preprocess(self, frames: Sequence) -> tuple[torch.Tensor, N.Letterbox]:
-        n = self._buf_key(len(frames))
-        self._in = self.input_tensor(len(frames))
+    def _preprocess(self, frames: Sequence, slot: int = 0) -> tuple[torch.Tensor, N.Letterbox]:
+        n = self._buf_key(len(frames), slot)
+        self._in = self.input_tensor(len(frames), slot)
         f0 = frames[0]
         if isinstance(f0, ops.Nv12Surface):
             # the border (pad value) of the input tensor is constant per geometry: the first launch into a buffer writes it,
             # the following ticks of the same geometry write the content rows only
             key = (f0.width, f0.height) if not any(f.mask is not None for f in frames) else None
-            have, bordered = self._in_border.get(n, (None, 0))
+            have, bordered = self._in_state[n].border if n in self._in_state else (None, 0)
             # steady: the border of this geometry is in place in every image the tick writes (a capacity buffer serves ticks of
             # several sizes: a tick larger than any before it is not steady)
             steady = key is not None and have == key and len(frames) <= bordered
             res = ops.preprocess_nv12(frames, self.input_hw, self.half, out=self._in, ctx=self.ctx, content_only=steady)
             if not steady:                                # new buffer, new geometry, more images or ROI masks: the border was (re)written
-                self._in_border[n] = (key, len(frames))
                 lb = res[1]
-                self._note_rows(n, (int(lb.pad_top), int(lb.pad_top) + int(lb.new_h)) if key is not None else (0, self.input_hw[0]))
+                self._note_written(n, (key, len(frames)),
+                                   (int(lb.pad_top), int(lb.pad_top) + int(lb.new_h)) if key is not None else (0, self.input_hw[0]))
             return res
         dev = []
         for f in frames:  # host BGR ndarray (the reference's FramePacket.frame) or device tensor
             t = torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f
             dev.append(t.to(self.device, non_blocking=True).contiguous())
-        self._in_border[n] = (None, 0)
-        self._note_rows(n, (0, self.input_hw[0]))         # K1 for host frames writes the whole tensor
+        self._note_written(n, (None, 0), (0, self.input_hw[0]))        # K1 for host frames writes the whole tensor
         return ops.preprocess_bgr(dev, self.input_hw, self.half, out=self._in, ctx=self.ctx)
 
-    def _note_rows(self, n, rows) -> None:
+    def _note_written(self, n, border, rows) -> None:
         """K1 has just written a whole input buffer whose rows outside ``rows`` will stay as they are on the steady ticks that
         follow: the slot's plan hears of it before its next run (``_infer``), which then covers all rows once."""
-        rows = (max(rows[0], 0), min(rows[1], self.input_hw[0]))
-        self._rows[n] = rows
-        self._rows_told[n] = False
+        self._in_state[n] = _InputState(border, (max(rows[0], 0), min(rows[1], self.input_hw[0])), told=False)
 
     def invalidate_engine(self) -> None:
         """Drop cached fused plans (call after editing ``self.net``'s weights)."""
         self._plans.clear()
-        self._rows_told.clear()
+        for st in self._in_state.values():                # nothing is pending: a new plan is built with the rows (plan_for)
+            st.told = True
 
-    def plan_for(self, tensor: torch.Tensor):
-        """The fused plan of this batch shape and the current slot (built and autotuned on first use; a second slot's plan
-        takes over the first one's kernel selection instead of tuning again).  With ``hip_plan_capacity`` the one plan of that
-        many images, told how many of them ``tensor`` holds (``FusedYoloV8.n``: what its ``result()`` hands out)."""
+    def plan_for(self, tensor: torch.Tensor, slot: int = 0):
+        """The fused plan of this batch shape and slot (built and autotuned on first use; a later slot's plan takes over the
+        first one's kernel selection instead of tuning again).  With ``hip_plan_capacity`` the one plan of that many images,
+        told how many of them ``tensor`` holds (``FusedYoloV8.n``: what its ``result()`` hands out)."""
         batch = int(tensor.shape[0])
         shape = (self._images(batch), int(tensor.shape[2]), int(tensor.shape[3]))
-        key = shape if self._slot == 0 else shape + (self._slot,)
+        key = shape if slot == 0 else shape + (slot,)
         plan = self._plans.get(key)
         if plan is None:
             from .engine import FusedYolo11, FusedYoloV5, FusedYoloV8
             plan_cls = {"yolov5": FusedYoloV5, "yolo11": FusedYolo11}.get(self.arch, FusedYoloV8)      # the same plan object and surface
-            first = self._plans.get(shape) if self._slot else None
+            first = self._plans.get(shape) if slot else None
             # the static rows at construction: the tuner times the windowed launches, and a later slot's plan has the first
             # slot's windows, whose kernel selection it takes over
-            n = shape[0] if self._slot == 0 else (shape[0], self._slot)
-            rows = first.static_rows if first is not None else self._rows.get(n)
+            st = self._in_state.get(self._buf_key(batch, slot))
+            rows = first.static_rows if first is not None else (st.rows if st is not None else None)
             plan = self._plans[key] = plan_cls(self.net, shape[0], shape[1:], device=self.device, ctx=self.ctx,
-                                               autotune=first is None, tune_overlap=getattr(self, "tune_overlap", 1),
+                                               autotune=first is None, tune_overlap=self.tune_overlap,
                                                precision="fp32" if self.engine == "fused-f32" else "fp16", box_rows=self.box_rows,
                                                static_rows=rows if self.engine == "fused" else None)
             if first is not None:
@@ -325,42 +332,43 @@ class HipYoloDetector(BaseDetector):
         plan.n = batch
         return plan
 
-    def rows_pending(self, batch: int) -> bool:
-        """K1 has rewritten the border of the current slot's input buffer and the slot's plan has not run since."""
-        return not self._rows_told.get(self._buf_key(batch), True)
+    def rows_pending(self, batch: int, slot: int = 0) -> bool:
+        """K1 has rewritten the border of the slot's input buffer and the slot's plan has not run since."""
+        st = self._in_state.get(self._buf_key(batch, slot))
+        return st is not None and not st.told
 
-    def _tell_rows(self, plan, tensor: torch.Tensor) -> None:
+    def _tell_rows(self, plan, tensor: torch.Tensor, slot: int = 0) -> None:
         """Hand the plan the static rows K1 left in the slot's input buffer, once per (re)written border.  The promise is about
         that buffer alone: any other tensor runs over all rows."""
-        n = self._buf_key(int(tensor.shape[0]))
-        own = self._in_bufs.get(n)
-        if own is None or own.data_ptr() != tensor.data_ptr() or n not in self._rows:
+        n = self._buf_key(int(tensor.shape[0]), slot)
+        own, st = self._in_bufs.get(n), self._in_state.get(n)
+        if own is None or own.data_ptr() != tensor.data_ptr() or st is None:
             if plan.static_rows != (0, plan.H):
                 plan.set_static_rows(0, plan.H)
-                if n in self._rows:
-                    self._rows_told[n] = False
+                if st is not None:
+                    st.told = False
             return
-        if self._rows_told.get(n, True):
+        if st.told:
             return
-        plan.set_static_rows(*self._rows[n])              # also where the rows are unchanged: the border bytes may be new
-        self._rows_told[n] = True
+        plan.set_static_rows(*st.rows)                    # also where the rows are unchanged: the border bytes may be new
+        st.told = True
 
-    def _infer(self, tensor: torch.Tensor):
+    def _infer(self, tensor: torch.Tensor, slot: int = 0):
         """The head tensor of the batch; with ``hip_box_rows: fp32`` an ``ops.SplitHead`` (head tensor, fp32 box rows)."""
         if self._infer_fn is not None:
             return self._infer_fn(tensor)
         if self.half:
             if tensor.dtype != torch.float16:
                 raise TypeError("half detector: the fused plan takes the fp16 tensor K1 writes")
-            plan = self.plan_for(tensor)
+            plan = self.plan_for(tensor, slot)
             if not torch.cuda.is_current_stream_capturing():
-                self._tell_rows(plan, tensor)
+                self._tell_rows(plan, tensor, slot)
             plan(tensor.contiguous())
             return plan.result()
         if self.engine == "fused-f32":
             if tensor.dtype != torch.float32:
                 raise TypeError("fp32 plan: takes the fp32 tensor K1 writes for half=false")
-            return self.plan_for(tensor)(tensor.contiguous())
+            return self.plan_for(tensor, slot)(tensor.contiguous())
         return self.net(tensor.float().contiguous(memory_format=torch.channels_last))
 
     def _postprocess_device(self, raw, metas: Sequence[N.Letterbox]) -> ops.PostBuffers:
@@ -377,22 +385,17 @@ class HipYoloDetector(BaseDetector):
                                metas, max_det=A, out=self._post, ctx=self.ctx, boxes=boxes)
 
     # -- the three stages of a tick, as the pipelined runner drives them (same protocol as the temporal heads) -------------
-    def stage_pre(self, packets: Sequence[FramePacket]):
-        return self._preprocess([p.frame for p in packets])            # (input tensor, letterbox meta)
+    def stage_pre(self, packets: Sequence[FramePacket], slot: int = 0) -> _YoloTick:     # slot: the runner's tick parity; per-frame API: 0
+        return _YoloTick(*self._preprocess([p.frame for p in packets], slot), slot)
 
-    def stage_net(self, pre):
-        return self._infer(pre[0])
+    def stage_net(self, pre: _YoloTick):
+        return self._infer(pre[0], pre.slot)
 
     def stage_post(self, raw, pre) -> ops.PostBuffers:
         return self._postprocess_device(raw, [pre[1]])
 
     # -- API ------------------------------------------------------------------------------------
-    @staticmethod
-    def geometry_key(frame) -> tuple:
-        """Frames that may share one K1 launch: same size and kind."""
-        if isinstance(frame, ops.Nv12Surface):
-            return (int(frame.width), int(frame.height), "nv12")
-        return (int(frame.shape[1]), int(frame.shape[0]), "bgr")
+    geometry_key = staticmethod(ops.geometry_key)
 
     def predict_batch_device(self, packets: Sequence[FramePacket]) -> ops.PostBuffers:
         """Device-resident result (no host sync): feeds the tracker kernel directly.  One frame geometry per call (the

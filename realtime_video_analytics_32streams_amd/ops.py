@@ -242,6 +242,13 @@ class Nv12Surface:
                            torch.from_numpy(np.ascontiguousarray(uv)).to(device), width, height)
 
 
+def geometry_key(frame) -> tuple:
+    """Frames that may share one K1 launch: same size and kind (every detector's ``geometry_key``)."""
+    if isinstance(frame, Nv12Surface):
+        return (int(frame.width), int(frame.height), "nv12")
+    return (int(frame.shape[1]), int(frame.shape[0]), "bgr")
+
+
 def preprocess_nv12(surfaces: Sequence[Nv12Surface], dst_hw=(640, 640), half: bool = True,
                     out: Optional[torch.Tensor] = None, clip: bool = False, ctx: Optional[N.Context] = None,
                     content_only: bool = False):

@@ -121,6 +121,7 @@ class TickPipeline:
             self.global_index[sl] = first_global_index + i
         self.n_global = n_global_streams or len(self.streams)
         self._tick = 0
+        self._host_dets: Dict[int, object] = {}    # stream index -> what a host or temporal detector produced this tick, for finish()
         self.snapshots = None          # a preview.SnapshotWriter: StreamWorker._maybe_save_snapshot (pipeline.py:196, 264-290)
         self.previews = None           # a preview.PreviewBatcher: the ``frame_jpeg`` of KafkaSink.send_tracks (kafka_sink.py:134-146), one batch per tick
         # pre-detector gates, configured by the reference's StreamConfig keys
@@ -285,7 +286,6 @@ class TickPipeline:
         if not plan.host_idx:
             return
         per = {}
-        self._host_dets = getattr(self, "_host_dets", {})
         for i in plan.host_idx:
             det = self.detectors[self.det_of[i]]
             dets = det.predict(packets[i])
@@ -325,7 +325,6 @@ class TickPipeline:
         """Temporal heads on the device path: remember which clip each stream fired (``finish`` copies the temporal
         fields into the tracks the clip's detections touched, tracker.py:58-67)."""
         if infos:
-            self._host_dets = getattr(self, "_host_dets", {})
             for i in g.idx:
                 if self.names[i] in infos:
                     self._host_dets[i] = infos[self.names[i]]
@@ -346,11 +345,10 @@ class TickPipeline:
         live = [i for i, p in enumerate(packets) if p is not None]
         names = [self.names[i] for i in live]
         tabs = [tables[self.slots[i]] for i in live]
-        host_dets = getattr(self, "_host_dets", {})
         tracks = {}
         for i, n, t in zip(live, names, tabs):
-            tracks[n] = self.tracker._materialise(n, t, host_dets.get(i, ()))
-        host_dets.clear()
+            tracks[n] = self.tracker._materialise(n, t, self._host_dets.get(i, ()))
+        self._host_dets.clear()
         emitted = {self.names[i]: int(emitted_all[self.slots[i]]) for i in live if processed_all[self.slots[i]] == 1}
         if self.snapshots is not None:                                # processed frames only, once per stream per five minutes; the
             for i, n in zip(live, names):                             # frame's surface must still be alive when its tick is collected
@@ -392,6 +390,11 @@ class TickPipeline:
         return res
 
 
+def runs_yolo_plan(det) -> bool:
+    """A hand-written YOLO plan runs the detector's network: fp16 ("fused", half: true) or fp32 ("fused-f32", hip_engine: plan)."""
+    return getattr(det, "engine", None) in ("fused", "fused-f32") and det._infer_fn is None
+
+
 class PipelinedTicks:
     """Throughput mode of :class:`TickPipeline`: ``depth`` ticks in flight, no host round trip inside a tick.
 
@@ -421,7 +424,7 @@ class PipelinedTicks:
     With ``hip_box_rows: fp32`` a slot's head tensor and the fp32 side tensor of its box rows are one buffer of the slot's plan
     (``FusedYoloV8.result()``): eager and captured tails of every layout hand K2 the side tensor of the same slot.
     With ``hip_plan_capacity: N`` every slot keeps one plan and one input buffer of ``N`` images, and a tick whose live-stream
-    count is ``n <= N`` runs their leading ``n`` images (``det.input_tensor(n)``, ``det.plan_for(tensor)``): no plan is built
+    count is ``n <= N`` runs their leading ``n`` images (``det.input_tensor(n, slot)``, ``det.plan_for(tensor, slot)``): no plan is built
     when a stream delivers no frame.  A tick of a new shape still runs eagerly once and re-captures its tail.
 
     ``submit()`` enqueues one tick and returns its ticket; ``collect()`` returns ``(ticket, tables)`` of the oldest
@@ -452,13 +455,10 @@ class PipelinedTicks:
         self.nslots = max(depth, 2)           # a tick's slot ("parity") = k mod nslots: buffers, events, snapshot slot
         self.det, self.dt = pipe.detector, pipe.tracker.device_tracker
         self.world_sharded = pipe.id_sync is not None
-        # the hand-written plans: fp16 ("fused", half: true) and fp32 ("fused-f32", half: false with hip_engine: plan)
-        is_fused = lambda d: ((getattr(d, "engine", None) == "fused" and d.half) or getattr(d, "engine", None) == "fused-f32") \
-            and d._infer_fn is None      # noqa: E731
-        fused = all(is_fused(d) for d in pipe.detectors)
+        fused = all(runs_yolo_plan(d) for d in pipe.detectors)
         # temporal heads run their (torch) network eagerly; they may still run as two chains: every result buffer of theirs
         # exists per tick parity and their frame ring has two slots more than a clip needs
-        chains_ok = all(is_fused(d) or getattr(d, "two_chain_ok", False) for d in pipe.detectors)
+        chains_ok = all(runs_yolo_plan(d) or getattr(d, "two_chain_ok", False) for d in pipe.detectors)
         self.use_graph = bool(use_graph) and fused
         self._fused = fused
         # The network itself is launched eagerly by default: its plan forks the detect branches onto side streams, which
@@ -499,7 +499,7 @@ class PipelinedTicks:
             self.sB = torch.cuda.Stream(device=self.det.device) if self.two_streams else self.sA
         # kernel selection objective of plans built from now on: launches timed `net_streams` at a time (see FusedYoloV8.autotune)
         for d in pipe.detectors:
-            if is_fused(d) and not getattr(d, "_plans", None):
+            if runs_yolo_plan(d) and not d._plans:
                 d.tune_overlap = max(self.net_streams, 1)
         ns = self.nslots
         self._pending = [None] * ns           # per slot: what the stream-B part of that tick needs
@@ -518,19 +518,19 @@ class PipelinedTicks:
         self._captured = False
 
     # -- pieces of a tick -------------------------------------------------------------------------------------
-    def _plan_of(self, det, tensor):
-        plan = det.plan_for(tensor)                                # builds + autotunes the plan of det's current slot (outside any capture)
+    def _det_slot(self, par: int) -> int:
+        """The detector slot (``stage_pre``'s ``slot``) of a tick parity: a slot per chain, or slot 0 with one network stream."""
+        return par if self.net_streams >= 2 else 0
+
+    def _plan_of(self, det, tensor, slot):
+        plan = det.plan_for(tensor, slot)                          # builds + autotunes the slot's plan (outside any capture)
         # detect branches in line when two passes overlap (see __init__), on side streams when one pass runs at a time
         plan.concurrent_heads = os.environ.get("RVA_SERIAL_HEADS") != "1" and self.net_streams < 2
         return plan
 
-    def _set_slot(self, par):
-        for d in self.pipe.detectors:
-            d._slot = par if self.net_streams >= 2 else 0
-
     def _post_part(self, plan, raws, pres, motion, events=None):
         """The tail of one tick for every group: K2/K3 (temporal heads: top-5) then K4 (+ filter, rescale, gates).
-        ``pres[g]``: what the group's ``stage_pre`` returned (YOLO: input tensor + letterbox meta)."""
+        ``pres[g]``: what the group's ``stage_pre`` returned (YOLO: input tensor, letterbox meta, slot)."""
         p = self.pipe
         gated = p.has_gates
         first = True
@@ -553,6 +553,7 @@ class PipelinedTicks:
     def _capture(self, plan, pres, motion):
         """Record the networks (per group and head-tensor parity) and the stream-B part (per parity) of a tick of this
         shape.  Nothing executes here; every kernel of the shape has already run eagerly once.
+        ``pres[g]``: a ``detector._YoloTick`` (``use_graph`` needs ``runs_yolo_plan``); a parity records from a copy with its slot.
 
         The cyclic garbage collector stays off while a stream captures.  A dead plan or context waits in a reference cycle (a
         plan's tunables hold closures over the plan) until some collection finalises it, ``torch.cuda.graph`` does not collect on
@@ -577,13 +578,13 @@ class PipelinedTicks:
             det = p.detectors[g.det]
             pair, epochs = [], []
             for par in range(self.nslots):
-                self._set_slot(par)
-                # the slot's own input tensor (tick chains: one per slot; it exists once the slot has run, else it is made here)
-                pre_par = pres[gi]
+                # the parity's own pre: its slot and, for recorded networks, the slot's input tensor (made here if it has not run)
+                slot = self._det_slot(par)
+                pre_par = pres[gi]._replace(slot=slot)
                 if self.net_streams >= 2 and self.net_graph:
                     with torch.inference_mode():
-                        pre_par = (det.input_tensor(int(pres[gi][0].shape[0])),) + tuple(pres[gi][1:])
-                fp = self._plan_of(det, pre_par[0])
+                        pre_par = pre_par._replace(tensor=det.input_tensor(int(pres[gi][0].shape[0]), slot))
+                fp = self._plan_of(det, pre_par[0], slot)
                 # head tensor (group, parity): a stable buffer of the plan (two network streams: of the parity's own plan)
                 fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
                 raws[gi][par] = fp.result()                        # (with hip_box_rows: fp32 the slot's side tensor rides along)
@@ -609,7 +610,6 @@ class PipelinedTicks:
                     self._ids_and_snapshot(par)                    # single GPU: ids + snapshot ride in the graph
             self._post_graphs[par] = gr
         torch.cuda.synchronize()
-        self._set_slot(0)
         self._cap_sig = plan.signature
         self._captured = True
 
@@ -619,8 +619,8 @@ class PipelinedTicks:
         epoch = self._net_epochs[gi][par]
         if epoch is None:
             return True
-        fp = det.plan_for(pre[0])
-        return fp.rows_epoch == epoch and not det.rows_pending(int(pre[0].shape[0]))
+        fp = det.plan_for(pre[0], pre.slot)
+        return fp.rows_epoch == epoch and not det.rows_pending(int(pre[0].shape[0]), pre.slot)
 
     def _issue_post(self, k, after, stream=None):
         par, prev = k % self.nslots, (k - 1) % self.nslots
@@ -659,7 +659,7 @@ class PipelinedTicks:
             packets = [src.next_packet() for src in p.sources]
         sa = self.sAs[par]                                         # roi / downsample / K5 / K1 ride on the tick's own stream (a separate,
                                                                    # even high-priority, stream for them cost 20 % of the throughput)
-        self._set_slot(par)
+        slot = self._det_slot(par)
         if self.net_streams >= 2:
             sa.wait_stream(torch.cuda.current_stream())            # whatever the caller queued before this tick (frame sources)
         with torch.cuda.stream(sa):
@@ -677,12 +677,11 @@ class PipelinedTicks:
         pres, raws = [], []
         for gi, g in enumerate(plan.groups):
             det = p.detectors[g.det]
-            plan_det = hasattr(det, "plan_for") and getattr(det, "engine", None) in ("fused", "fused-f32") and det._infer_fn is None
             with torch.cuda.stream(sa), torch.inference_mode():
                 if events and gi == 0: events[0].record()
                 if before_k1 and gi == 0: before_k1()
                 with ops.roctx(f"tick{k}:K1"):
-                    pre = det.stage_pre([packets[i] for i in g.idx])    # K1 (temporal heads: into the frame ring + clip schedule)
+                    pre = det.stage_pre([packets[i] for i in g.idx], slot)    # K1 (temporal heads: into the frame ring + clip schedule)
                 p._note_clips(g, getattr(pre, "infos", None))
                 if events and gi == 0: events[1].record()
                 if self.two_streams and gi == len(plan.groups) - 1:
@@ -695,18 +694,17 @@ class PipelinedTicks:
                     self._net_graphs[gi][par].replay()
                 else:
                     with torch.inference_mode():
-                        if plan_det and self.two_streams:
-                            fp = self._plan_of(det, pre[0])
-                            fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
-                        elif plan_det:
-                            self._plan_of(det, pre[0])             # sets the plan's branch mode for this runner's layout
+                        if runs_yolo_plan(det):
+                            fp = self._plan_of(det, pre[0], slot)  # sets the plan's branch mode for this runner's layout
+                            if self.two_streams:
+                                fp.use_output(gi if self.net_streams >= 2 else 2 * gi + par)
                         with ops.roctx(f"tick{k}:network"):
                             raws.append(det.stage_net(pre))
         with torch.cuda.stream(sa):
             if events: events[2].record()
             self._pending[par] = ("graph" if replay else "eager", plan, None if replay else raws, pres, motion,
                                   None if replay else events)
-            clips = dict(getattr(p, "_host_dets", {}))             # clips the temporal heads fired in THIS tick
+            clips = dict(p._host_dets)                             # clips the temporal heads fired in THIS tick
             if clips:
                 p._host_dets.clear()
             self._meta[par] = (packets, t0, clips)
@@ -714,7 +712,6 @@ class PipelinedTicks:
                 if not plan.groups:
                     self._k1_done[par].record(sa)
                 self._net_done[par].record(sa)
-        self._set_slot(0)
         if self.two_streams:
             if self.depth == 1:
                 self._issue_post(k, None)

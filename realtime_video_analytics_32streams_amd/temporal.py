@@ -191,7 +191,6 @@ class _HipTemporalDetector:
         self._ring: Dict[str, torch.Tensor] = {}
         self._free: Dict[str, List[int]] = {}
         # batched device path (stage_pre / stage_net / stage_post): one ring for all streams, [slots, columns, 3, H, W]
-        self._slot = 0                         # set by PipelinedTicks: tick parity -> which result buffers a tick uses
         self._col: Dict[str, int] = {}         # stream name -> ring column
         self._arrivals: Dict[str, int] = {}    # frames seen per stream (ring slot = arrivals % ring slots)
         self._bbuf: Dict[str, Deque] = {}      # per stream: (frame_id, ring slot, (h, w)) of the buffered frames
@@ -255,11 +254,7 @@ class _HipTemporalDetector:
     # -- batched device path: a whole tick of this head without a host round trip ----------------------------------------
     RING_EXTRA = 8        # ring slots beyond the clip buffer: up to eight ticks may be in flight (K1 of tick k+7 beside the network of k)
 
-    @staticmethod
-    def geometry_key(frame) -> tuple:
-        if isinstance(frame, ops.Nv12Surface):
-            return (int(frame.width), int(frame.height), "nv12")
-        return (int(frame.shape[1]), int(frame.shape[0]), "bgr")
+    geometry_key = staticmethod(ops.geometry_key)
 
     def reserve_streams(self, names: Sequence[str]) -> None:
         """Give every stream of the pipeline its ring column now (TickPipeline calls this once): the ring then never grows
@@ -286,7 +281,7 @@ class _HipTemporalDetector:
             self._bring = ring
         return [self._col[n] for n in names]
 
-    def stage_pre(self, packets: Sequence[FramePacket]) -> _ClipTick:
+    def stage_pre(self, packets: Sequence[FramePacket], slot: int = 0) -> _ClipTick:
         """K1 of the tick: every frame is pre-processed on arrival straight into its ring slot -- ONE launch when the
         streams of the group sit in adjacent columns and have seen the same number of frames (the steady state), one
         launch per stream otherwise -- and the clip schedule (host logic, temporal_detector.py:88-118) advances."""
@@ -312,9 +307,9 @@ class _HipTemporalDetector:
             if clip is not None:
                 fired.append((row, [c[1] for c in clip], clip[0][2]))
                 infos[n] = ClipInfo(clip[0][0], clip[-1][0], self.config.action_classes, min(5, self.config.num_action_classes))
-        if self.engine in CLIP_PLANS and self._slot not in self._plans:
-            self._plan_slot(self._slot, 0, len(packets))     # built on the slot's first tick, before any clip can fire
-        return _ClipTick(len(packets), fired, cols, infos, self._slot)
+        if self.engine in CLIP_PLANS and slot not in self._plans:
+            self._plan_slot(slot, 0, len(packets))     # built on the slot's first tick, before any clip can fire
+        return _ClipTick(len(packets), fired, cols, infos, slot)
 
     def stage_net(self, pre: _ClipTick) -> Optional[torch.Tensor]:
         """The clips that fired this tick as ONE network batch: ``[n_fired, classes]`` raw outputs (no softmax)."""

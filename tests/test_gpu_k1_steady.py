@@ -339,10 +339,10 @@ def test_detector_border_bookkeeping(seq, half, k1_flags):
     sc = StreamConfig(name="cam0", url="synthetic://1920x1080", warmup_seconds=0.0)
     for tick, (kind, (w, h), n, slot, content) in enumerate(SEQUENCES[seq]):
         frames, want = _tick_frames(kind, w, h, n, tick, half)
-        det._slot = slot
         before = len(k1_flags)
-        det.predict_batch_device([FramePacket(stream=sc, frame=f, frame_id=tick, timestamp=0.0) for f in frames])
-        det._slot = 0
+        with torch.inference_mode():                   # the three stages as the runner drives them, in the step's slot
+            pre = det.stage_pre([FramePacket(stream=sc, frame=f, frame_id=tick, timestamp=0.0) for f in frames], slot)
+            det.stage_post(det.stage_net(pre), pre)
         assert k1_flags[before:] == ([] if content is None else [content]), (seq, tick)
         assert len(head.seen) == tick + 1
         _same(_bits(head.seen[-1]), want, f"{seq} {'fp16' if half else 'fp32'} tick {tick} ({kind} {w}x{h} n={n} slot {slot})")

@@ -452,3 +452,82 @@ def test_gated_temporal_stream_keeps_its_gates_on_the_host():
         processed += 1 if "clip" in r.detections_emitted else 0
     arrivals = det._arrivals["clip"] - seen_before
     assert 0 < arrivals < 12 and det._arrivals["plain"] == 12              # the idle stream was throttled; skipped frames never reached its ring
+
+
+def _slot_rig(S=2):
+    """Two small NV12 streams on a ResNet head whose network is a stub (ten zero logits per frame): no network is built and no
+    plan tuned, every tick emits the same three full-frame detections per stream.  ``seen``: the ``slot`` of every ``stage_pre``."""
+    from realtime_video_analytics_32streams_amd.classify import HipResNetDetector
+    streams = [StreamConfig(name=f"cam{i}", url="synthetic://64x48", warmup_seconds=0.0) for i in range(S)]
+    srcs = [SyntheticNv12Stream(s, index=i, width=64, height=48, n_unique=2) for i, s in enumerate(streams)]
+    for s in srcs:
+        s.open_sync()
+    dcfg = DetectorConfig(model_path="resnet.onnx", backend="hip", model_type="resnet", confidence_threshold=-1.0, resnet_num_classes=10,
+                          resnet_top_k=3, input_size=[32, 32], warmup=False)
+    det = HipResNetDetector(dcfg, infer_fn=lambda x: torch.zeros((x.shape[0], 10), device=x.device))
+    seen, stage_pre = [], det.stage_pre
+
+    def spy(packets, *slot):                                       # passes on what it was given: the per-frame API gives no slot
+        seen.append(slot[0] if slot else 0)
+        return stage_pre(packets, *slot)
+    det.stage_pre = spy
+    trk = IouTracker(TrackerConfig(max_age=5, max_iou_distance=0.5, min_hits=1), max_streams=S, capacity=64)
+    return TickPipeline(streams, det, trk, sources=srcs), det, srcs, seen
+
+
+def _tabs(result):
+    return {n: _tab(t) for n, t in result.tracks.items()}          # now: the Track objects live on and change with later ticks
+
+
+def _run_pipelined(runner, ticks):
+    out = []
+    for _ in range(ticks):
+        if runner._next - runner._oldest == runner.depth:
+            out.append(_tabs(runner.collect_result()))
+        runner.submit()
+    while runner._oldest < runner._next:
+        out.append(_tabs(runner.collect_result()))
+    return out
+
+
+def test_the_runner_hands_every_tick_its_slot():
+    """``PipelinedTicks`` passes the detector slot of a tick to ``stage_pre``: the tick's parity with a chain per tick, slot 0 in the
+    one-network-stream layout and at depth 1.  The detector keeps buffers for exactly those slots, and the tables are ``tick()``'s."""
+    pipe, det, _, seen = _slot_rig()
+    got = _run_pipelined(PipelinedTicks(pipe, depth=3), 7)
+    assert seen == [0, 1, 2, 0, 1, 2, 0] and sorted(det._slots) == [0, 1, 2]
+    ref, ref_det, _, ref_seen = _slot_rig()
+    want = [_tabs(ref.tick()) for _ in range(7)]
+    assert ref_seen == [0] * 7 and sorted(ref_det._slots) == [0]
+    assert got == want and all(len(t) == 3 for t in want[-1].values())
+    for kw in (dict(depth=2, net_streams=1), dict(depth=1)):
+        pipe, det, _, seen = _slot_rig()
+        runner = PipelinedTicks(pipe, **kw)
+        assert runner.net_streams == 1
+        assert _run_pipelined(runner, 4) == want[:4]
+        assert seen == [0] * 4 and sorted(det._slots) == [0], kw
+
+
+def test_a_failed_submit_leaves_the_per_frame_api_in_slot_0():
+    """A ``submit()`` that raises half way (here the caller's ``before_k1`` hook, before tick 1's K1) must not leave the detector
+    in tick 1's slot: the per-frame API goes on using slot 0 -- no chain's buffers -- and the runner carries on."""
+    class Boom(Exception):
+        pass
+
+    def raiser():
+        raise Boom()
+    pipe, det, srcs, seen = _slot_rig()
+    runner = PipelinedTicks(pipe, depth=2)
+    assert runner.net_streams == 2
+    runner.submit()
+    runner.collect()
+    with pytest.raises(Boom):
+        runner.submit(before_k1=raiser)
+    before = sorted(det._slots)
+    packets = [src.next_packet() for src in srcs]
+    with torch.inference_mode():                                   # as the runner, whose result buffers of slot 0 the calls share
+        assert det.stage_pre(packets).slot == 0
+        det.predict_batch_device(packets)
+    assert sorted(det._slots) == before == [0]
+    k = runner.submit()
+    assert runner.collect()[0] == k == 1 and seen[-1] == 1 and sorted(det._slots) == [0, 1]
