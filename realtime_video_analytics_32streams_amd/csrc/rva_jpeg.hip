@@ -22,7 +22,9 @@
 // set: the ~4 300 restart intervals of 32 x 1080p fill the chip where one picture's 68 waves cannot (rva_jpeg_batch_*).
 // rva_jpeg_encode_bgr is a batch of one through the same kernels.  An image whose interval overflows its staging area, or that
 // the remaining capacity of `out` does not hold, reports -1, takes no bytes and leaves its neighbours intact.
-// Every stage is byte / integer work: bit-exact against the oracle (tests/test_gpu_api.py, tests/test_gpu_preview_batch.py).
+// Every stage is byte / integer work: bit-exact against the oracle (tests/test_gpu_api.py, tests/test_gpu_preview_batch.py on
+// smooth pictures; tests/test_gpu_jpeg_enc_craft.py on images crafted in the coefficient domain -- every AC symbol, every DC
+// category, 0xFF bytes at the edges of the stuffing steps and passes -- whose reach tests/test_jpeg_enc_craft_host.py measures).
 // Previews are rate-limited to 10 per second per stream (kafka_sink.py:49): at 30 fps all streams come due on the same tick.
 #include <cstring>
 
